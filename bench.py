@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the FIRA hot path on MI355X: training commits/s (+ greedy-decode tokens/s), BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16] [--dump-outputs DIR] [--full]
 
 A "step" is one optimisation step of run_model.py:101-112 (forward + backward + [RCCL all-reduce] + Adam) over one
 batch of synthetic commits in the reference's raw schema (there is no network for the real DataSet; seed-0 generator,
@@ -10,13 +10,18 @@ SURVEY.md §8d), with the reference's dropout (0.1 / 0.2) ON.  The default workl
 the bf16 MFMA with fp32 accumulation).  Every rank keeps its batch as N grows (weak scaling).  Inputs are resident in
 HBM before the timed region (pre-collated device batches, cycled).  One JSON line is printed by rank 0.
 
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`,
+`ms_per_step`, `dtype`, `config`, ...).  ``--dump-outputs DIR`` writes what the timed path computed by its last step as
+``DIR/<name>.npy`` (see ``dump_outputs``): the same arguments give the same inputs, so two builds compare output for output.
+``--full`` adds every other measurement below (profiled steps, side legs, decode, CPU baseline) and the detail file.
+
 ``--gpus N`` with N > 1: when the process was not started by torch.distributed.run (no WORLD_SIZE in the environment)
 bench.py re-launches itself under ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
 127.0.0.1`` (one process per GPU, RCCL) and passes the child's line through -- the reference's multi-GPU entry is one
 command too (run_model.py:392-394).  ``--dp-same-device`` puts every rank on cuda:0 with the gloo transport, which is
 how the N > 1 path is exercised on a one-GPU box (tests/test_dp_gpu.py).
 
-Extra objects on the line (all measured outside the timed region):
+Extra objects on the line with ``--full`` (all measured outside the timed region):
   b64 / b170    (default command only) the same step at batch 64 per GPU in fp32 AND bf16 (north_star's "at batch 64";
                 bf16 = BASELINE configs[2]'s per-GPU workload: `b64.bf16`, also `configs2` when N > 1), each with its
                 own `roofline`, `decoder_gemm` (FLOP / summed launch time of the decoder's M = B*30 products only) and
@@ -85,6 +90,11 @@ def parse_args():
                     "the two gradient buckets; auto = bf16 with --dtype bf16 (BASELINE configs[2]: 55.6 MB per step), else f32")
     ap.add_argument("--zero1", action="store_true", help="N > 1: reduce-scatter + sharded Adam + all-gather instead of "
                     "all-reduce + replicated Adam")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step "
+                    "computed (its loss) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: kernel-class "
+                    "profile, roofline objects, batch-64 / 170 and bf16 legs, stand-alone SpMM / GCN, host-inclusive, "
+                    "decode, CPU baseline, collective timings; writes the detail file")
     return ap.parse_args()
 
 
@@ -580,6 +590,23 @@ def lib_sha16():
         return None
 
 
+def dump_outputs(out_dir, model, trainer, rank):
+    """What the last timed step computed, as DIR/loss.npy (rank 0 writes): float64 [mean token loss, loss_sum, n_tok] of that
+    step's batch, global over ranks -- what Trainer.last_loss() gives its caller.  The parameters and Adam moments after the
+    timed steps are not written: they are not reproducible from run to run of one build (run-to-run
+    reproducibility: the backward's float-atomic sums differ in the last bits, and Adam turns last-bit differences of
+    near-zero gradients into steps of the size of the learning rate, which later ReLU ties amplify)."""
+    loss = trainer.last_loss()
+    if trainer.reducer is not None and trainer.reducer.world > 1:
+        loss_sum, n_tok = trainer.stats.tolist()
+    else:
+        loss_sum, n_tok = float(model.loss_sum.item()), float(model.n_tok.item())
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss, loss_sum, n_tok], dtype=np.float64))
+
+
 def box_fingerprint():
     """The pool's boxes fall into a slow and a fast class ~5 % apart on the training line; a device-to-device copy of 1 GiB
     (read + write, 20 repetitions) separates them the same way and costs 10 ms: GB/s of that copy, with the host name."""
@@ -744,7 +771,8 @@ def main():
 
     cfg = FiraConfig()
     B = a.batch or (64 if a.dtype == "bf16" else 32)
-    default_line = a.batch == 0 and a.dtype == "f32"      # the driver's command: carries the batch-64 / 170 objects too
+    default_line = a.batch == 0 and a.dtype == "f32"      # with --full the default command carries the batch-64 / 170 objects
+    # too; the store is sized for them with or without --full, so that the headline steps see the same commits either way
     want_legs = default_line and not a.no_extras
     n_commits = max(a.pool * B, a.decode_batch, 64, (a.pool * 64) if want_legs else 0, (2 * 170) if want_legs else 0)
     store = data.process_raw(cfg, synth.generate_dataset(n_commits, seed=1000 + rank))
@@ -885,8 +913,49 @@ def main():
     batches = make_batches(B, a.pool)
     nnz_mean = float(np.mean([b.nnz for b in batches]))
     dt, t_enq = timed_leg(batches, a.steps, a.warmup)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, trainer, rank)
     loss = trainer.last_loss()
     commits_per_s = a.steps * B * world / dt
+
+    def headline(box):
+        """The headline figure and what it was measured on: every line carries these keys."""
+        wl = ("BASELINE configs[1]: FIRA training step (fwd+bwd+Adam, dropout 0.1/0.2), batch %d commits/GPU, fp32"
+              if a.dtype == "f32" else
+              "BASELINE configs[2] per-GPU workload: FIRA training step (fwd+bwd+Adam, dropout 0.1/0.2), batch %d "
+              "commits/GPU, bf16 MFMA products with fp32 accumulation / storage / LayerNorm / loss / Adam")
+        return {
+            "metric": "training commits/sec (FIRA default config)", "value": commits_per_s, "unit": "commits/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
+            "host_enqueue_ms_per_step": t_enq / a.steps * 1e3,
+            "config": {"workload": (wl % B) + ", 650-node graphs (mean nnz %.0f/graph), vocab 24650" % (nnz_mean / B),
+                       "global_batch": B * world, "parallelism": "dp%d%s" % (world, "+zero1" if (a.zero1 and world > 1) else ""), "loss": loss,
+                       "lib_sha16": lib_sha16(), "box": box},
+        }
+
+    def process_group():
+        if world == 1:
+            return None
+        pg = {"rccl_world_size": torch.distributed.get_world_size(), "backend": torch.distributed.get_backend(),
+              "mode": "zero1 (reduce-scatter + sharded Adam + all-gather)" if a.zero1 else "all-reduce in 2 readiness buckets",
+              "gradient_bytes_per_rank": 4 * int(model.layout.live),
+              "fused_step": bool(getattr(trainer, "fused_dp", False)) and not a.zero1}
+        if trainer.reducer is not None and not a.zero1:
+            pg["wire"] = trainer.reducer.wire
+            pg["bytes_per_step"] = trainer.reducer.bytes_per_step()
+        return pg
+
+    if not a.full:                                     # the headline alone: everything below is --full
+        if rank == 0:
+            line = headline({"host": socket.gethostname()})
+            pg = process_group()
+            if pg:
+                line["process_group"] = pg
+            print(json.dumps(_sig(line)), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
 
     prof_steps = 3
     prof = profiled(batches, prof_steps)
@@ -979,38 +1048,20 @@ def main():
         trainer.reducer.timing = False
         barrier()
     if rank == 0:
-        pg = None
-        if world > 1:
-            pg = {"rccl_world_size": torch.distributed.get_world_size(), "backend": torch.distributed.get_backend(),
-                  "mode": "zero1 (reduce-scatter + sharded Adam + all-gather)" if a.zero1 else "all-reduce in 2 readiness buckets",
-                  "gradient_bytes_per_rank": 4 * int(model.layout.live),
-                  "fused_step": bool(getattr(trainer, "fused_dp", False)) and not a.zero1}
-            if trainer.reducer is not None and not a.zero1:
-                pg["wire"] = trainer.reducer.wire
-                pg["bytes_per_step"] = trainer.reducer.bytes_per_step()
-            if comm:
-                pg.update(comm)
-                pg["note"] = ("allreduce_ms_early = head+decoder bucket on the side stream from the mid-backward event "
-                              "(overlaps the encoder backward); allreduce_ms_late = encoder bucket, launch to ready on the "
-                              "caller's stream (overlaps Adam of the early slice); exposed_comm_ms = time the caller's "
-                              "stream stood waiting for the two buckets")
-        wl = ("BASELINE configs[1]: FIRA training step (fwd+bwd+Adam, dropout 0.1/0.2), batch %d commits/GPU, fp32"
-              if a.dtype == "f32" else
-              "BASELINE configs[2] per-GPU workload: FIRA training step (fwd+bwd+Adam, dropout 0.1/0.2), batch %d "
-              "commits/GPU, bf16 MFMA products with fp32 accumulation / storage / LayerNorm / loss / Adam")
-        line = {
-            "metric": "training commits/sec (FIRA default config)", "value": commits_per_s, "unit": "commits/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-            "host_enqueue_ms_per_step": t_enq / a.steps * 1e3,
-            "config": {"workload": (wl % B) + ", 650-node graphs (mean nnz %.0f/graph), vocab 24650" % (nnz_mean / B),
-                       "global_batch": B * world, "parallelism": "dp%d%s" % (world, "+zero1" if (a.zero1 and world > 1) else ""), "loss": loss,
-                       "lib_sha16": lib_sha16(), "box": box_fingerprint() if not a.no_extras else {"host": socket.gethostname()}},
+        pg = process_group()
+        if pg and comm:
+            pg.update(comm)
+            pg["note"] = ("allreduce_ms_early = head+decoder bucket on the side stream from the mid-backward event "
+                          "(overlaps the encoder backward); allreduce_ms_late = encoder bucket, launch to ready on the "
+                          "caller's stream (overlaps Adam of the early slice); exposed_comm_ms = time the caller's "
+                          "stream stood waiting for the two buckets")
+        line = headline(box_fingerprint() if not a.no_extras else {"host": socket.gethostname()})
+        line.update({
             "roofline": roofline, "decoder_gemm": decoder_gemm, "gcn": gcn_obj, "comb": comb_object(prof, prof_steps),
             "attention": attn_obj, "spmm": spmm_obj,
             "decode": decode, "cpu_baseline": cpu,
             "kernel_time_ms_per_step": {k: v["ms"] / prof_steps for k, v in prof.items()},
-        }
+        })
         if a.dtype == "bf16":
             line["roofline_hbm"] = roofline_hbm
         if pg:

@@ -9,7 +9,7 @@ DT=${1:-f32}
 OUT=$REPO/gpurun_out/pmc_traffic_$DT
 mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 170 rocprofv3 --pmc $c --output-format csv -d $OUT/$c -o t -- python $REPO/bench.py --dtype $DT --steps 2 --warmup 1 --no-decode --no-cpu-baseline --no-extras > $OUT/$c.log 2>&1
+  timeout 170 rocprofv3 --pmc $c --output-format csv -d $OUT/$c -o t -- python $REPO/bench.py --full --dtype $DT --steps 2 --warmup 1 --no-decode --no-cpu-baseline --no-extras > $OUT/$c.log 2>&1
   # keep only the counter table (the pass also writes large agent / kernel tables)
   find $OUT/$c -type f ! -name "*counter_collection.csv" -delete
 done

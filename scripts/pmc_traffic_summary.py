@@ -26,7 +26,7 @@ def main():
     import glob
     f = load(glob.glob(src + "/FETCH_SIZE/**/*counter_collection.csv", recursive=True)[0], "FETCH_SIZE")
     w = load(glob.glob(src + "/WRITE_SIZE/**/*counter_collection.csv", recursive=True)[0], "WRITE_SIZE")
-    note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, scripts/pmc_traffic.sh) over python bench.py --dtype <dtype> --steps 2 "
+    note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, scripts/pmc_traffic.sh) over python bench.py --full --dtype <dtype> --steps 2 "
             "--warmup 1 --no-decode --no-cpu-baseline --no-extras; FETCH_SIZE doubled (gfx950 reports half of wide coalesced reads; "
             "check: adam_kernel must read 4 x and write 3 x the 124 MB parameter buffer), WRITE_SIZE as reported")
     rows = []

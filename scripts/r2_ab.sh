@@ -8,7 +8,7 @@ cd $REPO
 for rep in 1 2; do
   for v in A B; do
     if [ $v = A ]; then E="$A"; else E="$B"; fi
-    env $E timeout 300 python bench.py --no-decode --no-cpu-baseline --no-extras --steps 40 "$@" > $OUT/${v}_$rep.json 2> $OUT/${v}_$rep.err
+    env $E timeout 300 python bench.py --full --no-decode --no-cpu-baseline --no-extras --steps 40 "$@" > $OUT/${v}_$rep.json 2> $OUT/${v}_$rep.err
     python - <<PY
 import json
 d=json.load(open("$OUT/${v}_$rep.json"))

@@ -33,13 +33,13 @@ for ST in "$@"; do
       timeout 1500 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider --timeout 300 > $OUT/tests.log 2>&1
       echo "tests rc=$?" >> $OUT/tests.log; tail -n 25 $OUT/tests.log ;;
     bench)
-      timeout 900 python bench.py > $OUT/bench_f32.json 2> $OUT/bench_f32.err; echo "bench f32 rc=$?"; head -c 1500 $OUT/bench_f32.json; echo; tail -n 5 $OUT/bench_f32.err ;;
+      timeout 900 python bench.py --full > $OUT/bench_f32.json 2> $OUT/bench_f32.err; echo "bench f32 rc=$?"; head -c 1500 $OUT/bench_f32.json; echo; tail -n 5 $OUT/bench_f32.err ;;
     bench16)
-      timeout 600 python bench.py --dtype bf16 > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "bench bf16 rc=$?"; head -c 600 $OUT/bench_bf16.json; echo ;;
+      timeout 600 python bench.py --full --dtype bf16 > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "bench bf16 rc=$?"; head -c 600 $OUT/bench_bf16.json; echo ;;
     prof|prof16)
       DT=f32; [ $ST = prof16 ] && DT=bf16
       cd /tmp; mkdir -p $OUT/prof_$DT
-      timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$DT -o step -- python $REPO/bench.py --dtype $DT --steps 10 --warmup 2 --no-decode --no-cpu-baseline --no-extras > $OUT/prof_$DT/bench.log 2>&1
+      timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$DT -o step -- python $REPO/bench.py --full --dtype $DT --steps 10 --warmup 2 --no-decode --no-cpu-baseline --no-extras > $OUT/prof_$DT/bench.log 2>&1
       python $REPO/scripts/rocpd_stats.py $(find $OUT/prof_$DT -name "*results.db" | head -1) 15 $OUT/timeline_$DT.md > $OUT/kernel_stats_$DT.md 2>&1
       find $OUT/prof_$DT -name "*.db" -delete
       cd $REPO; head -n 45 $OUT/kernel_stats_$DT.md ;;
@@ -58,12 +58,12 @@ for ST in "$@"; do
       for i in 1 2; do
         for V in "FIRA_COMPACT_DEC=0 FIRA_ENC_WGRAD_GROUP=0" "FIRA_COMPACT_DEC=0 FIRA_ENC_WGRAD_GROUP=1" "FIRA_COMPACT_DEC=1 FIRA_ENC_WGRAD_GROUP=1"; do
           for BS in 32 64; do
-            echo -n "$V batch $BS: "; env $V timeout 300 python bench.py --batch $BS --no-decode --no-cpu-baseline --no-extras --steps 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), 'commits/s', round(d['ms_per_step'],3), 'ms', 'host', round(d['host_enqueue_ms_per_step'],2))"
+            echo -n "$V batch $BS: "; env $V timeout 300 python bench.py --full --batch $BS --no-decode --no-cpu-baseline --no-extras --steps 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), 'commits/s', round(d['ms_per_step'],3), 'ms', 'host', round(d['host_enqueue_ms_per_step'],2))"
           done
         done
       done 2>&1 | tee $OUT/ab.txt ;;
     ab2)
-      one() { env $1 timeout 200 python bench.py $2 --no-decode --no-cpu-baseline --no-extras --steps 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_time_ms_per_step']; print(round(d['value']), 'commits/s', round(d['ms_per_step'],3), 'ms', 'attn', round(k['attention'],3), 'rowops', round(k['rowops'],3), 'head', round(k['head'],3))"; }
+      one() { env $1 timeout 200 python bench.py --full $2 --no-decode --no-cpu-baseline --no-extras --steps 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_time_ms_per_step']; print(round(d['value']), 'commits/s', round(d['ms_per_step'],3), 'ms', 'attn', round(k['attention'],3), 'rowops', round(k['rowops'],3), 'head', round(k['head'],3))"; }
       for i in 1 2; do
         for V in "FIRA_KV_PAD=0 FIRA_HEAD_FAST=0" "FIRA_KV_PAD=64 FIRA_HEAD_FAST=0" "FIRA_KV_PAD=64 FIRA_HEAD_FAST=1"; do
           echo -n "$V f32 b32: "; one "$V" "--batch 32"
@@ -72,7 +72,7 @@ for ST in "$@"; do
       done 2>&1 | tee $OUT/ab2.txt
       for V in "FIRA_KV_PAD=0" "FIRA_KV_PAD=64"; do echo -n "$V decode: "; env $V timeout 200 python scripts/decode_only.py 2>/dev/null | tail -n 2 | tr "\n" ";"; echo; done 2>&1 | tee -a $OUT/ab2.txt ;;
     ab3)   # two BUILDS on one box: fira_icse_amd/libfira_hip_prev.so (built from the previous commit) vs the tree's library
-      one() { env $1 timeout 200 python bench.py $2 --no-decode --no-cpu-baseline --no-extras --steps 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_time_ms_per_step']; print(round(d['value']), 'commits/s', round(d['ms_per_step'],3), 'ms', 'host', round(d['host_enqueue_ms_per_step'],2))"; }
+      one() { env $1 timeout 200 python bench.py --full $2 --no-decode --no-cpu-baseline --no-extras --steps 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_time_ms_per_step']; print(round(d['value']), 'commits/s', round(d['ms_per_step'],3), 'ms', 'host', round(d['host_enqueue_ms_per_step'],2))"; }
       for i in 1 2 3; do
         for V in "FIRA_HIP_LIB=$REPO/fira_icse_amd/libfira_hip_prev.so" "FIRA_X=1"; do
           echo -n "${V##*/} f32 b32: "; one "$V" "--batch 32"

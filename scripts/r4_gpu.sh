@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $REPO
 export TMPDIR=/tmp
 PREV=$REPO/fira_icse_amd/libfira_hip_prev.so
-one() { env $1 timeout 500 python bench.py $2 --no-decode --no-cpu-baseline --no-extras --steps 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_time_ms_per_step']; print(round(d['value']), 'commits/s', round(d['ms_per_step'],3), 'ms', 'attn', round(k['attention'],3), 'gemm', round(k['gemm'],3), 'rowops', round(k['rowops'],3), 'spmm', round(k['spmm'],3), 'host', round(d['host_enqueue_ms_per_step'],2))"; }
+one() { env $1 timeout 500 python bench.py --full $2 --no-decode --no-cpu-baseline --no-extras --steps 40 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_time_ms_per_step']; print(round(d['value']), 'commits/s', round(d['ms_per_step'],3), 'ms', 'attn', round(k['attention'],3), 'gemm', round(k['gemm'],3), 'rowops', round(k['rowops'],3), 'spmm', round(k['spmm'],3), 'host', round(d['host_enqueue_ms_per_step'],2))"; }
 for ST in "$@"; do
   case $ST in
     newtests)
@@ -83,17 +83,17 @@ for ST in "$@"; do
     adopt)   # make this session's counters / traces the ones bench.py quotes (profiles/traffic.json, r4_kernel_classes.json)
       cp $OUT/traffic.json $REPO/profiles/traffic.json; cp $OUT/kernel_classes.json $REPO/profiles/r4_kernel_classes.json; echo adopted ;;
     bench)
-      timeout 900 python bench.py > $OUT/bench_f32.json 2> $OUT/bench_f32.err; echo "bench f32 rc=$?"; head -c 1500 $OUT/bench_f32.json; echo; tail -n 5 $OUT/bench_f32.err ;;
+      timeout 900 python bench.py --full > $OUT/bench_f32.json 2> $OUT/bench_f32.err; echo "bench f32 rc=$?"; head -c 1500 $OUT/bench_f32.json; echo; tail -n 5 $OUT/bench_f32.err ;;
     bench16)
-      timeout 600 python bench.py --dtype bf16 > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "bench bf16 rc=$?"; head -c 600 $OUT/bench_bf16.json; echo ;;
+      timeout 600 python bench.py --full --dtype bf16 > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "bench bf16 rc=$?"; head -c 600 $OUT/bench_bf16.json; echo ;;
     prof|prof16)
       DT=f32; [ $ST = prof16 ] && DT=bf16
       cd /tmp; mkdir -p $OUT/prof_$DT
-      timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$DT -o step -- python $REPO/bench.py --dtype $DT --steps 10 --warmup 2 --no-decode --no-cpu-baseline --no-extras > $OUT/prof_$DT/bench.log 2>&1
+      timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$DT -o step -- python $REPO/bench.py --full --dtype $DT --steps 10 --warmup 2 --no-decode --no-cpu-baseline --no-extras > $OUT/prof_$DT/bench.log 2>&1
       VAL=$(grep -o '"value": [0-9.]*' $OUT/prof_$DT/bench.log | head -1 | cut -d' ' -f2)
       BS=32; [ $DT = bf16 ] && BS=64
       ROCPD_CLASSES_JSON=$OUT/kernel_classes.json ROCPD_DTYPE=$DT ROCPD_BATCH=$BS ROCPD_COMMIT=${R4_COMMIT:-unknown} ROCPD_VALUE=$VAL \
-        ROCPD_SOURCE="rocprofv3 --kernel-trace --stats -- python bench.py --dtype $DT --steps 10 --warmup 2 --no-decode --no-cpu-baseline --no-extras (15 steps in the trace; under the profiler)" \
+        ROCPD_SOURCE="rocprofv3 --kernel-trace --stats -- python bench.py --full --dtype $DT --steps 10 --warmup 2 --no-decode --no-cpu-baseline --no-extras (15 steps in the trace; under the profiler)" \
         python $REPO/scripts/rocpd_stats.py $(find $OUT/prof_$DT -name "*results.db" | head -1) 15 $OUT/timeline_$DT.md > $OUT/kernel_stats_$DT.md 2>&1
       find $OUT/prof_$DT -name "*.db" -delete
       cd $REPO; head -n 60 $OUT/kernel_stats_$DT.md ;;

@@ -46,6 +46,20 @@ def test_stdout_line_is_short_and_keeps_the_contract_keys():
     assert line["detail"].endswith(".json")
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    b = _bench()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = b.parse_args()
+        assert a.steps == 7 and a.warmup == 2 and not a.full and not a.dump_outputs
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = b.parse_args()
+        assert a.full and a.dump_outputs == "out"
+    finally:
+        sys.argv = argv
+
+
 def test_non_finite_numbers_never_reach_the_line():
     b = _bench()
     assert b._sig({"a": float("nan"), "b": [float("inf"), 1.23456789]}) == {"a": None, "b": [None, 1.23457]}

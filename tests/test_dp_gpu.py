@@ -161,8 +161,8 @@ def test_bench_two_gpus_over_rccl():
     """`python bench.py --gpus 2` with one rank per device: the line must say backend nccl and carry the collective timings."""
     import json
     import subprocess
-    cmd = [sys.executable, os.path.join(util.REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-decode",
-           "--no-cpu-baseline", "--no-extras"]
+    cmd = [sys.executable, os.path.join(util.REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--no-decode", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -175,7 +175,7 @@ def test_bench_self_launches_under_torchrun():
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(util.REPO, "bench.py"), "--gpus", "2", "--dp-same-device", "--steps", "3",
-           "--warmup", "1", "--no-decode", "--no-cpu-baseline", "--no-extras"]
+           "--warmup", "1", "--full", "--no-decode", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

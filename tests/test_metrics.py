@@ -1,5 +1,6 @@
-"""B-Norm / Penalty BLEU against the numbers the reference's own scorers give on its shipped OUTPUT/ files, and
-sentence BLEU (NLTK method 2) against hand-computed cases."""
+"""B-Norm / Penalty BLEU against the numbers the reference's own scorers give on its shipped OUTPUT/ files (stored
+gzipped under tests/golden/scorer_outputs/), and sentence BLEU (NLTK method 2) against hand-computed cases."""
+import gzip
 import math
 import os
 
@@ -9,17 +10,18 @@ import util
 from fira_icse_amd import metrics
 
 
-@pytest.mark.skipif(not util.has_reference(), reason="reference OUTPUT/ files not present (GPU box)")
+def _output_file(name):
+    with gzip.open(os.path.join(util.GOLDEN, "scorer_outputs", name + ".gz"), "rt", encoding="utf-8") as f:
+        return f.read()
+
+
 @pytest.mark.parametrize("name,bnorm,penalty", [
     ("output_fira", 17.666052790472175, 0.13298690691792042),      # SURVEY.md Appendix C.4 (paper: 17.67 / 13.30)
     ("output_nngen", 9.16, None), ("output_codisum", 16.55, None),
 ])
 def test_scores_reproduce_reference_scorers(name, bnorm, penalty):
-    ref = open(os.path.join(util.REFERENCE, "OUTPUT", "ground_truth")).read().split("\n")
-    path = os.path.join(util.REFERENCE, "OUTPUT", name)
-    if not os.path.exists(path):
-        pytest.skip("no %s" % name)
-    hyp = open(path).read().split("\n")
+    ref = _output_file("ground_truth").split("\n")
+    hyp = _output_file(name).split("\n")
     if hyp and hyp[-1] == "":
         hyp = hyp[:-1]
     b = metrics.bnorm_bleu(ref, hyp)

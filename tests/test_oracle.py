@@ -1,8 +1,7 @@
-"""Pin the CPU oracle (oracle/fira_oracle.py) to the outputs of the reference itself (tests/golden/*, generated by
-tests/golden/make_golden.py from /root/reference), and to the live reference when its tree is present."""
+"""Pin the CPU oracle (oracle/fira_oracle.py) to the outputs of the reference itself (tests/golden/*, generated from the
+reference tree by tests/golden/make_golden*.py)."""
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -59,14 +58,24 @@ def test_forward_backward_adam_match_reference_golden(ctx):
         opt.zero_grad(set_to_none=True)
         (ls / nt).backward()
         if it == 0:
+            # fc_k.bias of every attention and copy_net.LinearRes.bias have a mathematically ZERO gradient (a bias shared by
+            # all scores of one soft-max cancels): the reference's norms there are rounding noise (3e-10 .. 7e-9, the next
+            # smallest is 1.3e-3), which depends on the host's summation order, so both sides must be zero to rounding
+            zero = 1e-7 * float(g["grad_norm"].max())
             for n, ref in zip(names, g["grad_norm"]):
                 if ref < 0:
                     assert P[n].grad is None, n
+                elif ref <= zero:
+                    assert float(P[n].grad.double().norm()) <= zero, n
                 else:
                     assert abs(float(P[n].grad.double().norm()) - ref) <= 1e-5 * ref + 1e-12, n
             for n in util.GRAD_SAMPLE_KEYS:
                 t = P[n].grad.reshape(-1)
-                assert np.allclose(t[:: max(1, t.numel() // 64)][:64].numpy(), g["gs:" + n], rtol=1e-4, atol=1e-9), n
+                # absolute term on the tensor's scale: an entry that cancels to ~1e-4 of it (5.5e-7 in a bias of 4e-3)
+                # keeps the fp32 rounding of its summands, which differs with the host's BLAS / vector kernels
+                ref = g["gs:" + n]
+                assert np.allclose(t[:: max(1, t.numel() // 64)][:64].numpy(), ref, rtol=1e-4,
+                                   atol=max(1e-9, 1e-5 * float(np.abs(ref).max()))), n
         opt.step()
         curve.append((ls / nt).item())
     ls, nt = O.forward(P, *args, "train")
@@ -88,33 +97,25 @@ def test_decode_matches_reference_golden(ctx, beam):
 
 
 def test_init_and_position_table_match_live_reference(ctx):
-    if not util.has_reference():
-        pytest.skip("reference tree not present (GPU box)")
+    """Initialisation, position table and an eval-mode forward against what the live reference gave
+    (tests/golden/make_golden_init.py -> init_ref.json): every tensor bit-identical (SHA-256 of its bytes)."""
+    import hashlib
     cfg, raw, store, idx, base = ctx
-    sys.path.insert(0, util.REFERENCE)
-    from Model import TransModel
-    import gnn_transformer
-
-    class A(dict):
-        __getattr__ = dict.__getitem__
-    args = A(sou_len=cfg.sou_len, tar_len=cfg.tar_len, att_len=cfg.att_len, ast_change_len=cfg.ast_change_len,
-             sub_token_len=cfg.sub_token_len, dropout_rate=cfg.dropout_rate, num_head=cfg.num_head,
-             embedding_dim=cfg.embedding_dim, vocab_size=cfg.vocab_size, ast_change_vocab_size=cfg.ast_change_vocab_size)
-    torch.manual_seed(0)
-    ref = TransModel(args)
-    rsd = ref.state_dict()
-    assert list(rsd.keys()) == list(base.keys())
-    for k in rsd:
-        assert torch.equal(rsd[k], base[k]), k                      # bit-identical initialisation
-    assert torch.equal(gnn_transformer.position_encoding(210, 256), O.position_table(210, 256))
+    with open(os.path.join(util.GOLDEN, "init_ref.json")) as f:
+        gold = json.load(f)
+    sha = lambda t: hashlib.sha256(np.ascontiguousarray(t.detach().cpu().numpy()).tobytes()).hexdigest()
+    assert list(base.keys()) == gold["keys"]
+    for k in base:                                                   # bit-identical initialisation
+        assert list(base[k].shape) == gold["shapes"][k] and str(base[k].dtype) == gold["dtypes"][k], k
+        assert sha(base[k]) == gold["sha256"][k], k
+    pos = O.position_table(210, 256)
+    assert str(pos.dtype) == gold["position_table_dtype"] and sha(pos) == gold["position_table_sha256"]
     # live forward on a different batch than the golden one
     hb, tb = batch_of(store, cfg, idx["valid"][:3])
-    ref.eval()
     with torch.no_grad():
-        ls_ref, nt_ref = ref(tb["sou"], tb["tar"], None, tb["mark"], tb["ast_change"], tb["edge"], tb["tar_label"],
-                             tb["sub_token"], "train")
         ls, nt = O.forward(base, cfg, tb["sou"], tb["tar"], tb["mark"], tb["ast_change"], tb["edge"], tb["tar_label"],
                            tb["sub_token"], "train")
+    ls_ref, nt_ref = gold["forward_valid3"]["loss_sum"], gold["forward_valid3"]["n_tok"]
     assert int(nt) == int(nt_ref) and abs(float(ls) - float(ls_ref)) <= 1e-6 * float(ls_ref)
 
 

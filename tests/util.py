@@ -12,7 +12,6 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, "golden")
-REFERENCE = "/root/reference"
 for p in (REPO,):
     if p not in sys.path:
         sys.path.insert(0, p)
@@ -38,10 +37,6 @@ GRAD_SAMPLE_KEYS = [
     "decoder.feed_forward_list.5.fc1.weight", "out_fc.weight", "out_fc.bias",
     "copy_net.LinearSource.weight", "copy_net.LinearRes.weight", "copy_net.LinearProb.bias",
 ]
-
-
-def has_reference() -> bool:
-    return os.path.isdir(REFERENCE) and os.path.exists(os.path.join(REFERENCE, "Model.py"))
 
 
 def perturb_state_dict(sd: dict, seed: int = 1) -> dict:
