@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# FIRA_HIP_LIB: load another build of the same ABI instead (A/B timing of two builds on one GPU box)
+# FIRA_HIP_LIB: load another build of the same ABI (version 10) instead (A/B timing of two builds on one GPU box)
 LIB_PATH = os.environ.get("FIRA_HIP_LIB") or os.path.join(HERE, "libfira_hip.so")
 
 
@@ -164,35 +164,16 @@ def load():
             "fira_icse_amd: %s is missing and could not be built (%s). Build it with `python -m fira_icse_amd.build` "
             "(needs hipcc, gfx950). There is no CPU fallback." % (LIB_PATH, e))
     lib = C.CDLL(LIB_PATH)
-    foreign = bool(os.environ.get("FIRA_HIP_LIB"))
+    if lib.fira_abi_version() != 10:
+        raise ImportError("libfira_hip.so ABI version mismatch")
     for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)      # AttributeError if the library does not export a declared symbol
-        except AttributeError:
-            if foreign:                  # an older build loaded for A/B timing: its missing op-level entries are never called
-                continue
-            raise
+        fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
-    # FIRA_HIP_LIB (A/B timing of an older build through the model-level entry points, whose signatures did not change
-    # between v5 and v8 -- v8 appended a field to fira_batch, which older builds never read; callers ask has_symbol() before
-    # using an entry an older build lacks) may load an older library; the tree's own library must be v8
-    ok = (10,) if not os.environ.get("FIRA_HIP_LIB") else (5, 6, 7, 8, 9, 10)
-    if lib.fira_abi_version() not in ok:
-        raise ImportError("libfira_hip.so ABI version mismatch")
     return lib
 
 
 _lib = None
-
-
-def has_symbol(name: str) -> bool:
-    """True if the loaded library exports ``name`` (an older build loaded through FIRA_HIP_LIB may not)."""
-    try:
-        getattr(lib(), name)
-        return True
-    except AttributeError:
-        return False
 
 
 def lib():

@@ -417,12 +417,12 @@ __global__ __launch_bounds__(CF_WAVES * 64) void linear_x3_kernel(const LinearX3
 // (batch 32: 271 tiles on 256 workgroups) a d-memory pair moved 256 x 1.5 MB through L2 and was no faster than the fp32 GEMM it
 // replaced; on 136 workgroups of two tiles it is (+1.6 % of the step), and at batch 64 (507 tiles) 128 workgroups of four tiles
 // beat 256 of two (+1.1 % against +-0; profiles/r6_probes.md).  The launches run beside the decoder's chain: the CUs they
-// leave alone are not idle.  FIRA_LINX3_MAX_WGS (default 136).
+// leave alone are not idle.
 static int linear_x3_grid(int M) {
-    static const int cap = [] { const char* e = getenv("FIRA_LINX3_MAX_WGS"); const int v = e ? atoi(e) : 136; return std::max(8, std::min(CF_GRID, v / 8 * 8)); }();
+    constexpr int max_wgs = 136;                    // (a multiple of 8, at most CF_GRID)
     const int n_tiles = cdiv(M, CF_TILE);
     const int g = (cdiv(n_tiles, CF_TMAX) + 7) / 8 * 8;
-    return std::max(8, std::min(cap, g));
+    return std::max(8, std::min(max_wgs, g));
 }
 // The data-gradient shape of the same: out [M, 256] (+)= A [M, nkb * 256] B, B given as the planes of its nkb TRANSPOSED
 // [256, 256] row blocks (Bt_kb[n][k] = B[256 kb + k][n]: for a weight stored [N, 256] with out = dY W, the k-major copy of its
@@ -987,11 +987,10 @@ int comb_fused_bwd(hipStream_t s, int n_rows, float* dG, const int32_t* rows, co
     if (attr) return attr;
     if (WTx) {                           // bf16 planes (WTx: planes of Wq^T | Wk^T | Wo^T): three terms in fp32 mode, one in bf16 mode
         a.Wo = reinterpret_cast<const float*>(WTx);
-        // FIRA_COMB_BWD_TILES=1|2 forces the tiles per pass (A/B switch); default: two once some workgroup has more than one tile
-        static const int tm_env = [] { const char* e = getenv("FIRA_COMB_BWD_TILES"); return e ? atoi(e) : 0; }();
+        // two tiles per pass once some workgroup has more than one tile (every pass streams 1.15 MB of weight planes through
+        // the CU): +1.1 % at fp32 batch 64, +0.9 % in bf16 at batch 64 (profiles/r6_probes.md)
         const int n_tiles = (n_rows + CF_TILE - 1) / CF_TILE;
-        const bool two = tm_env == 2 || (tm_env != 1 && n_tiles > CF_GRID);
-        if (two) {
+        if (n_tiles > CF_GRID) {
             if (bf16) hipLaunchKernelGGL((comb_fused_bwd_kernel<false, 1, 2>), dim3(CF_GRID), dim3(CF_WAVES * 64), CB_LDS_X3_2, s, a);
             else hipLaunchKernelGGL((comb_fused_bwd_kernel<false, 3, 2>), dim3(CF_GRID), dim3(CF_WAVES * 64), CB_LDS_X3_2, s, a);
         } else

@@ -45,7 +45,6 @@ void gemm_bf16_group_reset();
 bool gemm_bf16_group_full();     // the next add would launch the queue by itself: the caller forks + flushes first
 // weight gradients as 256 x 256 panel products on the bf16 matrix cores (gemm_wgrad_panel.hip): C[M,N] += A^T B with A [K, lda],
 // B [K, ldb]; np = 1 (operands rounded to bf16) or 3 (three-term split: fp32-accurate).  A queue like the grouped launches.
-bool gemm_wgrad_panel_on();
 bool gemm_wgrad_panel_takes(int M, int N, int K, const float* A, int lda, const float* B, int ldb, int ldc);
 void gemm_wgrad_panel_reset();
 bool gemm_wgrad_panel_full();

@@ -54,15 +54,12 @@ struct DecGrad {
 // Row pitch of the cross-attention K|V rows (kv_all / dkv_all: [computed memory rows, 6 * 512] fp32).  The attention kernels read
 // ONE 128-byte head slice per key row; at the natural pitch of 12 288 bytes = 48 x 256 the slices of a whole launch land
 // on 8 of the 128 memory channels (gcd(48, 128) = 16).  Padding the row by 64 floats makes the pitch 49 x 256 bytes: every
-// channel in turn.  FIRA_KV_PAD overrides the pad (floats, multiple of 4; 0 = the natural pitch) for A/B runs.
-static int kv_row_pad() {
-    static const int pad = [] { const char* e = getenv("FIRA_KV_PAD"); const int v = e ? atoi(e) : 64; return v < 0 ? 0 : (v + 3) / 4 * 4; }();
-    return pad;
-}
+// channel in turn (floats, a multiple of 4).
+static constexpr int KV_ROW_PAD = 64;
 
 struct Plan {
     int B, NB, CB, MB, TB, N, L, S, A, T, V, ldl, nl, F;
-    int kvp;                        // row pitch (floats) of kv_all / dkv_all: nl * 512 + kv_row_pad()
+    int kvp;                        // row pitch (floats) of kv_all / dkv_all: nl * 512 + KV_ROW_PAD
     float *pos_code, *pos_tar;
     int32_t *mem_valid, *tar_valid, *compact_row, *iota, *code_slot, *mem_slot, *row_bt, *rows_c;
     int32_t *mem_off, *mem_valid_c;      // ragged cross-attention keys: commit b's computed memory rows, their key mask
@@ -150,7 +147,7 @@ struct Plan {
         mem_c = a.f((size_t)MB * D);
         src_c = a.f((size_t)MB * D);
         x0 = a.f((size_t)TB * D);
-        kvp = nl * 2 * D + kv_row_pad();
+        kvp = nl * 2 * D + KV_ROW_PAD;
         kv_all = a.f((size_t)MB * kvp);
         dec.resize(nl);
         for (int l = 0; l < nl; ++l) {
@@ -285,8 +282,7 @@ struct ShadowScope {            // publishes / withdraws the shadows of the runn
 };
 // shadow of the weight (or contiguous row slice of a weight) starting at W: as stored, or transposed (+ its row pitch)
 static bool shadow_of(const float* W, bool transposed, const uint16_t** out, int* ld) {
-    static const bool off_switch = [] { const char* e = getenv("FIRA_NO_SHADOW"); return e && e[0] == '1'; }();   // A/B
-    if (off_switch || !g_Wb || !g_tab) return false;
+    if (!g_Wb || !g_tab) return false;
     if (g_W21b && W >= g_W21 && W < g_W21 + g_W21n) {           // a folded GCN weight: uniform [256,256] blocks
         const int64_t off = W - g_W21;
         if (off % (FIRA_D * FIRA_D)) return false;
@@ -330,8 +326,8 @@ static inline int linear(hipStream_t s, int M, int N, int K, const float* X, int
 }
 // y = LN(dropout(X W^T + b [+ r c^T]) + res): the closing step of every block.  By default the product followed by the row
 // kernel; one fused launch where that was measured to win -- bf16 mode, K = 256, encoder-sized blocks (the panel kernel's
-// LayerNorm epilogue, gemm_bf16_panel.hip; FIRA_FUSED_LN_BF16).  (The fp32 "workgroup owns complete rows" kernels of round 2
-// lost in the step and are gone; the decoder's blocks are split at their LayerNorm instead: linear_presum below.)
+// LayerNorm epilogue, gemm_bf16_panel.hip).  (The fp32 "workgroup owns complete rows" kernels of round 2 lost in the step
+// and are gone; the decoder's blocks are split at their LayerNorm instead: linear_presum below.)
 static inline int linear_ln(hipStream_t s, int M, int K, const float* X, int ldx, const float* W, const float* b,
                             const float* res, const float* gamma, const float* beta, float* sum, float* y, float* stats,
                             float p_drop, uint64_t seed, uint32_t st, const int32_t* y_rows = nullptr,
@@ -361,14 +357,10 @@ static inline int linear_ln(hipStream_t s, int M, int K, const float* X, int ldx
 // pre-norm sum  sum = dropout(X W^T + b) + res  (EpiRes epilogue) and the next product normalises its A rows itself
 // (gemm_tile32_ln_try) -- one launch less per block on the dependent chain.  Both return false when the shape is not
 // taken; the caller then runs linear_ln / linear.
-static bool presum_on() {
-    static const bool off = [] { const char* e = getenv("FIRA_LN_PROLOGUE"); return e && e[0] == '0'; }();     // A/B switch
-    return !off && g_dtype == 0;
-}
 static inline bool linear_presum(hipStream_t s, int M, int K, const float* X, int ldx, const float* W, const float* b,
                                  const float* res, float* sum, float p_drop, uint64_t seed, uint32_t st, int* rc,
                                  uint32_t idx0 = 0) {
-    if (!presum_on() || !gemm_tile32_takes(1, M, FIRA_D, K, X, ldx, W, K)) return false;
+    if (g_dtype != 0 || !gemm_tile32_takes(1, M, FIRA_D, K, X, ldx, W, K)) return false;
     EpiRes er;
     er.res = res; er.ldr = FIRA_D; er.p = p_drop; er.inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
     er.seed = seed; er.site = st; er.idx0 = idx0;
@@ -391,13 +383,10 @@ struct SideStream {
     std::vector<hipEvent_t> events;
     size_t next = 0;
     bool enabled = true;
-    bool wide = true;            // FIRA_SIDE_WGRAD_ONLY=1: only the weight gradients use the side stream (A/B switch)
     int init() {
         if (stream) return 0;
         const char* off = getenv("FIRA_NO_WGRAD_OVERLAP");
         enabled = !(off && off[0] == '1');
-        const char* narrow = getenv("FIRA_SIDE_WGRAD_ONLY");
-        wide = !(narrow && narrow[0] == '1');
         // weight gradients: LOWEST priority -- nothing waits for them before the end of the step (or the mid-event), and
         // the big ones (the vocabulary projection: 138 MB of dlogits at batch 64) otherwise take the CUs from the
         // dependent chain on the caller's stream exactly when it has only small kernels to offer
@@ -486,7 +475,7 @@ static int side_join(hipStream_t main_s, int line = 0) {
     return 0;
 }
 
-static inline bool side_on() { SideStream& sd = side(); return sd.stream && sd.enabled && sd.wide; }
+static inline bool side_on() { SideStream& sd = side(); return sd.stream && sd.enabled; }
 // the auxiliary stream waits for everything enqueued on `main` so far
 static int aux_fork(hipStream_t main_s) {
     SideStream& sd = side();
@@ -512,18 +501,14 @@ static int main_wait(hipStream_t main_s, hipEvent_t e, int line = 0) {
 // dY and X must stay untouched until the next side_join (per-layer slots of Plan::encg / decg, saved activations).
 // (round 6) Weight gradients as panel products on the bf16 matrix cores (gemm_wgrad_panel.hip: 256 x 256 output tiles, every
 // operand row read once, no atomics; fp32 mode = three-term bf16 split, fp32-accurate) where the shape allows: dW [N,K] with
-// K (the layer's input width) a multiple of 256 and N >= 32.  FIRA_WGRAD_PANEL=0 restores the tiled kernels everywhere;
-// FIRA_WGRAD_PANEL_MASK selects the classes (1 encoder groups, 2 decoder / head groups, 4 vocabulary, 8 stacked K|V).
+// K (the layer's input width) a multiple of 256 and N >= 32, by class (1 encoder groups, 2 decoder / head groups, 4 vocabulary,
+// 8 stacked K|V).
 enum { PANEL_ENC = 1, PANEL_DEC = 2, PANEL_VOCAB = 4, PANEL_KV = 8 };
 // (measured, profiles/r6_probes.md: fp32 -- every class wins, mask 15; bf16 -- the decoder / head groups (K = the ~1 000 computed
 //  target rows) lose to the tiled grouped kernel, whose single-rounding MFMAs are already short: mask 13)
-static inline bool panel_class(int cls) {
-    static const int forced = [] { const char* e = getenv("FIRA_WGRAD_PANEL_MASK"); return e ? atoi(e) : -1; }();
-    const int mask = forced >= 0 ? forced : (g_dtype == 1 ? 13 : 15);
-    return gemm_wgrad_panel_on() && (mask & cls);
-}
 static inline bool panel_takes(int cls, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx) {
-    return panel_class(cls) && gemm_wgrad_panel_takes(N, K, M, dY, lddy, X, ldx, K);
+    const int mask = g_dtype == 1 ? 13 : 15;
+    return (mask & cls) && gemm_wgrad_panel_takes(N, K, M, dY, lddy, X, ldx, K);
 }
 static inline int panel_np() { return g_dtype == 1 ? 1 : 3; }
 
@@ -565,7 +550,8 @@ static inline int linear_wgrad_grouped(hipStream_t s, int M, int N, int K, const
 // One encoder layer's three weight gradients (folded GCN weight, Combination output and q|k projections): queued while
 // the layer's data-gradient chain runs, then issued as ONE grouped launch behind ONE fork (enc_wgrads_flush) -- every fork
 // is an event record on the caller's stream, i.e. a barrier packet in the dependent chain (scripts/event_cost.py: ~4-5 us
-// each), and the layer used to pay four of them.  FIRA_ENC_WGRAD_GROUP=0: one fork + launch per gradient (A/B switch).
+// each), and the layer used to pay four of them.  FIRA_ENC_WGRAD_GROUP=0: one fork + launch per gradient
+// (schedule switch: tests/test_model_gpu.py checks its gradients).
 static inline bool enc_group_on() {
     static const bool off = [] { const char* e = getenv("FIRA_ENC_WGRAD_GROUP"); return e && e[0] == '0'; }();
     SideStream& sd = side();
@@ -631,7 +617,8 @@ static int ln_bwd(hipStream_t s, int M, const float* dy, const float* sum, const
                   const float* row_w = nullptr, float* dsum = nullptr, float* dwsum = nullptr, bool* extras = nullptr,
                   uint32_t idx0 = 0) {
     const int nb = add_layernorm_bwd_blocks(M);
-    static const bool no_extra = [] { const char* e = getenv("FIRA_LN_BWD_EXTRA"); return e && e[0] == '0'; }();   // A/B switch
+    // FIRA_LN_BWD_EXTRA=0: the GCN blocks' extra column sums in a separate launch (schedule switch: tests/test_model_gpu.py)
+    static const bool no_extra = [] { const char* e = getenv("FIRA_LN_BWD_EXTRA"); return e && e[0] == '0'; }();
     const bool want = row_w && dsum && dwsum && !no_extra;
     float* part = want ? red().alloc((size_t)nb * 4 * FIRA_D) : nullptr;
     const bool ex = part != nullptr;
@@ -659,7 +646,7 @@ static int ln_bwd_dgrad(hipStream_t s, int M, int N, const float* dy, const floa
                         const float* W, int ldw, float* dX, int lddx, const float* relu_mask, uint32_t idx0 = 0) {
     // Up to ~1 500 rows (batch 64): beyond, the prologue repeated in each of the N / 32 column tiles of a row block is no longer
     // hidden by idle CUs (batch 170, 2 700 rows: 20 177 -> 20 567 commits/s without it; batch 64 neutral, batch 32 +0.5 % with it)
-    static const int lnb_max_rows = [] { const char* e = getenv("FIRA_LN_BWD_MAX_ROWS"); return e ? atoi(e) : 1536; }();
+    constexpr int lnb_max_rows = 1536;
     if (g_dtype == 0 && M <= lnb_max_rows && ds != dy && gemm_tile32_takes(0, M, N, FIRA_D, dy, FIRA_D, W, ldw)) {
         const int nb = gemm_tile32_lnb_blocks(M);
         float* part = red().alloc((size_t)nb * 2 * FIRA_D);
@@ -676,52 +663,27 @@ static int ln_bwd_dgrad(hipStream_t s, int M, int N, const float* dy, const floa
     return gemm_any(s, 0, 0, M, N, FIRA_D, dx_drop, FIRA_D, W, ldw, dX, lddx, nullptr, 0, 0, nullptr, nullptr, relu_mask);
 }
 
-// bf16 mode: the attention matmuls run on bf16 operands too (torch.autocast semantics); FIRA_ATTN_BF16=0 keeps the fp32
-// MFMA chains (A/B switch)
-static inline int attn_bf16() {
-    static const bool off = [] { const char* e = getenv("FIRA_ATTN_BF16"); return e && e[0] == '0'; }();
-    return g_dtype == 1 && !off;
-}
+// bf16 mode: the attention matmuls run on bf16 operands too (torch.autocast semantics)
+static inline int attn_bf16() { return g_dtype == 1; }
 
 // GCN layer as one fused launch per direction (gcn_fused.hip) instead of SpMM + product + add-LayerNorm (forward) /
-// product + SpMM (backward); FIRA_GCN_FUSED=0 restores the separate kernels (A/B switch)
-// ... and by the batch's density (round 6): the fused kernels' gather is built for FIRA's graphs (3-4 entries per computed row,
-// the first 16 of a row in one batched round trip); rows beyond 16 entries take a 64-at-a-time tail loop per row, and on BASELINE
-// config 5's graphs (116 entries per row) the fused forward costs 518 us against 319 us for aggregation + product + row kernel
-// (bench.py: gcn_cfg5).  Batches averaging more than FIRA_GCN_FUSED_MAX_DEG entries per computed row (default 48) run the separate
-// kernels; set per call by check_batch.
+// product + SpMM (backward), where the batch's density allows (round 6): the fused kernels' gather is built for FIRA's graphs
+// (3-4 entries per computed row, the first 16 of a row in one batched round trip); rows beyond 16 entries take a 64-at-a-time
+// tail loop per row, and on BASELINE config 5's graphs (116 entries per row) the fused forward costs 518 us against 319 us for
+// aggregation + product + row kernel (bench.py: gcn_cfg5).  Batches averaging more than GCN_FUSED_MAX_DEG entries per computed
+// row run the separate kernels; set per call by check_batch.
+// (The backward pass was measured unfused too -- V = A_hat dY by the CSR kernel, dX += V W21 by the product -- in bf16 at batch
+// 64, where the product is a few microseconds of MFMA time and the fused launch's phase latencies are exposed: 16 239 / 16 203
+// commits/s fused against 16 110 / 15 982.  Both directions follow the same rule.)
+static constexpr double GCN_FUSED_MAX_DEG = 48.0;
 static thread_local bool g_dense_graphs = false;
-static inline bool gcn_fused_on() {
-    static const bool off = [] { const char* e = getenv("FIRA_GCN_FUSED"); return e && e[0] == '0'; }();
-    return !off && !g_dense_graphs;
-}
+static inline bool gcn_fused_on() { return !g_dense_graphs; }
 static inline void note_graph_density(const fira_batch* b) {
-    static const double max_deg = [] { const char* e = getenv("FIRA_GCN_FUSED_MAX_DEG"); return e ? atof(e) : 48.0; }();
-    g_dense_graphs = b->n_nodes > 0 && (double)b->nnz > max_deg * (double)b->n_nodes;
+    g_dense_graphs = b->n_nodes > 0 && (double)b->nnz > GCN_FUSED_MAX_DEG * (double)b->n_nodes;
 }
 
-// ... and of the backward pass only (FIRA_GCN_FUSED_BWD=0: V = A_hat dY by the CSR kernel, dX += V W21 by the product -- the same
-// identity in two launches).  Measured in bf16 at batch 64, where the product is a few microseconds of MFMA time and the
-// fused launch's phase latencies are exposed: 16 239 / 16 203 commits/s fused against 16 110 / 15 982 -- fused stays the
-// default in both modes.
-static inline bool gcn_fused_bwd_on() {
-    static const bool off = [] { const char* e = getenv("FIRA_GCN_FUSED_BWD"); return e && e[0] == '0'; }();
-    return !off;
-}
-
-// Combination block as one fused launch (comb_fused.hip) instead of product + gate kernel + product + add-LayerNorm, in fp32
-// and in bf16 mode (operands rounded as the panel products round them).  FIRA_COMB_FUSED=0 restores the separate kernels,
-// FIRA_COMB_FUSED_BF16=0 in bf16 mode only (A/B switches).
-static inline bool comb_fused_on() {
-    static const bool off = [] { const char* e = getenv("FIRA_COMB_FUSED"); return e && e[0] == '0'; }();
-    static const bool off16 = [] { const char* e = getenv("FIRA_COMB_FUSED_BF16"); return e && e[0] == '0'; }();
-    return !off && !(g_dtype == 1 && off16);
-}
-
-static inline bool comb_fused_bwd_on() {         // FIRA_COMB_FUSED_BWD=0: the backward pass keeps its four launches (A/B switch)
-    static const bool off = [] { const char* e = getenv("FIRA_COMB_FUSED_BWD"); return e && e[0] == '0'; }();
-    return !off && comb_fused_on();
-}
+// The Combination block runs as one fused launch per direction (comb_fused.hip) instead of product + gate kernel + product +
+// add-LayerNorm, in fp32 and in bf16 mode (operands rounded as the panel products round them), for layers 0..7.
 
 enum Site { SITE_GATE = 0, SITE_COMB_OUT = 1, SITE_GCN = 2, SITE_SELF = 3, SITE_CROSS = 4, SITE_FFN = 5 };
 static inline uint32_t site(int layer, int kind) { return (uint32_t)(layer * 8 + kind + 1); }
@@ -817,10 +779,10 @@ static int decoder_lanes(Ctx& c) {
     // Measured (profiles/r6_probes.md, same-box triples): two lanes are -1.9 % at batch 32 (530 rows: every launch of the chain is
     // a latency-bound workgroup chain whose duration does not shrink with half the rows -- the two lanes' launches take as long
     // each as the one they replace, and the extra forks / joins are pure cost), +2.2 % at batch 64 (1 130 rows, fp32), +0.6 % in
-    // bf16 at batch 64.  Default: two lanes from FIRA_DEC_LANES_MIN_ROWS computed target rows; FIRA_DEC_LANES=1|2 forces.
+    // bf16 at batch 64.  Default: two lanes from DEC_LANES_MIN_ROWS computed target rows; FIRA_DEC_LANES=1|2 forces.
+    constexpr int DEC_LANES_MIN_ROWS = 768;
     static const int forced = [] { const char* e = getenv("FIRA_DEC_LANES"); return e ? (atoi(e) >= 2 ? 2 : 1) : 0; }();
-    static const int min_rows = [] { const char* e = getenv("FIRA_DEC_LANES_MIN_ROWS"); return e ? atoi(e) : 768; }();
-    const int want = forced ? forced : (c.Td >= min_rows ? 2 : 1);
+    const int want = forced ? forced : (c.Td >= DEC_LANES_MIN_ROWS ? 2 : 1);
     c.n_lanes = g_lanes = 1;
     c.lanes[0] = Lane{c.s, 0, c.pl->B, 0, c.Td};
     const fira_batch& bt = *c.bt;
@@ -870,31 +832,19 @@ static int lanes_fork_to(Ctx& c, hipStream_t target) {
 // The encoder runs on the batch's COMPUTED node list only (fira_batch.node_rows): padded nodes carry nothing but a
 // self-loop, are masked as attention keys / copy slots and receive exactly zero gradient (SURVEY.md §8a note N1), so
 // leaving them out changes no consumed value.  Nc = n_nodes, Cc = n_code, Mc = n_mem below.
-// FIRA_FOLD_ONE=0: the folded GCN weights as two products + a transpose per layer (14 launches) instead of one launch (A/B switch)
-// FIRA_GCN_X3=0: the fused GCN product of fp32 mode as fp32 MFMAs instead of three bf16 terms (A/B switch; gcn_fused.hip)
-static inline bool fold_one_launch();
-// FIRA_COMB_X3=0: the same switch for the fused Combination block's three products per direction (comb_fused.hip)
-static inline bool comb_x3_on(int nl) {
-    static const bool off = [] { const char* e = getenv("FIRA_COMB_X3"); return e && e[0] == '0'; }();
-    static const bool off16 = [] { const char* e = getenv("FIRA_X1_BF16"); return e && e[0] == '0'; }();
-    return !off && (g_dtype == 0 || !off16) && comb_fused_on() && nl <= 8;
-}
-// the training step's K|V projection of the memory rows as linear_x3 (three-term planes in fp32 mode, one plane in bf16 mode)
-// instead of one fp32 / bf16 GEMM launch per layer; FIRA_KV_X3=0: those launches (A/B switch)
-static inline bool kv_x3_on(int nl) {
-    static const bool off = [] { const char* e = getenv("FIRA_KV_X3"); return e && e[0] == '0'; }();
-    return !off && nl * 2 <= 24;
-}
-static inline bool gcn_x3_on(int nl) {
-    static const bool off = [] { const char* e = getenv("FIRA_GCN_X3"); return e && e[0] == '0'; }();
-    // (bf16 mode runs the one-plane form of the same kernels; FIRA_X1_BF16=0 = its round-5 kernels, A/B switch)
-    static const bool off16 = [] { const char* e = getenv("FIRA_X1_BF16"); return e && e[0] == '0'; }();
-    return !off && (g_dtype == 0 || !off16) && gcn_fused_on() && fold_one_launch() && nl <= 10;
-}
-static inline bool fold_one_launch() {
-    static const bool off = [] { const char* e = getenv("FIRA_FOLD_ONE"); return e && e[0] == '0'; }();
-    return !off;
-}
+// (round 5) The folded GCN weights of every layer in ONE launch (gcn_fold_weights) up to 10 layers instead of two products + a
+// transpose per layer (14 launches); deeper models take the per-layer launches.
+static inline bool fold_one_launch(int nl) { return nl <= 10; }
+// (round 6) The fused GCN product (gcn_fused.hip) and the fused Combination block's three products per direction
+// (comb_fused.hip) on pre-split bf16 planes of their weights: three terms per operand in fp32 mode instead of fp32 MFMA chains
+// (GCN +2.2 % / +1.9 % at batch 32 / 64, Combination +0.35 % / +1.3 %), one plane in bf16 mode instead of the round-5 kernels
+// that rounded fragments in every wave (+5.1 % at batch 64).  The planes of every layer are formed in one
+// launch, which bounds the depth.
+static inline bool comb_x3_on(int nl) { return nl <= 8; }
+static inline bool gcn_x3_on(int nl) { return gcn_fused_on() && fold_one_launch(nl); }
+// (round 6) the training step's K|V projection of the memory rows as linear_x3 (three-term planes in fp32 mode, one plane in
+// bf16 mode): two launches instead of one fp32 / bf16 GEMM launch per layer (+0.4 % at fp32 batch 64, +1.0 % in bf16)
+static inline bool kv_x3_on(int nl) { return nl * 2 <= 24; }
 
 // the target-word rows this batch's decoder gathers, brought up to step - 1 in memory (the dense-target-row path only: the
 // compact paths read lazily, adam_rows_load)
@@ -929,44 +879,41 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
     // ~100 us into the call, 12 launches of the auxiliary stream would not be through by then); the rest is awaited at
     // layer 1.
     hipEvent_t ev_fold0 = nullptr, ev_fold = nullptr, ev_comb = nullptr;
-    static const bool one_wait = [] { const char* e = getenv("FIRA_FOLD_ONE_WAIT"); return !(e && e[0] == '0'); }();   // A/B switch
     bool fold_waited = false;
     {
         const bool ax = side_on() && !c.serial;
         hipStream_t fs = ax ? side().aux : s;
         if (ax) TRY(aux_fork(s));
-        if (comb_fused_on()) {
-            // k-major copies of the Combination weights of every layer (Wq^T, Wk^T, Wo^T): one launch, the first thing on the
-            // auxiliary stream -- layer 0's block is the third launch of the caller's stream
-            TransposeTable tt;
-            for (int l = 0; l < p.nl && tt.n + 3 <= 24; ++l) {
-                const EncLayer& w = L.enc[l];
-                float* dst = p.WcT + (size_t)l * 3 * D * D;
-                tt.src[tt.n] = c.P + w.wqk; tt.dst[tt.n++] = dst;
-                tt.src[tt.n] = c.P + w.wqk + (size_t)D * D; tt.dst[tt.n++] = dst + (size_t)D * D;
-                tt.src[tt.n] = c.P + w.wo; tt.dst[tt.n++] = dst + (size_t)2 * D * D;
-            }
-            TRY(transpose256_table(fs, tt));
-            if (comb_x3_on(p.nl)) {      // planes of Wq | Wk | Wo as stored (forward) and of the k-major copies (backward)
-                const float* src[48];
-                uint16_t* dst[48];
-                int n = 0;
-                for (int l = 0; l < p.nl; ++l) {
-                    const EncLayer& w = L.enc[l];
-                    const float* st[3] = {c.P + w.wqk, c.P + w.wqk + (size_t)D * D, c.P + w.wo};
-                    for (int j = 0; j < 3; ++j) {
-                        src[n] = st[j]; dst[n++] = p.WcX + ((size_t)l * 3 + j) * 3 * D * D;
-                        if (c.G) { src[n] = p.WcT + ((size_t)l * 3 + j) * D * D; dst[n++] = p.WcTX + ((size_t)l * 3 + j) * 3 * D * D; }
-                    }
-                }
-                TRY(gcn_split_planes(fs, n, src, dst));
-            }
-            // (with the one-launch fold right behind it, ONE mark serves the first Combination block and the first GCN layer: every
-            //  wait is a barrier packet in the caller's chain, and the fold is through ~25 us into the call, before the first
-            //  Combination block starts)
-            if (ax && !(one_wait && fold_one_launch() && p.nl <= 10 && (!g_Wb || gcn_fused_on()))) TRY(side_mark(&ev_comb));
+        // k-major copies of the Combination weights of every layer (Wq^T, Wk^T, Wo^T): one launch, the first thing on the
+        // auxiliary stream -- layer 0's block is the third launch of the caller's stream
+        TransposeTable tt;
+        for (int l = 0; l < p.nl && tt.n + 3 <= 24; ++l) {
+            const EncLayer& w = L.enc[l];
+            float* dst = p.WcT + (size_t)l * 3 * D * D;
+            tt.src[tt.n] = c.P + w.wqk; tt.dst[tt.n++] = dst;
+            tt.src[tt.n] = c.P + w.wqk + (size_t)D * D; tt.dst[tt.n++] = dst + (size_t)D * D;
+            tt.src[tt.n] = c.P + w.wo; tt.dst[tt.n++] = dst + (size_t)2 * D * D;
         }
-        const bool fold_one = fold_one_launch() && p.nl <= 10;
+        TRY(transpose256_table(fs, tt));
+        if (comb_x3_on(p.nl)) {      // planes of Wq | Wk | Wo as stored (forward) and of the k-major copies (backward)
+            const float* src[48];
+            uint16_t* dst[48];
+            int n = 0;
+            for (int l = 0; l < p.nl; ++l) {
+                const EncLayer& w = L.enc[l];
+                const float* st[3] = {c.P + w.wqk, c.P + w.wqk + (size_t)D * D, c.P + w.wo};
+                for (int j = 0; j < 3; ++j) {
+                    src[n] = st[j]; dst[n++] = p.WcX + ((size_t)l * 3 + j) * 3 * D * D;
+                    if (c.G) { src[n] = p.WcT + ((size_t)l * 3 + j) * D * D; dst[n++] = p.WcTX + ((size_t)l * 3 + j) * 3 * D * D; }
+                }
+            }
+            TRY(gcn_split_planes(fs, n, src, dst));
+        }
+        const bool fold_one = fold_one_launch(p.nl);
+        // (with the one-launch fold right behind it, ONE mark serves the first Combination block and the first GCN layer: every
+        //  wait is a barrier packet in the caller's chain, and the fold is through ~25 us into the call, before the first
+        //  Combination block starts)
+        if (ax && !(fold_one && (!g_Wb || gcn_fused_on()))) TRY(side_mark(&ev_comb));
         if (fold_one) {
             // (round 5) every layer's W21, its k-major copy and c21: ONE launch (gemm_small.hip: gcn_fold_weights).  The fused GCN
             // kernels read the fp32 matrices in both modes, so the mark behind this launch is all the first layer waits for
@@ -1005,7 +952,7 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
         if (!fold_one && gcn_fused_on() && p.nl > 1) TRY(transpose256(fs, p.nl - 1, p.W21 + (size_t)D * D, p.W21t + (size_t)D * D));
         // (the closing mark only where something follows the fold that the encoder's own launches read: the unfused GCN path's
         //  bf16 shadows of the folded weights, or the layer-by-layer fold)
-        if (ax && !(one_wait && ev_fold0 && fold_one && gcn_fused_on())) TRY(side_mark(&ev_fold));
+        if (ax && !(ev_fold0 && fold_one && gcn_fused_on())) TRY(side_mark(&ev_fold));
         if (!ev_fold0) ev_fold0 = ev_fold;           // bf16 mode / one layer: a single mark
         if (c.shadow_tab) {                          // (see Ctx::shadow_tab)
             TRY(weight_shadows(fs, *c.shadow_tab, c.P, p.wb, p.wbt));
@@ -1036,7 +983,7 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
         float* X = p.X[l];
         // Combination (gnn_transformer.py:192-205): code rows only; the result overwrites them in place.  e.Xc (the code
         // rows before the update: residual, and the q|k weight gradient's operand) was stored by the kernel that produced X
-        if (comb_fused_on() && l < 8) {
+        if (l < 8) {                 // (the k-major weight copies above cover 8 layers; deeper layers: the four launches)
             if (l == 0 && ev_comb) TRY(main_wait(s, ev_comb, __LINE__));
             else if (l == 0 && ev_fold0) { TRY(main_wait(s, ev_fold0, __LINE__)); fold_waited = true; }
             const float* wt = p.WcT + (size_t)l * 3 * D * D;
@@ -1119,11 +1066,9 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
         }
         // ... and, in bf16 mode, the plane of the generator projection's transposed row blocks (one 38 MB pass under the decoder's
         // forward chain) for its data gradient as dgrad_x3_splitk: +1.0 % at batch 64.  (fp32 mode keeps the fp32 MFMA launch: the
-        // three-plane form streams 680 MB of planes through L2 per launch at batch 32 and LOST 0.9 % -- profiles/r6_probes.md;
-        // FIRA_VOCAB_DGRAD_X3=1 forces it, =0 switches it off in both modes.)
-        static const int vd_mode = [] { const char* e = getenv("FIRA_VOCAB_DGRAD_X3"); return e ? atoi(e) : -1; }();
-        if (c.G && (vd_mode == 1 || (vd_mode == -1 && g_dtype == 1))) {
-            TRY(split_planes_t(ss, c.P + L.wout, p.V, p.WoutTX, g_dtype == 1));
+        // three-plane form streams 680 MB of planes through L2 per launch at batch 32 and LOST 0.9 % -- profiles/r6_probes.md.)
+        if (c.G && g_dtype == 1) {
+            TRY(split_planes_t(ss, c.P + L.wout, p.V, p.WoutTX, true));
             c.wout_planes = true;
         }
         c.deferred = true;
@@ -1258,9 +1203,9 @@ static int head_forward(Ctx& c, int R, const int32_t* rows, float* loss_sum, int
         TRY(rows_gather_idx(s, R, p.dec_c, dec, rows));
         dec_rows = p.dec_c;
     }
-    // fp32 mode: the generator projection as three bf16 terms per operand (head_x3.hip; FIRA_HEAD_X3=0 = the fp32 tiled kernel)
-    static const bool head_x3_off = [] { const char* e = getenv("FIRA_HEAD_X3"); return e && e[0] == '0'; }();
-    if (g_dtype == 0 && !head_x3_off && R >= 64 && R <= p.TB)
+    // (round 6) fp32 mode: the generator projection as three bf16 terms per operand (head_x3.hip) instead of the fp32 tiled kernel
+    // (1.55x stand-alone; +-0 on the step at batch 32, +0.2 % at batch 64)
+    if (g_dtype == 0 && R >= 64 && R <= p.TB)
         TRY(head_logits_x3(s, R, p.V, dec_rows, D, c.P + L.wout, c.P + L.bout, p.logits, p.ldl, p.xh_planes));
     else
     TRY(linear(s, R, p.V, D, dec_rows, D, c.P + L.wout, c.P + L.bout, p.logits, p.ldl));
@@ -1287,11 +1232,6 @@ static inline int enc_wgrad_every(int n_rows, int n_layers) {
     static const int forced = [] { const char* e = getenv("FIRA_ENC_WGRAD_EVERY"); const int v = e ? atoi(e) : 0; return v >= 1 ? v : 0; }();
     if (forced) return forced;
     return n_rows <= 32768 ? std::max(1, n_layers) : 1;
-}
-
-static inline bool fewer_forks() {
-    static const bool off = [] { const char* e = getenv("FIRA_FEWER_FORKS"); return e && e[0] == '0'; }();
-    return !off;
 }
 
 // what the encoder half of the backward pass needs from the decoder half (the two halves are one call, or the two calls
@@ -1362,9 +1302,8 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     if (so) TRY(aux_fork(s));
     TRY(linear_dgrad(ss, Mc, D, D, p.dsrc_c, D, c.P + L.ws, p.dmem_c, D, false));
     // (round 5: LinearSource's weight gradient rides in the decoder's grouped launch -- its own fork was an event record on the
-    //  caller's stream right behind the auxiliary stream's; FIRA_FEWER_FORKS=0: its own fork and launch)
-    if (fewer_forks()) TRY(linear_wgrad_grouped(s, Mc, D, D, p.dsrc_c, D, p.mem_c, D, G + L.ws, nullptr, 8));
-    else TRY(linear_wgrad(s, Mc, D, D, p.dsrc_c, D, p.mem_c, D, G + L.ws, nullptr));
+    //  caller's stream right behind the auxiliary stream's)
+    TRY(linear_wgrad_grouped(s, Mc, D, D, p.dsrc_c, D, p.mem_c, D, G + L.ws, nullptr, 8));
     if (R > 0) {
         if (ev_dfc) TRY(main_wait(s, ev_dfc, __LINE__));
         TRY(rows_scatter_add_idx(s, R, p.ddec_c, p.ddec, rows));
@@ -1380,24 +1319,19 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     // first layers of the encoder's MFMA-bound chain.  Round 4 / early round 5 measured the early launches at -0.6 % (the
     // weight-gradient stream was busy with the encoder's per-layer launches afterwards anyway); with those behind the chain:
     // three layers per launch +0.9 % (fast class) / +-0 (slow class) at batch 32, +1.0 % at batch 64, two layers -1.3 %, bf16
-    // neutral (profiles/r5_probes.md).  fp32, single device (data-parallel runs hand the bucket over at the mid event);
-    // FIRA_DEC_WGRAD_EVERY=0: one launch behind the loop.
-    static const int dec_every_env = [] { const char* e = getenv("FIRA_DEC_WGRAD_EVERY"); const int v = e ? atoi(e) : 3; return v > 0 ? v : 0; }();
+    // neutral (profiles/r5_probes.md).  A depth that is not a multiple of DEC_WGRAD_EVERY: one launch behind the loop.
+    constexpr int DEC_WGRAD_EVERY = 3;
     // Round 6 re-measured both exclusions.  (1) A mid event (data-parallel steps) used to force the single launch; with the panel
-    // kernels that launch is the SLOW form (FIRA_DEC_WGRAD_EVERY=0 on one device: -11 % at batch 32, -17 % at batch 64), and the
-    // two-call step on one device (scripts/probes/dp1_probe.py) goes 2.716 -> 2.444 ms at batch 32, 4.214 -> 3.546 ms at batch 64
-    // with the launches of three layers.  Every gradient of [0, split) is still final when the mid event fires
+    // kernels that launch is the SLOW form (one launch behind the loop on one device: -11 % at batch 32, -17 % at batch 64), and
+    // the two-call step on one device (scripts/probes/dp1_probe.py) goes 2.716 -> 2.444 ms at batch 32, 4.214 -> 3.546 ms at
+    // batch 64 with the launches of three layers.  Every gradient of [0, split) is still final when the mid event fires
     // (scripts/probes/mid_event_probe.py: a stream waiting for the event snapshots the slice -- no element changes afterwards).
     // Taken by every caller with a mid event: fira_train_step_begin / _begin_rows and fira_train_fwd_bwd (the ZeRO-1 and the
-    // unfused trainers; FIRA_DEC_WGRAD_DP=0 = the single launch under a mid event, A/B switch).  (The ZeRO-1 test that kept the
-    // second group on the single launch for a while was a ReLU tie of the golden batch, not this schedule: one hidden unit of
-    // decoder layer 3 has a pre-activation of +-1e-9 in step 1 and two SINGLE-process runs disagree on its mask as often --
-    // scripts/probes/nondet_probe.py, profiles/r6_probes.md.)
-    // (2) bf16 mode: +0.8 % at batch 64 with the launches of three layers (23 513 -> 23 691, same-box triple); FIRA_DEC_WGRAD_BF16=0.
-    static const int dec_dp = [] { const char* e = getenv("FIRA_DEC_WGRAD_DP"); return e ? atoi(e) : -1; }();
-    static const bool dec_bf16_off = [] { const char* e = getenv("FIRA_DEC_WGRAD_BF16"); return e && e[0] == '0'; }();
-    const bool mid_single = mid_event && dec_dp == 0;
-    const int dec_every = (mid_single || (g_dtype != 0 && dec_bf16_off) || dec_every_env == 0 || p.nl % dec_every_env != 0) ? 0 : dec_every_env;
+    // unfused trainers).  (The ZeRO-1 test that kept the second group on the single launch for a while was a ReLU tie of the
+    // golden batch, not this schedule: one hidden unit of decoder layer 3 has a pre-activation of +-1e-9 in step 1 and two
+    // SINGLE-process runs disagree on its mask as often -- scripts/probes/nondet_probe.py, profiles/r6_probes.md.)
+    // (2) bf16 mode: +0.8 % at batch 64 with the launches of three layers (23 513 -> 23 691, same-box triple).
+    const int dec_every = p.nl % DEC_WGRAD_EVERY != 0 ? 0 : DEC_WGRAD_EVERY;
     {
     ProfScope prof_region(s, PROF_DEC_REGION, 0.0);      // wall time of the decoder's backward layers (see decoder_forward)
     TRY(lanes_fork(c));                        // (lane 1 starts behind the head's backward kernels)
@@ -1421,9 +1355,8 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
         // (r3_event_cost.txt) and hides ~20 us of work per layer
         // (two lanes, round 6: the product forks from the point where each lane's cross-attention backward has written its rows of
         //  dkv_all -- ev_kv_done, recorded there -- not from the lanes' tails behind the whole layer: the last pair, which the
-        //  encoder's backward pass waits for, then runs beside layer 0's self-attention backward instead of behind it.
-        //  FIRA_DMEM_FORK_EARLY=0: from the tails, A/B switch)
-        static const bool dmem_early_off = [] { const char* e = getenv("FIRA_DMEM_FORK_EARLY"); return e && e[0] == '0'; }();
+        //  encoder's backward pass waits for, then runs beside layer 0's self-attention backward instead of behind it: +0.7 % at
+        //  fp32 batch 64)
         hipEvent_t ev_kv_done[2] = {nullptr, nullptr};
         auto dmem_pair = [&]() -> int {
             if (!(so && (l % 2 == 0 || l == 0))) return 0;
@@ -1435,9 +1368,9 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
             } else
             TRY(aux_fork_all());
             prof_decoder_tag(-1);               // a memory-row product: not one of the decoder's M = B*30 ones
-            // (round 6) FIRA_DMEM_X3=0: the fp32 / bf16 GEMM launch instead of linear_x3_kacc (A/B switch)
-            static const bool dmem_x3_off = [] { const char* e = getenv("FIRA_DMEM_X3"); return e && e[0] == '0'; }();
-            const int rc_kv = (c.kv_planes && !dmem_x3_off)
+            // (round 6) linear_x3_kacc on the planes of the transposed K|V blocks when encoder_forward formed them (kv_x3_on):
+            // +1.2 % / +0.9 % at fp32 batch 32 / 64, +1.6 % in bf16; otherwise the fp32 / bf16 GEMM launch
+            const int rc_kv = c.kv_planes
                     ? linear_x3_kacc(ss, Mc, p.dkv_all + o, p.kvp, p.WkvTX + (size_t)l * 2 * 3 * D * D, nlay * 2, p.dmem_c, D, true, g_dtype == 1)
                     : linear_dgrad(ss, Mc, nlay * 2 * D, D, p.dkv_all + o, p.kvp, c.P + L.wkv_all + o * D, p.dmem_c, D, true);
             prof_decoder_tag(+1);
@@ -1469,7 +1402,7 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
                               p.mem_valid_c, 0, 0, e.ao2, D, bx, D, g.dq, D, p.dkv_all + l * 2 * D, p.kvp,
                               p.dkv_all + l * 2 * D + D, p.kvp, q_off, 0, attn_bf16(), p.mem_off + ln.b0));
             if (c.n_lanes == 1) TRY(dmem_pair());
-            else if (!dmem_early_off && so && l % 2 == 0 && k < 2) {
+            else if (so && l % 2 == 0 && k < 2) {
                 ev_kv_done[k] = side().ev();
                 if (hipEventRecord(ev_kv_done[k], ls) != hipSuccess) return set_err("lane event record failed");
             }
@@ -1523,13 +1456,11 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
         TRY(linear_dgrad(s, Mc, KV, D, p.dkv_all, p.kvp, c.P + L.wkv_all, p.dmem_c, D, true));
     }
     // (round 5: no fork of its own -- the weight-gradient stream waited for the caller's stream at the grouped launch above, and
-    //  dkv_all was complete by then)
-    if (dec_every > 0 && side().stream && side().enabled) {
-        // (the K|V weight gradient went out in row blocks inside the loop)
-    } else if (fewer_forks() && side().stream && side().enabled)
+    //  dkv_all was complete by then; with dec_every > 0 it went out in row blocks inside the loop)
+    if (!(side().stream && side().enabled))
+        TRY(linear_wgrad(s, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all, PANEL_KV));
+    else if (dec_every == 0)
         TRY(wgrad_on(side().stream, PANEL_KV, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all));
-    else
-    TRY(linear_wgrad(s, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all, PANEL_KV));
     // decoder LayerNorms, copy head: their partial rows were written before the fork of the weight gradient above, and only
     // the end of the step (or the mid-event below, which waits for this stream) reads the sums: off the dependent chain
     TRY(deferred_reduce(side().stream && side().enabled ? side().stream : s, red().tab));
@@ -1574,8 +1505,8 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
     float* dXn = p.dXa;
     float* other = p.dXb;
     UnfoldTable unfold_tab;                  // GCN layers whose dc comes out of the deferred reduction at the end
-    // (round 5) FIRA_UNFOLD_LATE=0: the folded weight's two unfold products per layer as two launches behind that layer's grouped
-    // weight gradients (A/B switch); default: all layers in one launch behind the last group
+    // (round 5) the folded weight's unfold products of all layers in one launch behind the last group; FIRA_UNFOLD_LATE=0: two
+    // launches per layer behind that layer's grouped weight gradients (schedule switch: tests/test_model_gpu.py checks both)
     static const bool unfold_late_off = [] { const char* e = getenv("FIRA_UNFOLD_LATE"); return e && e[0] == '0'; }();
     const bool unfold_late = !unfold_late_off && enc_group_on() && p.nl <= 16;
     // The per-layer unfold reads dW21 right behind the layer's grouped launch: without the late launch (the switch, or more
@@ -1630,13 +1561,8 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         if (gcn_fused_on()) {
             // one launch: V = A_hat dY (stored in e.Z, which the fused forward pass does not use), other = ds + V W21.
             // The weight gradient follows from the same V: dW21 = dY^T (A_hat X) = (A_hat dY)^T X = V^T X
-            if (gcn_fused_bwd_on()) {
-                TRY(gcn_fused_bwd(s, Nc, bt.rowptr, bt.col, bt.val, g.dY2, p.W21 + (size_t)l * D * D, e.Z, other, g_dtype == 1,
-                                  gcn_x3_on(p.nl) ? p.W21tx + (size_t)l * 3 * D * D : nullptr));
-            } else {
-                TRY(csr_spmm_ex(s, Nc, bt.rowptr, bt.col, bt.val, g.dY2, D, e.Z, D, 0, 1, 0, nullptr));            // V
-                TRY(linear_dgrad(s, Nc, D, D, e.Z, D, p.W21 + (size_t)l * D * D, other, D, true));                 // other += V W21
-            }
+            TRY(gcn_fused_bwd(s, Nc, bt.rowptr, bt.col, bt.val, g.dY2, p.W21 + (size_t)l * D * D, e.Z, other, g_dtype == 1,
+                              gcn_x3_on(p.nl) ? p.W21tx + (size_t)l * 3 * D * D : nullptr));
             TRY(enc_wgrad(s, Nc, D, D, e.Z, D, p.X[l], D, dW21, nullptr));
             if (!sums) TRY(colsum(s, Nc, D, g.dY2, D, G + w.fc2b));     // (db2 = column sums of dY, not of V)
             if (!grouped) TRY(unfold());
@@ -1648,27 +1574,24 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         }
         // Combination on the code rows, in place inside `other` through the code-row map: the LayerNorm backward reads
         // dG[code rows] and leaves the residual-branch gradient there; the q|k projection's dgrad adds to the same rows
-        bool comb_done = false;
-        if (comb_fused_bwd_on()) {
-            // one launch (comb_fused.hip): LayerNorm backward, dgrad through Wo, gate backward, dgrad through Wq | Wk
-            const int nb = comb_fused_bwd_parts();
-            // (both blocks or neither: six table rows and nb * 6 * D floats asked for at once)
-            float* part_ln = red().alloc((size_t)nb * 6 * D, 6);
-            float* part_v = part_ln ? part_ln + (size_t)nb * 2 * D : nullptr;
-            if (part_v) {
-                TRY(comb_fused_bwd(s, Cc, other, bt.code_rows, e.s1, e.st1, c.P + w.ln1g, c.P + w.wo, c.P + w.wqk, e.qk,
-                                   p.vtab_all + l * D, p.nl * D, bt.code_mark, g.dYc, g.dqk, part_ln, part_v, c.p_drop, c.seed,
-                                   site(l, SITE_GATE), site(l, SITE_COMB_OUT), g_dtype == 1,
-                                   comb_x3_on(p.nl) ? p.WcTX + (size_t)l * 9 * D * D : nullptr));
-                red().add(G + w.ln1g, part_ln, D, nb, 2 * D);
-                red().add(G + w.ln1b, part_ln + D, D, nb, 2 * D);
-                for (int k = 0; k < 4; ++k)
-                    red().add(p.dvtab_all + (size_t)k * p.nl * D + l * D, part_v + k * D, D, nb, 4 * D);
-                TRY(enc_wgrad(s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
-                comb_done = true;
-            }
-        }
-        if (!comb_done) {
+        // One launch (comb_fused.hip): LayerNorm backward, dgrad through Wo, gate backward, dgrad through Wq | Wk -- where the
+        // deferred reduction has room for its partial rows (both blocks or neither: six table rows and nb * 6 * D floats asked
+        // for at once); otherwise the four launches.
+        const int nb_comb = comb_fused_bwd_parts();
+        float* part_ln = red().alloc((size_t)nb_comb * 6 * D, 6);
+        const bool comb_done = part_ln != nullptr;
+        if (comb_done) {
+            float* part_v = part_ln + (size_t)nb_comb * 2 * D;
+            TRY(comb_fused_bwd(s, Cc, other, bt.code_rows, e.s1, e.st1, c.P + w.ln1g, c.P + w.wo, c.P + w.wqk, e.qk,
+                               p.vtab_all + l * D, p.nl * D, bt.code_mark, g.dYc, g.dqk, part_ln, part_v, c.p_drop, c.seed,
+                               site(l, SITE_GATE), site(l, SITE_COMB_OUT), g_dtype == 1,
+                               comb_x3_on(p.nl) ? p.WcTX + (size_t)l * 9 * D * D : nullptr));
+            red().add(G + w.ln1g, part_ln, D, nb_comb, 2 * D);
+            red().add(G + w.ln1b, part_ln + D, D, nb_comb, 2 * D);
+            for (int k = 0; k < 4; ++k)
+                red().add(p.dvtab_all + (size_t)k * p.nl * D + l * D, part_v + k * D, D, nb_comb, 4 * D);
+            TRY(enc_wgrad(s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
+        } else {
         TRY(ln_bwd(s, Cc, other, e.s1, e.st1, c.P + w.ln1g, other, g.dYc, G + w.ln1g, G + w.ln1b, c.p_drop,
                               c.seed, site(l, SITE_COMB_OUT), bt.code_rows));
         TRY(enc_wgrad(s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
@@ -1762,9 +1685,8 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
                          ad.step, c.n_tok, nullptr));
         }
         // ... and the encoder's two embedding tables (the head of group B: layout.cpp), whose gradients the two launches above
-        // on this stream have just completed -- also ahead of the join
-        static const bool emb_early_off = [] { const char* e = getenv("FIRA_ADAM_EMB_EARLY"); return e && e[0] == '0'; }();   // A/B switch
-        if (!emb_early_off && !c.adam_a_only) adam_b0 = L.mark_emb;
+        // on this stream have just completed -- also ahead of the join (+0.4 % against behind it, profiles/r5_probes.md)
+        if (!c.adam_a_only) adam_b0 = L.mark_emb;
         if (c.row_step && !c.adam_a_only) {
             // both vocabulary-sized tables as ONE launch over the rows whose gradient row is not zero (the gradient rows are
             // inspected: 2 x 25 MB read instead of 2 x 177 MB moved); the 71-row table joins the closing launch
@@ -1900,9 +1822,9 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
     const bool bf16 = opts && opts->dtype == 1;
     const ShadowTable* tab = bf16 ? shadow_table(*L) : nullptr;
     ShadowScope shadow_scope(params, L->total, bf16 ? p.wb : nullptr, bf16 ? p.wbt : nullptr, tab);
-    // FIRA_SHADOWS_LATE=0: the shadow refresh at the head of the caller's stream, as before round 5 (A/B switch)
-    static const bool shadows_late_off = [] { const char* e = getenv("FIRA_SHADOWS_LATE"); return e && e[0] == '0'; }();
-    const bool defer_sh = bf16 && !shadows_late_off && side_on() && gcn_fused_on() && comb_fused_on() && L->d.n_layer <= 8;
+    // (round 5) the shadow refresh on the auxiliary stream (see Ctx::shadow_tab) where the fused Combination / GCN kernels of every
+    // layer read the fp32 weights themselves; otherwise at the head of the caller's stream
+    const bool defer_sh = bf16 && side_on() && gcn_fused_on() && L->d.n_layer <= 8;
     if (bf16 && !defer_sh) TRY(weight_shadows(c.s, *tab, params, p.wb, p.wbt));
     if (defer_sh) c.shadow_tab = tab;
     // computed target rows: the decoder / head run on the prefix rows the batch lists (fira_batch.dec_off)
@@ -2226,9 +2148,9 @@ int fira_decode_step_ex(void* stream, const fira_dims* d, const float* params, v
     float* pend_y = nullptr;
     bool pending = false;
     DtypeScope dtype_scope(0);                  // the search runs the reference's fp32 arithmetic
-    // FIRA_DECODE_SELF_BLOCK=0: the three launches (A/B switch); the fused kernel needs the model's 8 x 32 heads and <= 32 keys
-    static const bool self_block_off = [] { const char* e = getenv("FIRA_DECODE_SELF_BLOCK"); return e && e[0] == '0'; }();
-    const bool self_block = !self_block_off && H * FIRA_DH == FIRA_D && H == 8 && T <= 32 && p.nl <= 12;
+    // (round 6) the self-attention block as one launch per layer (decode_self_block: 0.359 -> 0.333 ms per greedy step at batch
+    // 64); it needs the model's 8 x 32 heads and <= 32 keys -- otherwise the three launches
+    const bool self_block = H * FIRA_DH == FIRA_D && H == 8 && T <= 32 && p.nl <= 12;
     auto consume = [&](int N, const float* xin, const float* W, const float* b, float* Y, int flags) -> int {
         if (pending) {
             int rc = 0;

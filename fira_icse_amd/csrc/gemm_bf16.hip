@@ -703,8 +703,7 @@ int gemm_bf16_ex(hipStream_t s, int tA, int tB, int M, int N, int K, const float
     const bool can_split = (flags & FIRA_GEMM_ACCUM) && !(flags & FIRA_GEMM_RELU) && !relu_mask;
     int tile = ((flags >> FIRA_GEMM_TILE_SHIFT) & 3) - 1;       // -1: automatic; 0: 128x128; 1, 2: 64x64
     // skinny forward / dgrad shapes (the decoder): up to ~4 rounds of 32x32 tiles the latency kernel wins
-    static const int small_mode = [] { const char* e = getenv("FIRA_SMALL_GEMM"); return e ? atoi(e) : 1; }();
-    if (tile < 0 && splitk <= 1 && !colsum && !tA && small_mode && K % 64 == 0 && small_kernel_wins(M, N, K)) {
+    if (tile < 0 && splitk <= 1 && !colsum && !tA && K % 64 == 0 && small_kernel_wins(M, N, K)) {
         dim3 grid(cdiv(N, 32), cdiv(M, 32));
         if (tB) hipLaunchKernelGGL(gemm_bf16_small_kernel<true>, grid, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc, bias, flags & 3, c_rows, relu_mask);
         else hipLaunchKernelGGL(gemm_bf16_small_kernel<false>, grid, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc, bias, flags & 3, c_rows, relu_mask);
@@ -797,20 +796,16 @@ int gemm_bf16_wb_ex(hipStream_t s, int M, int N, int K, const float* A, int lda,
     FIRA_REQUIRE(c_rows || epilogue_fits(M, ldc), "gemm_bf16_wb: output of %d x %d floats exceeds the 2 GiB the kernels address", M, ldc);
     ProfScope prof(s, PROF_GEMM, 2.0 * M * N * (double)K, 4.0 * ((double)M * K + (double)M * N) + 2.0 * (double)N * K);
     const bool can_split = (flags & FIRA_GEMM_ACCUM) && !(flags & FIRA_GEMM_RELU) && !relu_mask;
-    static const int small_mode = [] { const char* e = getenv("FIRA_SMALL_GEMM"); return e ? atoi(e) : 2; }();
     // the coalesced tile kernel stays ahead of the tiled / panel kernels for more rounds of tiles and for long reductions
-    // (FIRA_SMALL_TILES16: A/B switch of the threshold)
-    static const long max_t32 = [] { const char* e = getenv("FIRA_SMALL_TILES16"); return e ? atol(e) : 1024L; }();
-    if (splitk <= 1 && small_mode >= 2 && K % 256 == 0 && K <= 1024 && (long)cdiv(M, 32) * cdiv(N, 32) <= max_t32 &&
-        !small_kernel_wins(M, N, K)) {
+    constexpr long max_t32 = 1024;
+    if (splitk <= 1 && K % 256 == 0 && K <= 1024 && (long)cdiv(M, 32) * cdiv(N, 32) <= max_t32 && !small_kernel_wins(M, N, K)) {
         int rc;
         if (gemm_bf16_tile32_try(s, M, N, K, A, lda, Bb, ldb, C, ldc, bias, flags & 3, c_rows, relu_mask, nullptr, &rc)) return rc;
     }
-    if (splitk <= 1 && small_mode && K % 64 == 0 && small_kernel_wins(M, N, K)) {
+    // the latency kernels' shapes: the coalesced tile kernel, or the fragment-load kernel where that one refuses the shape
+    if (splitk <= 1 && K % 64 == 0 && small_kernel_wins(M, N, K)) {
         int rc;
-        if (small_mode != 1 && gemm_bf16_tile32_try(s, M, N, K, A, lda, Bb, ldb, C, ldc, bias, flags & 3, c_rows, relu_mask,
-                                                    nullptr, &rc))
-            return rc;
+        if (gemm_bf16_tile32_try(s, M, N, K, A, lda, Bb, ldb, C, ldc, bias, flags & 3, c_rows, relu_mask, nullptr, &rc)) return rc;
         dim3 grid(cdiv(N, 32), cdiv(M, 32));
         hipLaunchKernelGGL((gemm_bf16_small_kernel<true, uint16_t>), grid, dim3(256), 0, s, M, N, K, A, lda, Bb, ldb, C, ldc,
                            bias, flags & 3, c_rows, relu_mask);
@@ -824,8 +819,7 @@ int gemm_bf16_wb_ex(hipStream_t s, int M, int N, int K, const float* A, int lda,
         // per element, one owner): the encoder's q|k data gradient [10 000, 256] x K 512 takes 2 x 12 us instead of the
         // tiled kernel's 43 us.  Not with a ReLU / ReLU mask, which must see the complete sum, and not for the decoder-sized
         // products with K = 768 / 1024, where one tiled launch (9.7 us) beats three or four chained ones.
-        static const int slice_mode = [] { const char* e = getenv("FIRA_PANEL_SLICES"); return e ? atoi(e) : 1; }();
-        if (slice_mode && K % 256 == 0 && K <= 1024 && (K == 512 || M >= 8192) && !(flags & FIRA_GEMM_RELU) && !relu_mask) {
+        if (K % 256 == 0 && K <= 1024 && (K == 512 || M >= 8192) && !(flags & FIRA_GEMM_RELU) && !relu_mask) {
             bool taken = true;
             for (int k0 = 0; k0 < K && taken; k0 += 256) {
                 const int fl = k0 == 0 ? (flags & FIRA_GEMM_ACCUM) : FIRA_GEMM_ACCUM;

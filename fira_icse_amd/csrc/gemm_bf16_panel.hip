@@ -436,11 +436,10 @@ bool linear_ln_bf16_try(hipStream_t s, int M, int K, const float* X, int ldx, co
                         float dropout, uint64_t seed, uint32_t site, const int32_t* y_rows, const float* r1_row,
                         const float* r1_col, int* rc, bool force) {
     *rc = 0;
-    // FIRA_FUSED_LN_BF16: 0 never | 1 every K = 256 block | 2 only the encoder-sized ones (M >= 4096) | 3 only the decoder-sized
-    // Measured on one box (profiles/r2_probes.md): 2 is +0.5 % on the batch-64 step, 3 is -1.8 % (M = 1 920 rows are 30
-    // workgroups here against 480 in the latency GEMM), 1 is -2.3 %.
-    static const int mode = [] { const char* e = getenv("FIRA_FUSED_LN_BF16"); return e ? atoi(e) : 2; }();
-    if (!force && (mode == 0 || (mode == 2 && M < 4096) || (mode == 3 && M >= 4096))) return false;
+    // Only the encoder-sized blocks (M >= 4096).  Measured on one box (profiles/r2_probes.md): that is +0.5 % on the batch-64
+    // step; the decoder-sized ones alone -1.8 % (M = 1 920 rows are 30 workgroups here against 480 in the latency GEMM), every
+    // K = 256 block -2.3 %.
+    if (!force && M < 4096) return false;
     if (K != PK || M < 64 || M >= (1 << 21) || ldx % 4 || ldb % 8 || ((uintptr_t)X % 16) || ((uintptr_t)Wb % 16) ||
         (long)M * ldx >= (1L << 29))
         return false;
@@ -458,10 +457,9 @@ bool linear_ln_bf16_try(hipStream_t s, int M, int K, const float* X, int ldx, co
 bool gemm_bf16_k256_try(hipStream_t s, int M, int N, int K, const float* A, int lda, const uint16_t* Bb, int ldb, float* C,
                         int ldc, const float* bias, int flags, const int32_t* c_rows, const float* relu_mask, int* rc) {
     *rc = 0;
-    static const int mode = [] { const char* e = getenv("FIRA_PANEL_GEMM"); return e ? atoi(e) : 1; }();   // A/B switch
-    if (!mode || K != PK || M < 64 || N < 32 || lda % 4 || ldb % 8 || ((uintptr_t)A % 16) || ((uintptr_t)Bb % 16)) return false;
+    if (K != PK || M < 64 || N < 32 || lda % 4 || ldb % 8 || ((uintptr_t)A % 16) || ((uintptr_t)Bb % 16)) return false;
     // BM 128 halves the weight-tile traffic per output; it needs enough rows to still fill the chip
-    const bool big = mode == 2 ? false : mode == 3 ? true : (N >= 512 && (long)M * N >= (4L << 20));
+    const bool big = N >= 512 && (long)M * N >= (4L << 20);
     const int bm = big ? 128 : 64;
     const int panels = cdiv(M, bm), n_tiles = cdiv(N, PBN);
     const int slots = 512;                                   // 2 resident workgroups per CU

@@ -355,19 +355,15 @@ __global__ __launch_bounds__(256) void gemm_grouped_wgrad_kernel(GroupTable g) {
         __syncthreads();
     }
 }
-// FIRA_WGRAD_WGS = n (experiment): weight-gradient launches use at most n workgroups (persistent over their tiles), so that
-// they leave wave / LDS slots and memory bandwidth to the latency-bound kernels of the dependent chain they run beside
-// Launches on the low-priority weight-gradient stream ask for FIRA_SIDE_LDS_PAD bytes of (unused) dynamic LDS on top of
+// Launches on the low-priority weight-gradient stream ask for SIDE_LDS_PAD bytes of (unused) dynamic LDS on top of
 // their tiles: four 34 KB workgroups fill a CU's 160 KB, and a workgroup of the dependent chain on the caller's stream
 // (33 KB for the 32x32 tile kernel) then waits for one of them to END before it can be placed -- stream priority orders
-// the dispatch of new workgroups, it frees nothing.  With the pad (default 7 KB) only three fit and the chain always finds
+// the dispatch of new workgroups, it frees nothing.  With the pad (7 KB) only three fit and the chain always finds
 // room: +0.3 % step on one box (11 409 -> 11 446 commits/s over three pairs); 20 KB (two per CU) costs 0.8 %.
+static constexpr unsigned SIDE_LDS_PAD = 7168;
 static hipStream_t g_pad_stream = nullptr;
 void gemm_set_pad_stream(hipStream_t s) { g_pad_stream = s; }
-static unsigned side_lds_pad(hipStream_t s) {
-    static const int pad = [] { const char* e = getenv("FIRA_SIDE_LDS_PAD"); return e ? atoi(e) : 7168; }();
-    return (pad > 0 && s && s == g_pad_stream) ? (unsigned)pad : 0u;
-}
+static unsigned side_lds_pad(hipStream_t s) { return (s && s == g_pad_stream) ? SIDE_LDS_PAD : 0u; }
 
 template <int BM, int BN>
 static int launch(hipStream_t s, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,

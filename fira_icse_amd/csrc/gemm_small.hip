@@ -483,11 +483,9 @@ static void tile32_launch(hipStream_t s, dim3 grid, int M, int N, const float* A
                        flags, c_rows, relu_mask, a_rows, tiles_n, er, LnA(), LnB());
 }
 
-// FIRA_TILE32_WAVES=0: always four waves (A/B switch).  8 waves (64 KB of slots: two workgroups per CU) up to 512 workgroups,
-// 12 / 16 waves (96 / 128 KB: one per CU) up to 256.
+// (round 5) 8 waves (64 KB of slots: two workgroups per CU) up to 512 workgroups, 12 / 16 waves (96 / 128 KB: one per CU) up
+// to 256; otherwise four.  Measured against always four waves: +1.4 % on the step (profiles/r5_probes.md).
 static int tile32_waves(int K, int n_wg) {
-    static const bool off = [] { const char* e = getenv("FIRA_TILE32_WAVES"); return e && e[0] == '0'; }();
-    if (off) return 4;
     const int chunks = K / 32;
     if (chunks == 32 && n_wg <= 256) return 16;
     if (chunks == 24 && n_wg <= 256) return 12;
@@ -523,8 +521,7 @@ static int tile32_launch_wide(hipStream_t s, int nw, int K, int tB, dim3 grid, i
 
 // shapes the coalesced tile kernel takes (the engine asks before it plans a fused LayerNorm prologue / residual epilogue)
 bool gemm_tile32_takes(int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb) {
-    static const int mode = [] { const char* e = getenv("FIRA_SMALL_GEMM"); return e ? atoi(e) : 2; }();
-    if (mode == 1 || M <= 0 || N <= 0) return false;
+    if (M <= 0 || N <= 0) return false;
     if (K % 128 != 0 || lda % 4 != 0 || ((uintptr_t)A % 16) != 0 || ldb % 4 != 0 || ((uintptr_t)B % 16) != 0) return false;
     const int nch = K / 128;
     if (nch != 1 && nch != 2 && nch != 3 && nch != 4 && nch != 6 && nch != 8) return false;
@@ -532,7 +529,7 @@ bool gemm_tile32_takes(int tB, int M, int N, int K, const float* A, int lda, con
     return true;
 }
 
-// true if the coalesced tile kernel took the call (FIRA_SMALL_GEMM=1 keeps the round-2 fragment-load kernel: A/B switch)
+// true if the coalesced tile kernel took the call
 bool gemm_tile32_try(hipStream_t s, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                      float* C, int ldc, const float* bias, int flags, int* rc, const int32_t* c_rows,
                      const float* relu_mask, const int32_t* a_rows, const EpiRes* er_in) {
@@ -566,8 +563,7 @@ bool gemm_tile32_try(hipStream_t s, int tB, int M, int N, int K, const float* A,
 bool gemm_tile32_ln_try(hipStream_t s, int M, int N, const float* S, int lds, const float* W, const float* bias, float* Y,
                         int ldy, int flags, const float* gamma, const float* beta, float* x_out, float* stats_out, int* rc) {
     if (!gemm_tile32_takes(1, M, N, FIRA_D, S, lds, W, FIRA_D)) return false;
-    static const bool off = [] { const char* e = getenv("FIRA_LN_PROLOGUE"); return e && e[0] == '0'; }();     // A/B switch
-    if (off || ((uintptr_t)gamma % 16) || ((uintptr_t)beta % 16) || ((uintptr_t)x_out % 16)) return false;
+    if (((uintptr_t)gamma % 16) || ((uintptr_t)beta % 16) || ((uintptr_t)x_out % 16)) return false;
     ProfScope prof(s, PROF_GEMM, 2.0 * M * N * (double)FIRA_D, 4.0 * ((double)M * FIRA_D + (double)N * FIRA_D + (double)M * N));
     const int tiles_n = cdiv(N, 32);
     LnA ln;
@@ -587,8 +583,7 @@ int gemm_tile32_lnb_blocks(int M) { return cdiv(M, 32); }
 bool gemm_tile32_lnb_try(hipStream_t s, int M, int N, const float* dy, const float* W, int ldw, float* dX, int lddx,
                          const float* relu_mask, const float* sum, const float* stats, const float* gamma, float* ds,
                          float* dx_drop, float* part, float dropout, uint64_t seed, uint32_t site, int* rc, uint32_t idx0) {
-    static const bool off = [] { const char* e = getenv("FIRA_LN_BWD_PROLOGUE"); return e && e[0] == '0'; }();     // A/B switch
-    if (off || !gemm_tile32_takes(0, M, N, FIRA_D, dy, FIRA_D, W, ldw)) return false;
+    if (!gemm_tile32_takes(0, M, N, FIRA_D, dy, FIRA_D, W, ldw)) return false;
     if (((uintptr_t)sum % 16) || ((uintptr_t)gamma % 16) || ((uintptr_t)ds % 16) || ((uintptr_t)dx_drop % 16) || ds == dy) return false;
     ProfScope prof(s, PROF_GEMM, 2.0 * M * N * (double)FIRA_D, 4.0 * ((double)M * FIRA_D + (double)N * FIRA_D + (double)M * N));
     const int tiles_n = cdiv(N, 32);
@@ -728,19 +723,13 @@ bool gemm_small_try(hipStream_t s, int tA, int tB, int M, int N, int K, const fl
                     float* C, int ldc, const float* bias, int flags, int* rc, const int32_t* c_rows,
                     const float* relu_mask) {
     *rc = 0;
-    // A/B switch: 0 = decode-sized products only, 1 = the round-2 fragment-load kernel, 2 (default) = coalesced tile kernel
-    static const int mode = [] { const char* e = getenv("FIRA_SMALL_GEMM"); return e ? atoi(e) : 2; }();
-    if (mode == 0 && M > 64) return false;          // 0: only the decode-sized products (M <= 64) stay here
     // beyond ~4 rounds of 32x32 tiles the LDS-tiled kernel's operand reuse wins; M <= 64 (decode) always lands here
+    constexpr long max_tiles = 1024;
     const long tiles = (long)cdiv(M, 32) * cdiv(N, 32);
-    // the coalesced tile kernel keeps winning for more rounds of tiles than the fragment-load one did (FIRA_SMALL_TILES: A/B)
-    static const long max_tiles = [] { const char* e = getenv("FIRA_SMALL_TILES"); return e ? atol(e) : 1024L; }();
-    if (!tA && mode != 1 && M > 64 && tiles > 1024 && tiles <= max_tiles) {
-        if (gemm_tile32_try(s, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, rc, c_rows, relu_mask, nullptr, nullptr)) return true;
-    }
-    if (tA || (M > 64 && tiles > 1024) || K % 32 != 0 || K < 64 || lda % 4 != 0 || ((uintptr_t)A % 16) != 0) return false;
+    if (tA || (M > 64 && tiles > max_tiles) || K % 32 != 0 || K < 64 || lda % 4 != 0 || ((uintptr_t)A % 16) != 0) return false;
     if (tB && (ldb % 4 != 0 || ((uintptr_t)B % 16) != 0)) return false;
-    if (mode != 1 && gemm_tile32_try(s, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, rc, c_rows, relu_mask, nullptr, nullptr))
+    // the coalesced tile kernel (round 3), or the round-2 fragment-load kernel where that one refuses the shape
+    if (gemm_tile32_try(s, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, rc, c_rows, relu_mask, nullptr, nullptr))
         return true;
     dim3 grid(cdiv(N, 32), cdiv(M, 32));
     if (tB) hipLaunchKernelGGL(gemm_small_kernel<true>, grid, dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, c_rows, relu_mask);

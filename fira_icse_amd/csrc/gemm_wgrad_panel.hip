@@ -305,14 +305,10 @@ struct PanelBuilder {
 };
 static PanelBuilder& panel() { static thread_local PanelBuilder b; return b; }
 
-bool gemm_wgrad_panel_on() {
-    static const bool off = [] { const char* e = getenv("FIRA_WGRAD_PANEL"); return e && e[0] == '0'; }();   // A/B switch
-    return !off;
-}
 // shapes the kernel takes: at least one full 32-row MFMA tile of output rows, whole 256-column tiles of B, 8-byte aligned
 // column pairs, a result the 31-bit byte offsets of the epilogue reach
 bool gemm_wgrad_panel_takes(int M, int N, int K, const float* A, int lda, const float* B, int ldb, int ldc) {
-    return gemm_wgrad_panel_on() && M >= 32 && N >= PN_T && N % PN_T == 0 && K >= 1 && lda % 2 == 0 && ldb % 2 == 0 &&
+    return M >= 32 && N >= PN_T && N % PN_T == 0 && K >= 1 && lda % 2 == 0 && ldb % 2 == 0 &&
            ((uintptr_t)A % 8) == 0 && ((uintptr_t)B % 8) == 0 && (long)K * lda * 4 < 0x7fffffffL && (long)K * ldb * 4 < 0x7fffffffL &&
            epilogue_fits(M, ldc);
 }
@@ -341,7 +337,7 @@ int gemm_wgrad_panel_flush(hipStream_t s, int np) {
     // Slab length: the launch's reduction rows spread over about one workgroup per CU (a slab is a multiple of 16 rows and at
     // least 256 of them: every slab of a split problem costs a 256 KB partial tile written and read once more); a launch
     // with many tiles (the vocabulary projection: 97) is not split at all.
-    static const int target_wgs = [] { const char* e = getenv("FIRA_WGRAD_PANEL_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
+    constexpr int target_wgs = 256;
     double work = 0, flop = 0, bytes = 0;
     for (int i = 0; i < t.n; ++i) {
         const PanelProblem& q = t.p[i];

@@ -339,10 +339,9 @@ int csr_spmm_ex(hipStream_t s, int n_rows, const int32_t* rowptr, const int32_t*
                            rowptr, col, val, X, ldx, Y, ldy);
     } else {
         // grid rounded up to a multiple of 8 so that the XCD remap above is a bijection onto the row groups
-        // FIRA_SPMM_ROWBATCH=0: the round-1 kernel, one row per wave (A/B switch); also for feature matrices of 2 GiB and more
-        // (the batched kernel addresses X through a buffer descriptor)
-        static const bool batch_off = [] { const char* e = getenv("FIRA_SPMM_ROWBATCH"); return e && e[0] == '0'; }();
-        if (variant != 5 && !batch_off && (size_t)n_rows * ldx * 4 < (1ull << 31))
+        // the round-1 kernel, one row per wave, for variant 5 and for feature matrices of 2 GiB and more (the batched kernel
+        // addresses X through a buffer descriptor)
+        if (variant != 5 && (size_t)n_rows * ldx * 4 < (1ull << 31))
         {
             const dim3 grid(cdiv(cdiv(n_rows, 16), 8) * 8);
             if (accum) hipLaunchKernelGGL(spmm_rowbatch_kernel<true>, grid, dim3(256), 0, s, n_rows, rowptr, col, val, X, ldx, Y, ldy, rowsum);

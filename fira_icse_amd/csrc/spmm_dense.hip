@@ -308,10 +308,10 @@ static int raise_lds(K kernel, bool* done) {
     return 0;
 }
 
-// bf16 != 0: bf16 operands (fp32 accumulate); otherwise fp32 MFMA.  Shape of the workgroup (FIRA_SPMM_DENSE_SHAPE, A/B):
-//   0 (default) = 128-row (bf16) / 64-row (fp32) slices, 8 waves, one workgroup per CU (H re-read from L2 4x / 8x per
-//   graph); 1 = 64 / 32 rows, 4 waves, two workgroups per CU (8x / 16x; graphs of <= 64 / 32 rows always take this form).
-// Measured (profiles/r3_spmm_crossover.md): shape 0 is 5-10 % ahead.  Tried and dropped: deeper rings of H chunks (3-4
+// bf16 != 0: bf16 operands (fp32 accumulate); otherwise fp32 MFMA.  Shape of the workgroup: 128-row (bf16) / 64-row (fp32)
+// slices, 8 waves, one workgroup per CU (H re-read from L2 4x / 8x per graph); graphs of <= 64 / 32 rows take 64 / 32 rows,
+// 4 waves, two workgroups per CU (8x / 16x).  Measured (profiles/r3_spmm_crossover.md): the large shape is 5-10 % ahead of
+// the small one on larger graphs.  Tried and dropped: deeper rings of H chunks (3-4
 // in flight: no gain, the bf16 form spills), and a 16-byte-access form (lane j of column tile t = column 4j + t, so one
 // float4 load feeds four column tiles and the stores are 16 bytes wide: 4 waves at one per SIMD -- 20-40 % SLOWER).
 int csr_spmm_dense(hipStream_t s, int n_rows, const int32_t* rowptr, const int32_t* col, const float* val, const float* X,
@@ -321,9 +321,8 @@ int csr_spmm_dense(hipStream_t s, int n_rows, const int32_t* rowptr, const int32
                  "csr_spmm: the block-dense variants need rows-per-graph (%d) <= 512 dividing n_rows", graph_rows);
     FIRA_REQUIRE(ldx >= FIRA_D && ldy >= FIRA_D && (long)graph_rows * ldx * 4 < (1L << 31) && (long)graph_rows * ldy * 4 < (1L << 31),
                  "csr_spmm: bad leading dimensions");
-    static const int shape = [] { const char* e = getenv("FIRA_SPMM_DENSE_SHAPE"); return e ? atoi(e) : 0; }();
     const int KP = cdiv(graph_rows, 64) * 64;
-    const bool big = shape == 0 && graph_rows > (bf16 ? 64 : 32);
+    const bool big = graph_rows > (bf16 ? 64 : 32);
     const int R = bf16 ? (big ? 128 : 64) : (big ? 64 : 32);
     const int nrb = cdiv(graph_rows, R);
     const int n_items = (n_rows / graph_rows) * nrb;

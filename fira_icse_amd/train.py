@@ -40,13 +40,13 @@ class Trainer:
             self.g_sh = [torch.zeros(c, dtype=torch.float32, device=dev) for c in chunks]
             self.zstream = torch.cuda.Stream()
             self.end_event = torch.cuda.Event()
-        # one library call per step (fira_train_step: the head + decoder slice of the update beside the last weight gradients);
-        # FIRA_FUSED_STEP=0 = fira_train_fwd_bwd + one Adam launch over [0, live) (A/B switch; identical results)
-        fused_on = os.environ.get("FIRA_FUSED_STEP", "1") != "0"
-        self.fused_step = (not distributed) and fused_on and _lib.has_symbol("fira_train_step")
+        # one library call per step (fira_train_step: the head + decoder slice of the update beside the last weight gradients;
+        # round 5: +0.9 % against fira_train_fwd_bwd + one Adam launch over [0, live), identical results)
+        self.fused_step = not distributed
         # data parallel (round 6): the same schedule as two calls with the collectives in between (fira_train_step_begin / _end:
-        # Adam of [0, split) inside the library, beside its last weight gradients, behind the early bucket's event)
-        self.fused_dp = distributed and not zero1 and fused_on and _lib.has_symbol("fira_train_step_begin")
+        # Adam of [0, split) inside the library, beside its last weight gradients, behind the early bucket's event).  ZeRO-1
+        # keeps fira_train_fwd_bwd: its optimizer runs on the owned shards after the reduce-scatter.
+        self.fused_dp = distributed and not zero1
         self.t = 0
         # row-sparse Adam of the two vocabulary-sized embedding tables (fira_train_step_rows, round 6): the rows a batch did
         # not touch are updated lazily, bit for bit (include/fira_hip.h); FIRA_ADAM_ROWS=0 = every row every step (A/B switch).
@@ -55,7 +55,7 @@ class Trainer:
         self._rows_dirty = False
         self._rows_hyper = None
         if (self.fused_step or self.fused_dp) and os.environ.get("FIRA_ADAM_ROWS", "1") != "0" \
-                and _lib.has_symbol("fira_train_step_end_rows") and model.cfg.embedding_dim == 256:
+                and model.cfg.embedding_dim == 256:
             model.sync_params()                                  # (an earlier trainer of this model may still owe rows)
             self.row_step = torch.zeros(2 * model.cfg.vocab_size, dtype=torch.int32, device=model.gbuf.device)
             model._rows_sync = self.sync

@@ -1,6 +1,6 @@
 """Search loops alone (no training): greedy batch 64 and beam-3 batch 20 on freshly initialised weights (every hypothesis
-runs all 29 steps), a few repetitions each; prints ms per batch / per step.  Used for A/B switches (FIRA_DECODE_ATTN, ...)
-and as the command of the decode rocprofv3 trace."""
+runs all 29 steps), a few repetitions each; prints ms per batch / per step.  Used for A/B timing of two builds of the same
+ABI (FIRA_HIP_LIB) and as the command of the decode rocprofv3 trace."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -2,7 +2,7 @@
 reads the previous product's output, 40 of them are captured into a hipGraph (no host launch cost) and replayed; the
 figure is microseconds per product including the kernel boundary.  Checked against an fp64 product first.
 
-    python scripts/gemm_chain.py [f32|bf16]        (FIRA_SMALL_GEMM=1 selects the round-2 fragment-load kernel)
+    python scripts/gemm_chain.py [f32|bf16]
 """
 import os
 import sys

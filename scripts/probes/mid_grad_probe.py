@@ -1,5 +1,5 @@
-"""Gradients of train_fwd_bwd with and without a mid event, per tensor (the decoder's weight gradients go out per 3 layers or in
-one launch behind the loop depending on it: FIRA_DEC_WGRAD_DP)."""
+"""Gradients of train_fwd_bwd with and without a mid event, per tensor (the mid event moves the early bucket's hand-off, not
+the decoder's weight-gradient launches: both runs issue them per 3 layers)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -57,7 +57,7 @@ def test_gemm_layouts(M, N, K, layout):
 @pytest.mark.parametrize("layout", ["nt", "nn"])
 def test_gemm_long_reduction_on_a_small_grid(M, N, K, layout):
     """The 32x32 tile kernel with 8 / 12 / 16 waves per workgroup (two K chunks per wave: gemm_small.hip, round 5) -- the
-    FFN-shaped products of the decoder chain and of the decode step; FIRA_TILE32_WAVES=0 restores four waves."""
+    FFN-shaped products of the decoder chain and of the decode step."""
     from fira_icse_amd import ops
     tB = layout == "nt"
     A = randn(M, K, seed=11)
