@@ -48,8 +48,9 @@ __device__ __forceinline__ void store_elem(char* p, float v, uint16_t) {
 // 64 entries per row, every lane of every slot a buffer load (lanes without an entry carry the descriptor's out-of-range
 // offset: no request, no branch), one round trip for the slice.  A slot is then one row's entries in lane order, so the row is
 // known (no search) and the neighbour's column is the adjacent lane's (wave_shl / wave_shr DPP).  Fast path of a slot -- no
-// entry has an equal successor (one compare + ballot) -- every entry stores its value; otherwise the LAST entry of a run of
-// equal columns (sorted rows) stores the run's sum, the earlier ones walked back in global memory.  Rows longer than the
+// entry has an equal successor and lane 0 does not continue a run of the previous slot (one compare each + ballot) -- every
+// entry stores its value; otherwise the LAST entry of a run of equal columns (sorted rows) stores the run's sum, the earlier
+// ones walked back in global memory.  Rows longer than the
 // slots finish in a tail loop.  (Round 5's form -- threads striding over the whole slice, eight entries in flight, the row
 // found by walking the LDS copy of the row offsets, the predecessor's column by a dependent load -- cost 35 us of the bf16
 // launch's 82 on config 5; a per-entry search over the wave's 16 row boundaries, 16.5 us per 128-row slice: this form is
@@ -95,11 +96,12 @@ __device__ __forceinline__ void densify_rows(char* tile, int* sm_rp, int pitch, 
             int cn = __builtin_amdgcn_update_dpp(nx0, c, 0x130, 0xf, 0xf, false);          // wave_shl:1: lane i <- lane i + 1
             const int e = rb + sl * 64 + lane;
             const bool more = sl + 1 == DN_SLOTS && rb + DN_SLOTS * 64 < re;               // (wave-uniform)
-            if (__ballot(e + 1 < re && cn == c) == 0ull && !more) {
+            const int pv0 = sl > 0 ? __builtin_amdgcn_readlane(pc[rr][sl > 0 ? sl - 1 : 0], 63) - row0 : -2;
+            // (lane 0 continuing the previous slot's last run: that lane 63 stored nothing, lane 0 must walk the run back)
+            if (__ballot((e + 1 < re && cn == c) || (sl > 0 && lane == 0 && pv0 == c)) == 0ull && !more) {
                 if (e < re && (unsigned)c < (unsigned)graph_rows) store_elem(rowp + (size_t)c * sizeof(T), pv[rr][sl], T());
                 continue;
             }
-            const int pv0 = sl > 0 ? __builtin_amdgcn_readlane(pc[rr][sl > 0 ? sl - 1 : 0], 63) - row0 : -2;
             const int cp = __builtin_amdgcn_update_dpp(pv0, c, 0x138, 0xf, 0xf, false);    // wave_shr:1: lane i <- lane i - 1
             if (more && lane == 63) cn = col[e + 1] - row0;
             if (e >= re || (e + 1 < re && cn == c) || (unsigned)c >= (unsigned)graph_rows) continue;

@@ -376,27 +376,41 @@ def test_block_dense_spmm_sums_repeated_columns():
 
 
 def test_block_dense_spmm_long_rows_with_runs_across_slot_boundaries():
-    """densify_rows requests a row's entries in slots of 64 (three per row, then a tail loop): rows of ~330 entries whose runs
-    of equal columns straddle entry 63|64, 127|128, 191|192 (the last slot's successor comes from memory) and sit in the tail."""
+    """densify_rows requests a row's entries in slots of 64 (three per row, then a tail loop).  Rows of ~330 entries hold
+    runs of equal columns at 62|63, 63|64, 126|127, 127|128, 190|191, 191|192 (the last slot's successor comes from memory)
+    and in the tail; those rows have several runs per slot, so every slot takes the slow path.  Rows of 151 distinct
+    columns whose ONLY run is 63|64 or 127|128 make the next slot's fast path meet lane 0 continuing a run."""
     from fira_icse_amd import ops
     N, B = 512, 2
     rng = np.random.default_rng(11)
     rowptr, col, val = [0], [], []
     dense = np.zeros((B, N, N), dtype=np.float64)
+    tile = np.zeros((B, N, N), dtype=np.float32)                           # what densify_rows stores: fp32 run sums
     for g in range(B):
         for r in range(N):
             n = 40 if r % 3 == 0 else 330                                  # short rows between the long ones
             cs = sorted(rng.choice(N, size=n, replace=False).tolist())
-            for pos in (62, 63, 126, 127, 190, 191, 192, 255, 256, 300):   # duplicate the entry AT pos: a run across pos | pos + 1
-                if pos < len(cs):
-                    cs.insert(pos + 1, cs[pos])
-            if r % 5 == 0 and len(cs) > 66:
-                cs[61:66] = [cs[61]] * 5                                   # a run of five over the first slot boundary
-                cs.sort()
-            for c in cs:
-                v = float(np.float32(rng.uniform(0.1, 1.0)))
-                dense[g, r, c] += v
-                col.append(g * N + c); val.append(v)
+            if n == 330 and r % 7 in (1, 2):                               # a lone pair at 63|64 or 127|128
+                cs = cs[:150]
+                pos = 63 if r % 7 == 1 else 127
+                cs.insert(pos + 1, cs[pos])
+            else:
+                for pos in (62, 63, 126, 127, 190, 191, 192, 255, 256, 300):   # duplicate the entry AT pos: a run across pos | pos + 1
+                    if pos < len(cs):
+                        cs.insert(pos + 1, cs[pos])
+                if r % 5 == 0 and len(cs) > 66:
+                    cs[61:66] = [cs[61]] * 5                               # a run of five over the first slot boundary
+                    cs.sort()
+            vs = [np.float32(rng.uniform(0.1, 1.0)) for _ in cs]
+            for i, (c, v) in enumerate(zip(cs, vs)):
+                dense[g, r, c] += float(v)
+                col.append(g * N + c); val.append(float(v))
+                if i + 1 == len(cs) or cs[i + 1] != c:                     # last entry of its run: the sum back to the first
+                    s, k = v, i - 1
+                    while k >= 0 and cs[k] == c:
+                        s = np.float32(s + vs[k])
+                        k -= 1
+                    tile[g, r, c] = s
             rowptr.append(len(col))
     t = lambda a, dt: torch.tensor(np.array(a, dtype=dt), device=DEV)
     X = randn(B * N, 256, seed=4)
@@ -405,9 +419,11 @@ def test_block_dense_spmm_long_rows_with_runs_across_slot_boundaries():
     Y = ops.csr_spmm(t(rowptr, np.int32), t(col, np.int32), t(val, np.float32), X, graph_rows=N, variant=3)
     assert rel_err(Y, ref) < 1e-6
     Yb = ops.csr_spmm(t(rowptr, np.int32), t(col, np.int32), t(val, np.float32), X, graph_rows=N, variant=4)
-    # the tile holds the bf16 rounding of the fp32 SUM of a run (summed last-to-first in fp32)
-    ref_b = torch.bmm(dn.float().bfloat16().double(), X.bfloat16().view(B, N, 256).double()).view(B * N, 256)
-    assert rel_err(Yb, ref_b) < 2e-4                                       # (a run's fp32 sum order may round the bf16 differently)
+    # the tile holds the bf16 rounding of the fp32 SUM of a run (summed last-to-first in fp32): exact products of the rounded
+    # operands, fp32 accumulation only
+    tb = torch.from_numpy(tile).bfloat16().double().to(DEV)
+    ref_b = torch.bmm(tb, X.bfloat16().view(B, N, 256).double()).view(B * N, 256)
+    assert rel_err(Yb, ref_b) < 2e-6
     assert rel_err(Yb, ref) < 6e-3
 
 
