@@ -11,6 +11,7 @@
 #include "adam_rows.h"
 #include <stdlib.h>
 #include "epilogue.h"
+#include "decode_row.h"
 
 namespace fira {
 
@@ -771,32 +772,6 @@ __global__ __launch_bounds__(256) void decode_dist_reg_kernel(int V, int S, cons
 // with 256 threads each a CU ran one wave per SIMD behind 100 dependent-latency loads), the row's logits requested once
 // and kept in registers (25 per thread), and the 2-way gate LinearProb(x) formed here from the decoder row instead of
 // by its own [64 x 2 x 256] product launch.  First-occurrence arg-max as torch.argmax.
-constexpr int DDW_NT = 1024, DDW_NPT = 25;
-__device__ __forceinline__ float block16_sum(float v, float* sm) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < DDW_NT / 64; ++k) t += sm[k];
-    return t;
-}
-__device__ __forceinline__ void block16_argmax(float& v, int& idx, float* smv, int* smi) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { smv[threadIdx.x >> 6] = v; smi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    v = smv[0]; idx = smi[0];
-#pragma unroll
-    for (int k = 1; k < DDW_NT / 64; ++k)
-        if (smv[k] > v || (smv[k] == v && smi[k] < idx)) { v = smv[k]; idx = smi[k]; }
-}
 __global__ __launch_bounds__(DDW_NT) void decode_dist_wide_kernel(int V, int S, const float* __restrict__ logits, int ldl,
                                                                   const float* __restrict__ score,
                                                                   const int32_t* __restrict__ mem_valid, int qpk,

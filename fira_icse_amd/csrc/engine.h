@@ -285,6 +285,12 @@ int decode_dist(hipStream_t s, int R, int V, int S, const float* logits, int ldl
                 const int32_t* mem_valid, int qpk, const float* gate_logits, float* dist, int32_t* best_id,
                 float* best_p, const float* x = nullptr, const float* wp = nullptr, const float* bp = nullptr);
 int inv_count(hipStream_t s, const int32_t* n_tok, float* out);
+// sample.hip: the same distribution row as decode_dist (inline gate form, bit-identical dist), then temperature / top-k / top-p
+// and a Gumbel-max draw per (commit, sample) row; best_id / best_p as decode_dist writes them (see fira_decode_step_sample)
+int sample_dist(hipStream_t s, int R, int n_sample, int V, int S, const float* logits, int ldl, const float* score,
+                const int32_t* mem_valid, const float* x, const float* wp, const float* bp, int T, int step,
+                const int32_t* key, const uint64_t* seed_dev, float temperature, int top_k, float top_p, float* dist,
+                int32_t* best_id, float* best_p);
 // ids / vals [R, k]: the k largest entries of every logits row, value descending, ties by ascending index (beam.hip; k <= 8)
 int row_topk(hipStream_t s, int R, int V, int k, const float* logits, int ldl, int32_t* ids, float* vals);
 int copy_score_bwd(hipStream_t s, int B, int T, int S, const float* src, const float* tgt, const float* w,

@@ -2120,24 +2120,30 @@ int fira_decode_step(void* stream, const fira_dims* d, const float* params, void
     return fira_decode_step_ex(stream, d, params, workspace, workspace_bytes, B, n_beam, step, tokens, parent, dist, best_id,
                                best_p, 0);
 }
-int fira_decode_step_ex(void* stream, const fira_dims* d, const float* params, void* workspace, size_t workspace_bytes,
-                        int B, int n_beam, int step, const int32_t* tokens, const int32_t* parent, float* dist,
-                        int32_t* best_id, float* best_p, int flags) {
+}  // extern "C"
+
+namespace fira {
+// The decoder part of one decode step (everything but the distribution kernel at its end): leaves the step's logits, copy
+// scores and final decoder rows in `dp`.  `beams`: the rows are beam hypotheses whose self-attention cache is parity-indexed
+// and re-ordered by `parent` (fira_decode_step); otherwise (fira_decode_step_sample) a row never changes its parent and
+// every step reads and appends the cache of parity 0, as beam 1 does.
+static int decode_step_body(hipStream_t s, const fira_dims* d, const float* params, void* workspace, size_t workspace_bytes,
+                            int B, int n_beam, int step, const int32_t* tokens, const int32_t* parent, int flags, bool beams,
+                            const char* who, DecodePlan& dp) {
     const Layout* Lp = get_layout(d);
     if (!Lp) return 1;
     const Layout& L = *Lp;
     FIRA_REQUIRE(params && workspace && tokens && B > 0 && n_beam >= 1, "bad argument");
     FIRA_REQUIRE(step >= 0 && step < d->tar_len, "step %d out of range", step);
-    FIRA_REQUIRE((flags & ~FIRA_DECODE_KV_BF16) == 0, "fira_decode_step_ex: unknown flags %d", flags);
-    DecodePlan dp;
+    FIRA_REQUIRE((flags & ~FIRA_DECODE_KV_BF16) == 0, "%s: unknown flags %d", who, flags);
     const size_t need = dp.build(workspace, *d, B, n_beam, flags);
     FIRA_REQUIRE(need <= workspace_bytes, "workspace too small: need %zu bytes, got %zu (fira_decode_workspace_bytes_ex with the same flags)",
                  need, workspace_bytes);
     Plan& p = dp.enc;
-    hipStream_t s = (hipStream_t)stream;
     const int D = FIRA_D, H = d->n_head, T = p.T, KV = p.nl * 2 * D, Sm = p.L + p.S, BR = dp.BR;
-    const int cur = n_beam > 1 ? (step & 1) : 0, prev = n_beam > 1 ? ((step + 1) & 1) : 0;
-    if (n_beam > 1 && step > 0)
+    const bool parity = beams && n_beam > 1;
+    const int cur = parity ? (step & 1) : 0, prev = parity ? ((step + 1) & 1) : 0;
+    if (parity && step > 0)
         TRY(permute_cache(s, p.nl, BR, T, step, parent, dp.kc[prev], dp.vc[prev], dp.kc[cur], dp.vc[cur], dp.hist[prev],
                           dp.hist[cur]));
     // key-valid history of this step + token embedding + position `step` (gnn_transformer.py:110-113): one launch
@@ -2207,9 +2213,45 @@ int fira_decode_step_ex(void* stream, const fira_dims* d, const float* params, v
     TRY(consume(D, dp.x, params + L.wt, nullptr, dp.tgt, 0));      // LinearTarget(LN(..)) [+ x materialised]
     TRY(linear(s, BR, p.V, D, dp.x, D, params + L.wout, params + L.bout, dp.logits, p.ldl));
     TRY(copy_score_fwd_ex(s, BR, 1, Sm, p.src, dp.tgt, params + L.wres, params + L.bres, dp.score, n_beam, p.mem_valid));
+    return 0;
+}
+}  // namespace fira
+
+extern "C" {
+int fira_decode_step_ex(void* stream, const fira_dims* d, const float* params, void* workspace, size_t workspace_bytes,
+                        int B, int n_beam, int step, const int32_t* tokens, const int32_t* parent, float* dist,
+                        int32_t* best_id, float* best_p, int flags) {
+    hipStream_t s = (hipStream_t)stream;
+    DecodePlan dp;
+    TRY(decode_step_body(s, d, params, workspace, workspace_bytes, B, n_beam, step, tokens, parent, flags, true,
+                         "fira_decode_step_ex", dp));
+    const Layout& L = *get_layout(d);
+    const Plan& p = dp.enc;
     // the 2-way gate LinearProb(x) is formed inside the distribution kernel
-    TRY(decode_dist(s, BR, p.V, Sm, dp.logits, p.ldl, dp.score, p.mem_valid, n_beam, nullptr, dist, best_id, best_p, dp.x,
-                    params + L.wp, params + L.bp));
+    TRY(decode_dist(s, dp.BR, p.V, p.L + p.S, dp.logits, p.ldl, dp.score, p.mem_valid, n_beam, nullptr, dist, best_id, best_p,
+                    dp.x, params + L.wp, params + L.bp));
+    return 0;
+}
+int fira_decode_step_sample(void* stream, const fira_dims* d, const float* params, void* workspace, size_t workspace_bytes,
+                            int B, int n_sample, int step, const int32_t* tokens, const int32_t* key, const uint64_t* seed_dev,
+                            float temperature, int top_k, float top_p, float* dist, int32_t* best_id, float* best_p,
+                            int flags) {
+    FIRA_REQUIRE(d, "fira_decode_step_sample: bad argument");
+    FIRA_REQUIRE(n_sample >= 1 && n_sample <= 8, "fira_decode_step_sample: n_sample %d outside 1..8", n_sample);
+    FIRA_REQUIRE(temperature > 0.f && temperature < INFINITY, "fira_decode_step_sample: temperature %g must be finite and > 0",
+                 (double)temperature);
+    const int W = d->vocab + d->sou_len + d->sub_len;
+    FIRA_REQUIRE(top_k >= 0 && top_k <= W, "fira_decode_step_sample: top_k %d outside 0..%d", top_k, W);
+    FIRA_REQUIRE(top_p > 0.f && top_p <= 1.f, "fira_decode_step_sample: top_p %g outside (0, 1]", (double)top_p);
+    FIRA_REQUIRE(key && seed_dev && best_id && best_p, "fira_decode_step_sample: key, seed_dev, best_id and best_p are required");
+    hipStream_t s = (hipStream_t)stream;
+    DecodePlan dp;
+    TRY(decode_step_body(s, d, params, workspace, workspace_bytes, B, n_sample, step, tokens, nullptr, flags, false,
+                         "fira_decode_step_sample", dp));
+    const Layout& L = *get_layout(d);
+    const Plan& p = dp.enc;
+    TRY(sample_dist(s, dp.BR, n_sample, p.V, p.L + p.S, dp.logits, p.ldl, dp.score, p.mem_valid, dp.x, params + L.wp,
+                    params + L.bp, p.T, step, key, seed_dev, temperature, top_k, top_p, dist, best_id, best_p));
     return 0;
 }
 

@@ -233,6 +233,94 @@ class Searcher:
             main.wait_stream(stream)
         return results
 
+    # ------------------------------------------------------------------ sampling: temperature / top-k / top-p, n per commit
+    def _sample_state(self, B, n, temperature, top_k, top_p):
+        """Static device buffers + captured hipGraphs of the sampling loop; the filters are fixed in the captured launches,
+        so they are part of the key.  The seed is a device scalar read at run time: one capture serves every seed."""
+        key = ("sample", B, n, float(temperature), int(top_k), float(top_p))
+        if key in self._ws:
+            return self._ws[key]
+        cfg, dev = self.cfg, self.model.device_
+        R, T = B * n, cfg.tar_len
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        st = dict(sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), key=i32(B),
+                  seed=torch.zeros(1, dtype=torch.int64, device=dev), out=i32(R, T), length=i32(R), prob=f32(R), logp=f32(R),
+                  alive=i32(R), tok=i32(R), n_alive=i32(T), best_id=i32(R), best_p=f32(R), graphs=None)
+        self._ws[key] = st
+        return st
+
+    def _sample_reset(self, st):
+        self._greedy_reset(st)
+        st["logp"].zero_()
+
+    def _sample_steps(self, st, ws, B, n, lo, hi, temperature, top_k, top_p):
+        """Steps lo..hi-1: the KV-cached decoder step with the sampling kernel in place of the arg-max, then the bookkeeping
+        of greedy search over the B * n rows (plus the log-probability sum); no torch op, no host round trip."""
+        lib, s = _lib.lib(), _lib.cur_stream()
+        for step in range(lo, hi):
+            _lib.check(lib.fira_decode_step_sample(s, C.byref(self.model.dims), _lib.ptr(self.model.flat.data), _lib.ptr(ws),
+                                                   ws.numel(), B, n, step, _lib.ptr(st["tok"]), _lib.ptr(st["key"]),
+                                                   _lib.ptr(st["seed"]), float(temperature), int(top_k), float(top_p), None,
+                                                   _lib.ptr(st["best_id"]), _lib.ptr(st["best_p"]), self.flags),
+                       "fira_decode_step_sample")
+            _lib.check(lib.fira_sample_advance(s, C.byref(self.model.dims), B, n, step, _lib.ptr(st["best_id"]),
+                                               _lib.ptr(st["best_p"]), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]),
+                                               _lib.ptr(st["out"]), _lib.ptr(st["length"]), _lib.ptr(st["prob"]),
+                                               _lib.ptr(st["logp"]), _lib.ptr(st["alive"]), _lib.ptr(st["tok"]),
+                                               _lib.ptr(st["n_alive"])), "fira_sample_advance")
+
+    @torch.no_grad()
+    def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+               keys=None, chunk: int = 5, use_graphs: bool = True):
+        """``n`` sampled messages per commit.  Returns (tokens [B,n,T] int64 starting with <start>, lengths [B,n],
+        probability [B,n], log-probability [B,n]); the probabilities are the model's (untempered, unfiltered) ones of the
+        emitted ids.
+
+        Filters in the order of HF ``generate``: temperature, then top-k (``0`` = off), then top-p (``1`` = off); the draw is a
+        Gumbel-max over the kept entries with counter-hash noise of (``seed``, ``keys[b]``, sample, step, entry), so a commit's
+        samples depend on its key (default: its row in the batch), not on the batch it lands in.  The step loop is captured
+        into hipGraphs per (B, n, temperature, top_k, top_p) like ``greedy``, with the same early stop between chunks."""
+        cfg = self.cfg
+        B, T = db.B, cfg.tar_len
+        ws = self._begin(db, n)
+        st = self._sample_state(B, n, temperature, top_k, top_p)
+        st["sou"].copy_(db.sou)
+        st["sub"].copy_(db.sub_token)
+        keys = torch.arange(B) if keys is None else torch.as_tensor(keys)
+        if keys.numel() != B:
+            raise ValueError("keys: %d values for a batch of %d commits" % (keys.numel(), B))
+        st["key"].copy_(keys.reshape(B).to(torch.int32))
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)     # the uint64 bits in an int64 tensor
+        self._sample_reset(st)
+        bounds = [(lo, min(lo + chunk, T - 1)) for lo in range(0, T - 1, chunk)]
+        run = lambda lo, hi: self._sample_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p)
+        if use_graphs and st["graphs"] is None:
+            run(0, 1)                                          # warm-up outside capture
+            torch.cuda.synchronize()
+            graphs = []
+            for lo, hi in bounds:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    run(lo, hi)
+                graphs.append(g)
+            st["graphs"] = graphs
+            self._sample_reset(st)
+        for i, (lo, hi) in enumerate(bounds):
+            if use_graphs:
+                st["graphs"][i].replay()
+            else:
+                run(lo, hi)
+            if hi < T - 1 and int(st["n_alive"][hi - 1].item()) == 0:     # every sample has emitted <eos>
+                break
+        return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
+                st["logp"].view(B, n).clone())
+
+    def best_sample(self, tokens, lengths, logp) -> List[List[int]]:
+        """The highest-log-probability sample per commit, first on ties."""
+        return self.best(tokens, lengths, logp)
+
     # ------------------------------------------------------------------ beam search with the reference's semantics
     def _beam_state(self, B, beam):
         key = ("beam", B, beam)

@@ -625,6 +625,31 @@ int fira_greedy_advance(void* stream, const fira_dims* d, int B, int step, const
                         const int32_t* sou, const int32_t* sub_token, int32_t* out, int32_t* length, float* prob,
                         int32_t* alive, int32_t* tokens, int32_t* n_alive);
 
+/* On-device sampling of candidate messages (temperature, top-k, top-p).  Workspace: fira_decode_begin_ex /
+ * fira_decode_workspace_bytes_ex with n_beam = n_sample (1..8) and the same flags (FIRA_DECODE_KV_BF16 allowed).
+ *   fira_decode_step_sample : fira_decode_step_ex for the B * n_sample rows (row r = commit r / n_sample, sample
+ *     r % n_sample; rows never change parent, so there is no cache permutation), then per row: the distribution p over
+ *     vocab + S entries (dist[r, :] if dist != NULL, bit-identical to fira_decode_step's), the filters -- temperature
+ *     T > 0 and finite: q ~ p^(1/T); top_k (0 = off, <= vocab + S): keep p >= the k-th largest p counted with
+ *     multiplicity; top_p (in (0, 1], 1 = off): renormalise q over what top-k kept and keep q >= the largest v whose
+ *     upper set {q >= v} holds at least top_p of the mass; ties at either threshold are kept -- and the Gumbel-max draw
+ *     best_id[r] = argmax over kept i of (log p_i / T + g_i), lowest index on ties, with the counter-hash noise
+ *       base   = mix32(key[b] ^ mix32((uint32)seed ^ mix32((uint32)(seed >> 32) + 0x632BE5AB)))
+ *       stream = mix32(base + 0x9E3779B9 * (uint32)(j * tar_len + step + 1))        (b = r / n_sample, j = r % n_sample)
+ *       u      = min(((mix32(i ^ stream) >> 8) + 0.5f) * 2^-24, largest float below 1),  g_i = -log(-log(u))
+ *     (mix32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16).  key [B] int32 per commit,
+ *     seed_dev a DEVICE uint64 read when the kernel runs (one captured graph serves every seed).  best_p[r] = p_{best_id}
+ *     (unfiltered, untempered), bit-identical to dist[r, best_id[r]].  Shapes beyond vocab 25 600 / S 1 024: error.
+ *   fira_sample_advance : fira_greedy_advance over the B * n_sample rows (copy ids resolved through commit r / n_sample)
+ *     that also adds logf(best_p[r]) to logp[r] for every id it appends.                                            */
+int fira_decode_step_sample(void* stream, const fira_dims* d, const float* params, void* workspace,
+                            size_t workspace_bytes, int B, int n_sample, int step, const int32_t* tokens,
+                            const int32_t* key, const uint64_t* seed_dev, float temperature, int top_k, float top_p,
+                            float* dist, int32_t* best_id, float* best_p, int flags);
+int fira_sample_advance(void* stream, const fira_dims* d, int B, int n_sample, int step, const int32_t* best_id,
+                        const float* best_p, const int32_t* sou, const int32_t* sub_token, int32_t* out, int32_t* length,
+                        float* prob, float* logp, int32_t* alive, int32_t* tokens, int32_t* n_alive);
+
 /* Decoder.forward over all tar_len positions on caller-supplied memory [B, sou+sub, 256] / mem_valid [B, sou+sub]
  * (gnn_transformer.py:108-122; the call of run_model.py:256).  Workspace: fira_workspace_bytes(d, B, 0).          */
 int fira_decoder_forward(void* stream, const fira_dims* d, const float* params, void* workspace,

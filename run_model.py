@@ -58,7 +58,7 @@ def parse_args(argv):
     ap.add_argument("--batch-size", type=int, default=None, help="GLOBAL train batch (reference: 170 x n_gpu)")
     ap.add_argument("--test-batch-size", type=int, default=20)
     ap.add_argument("--epochs", type=int, default=150)
-    ap.add_argument("--beam", type=int, default=3)
+    ap.add_argument("--beam", type=int, default=None, help="beam size of the test-time search (default 3; 1 with --sample)")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--dev-from-epoch", type=int, default=15)
     ap.add_argument("--dev-every", type=int, default=10)
@@ -78,7 +78,52 @@ def parse_args(argv):
                     "token normaliser stay fp32), else f32")
     ap.add_argument("--zero1", action="store_true", help="multi-GPU: reduce-scatter + Adam on the owned shard + all-gather "
                     "(Adam moments sharded over the ranks) instead of all-reduce + replicated Adam")
-    return ap.parse_args(argv)
+    ap.add_argument("--sample", type=int, default=None, metavar="N", help="test: draw N (1-8) candidate messages per commit "
+                    "on the device instead of searching; writes OUTPUT/output_fira (the candidate of highest log-probability) "
+                    "and OUTPUT/output_fira_samples (one JSON line per commit: the N candidates and their log-probabilities)")
+    ap.add_argument("--temperature", type=float, default=None, help="with --sample: temperature > 0 (default 1)")
+    ap.add_argument("--top-k", type=int, default=None, help="with --sample: keep the k most probable entries (default 0 = off)")
+    ap.add_argument("--top-p", type=float, default=None, help="with --sample: nucleus mass in (0, 1] (default 1 = off)")
+    ap.add_argument("--sample-seed", type=int, default=None, help="with --sample: seed of the sampling noise (default 0)")
+    a = ap.parse_args(argv)
+    try:
+        check_sample_args(a)
+    except ValueError as e:
+        ap.error(str(e))
+    return a
+
+
+SAMPLE_OPTIONS = (("temperature", "--temperature", 1.0), ("top_k", "--top-k", 0), ("top_p", "--top-p", 1.0),
+                  ("sample_seed", "--sample-seed", 0))
+
+
+def check_sample_args(a, vocab_size: int = None):
+    """Validates the sampling options of ``a`` in place (no GPU, no DataSet needed) and fills in their defaults; raises
+    ValueError on a conflict or an out-of-range value.  Without --sample the namespace is left as the search uses it."""
+    if a.sample is None:
+        given = [flag for name, flag, _ in SAMPLE_OPTIONS if getattr(a, name) is not None]
+        if given:
+            raise ValueError("%s only apply with --sample" % ", ".join(given))
+        if a.beam is None:
+            a.beam = 3
+        return a
+    if not 1 <= a.sample <= 8:
+        raise ValueError("--sample %d: between 1 and 8 candidates per commit" % a.sample)
+    if a.beam is not None and a.beam > 1:
+        raise ValueError("--sample draws candidates instead of searching: it does not combine with --beam %d" % a.beam)
+    a.beam = 1
+    for name, _, default in SAMPLE_OPTIONS:
+        if getattr(a, name) is None:
+            setattr(a, name, default)
+    if not (a.temperature > 0 and a.temperature < float("inf")):
+        raise ValueError("--temperature %g: must be finite and > 0" % a.temperature)
+    if a.top_k < 0 or (vocab_size is not None and a.top_k > vocab_size):
+        raise ValueError("--top-k %d: must be >= 0 (0 = off)" % a.top_k)
+    if not 0 < a.top_p <= 1:
+        raise ValueError("--top-p %g: must be in (0, 1] (1 = off)" % a.top_p)
+    if not 0 <= a.sample_seed < 1 << 64:
+        raise ValueError("--sample-seed %d: must be in [0, 2^64)" % a.sample_seed)
+    return a
 
 
 class Run:
@@ -223,12 +268,16 @@ class Run:
         from fira_icse_amd.decode import Searcher
         cfg, store = self.cfg, self.sets["test"].store
         test_index = self.all_index["test"]
+        if self.a.sample is not None:
+            check_sample_args(self.a, cfg.out_len)           # top-k against this vocabulary, before the model loads
         self.model = TransModel(cfg, device="cuda:%d" % self.local, init=False)
         self.model.load_state_dict(torch.load(os.path.join(self.root, "best_model.pt"), map_location="cpu"))
         self.model.compute_dtype = self.a.dtype
         self.model.eval()
         search = Searcher(self.model)
         mine = shard_indices(list(range(len(store))), self.rank, self.world)
+        if self.a.sample is not None:
+            return self.test_sample(search, store, mine)
         lines, n_tok, t0 = [], 0, time.time()
         # greedy: groups of `in_flight` batches share the GPU (independent launch chains: decode.Searcher.greedy_many; four lanes
         # on eight hardware queues: 0.14 ms per batch-step against 0.33 one at a time); the output order stays
@@ -253,6 +302,35 @@ class Run:
         if self.rank == 0:
             with open(self.out("output_fira"), "w") as f:
                 f.write("".join(l + "\n" for l in lines))
+        return lines
+
+    def test_sample(self, search, store, mine):
+        """--sample: N candidates per commit drawn on the device (decode.Searcher.sample); the noise of a commit is keyed by
+        its index in the test split, so its candidates do not depend on how the commits are grouped into batches."""
+        a, cfg = self.a, self.cfg
+        test_index = self.all_index["test"]
+        lines, samples, n_tok, t0 = [], [], 0, time.time()
+        for lo in range(0, len(mine), cfg.test_batch_size):
+            idx = mine[lo:lo + cfg.test_batch_size]
+            toks, lens, _, logp = search.sample(self.device_batch(store, idx), a.sample, temperature=a.temperature,
+                                                top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed, keys=idx)
+            best = search.best_sample(toks, lens, logp)
+            toks, lens, logp = toks.tolist(), lens.tolist(), logp.tolist()
+            for k, i in enumerate(idx):
+                var_map = self.var_maps[test_index[i]]
+                lines.append(text.detokenize(best[k], self.r_vocab, var_map))
+                cands = [text.detokenize(toks[k][j][:lens[k][j]], self.r_vocab, var_map) for j in range(a.sample)]
+                samples.append(json.dumps({"candidates": cands, "logp": logp[k]}))
+                n_tok += sum(max(n - 1, 0) for n in lens[k])
+            if self.rank == 0:
+                print("data: %d/%d  (%.1f tokens/s)" % (min(len(mine), lo + cfg.test_batch_size), len(mine),
+                                                        n_tok / max(time.time() - t0, 1e-9)), flush=True)
+        lines, samples = gather_lines(lines), gather_lines(samples)
+        if self.rank == 0:
+            with open(self.out("output_fira"), "w") as f:
+                f.write("".join(l + "\n" for l in lines))
+            with open(self.out("output_fira_samples"), "w") as f:
+                f.write("".join(l + "\n" for l in samples))
         return lines
 
 
