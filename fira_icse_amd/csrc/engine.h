@@ -291,6 +291,14 @@ int sample_dist(hipStream_t s, int R, int n_sample, int V, int S, const float* l
                 const int32_t* mem_valid, const float* x, const float* wp, const float* bp, int T, int step,
                 const int32_t* key, const uint64_t* seed_dev, float temperature, int top_k, float top_p, float* dist,
                 int32_t* best_id, float* best_p);
+// score.hip: the same distribution row again (bit-identical dist), then the probability of a given target word per (commit,
+// candidate) row: summed over every entry that resolves to it, its largest single entry, the copy share, an optional labelled
+// entry, the row's arg-max, and running log-probability sums (see fira_decode_step_score)
+int score_dist(hipStream_t s, int R, int n_cand, int V, int L, int S, const float* logits, int ldl, const float* score,
+               const int32_t* mem_valid, const float* x, const float* wp, const float* bp, const int32_t* target,
+               const int32_t* label, const int32_t* sou, const int32_t* sub, float* dist, float* p_word, float* p_entry,
+               int32_t* entry, float* copy_share, float* p_label, int32_t* top_id, float* logp_word, float* logp_entry,
+               float* logp_label);
 // ids / vals [R, k]: the k largest entries of every logits row, value descending, ties by ascending index (beam.hip; k <= 8)
 int row_topk(hipStream_t s, int R, int V, int k, const float* logits, int ldl, int32_t* ids, float* vals);
 int copy_score_bwd(hipStream_t s, int B, int T, int S, const float* src, const float* tgt, const float* w,

@@ -2254,6 +2254,29 @@ int fira_decode_step_sample(void* stream, const fira_dims* d, const float* param
                     params + L.bp, p.T, step, key, seed_dev, temperature, top_k, top_p, dist, best_id, best_p));
     return 0;
 }
+int fira_decode_step_score(void* stream, const fira_dims* d, const float* params, void* workspace, size_t workspace_bytes,
+                           int B, int n_cand, int step, const int32_t* tokens, const int32_t* target, const int32_t* label,
+                           const int32_t* sou, const int32_t* sub_token, float* dist, float* p_word, float* p_entry,
+                           int32_t* entry, float* copy_share, float* p_label, int32_t* top_id, float* logp_word,
+                           float* logp_entry, float* logp_label, int flags) {
+    FIRA_REQUIRE(d, "fira_decode_step_score: bad argument");
+    FIRA_REQUIRE(n_cand >= 1 && n_cand <= 8, "fira_decode_step_score: n_cand %d outside 1..8", n_cand);
+    FIRA_REQUIRE(target && sou && sub_token, "fira_decode_step_score: target, sou and sub_token are required");
+    FIRA_REQUIRE(p_word && p_entry && entry && copy_share && top_id && logp_word && logp_entry,
+                 "fira_decode_step_score: p_word, p_entry, entry, copy_share, top_id, logp_word and logp_entry are required");
+    FIRA_REQUIRE((label != nullptr) == (p_label != nullptr) && (label != nullptr) == (logp_label != nullptr),
+                 "fira_decode_step_score: label, p_label and logp_label are given together or not at all");
+    hipStream_t s = (hipStream_t)stream;
+    DecodePlan dp;
+    TRY(decode_step_body(s, d, params, workspace, workspace_bytes, B, n_cand, step, tokens, nullptr, flags, false,
+                         "fira_decode_step_score", dp));
+    const Layout& L = *get_layout(d);
+    const Plan& p = dp.enc;
+    TRY(score_dist(s, dp.BR, n_cand, p.V, p.L, p.L + p.S, dp.logits, p.ldl, dp.score, p.mem_valid, dp.x, params + L.wp,
+                   params + L.bp, target, label, sou, sub_token, dist, p_word, p_entry, entry, copy_share, p_label, top_id,
+                   logp_word, logp_entry, logp_label));
+    return 0;
+}
 
 // Decoder.forward on caller-supplied memory (the piecewise surface the reference's test loop uses:
 // model.decoder(ids, memory, mem_mask, tar_pad_mask), run_model.py:256): full 30-position recompute.

@@ -56,6 +56,23 @@ def concurrent_streams(n: int, device, pool: int = 12):
     return chosen
 
 
+class Scores(dict):
+    """Result of ``Searcher.score``: a dict whose keys also read as attributes."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+def rank_values(scores, by: str) -> torch.Tensor:
+    """The [B, n] values ``Searcher.rank`` orders candidates by (larger is better)."""
+    if by == "mean_logp_word":
+        return scores["logp_word"] / (scores["length"] - 1).clamp(min=1).to(scores["logp_word"].dtype)
+    return scores[by]
+
+
 class Searcher:
     def __init__(self, model: TransModel, kv_bf16: bool = False):
         """``kv_bf16``: stream a bf16 copy of the cross-attention K|V in the step loop (FIRA_DECODE_KV_BF16: half of the
@@ -320,6 +337,173 @@ class Searcher:
     def best_sample(self, tokens, lengths, logp) -> List[List[int]]:
         """The highest-log-probability sample per commit, first on ties."""
         return self.best(tokens, lengths, logp)
+
+    # ------------------------------------------------------------------ scoring given messages (teacher-forced)
+    SCORE_TOKEN_KEYS = ("p_word", "p_entry", "entry", "copy_share", "top_id", "p_label")
+    RANK_KEYS = ("logp_entry", "logp_word", "mean_logp_word")
+
+    def _score_state(self, B, n, labelled):
+        """Static device buffers + captured hipGraphs of the scoring loop.  Candidates, labels and per-token outputs are
+        step-major ([T, B * n]), so step t's inputs and outputs are plain rows of them."""
+        key = ("score", B, n, bool(labelled))
+        if key in self._ws:
+            return self._ws[key]
+        cfg, dev = self.cfg, self.model.device_
+        R, T = B * n, cfg.tar_len
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        st = dict(sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), cand=i32(T, R), label=i32(T, R),
+                  p_word=f32(T - 1, R), p_entry=f32(T - 1, R), entry=i32(T - 1, R), copy_share=f32(T - 1, R),
+                  p_label=f32(T - 1, R), top_id=i32(T - 1, R), logp_word=f32(R), logp_entry=f32(R), logp_label=f32(R),
+                  labelled=bool(labelled), graphs=None)
+        self._ws[key] = st
+        return st
+
+    def _score_reset(self, st):
+        for k in ("p_word", "p_entry", "copy_share", "p_label", "logp_word", "logp_entry", "logp_label"):
+            st[k].zero_()
+        st["entry"].fill_(-1)
+        st["top_id"].fill_(-1)
+
+    def _score_steps(self, st, ws, B, n, lo, hi, dist=None):
+        """Steps lo..hi-1: one library call per step -- the KV-cached decoder step fed with the candidates' own tokens and the
+        scoring kernel in place of the arg-max; no bookkeeping launch, no torch op, no host round trip."""
+        lib, s = _lib.lib(), _lib.cur_stream()
+        lab = st["labelled"]
+        for step in range(lo, hi):
+            _lib.check(lib.fira_decode_step_score(
+                s, C.byref(self.model.dims), _lib.ptr(self.model.flat.data), _lib.ptr(ws), ws.numel(), B, n, step,
+                _lib.ptr(st["cand"][step]), _lib.ptr(st["cand"][step + 1]), _lib.ptr(st["label"][step + 1]) if lab else None,
+                _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(dist[step]) if dist is not None else None,
+                _lib.ptr(st["p_word"][step]), _lib.ptr(st["p_entry"][step]), _lib.ptr(st["entry"][step]),
+                _lib.ptr(st["copy_share"][step]), _lib.ptr(st["p_label"][step]) if lab else None,
+                _lib.ptr(st["top_id"][step]), _lib.ptr(st["logp_word"]), _lib.ptr(st["logp_entry"]),
+                _lib.ptr(st["logp_label"]) if lab else None, self.flags), "fira_decode_step_score")
+
+    def check_candidates(self, cand, lengths=None, labels=None, B=None):
+        """Validates candidate messages on the host (nothing is launched) and returns them as int32 CPU tensors
+        (cand [B, n, tar_len] zero-padded, length [B, n], labels [B, n, tar_len] with -1 past the message, or None).
+        Raises ValueError on anything the scoring kernel's contract excludes."""
+        cfg = self.cfg
+        T, V = cfg.tar_len, cfg.vocab_size
+        cand = torch.as_tensor(cand).detach().cpu().long()
+        if cand.dim() == 2:
+            cand = cand[:, None, :]
+        if cand.dim() != 3:
+            raise ValueError("cand: expected [B, n, T] or [B, T] token ids, got shape %s" % (tuple(cand.shape),))
+        Bc, n, Tc = cand.shape
+        if B is not None and Bc != B:
+            raise ValueError("cand: %d commits for a batch of %d" % (Bc, B))
+        if not 1 <= n <= 8:
+            raise ValueError("cand: %d candidates per commit, outside 1..8" % n)
+        if not 1 <= Tc <= T:
+            raise ValueError("cand: %d positions, outside 1..tar_len = %d" % (Tc, T))
+        if Tc < T:
+            cand = torch.cat([cand, cand.new_zeros(Bc, n, T - Tc)], 2)
+        pos = torch.arange(T)[None, None, :]
+        if lengths is None:
+            length = (cand != PAD).long().cumprod(2).sum(2)                # the leading run of non-zero ids
+        else:
+            length = torch.as_tensor(lengths).detach().cpu().long().reshape(Bc, n)
+            if int(length.min()) < 1 or int(length.max()) > Tc:
+                raise ValueError("lengths: outside 1..%d" % Tc)
+            cand = torch.where(pos < length[:, :, None], cand, torch.zeros_like(cand))
+        inside = pos < length[:, :, None]
+        if bool(((cand == PAD) != ~inside).any()):
+            raise ValueError("cand: id 0 (<pad>) inside a message (only the padding after it may be 0)")
+        if int(cand.min()) < 0 or int(cand.max()) >= V:
+            raise ValueError("cand: token id outside the vocabulary [0, %d)" % V)
+        if bool((cand[:, :, 0] != START).any()):
+            raise ValueError("cand: every message starts with <start> (id %d)" % START)
+        if bool(((cand == EOS) & (pos != length[:, :, None] - 1)).any()):
+            raise ValueError("cand: <eos> before the end of a message")
+        if labels is not None:
+            labels = torch.as_tensor(labels).detach().cpu().long()
+            if labels.dim() == 2:
+                labels = labels[:, None, :]
+            if labels.shape[:2] != (Bc, n) or labels.shape[2] > T:
+                raise ValueError("labels: shape %s does not match the candidates' %s" % (tuple(labels.shape), (Bc, n, Tc)))
+            if labels.shape[2] < T:
+                labels = torch.cat([labels, labels.new_zeros(Bc, n, T - labels.shape[2])], 2)
+            if int(labels.max()) >= cfg.out_len:
+                raise ValueError("labels: entry index outside [0, %d)" % cfg.out_len)
+            labels = torch.where(inside & (labels >= 0), labels, torch.full_like(labels, -1)).to(torch.int32)
+        return cand.to(torch.int32), length.to(torch.int32), labels
+
+    @torch.no_grad()
+    def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None):
+        """Teacher-forced probability of given messages.  ``cand`` [B, n, T] (or [B, T]) vocabulary ids, each message starting
+        with <start> and ending with <eos> unless truncated, zero-padded; 1 <= n <= 8 candidates per commit share the
+        commit's encoder pass and memory (``fira_decode_begin`` with n rows per commit).  ``labels`` (same shape, optional):
+        the output entry credited at every position, as ``tar_label`` (-1 = none).
+
+        Returns a ``Scores`` dict: per token [B, n, tar_len - 1] (index t scores the id at position t + 1) ``p_word`` (the
+        word's probability over every entry that resolves to it), ``p_entry`` / ``entry`` (its largest single entry),
+        ``copy_share``, ``top_id`` (the model's arg-max entry, -1 where nothing is scored) and ``p_label``; per candidate
+        [B, n] ``logp_word``, ``logp_entry``, ``logp_label`` (float64 sums of log max(p, 1e-10)) and ``length`` (ids including
+        <start>; ``length - 1`` tokens are scored).  The step loop is captured into hipGraphs per (B, n) like ``greedy``;
+        how many chunks to replay follows from the longest candidate, so nothing is read back between chunks.
+        ``dist`` (tests): a [tar_len - 1, B * n, out_len] tensor that receives every step's distribution (eager only)."""
+        cfg = self.cfg
+        B, T = db.B, cfg.tar_len
+        cand, length, labels = self.check_candidates(cand, lengths, labels, B)        # raises before anything is launched
+        n = cand.shape[1]
+        R = B * n
+        ws = self._begin(db, n)
+        st = self._score_state(B, n, labels is not None)
+        st["sou"].copy_(db.sou)
+        st["sub"].copy_(db.sub_token)
+        st["cand"].copy_(cand.reshape(R, T).t())
+        if labels is not None:
+            st["label"].copy_(labels.reshape(R, T).t())
+        self._score_reset(st)
+        n_steps = max(int(length.max()) - 1, 0)               # step t scores position t + 1 <= length - 1
+        bounds = [(lo, min(lo + chunk, T - 1)) for lo in range(0, T - 1, chunk)]
+        use_graphs = use_graphs and dist is None
+        if use_graphs and st["graphs"] is None:
+            self._score_steps(st, ws, B, n, 0, 1)              # warm-up outside capture
+            torch.cuda.synchronize()
+            graphs = []
+            for lo, hi in bounds:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._score_steps(st, ws, B, n, lo, hi)
+                graphs.append(g)
+            st["graphs"] = graphs
+            self._score_reset(st)
+        for i, (lo, hi) in enumerate(bounds):
+            if lo >= n_steps:
+                break
+            if use_graphs:
+                st["graphs"][i].replay()
+            else:
+                self._score_steps(st, ws, B, n, lo, min(hi, n_steps), dist)
+        res = Scores()
+        scored = (st["cand"][1:] != PAD).t().reshape(B, n, T - 1)
+        for k in self.SCORE_TOKEN_KEYS:
+            if k == "p_label" and labels is None:
+                continue
+            res[k] = st[k].t().reshape(B, n, T - 1).clone()
+        res["top_id"] = torch.where(scored, res["top_id"], torch.full_like(res["top_id"], -1)).long()
+        res["entry"] = res["entry"].long()
+        # The per-candidate sums are re-formed here in float64 from the per-token values (exact fp32 inputs, one small torch
+        # expression).  The kernel's own fp32 running sums (the C ABI's logp_*) round once per step at the magnitude of the
+        # sum: measured 4.3e-6 relative on exp(logp) at logp = -32, above the T * 2^-23 a product of T factors stays within.
+        floor = lambda p: torch.log(p.double().clamp(min=1e-10))
+        res["logp_word"] = torch.where(scored, floor(res["p_word"]), 0.0).sum(2)
+        res["logp_entry"] = torch.where(scored, floor(res["p_entry"]), 0.0).sum(2)
+        if labels is not None:
+            labelled = scored & (st["label"][1:] >= 0).t().reshape(B, n, T - 1)
+            res["logp_label"] = torch.where(labelled, floor(res["p_label"]), 0.0).sum(2)
+        res["length"] = length.to(self.model.device_).long()
+        return res
+
+    def rank(self, scores, by: str = "logp_word") -> List[int]:
+        """Index of the best candidate per commit under ``by``: ``logp_entry`` (what ``best_sample`` ranks by: the largest
+        single entry per token), ``logp_word`` (the word marginal) or ``mean_logp_word`` (per scored token); first on ties."""
+        if by not in self.RANK_KEYS:
+            raise ValueError("rank: by=%r, expected one of %s" % (by, ", ".join(self.RANK_KEYS)))
+        return torch.argmax(rank_values(scores, by), dim=1).tolist()
 
     # ------------------------------------------------------------------ beam search with the reference's semantics
     def _beam_state(self, B, beam):

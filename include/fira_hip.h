@@ -650,6 +650,36 @@ int fira_sample_advance(void* stream, const fira_dims* d, int B, int n_sample, i
                         const float* best_p, const int32_t* sou, const int32_t* sub_token, int32_t* out, int32_t* length,
                         float* prob, float* logp, int32_t* alive, int32_t* tokens, int32_t* n_alive);
 
+/* Teacher-forced scoring of given candidate messages: how probable is this message for this commit?  Workspace:
+ * fira_decode_begin_ex / fira_decode_workspace_bytes_ex with n_beam = n_cand (1..8) and the same flags
+ * (FIRA_DECODE_KV_BF16 allowed), so the encoder, the cross-attention K|V and LinearSource(memory) are computed once per
+ * commit for all its candidates.
+ *   fira_decode_step_score : fira_decode_step_ex for the B * n_cand rows (row r = commit r / n_cand, candidate
+ *     r % n_cand; rows never change parent, so there is no cache permutation) fed with tokens[r] = the candidate's id at
+ *     position `step`, then per row the distribution p over vocab + S entries (dist[r, :] if dist != NULL, bit-identical
+ *     to fira_decode_step's) scored against target[r] = the candidate's id at position step + 1 (a vocabulary id; 0 =
+ *     nothing to score at this step).  With the candidates stored step-major ([tar_len, B * n_cand]) tokens and target
+ *     are two rows of one tensor: one call per step, no bookkeeping kernel.  Written for every row:
+ *       p_word[r]     p[y] (y < vocab) + the sum of p[vocab + s] over the memory slots s that are valid and whose source id
+ *                     (sou[b, s] for s < sou_len, sub_token[b, s - sou_len] above) is y: the probability of the WORD,
+ *                     over every entry that resolves to it; summed in one fixed order without atomics
+ *       p_entry[r], entry[r]   the largest single entry that resolves to y and its index (lowest index on ties; -1 and
+ *                     0 when no entry resolves to y): what a search is credited with when it emits y
+ *       copy_share[r] the copy part of p_word over p_word (0 when p_word == 0)
+ *       p_label[r]    p[label[r]] for label[r] in [0, vocab + S) (an entry index; -1 = none -> 0); label, p_label and
+ *                     logp_label are given together or all NULL
+ *       top_id[r]     the row's arg-max entry, identical to fira_decode_step_ex's best_id
+ *     and added to: logp_word[r], logp_entry[r], logp_label[r] += logf(max(p, 1e-10)) (the clamp of fira_head_loss) of
+ *     p_word, p_entry and p_label.  Rows with target 0 get p_word = p_entry = copy_share = p_label = 0, entry = -1, and
+ *     their sums are left alone.  Every single-entry value is bit-identical to dist[r, index].  sou [B, sou_len] and
+ *     sub_token [B, sub_len] are the commit's id rows (as fira_greedy_advance takes them).  Shapes beyond vocab 25 600 /
+ *     S 1 024: error.                                                                                                 */
+int fira_decode_step_score(void* stream, const fira_dims* d, const float* params, void* workspace,
+                           size_t workspace_bytes, int B, int n_cand, int step, const int32_t* tokens,
+                           const int32_t* target, const int32_t* label, const int32_t* sou, const int32_t* sub_token,
+                           float* dist, float* p_word, float* p_entry, int32_t* entry, float* copy_share, float* p_label,
+                           int32_t* top_id, float* logp_word, float* logp_entry, float* logp_label, int flags);
+
 /* Decoder.forward over all tar_len positions on caller-supplied memory [B, sou+sub, 256] / mem_valid [B, sou+sub]
  * (gnn_transformer.py:108-122; the call of run_model.py:256).  Workspace: fira_workspace_bytes(d, B, 0).          */
 int fira_decoder_forward(void* stream, const fira_dims* d, const float* params, void* workspace,

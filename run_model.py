@@ -85,12 +85,68 @@ def parse_args(argv):
     ap.add_argument("--top-k", type=int, default=None, help="with --sample: keep the k most probable entries (default 0 = off)")
     ap.add_argument("--top-p", type=float, default=None, help="with --sample: nucleus mass in (0, 1] (default 1 = off)")
     ap.add_argument("--sample-seed", type=int, default=None, help="with --sample: seed of the sampling noise (default 0)")
+    ap.add_argument("--score", default=None, metavar="refs|PATH", help="test: instead of searching, score given messages "
+                    "teacher-forced on the device: 'refs' = the test split's own messages, PATH = a file with one line per test "
+                    "commit in all_index['test'] order (plain text as in OUTPUT/output_fira, or the JSON lines of "
+                    "OUTPUT/output_fira_samples with up to 8 candidates); writes OUTPUT/output_fira_scores and prints the "
+                    "corpus perplexity")
+    ap.add_argument("--rerank", default=None, choices=RERANK_KEYS, help="with --sample: score the drawn candidates in the same "
+                    "run and write the best one under this key to OUTPUT/output_fira (default: the candidate of highest "
+                    "log-probability of the drawn entries)")
     a = ap.parse_args(argv)
     try:
+        check_score_args(a)
         check_sample_args(a)
     except ValueError as e:
         ap.error(str(e))
     return a
+
+
+RERANK_KEYS = ("logp_word", "mean_logp_word")
+
+
+def check_score_args(a):
+    """Validates --score / --rerank against the other options (no GPU, no DataSet needed); raises ValueError on a conflict."""
+    if a.rerank is not None and a.sample is None:
+        raise ValueError("--rerank %s ranks sampled candidates: it needs --sample" % a.rerank)
+    if a.score is None:
+        return a
+    if a.stage != "test":
+        raise ValueError("--score only applies to the test stage")
+    if a.sample is not None:
+        raise ValueError("--score scores given messages instead of producing them: it does not combine with --sample")
+    if a.beam is not None and a.beam > 1:
+        raise ValueError("--score scores given messages instead of searching: it does not combine with --beam %d" % a.beam)
+    if a.score != "refs" and not os.path.isfile(a.score):
+        raise ValueError("--score %s: not 'refs' and no such file" % a.score)
+    a.beam = 1
+    return a
+
+
+def read_score_lines(path, n_commits):
+    """The candidate lines of ``--score PATH``: per test commit (1..8 message strings, whether the line was JSON).  A line is plain text (the
+    format of OUTPUT/output_fira) or the JSON of OUTPUT/output_fira_samples ({"candidates": [...]}).  Raises ValueError on
+    a wrong line count or candidate count."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    if len(lines) != n_commits:
+        raise ValueError("--score %s: %d lines for %d test commits" % (path, len(lines), n_commits))
+    out = []
+    for k, line in enumerate(lines):
+        cands, is_json = [line], False
+        if line.lstrip().startswith("{"):
+            try:
+                rec = json.loads(line)
+                if isinstance(rec, dict) and isinstance(rec.get("candidates"), list):
+                    cands, is_json = [str(c) for c in rec["candidates"]], True
+            except ValueError:
+                pass                                          # not JSON: a message that starts with a brace
+        if not 1 <= len(cands) <= 8:
+            raise ValueError("--score %s: line %d holds %d candidates, outside 1..8" % (path, k + 1, len(cands)))
+        out.append((cands, is_json))
+    return out
 
 
 SAMPLE_OPTIONS = (("temperature", "--temperature", 1.0), ("top_k", "--top-k", 0), ("top_p", "--top-p", 1.0),
@@ -270,6 +326,9 @@ class Run:
         test_index = self.all_index["test"]
         if self.a.sample is not None:
             check_sample_args(self.a, cfg.out_len)           # top-k against this vocabulary, before the model loads
+        given = None
+        if self.a.score is not None and self.a.score != "refs":
+            given = read_score_lines(self.a.score, len(store))   # a wrong line count is an error before the model loads
         self.model = TransModel(cfg, device="cuda:%d" % self.local, init=False)
         self.model.load_state_dict(torch.load(os.path.join(self.root, "best_model.pt"), map_location="cpu"))
         self.model.compute_dtype = self.a.dtype
@@ -278,6 +337,8 @@ class Run:
         mine = shard_indices(list(range(len(store))), self.rank, self.world)
         if self.a.sample is not None:
             return self.test_sample(search, store, mine)
+        if self.a.score is not None:
+            return self.test_score(search, store, mine, given)
         lines, n_tok, t0 = [], 0, time.time()
         # greedy: groups of `in_flight` batches share the GPU (independent launch chains: decode.Searcher.greedy_many; four lanes
         # on eight hardware queues: 0.14 ms per batch-step against 0.33 one at a time); the output order stays
@@ -312,15 +373,22 @@ class Run:
         lines, samples, n_tok, t0 = [], [], 0, time.time()
         for lo in range(0, len(mine), cfg.test_batch_size):
             idx = mine[lo:lo + cfg.test_batch_size]
-            toks, lens, _, logp = search.sample(self.device_batch(store, idx), a.sample, temperature=a.temperature,
+            db = self.device_batch(store, idx)
+            toks, lens, _, logp = search.sample(db, a.sample, temperature=a.temperature,
                                                 top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed, keys=idx)
             best = search.best_sample(toks, lens, logp)
+            values = None
+            if a.rerank is not None:                         # score the drawn candidates; pick by the word marginal
+                best, values = self.rerank(search, db, toks, lens)
             toks, lens, logp = toks.tolist(), lens.tolist(), logp.tolist()
             for k, i in enumerate(idx):
                 var_map = self.var_maps[test_index[i]]
                 lines.append(text.detokenize(best[k], self.r_vocab, var_map))
                 cands = [text.detokenize(toks[k][j][:lens[k][j]], self.r_vocab, var_map) for j in range(a.sample)]
-                samples.append(json.dumps({"candidates": cands, "logp": logp[k]}))
+                rec = {"candidates": cands, "logp": logp[k]}
+                if values is not None:
+                    rec[a.rerank] = values[k]
+                samples.append(json.dumps(rec))
                 n_tok += sum(max(n - 1, 0) for n in lens[k])
             if self.rank == 0:
                 print("data: %d/%d  (%.1f tokens/s)" % (min(len(mine), lo + cfg.test_batch_size), len(mine),
@@ -332,6 +400,84 @@ class Run:
             with open(self.out("output_fira_samples"), "w") as f:
                 f.write("".join(l + "\n" for l in samples))
         return lines
+
+
+    def rerank(self, search, db, toks, lens):
+        """--rerank: the drawn candidates scored teacher-forced (decode.Searcher.score) and the best one per commit under the
+        key.  A candidate in which <pad> or <start> was drawn mid-message cannot be scored (its text drops that id): it is
+        scored up to there, reported as null and never preferred to a candidate that can."""
+        from fira_icse_amd.decode import rank_values
+        T = toks.shape[2]
+        inner = (toks[:, :, 1:] == PAD) | (toks[:, :, 1:] == START)
+        first = torch.where(inner.any(2), inner.long().argmax(2) + 1, torch.full_like(lens, T))
+        cut = torch.minimum(lens, first)
+        sc = search.score(db, toks, lengths=cut)
+        vals = rank_values(sc, self.a.rerank).cpu()
+        vals = torch.where(cut.cpu() < lens.cpu(), torch.full_like(vals, float("-inf")), vals)
+        pick = torch.argmax(vals, dim=1).tolist()
+        best = [toks[k, j, :int(lens[k, j])].tolist() for k, j in enumerate(pick)]
+        return best, [[v if v != float("-inf") else None for v in row] for row in vals.tolist()]
+
+    def test_score(self, search, store, mine, given):
+        """--score: teacher-forced scores of given messages (decode.Searcher.score), one JSON line per test commit in
+        OUTPUT/output_fira_scores, and the corpus perplexity exp(-sum logp_word / sum n_tokens)."""
+        cfg = self.cfg
+        test_index = self.all_index["test"]
+        V, L, T = cfg.vocab_size, cfg.sou_len, cfg.tar_len
+        recs, t0 = [], time.time()
+
+        def record(sc, k, j, ids, sou_row, sub_row):
+            n_tok = int(sc["length"][k][j]) - 1
+            src = []
+            for e in sc["entry"][k][j][:n_tok]:
+                src.append("none" if e < 0 else "gen" if e < V else "diff:%d" % (e - V) if e < V + L else "sub:%d" % (e - V - L))
+            rec = {"logp_word": sc["logp_word"][k][j], "n_tokens": n_tok, "tokens": ids[1:n_tok + 1],
+                   "p_word": sc["p_word"][k][j][:n_tok], "copy_share": sc["copy_share"][k][j][:n_tok], "source": src,
+                   "top": [text.resolve_copy(t, sou_row, sub_row, V, L) for t in sc["top_id"][k][j][:n_tok]]}
+            if "logp_label" in sc:
+                rec["logp_label"] = sc["logp_label"][k][j]
+            return rec
+
+        for lo in range(0, len(mine), cfg.test_batch_size):
+            idx = mine[lo:lo + cfg.test_batch_size]
+            if given is None:
+                counts = [1] * len(idx)
+                cand, labels = store.tar[idx][:, None, :], store.tar_label[idx][:, None, :]
+            else:
+                msgs = [[text.tokenize_message(m, self.vocab, self.var_maps[test_index[i]], T) for m in given[i][0]] for i in idx]
+                counts = [len(m) for m in msgs]
+                n = max(counts)                                # commits with fewer candidates repeat their first one
+                cand = np.zeros((len(idx), n, T), dtype=np.int64)
+                for k, m in enumerate(msgs):
+                    for j in range(n):
+                        ids = m[j] if j < len(m) else m[0]
+                        cand[k, j, :len(ids)] = ids
+                labels = None
+            sc = search.score(self.device_batch(store, idx), cand, labels=labels)
+            sc = {k: v.tolist() for k, v in sc.items()}
+            cand = np.asarray(cand).tolist()
+            for k, i in enumerate(idx):
+                rows = [record(sc, k, j, cand[k][j], store.sou[i], store.sub_token[i]) for j in range(counts[k])]
+                recs.append(json.dumps(rows[0] if given is None or not given[i][1] else {"candidates": rows}))
+            if self.rank == 0:
+                print("data: %d/%d  (%.1f commits/s)" % (min(len(mine), lo + cfg.test_batch_size), len(mine),
+                                                        len(recs) / max(time.time() - t0, 1e-9)), flush=True)
+        recs = gather_lines(recs)
+        if self.rank == 0:
+            with open(self.out("output_fira_scores"), "w") as f:
+                f.write("".join(l + "\n" for l in recs))
+            import math
+            flat = []
+            for l in recs:
+                r = json.loads(l)
+                flat.extend(r["candidates"] if "candidates" in r else [r])
+            n_tok = sum(r["n_tokens"] for r in flat)
+            line = "scored %d messages, %d tokens: perplexity %.4f" % (
+                len(flat), n_tok, math.exp(-sum(r["logp_word"] for r in flat) / max(n_tok, 1)))
+            if flat and "logp_label" in flat[0]:
+                line += " (label entries only: %.4f)" % math.exp(-sum(r["logp_label"] for r in flat) / max(n_tok, 1))
+            print(line, flush=True)
+        return recs
 
 
 def main(argv=None):
