@@ -45,6 +45,12 @@ class AdamOpts(C.Structure):
                 ("m", C.c_void_p), ("v", C.c_void_p)]
 
 
+class ClipState(C.Structure):
+    """fira_clip_state as the device holds it (64 bytes): read back with ``ClipState.from_buffer_copy``."""
+    _fields_ = [("sq", C.c_float * 4), ("norm", C.c_float), ("coef", C.c_float), ("zero_flag", C.c_int32),
+                ("n_clipped", C.c_int32), ("n_nonfinite", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
 _U64, _U32 = C.c_uint64, C.c_uint32
 _DP, _BP, _OP = C.POINTER(Dims), C.POINTER(Batch), C.POINTER(TrainOpts)
@@ -117,6 +123,12 @@ SIGNATURES = {
     "fira_adam_rows_step": (_I, [_P, _DP, _P, _P, C.POINTER(AdamOpts), _P, _P, _P, _I]),
     "fira_train_step_begin_rows": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, _P, C.POINTER(AdamOpts), _P]),
     "fira_train_step_end_rows": (_I, [_P, _P, C.POINTER(AdamOpts), _P, _P, _P]),
+    "fira_grad_sqsum_scratch_bytes": (_Z, []),
+    "fira_grad_sqsum": (_I, [_P, _L, _P, _P, _I, _P]),
+    "fira_clip_finish": (_I, [_P, _P, _I, _P, _P, _F]),
+    "fira_adam_step_clip": (_I, [_P, _L, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P, _P, _P]),
+    "fira_adam_rows_step_clip": (_I, [_P, _DP, _P, _P, C.POINTER(AdamOpts), _P, _P, _P, _I, _P]),
+    "fira_train_step_clip": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, C.POINTER(AdamOpts), _P, _F, _P, _P]),
     "fira_train_step_begin": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, _P]),
     "fira_train_step_end": (_I, [_P, _P, C.POINTER(AdamOpts), _P, _P]),
     "fira_f32_to_bf16": (_I, [_P, _L, _P, _P]),

@@ -936,7 +936,7 @@ int adam_step_mb(hipStream_t s, int64_t n, float* p, const float* g0, const floa
     FIRA_CHECK_LAUNCH("adam_step_mb");
     return 0;
 }
-static AdamRowsHist adam_rows_hist(float beta1, float beta2, int end) {
+AdamRowsHist adam_rows_hist(float beta1, float beta2, int end) {
     AdamRowsHist h;
     for (int k = 0; k < ADAM_ROWS_K; ++k) h.bc1[k] = h.bc2s[k] = 1.f;
     for (int j = std::max(1, end - ADAM_ROWS_K + 1); j <= end; ++j) {       // as adam_step_mb forms them for step j

@@ -335,6 +335,24 @@ int adam_rows_step(hipStream_t s, const AdamRowsTables& tb, const float* g, floa
 // rows brought up to step `to` by zero-gradient updates: the listed ids (ls) or, ls == nullptr, every row
 int adam_rows_catchup(hipStream_t s, const AdamRowsTables& tb, const AdamRowsLists* ls, float lr, float beta1, float beta2,
                       float eps, int to);
+AdamRowsHist adam_rows_hist(float beta1, float beta2, int end);     // bias corrections of the steps end - K + 1 .. end
+// Clipping by the global gradient norm (gradnorm.hip).  grad_sqsum: sum of squares of g[0, n) into st->sq[slot], through
+// `scratch` (grad_sqsum_scratch_bytes(), the partials of slot k at its own offset: ranges of different slots may be summed on
+// different streams); with `fin` the closing step follows in the same launch.  clip_finish: norm / coef / zero flag / counters
+// from st->sq[0 .. n_slots).  The *_clip updates are adam_step(_mb / count form) and adam_rows_step reading that state.
+struct ClipClose {
+    const int32_t* n_tok;      // normaliser 1 / max(*n_tok, 1) ...
+    const float* count;        // ... or, if given, 1 / max(*count, 1) (the all-reduced token count of a data-parallel step)
+    float max_norm;
+    int n_slots;
+};
+size_t grad_sqsum_scratch_bytes();
+int grad_sqsum(hipStream_t s, int64_t n, const float* g, fira_clip_state* st, int slot, void* scratch, const ClipClose* fin);
+int clip_finish(hipStream_t s, fira_clip_state* st, const ClipClose& fin);
+int adam_step_clip(hipStream_t s, int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
+                   float eps, int step, const int32_t* n0, const float* count, const fira_clip_state* st);
+int adam_rows_step_clip(hipStream_t s, const AdamRowsTables& tb, const float* g, float lr, float beta1, float beta2, float eps,
+                        int step, const int32_t* n0, const float* count, int tables, const fira_clip_state* st);
 
 // ---- parameter layout ---------------------------------------------------------------------------------
 struct ParamInfo {

@@ -688,6 +688,12 @@ static inline void note_graph_density(const fira_batch* b) {
 enum Site { SITE_GATE = 0, SITE_COMB_OUT = 1, SITE_GCN = 2, SITE_SELF = 3, SITE_CROSS = 4, SITE_FFN = 5 };
 static inline uint32_t site(int layer, int kind) { return (uint32_t)(layer * 8 + kind + 1); }
 
+struct ClipStep {
+    const fira_adam_opts* adam;
+    float max_norm;
+    fira_clip_state* state;
+    void* scratch;
+};
 struct Ctx {
     hipStream_t s;
     const Layout* L;
@@ -745,6 +751,10 @@ struct Ctx {
     bool adam_a_only = false;
     hipEvent_t ev_early = nullptr;
     const float* count = nullptr;
+    // fira_train_step_clip: the update clipped by the global gradient norm (gradnorm.hip).  Every update depends on every
+    // gradient, so nothing is updated ahead of the final join (c.adam stays null: no early Adam); the sum of squares of
+    // [0, split) runs on the auxiliary stream where mid_event would fire, beside the encoder's backward pass.
+    const ClipStep* clip = nullptr;
     // bf16 mode (round 5): the refresh of the bf16 weight shadows (one 46 us launch) runs on the auxiliary stream behind the GCN
     // fold instead of at the head of the caller's stream -- with the fused Combination / GCN kernels (which round the fp32
     // weights themselves) the first reader of a shadow is the decoder (and the auxiliary stream's own K|V projections)
@@ -1236,6 +1246,23 @@ static inline int enc_wgrad_every(int n_rows, int n_layers) {
 
 // what the encoder half of the backward pass needs from the decoder half (the two halves are one call, or the two calls
 // fira_train_step_begin / fira_train_step_end with the caller's collective in between)
+// The stream on which "every gradient of [0, split) is final" holds from its current tail on: BOTH the caller's stream and the
+// weight-gradient stream have reached this point, without holding up either of them -- the auxiliary stream (idle for the rest
+// of the backward pass) waits for the two.  (Joining the weight-gradient stream into the caller's stream here made the
+// encoder's backward wait for the vocabulary projection's weight gradient.)  Without the side streams: the caller's stream.
+static int group_a_final_stream(hipStream_t s, hipStream_t* out) {
+    SideStream& sd = side();
+    *out = s;
+    if (sd.stream && sd.enabled) {
+        TRY(aux_fork(s));
+        hipEvent_t e2 = sd.ev();
+        if (hipEventRecord(e2, sd.stream) != hipSuccess || hipStreamWaitEvent(sd.aux, e2, 0) != hipSuccess)
+            return set_err("group-A mark: weight-gradient stream mark failed");
+        *out = sd.aux;
+    }
+    return 0;
+}
+
 struct BwdMid {
     hipEvent_t ev_dmem = nullptr;      // d memory is complete (auxiliary stream)
     hipEvent_t ev_groupA = nullptr;    // every gradient of [0, split) is final (weight-gradient stream)
@@ -1472,22 +1499,16 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
         ev_groupA = side().ev();
         if (hipEventRecord(ev_groupA, side().stream) != hipSuccess) return set_err("group-A mark failed");
     }
-    if (mid_event) {                         // gradients of [0, split) are final from here on
-        // The event fires when BOTH the caller's stream and the weight-gradient stream have reached this point, without
-        // holding up either of them: the auxiliary stream (idle for the rest of the backward pass) waits for the two and
-        // records it.  (Joining the weight-gradient stream into the caller's stream here made the encoder's backward wait
-        // for the vocabulary projection's weight gradient.)
-        SideStream& sd = side();
-        hipStream_t es = s;
-        if (sd.stream && sd.enabled) {
-            TRY(aux_fork(s));
-            hipEvent_t e2 = sd.ev();
-            if (hipEventRecord(e2, sd.stream) != hipSuccess || hipStreamWaitEvent(sd.aux, e2, 0) != hipSuccess)
-                return set_err("mid-event: weight-gradient stream mark failed");
-            es = sd.aux;
+    if (mid_event || c.clip) {               // gradients of [0, split) are final from here on
+        hipStream_t es = nullptr;
+        TRY(group_a_final_stream(s, &es));
+        if (mid_event) {
+            hipError_t e = hipEventRecord(mid_event, es);
+            if (e != hipSuccess) return set_err("hipEventRecord: %s", hipGetErrorString(e));
         }
-        hipError_t e = hipEventRecord(mid_event, es);
-        if (e != hipSuccess) return set_err("hipEventRecord: %s", hipGetErrorString(e));
+        // clipped step: the sum of squares of [0, split) there, beside the encoder's backward pass; the caller's stream meets
+        // it again at the auxiliary stream's tail mark ahead of the final join
+        if (c.clip) TRY(grad_sqsum(es, L.split, G, c.clip->state, 0, c.clip->scratch, nullptr));
     }
     return 0;
 }
@@ -1708,6 +1729,30 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         TRY(adam_step_mb(s, L.live - adam_b0, c.Pw + adam_b0, G + adam_b0, nullptr, ad.m + adam_b0, ad.v + adam_b0, ad.lr, ad.beta1,
                          ad.beta2, ad.eps, ad.step, c.n_tok, nullptr));
     }
+    if (c.clip) {
+        // every gradient of [0, live) is final here (and the auxiliary stream's sum over [0, split) precedes ev_tail): the sum
+        // over [split, live) with the closing step in its second launch, then the whole update -- the two word tables by rows
+        // when row_step is given, the rest as dense launches over the gaps between them
+        const ClipStep& cl = *c.clip;
+        const fira_adam_opts& ad = *cl.adam;
+        const ClipClose fin{c.n_tok, nullptr, cl.max_norm, 2};
+        TRY(grad_sqsum(s, L.live - L.split, G + L.split, cl.state, 1, cl.scratch, &fin));
+        auto dense = [&](int64_t lo, int64_t hi) {
+            return adam_step_clip(s, hi - lo, c.Pw + lo, G + lo, ad.m + lo, ad.v + lo, ad.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+                                  c.n_tok, nullptr, cl.state);
+        };
+        if (c.row_step) {
+            const int64_t tab = (int64_t)L.d.vocab * D;
+            TRY(adam_rows_step_clip(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, ad.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+                                    c.n_tok, nullptr, 3, cl.state));
+            const int64_t t0 = std::min(L.dec_emb, L.emb), t1 = std::max(L.dec_emb, L.emb);
+            TRY(dense(0, t0));
+            TRY(dense(t0 + tab, t1));
+            TRY(dense(t1 + tab, L.live));
+        } else {
+            TRY(dense(0, L.live));
+        }
+    }
     return 0;
 }
 
@@ -1803,7 +1848,7 @@ static thread_local PendingStep g_pending;
 static int train_call(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
                       void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
                       int32_t* n_tok, void* mid_event, float* params_w, const fira_adam_opts* adam, bool begin_only = false,
-                      int32_t* row_step = nullptr) {
+                      int32_t* row_step = nullptr, const ClipStep* clip = nullptr) {
     const Layout* L = get_layout(d);
     if (!L) return 1;
     TRY(check_batch(batch));
@@ -1857,6 +1902,7 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
     }
     c.dp_begin = begin_only;
     if (begin_only) c.adam = nullptr;        // (fira_train_step_begin_rows: the optimizer's values serve the lazy reads only)
+    if (clip) { c.adam = nullptr; c.clip = clip; }      // (clipped step: the update follows the final join, see backward_encoder)
     TRY(encoder_forward(c, true));
     if (side_on()) {
         // the buffers the backward pass accumulates into are cleared on the auxiliary stream beside the forward pass (they
@@ -2019,6 +2065,31 @@ int fira_train_step_rows(void* stream, const fira_dims* d, const fira_batch* bat
     FIRA_REQUIRE(opts && opts->zero_grads, "fira_train_step_rows: needs opts.zero_grads (an all-zero gradient row = an untouched row)");
     return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
                       false, row_step);
+}
+// The one-call step with the update clipped by the global gradient norm (include/fira_hip.h; gradnorm.hip)
+int fira_train_step_clip(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads, void* workspace,
+                         size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok,
+                         const fira_adam_opts* adam, int32_t* row_step, float max_norm, fira_clip_state* state, void* scratch) {
+    FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_step_clip: Adam moments missing");
+    FIRA_REQUIRE(adam->step >= 1, "fira_train_step_clip: the Adam step counter starts at 1");
+    FIRA_REQUIRE(max_norm > 0.f, "fira_train_step_clip: max_norm must be > 0 (inf allowed)");
+    FIRA_REQUIRE(state && scratch && (uintptr_t)scratch % 8 == 0, "fira_train_step_clip: clip state / scratch missing");
+    FIRA_REQUIRE(!row_step || (opts && opts->zero_grads),
+                 "fira_train_step_clip: row_step needs opts.zero_grads (an all-zero gradient row = an untouched row)");
+    const ClipStep clip{adam, max_norm, state, scratch};
+    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
+                      false, row_step, &clip);
+}
+int fira_adam_rows_step_clip(void* stream, const fira_dims* d, float* params, const float* grads, const fira_adam_opts* adam,
+                             int32_t* row_step, const int32_t* n_tok, const float* count, int tables,
+                             const fira_clip_state* state) {
+    const Layout* L = get_layout(d);
+    if (!L) return 1;
+    FIRA_REQUIRE(params && grads && adam && adam->m && adam->v && row_step && (n_tok || count) && adam->step >= 1 && tables >= 1 &&
+                     tables <= 3 && state, "fira_adam_rows_step_clip: bad argument");
+    FIRA_REQUIRE(L->d.d_model == FIRA_D, "fira_adam_rows_step_clip: model width must be %d", FIRA_D);
+    return adam_rows_step_clip((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), grads, adam->lr, adam->beta1,
+                               adam->beta2, adam->eps, adam->step, n_tok, count, tables, state);
 }
 // op-level pieces of the same (tests/test_adam_rows_gpu.py compares them with fira_adam_step_mb bit for bit)
 int fira_adam_rows_step(void* stream, const fira_dims* d, float* params, const float* grads, const fira_adam_opts* adam,

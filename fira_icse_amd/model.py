@@ -498,12 +498,14 @@ class TransModel(nn.Module):
 
     def train_step(self, db: DeviceBatch, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, beta1: float = 0.9,
                    beta2: float = 0.999, eps: float = 1e-8, dropout: Optional[float] = None,
-                   gcn_dropout: Optional[float] = None, row_step: Optional[torch.Tensor] = None):
+                   gcn_dropout: Optional[float] = None, row_step: Optional[torch.Tensor] = None, clip=None):
         """``loss.backward(); optimizer.step()`` of run_model.py:104-111 as ONE library call (fira_train_step): the same
         arithmetic as :meth:`train_fwd_bwd` + ``ops.adam_step_mb`` over ``[0, live)``; the head + decoder slice of the update
         runs beside the last weight gradients.  ``m`` / ``v``: the Adam moments (flat, like ``self.flat``).
         ``row_step`` (int32 ``[2 * vocab]``): fira_train_step_rows -- the two vocabulary-sized embedding tables are updated on
-        the rows the step touched only; the caller owns the sync (:meth:`sync_params`, ``Trainer.sync``)."""
+        the rows the step touched only; the caller owns the sync (:meth:`sync_params`, ``Trainer.sync``).
+        ``clip`` = ``(max_norm, state, scratch)`` (``ops.clip_state``): fira_train_step_clip -- the update clipped by the global
+        gradient norm, a non-finite gradient applied as a zero-gradient step; with or without ``row_step``."""
         lib = _lib.lib()
         if row_step is None:
             self.sync_params()
@@ -515,6 +517,14 @@ class TransModel(nn.Module):
                               1 if self.compact_dec else 0, 1)
         adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v))
         ws = self.workspace(db.B, 1)
+        if clip is not None:
+            max_norm, state, scratch = clip
+            _lib.check(lib.fira_train_step_clip(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
+                                                _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
+                                                C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), C.byref(adam),
+                                                _lib.ptr(row_step), float(max_norm), _lib.ptr(state), _lib.ptr(scratch)),
+                       "fira_train_step_clip")
+            return self.loss_sum, self.n_tok
         if row_step is not None:
             _lib.check(lib.fira_train_step_rows(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
                                                 _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
@@ -561,12 +571,15 @@ class TransModel(nn.Module):
         return self.loss_sum, self.n_tok
 
     def train_step_end(self, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, early_event=None, count=None,
-                       beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, row_step=None):
+                       beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, row_step=None, update: bool = True):
         """Second half (fira_train_step_end): the encoder's backward pass; Adam of ``[0, split)`` once the current stream has
         passed ``early_event`` (the caller's event behind the all-reduce of that slice), scaled by ``1 / count`` (a device
-        float, the all-reduced token count).  ``[split, live)`` is left to the caller (its bucket is reduced afterwards)."""
+        float, the all-reduced token count).  ``[split, live)`` is left to the caller (its bucket is reduced afterwards).
+        ``update=False``: the backward pass only (adam = NULL) -- the caller updates both slices itself (clipped steps)."""
         adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v))
-        if row_step is not None:
+        if not update:
+            _lib.check(_lib.lib().fira_train_step_end(_lib.cur_stream(), None, None, None, None), "fira_train_step_end")
+        elif row_step is not None:
             _lib.check(_lib.lib().fira_train_step_end_rows(_lib.cur_stream(), _lib.ptr(self.flat.data), C.byref(adam),
                                                            self._event_handle(early_event), _lib.ptr(count), _lib.ptr(row_step)),
                        "fira_train_step_end_rows")

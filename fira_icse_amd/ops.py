@@ -461,6 +461,45 @@ def adam_step_mb(p, g0, g1, m, v, lr, step, n_tok0, n_tok1=None, beta1=0.9, beta
           "fira_adam_step_mb")
 
 
+def clip_state(device="cuda"):
+    """A zeroed fira_clip_state on the device (16 int32 = 64 bytes) and the scratch fira_grad_sqsum sums through."""
+    state = torch.zeros(16, dtype=torch.int32, device=device)
+    scratch = torch.zeros(_lib.lib().fira_grad_sqsum_scratch_bytes() // 8, dtype=torch.float64, device=device)
+    return state, scratch
+
+
+def read_clip_state(state):
+    """The fields of a device fira_clip_state as a dict (synchronises)."""
+    st = _lib.ClipState.from_buffer_copy(state.cpu().numpy().tobytes())
+    return {"sq": list(st.sq), "norm": st.norm, "coef": st.coef, "zero_flag": st.zero_flag, "n_clipped": st.n_clipped,
+            "n_nonfinite": st.n_nonfinite}
+
+
+def grad_sqsum_depth(n: int) -> int:
+    """D of fira_grad_sqsum for a range of n floats: the fp32 roundings one value can pass through (csrc/gradnorm.hip); the
+    result is within (D + 1) * 2^-24 relative of the exact sum of squares."""
+    n4 = n // 4
+    slice4 = -(-(-(-n4 // 1024)) // 1024) * 1024
+    return slice4 // 1024 + 12
+
+
+def grad_sqsum(g, state, slot, scratch):
+    """state.sq[slot] = sum of g^2 over the contiguous fp32 tensor g (fira_grad_sqsum)."""
+    assert g.dtype == torch.float32 and g.is_contiguous()
+    check(_lib.lib().fira_grad_sqsum(cur_stream(), g.numel(), ptr(g), ptr(state), slot, ptr(scratch)), "fira_grad_sqsum")
+
+
+def clip_finish(state, n_slots, max_norm, n_tok=None, count=None):
+    """norm / coef / zero_flag / counters from state.sq[0 .. n_slots) (fira_clip_finish); normaliser from n_tok or count."""
+    check(_lib.lib().fira_clip_finish(cur_stream(), ptr(state), n_slots, ptr(n_tok), ptr(count), max_norm), "fira_clip_finish")
+
+
+def adam_step_clip(p, g, m, v, lr, step, state, n_tok=None, count=None, beta1=0.9, beta2=0.999, eps=1e-8):
+    """adam_step_mb (n_tok) / adam_step_count (count) on g * inv * coef of the clip state, or on zeros under its zero flag."""
+    check(_lib.lib().fira_adam_step_clip(cur_stream(), p.numel(), ptr(_f32(p)), ptr(_f32(g)), ptr(_f32(m)), ptr(_f32(v)), lr,
+                                         beta1, beta2, eps, step, ptr(n_tok), ptr(count), ptr(state)), "fira_adam_step_clip")
+
+
 def inv_count(n_tok, out):
     check(_lib.lib().fira_inv_count(cur_stream(), ptr(_i32(n_tok)), ptr(_f32(out))), "fira_inv_count")
     return out

@@ -19,11 +19,21 @@ from .parallel import GradReducer, ShardedOptimizerComm
 
 class Trainer:
     def __init__(self, model: TransModel, lr: Optional[float] = None, betas=(0.9, 0.999), eps: float = 1e-8,
-                 distributed: bool = False, zero1: bool = False, grad_wire: str = "f32"):
+                 distributed: bool = False, zero1: bool = False, grad_wire: str = "f32",
+                 clip_grad_norm: Optional[float] = None):
         """``zero1`` (with ``distributed``): reduce-scatter + Adam on the owned 1/world shard + all-gather instead of
         all-reduce + replicated Adam; Adam moments exist only for the owned shard (parallel.ShardedOptimizerComm).
         ``grad_wire`` (with ``distributed``, all-reduce path): "f32", or "bf16" = the two gradient buckets travel as bf16
-        (half the bytes on xGMI; parallel.GradReducer)."""
+        (half the bytes on xGMI; parallel.GradReducer).
+        ``clip_grad_norm`` (``None`` = off: the code path of every release so far): the gradient is clipped to this global norm
+        on the device (``torch.nn.utils.clip_grad_norm_``; ``inf`` = observe and guard only) and a step whose gradient holds
+        an ``inf`` / ``nan`` is applied as a zero-gradient step instead of destroying the weights; see :meth:`last_grad_norm`."""
+        self.clip = None
+        if clip_grad_norm is not None:
+            self.clip = float(clip_grad_norm)
+            if not self.clip > 0:                                # (also refuses nan)
+                raise ValueError("clip_grad_norm must be > 0 (inf allowed), not %r" % (clip_grad_norm,))
+            self.clip_state, self.clip_scratch = ops.clip_state(model.gbuf.device)
         self.model = model
         self.lr = model.cfg.lr if lr is None else lr
         self.betas, self.eps = betas, eps
@@ -90,7 +100,9 @@ class Trainer:
         elif self.fused_step and self.reducer is None and self.zero is None:
             self._rows_check_hyper()
             self.t += 1
-            m.train_step(db, self.m, self.v, self.lr, self.t, self.betas[0], self.betas[1], self.eps, row_step=self.row_step)
+            clip = None if self.clip is None else (self.clip, self.clip_state, self.clip_scratch)
+            m.train_step(db, self.m, self.v, self.lr, self.t, self.betas[0], self.betas[1], self.eps, row_step=self.row_step,
+                         clip=clip)
             self._rows_dirty = self.row_step is not None
             return
         elif dp and self.fused_dp and self.zero is None:
@@ -113,6 +125,22 @@ class Trainer:
             ev = red.reduce_early(m.gbuf, self.stats, self.mid_event, pack=lambda: ops.pack_stats(loss_sum, n_tok, self.stats))
             self.t += 1
             count = self.stats[1:2]
+            if self.clip is not None:
+                # clipped: every update waits for the norm of the ALL-REDUCED gradient (every rank sums the same numbers, bf16
+                # wire included, and takes the same decision).  The encoder's backward pass runs without an update; the sum
+                # of squares of each bucket follows its all-reduce, the closing step uses the global token count.
+                if fused_dp:
+                    m.train_step_end(self.m, self.v, self.lr, self.t, update=False)
+                red.wait_early()
+                ops.grad_sqsum(m.gbuf[:split], self.clip_state, 0, self.clip_scratch)
+                red.start_late(m.gbuf)
+                red.wait_late(m.gbuf)
+                ops.grad_sqsum(m.gbuf[split:live], self.clip_state, 1, self.clip_scratch)
+                ops.clip_finish(self.clip_state, 2, self.clip, count=count)
+                self._adam_slice(0, split, count, table=0)
+                self._adam_slice(split, live, count, table=1)
+                self._rows_dirty = self.row_step is not None
+                return
             if fused_dp:
                 # encoder backward; Adam of [0, split) inside the library as soon as the caller's stream has passed the
                 # encoder's chain and `ev`, beside the last weight gradients; the join
@@ -134,6 +162,12 @@ class Trainer:
         # was measured on one box: 8 497 vs 8 553 commits/s -- the HBM-bound update only slows the backward kernels it
         # overlaps; profiles/r2_probes.md.)
         n = m.layout.live
+        if self.clip is not None:
+            ops.grad_sqsum(m.gbuf[:n], self.clip_state, 0, self.clip_scratch)
+            ops.clip_finish(self.clip_state, 1, self.clip, n_tok=n_tok)
+            ops.adam_step_clip(m.flat.data[:n], m.gbuf[:n], self.m[:n], self.v[:n], self.lr, self.t, self.clip_state,
+                               n_tok=n_tok, beta1=b1, beta2=b2, eps=self.eps)
+            return
         ops.adam_step_mb(m.flat.data[:n], m.gbuf[:n], None, self.m[:n], self.v[:n], self.lr, self.t, n_tok, None, b1, b2,
                          self.eps)
 
@@ -151,6 +185,27 @@ class Trainer:
         self.end_event.record(main)                            # backward pass done, global token count known
         self.t += 1
         zs.wait_event(self.end_event)
+        if self.clip is not None:
+            # clipped: each rank sums the squares of its owned shards, one extra all-reduce of the two scalars gives every
+            # rank the same global sums (a rank with an empty shard contributes zeros), then the clipped update on the shards
+            with torch.cuda.stream(zs):
+                for b in (0, 1):
+                    if b == 1:
+                        z.reduce_scatter(1, m.gbuf, self.g_sh[1])
+                    lo, hi = z.owned(b)
+                    ops.grad_sqsum(self.g_sh[b][:hi - lo], self.clip_state, b, self.clip_scratch)
+                sq = self.clip_state.view(torch.float32)[0:2]
+                torch.distributed.all_reduce(sq, op=torch.distributed.ReduceOp.SUM, group=z.group)
+                ops.clip_finish(self.clip_state, 2, self.clip, count=self.stats[1:2])
+                for b in (0, 1):
+                    lo, hi = z.owned(b)
+                    if hi > lo:
+                        n = hi - lo
+                        ops.adam_step_clip(m.flat.data[lo:hi], self.g_sh[b][:n], self.m_sh[b][:n], self.v_sh[b][:n], self.lr,
+                                           self.t, self.clip_state, count=self.stats[1:2], beta1=b1, beta2=b2, eps=self.eps)
+                    z.all_gather(b, m.flat.data)
+            main.wait_stream(zs)
+            return
         with torch.cuda.stream(zs):
             for b in (0, 1):
                 if b == 1:
@@ -179,10 +234,20 @@ class Trainer:
             import ctypes as C
             self._rows_check_hyper()
             adam = _lib.AdamOpts(self.lr, b1, b2, self.eps, int(self.t), _lib.ptr(self.m), _lib.ptr(self.v))
-            _lib.check(_lib.lib().fira_adam_rows_step(_lib.cur_stream(), C.byref(m.dims), _lib.ptr(m.flat.data), _lib.ptr(m.gbuf),
-                                                      C.byref(adam), _lib.ptr(self.row_step), None, _lib.ptr(count), 1 << table),
-                       "fira_adam_rows_step")
+            if self.clip is not None:
+                _lib.check(_lib.lib().fira_adam_rows_step_clip(_lib.cur_stream(), C.byref(m.dims), _lib.ptr(m.flat.data),
+                                                               _lib.ptr(m.gbuf), C.byref(adam), _lib.ptr(self.row_step), None,
+                                                               _lib.ptr(count), 1 << table, _lib.ptr(self.clip_state)),
+                           "fira_adam_rows_step_clip")
+            else:
+                _lib.check(_lib.lib().fira_adam_rows_step(_lib.cur_stream(), C.byref(m.dims), _lib.ptr(m.flat.data),
+                                                          _lib.ptr(m.gbuf), C.byref(adam), _lib.ptr(self.row_step), None,
+                                                          _lib.ptr(count), 1 << table), "fira_adam_rows_step")
             lo += m.cfg.vocab_size * 256
+        if self.clip is not None:
+            ops.adam_step_clip(m.flat.data[lo:hi], m.gbuf[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lr, self.t, self.clip_state,
+                               count=count, beta1=b1, beta2=b2, eps=self.eps)
+            return
         ops.adam_step_count(m.flat.data[lo:hi], m.gbuf[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lr, self.t, count, b1, b2,
                             self.eps)
 
@@ -207,6 +272,15 @@ class Trainer:
         else:
             s = [float(self.model.loss_sum.item()), float(self.model.n_tok.item())]
         return s[0] / max(s[1], 1.0)
+
+    def last_grad_norm(self):
+        """``(norm, coef, n_clipped, n_nonfinite)`` of the last step with ``clip_grad_norm``: the global norm of the (global)
+        batch's mean-token-loss gradient before clipping, the factor the update applied, and how many steps so far were
+        clipped / were applied as zero-gradient steps because the norm was not finite.  Synchronises, like :meth:`last_loss`."""
+        if self.clip is None:
+            raise RuntimeError("last_grad_norm: this Trainer was built without clip_grad_norm")
+        st = ops.read_clip_state(self.clip_state)
+        return st["norm"], st["coef"], st["n_clipped"], st["n_nonfinite"]
 
     def state_dict(self):
         """Everything a restart needs besides the weights: Adam moments, Adam step and the dropout step counter (so

@@ -140,7 +140,8 @@ size_t fira_decode_workspace_bytes(const fira_dims* d, int B, int n_beam);
 size_t fira_decode_workspace_bytes_ex(const fira_dims* d, int B, int n_beam, int flags);
 
 /* Per-kernel-class HIP-event profiling (bench.py's roofline leg).  Classes: 0 GEMM (work = FLOP), 1 CSR SpMM
- * (work = algorithmic bytes), 2 attention, 3 row ops, 4 copy score, 5 head/loss, 6 Adam.  report() synchronises,
+ * (work = algorithmic bytes), 2 attention, 3 row ops, 4 copy score, 5 head/loss, 6 Adam (with clipping on: the sum of squares
+ * of the gradient is booked here too).  report() synchronises,
  * returns per class the summed event time [ms], summed work and launch count since the last report, and resets. */
 #define FIRA_PROF_NCLASS 7
 /* two more classes are reported when n_class asks for them: 7 = the decoder's M = B*30 products (a sub-set of class 0's
@@ -565,6 +566,56 @@ int fira_train_step_begin_rows(void* stream, const fira_dims* d, const fira_batc
                                int32_t* n_tok, void* mid_event, const fira_adam_opts* adam, int32_t* row_step);
 int fira_train_step_end_rows(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count,
                              int32_t* row_step);
+
+/* Clipping by the GLOBAL gradient norm on the device (torch.nn.utils.clip_grad_norm_ between run_model.py:108 and :111,
+ * error_if_nonfinite = False) and a guard against non-finite gradients.  With g the flat loss-SUM gradient of [0, live) and
+ * inv = 1 / max(n_tok, 1) (or 1 / max(count, 1), the all-reduced token count of a data-parallel step), for max_norm C > 0
+ * (C = inf allowed: observe and guard only):
+ *     norm = inv * sqrt(sum_i g_i^2) ;   coef = min(1, C / (norm + 1e-6)) ;   Adam sees g_i * inv * coef
+ *   - coef == 1: the update is bit-identical to the unclipped kernels' on the same buffers;
+ *   - norm not finite (an inf / nan gradient element, or a sum of squares that overflows fp32: an element above about 1.8e19 on
+ *     the loss-SUM scale; torch's fp32 norm overflows alike): the step is applied as a ZERO-GRADIENT step -- every element takes g_i := 0, the
+ *     step number advances as usual, n_nonfinite counts it.  (Not "leave p, m, v untouched": the host does not know the outcome
+ *     without a sync, the bias corrections come from the step number, and the row-sparse update owes untouched rows exactly one
+ *     zero-gradient update per step: dense and row-sparse stay equal bit for bit, and every rank of a data-parallel run takes
+ *     the same decision from the same all-reduced numbers.)
+ * fira_clip_state (device memory, 64 bytes, zero-initialised by the caller once) carries the result from the norm to the updates:
+ * sq[k] = the sum of squares of the k-th range it was given (the two readiness buckets; ZeRO-1's shards), norm, coef, zero_flag
+ * of the last closing step, and two running counters.
+ *   fira_grad_sqsum   state->sq[slot] = sum of g[0, n)^2 (n < 2^31, g 16-byte aligned, n = 0 gives 0).  Fixed summation order (no
+ *                     atomics; partials added in a fixed strided + tree order, in double): the same bits on every call and graph replay; relative error <= (D + 1) * 2^-24 against the exact sum,
+ *                     D = roundup(ceil((n / 4) / 1024), 1024) / 1024 + 12 (19 for the model's live parameters).  scratch:
+ *                     fira_grad_sqsum_scratch_bytes() bytes, 8-byte aligned; slots use disjoint parts of it.
+ *   fira_clip_finish  norm / coef / zero_flag / counters from sq[0 .. n_slots), n_slots <= 4; n_tok or count as above.
+ *   fira_adam_step_clip / fira_adam_rows_step_clip   fira_adam_step_mb (g1 = NULL) / fira_adam_step_count (count != NULL) and
+ *                     fira_adam_rows_step on g * inv * coef, or on a zero gradient under zero_flag.
+ *   fira_train_step_clip   fira_train_step_rows (row_step given) / fira_train_step (row_step NULL) with the clipped update: the
+ *                     sum of squares of [0, split) runs beside the encoder's backward pass, that of [split, live), the closing
+ *                     step and the whole update behind the final join (the early update of [0, split) is what clipping costs).
+ *                     scratch as for fira_grad_sqsum.  Nothing synchronises, nothing allocates.                                  */
+typedef struct fira_clip_state {
+    float   sq[4];
+    float   norm;            /* of the last closing step (inf / nan when the gradient was not finite)   */
+    float   coef;            /* what the updates multiply by (1 under zero_flag)                        */
+    int32_t zero_flag;       /* 1: the updates take a zero gradient                                     */
+    int32_t n_clipped;       /* closing steps with coef < 1                                             */
+    int32_t n_nonfinite;     /* closing steps with a non-finite norm                                    */
+    int32_t reserved[7];
+} fira_clip_state;
+size_t fira_grad_sqsum_scratch_bytes(void);
+int fira_grad_sqsum(void* stream, int64_t n, const float* g, fira_clip_state* state, int slot, void* scratch);
+int fira_clip_finish(void* stream, fira_clip_state* state, int n_slots, const int32_t* n_tok, const float* count,
+                     float max_norm);
+int fira_adam_step_clip(void* stream, int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
+                        float beta2, float eps, int step, const int32_t* n_tok, const float* count,
+                        const fira_clip_state* state);
+int fira_adam_rows_step_clip(void* stream, const fira_dims* d, float* params, const float* grads, const fira_adam_opts* adam,
+                             int32_t* row_step, const int32_t* n_tok, const float* count, int tables,
+                             const fira_clip_state* state);
+int fira_train_step_clip(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads,
+                         void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
+                         int32_t* n_tok, const fira_adam_opts* adam, int32_t* row_step /* may be NULL */, float max_norm,
+                         fira_clip_state* state, void* scratch);
 
 /* (v8) bf16 wire format of a gradient bucket (BASELINE configs[2]: 55.6 MB instead of 111.2 MB per step on xGMI):
  * out[i] = bf16(in[i]) (round to nearest even) / out[i] = float(in[i]).  n % 4 == 0, 16-byte aligned buffers. */

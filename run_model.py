@@ -93,8 +93,13 @@ def parse_args(argv):
     ap.add_argument("--rerank", default=None, choices=RERANK_KEYS, help="with --sample: score the drawn candidates in the same "
                     "run and write the best one under this key to OUTPUT/output_fira (default: the candidate of highest "
                     "log-probability of the drawn entries)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
+                    "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
+                    "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
+                    "--loss-log line then carries grad_norm and clip_coef")
     a = ap.parse_args(argv)
     try:
+        check_clip_args(a)
         check_score_args(a)
         check_sample_args(a)
     except ValueError as e:
@@ -103,6 +108,18 @@ def parse_args(argv):
 
 
 RERANK_KEYS = ("logp_word", "mean_logp_word")
+
+
+def check_clip_args(a):
+    """Validates --clip-grad-norm (no GPU, no DataSet needed); raises ValueError on a conflict or an out-of-range value."""
+    c = a.clip_grad_norm
+    if c is None:
+        return a
+    if a.stage != "train":
+        raise ValueError("--clip-grad-norm only applies to the train stage")
+    if not c > 0:                                            # (also refuses nan)
+        raise ValueError("--clip-grad-norm %g: must be > 0 (inf = observe and guard only)" % c)
+    return a
 
 
 def check_score_args(a):
@@ -261,7 +278,8 @@ class Run:
         self.model.compute_dtype = a.dtype
         self.model.set_dropout_stream(a.seed, self.rank)           # masks depend on (--seed, rank, step)
         wire = a.grad_wire if a.grad_wire != "auto" else ("bf16" if a.dtype == "bf16" else "f32")
-        trainer = Trainer(self.model, lr=cfg.lr, distributed=self.world > 1, zero1=a.zero1, grad_wire=wire)
+        trainer = Trainer(self.model, lr=cfg.lr, distributed=self.world > 1, zero1=a.zero1, grad_wire=wire,
+                          clip_grad_norm=a.clip_grad_norm)
         state_path = os.path.join(self.root, "fira_train_state.pt")
         if a.resume and os.path.exists(state_path):
             trainer.load_state_dict(torch.load(state_path, map_location=self.model.device_))
@@ -297,9 +315,11 @@ class Run:
                 total_data += len(gidx)
                 steps += 1
                 if a.loss_log and self.rank == 0:
+                    rec = {"epoch": epoch, "batch": idx_b, "index": [int(i) for i in gidx], "loss": trainer.last_loss()}
+                    if a.clip_grad_norm is not None:
+                        rec["grad_norm"], rec["clip_coef"] = trainer.last_grad_norm()[:2]
                     with open(a.loss_log, "a") as f:
-                        f.write(json.dumps({"epoch": epoch, "batch": idx_b, "index": [int(i) for i in gidx],
-                                            "loss": trainer.last_loss()}) + "\n")
+                        f.write(json.dumps(rec) + "\n")
                 if idx_b % 10 == 0 and self.rank == 0:
                     print("epoch: %d batch: %d/%d  data: %d/%d loss: %.4f  (%.1f commits/s)" % (
                         epoch, idx_b, n_batches, total_data, len(store), trainer.last_loss(),
@@ -307,6 +327,10 @@ class Run:
                 if a.max_steps and steps >= a.max_steps:
                     break
             batches.close()                          # stops the worker thread and drops its prepared batches
+            if a.clip_grad_norm is not None and self.rank == 0:
+                _, _, n_clipped, n_nonfinite = trainer.last_grad_norm()      # running counts since the start of the run
+                print("epoch: %d  clipped steps so far: %d  non-finite (zero-gradient) steps so far: %d of %d" % (
+                    epoch, n_clipped, n_nonfinite, steps), flush=True)
             if a.max_steps and steps >= a.max_steps:
                 break
         if best_bleu < 0:                               # never reached a dev point (short runs): keep the last weights
