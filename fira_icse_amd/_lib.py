@@ -40,9 +40,21 @@ class TrainOpts(C.Structure):
                 ("dtype", C.c_int32), ("compact_dec", C.c_int32), ("zero_grads", C.c_int32)]
 
 
+class LrSchedule(C.Structure):
+    """fira_lr_schedule: kind 0 constant, 1 inv_sqrt, 2 cosine, 3 linear (include/fira_hip.h has the formulas)."""
+    _fields_ = [("kind", C.c_int32), ("base_lr", C.c_float), ("warmup_steps", C.c_int32), ("decay_steps", C.c_int32),
+                ("min_lr", C.c_float)]
+
+
 class AdamOpts(C.Structure):
+    # sched (trailing, zero-filled when a caller stops at v): NULL = every step uses lr
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int32),
-                ("m", C.c_void_p), ("v", C.c_void_p)]
+                ("m", C.c_void_p), ("v", C.c_void_p), ("sched", C.POINTER(LrSchedule))]
+
+
+def sched_ptr(sched):
+    """``AdamOpts.sched`` for an ``LrSchedule`` (or ``None``); the caller keeps the struct alive for the call."""
+    return None if sched is None else C.pointer(sched)
 
 
 class ClipState(C.Structure):
@@ -129,6 +141,8 @@ SIGNATURES = {
     "fira_adam_step_clip": (_I, [_P, _L, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P, _P, _P]),
     "fira_adam_rows_step_clip": (_I, [_P, _DP, _P, _P, C.POINTER(AdamOpts), _P, _P, _P, _I, _P]),
     "fira_train_step_clip": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, C.POINTER(AdamOpts), _P, _F, _P, _P]),
+    "fira_lr_at": (_F, [C.POINTER(LrSchedule), _I]),
+    "fira_lr_schedule_check": (_I, [C.POINTER(LrSchedule)]),
     "fira_train_step_begin": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, _P]),
     "fira_train_step_end": (_I, [_P, _P, C.POINTER(AdamOpts), _P, _P]),
     "fira_f32_to_bf16": (_I, [_P, _L, _P, _P]),

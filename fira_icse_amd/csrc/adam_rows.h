@@ -20,10 +20,13 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float gi
     p = __builtin_fmaf(-step_size, mi / denom, p);
 }
 
-__device__ __forceinline__ void adam_row_zero_steps(float4& pv, float4& mv, float4& vv, int from, int to, float gz, float lr,
+__device__ __forceinline__ void adam_row_zero_steps(float4& pv, float4& mv, float4& vv, int from, int to, float gz,
                                                     float beta1, float beta2, float eps, const AdamRowsHist& h) {
     for (int j = from; j <= to; ++j) {                    // the updates of steps from..to with a zero gradient row
-        const float ss = lr / h.bc1[j % ADAM_ROWS_K], b2s = h.bc2s[j % ADAM_ROWS_K];
+        // (j is wave-uniform at every call site but held in a vector register: as a scalar index the three ring entries of the
+        //  step come from the argument block by scalar loads instead of occupying a vector register each)
+        const int k = __builtin_amdgcn_readfirstlane(j % ADAM_ROWS_K);
+        const float ss = h.lr[k] / h.bc1[k], b2s = h.bc2s[k];
         adam_elem(pv.x, mv.x, vv.x, gz, beta1, beta2, eps, ss, b2s);
         adam_elem(pv.y, mv.y, vv.y, gz, beta1, beta2, eps, ss, b2s);
         adam_elem(pv.z, mv.z, vv.z, gz, beta1, beta2, eps, ss, b2s);
@@ -41,7 +44,7 @@ __device__ __forceinline__ float4 adam_rows_load(const float* __restrict__ table
         const int l = max(vw.last[row], vw.to - (ADAM_ROWS_K - 1));
         if (l < vw.to) {                                          // wave-uniform
             float4 mv = *reinterpret_cast<const float4*>(vw.m + o), vv = *reinterpret_cast<const float4*>(vw.v + o);
-            adam_row_zero_steps(pv, mv, vv, l + 1, vw.to, vw.gz, vw.lr, vw.beta1, vw.beta2, vw.eps, vw.h);
+            adam_row_zero_steps(pv, mv, vv, l + 1, vw.to, vw.gz, vw.beta1, vw.beta2, vw.eps, vw.h);
         }
     }
     return pv;

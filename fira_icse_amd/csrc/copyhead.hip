@@ -558,10 +558,11 @@ __global__ __launch_bounds__(256) void adam_mb_kernel(int64_t n, float* __restri
 // training step then moves 28 bytes per parameter only for the rows its batch touched (12 % / 1.5 % of the two tables at
 // batch 32) instead of for all 2 x 6.3 M of them: -330 MB of the 780 MB the dense update moves.  Every ADAM_ROWS_K-th step
 // updates every row (force), so a catch-up never spans more than ADAM_ROWS_K - 1 steps and the bias corrections of the
-// skipped steps fit the kernel's argument block (AdamRowsHist: host-computed exactly as adam_step_mb computes its own).
-// lr / beta / eps must not change inside a window without a sync (fira_adam_rows_sync).  One wave per 256-float row.
+// skipped steps fit the kernel's argument block (AdamRowsHist: host-computed exactly as adam_step_mb computes its own), and so
+// does the learning rate of each of them (h.lr: a schedule is a function of the step number, fira_lr_at).
+// beta / eps / the schedule must not change inside a window without a sync (fira_adam_rows_sync).  One wave per 256-float row.
 // gz: a zero the compiler cannot see through (the skipped updates must run the instruction sequence of the dense kernel)
-__global__ __launch_bounds__(256) void adam_rows_kernel(AdamRowsTables tb, const float* __restrict__ gbase, float lr,
+__global__ __launch_bounds__(256) void adam_rows_kernel(AdamRowsTables tb, const float* __restrict__ gbase,
                                                         float beta1, float beta2, float eps, int step, AdamRowsHist h,
                                                         const int32_t* __restrict__ n0, const float* __restrict__ count,
                                                         int force, float gz, int it_lo, int it_hi) {
@@ -571,7 +572,7 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(AdamRowsTables tb, const
     const int lane = threadIdx.x & 63;
     const int nw = gridDim.x * 4;
     const int total = it_hi;                              // rows it_lo .. it_hi of the two tables' combined row space
-    const float ss = lr / h.bc1[step % ADAM_ROWS_K], b2s = h.bc2s[step % ADAM_ROWS_K];
+    const float ss = h.lr[step % ADAM_ROWS_K] / h.bc1[step % ADAM_ROWS_K], b2s = h.bc2s[step % ADAM_ROWS_K];
     // four gradient rows requested per trip (the launch is a stream of 1 KB reads with a wave-uniform skip: one row per trip
     // left it latency-bound at 2.5 TB/s)
     for (int it0 = it_lo + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4; it0 < total; it0 += nw * 4) {
@@ -595,7 +596,7 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(AdamRowsTables tb, const
             const int l = max(tb.last[it], step - ADAM_ROWS_K);
             float4 pv = *reinterpret_cast<float4*>(tb.p + o), mv = *reinterpret_cast<float4*>(tb.m + o),
                    vv = *reinterpret_cast<float4*>(tb.v + o);
-            adam_row_zero_steps(pv, mv, vv, l + 1, step - 1, gz, lr, beta1, beta2, eps, h);
+            adam_row_zero_steps(pv, mv, vv, l + 1, step - 1, gz, beta1, beta2, eps, h);
             adam_elem(pv.x, mv.x, vv.x, gv.x * scale, beta1, beta2, eps, ss, b2s);
             adam_elem(pv.y, mv.y, vv.y, gv.y * scale, beta1, beta2, eps, ss, b2s);
             adam_elem(pv.z, mv.z, vv.z, gv.z * scale, beta1, beta2, eps, ss, b2s);
@@ -609,7 +610,7 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(AdamRowsTables tb, const
 }
 // Rows brought up to step `to` (zero-gradient updates only): the rows listed in the id arrays of `ls` (duplicates and
 // out-of-range ids allowed: a row is claimed through atomicMax on last[]), or, with no list, every row of both tables.
-__global__ __launch_bounds__(256) void adam_rows_catchup_kernel(AdamRowsTables tb, AdamRowsLists ls, float lr, float beta1,
+__global__ __launch_bounds__(256) void adam_rows_catchup_kernel(AdamRowsTables tb, AdamRowsLists ls, float beta1,
                                                                 float beta2, float eps, int to, AdamRowsHist h, float gz) {
     const int lane = threadIdx.x & 63;
     const int nw = gridDim.x * 4;
@@ -636,7 +637,7 @@ __global__ __launch_bounds__(256) void adam_rows_catchup_kernel(AdamRowsTables t
         const size_t o = (size_t)tb.off[t] + (size_t)r * 256 + lane * 4;
         float4 pv = *reinterpret_cast<float4*>(tb.p + o), mv = *reinterpret_cast<float4*>(tb.m + o),
                vv = *reinterpret_cast<float4*>(tb.v + o);
-        adam_row_zero_steps(pv, mv, vv, l + 1, to, gz, lr, beta1, beta2, eps, h);
+        adam_row_zero_steps(pv, mv, vv, l + 1, to, gz, beta1, beta2, eps, h);
         *reinterpret_cast<float4*>(tb.p + o) = pv;
         *reinterpret_cast<float4*>(tb.m + o) = mv;
         *reinterpret_cast<float4*>(tb.v + o) = vv;
@@ -936,25 +937,26 @@ int adam_step_mb(hipStream_t s, int64_t n, float* p, const float* g0, const floa
     FIRA_CHECK_LAUNCH("adam_step_mb");
     return 0;
 }
-AdamRowsHist adam_rows_hist(float beta1, float beta2, int end) {
+AdamRowsHist adam_rows_hist(const AdamLr& lr, float beta1, float beta2, int end) {
     AdamRowsHist h;
-    for (int k = 0; k < ADAM_ROWS_K; ++k) h.bc1[k] = h.bc2s[k] = 1.f;
+    for (int k = 0; k < ADAM_ROWS_K; ++k) { h.bc1[k] = h.bc2s[k] = 1.f; h.lr[k] = lr.lr; }
     for (int j = std::max(1, end - ADAM_ROWS_K + 1); j <= end; ++j) {       // as adam_step_mb forms them for step j
         h.bc1[j % ADAM_ROWS_K] = (float)(1.0 - pow((double)beta1, j));
         h.bc2s[j % ADAM_ROWS_K] = (float)sqrt(1.0 - pow((double)beta2, j));
+        h.lr[j % ADAM_ROWS_K] = lr.at(j);                                   // the float a dense launch of step j is given
     }
     return h;
 }
-AdamRowsView adam_rows_view(const AdamRowsTables& tb, int table, float lr, float beta1, float beta2, float eps, int to) {
+AdamRowsView adam_rows_view(const AdamRowsTables& tb, int table, const AdamLr& lr, float beta1, float beta2, float eps, int to) {
     AdamRowsView vw;
     if (to < 1) return vw;                                   // nothing owed ahead of step 1
     vw.m = tb.m + tb.off[table]; vw.v = tb.v + tb.off[table];
     vw.last = tb.last + (table ? tb.rows[0] : 0);
-    vw.to = to; vw.lr = lr; vw.beta1 = beta1; vw.beta2 = beta2; vw.eps = eps; vw.gz = 0.f;
-    vw.h = adam_rows_hist(beta1, beta2, to);
+    vw.to = to; vw.beta1 = beta1; vw.beta2 = beta2; vw.eps = eps; vw.gz = 0.f;
+    vw.h = adam_rows_hist(lr, beta1, beta2, to);
     return vw;
 }
-int adam_rows_step(hipStream_t s, const AdamRowsTables& tb, const float* g, float lr, float beta1, float beta2, float eps,
+int adam_rows_step(hipStream_t s, const AdamRowsTables& tb, const float* g, const AdamLr& lr, float beta1, float beta2, float eps,
                    int step, const int32_t* n0, const float* count, int tables) {
     ProfScope prof(s, PROF_ADAM, 0.0);
     FIRA_REQUIRE(step >= 1 && tb.last && (n0 || count), "adam_rows_step: bad argument");
@@ -962,12 +964,12 @@ int adam_rows_step(hipStream_t s, const AdamRowsTables& tb, const float* g, floa
     const int total = it_hi - it_lo;
     if (total <= 0) return 0;
     const int grid = std::min(cdiv(total, 16), 256 * 8);
-    hipLaunchKernelGGL(adam_rows_kernel, dim3(grid), dim3(256), 0, s, tb, g, lr, beta1, beta2, eps, step,
-                       adam_rows_hist(beta1, beta2, step), n0, count, step % ADAM_ROWS_K == 0 ? 1 : 0, 0.0f, it_lo, it_hi);
+    hipLaunchKernelGGL(adam_rows_kernel, dim3(grid), dim3(256), 0, s, tb, g, beta1, beta2, eps, step,
+                       adam_rows_hist(lr, beta1, beta2, step), n0, count, step % ADAM_ROWS_K == 0 ? 1 : 0, 0.0f, it_lo, it_hi);
     FIRA_CHECK_LAUNCH("adam_rows_step");
     return 0;
 }
-int adam_rows_catchup(hipStream_t s, const AdamRowsTables& tb, const AdamRowsLists* ls, float lr, float beta1, float beta2,
+int adam_rows_catchup(hipStream_t s, const AdamRowsTables& tb, const AdamRowsLists* ls, const AdamLr& lr, float beta1, float beta2,
                       float eps, int to) {
     ProfScope prof(s, PROF_ADAM, 0.0);
     FIRA_REQUIRE(tb.last, "adam_rows_catchup: bad argument");
@@ -977,8 +979,8 @@ int adam_rows_catchup(hipStream_t s, const AdamRowsTables& tb, const AdamRowsLis
     const int total = l.n_lists ? l.end[l.n_lists - 1] : tb.rows[0] + tb.rows[1];
     if (total <= 0) return 0;
     const int grid = std::min(cdiv(total, 4), 256 * 8);
-    hipLaunchKernelGGL(adam_rows_catchup_kernel, dim3(grid), dim3(256), 0, s, tb, l, lr, beta1, beta2, eps, to,
-                       adam_rows_hist(beta1, beta2, to), 0.0f);
+    hipLaunchKernelGGL(adam_rows_catchup_kernel, dim3(grid), dim3(256), 0, s, tb, l, beta1, beta2, eps, to,
+                       adam_rows_hist(lr, beta1, beta2, to), 0.0f);
     FIRA_CHECK_LAUNCH("adam_rows_catchup");
     return 0;
 }

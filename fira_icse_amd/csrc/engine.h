@@ -315,7 +315,22 @@ int adam_step_mb(hipStream_t s, int64_t n, float* p, const float* g0, const floa
 // off[t] / rows[t]: first float and row count of table t (0 = decoder.embedding, 1 = encoder.embedding; 256 floats per row);
 // last [rows[0] + rows[1]]: the step up to which each row is current.
 constexpr int ADAM_ROWS_K = 32;            // every K-th step updates every row: a catch-up spans at most K - 1 steps
-struct AdamRowsHist { float bc1[ADAM_ROWS_K], bc2s[ADAM_ROWS_K]; };          // bias corrections of step j at [j % K]
+// bias corrections and learning rate of step j at [j % K]
+struct AdamRowsHist { float bc1[ADAM_ROWS_K], bc2s[ADAM_ROWS_K], lr[ADAM_ROWS_K]; };
+// the rate of every step: the caller's constant or fira_lr_at of a schedule (a COPY of it: a begun data-parallel step outlives
+// the call that passed the pointer)
+struct AdamLr {
+    float lr = 0.f;
+    bool scheduled = false;
+    fira_lr_schedule sched{};
+    float at(int step) const { return scheduled ? fira_lr_at(&sched, step) : lr; }
+};
+inline AdamLr adam_lr(const fira_adam_opts& ad) {
+    AdamLr r;
+    r.lr = ad.lr;
+    if (ad.sched) { r.scheduled = true; r.sched = *ad.sched; }
+    return r;
+}
 struct AdamRowsTables { float *p, *m, *v; int64_t off[2]; int rows[2]; int32_t* last; };
 // a lazily updated table seen by a forward gather (adam_rows.h: adam_rows_load): m / v / last of THAT table, rows current at
 // step `to` once their owed zero-gradient updates are applied; last == nullptr: a plain table
@@ -323,19 +338,19 @@ struct AdamRowsView {
     const float *m = nullptr, *v = nullptr;
     const int32_t* last = nullptr;
     int to = 0;
-    float lr = 0.f, beta1 = 0.f, beta2 = 0.f, eps = 0.f, gz = 0.f;
+    float beta1 = 0.f, beta2 = 0.f, eps = 0.f, gz = 0.f;
     AdamRowsHist h;
 };
-AdamRowsView adam_rows_view(const AdamRowsTables& tb, int table, float lr, float beta1, float beta2, float eps, int to);
+AdamRowsView adam_rows_view(const AdamRowsTables& tb, int table, const AdamLr& lr, float beta1, float beta2, float eps, int to);
 struct AdamRowsLists { int n_lists; int end[4]; int table[4]; const int32_t* ids[4]; };   // end[k]: items of lists 0..k
 // the step `step` on every row whose gradient row is not zero (every row when step % K == 0); g: the flat gradient buffer;
 // normaliser 1 / max(*count, 1) if count else 1 / max(*n0, 1)
-int adam_rows_step(hipStream_t s, const AdamRowsTables& tb, const float* g, float lr, float beta1, float beta2, float eps,
+int adam_rows_step(hipStream_t s, const AdamRowsTables& tb, const float* g, const AdamLr& lr, float beta1, float beta2, float eps,
                    int step, const int32_t* n0, const float* count, int tables = 3);    // tables: bit t = table t takes part
 // rows brought up to step `to` by zero-gradient updates: the listed ids (ls) or, ls == nullptr, every row
-int adam_rows_catchup(hipStream_t s, const AdamRowsTables& tb, const AdamRowsLists* ls, float lr, float beta1, float beta2,
+int adam_rows_catchup(hipStream_t s, const AdamRowsTables& tb, const AdamRowsLists* ls, const AdamLr& lr, float beta1, float beta2,
                       float eps, int to);
-AdamRowsHist adam_rows_hist(float beta1, float beta2, int end);     // bias corrections of the steps end - K + 1 .. end
+AdamRowsHist adam_rows_hist(const AdamLr& lr, float beta1, float beta2, int end);     // of the steps end - K + 1 .. end
 // Clipping by the global gradient norm (gradnorm.hip).  grad_sqsum: sum of squares of g[0, n) into st->sq[slot], through
 // `scratch` (grad_sqsum_scratch_bytes(), the partials of slot k at its own offset: ranges of different slots may be summed on
 // different streams); with `fin` the closing step follows in the same launch.  clip_finish: norm / coef / zero flag / counters
@@ -351,7 +366,7 @@ int grad_sqsum(hipStream_t s, int64_t n, const float* g, fira_clip_state* st, in
 int clip_finish(hipStream_t s, fira_clip_state* st, const ClipClose& fin);
 int adam_step_clip(hipStream_t s, int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
                    float eps, int step, const int32_t* n0, const float* count, const fira_clip_state* st);
-int adam_rows_step_clip(hipStream_t s, const AdamRowsTables& tb, const float* g, float lr, float beta1, float beta2, float eps,
+int adam_rows_step_clip(hipStream_t s, const AdamRowsTables& tb, const float* g, const AdamLr& lr, float beta1, float beta2, float eps,
                         int step, const int32_t* n0, const float* count, int tables, const fira_clip_state* st);
 
 // ---- parameter layout ---------------------------------------------------------------------------------

@@ -743,7 +743,8 @@ struct Ctx {
     bool wout_planes = false;        // (round 6) WoutTX holds this step's planes: the vocabulary data gradient runs as dgrad_x3_splitk
     bool kv_planes = false;          // (round 6) WkvTX holds this step's planes: the d-memory products run as linear_x3_kacc
     int32_t* row_step = nullptr;
-    fira_adam_opts rows_ad{};        // lr / beta / eps / step / moments the lazy reads use (a COPY: a begun data-parallel step outlives the call)
+    fira_adam_opts rows_ad{};        // beta / eps / step / moments the lazy reads use (a COPY: a begun data-parallel step outlives the call)
+    AdamLr rows_lr;                  // ... and the rate of every step they replay (rows_ad.lr / rows_ad.sched are not read)
     // data-parallel form of the same (fira_train_step_begin / _end, round 6): the gradients of [0, split) are all-reduced by the
     // caller between the two calls -- Adam of [0, split) waits for ev_early (the caller's event behind that collective) instead of
     // the local weight-gradient mark, scales by the all-reduced token count `count` (a device float), and [split, live) is the
@@ -765,6 +766,9 @@ struct Ctx {
     struct Lane { hipStream_t s; int b0, nb, r0, nr; } lanes[2] = {};
 };
 typedef Ctx::Lane Lane;
+
+// adam->sched, when given, must be a valid schedule (every entry that takes fira_adam_opts)
+static int adam_sched_check(const fira_adam_opts* adam) { return adam && adam->sched ? fira_lr_schedule_check(adam->sched) : 0; }
 
 static AdamRowsTables adam_rows_tables(const Layout& L, float* params, const fira_adam_opts& ad, int32_t* row_step) {
     AdamRowsTables tb;
@@ -870,7 +874,7 @@ static int adam_rows_prefetch(Ctx& c, hipStream_t st) {
         ls.end[k] = (k ? ls.end[k - 1] : 0) + n;
     };
     add(bt.tar, p.B * p.T, 0);
-    return adam_rows_catchup(st, adam_rows_tables(*c.L, const_cast<float*>(c.P), ad, c.row_step), &ls, ad.lr, ad.beta1, ad.beta2, ad.eps,
+    return adam_rows_catchup(st, adam_rows_tables(*c.L, const_cast<float*>(c.P), ad, c.row_step), &ls, c.rows_lr, ad.beta1, ad.beta2, ad.eps,
                              ad.step - 1);
 }
 
@@ -981,7 +985,7 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
     //  registers -- adam_rows.h; the view is empty otherwise)
     AdamRowsView vw_emb;
     if (c.row_step)
-        vw_emb = adam_rows_view(adam_rows_tables(L, nullptr, c.rows_ad, c.row_step), 1, c.rows_ad.lr, c.rows_ad.beta1, c.rows_ad.beta2,
+        vw_emb = adam_rows_view(adam_rows_tables(L, nullptr, c.rows_ad, c.row_step), 1, c.rows_lr, c.rows_ad.beta1, c.rows_ad.beta2,
                                 c.rows_ad.eps, c.rows_ad.step - 1);
     TRY(node_features(s, Nc, bt.node_rows, p.N, p.L, p.S, bt.sou, bt.sub_token, bt.ast_change, c.P + L.emb, c.P + L.ast_emb,
                       p.pos_code, p.X[0], p.code_slot, p.enc[0].Xc, &vw_emb));
@@ -1097,7 +1101,7 @@ static int decoder_forward(Ctx& c) {
     if (c.row_bt) {
         AdamRowsView vw;                          // (see encoder_forward: the target-word table under a row-sparse Adam)
         if (c.row_step)
-            vw = adam_rows_view(adam_rows_tables(L, nullptr, c.rows_ad, c.row_step), 0, c.rows_ad.lr, c.rows_ad.beta1, c.rows_ad.beta2,
+            vw = adam_rows_view(adam_rows_tables(L, nullptr, c.rows_ad, c.row_step), 0, c.rows_lr, c.rows_ad.beta1, c.rows_ad.beta2,
                                 c.rows_ad.eps, c.rows_ad.step - 1);
         TRY(embed_rows_fwd(c.s, c.Td, p.T, c.row_bt, c.bt->tar, c.P + L.dec_emb, p.pos_tar, p.x0, &vw));
     } else {
@@ -1693,16 +1697,16 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
             // (row-sparse tables, data parallel: decoder.embedding -- the head of this slice -- by the rows of the ALL-REDUCED
             //  gradient that are not zero: the union of the ranks' touched rows, the same on every rank)
             const int64_t a0 = c.row_step ? L.dec_emb + (int64_t)L.d.vocab * D : 0;
-            if (c.count) TRY(adam_step(s, L.split - a0, c.Pw + a0, G + a0, ad.m + a0, ad.v + a0, ad.lr, ad.beta1, ad.beta2, ad.eps, ad.step, c.count, 1));
-            else TRY(adam_step_mb(s, L.split - a0, c.Pw + a0, G + a0, nullptr, ad.m + a0, ad.v + a0, ad.lr, ad.beta1, ad.beta2, ad.eps, ad.step, c.n_tok, nullptr));
+            if (c.count) TRY(adam_step(s, L.split - a0, c.Pw + a0, G + a0, ad.m + a0, ad.v + a0, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps, ad.step, c.count, 1));
+            else TRY(adam_step_mb(s, L.split - a0, c.Pw + a0, G + a0, nullptr, ad.m + a0, ad.v + a0, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps, ad.step, c.n_tok, nullptr));
             if (c.row_step)
-                TRY(adam_rows_step(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, ad.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+                TRY(adam_rows_step(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, adam_lr(ad), ad.beta1, ad.beta2, ad.eps, ad.step,
                                    c.count ? nullptr : c.n_tok, c.count, 1));
         } else {
         if (ev_groupA) TRY(main_wait(s, ev_groupA, __LINE__));
         // (row-sparse tables: decoder.embedding is the head of [0, split) -- layout.cpp -- and is left to the rows launch below)
         const int64_t a0 = c.row_step ? L.dec_emb + (int64_t)L.d.vocab * D : 0;
-        TRY(adam_step_mb(s, L.split - a0, c.Pw + a0, G + a0, nullptr, ad.m + a0, ad.v + a0, ad.lr, ad.beta1, ad.beta2, ad.eps,
+        TRY(adam_step_mb(s, L.split - a0, c.Pw + a0, G + a0, nullptr, ad.m + a0, ad.v + a0, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps,
                          ad.step, c.n_tok, nullptr));
         }
         // ... and the encoder's two embedding tables (the head of group B: layout.cpp), whose gradients the two launches above
@@ -1711,12 +1715,12 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         if (c.row_step && !c.adam_a_only) {
             // both vocabulary-sized tables as ONE launch over the rows whose gradient row is not zero (the gradient rows are
             // inspected: 2 x 25 MB read instead of 2 x 177 MB moved); the 71-row table joins the closing launch
-            TRY(adam_rows_step(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, ad.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+            TRY(adam_rows_step(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, adam_lr(ad), ad.beta1, ad.beta2, ad.eps, ad.step,
                                c.n_tok, nullptr));
             adam_b0 = L.ast_emb;
         } else
         if (adam_b0 > L.split)
-        TRY(adam_step_mb(s, adam_b0 - L.split, c.Pw + L.split, G + L.split, nullptr, ad.m + L.split, ad.v + L.split, ad.lr, ad.beta1,
+        TRY(adam_step_mb(s, adam_b0 - L.split, c.Pw + L.split, G + L.split, nullptr, ad.m + L.split, ad.v + L.split, adam_lr(ad).at(ad.step), ad.beta1,
                          ad.beta2, ad.eps, ad.step, c.n_tok, nullptr));
     }
     if (ev_tail) TRY(main_wait(s, ev_tail, __LINE__));
@@ -1726,7 +1730,7 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
     TRY(gcn_bias_unfold_all(s, unfold_tab));
     if (c.adam && !c.adam_a_only) {
         const fira_adam_opts& ad = *c.adam;
-        TRY(adam_step_mb(s, L.live - adam_b0, c.Pw + adam_b0, G + adam_b0, nullptr, ad.m + adam_b0, ad.v + adam_b0, ad.lr, ad.beta1,
+        TRY(adam_step_mb(s, L.live - adam_b0, c.Pw + adam_b0, G + adam_b0, nullptr, ad.m + adam_b0, ad.v + adam_b0, adam_lr(ad).at(ad.step), ad.beta1,
                          ad.beta2, ad.eps, ad.step, c.n_tok, nullptr));
     }
     if (c.clip) {
@@ -1738,12 +1742,12 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         const ClipClose fin{c.n_tok, nullptr, cl.max_norm, 2};
         TRY(grad_sqsum(s, L.live - L.split, G + L.split, cl.state, 1, cl.scratch, &fin));
         auto dense = [&](int64_t lo, int64_t hi) {
-            return adam_step_clip(s, hi - lo, c.Pw + lo, G + lo, ad.m + lo, ad.v + lo, ad.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+            return adam_step_clip(s, hi - lo, c.Pw + lo, G + lo, ad.m + lo, ad.v + lo, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps, ad.step,
                                   c.n_tok, nullptr, cl.state);
         };
         if (c.row_step) {
             const int64_t tab = (int64_t)L.d.vocab * D;
-            TRY(adam_rows_step_clip(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, ad.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+            TRY(adam_rows_step_clip(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, adam_lr(ad), ad.beta1, ad.beta2, ad.eps, ad.step,
                                     c.n_tok, nullptr, 3, cl.state));
             const int64_t t0 = std::min(L.dec_emb, L.emb), t1 = std::max(L.dec_emb, L.emb);
             TRY(dense(0, t0));
@@ -1899,6 +1903,8 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
     if (adam && row_step && L->d.d_model == FIRA_D) {        // (the forward gathers read lagging rows lazily: adam_rows_load)
         c.row_step = row_step;
         c.rows_ad = *adam;
+        c.rows_lr = adam_lr(*adam);
+        c.rows_ad.sched = nullptr;
     }
     c.dp_begin = begin_only;
     if (begin_only) c.adam = nullptr;        // (fira_train_step_begin_rows: the optimizer's values serve the lazy reads only)
@@ -2012,6 +2018,7 @@ int fira_train_step_begin_rows(void* stream, const fira_dims* d, const fira_batc
                                int32_t* n_tok, void* mid_event, const fira_adam_opts* adam, int32_t* row_step) {
     FIRA_REQUIRE(mid_event, "fira_train_step_begin_rows: mid_event missing (the caller's collective waits for it)");
     FIRA_REQUIRE(adam && adam->m && adam->v && adam->step >= 1 && row_step, "fira_train_step_begin_rows: bad Adam arguments");
+    TRY(adam_sched_check(adam));
     FIRA_REQUIRE(opts && opts->zero_grads, "fira_train_step_begin_rows: needs opts.zero_grads");
     // (adam only parameterises the lazy reads; train_call(begin_only) returns before any update)
     return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, mid_event, nullptr,
@@ -2031,6 +2038,7 @@ int fira_train_step_end(void* stream, float* params, const fira_adam_opts* adam,
     ps.active = false;
     FIRA_REQUIRE((hipStream_t)stream == ps.ctx.s, "fira_train_step_end: not the stream the step was begun on");
     FIRA_REQUIRE(!adam || (adam->m && adam->v && adam->step >= 1 && params), "fira_train_step_end: bad Adam arguments");
+    TRY(adam_sched_check(adam));
     FIRA_REQUIRE(!params || params == ps.params, "fira_train_step_end: not the parameter buffer the step was begun with");
     DtypeScope dtype_scope(ps.dtype);
     const bool bf16 = ps.dtype == 1;
@@ -2053,6 +2061,7 @@ int fira_train_step(void* stream, const fira_dims* d, const fira_batch* batch, f
                     const fira_adam_opts* adam) {
     FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_step: Adam moments missing");
     FIRA_REQUIRE(adam->step >= 1, "fira_train_step: the Adam step counter starts at 1");
+    TRY(adam_sched_check(adam));
     return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam);
 }
 
@@ -2061,6 +2070,7 @@ int fira_train_step_rows(void* stream, const fira_dims* d, const fira_batch* bat
                          const fira_adam_opts* adam, int32_t* row_step) {
     FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_step_rows: Adam moments missing");
     FIRA_REQUIRE(adam->step >= 1, "fira_train_step_rows: the Adam step counter starts at 1");
+    TRY(adam_sched_check(adam));
     FIRA_REQUIRE(row_step, "fira_train_step_rows: row_step missing");
     FIRA_REQUIRE(opts && opts->zero_grads, "fira_train_step_rows: needs opts.zero_grads (an all-zero gradient row = an untouched row)");
     return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
@@ -2072,6 +2082,7 @@ int fira_train_step_clip(void* stream, const fira_dims* d, const fira_batch* bat
                          const fira_adam_opts* adam, int32_t* row_step, float max_norm, fira_clip_state* state, void* scratch) {
     FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_step_clip: Adam moments missing");
     FIRA_REQUIRE(adam->step >= 1, "fira_train_step_clip: the Adam step counter starts at 1");
+    TRY(adam_sched_check(adam));
     FIRA_REQUIRE(max_norm > 0.f, "fira_train_step_clip: max_norm must be > 0 (inf allowed)");
     FIRA_REQUIRE(state && scratch && (uintptr_t)scratch % 8 == 0, "fira_train_step_clip: clip state / scratch missing");
     FIRA_REQUIRE(!row_step || (opts && opts->zero_grads),
@@ -2087,8 +2098,9 @@ int fira_adam_rows_step_clip(void* stream, const fira_dims* d, float* params, co
     if (!L) return 1;
     FIRA_REQUIRE(params && grads && adam && adam->m && adam->v && row_step && (n_tok || count) && adam->step >= 1 && tables >= 1 &&
                      tables <= 3 && state, "fira_adam_rows_step_clip: bad argument");
+    TRY(adam_sched_check(adam));
     FIRA_REQUIRE(L->d.d_model == FIRA_D, "fira_adam_rows_step_clip: model width must be %d", FIRA_D);
-    return adam_rows_step_clip((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), grads, adam->lr, adam->beta1,
+    return adam_rows_step_clip((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), grads, adam_lr(*adam), adam->beta1,
                                adam->beta2, adam->eps, adam->step, n_tok, count, tables, state);
 }
 // op-level pieces of the same (tests/test_adam_rows_gpu.py compares them with fira_adam_step_mb bit for bit)
@@ -2098,8 +2110,9 @@ int fira_adam_rows_step(void* stream, const fira_dims* d, float* params, const f
     if (!L) return 1;
     FIRA_REQUIRE(params && grads && adam && adam->m && adam->v && row_step && (n_tok || count) && adam->step >= 1 && tables >= 1 &&
                      tables <= 3, "fira_adam_rows_step: bad argument");
+    TRY(adam_sched_check(adam));
     FIRA_REQUIRE(L->d.d_model == FIRA_D, "fira_adam_rows_step: model width must be %d", FIRA_D);
-    return adam_rows_step((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), grads, adam->lr, adam->beta1,
+    return adam_rows_step((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), grads, adam_lr(*adam), adam->beta1,
                           adam->beta2, adam->eps, adam->step, count ? nullptr : n_tok, count, tables);
 }
 int fira_adam_rows_catchup(void* stream, const fira_dims* d, float* params, const fira_adam_opts* adam, int32_t* row_step,
@@ -2108,18 +2121,20 @@ int fira_adam_rows_catchup(void* stream, const fira_dims* d, float* params, cons
     if (!L) return 1;
     FIRA_REQUIRE(params && adam && adam->m && adam->v && row_step && ids && n_ids >= 0 && (table == 0 || table == 1),
                  "fira_adam_rows_catchup: bad argument");
+    TRY(adam_sched_check(adam));
     FIRA_REQUIRE(L->d.d_model == FIRA_D, "fira_adam_rows_catchup: model width must be %d", FIRA_D);
     AdamRowsLists ls{};
     ls.n_lists = 1; ls.ids[0] = ids; ls.table[0] = table; ls.end[0] = n_ids;
-    return adam_rows_catchup((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), &ls, adam->lr, adam->beta1,
+    return adam_rows_catchup((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), &ls, adam_lr(*adam), adam->beta1,
                              adam->beta2, adam->eps, adam->step);
 }
 int fira_adam_rows_sync(void* stream, const fira_dims* d, float* params, const fira_adam_opts* adam, int32_t* row_step) {
     const Layout* L = get_layout(d);
     if (!L) return 1;
     FIRA_REQUIRE(params && adam && adam->m && adam->v && row_step && adam->step >= 0, "fira_adam_rows_sync: bad argument");
+    TRY(adam_sched_check(adam));
     FIRA_REQUIRE(L->d.d_model == FIRA_D, "fira_adam_rows_sync: model width must be %d", FIRA_D);
-    return adam_rows_catchup((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), nullptr, adam->lr, adam->beta1,
+    return adam_rows_catchup((hipStream_t)stream, adam_rows_tables(*L, params, *adam, row_step), nullptr, adam_lr(*adam), adam->beta1,
                              adam->beta2, adam->eps, adam->step);
 }
 

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(int64_t n, float* __rest
 // adam_rows_kernel of copyhead.hip with the clip state.  Under the zero-gradient flag every row is "untouched" (wave-uniform:
 // the flag is one scalar), and a forced step applies the zero-gradient update gz to every row -- what the dense clipped kernel
 // does to every element, so the two stay equal bit for bit once fira_adam_rows_sync has run.
-__global__ __launch_bounds__(256) void adam_rows_clip_kernel(AdamRowsTables tb, const float* __restrict__ gbase, float lr,
+__global__ __launch_bounds__(256) void adam_rows_clip_kernel(AdamRowsTables tb, const float* __restrict__ gbase,
                                                              float beta1, float beta2, float eps, int step, AdamRowsHist h,
                                                              const int32_t* __restrict__ n0, const float* __restrict__ count,
                                                              int force, float gz, int it_lo, int it_hi,
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void adam_rows_clip_kernel(AdamRowsTables tb, 
     const int lane = threadIdx.x & 63;
     const int nw = gridDim.x * 4;
     const int total = it_hi;
-    const float ss = lr / h.bc1[step % ADAM_ROWS_K], b2s = h.bc2s[step % ADAM_ROWS_K];
+    const float ss = h.lr[step % ADAM_ROWS_K] / h.bc1[step % ADAM_ROWS_K], b2s = h.bc2s[step % ADAM_ROWS_K];
     for (int it0 = it_lo + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4; it0 < total; it0 += nw * 4) {
         float4 gq[4];
         size_t oq[4];
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void adam_rows_clip_kernel(AdamRowsTables tb, 
             const int l = max(tb.last[it], step - ADAM_ROWS_K);
             float4 pv = *reinterpret_cast<float4*>(tb.p + o), mv = *reinterpret_cast<float4*>(tb.m + o),
                    vv = *reinterpret_cast<float4*>(tb.v + o);
-            adam_row_zero_steps(pv, mv, vv, l + 1, step - 1, gz, lr, beta1, beta2, eps, h);
+            adam_row_zero_steps(pv, mv, vv, l + 1, step - 1, gz, beta1, beta2, eps, h);
             const float gx = gv.x * scale * coef, gy = gv.y * scale * coef, gzz = gv.z * scale * coef, gw = gv.w * scale * coef;
             adam_elem(pv.x, mv.x, vv.x, zf ? gz : gx, beta1, beta2, eps, ss, b2s);
             adam_elem(pv.y, mv.y, vv.y, zf ? gz : gy, beta1, beta2, eps, ss, b2s);
@@ -245,7 +245,7 @@ int adam_step_clip(hipStream_t s, int64_t n, float* p, const float* g, float* m,
     return 0;
 }
 
-int adam_rows_step_clip(hipStream_t s, const AdamRowsTables& tb, const float* g, float lr, float beta1, float beta2, float eps,
+int adam_rows_step_clip(hipStream_t s, const AdamRowsTables& tb, const float* g, const AdamLr& lr, float beta1, float beta2, float eps,
                         int step, const int32_t* n0, const float* count, int tables, const fira_clip_state* st) {
     ProfScope prof(s, PROF_ADAM, 0.0);
     FIRA_REQUIRE(step >= 1 && tb.last && (n0 || count) && st, "adam_rows_step_clip: bad argument");
@@ -253,8 +253,8 @@ int adam_rows_step_clip(hipStream_t s, const AdamRowsTables& tb, const float* g,
     const int total = it_hi - it_lo;
     if (total <= 0) return 0;
     const int grid = std::min(cdiv(total, 16), 256 * 8);
-    hipLaunchKernelGGL(adam_rows_clip_kernel, dim3(grid), dim3(256), 0, s, tb, g, lr, beta1, beta2, eps, step,
-                       adam_rows_hist(beta1, beta2, step), count ? nullptr : n0, count, step % ADAM_ROWS_K == 0 ? 1 : 0, 0.0f,
+    hipLaunchKernelGGL(adam_rows_clip_kernel, dim3(grid), dim3(256), 0, s, tb, g, beta1, beta2, eps, step,
+                       adam_rows_hist(lr, beta1, beta2, step), count ? nullptr : n0, count, step % ADAM_ROWS_K == 0 ? 1 : 0, 0.0f,
                        it_lo, it_hi, st);
     FIRA_CHECK_LAUNCH("adam_rows_step_clip");
     return 0;

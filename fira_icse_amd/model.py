@@ -498,14 +498,16 @@ class TransModel(nn.Module):
 
     def train_step(self, db: DeviceBatch, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, beta1: float = 0.9,
                    beta2: float = 0.999, eps: float = 1e-8, dropout: Optional[float] = None,
-                   gcn_dropout: Optional[float] = None, row_step: Optional[torch.Tensor] = None, clip=None):
+                   gcn_dropout: Optional[float] = None, row_step: Optional[torch.Tensor] = None, clip=None, sched=None):
         """``loss.backward(); optimizer.step()`` of run_model.py:104-111 as ONE library call (fira_train_step): the same
         arithmetic as :meth:`train_fwd_bwd` + ``ops.adam_step_mb`` over ``[0, live)``; the head + decoder slice of the update
         runs beside the last weight gradients.  ``m`` / ``v``: the Adam moments (flat, like ``self.flat``).
         ``row_step`` (int32 ``[2 * vocab]``): fira_train_step_rows -- the two vocabulary-sized embedding tables are updated on
         the rows the step touched only; the caller owns the sync (:meth:`sync_params`, ``Trainer.sync``).
         ``clip`` = ``(max_norm, state, scratch)`` (``ops.clip_state``): fira_train_step_clip -- the update clipped by the global
-        gradient norm, a non-finite gradient applied as a zero-gradient step; with or without ``row_step``."""
+        gradient norm, a non-finite gradient applied as a zero-gradient step; with or without ``row_step``.
+        ``sched`` (an ``_lib.LrSchedule``): ``lr`` is ignored and step j uses ``fira_lr_at(sched, j)`` -- this step and every
+        update a lagging row still owes."""
         lib = _lib.lib()
         if row_step is None:
             self.sync_params()
@@ -515,7 +517,7 @@ class TransModel(nn.Module):
         self.dropout_step += 1
         opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
                               1 if self.compact_dec else 0, 1)
-        adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v))
+        adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v), _lib.sched_ptr(sched))
         ws = self.workspace(db.B, 1)
         if clip is not None:
             max_norm, state, scratch = clip
@@ -538,7 +540,7 @@ class TransModel(nn.Module):
         return self.loss_sum, self.n_tok
 
     def train_step_begin(self, db: DeviceBatch, mid_event, dropout: Optional[float] = None,
-                         gcn_dropout: Optional[float] = None, rows=None):
+                         gcn_dropout: Optional[float] = None, rows=None, sched=None):
         """First half of a data-parallel step (fira_train_step_begin): forward + the backward pass of the head and the decoder;
         ``mid_event`` fires when the gradients of ``[0, split)`` are final.  The step stays pending until
         :meth:`train_step_end`; ``db`` must stay alive until then."""
@@ -555,9 +557,10 @@ class TransModel(nn.Module):
         self._pending_db = db
         if rows is not None:
             # row-sparse Adam of the word tables (fira_train_step_begin_rows): rows = (m, v, lr, step, beta1, beta2, eps, row_step)
-            # -- the optimizer's values parameterise the forward pass's lazy reads of lagging rows; nothing is updated here
+            # -- the optimizer's values (and `sched`, the schedule that replaces lr) parameterise the forward pass's lazy reads
+            # of lagging rows; nothing is updated here
             m_, v_, lr, step, b1, b2, eps, row_step = rows
-            adam = _lib.AdamOpts(lr, b1, b2, eps, int(step), _lib.ptr(m_), _lib.ptr(v_))
+            adam = _lib.AdamOpts(lr, b1, b2, eps, int(step), _lib.ptr(m_), _lib.ptr(v_), _lib.sched_ptr(sched))
             _lib.check(lib.fira_train_step_begin_rows(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
                                                       _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
                                                       C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok),
@@ -571,12 +574,13 @@ class TransModel(nn.Module):
         return self.loss_sum, self.n_tok
 
     def train_step_end(self, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, early_event=None, count=None,
-                       beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, row_step=None, update: bool = True):
+                       beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, row_step=None, update: bool = True,
+                       sched=None):
         """Second half (fira_train_step_end): the encoder's backward pass; Adam of ``[0, split)`` once the current stream has
         passed ``early_event`` (the caller's event behind the all-reduce of that slice), scaled by ``1 / count`` (a device
         float, the all-reduced token count).  ``[split, live)`` is left to the caller (its bucket is reduced afterwards).
         ``update=False``: the backward pass only (adam = NULL) -- the caller updates both slices itself (clipped steps)."""
-        adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v))
+        adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v), _lib.sched_ptr(sched))
         if not update:
             _lib.check(_lib.lib().fira_train_step_end(_lib.cur_stream(), None, None, None, None), "fira_train_step_end")
         elif row_step is not None:

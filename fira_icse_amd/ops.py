@@ -6,6 +6,8 @@ per-kernel parity tests.
 """
 from __future__ import annotations
 
+import dataclasses
+
 import torch
 
 from . import _lib
@@ -459,6 +461,67 @@ def adam_step_mb(p, g0, g1, m, v, lr, step, n_tok0, n_tok1=None, beta1=0.9, beta
     check(_lib.lib().fira_adam_step_mb(cur_stream(), p.numel(), ptr(_f32(p)), ptr(_f32(g0)), ptr(g1), ptr(_f32(m)),
                                        ptr(_f32(v)), lr, beta1, beta2, eps, step, ptr(_i32(n_tok0)), ptr(n_tok1)),
           "fira_adam_step_mb")
+
+
+LR_KINDS = ("constant", "inv_sqrt", "cosine", "linear")          # fira_lr_schedule.kind = the index
+
+
+@dataclasses.dataclass(frozen=True)
+class LrSchedule:
+    """A learning-rate schedule, the mirror of ``fira_lr_schedule`` (include/fira_hip.h has the formulas; the library's
+    ``fira_lr_at`` is their only implementation -- :func:`lr_at` calls it).  ``kind``: one of :data:`LR_KINDS`; ``base_lr``:
+    the peak; ``warmup_steps`` W >= 0; ``decay_steps`` N > W: the step at which cosine / linear reach ``min_lr``."""
+    kind: str = "constant"
+    base_lr: float = 1e-4
+    warmup_steps: int = 0
+    decay_steps: int = 0
+    min_lr: float = 0.0
+
+    @staticmethod
+    def make(obj) -> "LrSchedule":
+        """From an ``LrSchedule``, or a dict with its field names (``kind`` as a name -- ``inv-sqrt`` allowed -- or its number)."""
+        if isinstance(obj, LrSchedule):
+            s = obj
+        else:
+            d = dict(obj)
+            unknown = set(d) - {f.name for f in dataclasses.fields(LrSchedule)}
+            if unknown:
+                raise ValueError("lr_schedule: unknown field(s) %s" % sorted(unknown))
+            s = LrSchedule(**d)
+        kind = s.kind
+        if isinstance(kind, int) and not isinstance(kind, bool) and 0 <= kind < len(LR_KINDS):
+            kind = LR_KINDS[kind]
+        kind = str(kind).replace("-", "_")
+        if kind not in LR_KINDS:
+            raise ValueError("lr_schedule: kind %r is not one of %s" % (s.kind, ", ".join(LR_KINDS)))
+        s = LrSchedule(kind, float(s.base_lr), int(s.warmup_steps), int(s.decay_steps), float(s.min_lr))
+        lr_schedule_check(s)
+        return s
+
+    def struct(self) -> "_lib.LrSchedule":
+        return _lib.LrSchedule(LR_KINDS.index(self.kind), self.base_lr, self.warmup_steps, self.decay_steps, self.min_lr)
+
+    def as_dict(self) -> dict:
+        return dataclasses.asdict(self)
+
+
+def _sched_struct(sched):
+    return sched if isinstance(sched, _lib.LrSchedule) else sched.struct()
+
+
+def lr_at(sched, step: int) -> float:
+    """The rate of step ``step`` (counting from 1) under ``sched`` (an :class:`LrSchedule` or an ``_lib.LrSchedule``):
+    ``fira_lr_at``, the float every update kernel of that step is given.  Host only, no GPU."""
+    import ctypes as C
+    return float(_lib.lib().fira_lr_at(C.byref(_sched_struct(sched)), int(step)))
+
+
+def lr_schedule_check(sched):
+    """Raises ``ValueError`` with the library's message when ``sched`` is not a valid schedule (``fira_lr_schedule_check``)."""
+    import ctypes as C
+    lib = _lib.lib()
+    if lib.fira_lr_schedule_check(C.byref(_sched_struct(sched))) != 0:
+        raise ValueError(lib.fira_last_error().decode())
 
 
 def clip_state(device="cuda"):

@@ -20,14 +20,20 @@ from .parallel import GradReducer, ShardedOptimizerComm
 class Trainer:
     def __init__(self, model: TransModel, lr: Optional[float] = None, betas=(0.9, 0.999), eps: float = 1e-8,
                  distributed: bool = False, zero1: bool = False, grad_wire: str = "f32",
-                 clip_grad_norm: Optional[float] = None):
+                 clip_grad_norm: Optional[float] = None, lr_schedule=None):
         """``zero1`` (with ``distributed``): reduce-scatter + Adam on the owned 1/world shard + all-gather instead of
         all-reduce + replicated Adam; Adam moments exist only for the owned shard (parallel.ShardedOptimizerComm).
         ``grad_wire`` (with ``distributed``, all-reduce path): "f32", or "bf16" = the two gradient buckets travel as bf16
         (half the bytes on xGMI; parallel.GradReducer).
         ``clip_grad_norm`` (``None`` = off: the code path of every release so far): the gradient is clipped to this global norm
         on the device (``torch.nn.utils.clip_grad_norm_``; ``inf`` = observe and guard only) and a step whose gradient holds
-        an ``inf`` / ``nan`` is applied as a zero-gradient step instead of destroying the weights; see :meth:`last_grad_norm`."""
+        an ``inf`` / ``nan`` is applied as a zero-gradient step instead of destroying the weights; see :meth:`last_grad_norm`.
+        ``lr_schedule`` (``None`` = the constant ``lr``: the code path of every release so far): an ``ops.LrSchedule`` or a
+        dict of its fields -- warmup and decay as a function of the step number (``ops.lr_at``).  ``lr`` is then not used.
+        The row-sparse update stays lazy under it: the rate of every step a row still owes travels with the launch."""
+        self.lr_schedule = None if lr_schedule is None else ops.LrSchedule.make(lr_schedule)
+        self._last_lr = None
+        self._sched_cache = (None, None)
         self.clip = None
         if clip_grad_norm is not None:
             self.clip = float(clip_grad_norm)
@@ -89,6 +95,10 @@ class Trainer:
         m = self.model
         dp = self.reducer is not None and self.reducer.world > 1
         fused_dp = False
+        # once per step, before t advances -- also on a rank whose shard is empty: a sync that a changed hyper-parameter forces
+        # brings the rows up to the LAST completed step
+        self._rows_check_hyper()
+        sched = self._sched_struct()
         if db is None:
             if not dp and not (self.zero is not None and self.zero.world > 1):
                 return                                           # nothing to learn from, nobody to keep in step
@@ -98,19 +108,17 @@ class Trainer:
             self.mid_event.record()
             loss_sum, n_tok = m.loss_sum, m.n_tok
         elif self.fused_step and self.reducer is None and self.zero is None:
-            self._rows_check_hyper()
             self.t += 1
             clip = None if self.clip is None else (self.clip, self.clip_state, self.clip_scratch)
-            m.train_step(db, self.m, self.v, self.lr, self.t, self.betas[0], self.betas[1], self.eps, row_step=self.row_step,
-                         clip=clip)
+            m.train_step(db, self.m, self.v, self._rate(), self.t, self.betas[0], self.betas[1], self.eps,
+                         row_step=self.row_step, clip=clip, sched=sched)
             self._rows_dirty = self.row_step is not None
             return
         elif dp and self.fused_dp and self.zero is None:
             fused_dp = True
-            self._rows_check_hyper()
             rows = None if self.row_step is None else \
-                (self.m, self.v, self.lr, self.t + 1, self.betas[0], self.betas[1], self.eps, self.row_step)
-            loss_sum, n_tok = m.train_step_begin(db, self.mid_event, rows=rows)
+                (self.m, self.v, self._rate_of(self.t + 1), self.t + 1, self.betas[0], self.betas[1], self.eps, self.row_step)
+            loss_sum, n_tok = m.train_step_begin(db, self.mid_event, rows=rows, sched=sched)
         else:
             loss_sum, n_tok = m.train_fwd_bwd(db, zero_grad=True, mid_event=self.mid_event)
         b1, b2 = self.betas
@@ -124,13 +132,14 @@ class Trainer:
             # 1 / max(count, 1) from the all-reduced pair themselves: no torch arithmetic between the collective and Adam
             ev = red.reduce_early(m.gbuf, self.stats, self.mid_event, pack=lambda: ops.pack_stats(loss_sum, n_tok, self.stats))
             self.t += 1
+            lr = self._rate()
             count = self.stats[1:2]
             if self.clip is not None:
                 # clipped: every update waits for the norm of the ALL-REDUCED gradient (every rank sums the same numbers, bf16
                 # wire included, and takes the same decision).  The encoder's backward pass runs without an update; the sum
                 # of squares of each bucket follows its all-reduce, the closing step uses the global token count.
                 if fused_dp:
-                    m.train_step_end(self.m, self.v, self.lr, self.t, update=False)
+                    m.train_step_end(self.m, self.v, lr, self.t, update=False)
                 red.wait_early()
                 ops.grad_sqsum(m.gbuf[:split], self.clip_state, 0, self.clip_scratch)
                 red.start_late(m.gbuf)
@@ -144,8 +153,8 @@ class Trainer:
             if fused_dp:
                 # encoder backward; Adam of [0, split) inside the library as soon as the caller's stream has passed the
                 # encoder's chain and `ev`, beside the last weight gradients; the join
-                m.train_step_end(self.m, self.v, self.lr, self.t, early_event=ev, count=count, beta1=b1, beta2=b2, eps=self.eps,
-                                 row_step=self.row_step)
+                m.train_step_end(self.m, self.v, lr, self.t, early_event=ev, count=count, beta1=b1, beta2=b2, eps=self.eps,
+                                 row_step=self.row_step, sched=sched)
             else:
                 red.wait_early()
                 self._adam_slice(0, split, count, table=0)
@@ -162,13 +171,14 @@ class Trainer:
         # was measured on one box: 8 497 vs 8 553 commits/s -- the HBM-bound update only slows the backward kernels it
         # overlaps; profiles/r2_probes.md.)
         n = m.layout.live
+        lr = self._rate()
         if self.clip is not None:
             ops.grad_sqsum(m.gbuf[:n], self.clip_state, 0, self.clip_scratch)
             ops.clip_finish(self.clip_state, 1, self.clip, n_tok=n_tok)
-            ops.adam_step_clip(m.flat.data[:n], m.gbuf[:n], self.m[:n], self.v[:n], self.lr, self.t, self.clip_state,
+            ops.adam_step_clip(m.flat.data[:n], m.gbuf[:n], self.m[:n], self.v[:n], lr, self.t, self.clip_state,
                                n_tok=n_tok, beta1=b1, beta2=b2, eps=self.eps)
             return
-        ops.adam_step_mb(m.flat.data[:n], m.gbuf[:n], None, self.m[:n], self.v[:n], self.lr, self.t, n_tok, None, b1, b2,
+        ops.adam_step_mb(m.flat.data[:n], m.gbuf[:n], None, self.m[:n], self.v[:n], lr, self.t, n_tok, None, b1, b2,
                          self.eps)
 
     def _step_zero1(self, loss_sum, n_tok):
@@ -184,6 +194,7 @@ class Trainer:
         torch.distributed.all_reduce(self.stats, op=torch.distributed.ReduceOp.SUM, group=z.group)
         self.end_event.record(main)                            # backward pass done, global token count known
         self.t += 1
+        lr = self._rate()
         zs.wait_event(self.end_event)
         if self.clip is not None:
             # clipped: each rank sums the squares of its owned shards, one extra all-reduce of the two scalars gives every
@@ -201,7 +212,7 @@ class Trainer:
                     lo, hi = z.owned(b)
                     if hi > lo:
                         n = hi - lo
-                        ops.adam_step_clip(m.flat.data[lo:hi], self.g_sh[b][:n], self.m_sh[b][:n], self.v_sh[b][:n], self.lr,
+                        ops.adam_step_clip(m.flat.data[lo:hi], self.g_sh[b][:n], self.m_sh[b][:n], self.v_sh[b][:n], lr,
                                            self.t, self.clip_state, count=self.stats[1:2], beta1=b1, beta2=b2, eps=self.eps)
                     z.all_gather(b, m.flat.data)
             main.wait_stream(zs)
@@ -213,16 +224,38 @@ class Trainer:
                 lo, hi = z.owned(b)
                 if hi > lo:
                     n = hi - lo
-                    ops.adam_step_count(m.flat.data[lo:hi], self.g_sh[b][:n], self.m_sh[b][:n], self.v_sh[b][:n], self.lr,
+                    ops.adam_step_count(m.flat.data[lo:hi], self.g_sh[b][:n], self.m_sh[b][:n], self.v_sh[b][:n], lr,
                                         self.t, self.stats[1:2], b1, b2, self.eps)
                 z.all_gather(b, m.flat.data)
         main.wait_stream(zs)                                   # the next forward pass reads every parameter
 
     def _rows_check_hyper(self):
-        hyper = (self.lr, self.betas[0], self.betas[1], self.eps)
-        if self._rows_hyper != hyper:                            # lazily applied updates use the step's own lr / beta / eps
+        # lazily applied updates use each step's own rate (the schedule's, or the constant lr) and the beta / eps in force: a
+        # change of the schedule, of beta or eps -- or, without a schedule, of lr -- first settles what the rows owe
+        hyper = (self.lr_schedule, None if self.lr_schedule is not None else self.lr, self.betas[0], self.betas[1], self.eps)
+        if self._rows_hyper != hyper:
             self.sync()
             self._rows_hyper = hyper
+
+    def _sched_struct(self):
+        """The ``fira_lr_schedule`` of this trainer's schedule (``None`` without one), built once per schedule."""
+        if self.lr_schedule is None:
+            return None
+        if self._sched_cache[0] is not self.lr_schedule:
+            self._sched_cache = (self.lr_schedule, self.lr_schedule.struct())
+        return self._sched_cache[1]
+
+    def _rate_of(self, t: int) -> float:
+        return self.lr if self.lr_schedule is None else ops.lr_at(self._sched_struct(), t)
+
+    def _rate(self) -> float:
+        """The rate of step ``self.t`` (already advanced): what every update launch of this step is given."""
+        self._last_lr = self._rate_of(self.t)
+        return self._last_lr
+
+    def last_lr(self) -> Optional[float]:
+        """The learning rate the last step used (``None`` before the first step).  No synchronisation."""
+        return self._last_lr
 
     def _adam_slice(self, lo: int, hi: int, count, table: int):
         """Adam on ``[lo, hi)`` of the flat buffers, scaled by ``1 / count`` (data-parallel step).  On the row-sparse path the
@@ -230,10 +263,11 @@ class Trainer:
         ``split``) is updated on the rows of the all-reduced gradient that are not zero (fira_adam_rows_step)."""
         m = self.model
         b1, b2 = self.betas
+        lr = self._rate()
         if self.row_step is not None:
             import ctypes as C
-            self._rows_check_hyper()
-            adam = _lib.AdamOpts(self.lr, b1, b2, self.eps, int(self.t), _lib.ptr(self.m), _lib.ptr(self.v))
+            adam = _lib.AdamOpts(lr, b1, b2, self.eps, int(self.t), _lib.ptr(self.m), _lib.ptr(self.v),
+                                 _lib.sched_ptr(self._sched_struct()))
             if self.clip is not None:
                 _lib.check(_lib.lib().fira_adam_rows_step_clip(_lib.cur_stream(), C.byref(m.dims), _lib.ptr(m.flat.data),
                                                                _lib.ptr(m.gbuf), C.byref(adam), _lib.ptr(self.row_step), None,
@@ -245,10 +279,10 @@ class Trainer:
                                                           _lib.ptr(count), 1 << table), "fira_adam_rows_step")
             lo += m.cfg.vocab_size * 256
         if self.clip is not None:
-            ops.adam_step_clip(m.flat.data[lo:hi], m.gbuf[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lr, self.t, self.clip_state,
+            ops.adam_step_clip(m.flat.data[lo:hi], m.gbuf[lo:hi], self.m[lo:hi], self.v[lo:hi], lr, self.t, self.clip_state,
                                count=count, beta1=b1, beta2=b2, eps=self.eps)
             return
-        ops.adam_step_count(m.flat.data[lo:hi], m.gbuf[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lr, self.t, count, b1, b2,
+        ops.adam_step_count(m.flat.data[lo:hi], m.gbuf[lo:hi], self.m[lo:hi], self.v[lo:hi], lr, self.t, count, b1, b2,
                             self.eps)
 
     def sync(self):
@@ -258,9 +292,11 @@ class Trainer:
         if self.row_step is None or not self._rows_dirty:
             return
         self._rows_dirty = False
-        lr, b1, b2, eps = self._rows_hyper
+        schedule, lr, b1, b2, eps = self._rows_hyper           # (the values the owed updates were deferred under)
         import ctypes as C
-        adam = _lib.AdamOpts(lr, b1, b2, eps, int(self.t), _lib.ptr(self.m), _lib.ptr(self.v))
+        sched = None if schedule is None else schedule.struct()
+        adam = _lib.AdamOpts(lr if schedule is None else schedule.base_lr, b1, b2, eps, int(self.t), _lib.ptr(self.m),
+                             _lib.ptr(self.v), _lib.sched_ptr(sched))
         _lib.check(_lib.lib().fira_adam_rows_sync(_lib.cur_stream(), C.byref(self.model.dims), _lib.ptr(self.model.flat.data),
                                                   C.byref(adam), _lib.ptr(self.row_step)), "fira_adam_rows_sync")
         torch.cuda.current_stream().synchronize()
@@ -288,11 +324,23 @@ class Trainer:
         if self.zero is not None:                              # collective: every rank calls it, any rank may save it
             total = self.model.layout.total
             return {"m": self.zero.gather_full(self.m_sh, total), "v": self.zero.gather_full(self.v_sh, total),
-                    "t": self.t, "dropout_step": self.model.dropout_step}
+                    "t": self.t, "dropout_step": self.model.dropout_step, "lr_schedule": self._schedule_state()}
         self.sync()
-        return {"m": self.m, "v": self.v, "t": self.t, "dropout_step": self.model.dropout_step}
+        return {"m": self.m, "v": self.v, "t": self.t, "dropout_step": self.model.dropout_step,
+                "lr_schedule": self._schedule_state()}
+
+    def _schedule_state(self):
+        return None if self.lr_schedule is None else self.lr_schedule.as_dict()
 
     def load_state_dict(self, sd):
+        """Restores what :meth:`state_dict` holds.  The learning-rate schedule: a Trainer built without one takes the saved
+        one (a state without the key was saved by a constant-rate run: nothing to take); a Trainer built WITH one refuses a
+        state saved under a different schedule -- the run would silently continue on another curve."""
+        saved = sd.get("lr_schedule")
+        saved = None if saved is None else ops.LrSchedule.make(saved)
+        if self.lr_schedule is not None and saved != self.lr_schedule:
+            raise ValueError("load_state_dict: the state was saved under the learning-rate schedule %s, this Trainer was built "
+                             "with %s" % ("none (a constant rate)" if saved is None else saved, self.lr_schedule))
         if self.zero is not None:                              # the checkpoint holds full moments: keep the owned shards
             for b in (0, 1):
                 lo, hi = self.zero.owned(b)
@@ -300,6 +348,7 @@ class Trainer:
         else:
             self.sync()
             self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
+        self.lr_schedule = saved
         self.t = int(sd["t"])
         if self.row_step is not None:
             self.row_step.fill_(self.t)                          # a checkpoint holds synced tables

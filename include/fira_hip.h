@@ -502,11 +502,34 @@ int fira_head_logits_x3(void* stream, int R, int V, const float* x, int ldx, con
  * enqueued as soon as the caller's stream has finished the encoder's backward chain, beside the last weight gradients of the
  * library's other streams; [split, live) follows their join.  params is updated in place, m / v are the Adam moments
  * ([>= live] floats each), step counts from 1.  Data-parallel runs keep the two-call form (the all-reduce sits between). */
+/* A learning-rate schedule: a pure function of the step number t = 1, 2, ... (W = warmup_steps, N = decay_steps), evaluated in
+ * double and rounded to float once:
+ *     w = W > 0 ? min(1, t / W) : 1 ;   q = clamp((t - W) / (N - W), 0, 1)
+ *     constant   base * w
+ *     inv_sqrt   base * min(t / W, sqrt(W / t))                                   (needs W >= 1)
+ *     cosine     t <= W ? base * w : min_lr + (base - min_lr) * 0.5 * (1 + cos(pi q))
+ *     linear     t <= W ? base * w : min_lr + (base - min_lr) * (1 - q)
+ * fira_lr_at is the one definition: the library takes every rate of a scheduled run from it (fira_adam_opts.sched), and a
+ * caller of the entries that take a bare `float lr` passes them fira_lr_at(sched, step).  Host functions, no GPU.            */
+typedef struct fira_lr_schedule {
+    int32_t kind;          /* 0 constant, 1 inv_sqrt, 2 cosine, 3 linear                                 */
+    float   base_lr;       /* the peak rate                                                              */
+    int32_t warmup_steps;  /* W >= 0                                                                     */
+    int32_t decay_steps;   /* N: the step at which cosine / linear reach min_lr (N > W)                  */
+    float   min_lr;        /* 0 <= min_lr <= base_lr                                                     */
+} fira_lr_schedule;
+float fira_lr_at(const fira_lr_schedule* s, int step);   /* step counts from 1 (below 1: as 1); NULL gives 0 */
+int   fira_lr_schedule_check(const fira_lr_schedule* s); /* 0, or non-zero with the reason in fira_last_error() */
+
 typedef struct fira_adam_opts {
     float   lr, beta1, beta2, eps;
     int32_t step;
     float*  m;
     float*  v;
+    /* NULL: every step uses `lr`.  Otherwise `lr` is ignored and step j uses fira_lr_at(sched, j) -- the step itself and
+     * every update a lazily updated row still owes (fira_train_step_rows), so a rate that changes every step needs no
+     * fira_adam_rows_sync.  Read during the call only.                                                                  */
+    const fira_lr_schedule* sched;
 } fira_adam_opts;
 int fira_train_step(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads,
                     void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
@@ -540,7 +563,8 @@ int fira_train_step_end(void* stream, float* params, const fira_adam_opts* adam,
  * first) holds the step up to which each row of params / m / v is current.  Every 32nd step updates every row, so a row lags
  * at most 31 steps.  Results are those of fira_train_step bit for bit ONCE fira_adam_rows_sync has run: call it (same adam
  * values, step = the last completed step) before anything else reads the tables or the moments -- checkpoint, dev pass,
- * search, another optimizer -- and before changing lr / beta / eps.  adam->step must advance by one per call.  Needs
+ * search, another optimizer -- and before changing the schedule, beta or eps (with adam->sched NULL, lr is the schedule:
+ * a constant).  adam->step must advance by one per call.  Needs
  * opts->zero_grads = 1.  (Data parallel: fira_train_step_begin_rows / _end_rows below.)                                      */
 int fira_train_step_rows(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads,
                          void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,

@@ -97,9 +97,21 @@ def parse_args(argv):
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
                     "--loss-log line then carries grad_norm and clip_coef")
+    ap.add_argument("--lr-schedule", default=None, choices=LR_SCHEDULES, help="train: warmup and decay of the learning rate "
+                    "as a function of the optimisation step (--lr is the peak): constant = --lr behind a linear warmup; "
+                    "inv-sqrt = linear warmup, then lr * sqrt(W / step); cosine / linear = linear warmup, then down to --lr-min at "
+                    "step --lr-decay-steps.  Every --loss-log line then carries lr.  Default: none (--lr at every step)")
+    ap.add_argument("--warmup-steps", type=int, default=None, metavar="W", help="with --lr-schedule: steps of linear warmup "
+                    "(default 0; inv-sqrt needs W >= 1)")
+    ap.add_argument("--lr-decay-steps", type=int, default=None, metavar="N", help="with --lr-schedule cosine|linear: the step "
+                    "at which the rate reaches --lr-min, N > W (default: the optimisation steps the run plans -- --max-steps if "
+                    "given, else epochs x steps per epoch -- counted from the step a --resume starts at)")
+    ap.add_argument("--lr-min", type=float, default=None, metavar="X", help="with --lr-schedule cosine|linear: the rate from "
+                    "step N on, 0 <= X <= --lr (default 0)")
     a = ap.parse_args(argv)
     try:
         check_clip_args(a)
+        check_lr_schedule_args(a)
         check_score_args(a)
         check_sample_args(a)
     except ValueError as e:
@@ -108,6 +120,7 @@ def parse_args(argv):
 
 
 RERANK_KEYS = ("logp_word", "mean_logp_word")
+LR_SCHEDULES = ("constant", "inv-sqrt", "cosine", "linear")
 
 
 def check_clip_args(a):
@@ -120,6 +133,50 @@ def check_clip_args(a):
     if not c > 0:                                            # (also refuses nan)
         raise ValueError("--clip-grad-norm %g: must be > 0 (inf = observe and guard only)" % c)
     return a
+
+
+def check_lr_schedule_args(a):
+    """Validates --lr-schedule / --warmup-steps / --lr-decay-steps / --lr-min (no GPU, no DataSet needed); raises ValueError on
+    a conflict or an out-of-range value.  The formulas themselves live in the library (fira_lr_at)."""
+    kind, W, N, mn = a.lr_schedule, a.warmup_steps, a.lr_decay_steps, a.lr_min
+    given = [n for n, v in (("--warmup-steps", W), ("--lr-decay-steps", N), ("--lr-min", mn)) if v is not None]
+    if kind is None:
+        if given:
+            raise ValueError("%s needs --lr-schedule" % ", ".join(given))
+        return a
+    if a.stage != "train":
+        raise ValueError("--lr-schedule only applies to the train stage")
+    if not (a.lr > 0 and a.lr < float("inf")):                 # (also refuses nan)
+        raise ValueError("--lr %g: a schedule needs a finite peak rate > 0" % a.lr)
+    if kind in ("constant", "inv-sqrt"):
+        for name, v in (("--lr-decay-steps", N), ("--lr-min", mn)):
+            if v is not None:
+                raise ValueError("%s has no meaning with --lr-schedule %s (it never reaches a floor)" % (name, kind))
+    if W is not None and W < 0:
+        raise ValueError("--warmup-steps %d: must be >= 0" % W)
+    if kind == "inv-sqrt" and (W is None or W < 1):
+        raise ValueError("--lr-schedule inv-sqrt needs --warmup-steps W >= 1")
+    if kind in ("cosine", "linear"):
+        if N is not None and N <= (W or 0):
+            raise ValueError("--lr-decay-steps %d: --lr-schedule %s needs N > W (--warmup-steps %d)" % (N, kind, W or 0))
+        if mn is not None and not (0 <= mn <= a.lr):           # (also refuses nan)
+            raise ValueError("--lr-min %g: must be in [0, --lr %g]" % (mn, a.lr))
+    return a
+
+
+def lr_schedule_from_args(a, planned_steps: int, done_steps: int = 0):
+    """The ops.LrSchedule fields the options describe (None without --lr-schedule).  planned_steps: the optimisation steps
+    this run plans; done_steps: the steps a resumed state has behind it -- the default of --lr-decay-steps is their sum."""
+    if a.lr_schedule is None:
+        return None
+    W = a.warmup_steps or 0
+    decays = a.lr_schedule in ("cosine", "linear")
+    N = (a.lr_decay_steps if a.lr_decay_steps is not None else done_steps + planned_steps) if decays else 0
+    if decays and N <= W:
+        raise ValueError("--lr-schedule %s: the run plans %d steps, not more than --warmup-steps %d; give --lr-decay-steps"
+                         % (a.lr_schedule, N, W))
+    return {"kind": a.lr_schedule.replace("-", "_"), "base_lr": a.lr, "warmup_steps": W, "decay_steps": N,
+            "min_lr": (a.lr_min or 0.0) if decays else 0.0}
 
 
 def check_score_args(a):
@@ -278,14 +335,22 @@ class Run:
         self.model.compute_dtype = a.dtype
         self.model.set_dropout_stream(a.seed, self.rank)           # masks depend on (--seed, rank, step)
         wire = a.grad_wire if a.grad_wire != "auto" else ("bf16" if a.dtype == "bf16" else "f32")
-        trainer = Trainer(self.model, lr=cfg.lr, distributed=self.world > 1, zero1=a.zero1, grad_wire=wire,
-                          clip_grad_norm=a.clip_grad_norm)
         state_path = os.path.join(self.root, "fira_train_state.pt")
-        if a.resume and os.path.exists(state_path):
-            trainer.load_state_dict(torch.load(state_path, map_location=self.model.device_))
+        state = torch.load(state_path, map_location=self.model.device_) if a.resume and os.path.exists(state_path) else None
+        n_batches = -(-len(store) // cfg.batch_size)
+        # (no --lr-schedule: no schedule object, the constant-rate path; a resumed state then brings its own, if it has one)
+        schedule = lr_schedule_from_args(a, a.max_steps if a.max_steps else cfg.epoches * n_batches,
+                                         int(state["t"]) if state is not None else 0)
+        trainer = Trainer(self.model, lr=cfg.lr, distributed=self.world > 1, zero1=a.zero1, grad_wire=wire,
+                          clip_grad_norm=a.clip_grad_norm, lr_schedule=schedule)
+        if state is not None:
+            trainer.load_state_dict(state)                   # (refuses a state saved under another schedule)
+            del state
+        scheduled = trainer.lr_schedule is not None
+        if scheduled and self.rank == 0:
+            print("learning-rate schedule: %s" % (trainer.lr_schedule,), flush=True)
         self.model.train(not a.no_dropout)
         best_bleu, steps = -1.0, 0
-        n_batches = -(-len(store) // cfg.batch_size)
         for epoch in range(cfg.epoches):
             total_data, t0 = 0, time.time()
             def prepare(gidx):                                     # worker thread: collate + H2D of this rank's shard
@@ -318,6 +383,8 @@ class Run:
                     rec = {"epoch": epoch, "batch": idx_b, "index": [int(i) for i in gidx], "loss": trainer.last_loss()}
                     if a.clip_grad_norm is not None:
                         rec["grad_norm"], rec["clip_coef"] = trainer.last_grad_norm()[:2]
+                    if scheduled:
+                        rec["lr"] = trainer.last_lr()
                     with open(a.loss_log, "a") as f:
                         f.write(json.dumps(rec) + "\n")
                 if idx_b % 10 == 0 and self.rank == 0:
@@ -331,6 +398,8 @@ class Run:
                 _, _, n_clipped, n_nonfinite = trainer.last_grad_norm()      # running counts since the start of the run
                 print("epoch: %d  clipped steps so far: %d  non-finite (zero-gradient) steps so far: %d of %d" % (
                     epoch, n_clipped, n_nonfinite, steps), flush=True)
+            if scheduled and self.rank == 0:
+                print("epoch: %d  learning rate: %.6g (step %d)" % (epoch, trainer.last_lr() or 0.0, trainer.t), flush=True)
             if a.max_steps and steps >= a.max_steps:
                 break
         if best_bleu < 0:                               # never reached a dev point (short runs): keep the last weights
