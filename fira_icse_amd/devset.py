@@ -1,0 +1,162 @@
+"""Dev-set model selection (reference run_model.py:118-184): a teacher-forced pass over the valid split and NLTK
+sentence-BLEU (method 2) per commit, as the host loop the driver has always run (``host_pass``) and on the device
+(``device_pass``: resident batches, ``fira_dev_bleu_stats`` on token ids, one copy back per pass).
+
+Both passes return ``(total, lines)``: this rank's plain running sum of the per-commit scores over its shard, in shard order,
+and a callable that builds this rank's ``dev_output`` lines.  The two are interchangeable: the totals are ``==`` and the lines
+the same strings (DESIGN.md 6i has the argument; tests/test_dev_bleu_gpu.py holds them to it).
+"""
+from __future__ import annotations
+
+from typing import Callable, Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import metrics, text
+from .config import EOS, PAD, UNK, FiraConfig
+from .parallel import shard_indices
+
+_STAT_COLS = 12
+
+
+def check_vocabulary(r_vocab: Dict[int, str], vocab_size: int) -> None:
+    """Raises ValueError unless comparing vocabulary ids is the same as comparing the words the host pass compares.
+
+    The host joins the hypothesis' words with blanks, deletes ``<pad>``, writes ``<unkm>`` as the emoji, and splits at white
+    space.  That round trip gives back exactly the non-pad words, one per id, iff every id has a word, no word is empty or
+    contains white space, no word other than the two tokens themselves contains ``<pad>`` / ``<unkm>``, and no word IS the
+    emoji (a hypothesis ``<unkm>`` would then equal that word in a reference).  Distinct ids always carry distinct words:
+    ``r_vocab`` inverts a word -> id dictionary."""
+    if r_vocab.get(PAD) != "<pad>" or r_vocab.get(UNK) != "<unkm>":
+        raise ValueError("device dev pass: ids %d / %d must be '<pad>' / '<unkm>', not %r / %r"
+                         % (PAD, UNK, r_vocab.get(PAD), r_vocab.get(UNK)))
+    for i in range(vocab_size):
+        if i not in r_vocab:
+            raise ValueError("device dev pass: vocabulary id %d has no word" % i)
+    for i, w in r_vocab.items():
+        if w.split() != [w]:
+            raise ValueError("device dev pass: the word of id %d (%r) is empty or contains white space" % (i, w))
+        if w == text.UNK_EMOJI:
+            raise ValueError("device dev pass: the word of id %d is the emoji the host writes for <unkm>" % i)
+        for tok in ("<pad>", "<unkm>"):
+            if tok in w and w != tok:
+                raise ValueError("device dev pass: the word of id %d (%r) contains %s" % (i, w, tok))
+
+
+class DevEvaluator:
+    """The valid split of one rank, scored on the host or on the device.
+
+    ``model`` supplies ``forward_dev`` and the device (None: a CPU evaluator for ``host_pass`` with an injected ``ids_fn``);
+    ``store`` is the valid ``GraphStore``; ``var_maps`` / ``valid_index`` map a commit to its ``variable.json`` entry.
+    ``ids_fn(db) -> int32 [B, T]`` replaces ``model.forward_dev`` in BOTH passes; every batch carries the store positions of
+    its commits as ``db.commits``.  Sharding and batch boundaries are the driver's: ``shard_indices`` over the split, batches of
+    ``batch_size // world`` commits, tail batch included.
+
+    Resident set of ``device_pass``.  A ``DeviceBatch`` owns its device arena (the pinned ring is only the staging side of its
+    one copy), so the batches built at the first call stay valid whatever is collated later.  An arena holds the id arrays,
+    the node lists and the CSR adjacency: on ``synth.py`` commits 18.4 kB per commit (18.0 to 18.8 kB over four batches of 170: 3.06 to 3.20 MB
+    per arena), i.e. about 148 MB for the reference's 8 000 valid commits on one rank -- 0.05 % of 288 GB -- plus
+    4 * (12 + tar_len) = 168 bytes per commit (1.3 MB) for the two pass-wide result buffers.  ``resident_bytes`` has the
+    actual figure of a built set.
+    """
+
+    def __init__(self, model, store, cfg: FiraConfig, r_vocab: Dict[int, str], var_maps: Sequence[Dict[str, str]],
+                 valid_index: Sequence[int], rank: int = 0, world: int = 1,
+                 ids_fn: Optional[Callable] = None, device=None):
+        self.model, self.store, self.cfg = model, store, cfg
+        self.r_vocab, self.var_maps, self.valid_index = r_vocab, var_maps, valid_index
+        self.rank, self.world = rank, world
+        self.device = torch.device(device if device is not None else (model.device_ if model is not None else "cpu"))
+        if ids_fn is None:
+            if model is None:
+                raise ValueError("DevEvaluator needs a model or an ids_fn")
+            ids_fn = model.forward_dev
+        self.ids_fn = ids_fn
+        self.mine: List[int] = shard_indices(list(range(len(store))), rank, world)
+        self.bs = max(1, cfg.batch_size // world)
+        self.last_scores: List[float] = []       # per-commit scores of the latest pass, in shard order
+        self._batches = None                     # resident DeviceBatches (device_pass)
+        self._out = None                         # [n_mine, 12 + T] int32: stats | hyp of one pass
+
+    def _batch(self, idx):
+        from .model import DeviceBatch
+        db = DeviceBatch(self.store.batch(idx), self.cfg, self.device)
+        db.commits = list(idx)
+        return db
+
+    def _line(self, i: int, words: List[str], b: float) -> str:
+        back = {v: k for k, v in self.var_maps[self.valid_index[i]].items()}
+        return " ".join(back.get(t, t) for t in words) + "," + str(b)
+
+    # ------------------------------------------------------------------------------ the host loop (run_model.py:118-184)
+    @torch.no_grad()
+    def host_pass(self):
+        cfg, store = self.cfg, self.store
+        lines, total, scores = [], 0.0, []
+        for lo in range(0, len(self.mine), self.bs):
+            idx = self.mine[lo:lo + self.bs]
+            ids = self.ids_fn(self._batch(idx)).cpu().tolist()
+            for k, i in enumerate(idx):
+                sen = text.dev_sentence(ids[k], store.sou[i], store.sub_token[i], cfg.vocab_size, cfg.sou_len, EOS)
+                s = " ".join(self.r_vocab[t] for t in sen).replace("<pad>", "").replace("<unkm>", text.UNK_EMOJI).strip()
+                hyp = s.split()
+                ref_ids = store.tar[i].tolist()
+                ref = [self.r_vocab[t] for t in ref_ids[1:ref_ids.index(EOS)]]
+                b = metrics.sentence_bleu_method2([ref], hyp)
+                total += b
+                scores.append(b)
+                lines.append(self._line(i, hyp, b))
+        self.last_scores = scores
+        return total, lambda: lines
+
+    # ------------------------------------------------------------------------------ the device pass
+    def _build_resident(self):
+        check_vocabulary(self.r_vocab, self.cfg.vocab_size)
+        tar = np.asarray(self.store.tar)[self.mine] if self.mine else np.zeros((0, self.cfg.tar_len), np.int64)
+        no_eos = np.nonzero(~(tar == EOS).any(axis=1))[0]
+        if no_eos.size:                          # (the host pass raises ValueError from list.index on such a commit)
+            raise ValueError("device dev pass: valid commit %d has no <eos> in its target" % self.mine[int(no_eos[0])])
+        self._batches = [self._batch(self.mine[lo:lo + self.bs]) for lo in range(0, len(self.mine), self.bs)]
+        self._out = torch.empty((len(self.mine) * (_STAT_COLS + self.cfg.tar_len),), dtype=torch.int32, device=self.device)
+
+    @property
+    def resident_bytes(self) -> int:
+        """Device bytes the resident set holds (0 before the first ``device_pass``)."""
+        if self._batches is None:
+            return 0
+        return sum(db.arena.numel() for db in self._batches) + self._out.numel() * 4
+
+    @torch.no_grad()
+    def device_pass(self):
+        from . import ops
+        cfg, n, T = self.cfg, len(self.mine), self.cfg.tar_len
+        if self._batches is None:
+            self._build_resident()
+        stats = self._out[:n * _STAT_COLS].view(n, _STAT_COLS)
+        hyp = self._out[n * _STAT_COLS:].view(n, T)
+        off = 0
+        for db in self._batches:
+            ids = self.ids_fn(db)
+            db.wait_ready()
+            ops.dev_bleu_stats(ids, db.sou, db.sub_token, db.tar, cfg.vocab_size, hyp=hyp[off:off + db.B],
+                               stats=stats[off:off + db.B])
+            off += db.B
+        host = self._out.cpu()                   # the pass's one copy back and its one synchronisation
+        st = host[:n * _STAT_COLS].view(n, _STAT_COLS).tolist()
+        total, scores = 0.0, []
+        for row in st:
+            b = metrics.bleu_method2_from_stats(row[0:4], row[4:8], row[8], row[9])
+            total += b
+            scores.append(b)
+        self.last_scores = scores
+        hyp_host = host[n * _STAT_COLS:].view(n, T)
+
+        def lines():
+            out = []
+            for k, (i, row) in enumerate(zip(self.mine, hyp_host.tolist())):
+                words = [text.UNK_EMOJI if t == UNK else self.r_vocab[t] for t in row[:st[k][8]]]
+                out.append(self._line(i, words, scores[k]))
+            return out
+
+        return total, lines

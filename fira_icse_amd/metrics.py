@@ -102,7 +102,7 @@ def sentence_bleu_method2(references: Sequence[Sequence[str]], hypothesis: Seque
     hyp = list(hypothesis)
     if not hyp:
         return 0.0
-    nums, dens = [], []
+    nums, cnts = [], []
     for n in range(1, 5):
         counts = Counter(tuple(hyp[i:i + n]) for i in range(len(hyp) - n + 1))
         max_ref = Counter()
@@ -111,11 +111,24 @@ def sentence_bleu_method2(references: Sequence[Sequence[str]], hypothesis: Seque
             for g in counts:
                 max_ref[g] = max(max_ref[g], rc[g])
         nums.append(sum(min(c, max_ref[g]) for g, c in counts.items()))
-        dens.append(max(1, sum(counts.values())))
+        cnts.append(sum(counts.values()))
     if nums[0] == 0:
         return 0.0
     hyp_len = len(hyp)
     ref_len = min((abs(len(r) - hyp_len), len(r)) for r in references)[1]
+    return bleu_method2_from_stats(nums, cnts, hyp_len, ref_len)
+
+
+def bleu_method2_from_stats(num: Sequence[int], cnt: Sequence[int], hyp_len: int, ref_len: int) -> float:
+    """``sentence_bleu_method2`` from its integer statistics (Python ints): for n = 1..4 ``cnt[n-1]`` hypothesis n-grams, of
+    which ``num[n-1]`` are matched after clipping; the hypothesis and the (closest) reference length.  These are the twelve
+    numbers ``fira_dev_bleu_stats`` writes per commit, and the expressions -- ``max(1, cnt)``, ``math.log``, ``math.fsum``,
+    ``math.exp``, in this order -- are the ones the string scorer has always used, so the value is ``==`` its value."""
+    if hyp_len == 0:
+        return 0.0
+    dens = [max(1, c) for c in cnt]
+    if num[0] == 0:
+        return 0.0
     bp = 1.0 if hyp_len > ref_len else math.exp(1 - ref_len / hyp_len)
-    logs = [math.log(nums[0] / dens[0])] + [math.log((nums[i] + 1) / (dens[i] + 1)) for i in range(1, 4)]
+    logs = [math.log(num[0] / dens[0])] + [math.log((num[i] + 1) / (dens[i] + 1)) for i in range(1, 4)]
     return bp * math.exp(math.fsum(0.25 * x for x in logs))

@@ -650,3 +650,21 @@ def gemm_wgrad_panel(A, B, out, colsum=None, dtype=0, split=True):
                                            out.stride(0), ptr(colsum), ptr(scratch), scratch.numel() if split else 0),
           "fira_gemm_wgrad_panel")
     return out
+
+
+def dev_bleu_stats(ids, sou, sub_token, tar, V, hyp=None, stats=None):
+    """fira_dev_bleu_stats: per commit the sentence-BLEU statistics of ``Run.dev`` on token ids.  ids [B,T] are output indices
+    of ``forward_dev``, sou [B,L], sub_token [B,S], tar [B,T], all int32.  Returns (hyp [B,T]: the hypothesis' vocabulary ids,
+    compacted, -1 behind its length; stats [B,12]: num[4], cnt[4], hyp_len, ref_len, 0, 0) -- into ``hyp`` / ``stats`` when
+    given (slices of a pass-wide buffer).  ``metrics.bleu_method2_from_stats`` turns a stats row into the score."""
+    B, T = ids.shape
+    L, S = sou.shape[1], sub_token.shape[1]
+    assert sou.shape[0] == B and sub_token.shape[0] == B and tuple(tar.shape) == (B, T)
+    if hyp is None:
+        hyp = torch.empty((B, T), dtype=torch.int32, device=ids.device)
+    if stats is None:
+        stats = torch.empty((B, 12), dtype=torch.int32, device=ids.device)
+    assert tuple(hyp.shape) == (B, T) and tuple(stats.shape) == (B, 12)
+    check(_lib.lib().fira_dev_bleu_stats(cur_stream(), B, T, int(V), L, S, ptr(_i32(ids)), ptr(_i32(sou)), ptr(_i32(sub_token)),
+                                         ptr(_i32(tar)), ptr(_i32(hyp)), ptr(_i32(stats))), "fira_dev_bleu_stats")
+    return hyp, stats

@@ -651,6 +651,18 @@ int fira_forward_dev(void* stream, const fira_dims* d, const fira_batch* batch, 
                      void* workspace, size_t workspace_bytes, int32_t* ids_out, float* loss_sum, int32_t* n_tok,
                      int dtype /* FIRA_F32 | FIRA_BF16 */);
 
+/* Sentence-BLEU statistics of dev() (run_model.py:138-177) on token ids, one row per commit (csrc/bleu.hip; additive, the ABI
+ * version is unchanged).  Hypothesis: ids[b] up to its first raw <eos> (all T without one), copy entries resolved through sou /
+ * sub_token (index clamped), resolved <pad> dropped; reference: tar[b][1 : first <eos>] (to T without one).  A hypothesis <unkm>
+ * matches nothing.  For n = 1..4: cnt = hypothesis n-grams, num = sum over distinct hypothesis n-grams of min(count in the
+ * hypothesis, count in the reference).  int32 and exact; T <= 64, V >= 4, L, S >= 1; B == 0 is a no-op.                        */
+int fira_dev_bleu_stats(void* stream, int B, int T, int V, int L, int S,
+                        const int32_t* ids,  /* [B,T] output indices of fira_forward_dev, in [0, V+L+S) */
+                        const int32_t* sou,  /* [B,L] */  const int32_t* sub_token, /* [B,S] */
+                        const int32_t* tar,  /* [B,T] */
+                        int32_t* hyp,        /* [B,T] resolved vocabulary ids of the hypothesis, compacted, -1 behind hyp_len */
+                        int32_t* stats);     /* [B,12]: num[4], cnt[4], hyp_len, ref_len, 0, 0 */
+
 /* Encoder once per batch (run_model.py:202-207) + everything of the decode loop that does not depend
  * on the generated prefix: memory [B,S,256], mem_valid [B,S], cross-attention K/V of all layers,
  * LinearSource(memory).  State lives in the caller's workspace.                                     */

@@ -36,7 +36,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
-from fira_icse_amd import data, metrics, text                      # noqa: E402
+from fira_icse_amd import data, text                               # noqa: E402
 from fira_icse_amd.config import EOS, PAD, START, UNK, FiraConfig                 # noqa: E402
 from fira_icse_amd.parallel import gather_lines, init_from_env, shard_indices   # noqa: E402
 from fira_icse_amd.prefetch import prefetch                        # noqa: E402
@@ -62,6 +62,10 @@ def parse_args(argv):
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--dev-from-epoch", type=int, default=15)
     ap.add_argument("--dev-every", type=int, default=10)
+    ap.add_argument("--dev-on-device", action="store_true", help="train: score the dev passes on the device -- the valid split "
+                    "stays resident in HBM, sentence-BLEU statistics come from a kernel on token ids, one copy back per pass, and "
+                    "the dev_output text is only built for a new best; train_process, dev_output and the chosen checkpoint are "
+                    "identical to a run without it")
     ap.add_argument("--max-steps", type=int, default=0, help="stop after this many optimisation steps (0 = no limit)")
     ap.add_argument("--no-dropout", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
@@ -296,32 +300,34 @@ class Run:
     # ------------------------------------------------------------------------------ dev (run_model.py:118-184)
     @torch.no_grad()
     def dev(self, epoch):
-        cfg, store = self.cfg, self.sets["valid"].store
-        valid_index = self.all_index["valid"]
+        """(mean sentence-BLEU over the valid split, callable -> the text of OUTPUT/dev_output).  The pass itself lives in
+        fira_icse_amd.devset: the host loop, or with --dev-on-device the resident valid set and the BLEU kernel; there the
+        lines are only built (and gathered: a collective every rank enters, all ranks compare the same all-reduced number)
+        when the caller asks for them."""
+        store = self.sets["valid"].store
+        if getattr(self, "dev_eval", None) is None or self.dev_eval.model is not self.model:
+            from fira_icse_amd.devset import DevEvaluator
+            self.dev_eval = DevEvaluator(self.model, store, self.cfg, self.r_vocab, self.var_maps, self.all_index["valid"],
+                                         self.rank, self.world)
+        on_device = getattr(self.a, "dev_on_device", False)
         self.model.eval()
-        mine = shard_indices(list(range(len(store))), self.rank, self.world)
-        lines, total = [], 0.0
-        bs = max(1, cfg.batch_size // self.world)
-        for lo in range(0, len(mine), bs):
-            idx = mine[lo:lo + bs]
-            ids = self.model.forward_dev(self.device_batch(store, idx)).cpu().tolist()
-            for k, i in enumerate(idx):
-                sen = text.dev_sentence(ids[k], store.sou[i], store.sub_token[i], cfg.vocab_size, cfg.sou_len, EOS)
-                s = " ".join(self.r_vocab[t] for t in sen).replace("<pad>", "").replace("<unkm>", "\U0001F605").strip()
-                hyp = s.split()
-                ref_ids = store.tar[i].tolist()
-                ref = [self.r_vocab[t] for t in ref_ids[1:ref_ids.index(EOS)]]
-                b = metrics.sentence_bleu_method2([ref], hyp)
-                total += b
-                back = {v: k2 for k2, v in self.var_maps[valid_index[i]].items()}
-                lines.append(" ".join(back.get(t, t) for t in hyp) + "," + str(b))
+        total, lines = self.dev_eval.device_pass() if on_device else self.dev_eval.host_pass()
         if self.world > 1:
             t = torch.tensor([total], dtype=torch.float64, device=self.model.device_)
             torch.distributed.all_reduce(t)
             total = float(t.item())
-            lines = gather_lines(lines)
+
+        def output():
+            out = lines()
+            if self.world > 1:
+                out = gather_lines(out)
+            return "\n".join(out) + "\n"
+
+        if not on_device:                            # as ever: the lines are built and gathered in every pass
+            done = output()
+            output = lambda: done
         self.model.train()
-        return total / max(1, len(store)), "\n".join(lines) + "\n"
+        return total / max(1, len(store)), output
 
     # ------------------------------------------------------------------------------ train (run_model.py:83-117,382-399)
     def train(self):
@@ -361,13 +367,14 @@ class Run:
                                device=self.model.device_)
             for idx_b, (gidx, db) in enumerate(batches):
                 if epoch >= a.dev_from_epoch and idx_b % a.dev_every == 0:
-                    cur_bleu, output_str = self.dev(epoch)
+                    cur_bleu, dev_text = self.dev(epoch)
                     if self.rank == 0:
                         with open(self.out("train_process"), "a") as f:
                             f.write("epoch: {} batch: {} dev bleu: {} is better: {}\n".format(
                                 epoch, idx_b, cur_bleu, cur_bleu > best_bleu))
                     if cur_bleu > best_bleu:
                         best_bleu = cur_bleu
+                        output_str = dev_text()              # (--dev-on-device: builds the lines now; collective when world > 1)
                         opt_state = trainer.state_dict() if a.save_optimizer else None     # collective with --zero1
                         if self.rank == 0:
                             torch.save(self.model.state_dict(), os.path.join(self.root, "best_model.pt"))
