@@ -154,6 +154,7 @@ SIGNATURES = {
     "fira_host_collate_csr": (_I, [_I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
     "fira_forward_dev": (_I, [_P, _DP, _BP, _P, _P, _Z, _P, _P, _P, _I]),
     "fira_dev_bleu_stats": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "fira_mbr_bleu_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "fira_decode_begin": (_I, [_P, _DP, _BP, _P, _P, _Z, _I]),
     "fira_decode_begin_ex": (_I, [_P, _DP, _BP, _P, _P, _Z, _I, _I]),
     "fira_decode_step_ex": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _P, _P, _I]),

@@ -140,6 +140,95 @@ __global__ __launch_bounds__(BLEU_CPW * 64) void dev_bleu_stats_kernel(int B, in
     if (live && lane < 12) stats[b * 12 + lane] = out;
 }
 
+// ---------------------------------------------------------------- all pairs of one commit's candidates (MBR selection)
+// fira_mbr_bleu_stats: the statistics above for every ordered pair (hypothesis i, reference j) of the n candidate messages of a
+// commit.  The message of a candidate is its row's ids at positions 1 .. min(length, T) - 1 with every <pad> / <eos> / <start>
+// dropped wherever it stands (text.detokenize's string replacement); <unkm> is an ordinary word (both sides print the same
+// emoji).  One workgroup of MBR_WAVES waves per commit:
+//   1. wave w compacts candidates w, w + MBR_WAVES, ... into LDS (one row load and one length load per candidate, indices
+//      clamped, nothing behind a branch; a ballot gives the kept lanes and their positions).  One barrier.
+//   2. wave w owns hypotheses w, w + MBR_WAVES, ...: per hypothesis it builds Eh, the three neighbour masks (wave shuffles; no
+//      LDS round trip, so no barrier inside the loops), the first-occurrence flags and popc(Mh_n) ONCE, then per reference j
+//      only Er (64 LDS reads at a wave-uniform address) and Mr_n, four wave sums, and one 12-lane store.
+// A reference is read from LDS, not from HBM n times.  Lengths, not sentinels, bound every mask, so any int32 is a word.
+constexpr int MBR_WAVES = 4;
+constexpr int MBR_N = 32;              // candidates per commit the LDS stage holds
+constexpr int BLEU_START = 2;          // config.START
+
+__device__ __forceinline__ uint64_t shfl_up_mask(uint64_t m, int lane, int k) {      // m of lane + k, >> k; 0 past the wave
+    const int lo = __shfl((int)(uint32_t)m, lane + k), hi = __shfl((int)(uint32_t)(m >> 32), lane + k);
+    const uint64_t v = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+    return lane + k < 64 ? v >> k : 0;
+}
+
+__device__ __forceinline__ uint64_t equal_mask(const int32_t* __restrict__ row, int mine) {      // bit t = row[t] == mine
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int t = 0; t < 32; ++t) {
+        lo |= (uint32_t)(row[t] == mine) << t;
+        hi |= (uint32_t)(row[32 + t] == mine) << t;
+    }
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(MBR_WAVES * 64) void mbr_bleu_stats_kernel(int n, int T, const int32_t* __restrict__ tokens,
+                                                                        const int32_t* __restrict__ length,
+                                                                        int32_t* __restrict__ stats) {
+    __shared__ __attribute__((aligned(16))) int32_t s_tok[MBR_N][BLEU_T];      // compacted messages (entries past s_len: unwritten)
+    __shared__ int32_t s_len[MBR_N];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t row0 = (size_t)blockIdx.x * n;                                // first candidate row of this commit
+    const int tc = lane < T ? lane : T - 1;
+    const uint64_t below = low_bits(lane);
+
+    // ---- 1. compact the commit's candidates into LDS
+    for (int c = w; c < n; c += MBR_WAVES) {                                   // (wave-uniform trip count)
+        const int tok = tokens[(row0 + c) * T + tc];
+        const int len = clampi(length[row0 + c], 0, T);
+        const bool keep = lane >= 1 && lane < len && tok != BLEU_PAD && tok != BLEU_EOS && tok != BLEU_START;
+        const uint64_t keep_m = __ballot(keep);
+        if (keep) s_tok[c][__builtin_popcountll(keep_m & below)] = tok;
+        if (lane == 0) s_len[c] = __builtin_popcountll(keep_m);
+    }
+    __syncthreads();
+
+    // ---- 2. every hypothesis of this wave against every candidate
+    for (int i = w; i < n; i += MBR_WAVES) {
+        const int hyp_len = s_len[i];
+        const bool in_h = lane < hyp_len;
+        const int tok_l = s_tok[i][lane];                                      // (unwritten past hyp_len: dropped by the select
+        const int mine = in_h ? tok_l : -1;                                    //  and by in_h on the masks)
+        const uint64_t eh = in_h ? equal_mask(s_tok[i], mine) & low_bits(hyp_len) : 0;
+        uint64_t mh = ~0ull;
+        int ch[4], cnt[4];
+        bool take[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            mh &= k == 0 ? eh : shfl_up_mask(eh, lane, k);
+            ch[k] = __builtin_popcountll(mh);
+            take[k] = lane + k + 1 <= hyp_len && (mh & below) == 0;            // starts a (k+1)-gram, first occurrence of it
+            cnt[k] = hyp_len > k ? hyp_len - k : 0;
+        }
+        for (int j = 0; j < n; ++j) {
+            const int ref_len = s_len[j];
+            const uint64_t er = in_h ? equal_mask(s_tok[j], mine) & low_bits(ref_len) : 0;
+            uint64_t mr = ~0ull;
+            int out = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                mr &= k == 0 ? er : shfl_up_mask(er, lane, k);
+                const int cr = __builtin_popcountll(mr);
+                const int num = wave_sum_i32(take[k] ? (ch[k] < cr ? ch[k] : cr) : 0);
+                out = lane == k ? num : out;
+                out = lane == 4 + k ? cnt[k] : out;
+            }
+            out = lane == 8 ? hyp_len : out;
+            out = lane == 9 ? ref_len : out;
+            if (lane < 12) stats[((row0 + i) * n + j) * 12 + lane] = out;
+        }
+    }
+}
+
 }  // namespace fira
 
 extern "C" int fira_dev_bleu_stats(void* stream, int B, int T, int V, int L, int S, const int32_t* ids, const int32_t* sou,
@@ -155,5 +244,18 @@ extern "C" int fira_dev_bleu_stats(void* stream, int B, int T, int V, int L, int
     hipLaunchKernelGGL(dev_bleu_stats_kernel, dim3(cdiv(B, BLEU_CPW)), dim3(BLEU_CPW * 64), 0, (hipStream_t)stream, B, T, V, L, S,
                        ids, sou, sub_token, tar, hyp, stats);
     FIRA_CHECK_LAUNCH("fira_dev_bleu_stats");
+    return 0;
+}
+
+extern "C" int fira_mbr_bleu_stats(void* stream, int B, int n, int T, const int32_t* tokens, const int32_t* length,
+                                   int32_t* stats) {
+    using namespace fira;
+    FIRA_REQUIRE(B >= 0, "fira_mbr_bleu_stats: B = %d is negative", B);
+    FIRA_REQUIRE(n >= 1 && n <= MBR_N, "fira_mbr_bleu_stats: n = %d outside 1..%d (candidates per commit)", n, MBR_N);
+    FIRA_REQUIRE(T >= 1 && T <= BLEU_T, "fira_mbr_bleu_stats: T = %d outside 1..%d (one lane per position)", T, BLEU_T);
+    if (B == 0) return 0;
+    FIRA_REQUIRE(tokens && length && stats, "fira_mbr_bleu_stats: null pointer (tokens, length or stats)");
+    hipLaunchKernelGGL(mbr_bleu_stats_kernel, dim3(B), dim3(MBR_WAVES * 64), 0, (hipStream_t)stream, n, T, tokens, length, stats);
+    FIRA_CHECK_LAUNCH("fira_mbr_bleu_stats");
     return 0;
 }

@@ -338,6 +338,53 @@ class Searcher:
         """The highest-log-probability sample per commit, first on ties."""
         return self.best(tokens, lengths, logp)
 
+    # ------------------------------------------------------------------ minimum-Bayes-risk pick by expected sentence BLEU
+    MBR_MAX_N, MBR_MAX_T = 32, 64
+
+    def mbr(self, tokens, lengths, logp=None):
+        """Minimum-Bayes-risk selection among candidate messages: the candidates of a commit are taken as draws from the model
+        and the one with the highest mean sentence BLEU (method 2) against the others wins.  ``tokens`` [B, n, T] vocabulary
+        ids and ``lengths`` [B, n] as ``sample`` returns them (or several ``sample`` calls concatenated along n), 1 <= n <= 32,
+        1 <= T <= 64; the message of a candidate is its ids at positions 1 .. length - 1 without <pad> / <eos> / <start>, which
+        is its text (``text.detokenize``).  ``logp`` [B, n] (optional) breaks ties, then the lower index.
+
+        Returns (pick: the winner's index per commit, utilities [B, n] float64 CPU tensor).  One launch
+        (``fira_mbr_bleu_stats``: all n x n pairs, exact integers), one copy back, the scores formed on the host by
+        ``metrics.mbr_utilities`` / ``mbr_pick`` -- ``==`` the string scorer on the same words.  Raises ValueError before
+        anything is launched on a wrong shape, an id outside int32 or n / T outside the limits."""
+        from . import metrics, ops
+        if not (torch.is_tensor(tokens) and torch.is_tensor(lengths)):
+            tokens, lengths = torch.as_tensor(tokens), torch.as_tensor(lengths)
+        if tokens.dim() != 3:
+            raise ValueError("tokens: expected [B, n, T] token ids, got shape %s" % (tuple(tokens.shape),))
+        B, n, T = tokens.shape
+        if not 1 <= n <= self.MBR_MAX_N:
+            raise ValueError("tokens: n = %d candidates per commit, outside 1..%d" % (n, self.MBR_MAX_N))
+        if not 1 <= T <= self.MBR_MAX_T:
+            raise ValueError("tokens: T = %d positions, outside 1..%d" % (T, self.MBR_MAX_T))
+        if tuple(lengths.shape) != (B, n):
+            raise ValueError("lengths: shape %s, expected %s" % (tuple(lengths.shape), (B, n)))
+        int_types = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
+        if tokens.dtype not in int_types or lengths.dtype not in int_types:
+            raise ValueError("tokens / lengths: expected integer tensors, got %s / %s" % (tokens.dtype, lengths.dtype))
+        if logp is not None:
+            logp = torch.as_tensor(logp)
+            if tuple(logp.shape) != (B, n):
+                raise ValueError("logp: shape %s, expected %s" % (tuple(logp.shape), (B, n)))
+        if B == 0:
+            return [], torch.zeros((0, n), dtype=torch.float64)
+        dev = self.model.device_
+        tokens, lengths = tokens.to(dev), lengths.to(dev)
+        if tokens.dtype == torch.int64:                       # (the one range check: a single read-back, before the launch)
+            lo, hi = torch.aminmax(tokens)
+            if int(lo) < -(1 << 31) or int(hi) >= 1 << 31:
+                raise ValueError("tokens: id outside the int32 range")
+        lengths = lengths.clamp(min=0, max=T)                 # (the message ends at min(length, T) anyway)
+        stats = ops.mbr_bleu_stats(tokens.to(torch.int32).contiguous(), lengths.to(torch.int32).contiguous())
+        util = metrics.mbr_utilities(stats.cpu())
+        pick = metrics.mbr_pick(util, None if logp is None else logp.detach().cpu())
+        return pick, torch.tensor(util, dtype=torch.float64).reshape(B, n)
+
     # ------------------------------------------------------------------ scoring given messages (teacher-forced)
     SCORE_TOKEN_KEYS = ("p_word", "p_entry", "entry", "copy_share", "top_id", "p_label")
     RANK_KEYS = ("logp_entry", "logp_word", "mean_logp_word")

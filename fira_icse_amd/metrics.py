@@ -132,3 +132,39 @@ def bleu_method2_from_stats(num: Sequence[int], cnt: Sequence[int], hyp_len: int
     bp = 1.0 if hyp_len > ref_len else math.exp(1 - ref_len / hyp_len)
     logs = [math.log(num[0] / dens[0])] + [math.log((num[i] + 1) / (dens[i] + 1)) for i in range(1, 4)]
     return bp * math.exp(math.fsum(0.25 * x for x in logs))
+
+
+def mbr_utilities(stats) -> List[List[float]]:
+    """Expected-BLEU utilities from the all-pairs statistics of ``fira_mbr_bleu_stats``: ``stats`` is [B][n][n][12] integers
+    (nested lists, a numpy array or a CPU tensor), row [b][i][j] the statistics of candidate i scored against candidate j.
+    ``u[b][i]`` is the mean over j != i of ``bleu_method2_from_stats`` of pair (i, j) -- Python ints in, ``math.fsum`` for the
+    mean -- so it is ``==`` the same mean of ``sentence_bleu_method2`` on the candidates' word lists.  0.0 for n == 1."""
+    if hasattr(stats, "tolist"):
+        stats = stats.tolist()
+    out = []
+    for commit in stats:
+        n = len(commit)
+        row = []
+        for i in range(n):
+            scores = [bleu_method2_from_stats(st[0:4], st[4:8], st[8], st[9]) for j, st in enumerate(commit[i]) if j != i]
+            row.append(math.fsum(scores) / (n - 1) if n > 1 else 0.0)
+        out.append(row)
+    return out
+
+
+def mbr_pick(utilities, logp=None) -> List[int]:
+    """Index of the candidate of highest utility per commit; ties go to the larger ``logp[b][i]`` when given, then to the
+    lower index (candidates that share no word with any other all have utility 0)."""
+    if hasattr(utilities, "tolist"):
+        utilities = utilities.tolist()
+    if logp is not None and hasattr(logp, "tolist"):
+        logp = logp.tolist()
+    pick = []
+    for b, row in enumerate(utilities):
+        if not row:
+            raise ValueError("mbr_pick: commit %d has no candidates" % b)
+        if logp is not None and len(logp[b]) != len(row):
+            raise ValueError("mbr_pick: commit %d has %d utilities and %d log-probabilities" % (b, len(row), len(logp[b])))
+        key = (lambda i: (row[i], logp[b][i], -i)) if logp is not None else (lambda i: (row[i], -i))
+        pick.append(max(range(len(row)), key=key))
+    return pick

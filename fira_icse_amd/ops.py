@@ -668,3 +668,19 @@ def dev_bleu_stats(ids, sou, sub_token, tar, V, hyp=None, stats=None):
     check(_lib.lib().fira_dev_bleu_stats(cur_stream(), B, T, int(V), L, S, ptr(_i32(ids)), ptr(_i32(sou)), ptr(_i32(sub_token)),
                                          ptr(_i32(tar)), ptr(_i32(hyp)), ptr(_i32(stats))), "fira_dev_bleu_stats")
     return hyp, stats
+
+
+def mbr_bleu_stats(tokens, length, stats=None):
+    """fira_mbr_bleu_stats: the sentence-BLEU statistics of every ordered pair of a commit's candidate messages.  tokens
+    [B,n,T] vocabulary ids, length [B,n], int32 (n <= 32, T <= 64); the message of a candidate is its ids at positions
+    1 .. length - 1 without <pad> / <eos> / <start>.  Returns stats [B,n,n,12] int32 -- row [b,i,j]: num[4], cnt[4], hyp_len,
+    ref_len, 0, 0 with candidate i as the hypothesis and j as the reference -- into ``stats`` when given.
+    ``metrics.mbr_utilities`` turns it into expected-BLEU utilities."""
+    B, n, T = tokens.shape
+    assert tuple(length.shape) == (B, n)
+    if stats is None:
+        stats = torch.empty((B, n, n, 12), dtype=torch.int32, device=tokens.device)
+    assert tuple(stats.shape) == (B, n, n, 12)
+    check(_lib.lib().fira_mbr_bleu_stats(cur_stream(), B, n, T, ptr(_i32(tokens)), ptr(_i32(length)), ptr(_i32(stats))),
+          "fira_mbr_bleu_stats")
+    return stats

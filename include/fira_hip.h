@@ -663,6 +663,16 @@ int fira_dev_bleu_stats(void* stream, int B, int T, int V, int L, int S,
                         int32_t* hyp,        /* [B,T] resolved vocabulary ids of the hypothesis, compacted, -1 behind hyp_len */
                         int32_t* stats);     /* [B,12]: num[4], cnt[4], hyp_len, ref_len, 0, 0 */
 
+/* The same statistics for every ordered pair of the n candidate messages of a commit (minimum-Bayes-risk selection by expected
+ * sentence BLEU; csrc/bleu.hip; additive, the ABI version is unchanged).  The message of candidate (b, i) is tokens[b][i] at
+ * positions 1 .. min(length[b][i], T) - 1 with every <pad> (0), <eos> (1) and <start> (2) dropped wherever it stands; ids at or
+ * past length are ignored; length <= 1 is the empty message; <unkm> is an ordinary word.  stats[b][i][j] takes candidate i as the
+ * hypothesis and candidate j as the reference (the diagonal included: num == cnt there).  int32 and exact; 1 <= n <= 32,
+ * 1 <= T <= 64; B == 0 is a no-op.                                                                                             */
+int fira_mbr_bleu_stats(void* stream, int B, int n, int T,
+                        const int32_t* tokens, /* [B,n,T] vocabulary ids */  const int32_t* length, /* [B,n] */
+                        int32_t* stats);       /* [B,n,n,12]: num[4], cnt[4], hyp_len, ref_len, 0, 0 */
+
 /* Encoder once per batch (run_model.py:202-207) + everything of the decode loop that does not depend
  * on the generated prefix: memory [B,S,256], mem_valid [B,S], cross-attention K/V of all layers,
  * LinearSource(memory).  State lives in the caller's workspace.                                     */

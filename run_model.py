@@ -96,7 +96,10 @@ def parse_args(argv):
                     "corpus perplexity")
     ap.add_argument("--rerank", default=None, choices=RERANK_KEYS, help="with --sample: score the drawn candidates in the same "
                     "run and write the best one under this key to OUTPUT/output_fira (default: the candidate of highest "
-                    "log-probability of the drawn entries)")
+                    "log-probability of the drawn entries).  logp_word / mean_logp_word: teacher-forced word probability; "
+                    "mbr_bleu: minimum-Bayes-risk -- the candidate of highest mean sentence BLEU against the other N - 1, "
+                    "computed on the device on token ids, ties to the higher log-probability (no scoring pass); every line of "
+                    "OUTPUT/output_fira_samples then carries the N values under the key")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
@@ -123,7 +126,7 @@ def parse_args(argv):
     return a
 
 
-RERANK_KEYS = ("logp_word", "mean_logp_word")
+RERANK_KEYS = ("logp_word", "mean_logp_word", "mbr_bleu")
 LR_SCHEDULES = ("constant", "inv-sqrt", "cosine", "linear")
 
 
@@ -478,7 +481,11 @@ class Run:
                                                 top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed, keys=idx)
             best = search.best_sample(toks, lens, logp)
             values = None
-            if a.rerank is not None:                         # score the drawn candidates; pick by the word marginal
+            if a.rerank == "mbr_bleu":                       # expected BLEU among the candidates themselves: no scoring pass
+                pick, util = search.mbr(toks, lens, logp)
+                best = [toks[k, j, :int(lens[k, j])].tolist() for k, j in enumerate(pick)]
+                values = util.tolist()
+            elif a.rerank is not None:                       # score the drawn candidates; pick by the word marginal
                 best, values = self.rerank(search, db, toks, lens)
             toks, lens, logp = toks.tolist(), lens.tolist(), logp.tolist()
             for k, i in enumerate(idx):
