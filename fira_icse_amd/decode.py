@@ -10,12 +10,13 @@ resolution) stays on the device with the reference's exact semantics.  ``beam = 
 from __future__ import annotations
 
 import ctypes as C
-from typing import List
+import dataclasses
+from typing import List, Optional, Tuple
 
 import torch
 
 from . import _lib
-from .config import EOS, PAD, START
+from .config import EOS, PAD, START, UNK
 from .model import DeviceBatch, TransModel
 
 
@@ -54,6 +55,61 @@ def concurrent_streams(n: int, device, pool: int = 12):
         if c not in chosen:
             chosen.append(c)
     return chosen
+
+
+@dataclasses.dataclass(frozen=True)
+class Constraints:
+    """What a search must not emit (``fira_constrain_dist``).  A constraint blocks a WORD: its generator id and
+    every copy slot of the commit that carries it, so the copy head cannot route around it.
+
+    ``no_repeat_ngram`` n >= 1: no n-gram of words occurs twice in a message (1: no word twice); 0 = off.
+    ``min_length`` M: no <eos> before M words (a hypothesis that runs to tar_len ends without one, as always); 0 = off.
+    ``banned``: up to 32 vocabulary ids in [UNK, vocab) = [3, vocab) -- <pad>, <eos> and <start> (0..2) cannot be banned,
+    <unkm> (3) can; stored sorted and without duplicates, so equal sets compare and hash equal.
+
+    Values are checked here (``ValueError`` with the reason); what depends on the model (n and M against tar_len, ids against
+    the vocabulary) is checked by ``check`` when a ``Searcher`` takes the value."""
+    no_repeat_ngram: int = 0
+    min_length: int = 0
+    banned: Tuple[int, ...] = ()
+
+    MAX_BANNED = 32
+
+    def __post_init__(self):
+        for name in ("no_repeat_ngram", "min_length"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError("Constraints: %s = %r is not an integer" % (name, v))
+            if v < 0:
+                raise ValueError("Constraints: %s = %d is negative" % (name, v))
+        try:
+            ids = list(self.banned)
+        except TypeError:
+            raise ValueError("Constraints: banned = %r is not a sequence of vocabulary ids" % (self.banned,)) from None
+        for w in ids:
+            if isinstance(w, bool) or not isinstance(w, int):
+                raise ValueError("Constraints: banned id %r is not an integer" % (w,))
+            if w < UNK:
+                raise ValueError("Constraints: banned id %d is below %d (<pad>, <eos> and <start> cannot be banned)" % (w, UNK))
+        ids = tuple(sorted(set(ids)))
+        if len(ids) > self.MAX_BANNED:
+            raise ValueError("Constraints: %d banned ids, more than %d" % (len(ids), self.MAX_BANNED))
+        object.__setattr__(self, "banned", ids)
+
+    @property
+    def active(self) -> bool:
+        return bool(self.no_repeat_ngram or self.min_length or self.banned)
+
+    def check(self, cfg) -> "Constraints":
+        """Against a model's geometry (the kernel's own argument checks, with the names of this class)."""
+        if self.no_repeat_ngram > cfg.tar_len:
+            raise ValueError("Constraints: no_repeat_ngram = %d exceeds tar_len = %d" % (self.no_repeat_ngram, cfg.tar_len))
+        if self.min_length > cfg.tar_len - 2:
+            raise ValueError("Constraints: min_length = %d exceeds tar_len - 2 = %d" % (self.min_length, cfg.tar_len - 2))
+        for w in self.banned:
+            if w >= cfg.vocab_size:
+                raise ValueError("Constraints: banned id %d outside the vocabulary [%d, %d)" % (w, UNK, cfg.vocab_size))
+        return self
 
 
 class Scores(dict):
@@ -106,10 +162,31 @@ class Searcher:
                                                   _lib.ptr(tokens), _lib.ptr(parent), _lib.ptr(dist), _lib.ptr(best_id),
                                                   _lib.ptr(best_p), self.flags), "fira_decode_step")
 
+    def _active(self, constraints: Optional[Constraints]) -> Optional[Constraints]:
+        """None for "no constraint" (None or an inactive value: today's launches, buffers and graphs), else the checked value."""
+        if constraints is None:
+            return None
+        if not isinstance(constraints, Constraints):
+            raise ValueError("constraints: expected decode.Constraints or None, got %r" % (constraints,))
+        return constraints.check(self.cfg) if constraints.active else None
+
+    def _constrain(self, st, R, rows_per_commit, gen, length, best_id, best_p):
+        """fira_constrain_dist on st["dist"] with the constraints of the state ``st`` (scalars baked into a captured graph)."""
+        c = st["con"]
+        _lib.check(_lib.lib().fira_constrain_dist(_lib.cur_stream(), C.byref(self.model.dims), R, rows_per_commit, _lib.ptr(gen),
+                                                  _lib.ptr(length), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), c.no_repeat_ngram,
+                                                  c.min_length, _lib.ptr(st["banned"]), len(c.banned), _lib.ptr(st["dist"]),
+                                                  _lib.ptr(best_id), _lib.ptr(best_p)), "fira_constrain_dist")
+
+    def _banned_buffer(self, c: Constraints):
+        return torch.tensor(list(c.banned) or [0], dtype=torch.int32, device=self.model.device_)
+
     # ------------------------------------------------------------------ greedy (beam 1): no sort, no dist tensor
-    def _greedy_state(self, B):
-        """Static device buffers + captured hipGraphs of the step loop for batch size B (built on first use)."""
-        key = ("greedy", B)
+    def _greedy_state(self, B, con: Optional[Constraints] = None):
+        """Static device buffers + captured hipGraphs of the step loop for batch size B (built on first use).  With active
+        constraints the state (and so its graphs: the scalars are baked into the captured launches) is keyed by their value and
+        also owns the [B, out_len] distribution the constraint kernel edits and the banned ids."""
+        key = ("greedy", B) if con is None else ("greedy", B, con)
         if key in self._ws:
             return self._ws[key]
         cfg, dev = self.cfg, self.model.device_
@@ -117,7 +194,10 @@ class Searcher:
         i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
         st = dict(sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), out=i32(B, T), length=i32(B),
                   prob=torch.ones(B, dtype=torch.float32, device=dev), alive=i32(B), tok=i32(B), n_alive=i32(T),
-                  best_id=i32(B), best_p=torch.empty(B, dtype=torch.float32, device=dev), graphs=None)
+                  best_id=i32(B), best_p=torch.empty(B, dtype=torch.float32, device=dev), graphs=None, con=con)
+        if con is not None:
+            st["dist"] = torch.empty((B, cfg.out_len), dtype=torch.float32, device=dev)
+            st["banned"] = self._banned_buffer(con)
         self._ws[key] = st
         return st
 
@@ -135,19 +215,24 @@ class Searcher:
         arg-max of the output distribution, then the hypothesis bookkeeping), no torch op, no host round trip."""
         lib, s = _lib.lib(), _lib.cur_stream()
         for step in range(lo, hi):
-            self._step(ws, B, 1, step, st["tok"], None, None, st["best_id"], st["best_p"])
+            if st["con"] is None:
+                self._step(ws, B, 1, step, st["tok"], None, None, st["best_id"], st["best_p"])
+            else:       # the step writes the distribution, the constraint kernel edits it and takes the arg-max of what is left
+                self._step(ws, B, 1, step, st["tok"], None, st["dist"], None, None)
+                self._constrain(st, B, 1, st["out"], st["length"], st["best_id"], st["best_p"])
             _lib.check(lib.fira_greedy_advance(s, C.byref(self.model.dims), B, step, _lib.ptr(st["best_id"]),
                                                _lib.ptr(st["best_p"]), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]),
                                                _lib.ptr(st["out"]), _lib.ptr(st["length"]), _lib.ptr(st["prob"]),
                                                _lib.ptr(st["alive"]), _lib.ptr(st["tok"]), _lib.ptr(st["n_alive"])),
                        "fira_greedy_advance")
 
-    def _greedy_start(self, db: DeviceBatch, chunk: int, use_graphs: bool):
+    def _greedy_start(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None):
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the loop's context."""
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
+        con = self._active(constraints)                      # raises before anything is launched
         ws = self._begin(db, 1)
-        st = self._greedy_state(B)
+        st = self._greedy_state(B, con)
         st["sou"].copy_(db.sou)
         st["sub"].copy_(db.sub_token)
         self._greedy_reset(st)
@@ -183,13 +268,15 @@ class Searcher:
         return int(ctx["st"]["n_alive"][hi - 1].item()) == 0      # every hypothesis has emitted <eos> (run_model.py:276-279)
 
     @torch.no_grad()
-    def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True):
-        """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).
+    def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None):
+        """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``: a ``Constraints``
+        value; the step then writes its distribution, ``fira_constrain_dist`` zeroes the blocked words' entries and takes the
+        arg-max of the rest (probability = the product of the UNnormalised entries taken); None or inactive: today's loop.
 
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
-        ctx = self._greedy_start(db, chunk, use_graphs)
+        ctx = self._greedy_start(db, chunk, use_graphs, constraints)
         while True:
             self._greedy_launch(ctx)
             if self._greedy_done(ctx):
@@ -198,7 +285,7 @@ class Searcher:
         return st["out"].long(), st["length"].long(), st["prob"].clone()
 
     @torch.no_grad()
-    def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5):
+    def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -209,8 +296,9 @@ class Searcher:
         BELOW one lane (x0.8) once the process had created more streams (a trainer's) -- two lanes on one queue run one after
         the other.  On 8 queues (run_model.py / bench.py / this package set GPU_MAX_HW_QUEUES=8 before HIP initialises) three
         lanes give x2.06 and four x2.35 in a process that trained first; six collapse again (profiles/r6_probes.md).
-        Same arithmetic, same ids as ``greedy`` batch by batch."""
+        Same arithmetic, same ids as ``greedy`` batch by batch, ``constraints`` included."""
         dbs = list(dbs)
+        self._active(constraints)                            # raises before a lane starts
         n_lane = max(1, min(in_flight, len(dbs)))
         if not hasattr(self, "_lanes") or len(self._lanes) < n_lane:
             streams = concurrent_streams(n_lane, self.model.device_)
@@ -239,7 +327,7 @@ class Searcher:
                         else:
                             lane._greedy_launch(ctx)
                     if active[k] is None and nxt < len(dbs):
-                        ctx = lane._greedy_start(dbs[nxt], chunk, True)
+                        ctx = lane._greedy_start(dbs[nxt], chunk, True, constraints)
                         lane._greedy_launch(ctx)
                         active[k] = (nxt, ctx)
                         nxt += 1
@@ -553,8 +641,8 @@ class Searcher:
         return torch.argmax(rank_values(scores, by), dim=1).tolist()
 
     # ------------------------------------------------------------------ beam search with the reference's semantics
-    def _beam_state(self, B, beam):
-        key = ("beam", B, beam)
+    def _beam_state(self, B, beam, con: Optional[Constraints] = None):
+        key = ("beam", B, beam) if con is None else ("beam", B, beam, con)      # (a captured graph bakes the constraint scalars)
         if key in self._ws:
             return self._ws[key]
         cfg, dev = self.cfg, self.model.device_
@@ -564,7 +652,9 @@ class Searcher:
                   prob=[torch.zeros(BR, dtype=torch.float32, device=dev) for _ in range(2)],
                   tok=i32(BR), parent=i32(BR), fin=i32(BR), active=i32(9), done=i32(1),
                   dist=torch.empty((BR, cfg.out_len), dtype=torch.float32, device=dev),
-                  sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), graphs=None)
+                  sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), graphs=None, con=con)
+        if con is not None:
+            st["banned"] = self._banned_buffer(con)
         self._ws[key] = st
         return st
 
@@ -578,7 +668,8 @@ class Searcher:
         st["done"].zero_()
 
     def _beam_steps(self, st, ws, B, beam, lo, hi):
-        """Steps lo..hi-1 of run_model.py:225-340: prepare -> KV-cached decoder step -> select, all on the device."""
+        """Steps lo..hi-1 of run_model.py:225-340: prepare -> KV-cached decoder step -> (constraints, when the state has them)
+        -> select, all on the device."""
         lib, s, T = _lib.lib(), _lib.cur_stream(), self.cfg.tar_len
         for step in range(lo, hi):
             cur, nxt = step & 1, (step + 1) & 1
@@ -586,6 +677,8 @@ class Searcher:
                                              _lib.ptr(st["tok"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]),
                                              _lib.ptr(st["done"])), "fira_beam_prepare")
             self._step(ws, B, beam, step, st["tok"], st["parent"] if step > 0 else None, st["dist"], None, None)
+            if st["con"] is not None:
+                self._constrain(st, B * beam, beam, st["gen"][cur], st["length"][cur], None, None)
             _lib.check(lib.fira_beam_select(s, C.byref(self.model.dims), B, beam, _lib.ptr(st["dist"]),
                                             _lib.ptr(st["fin"]), _lib.ptr(st["active"]), _lib.ptr(st["done"]),
                                             _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["gen"][cur]),
@@ -594,16 +687,20 @@ class Searcher:
                                             _lib.ptr(st["prob"][nxt]), _lib.ptr(st["parent"])), "fira_beam_select")
 
     @torch.no_grad()
-    def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True):
-        """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).
+    def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
+             constraints: Optional[Constraints] = None):
+        """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``: a ``Constraints``
+        value; one ``fira_constrain_dist`` call per step then zeroes the blocked words' entries of every row between the step
+        and the selection (nothing is renormalised); None or inactive: today's three calls per step and today's graphs.
 
         Per step: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library calls, no torch
         op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam) shape, and
         the ``done`` latch is read back between chunks (run_model.py:276-279)."""
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
+        con = self._active(constraints)                      # raises before anything is launched
         ws = self._begin(db, beam)
-        st = self._beam_state(B, beam)
+        st = self._beam_state(B, beam, con)
         st["sou"].copy_(db.sou)
         st["sub"].copy_(db.sub_token)
         self._beam_reset(st, B, beam)

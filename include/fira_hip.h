@@ -722,6 +722,36 @@ int fira_greedy_advance(void* stream, const fira_dims* d, int B, int step, const
                         const int32_t* sou, const int32_t* sub_token, int32_t* out, int32_t* length, float* prob,
                         int32_t* alive, int32_t* tokens, int32_t* n_alive);
 
+/* Search constraints (csrc/constrain.hip; additive, the ABI version is unchanged): edits the step's distribution in place
+ * between fira_decode_step and fira_beam_select / fira_greedy_advance.  W = vocab + sou_len + sub_len; entry i resolves to the
+ * word w(i) = i below vocab, sou[b, i - vocab] below vocab + sou_len, sub_token[b, i - vocab - sou_len] above, as the two
+ * selection kernels resolve it (b = r / rows_per_commit: n_beam for a beam search, 1 for greedy).  The hypothesis of row r is
+ * h_1 .. h_m = gen[r, 1 .. length[r] - 1], m = length[r] - 1 (<start> at position 0 is not counted; ids at or past length are
+ * ignored; length is clamped to 1 .. tar_len).  A row with gen[r, length[r] - 1] == <eos> (1) is finished: its dist is left
+ * untouched.  For every other row the blocked words are the union of
+ *   ban        every banned[k] inside [0, vocab) (ids outside are ignored; the Python layer rejects them)
+ *   no-repeat  for n = no_repeat_ngram >= 1: every h_{j+n-1} with 1 <= j and j + n - 1 <= m whose predecessors h_j .. h_{j+n-2}
+ *              equal the last n - 1 words h_{m-n+2} .. h_m (n = 1: every word emitted so far; nothing while m < n; the tail
+ *              never matches itself as a completed n-gram: j + n - 1 <= m is the whole condition); 0 = off
+ *   min length <eos> while m < min_length
+ * and every entry i with w(i) blocked -- the generator id and every copy slot that carries the word -- is set to exactly 0.0f.
+ * Every other element keeps its bits; nothing is renormalised (the search ranks products of probabilities: a zero loses).
+ * best_id / best_p (both NULL, or both [R]): the arg-max entry of the EDITED row and its value, under fira_decode_step_ex's rule
+ * for its own best_id: the largest value, the lowest entry index among equals (there: the first maximum within the generator
+ * part, the first within the copy part, the generator part on a tie between the two).  With every constraint off they equal
+ * the step's own bit for bit (a finished row reports the arg-max of its untouched row); NaN never wins.  A row whose every
+ * positive entry is blocked is not special-cased: all its candidates tie at 0 and the tie rule decides -- entry 0 here, the
+ * lowest flattened index in fira_beam_select.  Without best_id the row is not read, only the blocked entries are stored.
+ * tar_len <= 64, vocab <= 25 600, sou_len + sub_len <= 1 024 (the limits of fira_decode_step_sample / _score),
+ * 0 <= no_repeat_ngram <= tar_len, 0 <= min_length <= tar_len - 2, 0 <= n_banned <= 32, rows_per_commit >= 1 divides R;
+ * R == 0 is a no-op.  Any row width and pitch alignment; vector stores only, no atomics on global memory.                  */
+int fira_constrain_dist(void* stream, const fira_dims* d, int R, int rows_per_commit, const int32_t* gen /* [R, tar_len] */,
+                        const int32_t* length /* [R] */, const int32_t* sou /* [R / rows_per_commit, sou_len] */,
+                        const int32_t* sub_token /* [R / rows_per_commit, sub_len] */, int no_repeat_ngram, int min_length,
+                        const int32_t* banned /* device, [n_banned] */, int n_banned,
+                        float* dist /* [R, vocab + sou_len + sub_len], in place */,
+                        int32_t* best_id, float* best_p /* both NULL or both given */);
+
 /* On-device sampling of candidate messages (temperature, top-k, top-p).  Workspace: fira_decode_begin_ex /
  * fira_decode_workspace_bytes_ex with n_beam = n_sample (1..8) and the same flags (FIRA_DECODE_KV_BF16 allowed).
  *   fira_decode_step_sample : fira_decode_step_ex for the B * n_sample rows (row r = commit r / n_sample, sample

@@ -100,6 +100,13 @@ def parse_args(argv):
                     "mbr_bleu: minimum-Bayes-risk -- the candidate of highest mean sentence BLEU against the other N - 1, "
                     "computed on the device on token ids, ties to the higher log-probability (no scoring pass); every line of "
                     "OUTPUT/output_fira_samples then carries the N values under the key")
+    ap.add_argument("--no-repeat-ngram", type=int, default=None, metavar="N", help="test: the search (any --beam) emits no "
+                    "N-gram of words twice in a message (1: no word twice); a word is blocked through its generator id and "
+                    "through every copy slot of the commit that carries it")
+    ap.add_argument("--min-length", type=int, default=None, metavar="M", help="test: the search does not end a message before "
+                    "M words (at most tar_len - 2)")
+    ap.add_argument("--ban-words", default=None, metavar="W[,W...]", help="test: up to 32 vocabulary words the search never "
+                    "emits, generator or copied (<unkm> may be given by name; <pad>, <eos> and <start> may not)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
@@ -120,6 +127,7 @@ def parse_args(argv):
         check_clip_args(a)
         check_lr_schedule_args(a)
         check_score_args(a)
+        check_constraint_args(a)
         check_sample_args(a)
     except ValueError as e:
         ap.error(str(e))
@@ -228,6 +236,50 @@ def read_score_lines(path, n_commits):
             raise ValueError("--score %s: line %d holds %d candidates, outside 1..8" % (path, k + 1, len(cands)))
         out.append((cands, is_json))
     return out
+
+
+CONSTRAINT_OPTIONS = (("no_repeat_ngram", "--no-repeat-ngram"), ("min_length", "--min-length"), ("ban_words", "--ban-words"))
+
+
+def check_constraint_args(a):
+    """Validates --no-repeat-ngram / --min-length / --ban-words against the other options (no GPU, no DataSet needed); raises
+    ValueError on a conflict or an out-of-range value.  The words are looked up later (constraints_from_args)."""
+    given = [flag for name, flag in CONSTRAINT_OPTIONS if getattr(a, name) is not None]
+    if not given:
+        return a
+    if a.stage != "test":
+        raise ValueError("%s only apply to the test stage" % ", ".join(given))
+    if a.sample is not None:
+        raise ValueError("%s constrain a search: they do not combine with --sample" % ", ".join(given))
+    if a.score is not None:
+        raise ValueError("%s constrain a search: they do not combine with --score" % ", ".join(given))
+    if a.no_repeat_ngram is not None and a.no_repeat_ngram < 0:
+        raise ValueError("--no-repeat-ngram %d: must be >= 0 (0 = off)" % a.no_repeat_ngram)
+    if a.min_length is not None and a.min_length < 0:
+        raise ValueError("--min-length %d: must be >= 0 (0 = off)" % a.min_length)
+    if a.ban_words is not None and not [w for w in a.ban_words.split(",") if w.strip()]:
+        raise ValueError("--ban-words: no word given")
+    return a
+
+
+def constraints_from_args(a, vocab, cfg=None):
+    """The decode.Constraints of the command line (None without the options): --ban-words looked up in ``vocab`` (word -> id).
+    Raises ValueError naming an unknown word, a word that cannot be banned, or a value outside the model's limits."""
+    from fira_icse_amd.decode import Constraints
+    if all(getattr(a, name, None) is None for name, _ in CONSTRAINT_OPTIONS):
+        return None
+    ids = []
+    for w in (a.ban_words or "").split(","):
+        w = w.strip()
+        if not w:
+            continue
+        if w not in vocab:
+            raise ValueError("--ban-words: %r is not in the vocabulary" % w)
+        if vocab[w] < UNK:
+            raise ValueError("--ban-words: %s cannot be banned" % w)
+        ids.append(int(vocab[w]))
+    c = Constraints(no_repeat_ngram=a.no_repeat_ngram or 0, min_length=a.min_length or 0, banned=tuple(ids))
+    return c.check(cfg) if cfg is not None else c
 
 
 SAMPLE_OPTIONS = (("temperature", "--temperature", 1.0), ("top_k", "--top-k", 0), ("top_p", "--top-p", 1.0),
@@ -432,6 +484,7 @@ class Run:
         given = None
         if self.a.score is not None and self.a.score != "refs":
             given = read_score_lines(self.a.score, len(store))   # a wrong line count is an error before the model loads
+        constraints = constraints_from_args(self.a, self.vocab, cfg)       # an unknown word too
         self.model = TransModel(cfg, device="cuda:%d" % self.local, init=False)
         self.model.load_state_dict(torch.load(os.path.join(self.root, "best_model.pt"), map_location="cpu"))
         self.model.compute_dtype = self.a.dtype
@@ -452,9 +505,9 @@ class Run:
             idxs = [mine[lo:lo + cfg.test_batch_size] for lo in starts[g0:g0 + group]]
             dbs = [self.device_batch(store, idx) for idx in idxs]
             if cfg.beam_size == 1:
-                outs = [search.best(*r) for r in search.greedy_many(dbs, in_flight=group)]
+                outs = [search.best(*r) for r in search.greedy_many(dbs, in_flight=group, constraints=constraints)]
             else:
-                outs = [search.best(*search.beam(dbs[0], cfg.beam_size))]
+                outs = [search.best(*search.beam(dbs[0], cfg.beam_size, constraints=constraints))]
             for idx, hyps in zip(idxs, outs):
                 for h, i in zip(hyps, idx):
                     lines.append(text.detokenize(h, self.r_vocab, self.var_maps[test_index[i]]))
