@@ -163,65 +163,34 @@ __global__ __launch_bounds__(NT) void beam_select_kernel(int beam, int T, int W,
     }
 }
 
-// Greedy (beam 1) bookkeeping of one step, run_model.py:305-340 with one hypothesis per commit: resolve the chosen
-// output index to a vocabulary id (copy slots read the commit's code / sub-token ids), append it, multiply the running
-// probability, and stop the hypothesis at <eos>.  n_alive[step] (zeroed by the caller before the first step) receives
-// the number of hypotheses still running after this step, so the host can stop early with ONE read-back per chunk.
-__global__ __launch_bounds__(256) void greedy_advance_kernel(int B, int T, int V, int L, int S, int step,
-                                                             const int32_t* __restrict__ best_id,
-                                                             const float* __restrict__ best_p,
-                                                             const int32_t* __restrict__ sou,
-                                                             const int32_t* __restrict__ sub, int32_t* __restrict__ out,
-                                                             int32_t* __restrict__ length, float* __restrict__ prob,
-                                                             int32_t* __restrict__ alive, int32_t* __restrict__ tok,
-                                                             int32_t* __restrict__ n_alive) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    int still = 0;
-    if (b < B) {
-        if (alive[b]) {
-            const int w = best_id[b];
-            int nt = w;
-            if (w >= V + L) nt = sub[(size_t)b * S + min(w - V - L, S - 1)];
-            else if (w >= V) nt = sou[(size_t)b * L + (w - V)];
-            out[(size_t)b * T + step + 1] = nt;
-            prob[b] *= best_p[b];
-            length[b] += 1;
-            still = nt != 1;                       // <eos> = 1 (config.EOS; the CLI checks the vocabulary agrees)
-            alive[b] = still;
-            tok[b] = still ? nt : 0;
-        } else {
-            tok[b] = 0;
-        }
-    }
-    const unsigned long long m = __ballot(still);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&n_alive[step], __popcll(m));
-}
-
-// Sampling bookkeeping of one step: greedy_advance_kernel over the B * n_sample rows of fira_decode_step_sample, copy ids
-// resolved through the sou / sub-token row of the row's commit r / n_sample, and the log-probability of every emitted id
-// summed as well (the product of ~30 sampled probabilities can underflow fp32; the log sum ranks candidates).
-__global__ __launch_bounds__(256) void sample_advance_kernel(int R, int n_sample, int T, int V, int L, int S, int step,
-                                                             const int32_t* __restrict__ best_id,
-                                                             const float* __restrict__ best_p,
-                                                             const int32_t* __restrict__ sou,
-                                                             const int32_t* __restrict__ sub, int32_t* __restrict__ out,
-                                                             int32_t* __restrict__ length, float* __restrict__ prob,
-                                                             float* __restrict__ logp, int32_t* __restrict__ alive,
-                                                             int32_t* __restrict__ tok, int32_t* __restrict__ n_alive) {
+// Greedy (beam 1) and sampling bookkeeping of one step, run_model.py:305-340 with one hypothesis per row: resolve the chosen
+// output index to a vocabulary id (copy slots read the code / sub-token ids of the row's commit r / rows_per_commit), append it,
+// multiply the running probability, and stop the hypothesis at <eos>.  Greedy: R = B rows, one per commit, logp = nullptr.
+// Sampling: the B * n_sample rows of fira_decode_step_sample, and logp also sums the log-probability of every emitted id (the
+// product of ~30 sampled probabilities can underflow fp32; the log sum ranks candidates).  n_alive[step] (zeroed by the caller
+// before the first step) receives the number of hypotheses still running after this step, so the host can stop early with ONE
+// read-back per chunk.
+__global__ __launch_bounds__(256) void advance_kernel(int R, int rows_per_commit, int T, int V, int L, int S, int step,
+                                                      const int32_t* __restrict__ best_id, const float* __restrict__ best_p,
+                                                      const int32_t* __restrict__ sou, const int32_t* __restrict__ sub,
+                                                      int32_t* __restrict__ out, int32_t* __restrict__ length,
+                                                      float* __restrict__ prob, float* __restrict__ logp,
+                                                      int32_t* __restrict__ alive, int32_t* __restrict__ tok,
+                                                      int32_t* __restrict__ n_alive) {
     const int r = blockIdx.x * 256 + threadIdx.x;
     int still = 0;
     if (r < R) {
         if (alive[r]) {
-            const int b = r / n_sample;
+            const int b = r / rows_per_commit;
             const int w = best_id[r];
             int nt = w;
             if (w >= V + L) nt = sub[(size_t)b * S + min(w - V - L, S - 1)];
             else if (w >= V) nt = sou[(size_t)b * L + (w - V)];
             out[(size_t)r * T + step + 1] = nt;
             prob[r] *= best_p[r];
-            logp[r] += logf(best_p[r]);
+            if (logp) logp[r] += logf(best_p[r]);
             length[r] += 1;
-            still = nt != 1;                       // <eos> = 1 (config.EOS)
+            still = nt != 1;                       // <eos> = 1 (config.EOS; the CLI checks the vocabulary agrees)
             alive[r] = still;
             tok[r] = still ? nt : 0;
         } else {
@@ -290,9 +259,9 @@ int fira_greedy_advance(void* stream, const fira_dims* d, int B, int step, const
                         const int32_t* sou, const int32_t* sub_token, int32_t* out, int32_t* length, float* prob,
                         int32_t* alive, int32_t* tokens, int32_t* n_alive) {
     FIRA_REQUIRE(d && B > 0 && step >= 0 && step + 1 < d->tar_len, "fira_greedy_advance: bad step %d", step);
-    hipLaunchKernelGGL(fira::greedy_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, B,
-                       d->tar_len, d->vocab, d->sou_len, d->sub_len, step, best_id, best_p, sou, sub_token, out, length,
-                       prob, alive, tokens, n_alive);
+    hipLaunchKernelGGL(fira::advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, 1, d->tar_len,
+                       d->vocab, d->sou_len, d->sub_len, step, best_id, best_p, sou, sub_token, out, length, prob,
+                       (float*)nullptr, alive, tokens, n_alive);
     FIRA_CHECK_LAUNCH("greedy_advance");
     return 0;
 }
@@ -302,7 +271,7 @@ int fira_sample_advance(void* stream, const fira_dims* d, int B, int n_sample, i
     FIRA_REQUIRE(d && B > 0 && step >= 0 && step + 1 < d->tar_len, "fira_sample_advance: bad step %d", step);
     FIRA_REQUIRE(n_sample >= 1 && n_sample <= 8, "fira_sample_advance: n_sample %d outside 1..8", n_sample);
     const int R = B * n_sample;
-    hipLaunchKernelGGL(fira::sample_advance_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, R, n_sample,
+    hipLaunchKernelGGL(fira::advance_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, R, n_sample,
                        d->tar_len, d->vocab, d->sou_len, d->sub_len, step, best_id, best_p, sou, sub_token, out, length,
                        prob, logp, alive, tokens, n_alive);
     FIRA_CHECK_LAUNCH("sample_advance");

@@ -6,6 +6,11 @@ Here the encoder, the cross-attention K/V of all layers and ``LinearSource(memor
 (``fira_decode_begin``); every step is one KV-cached pass over the (commit, beam) rows (``fira_decode_step``), and the
 hypothesis bookkeeping (probability products, -1 for finished rows, carried finished beams, descending sort, copy-id
 resolution) stays on the device with the reference's exact semantics.  ``beam = 1`` is the reference's "greedy".
+
+Every search (``greedy`` / ``greedy_many``, ``sample``, ``score``, ``beam``) is the same chunked step loop, driven by ``_Loop``:
+static buffers per ``Searcher._ws`` key, the steps captured once into hipGraphs of ``chunk`` steps, replayed chunk by chunk with
+at most one device value read back between chunks.  A search supplies its state, its reset, its ``steps(lo, hi)`` (the library
+calls of those steps), its stop test and how its results are read out -- nothing else.
 """
 from __future__ import annotations
 
@@ -129,6 +134,79 @@ def rank_values(scores, by: str) -> torch.Tensor:
     return scores[by]
 
 
+class _Loop:
+    """The chunked step loop of one search over one batch, on the current stream.
+
+    Creating it runs the encoder pass (``Searcher._begin``) and finds or builds the search's static state under ``key`` (see
+    ``Searcher._state``); the search then fills in its own inputs and calls ``start`` with its ``steps(lo, hi)``, its
+    ``reset()`` and, if it can end early, its ``stop(hi)`` (evaluated on the host after the chunk that ended at step ``hi``:
+    the one read-back between chunks).  ``n_steps`` is the number of steps the loop needs when the host knows it (default: all
+    tar_len - 1): chunks that begin at or after it are not run, and eager launches trim the last chunk to it (a captured chunk
+    is replayed whole).  ``launch`` / ``done`` are one turn of the loop, so a caller can keep several loops in flight; ``run``
+    is all turns of one.
+
+    The graphs live in the state (``st["graphs"]``: None before capture, then one object with ``.replay()`` per chunk) beside
+    the ``chunk`` and the ``bounds`` they were captured with: a graph call with another ``chunk`` is refused, since the captured
+    chunks would not match its bounds.  Eager calls take any ``chunk``."""
+
+    def __init__(self, search: "Searcher", db: DeviceBatch, rows: int, key, make, chunk: int, use_graphs: bool):
+        st = search._ws.get(key)
+        if use_graphs and st is not None and st["graphs"] is not None and st["chunk"] != chunk:
+            raise ValueError("chunk = %d, but the graphs of %r were captured with chunk = %d (use_graphs=False takes any chunk)"
+                             % (chunk, key, st["chunk"]))
+        self.T, self.chunk, self.use_graphs = search.cfg.tar_len, chunk, use_graphs
+        self.ws = search._begin(db, rows)
+        self.st = search._state(key, db, make)
+
+    def start(self, steps, reset, stop=None, n_steps: Optional[int] = None):
+        st, T = self.st, self.T
+        self.steps, self.stop = steps, stop
+        self.n_steps = T - 1 if n_steps is None else n_steps
+        reset()
+        if self.use_graphs and st["graphs"] is not None:
+            self.bounds = st["bounds"]
+        else:
+            self.bounds = [(lo, min(lo + self.chunk, T - 1)) for lo in range(0, T - 1, self.chunk)]
+            if self.use_graphs:
+                # warm-up outside capture (lazy initialisation inside the library / torch), then capture every chunk
+                steps(0, 1)
+                torch.cuda.synchronize()
+                graphs = []
+                for lo, hi in self.bounds:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        steps(lo, hi)
+                    graphs.append(g)
+                st.update(graphs=graphs, chunk=self.chunk, bounds=self.bounds)
+                reset()
+        self.n = sum(lo < self.n_steps for lo, _ in self.bounds)      # chunks this loop runs at most
+        self.i = self.hi = 0                                           # next chunk; end of the last step run
+        return self
+
+    def launch(self):
+        """Enqueue the next chunk of steps: one hipGraph replay, or the eager calls."""
+        lo, hi = self.bounds[self.i]
+        if self.use_graphs:
+            self.st["graphs"][self.i].replay()
+        else:
+            hi = min(hi, self.n_steps)
+            self.steps(lo, hi)
+        self.hi = hi
+
+    def done(self) -> bool:
+        """After the chunk launched last: advance, and only if chunks remain evaluate the stop test (which synchronises with
+        that chunk); nothing is read back after the final chunk."""
+        self.i += 1
+        return self.i >= self.n or (self.stop is not None and self.stop(self.hi))
+
+    def run(self):
+        done = self.n == 0
+        while not done:
+            self.launch()
+            done = self.done()
+        return self.st
+
+
 class Searcher:
     def __init__(self, model: TransModel, kv_bf16: bool = False):
         """``kv_bf16``: stream a bf16 copy of the cross-attention K|V in the step loop (FIRA_DECODE_KV_BF16: half of the
@@ -181,26 +259,26 @@ class Searcher:
     def _banned_buffer(self, c: Constraints):
         return torch.tensor(list(c.banned) or [0], dtype=torch.int32, device=self.model.device_)
 
-    # ------------------------------------------------------------------ greedy (beam 1): no sort, no dist tensor
-    def _greedy_state(self, B, con: Optional[Constraints] = None):
-        """Static device buffers + captured hipGraphs of the step loop for batch size B (built on first use).  With active
-        constraints the state (and so its graphs: the scalars are baked into the captured launches) is keyed by their value and
-        also owns the [B, out_len] distribution the constraint kernel edits and the banned ids."""
-        key = ("greedy", B) if con is None else ("greedy", B, con)
-        if key in self._ws:
-            return self._ws[key]
-        cfg, dev = self.cfg, self.model.device_
-        T = cfg.tar_len
-        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-        st = dict(sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), out=i32(B, T), length=i32(B),
-                  prob=torch.ones(B, dtype=torch.float32, device=dev), alive=i32(B), tok=i32(B), n_alive=i32(T),
-                  best_id=i32(B), best_p=torch.empty(B, dtype=torch.float32, device=dev), graphs=None, con=con)
-        if con is not None:
-            st["dist"] = torch.empty((B, cfg.out_len), dtype=torch.float32, device=dev)
-            st["banned"] = self._banned_buffer(con)
-        self._ws[key] = st
+    def _state(self, key, db: DeviceBatch, make):
+        """The static device buffers of one search loop (its captured hipGraphs live beside them), built on first use as
+        ``make(i32, f32)`` (zero-filled int32 / float32 allocators) plus what every search has: the commits' ``sou`` /
+        ``sub`` id rows, which are filled from ``db`` here, and ``graphs`` = None until ``_Loop`` captures."""
+        st = self._ws.get(key)
+        if st is None:
+            cfg, dev = self.cfg, self.model.device_
+            i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            st = self._ws[key] = dict(make(i32, f32), sou=i32(db.B, cfg.sou_len), sub=i32(db.B, cfg.sub_token_len), graphs=None)
+        st["sou"].copy_(db.sou)
+        st["sub"].copy_(db.sub_token)
         return st
 
+    def _hypothesis_rows(self, i32, f32, R):
+        """The per-row state of ``fira_greedy_advance`` / ``fira_sample_advance`` over R rows."""
+        return dict(out=i32(R, self.cfg.tar_len), length=i32(R), prob=f32(R), alive=i32(R), tok=i32(R),
+                    n_alive=i32(self.cfg.tar_len), best_id=i32(R), best_p=f32(R))
+
+    # ------------------------------------------------------------------ greedy (beam 1): no sort, no dist tensor
     def _greedy_reset(self, st):
         st["out"].zero_()
         st["out"][:, 0] = START
@@ -226,46 +304,31 @@ class Searcher:
                                                _lib.ptr(st["alive"]), _lib.ptr(st["tok"]), _lib.ptr(st["n_alive"])),
                        "fira_greedy_advance")
 
-    def _greedy_start(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None):
-        """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the loop's context."""
-        cfg = self.cfg
-        B, T = db.B, cfg.tar_len
+    def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None) -> _Loop:
+        """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  With
+        active constraints the state (and so its graphs: the scalars are baked into the captured launches) is keyed by their
+        value and also owns the [B, out_len] distribution the constraint kernel edits and the banned ids."""
+        B = db.B
         con = self._active(constraints)                      # raises before anything is launched
-        ws = self._begin(db, 1)
-        st = self._greedy_state(B, con)
-        st["sou"].copy_(db.sou)
-        st["sub"].copy_(db.sub_token)
-        self._greedy_reset(st)
-        bounds = [(lo, min(lo + chunk, T - 1)) for lo in range(0, T - 1, chunk)]
-        if use_graphs and st["graphs"] is None:
-            # warm-up outside capture (lazy initialisation inside the library / torch), then capture every chunk
-            self._greedy_steps(st, ws, B, 0, 1)
-            torch.cuda.synchronize()
-            graphs = []
-            for lo, hi in bounds:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._greedy_steps(st, ws, B, lo, hi)
-                graphs.append(g)
-            st["graphs"] = graphs
-            self._greedy_reset(st)
-        return dict(st=st, ws=ws, B=B, bounds=bounds, i=0, use_graphs=use_graphs)
 
-    def _greedy_launch(self, ctx):
-        """Enqueue the next chunk of steps (one hipGraph replay) on the current stream."""
-        lo, hi = ctx["bounds"][ctx["i"]]
-        if ctx["use_graphs"]:
-            ctx["st"]["graphs"][ctx["i"]].replay()
-        else:
-            self._greedy_steps(ctx["st"], ctx["ws"], ctx["B"], lo, hi)
+        def make(i32, f32):
+            st = dict(self._hypothesis_rows(i32, f32, B), con=con)
+            if con is not None:
+                st.update(dist=f32(B, self.cfg.out_len), banned=self._banned_buffer(con))
+            return st
+        loop = _Loop(self, db, 1, ("greedy", B) if con is None else ("greedy", B, con), make, chunk, use_graphs)
+        st, ws = loop.st, loop.ws
+        return loop.start(lambda lo, hi: self._greedy_steps(st, ws, B, lo, hi), lambda: self._greedy_reset(st),
+                          lambda hi: self._none_alive(st, hi))
 
-    def _greedy_done(self, ctx) -> bool:
-        """After the chunk launched last: read the alive counter back (synchronises with the chunk) and advance."""
-        lo, hi = ctx["bounds"][ctx["i"]]
-        ctx["i"] += 1
-        if ctx["i"] >= len(ctx["bounds"]):
-            return True
-        return int(ctx["st"]["n_alive"][hi - 1].item()) == 0      # every hypothesis has emitted <eos> (run_model.py:276-279)
+    @staticmethod
+    def _none_alive(st, hi) -> bool:
+        """Stop test of greedy and sample: every hypothesis has emitted <eos> by step hi - 1 (run_model.py:276-279)."""
+        return int(st["n_alive"][hi - 1].item()) == 0
+
+    @staticmethod
+    def _greedy_result(st):
+        return st["out"].long(), st["length"].long(), st["prob"].clone()
 
     @torch.no_grad()
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None):
@@ -276,13 +339,7 @@ class Searcher:
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
-        ctx = self._greedy_start(db, chunk, use_graphs, constraints)
-        while True:
-            self._greedy_launch(ctx)
-            if self._greedy_done(ctx):
-                break
-        st = ctx["st"]
-        return st["out"].long(), st["length"].long(), st["prob"].clone()
+        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints).run())
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None):
@@ -307,7 +364,7 @@ class Searcher:
                             streams[k]) for k in range(n_lane)]
         main = torch.cuda.current_stream()
         results = [None] * len(dbs)
-        active = [None] * n_lane                                # per lane: (batch index, loop context)
+        active = [None] * n_lane                                # per lane: (batch index, loop)
         nxt = 0
         for lane, stream in self._lanes[:n_lane]:
             stream.wait_stream(main)
@@ -317,19 +374,18 @@ class Searcher:
                 lane, stream = self._lanes[k]
                 with torch.cuda.stream(stream):
                     if active[k] is not None:
-                        j, ctx = active[k]
-                        if lane._greedy_done(ctx):              # (synchronises with this lane's last chunk only)
-                            st = ctx["st"]
-                            results[j] = (st["out"].long(), st["length"].long(), st["prob"].clone())
+                        j, loop = active[k]
+                        if loop.done():                         # (synchronises with this lane's last chunk only)
+                            results[j] = self._greedy_result(loop.st)
                             for r_ in results[j]:
                                 r_.record_stream(main)          # allocated on the lane's stream, consumed on the caller's
                             active[k] = None
                         else:
-                            lane._greedy_launch(ctx)
+                            loop.launch()
                     if active[k] is None and nxt < len(dbs):
-                        ctx = lane._greedy_start(dbs[nxt], chunk, True, constraints)
-                        lane._greedy_launch(ctx)
-                        active[k] = (nxt, ctx)
+                        loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints)
+                        loop.launch()
+                        active[k] = (nxt, loop)
                         nxt += 1
                 busy = busy or active[k] is not None
             if not busy:
@@ -339,22 +395,6 @@ class Searcher:
         return results
 
     # ------------------------------------------------------------------ sampling: temperature / top-k / top-p, n per commit
-    def _sample_state(self, B, n, temperature, top_k, top_p):
-        """Static device buffers + captured hipGraphs of the sampling loop; the filters are fixed in the captured launches,
-        so they are part of the key.  The seed is a device scalar read at run time: one capture serves every seed."""
-        key = ("sample", B, n, float(temperature), int(top_k), float(top_p))
-        if key in self._ws:
-            return self._ws[key]
-        cfg, dev = self.cfg, self.model.device_
-        R, T = B * n, cfg.tar_len
-        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        st = dict(sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), key=i32(B),
-                  seed=torch.zeros(1, dtype=torch.int64, device=dev), out=i32(R, T), length=i32(R), prob=f32(R), logp=f32(R),
-                  alive=i32(R), tok=i32(R), n_alive=i32(T), best_id=i32(R), best_p=f32(R), graphs=None)
-        self._ws[key] = st
-        return st
-
     def _sample_reset(self, st):
         self._greedy_reset(st)
         st["logp"].zero_()
@@ -385,40 +425,23 @@ class Searcher:
         Filters in the order of HF ``generate``: temperature, then top-k (``0`` = off), then top-p (``1`` = off); the draw is a
         Gumbel-max over the kept entries with counter-hash noise of (``seed``, ``keys[b]``, sample, step, entry), so a commit's
         samples depend on its key (default: its row in the batch), not on the batch it lands in.  The step loop is captured
-        into hipGraphs per (B, n, temperature, top_k, top_p) like ``greedy``, with the same early stop between chunks."""
-        cfg = self.cfg
-        B, T = db.B, cfg.tar_len
-        ws = self._begin(db, n)
-        st = self._sample_state(B, n, temperature, top_k, top_p)
-        st["sou"].copy_(db.sou)
-        st["sub"].copy_(db.sub_token)
+        into hipGraphs by the loop driver of ``greedy`` (``_Loop``), with the same early stop between chunks.  The filters are
+        fixed in the captured launches, so they are part of the state's key; the seed is a device scalar read at run time: one
+        capture serves every seed."""
+        B, T = db.B, self.cfg.tar_len
+        R = B * n
         keys = torch.arange(B) if keys is None else torch.as_tensor(keys)
-        if keys.numel() != B:
+        if keys.numel() != B:                                 # raises before anything is launched
             raise ValueError("keys: %d values for a batch of %d commits" % (keys.numel(), B))
+        make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), key=i32(B),
+                                     seed=torch.zeros(1, dtype=torch.int64, device=self.model.device_))
+        loop = _Loop(self, db, n, ("sample", B, n, float(temperature), int(top_k), float(top_p)), make, chunk, use_graphs)
+        st, ws = loop.st, loop.ws
         st["key"].copy_(keys.reshape(B).to(torch.int32))
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)     # the uint64 bits in an int64 tensor
-        self._sample_reset(st)
-        bounds = [(lo, min(lo + chunk, T - 1)) for lo in range(0, T - 1, chunk)]
-        run = lambda lo, hi: self._sample_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p)
-        if use_graphs and st["graphs"] is None:
-            run(0, 1)                                          # warm-up outside capture
-            torch.cuda.synchronize()
-            graphs = []
-            for lo, hi in bounds:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    run(lo, hi)
-                graphs.append(g)
-            st["graphs"] = graphs
-            self._sample_reset(st)
-        for i, (lo, hi) in enumerate(bounds):
-            if use_graphs:
-                st["graphs"][i].replay()
-            else:
-                run(lo, hi)
-            if hi < T - 1 and int(st["n_alive"][hi - 1].item()) == 0:     # every sample has emitted <eos>
-                break
+        loop.start(lambda lo, hi: self._sample_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p),
+                   lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
                 st["logp"].view(B, n).clone())
 
@@ -476,23 +499,6 @@ class Searcher:
     # ------------------------------------------------------------------ scoring given messages (teacher-forced)
     SCORE_TOKEN_KEYS = ("p_word", "p_entry", "entry", "copy_share", "top_id", "p_label")
     RANK_KEYS = ("logp_entry", "logp_word", "mean_logp_word")
-
-    def _score_state(self, B, n, labelled):
-        """Static device buffers + captured hipGraphs of the scoring loop.  Candidates, labels and per-token outputs are
-        step-major ([T, B * n]), so step t's inputs and outputs are plain rows of them."""
-        key = ("score", B, n, bool(labelled))
-        if key in self._ws:
-            return self._ws[key]
-        cfg, dev = self.cfg, self.model.device_
-        R, T = B * n, cfg.tar_len
-        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        st = dict(sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), cand=i32(T, R), label=i32(T, R),
-                  p_word=f32(T - 1, R), p_entry=f32(T - 1, R), entry=i32(T - 1, R), copy_share=f32(T - 1, R),
-                  p_label=f32(T - 1, R), top_id=i32(T - 1, R), logp_word=f32(R), logp_entry=f32(R), logp_label=f32(R),
-                  labelled=bool(labelled), graphs=None)
-        self._ws[key] = st
-        return st
 
     def _score_reset(self, st):
         for k in ("p_word", "p_entry", "copy_share", "p_label", "logp_word", "logp_entry", "logp_label"):
@@ -576,43 +582,27 @@ class Searcher:
         word's probability over every entry that resolves to it), ``p_entry`` / ``entry`` (its largest single entry),
         ``copy_share``, ``top_id`` (the model's arg-max entry, -1 where nothing is scored) and ``p_label``; per candidate
         [B, n] ``logp_word``, ``logp_entry``, ``logp_label`` (float64 sums of log max(p, 1e-10)) and ``length`` (ids including
-        <start>; ``length - 1`` tokens are scored).  The step loop is captured into hipGraphs per (B, n) like ``greedy``;
-        how many chunks to replay follows from the longest candidate, so nothing is read back between chunks.
+        <start>; ``length - 1`` tokens are scored).  The step loop is captured into hipGraphs per (B, n, labels given) by the
+        loop driver of ``greedy`` (``_Loop``); how many chunks to replay follows from the longest candidate, so nothing is read
+        back between chunks.  Candidates, labels and per-token outputs are step-major in the state ([T, B * n]), so step t's
+        inputs and outputs are plain rows of them.
         ``dist`` (tests): a [tar_len - 1, B * n, out_len] tensor that receives every step's distribution (eager only)."""
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
         cand, length, labels = self.check_candidates(cand, lengths, labels, B)        # raises before anything is launched
         n = cand.shape[1]
         R = B * n
-        ws = self._begin(db, n)
-        st = self._score_state(B, n, labels is not None)
-        st["sou"].copy_(db.sou)
-        st["sub"].copy_(db.sub_token)
+        make = lambda i32, f32: dict(cand=i32(T, R), label=i32(T, R), p_word=f32(T - 1, R), p_entry=f32(T - 1, R),
+                                     entry=i32(T - 1, R), copy_share=f32(T - 1, R), p_label=f32(T - 1, R), top_id=i32(T - 1, R),
+                                     logp_word=f32(R), logp_entry=f32(R), logp_label=f32(R), labelled=labels is not None)
+        loop = _Loop(self, db, n, ("score", B, n, labels is not None), make, chunk, use_graphs and dist is None)
+        st, ws = loop.st, loop.ws
         st["cand"].copy_(cand.reshape(R, T).t())
         if labels is not None:
             st["label"].copy_(labels.reshape(R, T).t())
-        self._score_reset(st)
-        n_steps = max(int(length.max()) - 1, 0)               # step t scores position t + 1 <= length - 1
-        bounds = [(lo, min(lo + chunk, T - 1)) for lo in range(0, T - 1, chunk)]
-        use_graphs = use_graphs and dist is None
-        if use_graphs and st["graphs"] is None:
-            self._score_steps(st, ws, B, n, 0, 1)              # warm-up outside capture
-            torch.cuda.synchronize()
-            graphs = []
-            for lo, hi in bounds:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._score_steps(st, ws, B, n, lo, hi)
-                graphs.append(g)
-            st["graphs"] = graphs
-            self._score_reset(st)
-        for i, (lo, hi) in enumerate(bounds):
-            if lo >= n_steps:
-                break
-            if use_graphs:
-                st["graphs"][i].replay()
-            else:
-                self._score_steps(st, ws, B, n, lo, min(hi, n_steps), dist)
+        # step t scores position t + 1 <= length - 1: the loop needs max(length) - 1 steps and no stop test
+        loop.start(lambda lo, hi: self._score_steps(st, ws, B, n, lo, hi, dist), lambda: self._score_reset(st),
+                   n_steps=max(int(length.max()) - 1, 0)).run()
         res = Scores()
         scored = (st["cand"][1:] != PAD).t().reshape(B, n, T - 1)
         for k in self.SCORE_TOKEN_KEYS:
@@ -641,23 +631,6 @@ class Searcher:
         return torch.argmax(rank_values(scores, by), dim=1).tolist()
 
     # ------------------------------------------------------------------ beam search with the reference's semantics
-    def _beam_state(self, B, beam, con: Optional[Constraints] = None):
-        key = ("beam", B, beam) if con is None else ("beam", B, beam, con)      # (a captured graph bakes the constraint scalars)
-        if key in self._ws:
-            return self._ws[key]
-        cfg, dev = self.cfg, self.model.device_
-        BR, T = B * beam, cfg.tar_len
-        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-        st = dict(gen=[i32(BR, T), i32(BR, T)], length=[i32(BR), i32(BR)],
-                  prob=[torch.zeros(BR, dtype=torch.float32, device=dev) for _ in range(2)],
-                  tok=i32(BR), parent=i32(BR), fin=i32(BR), active=i32(9), done=i32(1),
-                  dist=torch.empty((BR, cfg.out_len), dtype=torch.float32, device=dev),
-                  sou=i32(B, cfg.sou_len), sub=i32(B, cfg.sub_token_len), graphs=None, con=con)
-        if con is not None:
-            st["banned"] = self._banned_buffer(con)
-        self._ws[key] = st
-        return st
-
     def _beam_reset(self, st, B, beam):
         for k in ("gen", "length", "prob"):
             st[k][0].zero_()
@@ -696,36 +669,22 @@ class Searcher:
         Per step: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library calls, no torch
         op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam) shape, and
         the ``done`` latch is read back between chunks (run_model.py:276-279)."""
-        cfg = self.cfg
-        B, T = db.B, cfg.tar_len
+        B, T = db.B, self.cfg.tar_len
+        BR = B * beam
         con = self._active(constraints)                      # raises before anything is launched
-        ws = self._begin(db, beam)
-        st = self._beam_state(B, beam, con)
-        st["sou"].copy_(db.sou)
-        st["sub"].copy_(db.sub_token)
-        self._beam_reset(st, B, beam)
-        bounds = [(lo, min(lo + chunk, T - 1)) for lo in range(0, T - 1, chunk)]
-        if use_graphs and st["graphs"] is None:
-            self._beam_steps(st, ws, B, beam, 0, 1)            # warm-up outside capture
-            torch.cuda.synchronize()
-            graphs = []
-            for lo, hi in bounds:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._beam_steps(st, ws, B, beam, lo, hi)
-                graphs.append(g)
-            st["graphs"] = graphs
-            self._beam_reset(st, B, beam)
-        last = 0
-        for i, (lo, hi) in enumerate(bounds):
-            if use_graphs:
-                st["graphs"][i].replay()
-            else:
-                self._beam_steps(st, ws, B, beam, lo, hi)
-            last = hi
-            if hi < T - 1 and bool(st["done"].item()):
-                break
-        cur = last & 1
+
+        def make(i32, f32):
+            st = dict(gen=[i32(BR, T), i32(BR, T)], length=[i32(BR), i32(BR)], prob=[f32(BR), f32(BR)], tok=i32(BR),
+                      parent=i32(BR), fin=i32(BR), active=i32(9), done=i32(1), dist=f32(BR, self.cfg.out_len), con=con)
+            if con is not None:
+                st["banned"] = self._banned_buffer(con)
+            return st
+        # (a captured graph bakes the constraint scalars: they are part of the key)
+        loop = _Loop(self, db, beam, ("beam", B, beam) if con is None else ("beam", B, beam, con), make, chunk, use_graphs)
+        st, ws = loop.st, loop.ws
+        loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
+                   lambda hi: bool(st["done"].item())).run()
+        cur = loop.hi & 1                                    # the ping-pong buffer the last step run wrote
         return (st["gen"][cur].view(B, beam, T).long(), st["length"][cur].view(B, beam).long(),
                 st["prob"][cur].view(B, beam).clone())
 
