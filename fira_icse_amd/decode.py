@@ -256,6 +256,18 @@ class Searcher:
                                                   c.min_length, _lib.ptr(st["banned"]), len(c.banned), _lib.ptr(st["dist"]),
                                                   _lib.ptr(best_id), _lib.ptr(best_p)), "fira_constrain_dist")
 
+    def _merge(self, st, R, rows_per_commit, best_id, best_p):
+        """fira_merge_dist on st["dist"]: every copy entry folded into the generator entry of its word."""
+        _lib.check(_lib.lib().fira_merge_dist(_lib.cur_stream(), C.byref(self.model.dims), R, rows_per_commit, _lib.ptr(st["sou"]),
+                                              _lib.ptr(st["sub"]), _lib.ptr(st["dist"]), _lib.ptr(best_id), _lib.ptr(best_p)),
+                   "fira_merge_dist")
+
+    @staticmethod
+    def _key(base, merge: bool, con):
+        """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
+        so merged and unmerged searches own separate buffers and graphs."""
+        return base + (("merge",) if merge else ()) + ((con,) if con is not None else ())
+
     def _banned_buffer(self, c: Constraints):
         return torch.tensor(list(c.banned) or [0], dtype=torch.int32, device=self.model.device_)
 
@@ -293,30 +305,41 @@ class Searcher:
         arg-max of the output distribution, then the hypothesis bookkeeping), no torch op, no host round trip."""
         lib, s = _lib.lib(), _lib.cur_stream()
         for step in range(lo, hi):
-            if st["con"] is None:
+            con, merge = st["con"], st.get("merge", False)
+            if con is None and not merge:
                 self._step(ws, B, 1, step, st["tok"], None, None, st["best_id"], st["best_p"])
-            else:       # the step writes the distribution, the constraint kernel edits it and takes the arg-max of what is left
+            else:       # the step writes the distribution; the last kernel that edits it takes the arg-max of what is left
                 self._step(ws, B, 1, step, st["tok"], None, st["dist"], None, None)
-                self._constrain(st, B, 1, st["out"], st["length"], st["best_id"], st["best_p"])
+                if merge:                                    # words first: a blocked word's mass then sits on its generator entry
+                    self._merge(st, B, 1, *((st["best_id"], st["best_p"]) if con is None else (None, None)))
+                if con is not None:
+                    self._constrain(st, B, 1, st["out"], st["length"], st["best_id"], st["best_p"])
             _lib.check(lib.fira_greedy_advance(s, C.byref(self.model.dims), B, step, _lib.ptr(st["best_id"]),
                                                _lib.ptr(st["best_p"]), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]),
                                                _lib.ptr(st["out"]), _lib.ptr(st["length"]), _lib.ptr(st["prob"]),
                                                _lib.ptr(st["alive"]), _lib.ptr(st["tok"]), _lib.ptr(st["n_alive"])),
                        "fira_greedy_advance")
 
-    def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None) -> _Loop:
+    def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
+                     merge_copies: bool = False) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  With
         active constraints the state (and so its graphs: the scalars are baked into the captured launches) is keyed by their
-        value and also owns the [B, out_len] distribution the constraint kernel edits and the banned ids."""
+        value and also owns the [B, out_len] distribution the constraint kernel edits and the banned ids.  ``merge_copies``
+        is part of the key too (("greedy", B, "merge"), ("greedy", B, "merge", constraints)) and brings the distribution."""
         B = db.B
         con = self._active(constraints)                      # raises before anything is launched
+        merge = bool(merge_copies)
 
         def make(i32, f32):
             st = dict(self._hypothesis_rows(i32, f32, B), con=con)
+            if merge:
+                st["merge"] = True
+            if con is not None or merge:
+                st["dist"] = f32(B, self.cfg.out_len)
             if con is not None:
-                st.update(dist=f32(B, self.cfg.out_len), banned=self._banned_buffer(con))
+                st["banned"] = self._banned_buffer(con)
             return st
-        loop = _Loop(self, db, 1, ("greedy", B) if con is None else ("greedy", B, con), make, chunk, use_graphs)
+        loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
         return loop.start(lambda lo, hi: self._greedy_steps(st, ws, B, lo, hi), lambda: self._greedy_reset(st),
                           lambda hi: self._none_alive(st, hi))
@@ -331,18 +354,27 @@ class Searcher:
         return st["out"].long(), st["length"].long(), st["prob"].clone()
 
     @torch.no_grad()
-    def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None):
+    def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
+               merge_copies: bool = False):
         """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``: a ``Constraints``
         value; the step then writes its distribution, ``fira_constrain_dist`` zeroes the blocked words' entries and takes the
         arg-max of the rest (probability = the product of the UNnormalised entries taken); None or inactive: today's loop.
 
+        ``merge_copies``: search over WORDS instead of entries.  The step writes its distribution and ``fira_merge_dist`` folds
+        every copy entry into the generator entry of the word it resolves to, so the arg-max is the most probable word, not the
+        largest single entry (with constraints: step, merge, then the constraint kernel, which reports the arg-max).  The
+        returned probability is then the probability of the WORD SEQUENCE: the sum over every entry path that spells it --
+        exact, because the next step depends on the resolved ids only -- and no longer the product of the entries taken.
+        False: today's loop, keys, buffers and graphs.
+
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
-        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints).run())
+        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies).run())
 
     @torch.no_grad()
-    def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None):
+    def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
+                    merge_copies: bool = False):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -353,7 +385,8 @@ class Searcher:
         BELOW one lane (x0.8) once the process had created more streams (a trainer's) -- two lanes on one queue run one after
         the other.  On 8 queues (run_model.py / bench.py / this package set GPU_MAX_HW_QUEUES=8 before HIP initialises) three
         lanes give x2.06 and four x2.35 in a process that trained first; six collapse again (profiles/r6_probes.md).
-        Same arithmetic, same ids as ``greedy`` batch by batch, ``constraints`` included."""
+        Same arithmetic, same ids as ``greedy`` batch by batch, ``constraints`` and ``merge_copies`` included (with
+        ``merge_copies`` the probability is that of the word sequence, summed over every entry path that spells it)."""
         dbs = list(dbs)
         self._active(constraints)                            # raises before a lane starts
         n_lane = max(1, min(in_flight, len(dbs)))
@@ -383,7 +416,7 @@ class Searcher:
                         else:
                             loop.launch()
                     if active[k] is None and nxt < len(dbs):
-                        loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints)
+                        loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies)
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -641,8 +674,8 @@ class Searcher:
         st["done"].zero_()
 
     def _beam_steps(self, st, ws, B, beam, lo, hi):
-        """Steps lo..hi-1 of run_model.py:225-340: prepare -> KV-cached decoder step -> (constraints, when the state has them)
-        -> select, all on the device."""
+        """Steps lo..hi-1 of run_model.py:225-340: prepare -> KV-cached decoder step -> (merge, then constraints, when the state
+        has them) -> select, all on the device."""
         lib, s, T = _lib.lib(), _lib.cur_stream(), self.cfg.tar_len
         for step in range(lo, hi):
             cur, nxt = step & 1, (step + 1) & 1
@@ -650,6 +683,8 @@ class Searcher:
                                              _lib.ptr(st["tok"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]),
                                              _lib.ptr(st["done"])), "fira_beam_prepare")
             self._step(ws, B, beam, step, st["tok"], st["parent"] if step > 0 else None, st["dist"], None, None)
+            if st.get("merge", False):
+                self._merge(st, B * beam, beam, None, None)
             if st["con"] is not None:
                 self._constrain(st, B * beam, beam, st["gen"][cur], st["length"][cur], None, None)
             _lib.check(lib.fira_beam_select(s, C.byref(self.model.dims), B, beam, _lib.ptr(st["dist"]),
@@ -661,10 +696,17 @@ class Searcher:
 
     @torch.no_grad()
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
-             constraints: Optional[Constraints] = None):
+             constraints: Optional[Constraints] = None, merge_copies: bool = False):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``: a ``Constraints``
         value; one ``fira_constrain_dist`` call per step then zeroes the blocked words' entries of every row between the step
         and the selection (nothing is renormalised); None or inactive: today's three calls per step and today's graphs.
+
+        ``merge_copies``: search over WORDS instead of entries.  One ``fira_merge_dist`` call per step, between the step and
+        the constraints / the selection, folds every copy entry into the generator entry of the word it resolves to: a word is
+        one candidate however many entries carry it, so the slots of positive probability hold pairwise distinct word
+        sequences.  The returned probability is then the probability of the WORD SEQUENCE: the sum over every entry path that
+        spells it -- exact, because the next step depends on the resolved ids only -- and no longer the product of the entries
+        taken.  The state is keyed ("beam", B, beam, "merge"[, constraints]); False: today's calls, keys, buffers and graphs.
 
         Per step: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library calls, no torch
         op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam) shape, and
@@ -672,15 +714,18 @@ class Searcher:
         B, T = db.B, self.cfg.tar_len
         BR = B * beam
         con = self._active(constraints)                      # raises before anything is launched
+        merge = bool(merge_copies)
 
         def make(i32, f32):
             st = dict(gen=[i32(BR, T), i32(BR, T)], length=[i32(BR), i32(BR)], prob=[f32(BR), f32(BR)], tok=i32(BR),
                       parent=i32(BR), fin=i32(BR), active=i32(9), done=i32(1), dist=f32(BR, self.cfg.out_len), con=con)
+            if merge:
+                st["merge"] = True
             if con is not None:
                 st["banned"] = self._banned_buffer(con)
             return st
-        # (a captured graph bakes the constraint scalars: they are part of the key)
-        loop = _Loop(self, db, beam, ("beam", B, beam) if con is None else ("beam", B, beam, con), make, chunk, use_graphs)
+        # (a captured graph bakes the constraint scalars and the merge launch: they are part of the key)
+        loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()

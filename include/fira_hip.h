@@ -752,6 +752,33 @@ int fira_constrain_dist(void* stream, const fira_dims* d, int R, int rows_per_co
                         float* dist /* [R, vocab + sou_len + sub_len], in place */,
                         int32_t* best_id, float* best_p /* both NULL or both given */);
 
+/* Search over words (csrc/merge.hip; additive, the ABI version is unchanged): folds the copy entries of the step's distribution
+ * into the generator entry of their word, in place, between fira_decode_step and the selection (fira_constrain_dist, if any, then
+ * fira_beam_select / fira_greedy_advance).  W = vocab + sou_len + sub_len; row r belongs to commit b = r / rows_per_commit
+ * (n_beam for a beam search, 1 for greedy); slot s in [0, sou_len + sub_len) has the source id w_s = sou[b, s] below sou_len,
+ * sub_token[b, s - sou_len] above -- the id the selection kernels resolve entry vocab + s to.  Two entries with one id are one
+ * continuation (only the id reaches the hypothesis and the next step), so for every id w in [0, vocab) that is the source of at
+ * least one slot, with its slots s_1 < s_2 < ... < s_k in ascending slot index:
+ *     acc        = ((p[vocab + s_1] + p[vocab + s_2]) + ...) + p[vocab + s_k]
+ *     dist[r, w] = acc + dist[r, w]                      (the generator entry is added last, as fira_decode_step_score's p_word)
+ *     dist[r, vocab + s_j] = 0.0f                        for j = 1 .. k
+ * in plain fp32 additions in exactly this order: no float atomics, no tree reduction, so every run and every graph replay gives
+ * the same bits (a loop of np.float32 additions is the reference).  Every other element keeps its bits: generator entries that
+ * no slot carries, and slots whose id is outside [0, vocab) -- such an id is never used as an index.  Nothing is renormalised;
+ * the row's mass is conserved up to the rounding of the additions.  A masked or padded slot holds exactly 0.0f and may carry
+ * id 0 or a stale id: it takes part like any other slot and changes nothing, since x + 0.0f == x for x >= 0.
+ * best_id / best_p (both NULL, or both [R]): the arg-max of the row AS STORED and its value, under (value descending, index
+ * ascending) -- the order of fira_constrain_dist; NaN never wins.  After the edit the winner is a generator index whenever a
+ * word has positive mass.  Without best_id the generator part of the row is not streamed: only the slots, and the generator
+ * entries they fold into, are touched.  A finished or ended row is not special-cased (fira_beam_select and fira_greedy_advance
+ * ignore such rows).  vocab in 4 .. 25 600, sou_len + sub_len <= 1 024, rows_per_commit >= 1 divides R; R == 0 is a no-op.
+ * Any row width and pitch alignment; vector stores only, no atomics on global memory.                                    */
+int fira_merge_dist(void* stream, const fira_dims* d, int R, int rows_per_commit,
+                    const int32_t* sou /* [R / rows_per_commit, sou_len] */,
+                    const int32_t* sub_token /* [R / rows_per_commit, sub_len] */,
+                    float* dist /* [R, vocab + sou_len + sub_len], in place */,
+                    int32_t* best_id, float* best_p /* both NULL or both given */);
+
 /* On-device sampling of candidate messages (temperature, top-k, top-p).  Workspace: fira_decode_begin_ex /
  * fira_decode_workspace_bytes_ex with n_beam = n_sample (1..8) and the same flags (FIRA_DECODE_KV_BF16 allowed).
  *   fira_decode_step_sample : fira_decode_step_ex for the B * n_sample rows (row r = commit r / n_sample, sample

@@ -107,6 +107,13 @@ def parse_args(argv):
                     "M words (at most tar_len - 2)")
     ap.add_argument("--ban-words", default=None, metavar="W[,W...]", help="test: up to 32 vocabulary words the search never "
                     "emits, generator or copied (<unkm> may be given by name; <pad>, <eos> and <start> may not)")
+    ap.add_argument("--merge-copies", action="store_true", help="test: the search (any --beam) ranks WORDS, not entries: the "
+                    "copy entries of a step's distribution are folded into the generator entry of the word they resolve to, so "
+                    "a word counts once with its whole probability and the beam holds distinct messages; combines with "
+                    "--no-repeat-ngram, --min-length and --ban-words")
+    ap.add_argument("--nbest", action="store_true", help="test, beam above 1: also write OUTPUT/output_fira_nbest, one JSON "
+                    "line per commit with the beam's messages and their probabilities, best first (OUTPUT/output_fira is "
+                    "unchanged: its line is the first message); without --merge-copies the list may repeat a message")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
@@ -128,6 +135,7 @@ def parse_args(argv):
         check_lr_schedule_args(a)
         check_score_args(a)
         check_constraint_args(a)
+        check_merge_args(a)
         check_sample_args(a)
     except ValueError as e:
         ap.error(str(e))
@@ -280,6 +288,31 @@ def constraints_from_args(a, vocab, cfg=None):
         ids.append(int(vocab[w]))
     c = Constraints(no_repeat_ngram=a.no_repeat_ngram or 0, min_length=a.min_length or 0, banned=tuple(ids))
     return c.check(cfg) if cfg is not None else c
+
+
+def check_merge_args(a):
+    """Validates --merge-copies / --nbest against the other options (no GPU, no DataSet needed); raises ValueError on a
+    conflict."""
+    merge, nbest = getattr(a, "merge_copies", False), getattr(a, "nbest", False)
+    given = [flag for on, flag in ((merge, "--merge-copies"), (nbest, "--nbest")) if on]
+    if not given:
+        return a
+    if a.stage != "test":
+        raise ValueError("%s only apply to the test stage" % ", ".join(given))
+    if a.sample is not None:
+        raise ValueError("%s belong to a search: they do not combine with --sample" % ", ".join(given))
+    if a.score is not None:
+        raise ValueError("%s belong to a search: they do not combine with --score" % ", ".join(given))
+    if nbest and a.beam is not None and a.beam <= 1:
+        raise ValueError("--nbest lists the hypotheses of a beam: it does not combine with --beam %d" % a.beam)
+    return a
+
+
+def nbest_record(messages, probs):
+    """One line of OUTPUT/output_fira_nbest: the beam's messages of positive probability (the -1 padding and zero-probability
+    candidates are left out), ordered by probability descending, then slot ascending."""
+    order = sorted((j for j in range(len(probs)) if probs[j] > 0), key=lambda j: (-probs[j], j))
+    return json.dumps({"messages": [messages[j] for j in order], "prob": [probs[j] for j in order]})
 
 
 SAMPLE_OPTIONS = (("temperature", "--temperature", 1.0), ("top_k", "--top-k", 0), ("top_p", "--top-p", 1.0),
@@ -495,7 +528,8 @@ class Run:
             return self.test_sample(search, store, mine)
         if self.a.score is not None:
             return self.test_score(search, store, mine, given)
-        lines, n_tok, t0 = [], 0, time.time()
+        merge, want_nbest = bool(getattr(self.a, "merge_copies", False)), bool(getattr(self.a, "nbest", False))
+        lines, nbest, n_tok, t0 = [], [], 0, time.time()
         # greedy: groups of `in_flight` batches share the GPU (independent launch chains: decode.Searcher.greedy_many; four lanes
         # on eight hardware queues: 0.14 ms per batch-step against 0.33 one at a time); the output order stays
         # all_index['test'] order (run_model.py:372)
@@ -505,9 +539,17 @@ class Run:
             idxs = [mine[lo:lo + cfg.test_batch_size] for lo in starts[g0:g0 + group]]
             dbs = [self.device_batch(store, idx) for idx in idxs]
             if cfg.beam_size == 1:
-                outs = [search.best(*r) for r in search.greedy_many(dbs, in_flight=group, constraints=constraints)]
+                outs = [search.best(*r) for r in search.greedy_many(dbs, in_flight=group, constraints=constraints,
+                                                                    merge_copies=merge)]
             else:
-                outs = [search.best(*search.beam(dbs[0], cfg.beam_size, constraints=constraints))]
+                gen, length, prob = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge)
+                outs = [search.best(gen, length, prob)]
+                if want_nbest:                               # the whole beam of every commit, best first
+                    gen, length, prob = gen.tolist(), length.tolist(), prob.tolist()
+                    for k, i in enumerate(idxs[0]):
+                        msgs = [text.detokenize(g[:n], self.r_vocab, self.var_maps[test_index[i]])
+                                for g, n in zip(gen[k], length[k])]
+                        nbest.append(nbest_record(msgs, prob[k]))
             for idx, hyps in zip(idxs, outs):
                 for h, i in zip(hyps, idx):
                     lines.append(text.detokenize(h, self.r_vocab, self.var_maps[test_index[i]]))
@@ -516,9 +558,14 @@ class Run:
                 done = min(len(mine), starts[min(g0 + group, len(starts)) - 1] + cfg.test_batch_size)
                 print("data: %d/%d  (%.1f tokens/s)" % (done, len(mine), n_tok / max(time.time() - t0, 1e-9)), flush=True)
         lines = gather_lines(lines)
+        if want_nbest:
+            nbest = gather_lines(nbest)
         if self.rank == 0:
             with open(self.out("output_fira"), "w") as f:
                 f.write("".join(l + "\n" for l in lines))
+            if want_nbest:
+                with open(self.out("output_fira_nbest"), "w") as f:
+                    f.write("".join(l + "\n" for l in nbest))
         return lines
 
     def test_sample(self, search, store, mine):

@@ -1,0 +1,352 @@
+"""Search over words on the device: fira_merge_dist alone on synthetic rows against the numpy statement (merge_ref.py), then
+``Searcher.beam`` / ``greedy`` / ``greedy_many`` with ``merge_copies`` against the torch / host loops of the same file, alone and
+composed with ``Constraints``, the distinctness of the merged beam, the cross-check against ``Searcher.score``'s ``p_word``, the
+flag-off paths, the state keys, and the command line with ``--merge-copies`` / ``--nbest``."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import util
+import merge_ref as M
+from fira_icse_amd import _lib, data, synth
+from fira_icse_amd.config import EOS, PAD, START, UNK, FiraConfig
+from fira_icse_amd.decode import Constraints
+
+pytestmark = pytest.mark.gpu
+
+# ------------------------------------------------------------------------------------------------ the kernel alone
+ALPHABET = (UNK, 5, 6, 9)                        # four words, so slots collide
+FREE = 4                                         # a generator index below 9 that no slot carries
+SMALL = (37, 5, 3)                               # vocab, sou_len, sub_len: W = 45, not a multiple of 4
+GEOMETRIES = [("small-R7", SMALL, 7, 1), ("small-R6x3", SMALL, 6, 3), ("no-sub-R7", (37, 5, 0), 7, 1),
+              ("no-diff-R7", (37, 0, 3), 7, 1), ("full-R4", (37, 600, 424), 4, 1), ("model-R6x3", (24650, 210, 160), 6, 3)]
+SEED = 3
+
+
+def make_case(name, dims, n_rows, rpc, seed=SEED):
+    """Synthetic rows.  Source ids over ALPHABET plus the out-of-range ids V and -1; probabilities uniform in (1e-6, 1) with a
+    handful of exact 0.0f slots.  Forced into the sources, so no property rests on the draw: three slots of word 9, a slot with
+    id V, and a word-5 slot beside two word-6 slots (with 8 slots or more all of them in every commit, else by commit % 3).  Two
+    traps in the rows:
+      tie    (even rows of a commit with word-9 slots) word 9's generator entry is made large and the untouched generator entry
+             FREE = 4 is set to the bits of word 9's merged sum: an exact tie that the lower index must win;
+      flip   (odd rows of a commit with the 5 / 6 / 6 slots) the word-5 slot holds X, the largest entry of the row, and the two
+             word-6 slots 0.75 X each: the arg-max entry of the unedited row is the word-5 slot, the arg-max of the edited row
+             is word 6 (X = 4 (L + S) + 4 is larger than anything the other slots of a word can add up to)."""
+    V, L, S = dims
+    NS = L + S
+    n_commits = n_rows // rpc
+    rng = np.random.RandomState(seed + 17 * NS + n_rows)
+    ids = rng.choice(ALPHABET + (V, -1), size=(n_commits, NS)).astype(np.int32)
+    nine, flip = [False] * n_commits, [None] * n_commits
+    for c in range(n_commits):
+        if NS >= 8:
+            ids[c, :8] = (9, 9, 9, V, 5, 6, 6, -1)
+            nine[c], flip[c] = True, (4, 5, 6)
+        elif c % 3 == 0:
+            ids[c, :3] = 9
+            nine[c] = True
+        elif c % 3 == 1:
+            ids[c, 0] = V
+            ids[c, 1] = -1
+        else:
+            ids[c, :3] = (5, 6, 6)
+            flip[c] = (0, 1, 2)
+    dist = rng.uniform(1e-6, 1.0, size=(n_rows, V + NS)).astype(np.float32)
+    for r in range(n_rows):
+        for s in rng.choice(NS, size=min(3, NS), replace=False):
+            dist[r, V + s] = np.float32(0.0)
+    case = dict(name=name, dims=dims, R=n_rows, rpc=rpc, sou=np.ascontiguousarray(ids[:, :L]), sub=np.ascontiguousarray(ids[:, L:]),
+                ids=ids, tie_rows=[], flip_rows=[])
+    X = np.float32(4 * NS + 4)
+    for r in range(n_rows):
+        c = r // rpc
+        if r % 2 == 1 and flip[c] is not None:
+            a, b1, b2 = flip[c]
+            dist[r, V + a] = X
+            dist[r, V + b1] = dist[r, V + b2] = np.float32(0.75) * X
+            case["flip_rows"].append(r)
+        elif r % 2 == 0 and nine[c]:
+            dist[r, 9] = np.float32(8 * (NS + 1))
+            dist[r, FREE] = M.merged(dist[r], case["sou"][c], case["sub"][c], dims)[9]
+            case["tie_rows"].append(r)
+    case["dist"] = dist
+    return case
+
+
+def reference(case):
+    out = M.merged_rows(case["dist"], case["sou"], case["sub"], case["dims"], case["rpc"])
+    best = [M.argmax_ref(out[r]) for r in range(case["R"])]
+    return out, np.array([b[0] for b in best], dtype=np.int32), np.array([b[1] for b in best], dtype=np.float32)
+
+
+def device_dims(dims):
+    d = _lib.make_dims(FiraConfig())
+    d.vocab, d.sou_len, d.sub_len = dims
+    return d
+
+
+def run_kernel(dims, rpc, sou, sub, dist, want_best, offset=1):
+    """The entry on a copy of ``dist`` that starts ``offset`` floats into its buffer (rows then begin at every alignment)."""
+    dev = "cuda"
+    n_rows, W = dist.shape
+    buf = torch.zeros(n_rows * W + offset + 8, dtype=torch.float32, device=dev)
+    d_dev = buf[offset:offset + n_rows * W].view(n_rows, W)
+    d_dev.copy_(torch.from_numpy(dist))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) if a.size else torch.zeros(1, dtype=torch.int32, device=dev)
+    sou_d, sub_d = t(sou), t(sub)
+    best_id = torch.full((n_rows,), -7, dtype=torch.int32, device=dev) if want_best else None
+    best_p = torch.full((n_rows,), -7.0, dtype=torch.float32, device=dev) if want_best else None
+    dd = device_dims(dims)
+    _lib.check(_lib.lib().fira_merge_dist(_lib.cur_stream(), C.byref(dd), n_rows, rpc, _lib.ptr(sou_d), _lib.ptr(sub_d),
+                                          _lib.ptr(d_dev), _lib.ptr(best_id), _lib.ptr(best_p)), "fira_merge_dist")
+    torch.cuda.synchronize()
+    assert float(buf[:offset].abs().sum()) == 0 and float(buf[offset + n_rows * W:].abs().sum()) == 0      # nothing outside the rows
+    return d_dev.cpu(), None if best_id is None else best_id.cpu(), None if best_p is None else best_p.cpu()
+
+
+def bits(x):
+    return (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).contiguous().view(torch.int32)
+
+
+def test_inputs_are_not_vacuous():
+    """Decided on the reference alone (no launch): every case has a word with at least 3 slots and a left-alone slot, the full case
+    a word with more than 64 slots, both traps exist in every case, the tie is a tie that the lower index wins, and the flip
+    really moves the arg-max from a slot of the unedited row to a generator entry of the edited one."""
+    for g in GEOMETRIES:
+        case = make_case(*g)
+        V, L, S = case["dims"]
+        counts = [np.bincount(row[(row >= 0) & (row < V)], minlength=V) for row in case["ids"]]
+        assert max(int(c.max()) for c in counts) >= 3, g[0]
+        assert ((case["ids"] < 0) | (case["ids"] >= V)).any(), g[0]
+        assert (case["dist"][:, V:] == 0).any(), g[0]
+        if g[0].startswith("full"):
+            assert L + S == 1024 and max(int(c.max()) for c in counts) > 64
+        out, best_id, best_p = reference(case)
+        assert case["tie_rows"] and case["flip_rows"], g[0]
+        for r in case["tie_rows"]:
+            assert best_id[r] == FREE and out[r, 9].tobytes() == out[r, FREE].tobytes() == best_p[r].tobytes(), (g[0], r)
+            assert case["dist"][r, FREE].tobytes() == out[r, FREE].tobytes()                  # (untouched)
+        for r in case["flip_rows"]:
+            before = int(np.argmax(case["dist"][r]))
+            assert before >= V and case["ids"][r // case["rpc"], before - V] == 5 and best_id[r] == 6, (g[0], r, before, best_id[r])
+
+
+@pytest.mark.parametrize("geometry", GEOMETRIES, ids=[g[0] for g in GEOMETRIES])
+def test_kernel_equals_the_reference_bit_for_bit(geometry):
+    case = make_case(*geometry)
+    out, best_id, best_p = reference(case)
+    for want_best in (True, False):                           # (without best the generator part is never streamed)
+        for offset in (1, 0):
+            got, gid, gp = run_kernel(case["dims"], case["rpc"], case["sou"], case["sub"], case["dist"], want_best, offset)
+            assert torch.equal(bits(got), bits(out)), (case["name"], want_best, offset)
+            if want_best:
+                assert gid.tolist() == best_id.tolist(), (case["name"], offset)
+                assert torch.equal(bits(gp), bits(best_p)), (case["name"], offset)
+
+
+@pytest.mark.parametrize("geometry", [GEOMETRIES[1], GEOMETRIES[5]], ids=[GEOMETRIES[1][0], GEOMETRIES[5][0]])
+def test_ids_all_out_of_range_leave_every_bit_alone(geometry):
+    case = make_case(*geometry)
+    V, L, S = case["dims"]
+    rng = np.random.RandomState(9)
+    ids = rng.choice((V, -1, V + 3, -(1 << 31)), size=case["ids"].shape).astype(np.int32)
+    sou, sub = np.ascontiguousarray(ids[:, :L]), np.ascontiguousarray(ids[:, L:])
+    dist = rng.uniform(1e-6, 1.0, size=case["dist"].shape).astype(np.float32)
+    dist[0, V + 1] = np.float32(2.0)                          # the row's arg-max is a left-alone slot
+    dist[1, 7] = dist[1, V + L + 1] = np.float32(2.0)         # an exact tie between a generator entry and a slot: the lower index
+    got, gid, gp = run_kernel(case["dims"], case["rpc"], sou, sub, dist, True)
+    assert torch.equal(bits(got), bits(dist))
+    assert gid.tolist() == dist.argmax(1).tolist() and gid[0] == V + 1 and gid[1] == 7
+    assert torch.equal(bits(gp), bits(dist.max(1)))
+    got, _, _ = run_kernel(case["dims"], case["rpc"], sou, sub, dist, False)
+    assert torch.equal(bits(got), bits(dist))
+
+
+# ------------------------------------------------------------------------------------------------ through the model
+CON = Constraints(2, 3, (UNK,))
+
+
+@pytest.fixture(scope="module")
+def setup():
+    """The commits of test_constrain_gpu.py (the golden synthetic ones) under ``util.perturb_state_dict`` of the seeded
+    initialisation, seed 1.  Its peaked weights (``peaked_state_dict`` / ``tie_state_dict``, seeds 1..5) put nearly all mass on one
+    generator entry per step: the word search and the entry search then agree on every commit, and the non-vacuity test below
+    would show nothing.  The unsharpened weights spread the mass, a word that occurs at several diff positions outweighs the
+    largest single entry, and the merged greedy message differs from the unmerged one for every commit (seeds 1..5 alike)."""
+    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
+    from fira_icse_amd.decode import Searcher
+    cfg = FiraConfig()
+    raw = util.load_golden_raw()
+    store = data.process_raw(cfg, raw)
+    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
+    ids = idx["test"][:util.GOLDEN_B]
+    torch.manual_seed(0)
+    model = TransModel(cfg, init=False)
+    model.load_state_dict(util.perturb_state_dict(reference_init_state_dict(cfg), seed=1))
+    model.eval()
+    return cfg, model, DeviceBatch(store.batch(ids), cfg), Searcher(model)
+
+
+@pytest.fixture(scope="module")
+def refs(setup):
+    """The reference loops, once per configuration (shared, never modified); None = today's searches on the device."""
+    cfg, model, db, search = setup
+    sou, sub, dims = db.sou.cpu().numpy(), db.sub_token.cpu().numpy(), M.dims_of(cfg)
+    out = {}
+    for c in (None, CON):
+        out["merge", c] = dict(beam=tuple(t.cpu() for t in M.beam_edited(search, db, 3, M.make_edit(sou, sub, dims, 3, c))),
+                               greedy=M.greedy_edited(search, db, M.make_edit(sou, sub, dims, 1, c)))
+    out[None] = dict(beam=tuple(t.cpu().clone() for t in search.beam(db, 3)), greedy=tuple(t.cpu().clone() for t in search.greedy(db)))
+    return out
+
+
+def same_search(got, want):
+    """The rule of test_constrain_gpu.py: lengths and probabilities equal, ids equal inside the lengths."""
+    (gen, length, p), (gen_t, len_t, p_t) = [tuple(t.cpu() for t in x[:3]) for x in (got, want)]
+    assert torch.equal(length, len_t)
+    assert torch.equal(p, p_t)
+    live = torch.arange(gen.shape[-1])[(None,) * (gen.dim() - 1)] < length[..., None]
+    assert torch.equal(gen * live, gen_t * live)
+
+
+def slot_messages(gen, length, prob):
+    """Per commit: the word sequences of the beam slots of positive probability."""
+    gen, length, prob = gen.cpu().tolist(), length.cpu().tolist(), prob.cpu().tolist()
+    return [[tuple(g[1:n]) for g, n, p in zip(gen[k], length[k], prob[k]) if p > 0] for k in range(len(gen))]
+
+
+@pytest.mark.parametrize("c", [None, CON], ids=["merge", "merge-n2-M3-unk"])
+def test_beam_and_greedy_equal_the_reference_loops(setup, refs, c):
+    cfg, model, db, search = setup
+    want = refs["merge", c]
+    for use_graphs in (False, True, True):                    # eager, captured, replayed
+        same_search(search.beam(db, 3, use_graphs=use_graphs, constraints=c, merge_copies=True), want["beam"])
+        same_search(search.greedy(db, use_graphs=use_graphs, constraints=c, merge_copies=True), want["greedy"])
+    many = search.greedy_many([db, db, db], in_flight=3, constraints=c, merge_copies=True)
+    torch.cuda.synchronize()
+    assert len(many) == 3
+    for got in many:
+        same_search(got, want["greedy"])
+        same_search(got, search.greedy(db, constraints=c, merge_copies=True))
+
+
+def test_merged_beam_holds_distinct_messages_and_today_it_does_not(setup, refs):
+    """Fails without the feature.  With the weights of ``setup`` (perturb_state_dict, seed 1) the unmerged beam-3 search holds one
+    word sequence in two slots of positive probability for some commit, or unmerged and merged greedy messages differ (here: the
+    latter, for every commit); the merged beam never repeats a word sequence among its slots of positive probability."""
+    cfg, model, db, search = setup
+    plain = slot_messages(*refs[None]["beam"])
+    repeats = sum(len(m) != len(set(m)) for m in plain)
+    g0, g1 = refs[None]["greedy"], refs["merge", None]["greedy"]
+    differ = sum(a != b for a, b in zip(search.best(*g0[:3]), search.best(*g1[:3])))
+    print("commits whose unmerged beam repeats a message: %d; commits whose greedy message changes: %d" % (repeats, differ))
+    assert repeats >= 1 or differ >= 1
+    for c in (None, CON):
+        got = slot_messages(*search.beam(db, 3, constraints=c, merge_copies=True))
+        if c is None:                                        # (under CON the unsharpened products underflow fp32 to 0 for some commits)
+            assert all(len(m) >= 2 for m in got)
+        assert all(len(m) == len(set(m)) for m in got), got
+
+
+def test_merged_factors_agree_with_the_scorers_p_word(setup, refs):
+    """For the merged greedy messages, ``Searcher.score``'s per-token p_word (generator entry first, then the slots) against the
+    factor the merged search multiplied in (slots first, the generator entry last): two summation orders of at most L + S + 1
+    non-negative terms, each within (L + S) 2^-24 relative of the exact sum."""
+    cfg, model, db, search = setup
+    out, length, prob, factors = refs["merge", None]["greedy"]
+    T = cfg.tar_len
+    inner = (out[:, 1:] == PAD) | (out[:, 1:] == START)       # ids the scorer's contract excludes end the scored part
+    pos = torch.arange(1, T)[None, :]
+    first = torch.where((inner & (pos < length[:, None])).any(1), (inner & (pos < length[:, None])).long().argmax(1) + 1,
+                        torch.full_like(length, T))
+    cut = torch.minimum(length, first)
+    assert int((cut - 1).sum()) >= db.B                       # (something is scored)
+    sc = search.score(db, out[:, None, :], lengths=cut[:, None])
+    p_word = sc["p_word"][:, 0].cpu().double()
+    bound = 2.0 * (cfg.sou_len + cfg.sub_token_len) * 2.0 ** -24
+    worst = 0.0
+    for b in range(db.B):
+        for t in range(int(cut[b]) - 1):
+            f = float(factors[b, t])
+            worst = max(worst, abs(float(p_word[b, t]) - f) / f)
+    print("largest relative difference %.3g, bound %.3g" % (worst, bound))
+    assert worst <= bound
+
+
+def test_flag_off_is_todays_search(setup, refs):
+    cfg, model, db, search = setup
+    from fira_icse_amd.decode import Searcher
+    fresh, today = Searcher(model), Searcher(model)
+    for use_graphs in (True, False):
+        want_b = tuple(t.clone() for t in today.beam(db, 3, use_graphs=use_graphs))            # the calls as they were
+        want_g = tuple(t.clone() for t in today.greedy(db, use_graphs=use_graphs))
+        got_b = fresh.beam(db, 3, use_graphs=use_graphs, merge_copies=False)
+        got_g = fresh.greedy(db, use_graphs=use_graphs, merge_copies=False)
+        assert all(torch.equal(a, b) for a, b in zip(got_b, want_b)) and all(torch.equal(a, b) for a, b in zip(got_g, want_g))
+        assert all(torch.equal(a.cpu(), b) for a, b in zip(want_b, refs[None]["beam"]))
+        assert all(torch.equal(a.cpu(), b) for a, b in zip(want_g, refs[None]["greedy"]))
+    assert set(fresh._ws) == {(db.B, 3), (db.B, 1), ("beam", db.B, 3), ("greedy", db.B)}
+    assert "dist" not in fresh._ws[("greedy", db.B)] and "merge" not in fresh._ws[("beam", db.B, 3)]
+    # merged and unmerged states have their own keys: running one does not re-capture the other
+    graphs = {k: fresh._ws[k]["graphs"] for k in (("beam", db.B, 3), ("greedy", db.B))}
+    same_search(fresh.beam(db, 3, merge_copies=True), refs["merge", None]["beam"])
+    same_search(fresh.greedy(db, merge_copies=True), refs["merge", None]["greedy"])
+    same_search(fresh.beam(db, 3, merge_copies=True, constraints=CON), refs["merge", CON]["beam"])
+    same_search(fresh.greedy(db, merge_copies=True, constraints=CON), refs["merge", CON]["greedy"])
+    assert {("beam", db.B, 3, "merge"), ("greedy", db.B, "merge"), ("beam", db.B, 3, "merge", CON),
+            ("greedy", db.B, "merge", CON)} <= set(fresh._ws)
+    assert fresh._ws[("greedy", db.B, "merge")]["dist"].shape == (db.B, cfg.out_len)
+    assert all(fresh._ws[k]["graphs"] is g for k, g in graphs.items())
+    same_search(fresh.beam(db, 3), refs[None]["beam"])
+    same_search(fresh.greedy(db), refs[None]["greedy"])
+    assert all(fresh._ws[k]["graphs"] is g for k, g in graphs.items())
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def run(args, cwd):
+    env = dict(os.environ, PYTHONPATH=util.REPO)
+    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return r.stdout
+
+
+def test_cli_merge_copies_and_nbest(tmp_path):
+    from fira_icse_amd.model import reference_init_state_dict
+    root = str(tmp_path)
+    cfg = FiraConfig()
+    synth.write_dataset(root, util.load_golden_raw())
+    torch.manual_seed(0)
+    torch.save(util.peaked_state_dict(reference_init_state_dict(cfg), seed=2), os.path.join(root, "best_model.pt"))
+    base = ["test", "--splits", "16,4,4", "--test-batch-size", "3"]
+    out_f, nbest_f = os.path.join(root, "OUTPUT", "output_fira"), os.path.join(root, "OUTPUT", "output_fira_nbest")
+
+    def check_nbest(distinct):
+        lines = open(out_f).read().split("\n")
+        recs = open(nbest_f).read().split("\n")
+        assert len(lines) == 5 and lines[-1] == "" and len(recs) == 5 and recs[-1] == ""
+        for line, rec in zip(lines[:-1], recs[:-1]):
+            rec = json.loads(rec)
+            assert sorted(rec) == ["messages", "prob"] and 1 <= len(rec["messages"]) == len(rec["prob"]) <= 3
+            assert rec["messages"][0] == line
+            assert all(p > 0 for p in rec["prob"]) and rec["prob"] == sorted(rec["prob"], reverse=True)
+            if distinct:
+                assert len(set(rec["messages"])) == len(rec["messages"]), rec
+
+    # neither option: the output recorded before the options existed (same root, same seed), and no n-best file
+    run(base, root)
+    gold = json.load(open(os.path.join(util.GOLDEN, "decode_ref.json")))["beam3"]
+    plain = open(out_f, "rb").read()
+    assert plain == "".join(l + "\n" for l in gold).encode() and not os.path.exists(nbest_f)
+    run(base + ["--nbest"], root)                            # --nbest alone changes nothing in output_fira
+    assert open(out_f, "rb").read() == plain
+    check_nbest(distinct=False)
+    run(base + ["--merge-copies", "--nbest"], root)
+    check_nbest(distinct=True)
