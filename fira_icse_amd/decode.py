@@ -117,6 +117,57 @@ class Constraints:
         return self
 
 
+@dataclasses.dataclass(frozen=True)
+class BeamScoring:
+    """How a beam search ranks its hypotheses (``fira_beam_select_scored``).
+
+    ``length_alpha`` a: hypotheses are ranked by ln(prob) / ((5 + m) / 6)^a, m = words emitted (GNMT's length penalty; 0 = the
+    raw probability, under which a hypothesis that ends early wins).
+    ``groups`` G and ``diversity`` l: the beam is G groups of beam / G slots; a group ranks a continuation l lower for every
+    earlier group that has just appended the same WORD (generator or copied) for the commit, so the groups spell different
+    messages (diverse beam search, Hamming diversity).  Both or neither: a penalty needs groups, groups without a penalty
+    would search the same thing G times.
+
+    Values are checked here (``ValueError`` with the reason); ``check`` holds the value against a beam size."""
+    length_alpha: float = 0.0
+    groups: int = 1
+    diversity: float = 0.0
+
+    MAX_ALPHA, MAX_GROUPS, MAX_DIVERSITY = 4.0, 8, 1024.0
+
+    def __post_init__(self):
+        for name, hi in (("length_alpha", self.MAX_ALPHA), ("diversity", self.MAX_DIVERSITY)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError("BeamScoring: %s = %r is not a number" % (name, v))
+            if not 0 <= v <= hi:                              # (also refuses nan)
+                raise ValueError("BeamScoring: %s = %r outside [0, %g]" % (name, v, hi))
+            object.__setattr__(self, name, float(v))
+        g = self.groups
+        if isinstance(g, bool) or not isinstance(g, int):
+            raise ValueError("BeamScoring: groups = %r is not an integer" % (g,))
+        if not 1 <= g <= self.MAX_GROUPS:
+            raise ValueError("BeamScoring: groups = %d outside 1..%d" % (g, self.MAX_GROUPS))
+        if self.diversity > 0 and g == 1:
+            raise ValueError("BeamScoring: diversity = %g needs groups > 1 (the penalty acts between groups)" % self.diversity)
+        if g > 1 and self.diversity == 0:
+            raise ValueError("BeamScoring: groups = %d needs diversity > 0 (else every group searches the same)" % g)
+
+    def active(self) -> bool:
+        return bool(self.length_alpha or self.groups > 1)
+
+    def check(self, beam: int) -> "BeamScoring":
+        if beam < 2:
+            raise ValueError("BeamScoring: a beam of %d has nothing to rank (beam >= 2)" % beam)
+        if beam % self.groups:
+            raise ValueError("BeamScoring: groups = %d does not divide the beam of %d" % (self.groups, beam))
+        return self
+
+    def inv_lp(self, tar_len: int) -> List[float]:
+        """inv_lp[m] = 1 / ((5 + m) / 6)^length_alpha for m = 0 .. tar_len, in float64 (the device buffer rounds it to fp32)."""
+        return [1.0 / ((5.0 + m) / 6.0) ** self.length_alpha for m in range(tar_len + 1)]
+
+
 class Scores(dict):
     """Result of ``Searcher.score``: a dict whose keys also read as attributes."""
 
@@ -263,10 +314,11 @@ class Searcher:
                    "fira_merge_dist")
 
     @staticmethod
-    def _key(base, merge: bool, con):
+    def _key(base, merge: bool, con, scoring=None):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
-        so merged and unmerged searches own separate buffers and graphs."""
-        return base + (("merge",) if merge else ()) + ((con,) if con is not None else ())
+        so merged and unmerged searches own separate buffers and graphs; an active BeamScoring value comes last."""
+        return (base + (("merge",) if merge else ()) + ((con,) if con is not None else ())
+                + ((scoring,) if scoring is not None else ()))
 
     def _banned_buffer(self, c: Constraints):
         return torch.tensor(list(c.banned) or [0], dtype=torch.int32, device=self.model.device_)
@@ -670,7 +722,11 @@ class Searcher:
             st[k][1].zero_()
         st["gen"][0][:, 0] = START
         st["length"][0].fill_(1)
-        st["prob"][0].view(B, beam)[:, 0] = 1.0
+        sc = st.get("scoring")
+        if sc is None:
+            st["prob"][0].view(B, beam)[:, 0] = 1.0
+        else:
+            st["prob"][0].view(B, beam)[:, ::beam // sc.groups] = 1.0       # the first slot of every group
         st["done"].zero_()
 
     def _beam_steps(self, st, ws, B, beam, lo, hi):
@@ -687,16 +743,21 @@ class Searcher:
                 self._merge(st, B * beam, beam, None, None)
             if st["con"] is not None:
                 self._constrain(st, B * beam, beam, st["gen"][cur], st["length"][cur], None, None)
-            _lib.check(lib.fira_beam_select(s, C.byref(self.model.dims), B, beam, _lib.ptr(st["dist"]),
-                                            _lib.ptr(st["fin"]), _lib.ptr(st["active"]), _lib.ptr(st["done"]),
-                                            _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["gen"][cur]),
-                                            _lib.ptr(st["length"][cur]), _lib.ptr(st["prob"][cur]),
-                                            _lib.ptr(st["gen"][nxt]), _lib.ptr(st["length"][nxt]),
-                                            _lib.ptr(st["prob"][nxt]), _lib.ptr(st["parent"])), "fira_beam_select")
+            state = (_lib.ptr(st["dist"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]), _lib.ptr(st["done"]),
+                     _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]),
+                     _lib.ptr(st["prob"][cur]), _lib.ptr(st["gen"][nxt]), _lib.ptr(st["length"][nxt]),
+                     _lib.ptr(st["prob"][nxt]), _lib.ptr(st["parent"]))
+            sc = st.get("scoring")
+            if sc is None:
+                _lib.check(lib.fira_beam_select(s, C.byref(self.model.dims), B, beam, *state), "fira_beam_select")
+            else:
+                _lib.check(lib.fira_beam_select_scored(s, C.byref(self.model.dims), B, beam, *state, _lib.ptr(st["inv_lp"]),
+                                                       sc.groups, sc.diversity, _lib.ptr(st["key"])), "fira_beam_select_scored")
 
     @torch.no_grad()
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
-             constraints: Optional[Constraints] = None, merge_copies: bool = False):
+             constraints: Optional[Constraints] = None, merge_copies: bool = False,
+             scoring: Optional[BeamScoring] = None):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``: a ``Constraints``
         value; one ``fira_constrain_dist`` call per step then zeroes the blocked words' entries of every row between the step
         and the selection (nothing is renormalised); None or inactive: today's three calls per step and today's graphs.
@@ -708,6 +769,15 @@ class Searcher:
         spells it -- exact, because the next step depends on the resolved ids only -- and no longer the product of the entries
         taken.  The state is keyed ("beam", B, beam, "merge"[, constraints]); False: today's calls, keys, buffers and graphs.
 
+        ``scoring``: a ``BeamScoring`` value.  ``fira_beam_select_scored`` then takes the place of ``fira_beam_select`` (after
+        merge and constraints): hypotheses are ranked by the length-normalised key ln(prob) / ((5 + m) / 6)^alpha instead of
+        the raw probability, within ``groups`` beam groups that a ``diversity`` penalty per repeated word keeps apart.  The
+        call then returns FOUR tensors, (hypotheses, lengths, probabilities, keys [B,beam]) -- the raw probability and the
+        unpenalised key of every slot, -inf where the probability is 0 -- and ``best(gen, length, key)`` picks by key.  The
+        value joins the state key (the scalars are baked into captured graphs); the state owns the inv_lp table and the key
+        buffer, and its reset seeds the first slot of every group.  None or an inactive value: today's key, buffers,
+        launches, graphs and three tensors.  A beam of 1 with ``scoring`` given is a ``ValueError``.
+
         Per step: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library calls, no torch
         op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam) shape, and
         the ``done`` latch is read back between chunks (run_model.py:276-279)."""
@@ -715,6 +785,10 @@ class Searcher:
         BR = B * beam
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
+        if scoring is not None:
+            if not isinstance(scoring, BeamScoring):
+                raise ValueError("scoring: expected decode.BeamScoring or None, got %r" % (scoring,))
+            scoring = scoring.check(beam) if scoring.active() or beam < 2 else None
 
         def make(i32, f32):
             st = dict(gen=[i32(BR, T), i32(BR, T)], length=[i32(BR), i32(BR)], prob=[f32(BR), f32(BR)], tok=i32(BR),
@@ -723,15 +797,19 @@ class Searcher:
                 st["merge"] = True
             if con is not None:
                 st["banned"] = self._banned_buffer(con)
+            if scoring is not None:
+                st.update(scoring=scoring, key=f32(BR),
+                          inv_lp=torch.tensor(scoring.inv_lp(T), dtype=torch.float64).to(torch.float32).to(self.model.device_))
             return st
-        # (a captured graph bakes the constraint scalars and the merge launch: they are part of the key)
-        loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con), make, chunk, use_graphs)
+        # (a captured graph bakes the constraint scalars, the merge launch and the scoring scalars: they are part of the key)
+        loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
         cur = loop.hi & 1                                    # the ping-pong buffer the last step run wrote
-        return (st["gen"][cur].view(B, beam, T).long(), st["length"][cur].view(B, beam).long(),
-                st["prob"][cur].view(B, beam).clone())
+        res = (st["gen"][cur].view(B, beam, T).long(), st["length"][cur].view(B, beam).long(),
+               st["prob"][cur].view(B, beam).clone())
+        return res if scoring is None else res + (st["key"].view(B, beam).clone(),)
 
     def best(self, gen, length, prob) -> List[List[int]]:
         """argmax-probability hypothesis per item, first on ties (run_model.py:351-352)."""

@@ -713,6 +713,36 @@ int fira_beam_select(void* stream, const fira_dims* d, int B, int n_beam, const 
                      const int32_t* gen_in, const int32_t* len_in, const float* prob_in, int32_t* gen_out,
                      int32_t* len_out, float* prob_out, int32_t* parent);
 
+/* fira_beam_select under a length-normalised key, in diverse beam groups (csrc/beam_score.hip; additive, the ABI version is
+ * unchanged).  The arguments of fira_beam_select, then inv_lp, n_groups, diversity and key_out; the state is the same, since a
+ * hypothesis's key is a function of its (prob, length):
+ *     key(p, m) = ln(p) * inv_lp[m],  inv_lp[m] = 1 / ((5 + m) / 6)^alpha  (GNMT; computed by the caller in float64, rounded to
+ *     fp32, tar_len + 1 entries on the device),  m = words emitted = length - 1 (<start> not counted, <eos> counted),  ln 0 = -inf.
+ * Candidates of a step, per commit:
+ *     running   entry i of running slot j: p = fp32(dist[j, i] * prob[j]) (the product fira_beam_select forms), m = len_j
+ *     carried   a finished hypothesis of the commit: p = prob[j], m = len_j - 1 (fixed from the moment it finished)
+ *     void      the entries of a finished hypothesis's row and the padding of the carried list (fira_beam_select's two -1)
+ * Total order: void last, then penalised key descending, then p descending, then fira_beam_select's flattened index ascending
+ * (running slots in slot order, then the carried list).  With every inv_lp[m] = 1 (alpha = 0) and n_groups = 1 the order is
+ * (p descending, index ascending): gen_out, len_out, prob_out and parent equal fira_beam_select's bit for bit.
+ * Groups: the n_beam slots are n_groups groups of k = n_beam / n_groups consecutive slots, handled in ascending order within
+ * the step; group g takes its k best among the candidates of ITS OWN slots (their running rows and their finished hypotheses)
+ * and writes them to its own slots, best first.  Penalised key of a running candidate: key - diversity * c, c = the number of
+ * picks made earlier in this step, for this commit, by groups < g that EXTENDED a hypothesis with the same WORD (multiplicity
+ * counts); the word of entry i is w(i) of fira_constrain_dist: the generator id, or the sou / sub_token id of a copy slot.
+ * Carried candidates are never penalised and contribute to no count.  The penalty affects selection only: prob_out is the raw
+ * product, key_out[r] (optional) = key(prob_out[r], len_out[r] - 1), -inf for a probability of 0.  The caller seeds slot g * k
+ * of every group with probability 1 and the other slots with 0.  Keys are formed and compared in fp64 on the fp32 products.
+ * Once `done` is set the state is copied through (key_out is still written).  Nothing is renormalised.
+ * 2 <= n_beam <= 8, n_groups >= 1 divides n_beam, diversity finite and >= 0, tar_len <= 64, sou_len + sub_len <= 1 024,
+ * vocab > 8.  One workgroup per commit, the bytes streamed are fira_beam_select's; vector stores only, no global atomics. */
+int fira_beam_select_scored(void* stream, const fira_dims* d, int B, int n_beam, const float* dist, const int32_t* finished,
+                            const int32_t* active, const int32_t* done, const int32_t* sou, const int32_t* sub_token,
+                            const int32_t* gen_in, const int32_t* len_in, const float* prob_in, int32_t* gen_out,
+                            int32_t* len_out, float* prob_out, int32_t* parent,
+                            const float* inv_lp /* device, [tar_len + 1] */, int n_groups, float diversity,
+                            float* key_out /* [B*n_beam] or NULL */);
+
 /* Greedy search bookkeeping (the same loop at beam 1 without the [B, vocab+S] distribution): consumes the arg-max
  * index / probability fira_decode_step wrote, resolves copy indices through sou / sub_token, appends the id at
  * out[b, step+1], multiplies prob, bumps length, clears alive[b] at <eos>, writes the next step's input ids to `tokens`

@@ -114,6 +114,15 @@ def parse_args(argv):
     ap.add_argument("--nbest", action="store_true", help="test, beam above 1: also write OUTPUT/output_fira_nbest, one JSON "
                     "line per commit with the beam's messages and their probabilities, best first (OUTPUT/output_fira is "
                     "unchanged: its line is the first message); without --merge-copies the list may repeat a message")
+    ap.add_argument("--length-penalty", type=float, default=None, metavar="A", help="test, beam above 1: rank hypotheses by "
+                    "ln(prob) / ((5 + m) / 6)^A, m = words emitted (GNMT's length penalty, 0 <= A <= 4) instead of the raw "
+                    "probability, under which a message that ends early wins; combines with the constraint options, "
+                    "--merge-copies and --nbest")
+    ap.add_argument("--beam-groups", type=int, default=None, metavar="G", help="test, beam above 1: diverse beam search -- the "
+                    "beam is G groups (G divides --beam) that --diversity-penalty keeps apart; needs --diversity-penalty")
+    ap.add_argument("--diversity-penalty", type=float, default=None, metavar="L", help="test, with --beam-groups: a group ranks "
+                    "a continuation L lower (in log-probability) for every earlier group that has just appended the same word, "
+                    "generator or copied (0 < L <= 1024)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
@@ -136,6 +145,7 @@ def parse_args(argv):
         check_score_args(a)
         check_constraint_args(a)
         check_merge_args(a)
+        check_scoring_args(a)
         check_sample_args(a)
     except ValueError as e:
         ap.error(str(e))
@@ -308,11 +318,60 @@ def check_merge_args(a):
     return a
 
 
-def nbest_record(messages, probs):
+SCORING_OPTIONS = (("length_penalty", "--length-penalty"), ("beam_groups", "--beam-groups"),
+                   ("diversity_penalty", "--diversity-penalty"))
+
+
+def check_scoring_args(a):
+    """Validates --length-penalty / --beam-groups / --diversity-penalty against the other options (no GPU, no DataSet needed);
+    raises ValueError naming the flags on a conflict or an out-of-range value (the ranges are decode.BeamScoring's)."""
+    given = [flag for name, flag in SCORING_OPTIONS if getattr(a, name, None) is not None]
+    if not given:
+        return a
+    if a.stage != "test":
+        raise ValueError("%s only apply to the test stage" % ", ".join(given))
+    if a.sample is not None:
+        raise ValueError("%s rank the hypotheses of a beam: they do not combine with --sample" % ", ".join(given))
+    if a.score is not None:
+        raise ValueError("%s rank the hypotheses of a beam: they do not combine with --score" % ", ".join(given))
+    if a.beam is not None and a.beam <= 1:
+        raise ValueError("%s rank the hypotheses of a beam: they do not combine with --beam %d" % (", ".join(given), a.beam))
+    A, G, lam = a.length_penalty, a.beam_groups, a.diversity_penalty
+    if A is not None and not 0 <= A <= 4:                      # (also refuses nan)
+        raise ValueError("--length-penalty %g: must be in [0, 4] (0 = off)" % A)
+    if G is not None and not 1 <= G <= 8:
+        raise ValueError("--beam-groups %d: must be in 1..8 (1 = off)" % G)
+    if lam is not None and not 0 <= lam <= 1024:
+        raise ValueError("--diversity-penalty %g: must be in [0, 1024] (0 = off)" % lam)
+    if (lam or 0) > 0 and (G or 1) == 1:
+        raise ValueError("--diversity-penalty %g acts between beam groups: it needs --beam-groups above 1" % lam)
+    if (G or 1) > 1 and not (lam or 0) > 0:
+        raise ValueError("--beam-groups %d needs --diversity-penalty above 0 (else every group searches the same)" % G)
+    beam = a.beam if a.beam is not None else 3
+    if beam % (G or 1):
+        raise ValueError("--beam-groups %d does not divide --beam %d" % (G, beam))
+    return a
+
+
+def scoring_from_args(a):
+    """The decode.BeamScoring of the command line; None without the options or when they are all at their off values."""
+    from fira_icse_amd.decode import BeamScoring
+    if all(getattr(a, name, None) is None for name, _ in SCORING_OPTIONS):
+        return None
+    sc = BeamScoring(length_alpha=a.length_penalty or 0.0, groups=a.beam_groups or 1, diversity=a.diversity_penalty or 0.0)
+    return sc.check(a.beam) if sc.active() else None
+
+
+def nbest_record(messages, probs, keys=None):
     """One line of OUTPUT/output_fira_nbest: the beam's messages of positive probability (the -1 padding and zero-probability
-    candidates are left out), ordered by probability descending, then slot ascending."""
-    order = sorted((j for j in range(len(probs)) if probs[j] > 0), key=lambda j: (-probs[j], j))
-    return json.dumps({"messages": [messages[j] for j in order], "prob": [probs[j] for j in order]})
+    candidates are left out), ordered by probability descending, then slot ascending.  With ``keys`` (a search under
+    --length-penalty / --beam-groups): ordered by key descending, then slot ascending, and the line carries the keys too."""
+    rank = probs if keys is None else keys
+    order = sorted((j for j in range(len(probs)) if probs[j] > 0), key=lambda j: (-rank[j], j))
+    rec = {"messages": [messages[j] for j in order], "prob": [probs[j] for j in order]}
+    if keys is not None:
+        rec["key"] = [keys[j] for j in order]
+    return json.dumps(rec)
 
 
 SAMPLE_OPTIONS = (("temperature", "--temperature", 1.0), ("top_k", "--top-k", 0), ("top_p", "--top-p", 1.0),
@@ -518,6 +577,7 @@ class Run:
         if self.a.score is not None and self.a.score != "refs":
             given = read_score_lines(self.a.score, len(store))   # a wrong line count is an error before the model loads
         constraints = constraints_from_args(self.a, self.vocab, cfg)       # an unknown word too
+        scoring = scoring_from_args(self.a)
         self.model = TransModel(cfg, device="cuda:%d" % self.local, init=False)
         self.model.load_state_dict(torch.load(os.path.join(self.root, "best_model.pt"), map_location="cpu"))
         self.model.compute_dtype = self.a.dtype
@@ -542,14 +602,21 @@ class Run:
                 outs = [search.best(*r) for r in search.greedy_many(dbs, in_flight=group, constraints=constraints,
                                                                     merge_copies=merge)]
             else:
-                gen, length, prob = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge)
-                outs = [search.best(gen, length, prob)]
+                keys = None
+                if scoring is None:
+                    gen, length, prob = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge)
+                    outs = [search.best(gen, length, prob)]
+                else:                                        # ranked by key: the best slot of positive probability, lowest on ties
+                    gen, length, prob, keys = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge,
+                                                          scoring=scoring)
+                    outs = [search.best(gen, length, keys)]
+                    keys = keys.tolist()
                 if want_nbest:                               # the whole beam of every commit, best first
                     gen, length, prob = gen.tolist(), length.tolist(), prob.tolist()
                     for k, i in enumerate(idxs[0]):
                         msgs = [text.detokenize(g[:n], self.r_vocab, self.var_maps[test_index[i]])
                                 for g, n in zip(gen[k], length[k])]
-                        nbest.append(nbest_record(msgs, prob[k]))
+                        nbest.append(nbest_record(msgs, prob[k], None if keys is None else keys[k]))
             for idx, hyps in zip(idxs, outs):
                 for h, i in zip(hyps, idx):
                     lines.append(text.detokenize(h, self.r_vocab, self.var_maps[test_index[i]]))
