@@ -178,6 +178,39 @@ class Scores(dict):
             raise AttributeError(name) from None
 
 
+MAX_MODELS = 8                                   # fira_mix_dist: 2 <= n_members <= 8
+
+
+def ensemble_weights(weights, n_models: int):
+    """The mixing weights of an ensemble of ``n_models`` models as a float32 numpy array, the primary first.  None: uniform,
+    np.float32(1) / np.float32(M).  Given weights are normalised in float64 to sum 1, then cast to float32.  ``ValueError`` on a
+    wrong count, a negative or non-finite weight, or weights that sum to 0."""
+    import numpy as np
+    if weights is None:
+        return np.full(n_models, np.float32(1) / np.float32(n_models), dtype=np.float32)
+    try:
+        w = np.array([float(x) for x in weights], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("weights: %r is not a sequence of numbers" % (weights,)) from None
+    if w.shape != (n_models,):
+        raise ValueError("weights: %d values for %d models (one per model, the primary first)" % (w.size, n_models))
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("weights: %s holds a negative or non-finite value" % (w.tolist(),))
+    if not w.sum() > 0:
+        raise ValueError("weights: %s sum to 0" % (w.tolist(),))
+    return (w / w.sum()).astype(np.float32)
+
+
+class _Members:
+    """What ``Searcher._begin`` hands to ``Searcher._step`` for an ensemble in place of the one decode workspace: the decode
+    workspace and the [R, out_len] distribution buffer of every member, and the host arrays ``fira_mix_dist`` reads at launch."""
+
+    def __init__(self, ws, dist, weights):
+        self.ws, self.dist = ws, dist
+        self.ptrs = (C.c_void_p * len(dist))(*[t.data_ptr() for t in dist])
+        self.weights = (C.c_float * len(dist))(*[float(x) for x in weights])
+
+
 def rank_values(scores, by: str) -> torch.Tensor:
     """The [B, n] values ``Searcher.rank`` orders candidates by (larger is better)."""
     if by == "mean_logp_word":
@@ -259,37 +292,97 @@ class _Loop:
 
 
 class Searcher:
-    def __init__(self, model: TransModel, kv_bf16: bool = False):
+    def __init__(self, model: TransModel, kv_bf16: bool = False, members=(), weights=None):
         """``kv_bf16``: stream a bf16 copy of the cross-attention K|V in the step loop (FIRA_DECODE_KV_BF16: half of the
-        bytes a step moves; ids no longer bit-identical to the fp32 search -- off by default)."""
+        bytes a step moves; ids no longer bit-identical to the fp32 search -- off by default).
+
+        ``members``: further ``TransModel`` instances of the same geometry on the same device.  ``greedy`` / ``greedy_many`` /
+        ``beam`` then search under the linear mix of the models' step distributions (``fira_mix_dist``):
+        p = w_0 p_0 + w_1 p_1 + ..., ``model`` being member 0.  ``weights``: one value per model, the primary first (default
+        uniform; given weights are normalised to sum 1: ``ensemble_weights``).  With ``members == ()`` nothing changes."""
         self.model = model
         self.cfg = model.cfg
         self.flags = 1 if kv_bf16 else 0
         self._ws = {}
+        self.members = tuple(members)
+        models = (model,) + self.members
+        if len(models) > MAX_MODELS:
+            raise ValueError("members: %d models in all, more than %d" % (len(models), MAX_MODELS))
+        for k, m in enumerate(self.members, 1):
+            if not isinstance(m, TransModel):
+                raise ValueError("members: member %d is %r, not a TransModel" % (k, type(m).__name__))
+            for name, _ in _lib.Dims._fields_:
+                if getattr(m.dims, name) != getattr(model.dims, name):
+                    raise ValueError("members: member %d has %s = %d, the primary %d (every member has the primary's geometry)"
+                                     % (k, name, getattr(m.dims, name), getattr(model.dims, name)))
+            if m.device_ != model.device_:
+                raise ValueError("members: member %d is on %s, the primary on %s" % (k, m.device_, model.device_))
+        if not self.members and weights is not None:
+            ensemble_weights(weights, 1)                      # (one model: only the count and the values can be wrong)
+        self.weights = ensemble_weights(weights, len(models)) if self.members else None
 
-    def _workspace(self, B, beam):
-        key = (B, beam)
+    def _lane(self) -> "Searcher":
+        """A second Searcher over the same models (its own workspaces, states and graphs) for a lane of ``greedy_many``."""
+        lane = Searcher(self.model, kv_bf16=bool(self.flags), members=self.members)
+        lane.weights = self.weights                           # the very float32 values: normalising twice may move a bit
+        return lane
+
+    def _no_ensemble(self, what: str):
+        if self.members:
+            raise ValueError("%s does not combine with an ensemble (its fused step has no distribution hand-off)" % what)
+
+    def _workspace(self, B, beam, model=None, key=None):
+        model = self.model if model is None else model
+        key = (B, beam) if key is None else key
         if key not in self._ws:
-            n = _lib.lib().fira_decode_workspace_bytes_ex(C.byref(self.model.dims), B, beam, self.flags)
+            n = _lib.lib().fira_decode_workspace_bytes_ex(C.byref(model.dims), B, beam, self.flags)
             if n == 0:
                 _lib.check(1, "fira_decode_workspace_bytes")
-            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.model.device_)
+            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=model.device_)
         return self._ws[key]
+
+    def _begin_model(self, model, ws, db, beam):
+        _lib.check(_lib.lib().fira_decode_begin_ex(_lib.cur_stream(), C.byref(model.dims), C.byref(db.struct),
+                                                   _lib.ptr(model.flat.data), _lib.ptr(ws), ws.numel(), beam,
+                                                   self.flags), "fira_decode_begin")
 
     def _begin(self, db, beam):
         ws = self._workspace(db.B, beam)
         self.model.sync_params()
         db.wait_ready()
-        _lib.check(_lib.lib().fira_decode_begin_ex(_lib.cur_stream(), C.byref(self.model.dims), C.byref(db.struct),
-                                                   _lib.ptr(self.model.flat.data), _lib.ptr(ws), ws.numel(), beam,
-                                                   self.flags), "fira_decode_begin")
-        return ws
+        self._begin_model(self.model, ws, db, beam)
+        if not self.members:
+            return ws
+        # an ensemble: one workspace (the primary's under today's key) and one distribution buffer per member; the encoder pass
+        # of every member on the current stream, in member order, all of them reading the one ``db``
+        key = ("members", db.B, beam)
+        if key not in self._ws:
+            wss = [ws] + [self._workspace(db.B, beam, m, ("member", k, db.B, beam)) for k, m in enumerate(self.members, 1)]
+            dist = [torch.zeros((db.B * beam, self.cfg.out_len), dtype=torch.float32, device=self.model.device_) for _ in wss]
+            self._ws[key] = _Members(wss, dist, self.weights)
+        mem = self._ws[key]
+        for model, w in zip(self.members, mem.ws[1:]):
+            model.sync_params()
+            self._begin_model(model, w, db, beam)
+        return mem
 
-    def _step(self, ws, B, beam, step, tokens, parent, dist, best_id, best_p):
-        _lib.check(_lib.lib().fira_decode_step_ex(_lib.cur_stream(), C.byref(self.model.dims),
-                                                  _lib.ptr(self.model.flat.data), _lib.ptr(ws), ws.numel(), B, beam, step,
+    def _step_model(self, model, ws, B, beam, step, tokens, parent, dist, best_id, best_p):
+        _lib.check(_lib.lib().fira_decode_step_ex(_lib.cur_stream(), C.byref(model.dims),
+                                                  _lib.ptr(model.flat.data), _lib.ptr(ws), ws.numel(), B, beam, step,
                                                   _lib.ptr(tokens), _lib.ptr(parent), _lib.ptr(dist), _lib.ptr(best_id),
                                                   _lib.ptr(best_p), self.flags), "fira_decode_step")
+
+    def _step(self, ws, B, beam, step, tokens, parent, dist, best_id, best_p):
+        if not self.members:
+            return self._step_model(self.model, ws, B, beam, step, tokens, parent, dist, best_id, best_p)
+        # an ensemble (``ws`` is the _Members of ``_begin``): every member's step with the same tokens and parents into its own
+        # buffer, then one fira_mix_dist into the caller's ``dist`` -- or, for a search that asks for the arg-max only, in place
+        # over member 0's buffer -- which also delivers best_id / best_p
+        for model, w, d in zip((self.model,) + self.members, ws.ws, ws.dist):
+            self._step_model(model, w, B, beam, step, tokens, parent, d, None, None)
+        out = ws.dist[0] if dist is None else dist
+        _lib.check(_lib.lib().fira_mix_dist(_lib.cur_stream(), B * beam, self.cfg.out_len, len(ws.dist), ws.ptrs, ws.weights,
+                                            _lib.ptr(out), _lib.ptr(best_id), _lib.ptr(best_p)), "fira_mix_dist")
 
     def _active(self, constraints: Optional[Constraints]) -> Optional[Constraints]:
         """None for "no constraint" (None or an inactive value: today's launches, buffers and graphs), else the checked value."""
@@ -445,7 +538,7 @@ class Searcher:
         if not hasattr(self, "_lanes") or len(self._lanes) < n_lane:
             streams = concurrent_streams(n_lane, self.model.device_)
             old = getattr(self, "_lanes", [])
-            self._lanes = [(old[k][0] if k < len(old) else (Searcher(self.model, kv_bf16=bool(self.flags)) if k else self),
+            self._lanes = [(old[k][0] if k < len(old) else (self._lane() if k else self),
                             streams[k]) for k in range(n_lane)]
         main = torch.cuda.current_stream()
         results = [None] * len(dbs)
@@ -513,6 +606,7 @@ class Searcher:
         into hipGraphs by the loop driver of ``greedy`` (``_Loop``), with the same early stop between chunks.  The filters are
         fixed in the captured launches, so they are part of the state's key; the seed is a device scalar read at run time: one
         capture serves every seed."""
+        self._no_ensemble("sample")                           # raises before anything is launched
         B, T = db.B, self.cfg.tar_len
         R = B * n
         keys = torch.arange(B) if keys is None else torch.as_tensor(keys)
@@ -672,6 +766,7 @@ class Searcher:
         back between chunks.  Candidates, labels and per-token outputs are step-major in the state ([T, B * n]), so step t's
         inputs and outputs are plain rows of them.
         ``dist`` (tests): a [tar_len - 1, B * n, out_len] tensor that receives every step's distribution (eager only)."""
+        self._no_ensemble("score")                            # raises before anything is launched
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
         cand, length, labels = self.check_candidates(cand, lengths, labels, B)        # raises before anything is launched

@@ -809,6 +809,26 @@ int fira_merge_dist(void* stream, const fira_dims* d, int R, int rows_per_commit
                     float* dist /* [R, vocab + sou_len + sub_len], in place */,
                     int32_t* best_id, float* best_p /* both NULL or both given */);
 
+/* Ensemble decoding (csrc/mix.hip; additive, the ABI version is unchanged): mixes the step distributions of n_members models into
+ * one, between the members' fira_decode_step calls and whatever takes a distribution next (fira_merge_dist, fira_constrain_dist,
+ * fira_beam_select / fira_beam_select_scored / fira_greedy_advance).  For every element i of the [R, W] rows, in member order,
+ * every multiply and every add rounded to fp32 on its own (no fused multiply-add):
+ *     acc = weights[0] * dists[0][i];   acc = acc + weights[1] * dists[1][i];   ...   out[i] = acc
+ * so a loop of np.float32 operations is the reference and every run and every graph replay gives the same bits.  Nothing is
+ * renormalised: with weights that sum to 1 the mix of distributions is a distribution up to rounding.  dists and weights are HOST
+ * arrays read at launch; the pointers and the weights travel as kernel arguments, so a captured launch bakes them in.
+ * out may be dists[0] (in place over member 0); any other overlap of out with a member is refused.
+ * best_id / best_p (both NULL, or both [R]): the arg-max of the row AS STORED and its value, under (value descending, index
+ * ascending) -- the order of fira_merge_dist and fira_constrain_dist; NaN never wins.  Without best_id no reduction runs.
+ * 2 <= n_members <= 8, W >= 1, every weight finite and >= 0 (else non-zero with the reason in fira_last_error(), nothing
+ * launched); R == 0 is a no-op.  Any row width and any 4-byte alignment of any pointer (16-byte accesses where the addresses
+ * allow, 4-byte ones at the edges); vector stores only, no atomics on global memory.                                          */
+int fira_mix_dist(void* stream, int R, int W, int n_members,
+                  const float* const* dists /* HOST array of n_members device pointers, each [R, W] contiguous */,
+                  const float* weights /* HOST array of n_members floats */,
+                  float* out /* [R, W]; may be dists[0] */,
+                  int32_t* best_id, float* best_p /* both NULL or both [R] */);
+
 /* On-device sampling of candidate messages (temperature, top-k, top-p).  Workspace: fira_decode_begin_ex /
  * fira_decode_workspace_bytes_ex with n_beam = n_sample (1..8) and the same flags (FIRA_DECODE_KV_BF16 allowed).
  *   fira_decode_step_sample : fira_decode_step_ex for the B * n_sample rows (row r = commit r / n_sample, sample

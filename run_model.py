@@ -123,6 +123,11 @@ def parse_args(argv):
     ap.add_argument("--diversity-penalty", type=float, default=None, metavar="L", help="test, with --beam-groups: a group ranks "
                     "a continuation L lower (in log-probability) for every earlier group that has just appended the same word, "
                     "generator or copied (0 < L <= 1024)")
+    ap.add_argument("--ensemble", default=None, metavar="PATH[,PATH...]", help="test: search (any --beam) under the weighted "
+                    "mean of several checkpoints' step distributions, mixed on the device: each PATH is a further state-dict "
+                    "file in the layout of best_model.pt, which stays member 0 (up to 8 models in all)")
+    ap.add_argument("--ensemble-weights", default=None, metavar="W0,W1,...", help="with --ensemble: one weight >= 0 per model, "
+                    "best_model.pt first; normalised to sum 1 (default: uniform)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
@@ -146,6 +151,7 @@ def parse_args(argv):
         check_constraint_args(a)
         check_merge_args(a)
         check_scoring_args(a)
+        check_ensemble_args(a)
         check_sample_args(a)
     except ValueError as e:
         ap.error(str(e))
@@ -360,6 +366,48 @@ def scoring_from_args(a):
         return None
     sc = BeamScoring(length_alpha=a.length_penalty or 0.0, groups=a.beam_groups or 1, diversity=a.diversity_penalty or 0.0)
     return sc.check(a.beam) if sc.active() else None
+
+
+def check_ensemble_args(a):
+    """Validates --ensemble / --ensemble-weights against the other options and the file system (no GPU, no DataSet needed, no
+    model loaded); raises ValueError on a conflict, a missing file, a wrong weight count or a bad weight.  Leaves
+    ``a.ensemble`` as the list of paths (or None) and ``a.ensemble_weights`` as the list of weights as given (or None)."""
+    from fira_icse_amd.decode import MAX_MODELS, ensemble_weights
+    paths, weights = getattr(a, "ensemble", None), getattr(a, "ensemble_weights", None)
+    if paths is None:
+        if weights is not None:
+            raise ValueError("--ensemble-weights only applies with --ensemble")
+        return a
+    if a.stage != "test":
+        raise ValueError("--ensemble only applies to the test stage")
+    if a.sample is not None:
+        raise ValueError("--ensemble mixes the distributions of a search: it does not combine with --sample")
+    if a.score is not None:
+        raise ValueError("--ensemble mixes the distributions of a search: it does not combine with --score")
+    if isinstance(paths, str):
+        paths = [p for p in paths.split(",")]
+    if not paths or any(not p for p in paths):
+        raise ValueError("--ensemble: an empty path")
+    if 1 + len(paths) > MAX_MODELS:
+        raise ValueError("--ensemble: %d models in all, more than %d" % (1 + len(paths), MAX_MODELS))
+    for p in paths:
+        if not os.path.isfile(p):
+            raise ValueError("--ensemble: no such file: %s" % p)
+    if isinstance(weights, str):
+        try:
+            weights = [float(x) for x in weights.split(",")]
+        except ValueError:
+            raise ValueError("--ensemble-weights %s: not a list of numbers" % weights) from None
+    if weights is not None:
+        if len(weights) != 1 + len(paths):
+            raise ValueError("--ensemble-weights: %d weights for %d models (best_model.pt first, then one per --ensemble path)"
+                             % (len(weights), 1 + len(paths)))
+        try:
+            ensemble_weights(weights, 1 + len(paths))        # (checked here, normalised by the Searcher)
+        except ValueError as e:
+            raise ValueError("--ensemble-weights: %s" % e) from None
+    a.ensemble, a.ensemble_weights = paths, weights
+    return a
 
 
 def nbest_record(messages, probs, keys=None):
@@ -582,7 +630,14 @@ class Run:
         self.model.load_state_dict(torch.load(os.path.join(self.root, "best_model.pt"), map_location="cpu"))
         self.model.compute_dtype = self.a.dtype
         self.model.eval()
-        search = Searcher(self.model)
+        members = []
+        for path in getattr(self.a, "ensemble", None) or ():   # further checkpoints, loaded the way the primary is
+            m = TransModel(cfg, device="cuda:%d" % self.local, init=False)
+            m.load_state_dict(torch.load(path, map_location="cpu"))
+            m.compute_dtype = self.a.dtype
+            m.eval()
+            members.append(m)
+        search = Searcher(self.model, members=members, weights=getattr(self.a, "ensemble_weights", None))
         mine = shard_indices(list(range(len(store))), self.rank, self.world)
         if self.a.sample is not None:
             return self.test_sample(search, store, mine)
