@@ -135,6 +135,8 @@ SIGNATURES = {
     "fira_adam_rows_step": (_I, [_P, _DP, _P, _P, C.POINTER(AdamOpts), _P, _P, _P, _I]),
     "fira_train_step_begin_rows": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, _P, C.POINTER(AdamOpts), _P]),
     "fira_train_step_end_rows": (_I, [_P, _P, C.POINTER(AdamOpts), _P, _P, _P]),
+    "fira_ema_update": (_I, [_P, _L, _P, _P, _F]),
+    "fira_ema_update_rows": (_I, [_P, _DP, _P, _P, C.POINTER(AdamOpts), _P, _F]),
     "fira_grad_sqsum_scratch_bytes": (_Z, []),
     "fira_grad_sqsum": (_I, [_P, _L, _P, _P, _I, _P]),
     "fira_clip_finish": (_I, [_P, _P, _I, _P, _P, _F]),

@@ -463,6 +463,36 @@ def adam_step_mb(p, g0, g1, m, v, lr, step, n_tok0, n_tok1=None, beta1=0.9, beta
           "fira_adam_step_mb")
 
 
+def ema_check(decay, every):
+    """Validates a per-step decay ``0 < D < 1`` and a cadence ``K >= 1`` of the weight average; raises ``ValueError``."""
+    try:
+        ok = 0.0 < float(decay) < 1.0                          # (also refuses nan)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("ema decay %r: must be a number in (0, 1)" % (decay,))
+    if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+        raise ValueError("ema cadence %r: must be an integer >= 1" % (every,))
+    return float(decay), int(every)
+
+
+def ema_weight(decay: float, every: int = 1) -> float:
+    """``w = float32(1 - D**K)``: the weight of one update of an average with per-step decay ``D`` that runs every ``K``
+    steps.  Formed in double, rounded once to fp32 -- the float the update kernels are given.  Host only, no GPU."""
+    import numpy as np
+    decay, every = ema_check(decay, every)
+    return float(np.float32(1.0 - decay ** every))
+
+
+def ema_update(ema, p, w: float):
+    """``ema += w * (p - ema)`` element by element (fira_ema_update): the subtraction, the multiply and the add each rounded to
+    fp32 on its own, so a numpy float32 loop is the bit-exact reference.  Any length >= 1, any 4-byte alignment; ``ema`` must
+    not overlap ``p``."""
+    assert ema.numel() == p.numel(), "ema and p differ in length"
+    check(_lib.lib().fira_ema_update(cur_stream(), ema.numel(), ptr(_f32(ema)), ptr(_f32(p)), float(w)), "fira_ema_update")
+    return ema
+
+
 LR_KINDS = ("constant", "inv_sqrt", "cosine", "linear")          # fira_lr_schedule.kind = the index
 
 

@@ -7,6 +7,7 @@ run_model.py:112); ``last_loss()`` reads it back only when asked.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Optional
 
@@ -20,7 +21,8 @@ from .parallel import GradReducer, ShardedOptimizerComm
 class Trainer:
     def __init__(self, model: TransModel, lr: Optional[float] = None, betas=(0.9, 0.999), eps: float = 1e-8,
                  distributed: bool = False, zero1: bool = False, grad_wire: str = "f32",
-                 clip_grad_norm: Optional[float] = None, lr_schedule=None):
+                 clip_grad_norm: Optional[float] = None, lr_schedule=None, ema_decay: Optional[float] = None,
+                 ema_every: int = 32):
         """``zero1`` (with ``distributed``): reduce-scatter + Adam on the owned 1/world shard + all-gather instead of
         all-reduce + replicated Adam; Adam moments exist only for the owned shard (parallel.ShardedOptimizerComm).
         ``grad_wire`` (with ``distributed``, all-reduce path): "f32", or "bf16" = the two gradient buckets travel as bf16
@@ -30,7 +32,21 @@ class Trainer:
         an ``inf`` / ``nan`` is applied as a zero-gradient step instead of destroying the weights; see :meth:`last_grad_norm`.
         ``lr_schedule`` (``None`` = the constant ``lr``: the code path of every release so far): an ``ops.LrSchedule`` or a
         dict of its fields -- warmup and decay as a function of the step number (``ops.lr_at``).  ``lr`` is then not used.
-        The row-sparse update stays lazy under it: the rate of every step a row still owes travels with the launch."""
+        The row-sparse update stays lazy under it: the rate of every step a row still owes travels with the launch.
+        ``ema_decay`` (``None`` = off: no buffer, no launch, the code path of every release so far): a per-step decay
+        ``0 < D < 1`` of an exponential moving average of the weights, ``self.ema`` (flat, like ``model.flat``; one full copy
+        on every rank, also with ``zero1``).  It starts as a copy of the parameters -- no warm-up of the decay and no bias
+        correction -- and after every ``ema_every``-th step (K, default 32: the cadence at which the row-sparse update has
+        just written every row) moves toward them by ``w = ops.ema_weight(D, K) = float32(1 - D**K)``:
+        ``e += w * (p - e)``, each operation rounded to fp32 on its own.  Embedding rows the row-sparse Adam still owes updates
+        are read as the forward pass reads them (fira_ema_update_rows): nothing is synced.  See :meth:`averaged`."""
+        self.ema = None
+        self.ema_cfg = None
+        self.ema_updates = 0                                     # updates behind self.ema (a loaded state: t // K)
+        self._raw = None                                         # the raw parameters while averaged() holds the model
+        if ema_decay is not None:
+            self.ema_cfg = ops.ema_check(ema_decay, ema_every)
+            self._ema_w = ops.ema_weight(*self.ema_cfg)
         self.lr_schedule = None if lr_schedule is None else ops.LrSchedule.make(lr_schedule)
         self._last_lr = None
         self._sched_cache = (None, None)
@@ -75,6 +91,9 @@ class Trainer:
             model.sync_params()                                  # (an earlier trainer of this model may still owe rows)
             self.row_step = torch.zeros(2 * model.cfg.vocab_size, dtype=torch.int32, device=model.gbuf.device)
             model._rows_sync = self.sync
+        if self.ema_cfg is not None:
+            model.sync_params()
+            self.ema = model.flat.data.clone()
         self.inv = torch.zeros(1, dtype=torch.float32, device=model.gbuf.device)
         self.stats = torch.zeros(2, dtype=torch.float32, device=model.gbuf.device)
         self.reducer = GradReducer(model.layout.split, model.layout.live, wire=grad_wire) if distributed else None
@@ -86,6 +105,57 @@ class Trainer:
             self.mid_event.record()            # torch creates the hipEvent lazily: force it so its handle can be passed
 
     def step(self, db: Optional[DeviceBatch]):
+        """One optimisation step (:meth:`_step`), then -- with ``ema_decay`` -- the update of the weight average, on every path
+        that advanced ``self.t`` (also on a rank with an empty shard that took part in the collectives; not where nothing was
+        applied).  Every branch of ``_step`` returns with all parameters final on the caller's stream."""
+        if self._raw is not None:
+            raise RuntimeError("Trainer.step inside Trainer.averaged(): the model holds the averaged weights")
+        t = self.t
+        self._step(db)
+        if self.ema is not None and self.t != t:
+            self._ema_update()
+
+    def _ema_update(self):
+        """``self.ema`` toward the parameters as they stand after step ``self.t``, if that step is on the cadence.  One launch on
+        the caller's stream, no synchronisation: with rows still owed, the rows entry applies what they owe in registers, under
+        the hyper-parameters the updates were deferred under (``_rows_check_hyper`` settles the rows before those change)."""
+        if self.t % self.ema_cfg[1]:
+            return
+        m = self.model
+        if self.row_step is not None and self._rows_dirty:
+            import ctypes as C
+            schedule, lr, b1, b2, eps = self._rows_hyper
+            adam = _lib.AdamOpts(lr if schedule is None else schedule.base_lr, b1, b2, eps, int(self.t), _lib.ptr(self.m),
+                                 _lib.ptr(self.v), _lib.sched_ptr(self._sched_struct()))
+            _lib.check(_lib.lib().fira_ema_update_rows(_lib.cur_stream(), C.byref(m.dims), _lib.ptr(self.ema),
+                                                       _lib.ptr(m.flat.data), C.byref(adam), _lib.ptr(self.row_step),
+                                                       self._ema_w), "fira_ema_update_rows")
+        else:
+            ops.ema_update(self.ema, m.flat.data, self._ema_w)
+        self.ema_updates += 1
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside the context the model holds the averaged weights (dev pass, checkpoint, search); on exit the raw parameters
+        are back bit for bit.  A phase change, not a per-step call: it syncs the rows (:meth:`sync`) and copies the flat buffer
+        twice.  The averaged weights are written INTO ``model.flat`` -- the address every captured search graph has baked in --
+        and the library forms its derived weights (folded GCN weights, planes, bf16 shadows) from the parameters inside every
+        call, so nothing is left to invalidate.  Not re-entrant; :meth:`step` and :meth:`load_state_dict` inside it raise."""
+        if self.ema is None:
+            raise RuntimeError("Trainer.averaged: this Trainer was built without ema_decay")
+        if self._raw is not None:
+            raise RuntimeError("Trainer.averaged: already inside the context (it does not nest)")
+        self.sync()
+        flat = self.model.flat.data
+        self._raw = flat.clone()
+        flat.copy_(self.ema)
+        try:
+            yield self.model
+        finally:
+            flat.copy_(self._raw)
+            self._raw = None
+
+    def _step(self, db: Optional[DeviceBatch]):
         """One optimisation step on this rank's shard of the global batch.
 
         ``db is None`` = this rank's shard of the global batch is empty (``shard_range`` chunks like
@@ -323,11 +393,20 @@ class Trainer:
         that a resumed run continues the mask sequence instead of replaying it from step 1)."""
         if self.zero is not None:                              # collective: every rank calls it, any rank may save it
             total = self.model.layout.total
-            return {"m": self.zero.gather_full(self.m_sh, total), "v": self.zero.gather_full(self.v_sh, total),
-                    "t": self.t, "dropout_step": self.model.dropout_step, "lr_schedule": self._schedule_state()}
+            return self._ema_state({"m": self.zero.gather_full(self.m_sh, total), "v": self.zero.gather_full(self.v_sh, total),
+                                    "t": self.t, "dropout_step": self.model.dropout_step,
+                                    "lr_schedule": self._schedule_state()})
         self.sync()
-        return {"m": self.m, "v": self.v, "t": self.t, "dropout_step": self.model.dropout_step,
-                "lr_schedule": self._schedule_state()}
+        return self._ema_state({"m": self.m, "v": self.v, "t": self.t, "dropout_step": self.model.dropout_step,
+                                "lr_schedule": self._schedule_state()})
+
+    def _ema_state(self, sd):
+        """With ``ema_decay``: the average, its configuration and the RAW parameters (inside :meth:`averaged` the model -- and
+        so the checkpoint written from it -- holds the averaged ones; a restart needs both).  Copies, not views."""
+        if self.ema is not None:
+            raw = self.model.flat.data if self._raw is None else self._raw
+            sd.update(ema=self.ema.clone(), ema_cfg={"decay": self.ema_cfg[0], "every": self.ema_cfg[1]}, params=raw.clone())
+        return sd
 
     def _schedule_state(self):
         return None if self.lr_schedule is None else self.lr_schedule.as_dict()
@@ -335,7 +414,17 @@ class Trainer:
     def load_state_dict(self, sd):
         """Restores what :meth:`state_dict` holds.  The learning-rate schedule: a Trainer built without one takes the saved
         one (a state without the key was saved by a constant-rate run: nothing to take); a Trainer built WITH one refuses a
-        state saved under a different schedule -- the run would silently continue on another curve."""
+        state saved under a different schedule -- the run would silently continue on another curve.  The weight average: a
+        Trainer built with ``ema_decay`` takes ``"ema"`` and the raw ``"params"`` from a state that has them and refuses one
+        saved under another ``(decay, every)``; from a state without them the average starts at the model's (loaded)
+        parameters.  A Trainer built without it ignores the keys."""
+        if self._raw is not None:
+            raise RuntimeError("Trainer.load_state_dict inside Trainer.averaged()")
+        if self.ema is not None and "ema" in sd:
+            cfg = sd.get("ema_cfg") or {}
+            if (cfg.get("decay"), cfg.get("every")) != self.ema_cfg:
+                raise ValueError("load_state_dict: the state's weight average was kept with (decay, every) = (%r, %r), this "
+                                 "Trainer was built with (%r, %r)" % ((cfg.get("decay"), cfg.get("every")) + self.ema_cfg))
         saved = sd.get("lr_schedule")
         saved = None if saved is None else ops.LrSchedule.make(saved)
         if self.lr_schedule is not None and saved != self.lr_schedule:
@@ -353,3 +442,12 @@ class Trainer:
         if self.row_step is not None:
             self.row_step.fill_(self.t)                          # a checkpoint holds synced tables
         self.model.dropout_step = int(sd.get("dropout_step", self.t))
+        if self.ema is not None:
+            if "ema" in sd:
+                if "params" in sd:
+                    self.model.flat.data.copy_(sd["params"])
+                self.ema.copy_(sd["ema"])
+                self.ema_updates = self.t // self.ema_cfg[1]
+            else:
+                self.ema.copy_(self.model.flat.data)
+                self.ema_updates = 0

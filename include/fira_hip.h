@@ -591,6 +591,24 @@ int fira_train_step_begin_rows(void* stream, const fira_dims* d, const fira_batc
 int fira_train_step_end_rows(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count,
                              int32_t* row_step);
 
+/* Exponential moving average of the weights (csrc/ema.hip; additive, the ABI version is unchanged).  For every element
+ *     diff = p - e;   e = e + w * diff
+ * the subtraction, the multiply and the add each rounded to fp32 on its own (no fused multiply-add), so a loop of np.float32
+ * operations is the reference; an element with p == e keeps its value.  w = (float)(1 - D^K) for a per-step decay D applied
+ * every K steps, formed by the caller in double.  0 <= w <= 1 and finite, else non-zero with the reason in fira_last_error()
+ * and nothing launched.
+ *   fira_ema_update       ema[0, n) toward p[0, n); n >= 1, any 4-byte alignment of either pointer (16-byte accesses where the
+ *                         addresses allow, 4-byte ones at the edges).  ema must not overlap p (refused).
+ *   fira_ema_update_rows  the whole flat buffer [0, fira_param_total(d)) of a model trained with fira_train_step_rows, in one
+ *                         launch: the two vocabulary-sized embedding tables are read as a forward pass reads them -- a row that
+ *                         lags behind adam->step with the zero-gradient updates it owes applied in registers (same adam values
+ *                         as the step that has just run, step = the last completed step) -- so the average is the one a dense
+ *                         Adam would give, bit for bit, WITHOUT fira_adam_rows_sync.  It writes ema only: params, the moments
+ *                         and row_step are read.  ema, params and the moments 16-byte aligned; ema overlaps none of them.   */
+int fira_ema_update(void* stream, int64_t n, float* ema, const float* p, float w);
+int fira_ema_update_rows(void* stream, const fira_dims* d, float* ema, const float* params, const fira_adam_opts* adam,
+                         const int32_t* row_step, float w);
+
 /* Clipping by the GLOBAL gradient norm on the device (torch.nn.utils.clip_grad_norm_ between run_model.py:108 and :111,
  * error_if_nonfinite = False) and a guard against non-finite gradients.  With g the flat loss-SUM gradient of [0, live) and
  * inv = 1 / max(n_tok, 1) (or 1 / max(count, 1), the all-reduced token count of a data-parallel step), for max_norm C > 0

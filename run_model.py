@@ -17,6 +17,7 @@ single-process ``nn.DataParallel``.
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import random
@@ -143,9 +144,16 @@ def parse_args(argv):
                     "given, else epochs x steps per epoch -- counted from the step a --resume starts at)")
     ap.add_argument("--lr-min", type=float, default=None, metavar="X", help="with --lr-schedule cosine|linear: the rate from "
                     "step N on, 0 <= X <= --lr (default 0)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D", help="train: keep an exponential moving average of "
+                    "the weights on the device, per-step decay 0 < D < 1 (for example 0.999); the dev passes run on it and "
+                    "best_model.pt holds it (the raw weights travel in fira_train_state.pt with --save-optimizer)")
+    ap.add_argument("--ema-every", type=int, default=None, metavar="K", help="with --ema-decay: update the average every K-th "
+                    "step by the weight 1 - D^K (default 32, the cadence at which the row-sparse Adam has just written every "
+                    "row; 1 = the per-step average)")
     a = ap.parse_args(argv)
     try:
         check_clip_args(a)
+        check_ema_args(a)
         check_lr_schedule_args(a)
         check_score_args(a)
         check_constraint_args(a)
@@ -171,6 +179,25 @@ def check_clip_args(a):
         raise ValueError("--clip-grad-norm only applies to the train stage")
     if not c > 0:                                            # (also refuses nan)
         raise ValueError("--clip-grad-norm %g: must be > 0 (inf = observe and guard only)" % c)
+    return a
+
+
+def check_ema_args(a):
+    """Validates --ema-decay / --ema-every (no GPU, no DataSet needed); raises ValueError on a conflict or an out-of-range
+    value.  Fills in the default cadence."""
+    if a.ema_decay is None:
+        if a.ema_every is not None:
+            raise ValueError("--ema-every needs --ema-decay")
+        return a
+    if a.stage != "train":
+        raise ValueError("--ema-decay only applies to the train stage")
+    from fira_icse_amd import ops
+    try:
+        ops.ema_check(a.ema_decay, 32 if a.ema_every is None else a.ema_every)
+    except ValueError as e:
+        raise ValueError("--ema-decay / --ema-every: %s" % e)
+    if a.ema_every is None:
+        a.ema_every = 32
     return a
 
 
@@ -538,12 +565,18 @@ class Run:
         wire = a.grad_wire if a.grad_wire != "auto" else ("bf16" if a.dtype == "bf16" else "f32")
         state_path = os.path.join(self.root, "fira_train_state.pt")
         state = torch.load(state_path, map_location=self.model.device_) if a.resume and os.path.exists(state_path) else None
+        if state is not None and "params" in state:
+            # a run with --ema-decay wrote the AVERAGED weights to best_model.pt; training continues from the raw ones
+            self.model.flat.data.copy_(state["params"])
         n_batches = -(-len(store) // cfg.batch_size)
         # (no --lr-schedule: no schedule object, the constant-rate path; a resumed state then brings its own, if it has one)
         schedule = lr_schedule_from_args(a, a.max_steps if a.max_steps else cfg.epoches * n_batches,
                                          int(state["t"]) if state is not None else 0)
         trainer = Trainer(self.model, lr=cfg.lr, distributed=self.world > 1, zero1=a.zero1, grad_wire=wire,
-                          clip_grad_norm=a.clip_grad_norm, lr_schedule=schedule)
+                          clip_grad_norm=a.clip_grad_norm, lr_schedule=schedule,
+                          **({} if a.ema_decay is None else {"ema_decay": a.ema_decay, "ema_every": a.ema_every}))
+        # with --ema-decay the dev passes and every best_model.pt are taken on the averaged weights
+        averaged = contextlib.nullcontext if a.ema_decay is None else trainer.averaged
         if state is not None:
             trainer.load_state_dict(state)                   # (refuses a state saved under another schedule)
             del state
@@ -562,21 +595,22 @@ class Run:
                                device=self.model.device_)
             for idx_b, (gidx, db) in enumerate(batches):
                 if epoch >= a.dev_from_epoch and idx_b % a.dev_every == 0:
-                    cur_bleu, dev_text = self.dev(epoch)
-                    if self.rank == 0:
-                        with open(self.out("train_process"), "a") as f:
-                            f.write("epoch: {} batch: {} dev bleu: {} is better: {}\n".format(
-                                epoch, idx_b, cur_bleu, cur_bleu > best_bleu))
-                    if cur_bleu > best_bleu:
-                        best_bleu = cur_bleu
-                        output_str = dev_text()              # (--dev-on-device: builds the lines now; collective when world > 1)
-                        opt_state = trainer.state_dict() if a.save_optimizer else None     # collective with --zero1
+                    with averaged():
+                        cur_bleu, dev_text = self.dev(epoch)
                         if self.rank == 0:
-                            torch.save(self.model.state_dict(), os.path.join(self.root, "best_model.pt"))
-                            if a.save_optimizer:
-                                torch.save(opt_state, state_path)
-                            with open(self.out("dev_output"), "w") as f:
-                                f.write(output_str)
+                            with open(self.out("train_process"), "a") as f:
+                                f.write("epoch: {} batch: {} dev bleu: {} is better: {}\n".format(
+                                    epoch, idx_b, cur_bleu, cur_bleu > best_bleu))
+                        if cur_bleu > best_bleu:
+                            best_bleu = cur_bleu
+                            output_str = dev_text()          # (--dev-on-device: builds the lines now; collective when world > 1)
+                            opt_state = trainer.state_dict() if a.save_optimizer else None     # collective with --zero1
+                            if self.rank == 0:
+                                torch.save(self.model.state_dict(), os.path.join(self.root, "best_model.pt"))
+                                if a.save_optimizer:
+                                    torch.save(opt_state, state_path)
+                                with open(self.out("dev_output"), "w") as f:
+                                    f.write(output_str)
                     self.model.train(not a.no_dropout)
                 trainer.step(db)                     # db None (empty shard of a short tail batch): still joins the collectives
                 total_data += len(gidx)
@@ -600,16 +634,20 @@ class Run:
                 _, _, n_clipped, n_nonfinite = trainer.last_grad_norm()      # running counts since the start of the run
                 print("epoch: %d  clipped steps so far: %d  non-finite (zero-gradient) steps so far: %d of %d" % (
                     epoch, n_clipped, n_nonfinite, steps), flush=True)
+            if trainer.ema is not None and self.rank == 0:
+                print("epoch: %d  weight-average (EMA) updates so far: %d (step %d)" % (epoch, trainer.ema_updates, trainer.t),
+                      flush=True)
             if scheduled and self.rank == 0:
                 print("epoch: %d  learning rate: %.6g (step %d)" % (epoch, trainer.last_lr() or 0.0, trainer.t), flush=True)
             if a.max_steps and steps >= a.max_steps:
                 break
         if best_bleu < 0:                               # never reached a dev point (short runs): keep the last weights
-            opt_state = trainer.state_dict() if a.save_optimizer else None                 # collective with --zero1
-            if self.rank == 0:
-                torch.save(self.model.state_dict(), os.path.join(self.root, "best_model.pt"))
-                if a.save_optimizer:                     # ... and the optimizer state that belongs to them (--resume)
-                    torch.save(opt_state, state_path)
+            with averaged():
+                opt_state = trainer.state_dict() if a.save_optimizer else None             # collective with --zero1
+                if self.rank == 0:
+                    torch.save(self.model.state_dict(), os.path.join(self.root, "best_model.pt"))
+                    if a.save_optimizer:                 # ... and the optimizer state that belongs to them (--resume)
+                        torch.save(opt_state, state_path)
         return best_bleu
 
     # ------------------------------------------------------------------------------ test (run_model.py:187-380,401-415)
