@@ -13,10 +13,9 @@
 #include <limits.h>
 #include <stdlib.h>
 #include "engine.h"
+#include "decode_row.h"
 
 namespace fira {
-
-constexpr int BEAM_MAX = 8;
 
 __global__ __launch_bounds__(256) void beam_prepare_kernel(int rows, int beam, int T, int step,
                                                            const int32_t* __restrict__ gen,
@@ -43,9 +42,6 @@ __global__ __launch_bounds__(256) void beam_prepare_kernel(int rows, int beam, i
     }
 }
 
-struct Cand { float v; int i; };
-__device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-
 // NB = length of the per-thread candidate list (>= beam: only the `beam` best of a thread can be among the `beam` best of
 // the commit), NT threads per commit.  The result is the exact top-`beam` under the total order (probability descending,
 // flattened index ascending), so it does not depend on NB / NT: round 2 went from 256 threads x 8-deep lists (166 us per
@@ -68,28 +64,15 @@ __global__ __launch_bounds__(NT) void beam_select_kernel(int beam, int T, int W,
     __shared__ float sel_v[BEAM_MAX];
     __shared__ int sel_i[BEAM_MAX], act_slot[BEAM_MAX], order[BEAM_MAX], src_of[BEAM_MAX], tok_of[BEAM_MAX],
         carry_of[BEAM_MAX];
+    static_assert(NT == DDW_NT, "the toolkit's block reductions are those of 1024 threads");
     const int b = blockIdx.x, t = threadIdx.x, r0 = b * beam;
-    if (*done) {                                                     // search over: hand the state on unchanged
-        for (int x = t; x < beam * T; x += NT) gen_out[(size_t)r0 * T + x] = gen_in[(size_t)r0 * T + x];
-        if (t < beam) { len_out[r0 + t] = len_in[r0 + t]; prob_out[r0 + t] = prob_in[r0 + t]; parent[r0 + t] = r0 + t; }
+    if (*done) {
+        pass_through_done(r0, beam, T, gen_in, len_in, prob_in, gen_out, len_out, prob_out, parent);
         return;
     }
     const int n_act = active[BEAM_MAX];
-    // thread-local best `beam` candidates, kept sorted
-    float lv[NB];
-    int li[NB];
-#pragma unroll
-    for (int q = 0; q < NB; ++q) { lv[q] = -INFINITY; li[q] = INT_MAX; }
-    auto offer = [&](float v, int i) {
-        if (!better(v, i, lv[NB - 1], li[NB - 1])) return;
-        lv[NB - 1] = v; li[NB - 1] = i;
-#pragma unroll
-        for (int q = NB - 1; q > 0; --q)
-            if (better(lv[q], li[q], lv[q - 1], li[q - 1])) {
-                const float tv = lv[q]; lv[q] = lv[q - 1]; lv[q - 1] = tv;
-                const int ti = li[q]; li[q] = li[q - 1]; li[q - 1] = ti;
-            }
-    };
+    TopList<NB, Cand> top;                                           // thread-local best `beam` candidates
+    top.clear();
     int k = 0;
     for (int j = 0; j < beam; ++j) {
         if (!active[j]) continue;
@@ -104,39 +87,22 @@ __global__ __launch_bounds__(NT) void beam_select_kernel(int beam, int T, int W,
             for (int u = 0; u < 4; ++u) x[u] = row[min(w0 + u * NT, W - 1)];
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (w0 + u * NT < W) offer(f ? -1.0f : x[u] * pj, k * W + w0 + u * NT);
+                if (w0 + u * NT < W) top.offer({f ? -1.0f : x[u] * pj, k * W + w0 + u * NT});
         }
         ++k;
     }
     if (t == 0) {                                                    // finished hypotheses, slot order, -1 padding (:283-296)
         int c = 0;
         for (int j = 0; j < beam; ++j)
-            if (fin[r0 + j]) { order[c] = j; offer(prob_in[r0 + j], n_act * W + c); ++c; }
-        for (int q = c; q < beam; ++q) { order[q] = 0; offer(-1.0f, n_act * W + q); }
+            if (fin[r0 + j]) { order[c] = j; top.offer({prob_in[r0 + j], n_act * W + c}); ++c; }
+        for (int q = c; q < beam; ++q) { order[q] = 0; top.offer({-1.0f, n_act * W + q}); }
     }
     // `beam` rounds of a block-wide arg-max over the list heads; the owner of the winner pops it
     for (int round = 0; round < beam; ++round) {
-        float v = lv[0];
-        int i = li[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(v, o, 64);
-            const int oi = __shfl_xor(i, o, 64);
-            if (better(ov, oi, v, i)) { v = ov; i = oi; }
-        }
-        __syncthreads();
-        if ((t & 63) == 0) { smv[t >> 6] = v; smi[t >> 6] = i; }
-        __syncthreads();
-        v = smv[0]; i = smi[0];
-#pragma unroll
-        for (int q = 1; q < NT / 64; ++q)
-            if (better(smv[q], smi[q], v, i)) { v = smv[q]; i = smi[q]; }
-        if (t == 0) { sel_v[round] = v; sel_i[round] = i; }
-        if (li[0] == i) {
-#pragma unroll
-            for (int q = 0; q < NB - 1; ++q) { lv[q] = lv[q + 1]; li[q] = li[q + 1]; }
-            lv[NB - 1] = -INFINITY; li[NB - 1] = INT_MAX;
-        }
+        Cand c = top.e[0];
+        block16_argmax(c.v, c.i, smv, smi);
+        if (t == 0) { sel_v[round] = c.v; sel_i[round] = c.i; }
+        if (top.e[0].i == c.i) top.pop();
     }
     __syncthreads();
     if (t < beam) {                                                  // run_model.py:305-340
@@ -144,23 +110,14 @@ __global__ __launch_bounds__(NT) void beam_select_kernel(int beam, int T, int W,
         const int which = idx / W, w = idx - which * W;
         const int carry = which >= n_act;
         const int src = carry ? order[min(w, beam - 1)] : act_slot[which];
-        int nt = w;
-        if (w >= V + L) nt = sub[(size_t)b * S + min(w - V - L, S - 1)];
-        else if (w >= V) nt = sou[(size_t)b * L + (w - V)];
-        src_of[t] = src; tok_of[t] = nt; carry_of[t] = carry;
+        src_of[t] = src; tok_of[t] = entry_word(w, sou, sub, (size_t)b, V, L, S); carry_of[t] = carry;
         const int sl = len_in[r0 + src];
         len_out[r0 + t] = carry ? sl : sl + 1;
         prob_out[r0 + t] = sel_v[t];
         parent[r0 + t] = r0 + src;
     }
     __syncthreads();
-    for (int x = t; x < beam * T; x += NT) {
-        const int c = x / T, p = x - c * T;
-        const int src = src_of[c];
-        int g = gen_in[(size_t)(r0 + src) * T + p];
-        if (!carry_of[c] && p == min(len_in[r0 + src], T - 1)) g = tok_of[c];
-        gen_out[(size_t)(r0 + c) * T + p] = g;
-    }
+    write_hypotheses(r0, beam, T, src_of, tok_of, carry_of, gen_in, len_in, gen_out);
 }
 
 // Greedy (beam 1) and sampling bookkeeping of one step, run_model.py:305-340 with one hypothesis per row: resolve the chosen
@@ -181,11 +138,7 @@ __global__ __launch_bounds__(256) void advance_kernel(int R, int rows_per_commit
     int still = 0;
     if (r < R) {
         if (alive[r]) {
-            const int b = r / rows_per_commit;
-            const int w = best_id[r];
-            int nt = w;
-            if (w >= V + L) nt = sub[(size_t)b * S + min(w - V - L, S - 1)];
-            else if (w >= V) nt = sou[(size_t)b * L + (w - V)];
+            const int nt = entry_word(best_id[r], sou, sub, (size_t)(r / rows_per_commit), V, L, S);
             out[(size_t)r * T + step + 1] = nt;
             prob[r] *= best_p[r];
             if (logp) logp[r] += logf(best_p[r]);

@@ -19,8 +19,8 @@
 // unpenalised key(prob_out, len_out - 1).
 //
 // One workgroup of 1024 threads per commit; the groups are phases inside it.  Per group:
-//   1. every running row of the group is streamed once, exactly as beam.hip does (four loads in flight, nothing behind a branch),
-//      into a thread-local list of the NB best products of the row.  No logarithm is paid per element: within a row all entries
+//   1. every running row of the group is streamed once (four loads in flight, nothing behind a branch) into a thread-local
+//      TopList (decode_row.h) of the NB best products of the row.  No logarithm is paid per element: within a row all entries
 //      share prob[j] and m, so the order by product is the order by unpenalised key.
 //   2. the list entries of the row -- best first -- get their key in fp64 (ln of an fp32 product is then strictly monotone in
 //      it: two fp32 neighbours are 6e-8 apart in ln, the fp64 logarithm errs by 1e-14) and their penalty count, and are offered
@@ -33,24 +33,25 @@
 // pick), so at most n_beam - k + 1 of its entries are penalised.  The list holds NB >= k + (n_beam - k + 1) entries (NB >= k with
 // one group, where nothing is penalised): the thread's k best unpenalised entries are always on it, and a penalised entry that
 // is not on it has k + 1 unpenalised entries of higher product -- hence of higher penalised key -- above it.  The same count
-// gives each thread its slot's word once per commit (constrain.hip): a list entry at or above V is that slot.
+// gives each thread its slot's word once per commit (slot_word): a list entry at or above V is that slot.
 // Void candidates are never offered: a group with r running and k - r finished slots has r * W + (k - r) >= k others.
 // Plain vector stores, no atomics on global memory.
 #include <float.h>
 #include <limits.h>
 #include <math.h>
 #include "engine.h"
+#include "decode_row.h"
 
 namespace fira {
 
-constexpr int BS_BEAM_MAX = 8;
-constexpr int BS_NT = 1024;
-constexpr int BS_MAX_T = 64;
-constexpr int BS_MAX_SLOTS = BS_NT;              // one copy slot per thread and row
+constexpr int BS_NT = DDW_NT;
 
-__device__ __forceinline__ bool bs_better(double ka, float pa, int ia, double kb, float pb, int ib) {
-    return ka > kb || (ka == kb && (pa > pb || (pa == pb && ia < ib)));
-}
+// A candidate of a group: penalised key descending, then Cand's order.
+struct KeyCand {
+    double k; float p; int i;
+    static __device__ __forceinline__ KeyCand none() { return {-INFINITY, -2.0f, INT_MAX}; }        // below every candidate
+    __device__ __forceinline__ bool before(const KeyCand& o) const { return k > o.k || (k == o.k && better(p, i, o.p, o.i)); }
+};
 __device__ __forceinline__ double bs_key(float p, float inv) { return p > 0.0f ? log((double)p) * (double)inv : -INFINITY; }
 
 // NB: length of the per-row product list; KN >= k: length of the thread's list of the group
@@ -65,49 +66,26 @@ __global__ __launch_bounds__(BS_NT) void beam_select_scored_kernel(
     __shared__ double smk[BS_NT / 64];
     __shared__ float smp[BS_NT / 64];
     __shared__ int smi[BS_NT / 64];
-    __shared__ float sel_p[BS_BEAM_MAX];
-    __shared__ int sel_i[BS_BEAM_MAX], order[BS_BEAM_MAX], src_of[BS_BEAM_MAX], tok_of[BS_BEAM_MAX], carry_of[BS_BEAM_MAX],
-        pen_w[BS_BEAM_MAX];
+    __shared__ float sel_p[BEAM_MAX];
+    __shared__ int sel_i[BEAM_MAX], order[BEAM_MAX], src_of[BEAM_MAX], tok_of[BEAM_MAX], carry_of[BEAM_MAX],
+        pen_w[BEAM_MAX];
     __shared__ int s_npen;
     const int b = blockIdx.x, t = threadIdx.x, r0 = b * beam, k = beam / n_groups;
-    if (*done) {                                                     // search over: hand the state on unchanged
-        for (int x = t; x < beam * T; x += BS_NT) gen_out[(size_t)r0 * T + x] = gen_in[(size_t)r0 * T + x];
-        if (t < beam) {
-            const int len = len_in[r0 + t];
-            const float p = prob_in[r0 + t];
-            len_out[r0 + t] = len; prob_out[r0 + t] = p; parent[r0 + t] = r0 + t;
-            if (key_out) key_out[r0 + t] = (float)bs_key(p, inv_lp[min(max(len - 1, 0), T)]);
-        }
+    if (*done) {
+        pass_through_done(r0, beam, T, gen_in, len_in, prob_in, gen_out, len_out, prob_out, parent);
+        if (t < beam && key_out) key_out[r0 + t] = (float)bs_key(prob_in[r0 + t], inv_lp[min(max(len_in[r0 + t] - 1, 0), T)]);
         return;
     }
-    // the word of the one copy slot this thread streams: entry V + s with V + s = t (mod 1024); both requests unconditional
-    const int s = (t - V % BS_NT + BS_NT) % BS_NT;
-    int id_sou = L > 0 ? sou[(size_t)b * L + min(s, L - 1)] : 0;
-    int id_sub = S > 0 ? sub[(size_t)b * S + min(max(s - L, 0), S - 1)] : 0;
-    asm volatile("" : "+v"(id_sou), "+v"(id_sub));
-    const int my_word = s < L ? id_sou : id_sub;
+    // the word of the one copy slot this thread streams: entry V + s with V + s = t (mod 1024)
+    const int my_word = slot_word(sou, sub, (size_t)b, L, S, (t - V % BS_NT + BS_NT) % BS_NT);
     const double lam = (double)diversity;
     if (t == 0) s_npen = 0;
 
-    double kk[KN];
-    float kp[KN];
-    int ki[KN];
-    auto k_offer = [&](double key, float p, int i) {
-        if (!bs_better(key, p, i, kk[KN - 1], kp[KN - 1], ki[KN - 1])) return;
-        kk[KN - 1] = key; kp[KN - 1] = p; ki[KN - 1] = i;
-#pragma unroll
-        for (int q = KN - 1; q > 0; --q)
-            if (bs_better(kk[q], kp[q], ki[q], kk[q - 1], kp[q - 1], ki[q - 1])) {
-                const double tk = kk[q]; kk[q] = kk[q - 1]; kk[q - 1] = tk;
-                const float tp = kp[q]; kp[q] = kp[q - 1]; kp[q - 1] = tp;
-                const int ti = ki[q]; ki[q] = ki[q - 1]; ki[q - 1] = ti;
-            }
-    };
+    TopList<KN, KeyCand> group;
 
     for (int g = 0; g < n_groups; ++g) {
         const int j0 = g * k;
-#pragma unroll
-        for (int q = 0; q < KN; ++q) { kk[q] = -INFINITY; kp[q] = -2.0f; ki[q] = INT_MAX; }      // below every candidate
+        group.clear();
         __syncthreads();                                             // the words of the groups before are listed
         const int npen = s_npen;
         for (int jj = 0; jj < k; ++jj) {
@@ -116,41 +94,30 @@ __global__ __launch_bounds__(BS_NT) void beam_select_scored_kernel(
             const float pj = prob_in[r0 + j];
             const float inv = inv_lp[min(max(len_in[r0 + j], 0), T)];
             const float* row = dist + (size_t)(r0 + j) * W;
-            float lv[NB];
-            int li[NB];
-#pragma unroll
-            for (int q = 0; q < NB; ++q) { lv[q] = -INFINITY; li[q] = INT_MAX; }
-            auto offer = [&](float v, int i) {
-                if (!(v > lv[NB - 1] || (v == lv[NB - 1] && i < li[NB - 1]))) return;
-                lv[NB - 1] = v; li[NB - 1] = i;
-#pragma unroll
-                for (int q = NB - 1; q > 0; --q)
-                    if (lv[q] > lv[q - 1] || (lv[q] == lv[q - 1] && li[q] < li[q - 1])) {
-                        const float tv = lv[q]; lv[q] = lv[q - 1]; lv[q - 1] = tv;
-                        const int ti = li[q]; li[q] = li[q - 1]; li[q - 1] = ti;
-                    }
-            };
-            for (int w0 = t; w0 < W; w0 += 4 * BS_NT) {              // four loads in flight per trip, as beam.hip
+            TopList<NB, Cand> top;
+            top.clear();
+            for (int w0 = t; w0 < W; w0 += 4 * BS_NT) {              // four loads in flight per trip
                 float x[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) x[u] = row[min(w0 + u * BS_NT, W - 1)];
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
-                    if (w0 + u * BS_NT < W) offer(x[u] * pj, w0 + u * BS_NT);
+                    if (w0 + u * BS_NT < W) top.offer({x[u] * pj, w0 + u * BS_NT});
             }
             bool live = true;
 #pragma unroll
             for (int q = 0; q < NB; ++q) {
-                if (live && li[q] != INT_MAX) {
-                    const double uk = bs_key(lv[q], inv);
-                    const int idx = jj * W + li[q];
-                    if (!bs_better(uk, lv[q], idx, kk[KN - 1], kp[KN - 1], ki[KN - 1])) {
+                const Cand c = top.e[q];
+                if (live && c.i != INT_MAX) {
+                    const double uk = bs_key(c.v, inv);
+                    const int idx = jj * W + c.i;
+                    if (!group.admits({uk, c.v, idx})) {
                         live = false;                                // the rest of the row ranks below this entry
                     } else {
-                        const int word = li[q] < V ? li[q] : my_word;
-                        int c = 0;
-                        for (int n = 0; n < npen; ++n) c += pen_w[n] == word;
-                        k_offer(uk - lam * (double)c, lv[q], idx);
+                        const int word = c.i < V ? c.i : my_word;
+                        int n_pen = 0;
+                        for (int n = 0; n < npen; ++n) n_pen += pen_w[n] == word;
+                        group.offer({uk - lam * (double)n_pen, c.v, idx});
                     }
                 }
             }
@@ -161,36 +128,30 @@ __global__ __launch_bounds__(BS_NT) void beam_select_scored_kernel(
                 if (fin[r0 + j0 + jj]) {
                     order[c] = j0 + jj;
                     const float p = prob_in[r0 + j0 + jj];
-                    k_offer(bs_key(p, inv_lp[min(max(len_in[r0 + j0 + jj] - 1, 0), T)]), p, k * W + c);
+                    group.offer({bs_key(p, inv_lp[min(max(len_in[r0 + j0 + jj] - 1, 0), T)]), p, k * W + c});
                     ++c;
                 }
             for (int q = c; q < k; ++q) order[q] = j0;
         }
         // k rounds of a block-wide arg-max over the list heads; the owner of the winner pops it
         for (int round = 0; round < k; ++round) {
-            double v = kk[0];
-            float p = kp[0];
-            int i = ki[0];
+            KeyCand c = group.e[0];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
-                const double ov = __shfl_xor(v, o, 64);
-                const float op = __shfl_xor(p, o, 64);
-                const int oi = __shfl_xor(i, o, 64);
-                if (bs_better(ov, op, oi, v, p, i)) { v = ov; p = op; i = oi; }
+                const KeyCand oc = {__shfl_xor(c.k, o, 64), __shfl_xor(c.p, o, 64), __shfl_xor(c.i, o, 64)};
+                if (oc.before(c)) c = oc;
             }
             __syncthreads();
-            if ((t & 63) == 0) { smk[t >> 6] = v; smp[t >> 6] = p; smi[t >> 6] = i; }
+            if ((t & 63) == 0) { smk[t >> 6] = c.k; smp[t >> 6] = c.p; smi[t >> 6] = c.i; }
             __syncthreads();
-            v = smk[0]; p = smp[0]; i = smi[0];
+            c = {smk[0], smp[0], smi[0]};
 #pragma unroll
-            for (int q = 1; q < BS_NT / 64; ++q)
-                if (bs_better(smk[q], smp[q], smi[q], v, p, i)) { v = smk[q]; p = smp[q]; i = smi[q]; }
-            if (t == 0) { sel_p[j0 + round] = p; sel_i[j0 + round] = i; }
-            if (ki[0] == i) {
-#pragma unroll
-                for (int q = 0; q < KN - 1; ++q) { kk[q] = kk[q + 1]; kp[q] = kp[q + 1]; ki[q] = ki[q + 1]; }
-                kk[KN - 1] = -INFINITY; kp[KN - 1] = -2.0f; ki[KN - 1] = INT_MAX;
+            for (int q = 1; q < BS_NT / 64; ++q) {
+                const KeyCand oc = {smk[q], smp[q], smi[q]};
+                if (oc.before(c)) c = oc;
             }
+            if (t == 0) { sel_p[j0 + round] = c.p; sel_i[j0 + round] = c.i; }
+            if (group.e[0].i == c.i) group.pop();
         }
         __syncthreads();
         if (t < 64) {                                                // (wave-uniform) lanes 0 .. k - 1 resolve the group's picks
@@ -203,9 +164,7 @@ __global__ __launch_bounds__(BS_NT) void beam_select_scored_kernel(
                 const int which = none ? k : idx / W, w = none ? 0 : idx - which * W;
                 const int carry = which >= k;
                 const int src = carry ? order[min(w, k - 1)] : j0 + which;
-                nt = w;
-                if (w >= V + L) nt = sub[(size_t)b * S + min(w - V - L, S - 1)];
-                else if (w >= V) nt = sou[(size_t)b * L + (w - V)];
+                nt = entry_word(w, sou, sub, (size_t)b, V, L, S);
                 src_of[o] = src; tok_of[o] = nt; carry_of[o] = carry;
                 const int sl = len_in[r0 + src];
                 const int lo = carry ? sl : sl + 1;
@@ -222,13 +181,7 @@ __global__ __launch_bounds__(BS_NT) void beam_select_scored_kernel(
         }
     }
     __syncthreads();
-    for (int x = t; x < beam * T; x += BS_NT) {
-        const int c = x / T, p = x - c * T;
-        const int src = src_of[c];
-        int g = gen_in[(size_t)(r0 + src) * T + p];
-        if (!carry_of[c] && p == min(len_in[r0 + src], T - 1)) g = tok_of[c];
-        gen_out[(size_t)(r0 + c) * T + p] = g;
-    }
+    write_hypotheses(r0, beam, T, src_of, tok_of, carry_of, gen_in, len_in, gen_out);
 }
 
 }  // namespace fira
@@ -241,16 +194,16 @@ extern "C" int fira_beam_select_scored(void* stream, const fira_dims* d, int B, 
     using namespace fira;
     FIRA_REQUIRE(d, "fira_beam_select_scored: null dims");
     FIRA_REQUIRE(B > 0, "fira_beam_select_scored: B = %d must be positive", B);
-    FIRA_REQUIRE(n_beam >= 2 && n_beam <= BS_BEAM_MAX, "fira_beam_select_scored: n_beam = %d outside 2..%d", n_beam, BS_BEAM_MAX);
+    FIRA_REQUIRE(n_beam >= 2 && n_beam <= BEAM_MAX, "fira_beam_select_scored: n_beam = %d outside 2..%d", n_beam, BEAM_MAX);
     FIRA_REQUIRE(n_groups >= 1 && n_beam % n_groups == 0, "fira_beam_select_scored: n_groups = %d must be >= 1 and divide n_beam = %d",
                  n_groups, n_beam);
     FIRA_REQUIRE(diversity >= 0.0f && diversity <= FLT_MAX, "fira_beam_select_scored: diversity = %g must be finite and >= 0",
                  (double)diversity);
-    FIRA_REQUIRE(d->tar_len >= 1 && d->tar_len <= BS_MAX_T, "fira_beam_select_scored: tar_len = %d outside 1..%d (inv_lp has tar_len + 1 entries)",
-                 d->tar_len, BS_MAX_T);
-    FIRA_REQUIRE(d->vocab > BS_BEAM_MAX && d->sou_len >= 0 && d->sub_len >= 0 && d->sou_len + d->sub_len <= BS_MAX_SLOTS,
+    FIRA_REQUIRE(d->tar_len >= 1 && d->tar_len <= ROW_MAX_T, "fira_beam_select_scored: tar_len = %d outside 1..%d (inv_lp has tar_len + 1 entries)",
+                 d->tar_len, ROW_MAX_T);
+    FIRA_REQUIRE(d->vocab > BEAM_MAX && d->sou_len >= 0 && d->sub_len >= 0 && d->sou_len + d->sub_len <= ROW_MAX_SLOTS,
                  "fira_beam_select_scored: vocabulary %d / %d memory slots outside %d.. / 0..%d", d->vocab, d->sou_len + d->sub_len,
-                 BS_BEAM_MAX + 1, BS_MAX_SLOTS);
+                 BEAM_MAX + 1, ROW_MAX_SLOTS);
     FIRA_REQUIRE(dist && finished && active && done && sou && sub_token && gen_in && len_in && prob_in && gen_out && len_out &&
                      prob_out && parent && inv_lp,
                  "fira_beam_select_scored: null pointer (key_out alone may be NULL)");

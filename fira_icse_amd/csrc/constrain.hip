@@ -17,22 +17,16 @@
 //      the set positions, the banned ids inside [0, V) and <eos> while m < min_length go to an LDS list (<= 63 + 32 + 1 words).
 //   2. the list marks the bitmap: the generator bit of each word, and the bit of each slot whose source id is in the list
 //      (each thread compares its one id against the list: LDS reads at a wave-uniform address).  LDS atomics only.
-//   3. with best_id / best_p: one streaming pass over the row (16-byte loads between a scalar head and tail, so any row width
-//      and pitch works) that takes a set bit as the value 0 and reduces the arg-max under (value descending, index ascending).
+//   3. with best_id / best_p: one stream_row_marked pass over the row that takes a set bit as the value 0, into an ArgMax.
 //   4. the stores: a thread walks "its" bitmap word and stores one 0.0f per set bit -- plain vector stores, no read of the row.
 //      Without best_id the row is never read at all: the call costs the bitmap, not the 100 KB of the row.
 // A finished row (last id <eos>) has an empty list: nothing is stored and its best is the arg-max of the row as it is.
-#include <limits.h>
 #include "decode_row.h"
 
 namespace fira {
 
-constexpr int CON_T = 64;                       // positions one wave covers
 constexpr int CON_MAX_BAN = 32;
-constexpr int CON_MAX_V = DDW_NPT * DDW_NT;     // 25 600 / 1 024: the limits sample.hip and score.hip state
-constexpr int CON_MAX_SLOTS = DDW_NT;
-constexpr int CON_MAX_BLK = CON_T - 1 + CON_MAX_BAN + 1;
-constexpr int CON_BM_WORDS = (CON_MAX_V + CON_MAX_SLOTS + 31) / 32 + 1;      // + 1: a 4-bit field may straddle into the next word
+constexpr int CON_MAX_BLK = ROW_MAX_T - 1 + CON_MAX_BAN + 1;
 constexpr int CON_EOS = 1;                      // config.EOS
 
 __global__ __launch_bounds__(DDW_NT) void constrain_dist_kernel(int T, int V, int L, int S, int rows_per_commit,
@@ -43,7 +37,7 @@ __global__ __launch_bounds__(DDW_NT) void constrain_dist_kernel(int T, int V, in
                                                                 const int32_t* __restrict__ banned, int n_banned,
                                                                 float* __restrict__ dist, int32_t* __restrict__ best_id,
                                                                 float* __restrict__ best_p) {
-    __shared__ uint32_t s_bm[CON_BM_WORDS];
+    __shared__ uint32_t s_bm[bitmap_words(ROW_MAX_V + ROW_MAX_SLOTS)];
     __shared__ int32_t s_blk[CON_MAX_BLK];
     __shared__ int s_nblk;
     __shared__ float smf[DDW_NT / 64];
@@ -54,10 +48,7 @@ __global__ __launch_bounds__(DDW_NT) void constrain_dist_kernel(int T, int V, in
     const int n_words = (W + 31) / 32;
 
     // ---- 1. requests (unconditional, indices clamped); the bitmap cleared; wave 0 finds the blocked words
-    int src = L > 0 ? sou[b * L + min(tid, L - 1)] : 0;
-    int src_sub = S > 0 ? sub[b * S + min(max(tid - L, 0), S - 1)] : 0;
-    asm volatile("" : "+v"(src), "+v"(src_sub));           // both loads in flight, neither sunk under the select (bleu.hip)
-    src = tid < L ? src : src_sub;
+    const int src = slot_word(sou, sub, b, L, S, tid);
     for (int w = tid; w <= n_words; w += DDW_NT) s_bm[w] = 0;
     if (tid < 64) {                                        // wave-uniform: all of wave 0
         const int len = min(max(length[r], 1), T);
@@ -107,43 +98,12 @@ __global__ __launch_bounds__(DDW_NT) void constrain_dist_kernel(int T, int V, in
     }
 
     float* row = dist + (size_t)r * W;
-    // ---- 3. arg-max of the edited row: scalar head up to a 16-byte boundary, float4 body, scalar tail
+    // ---- 3. arg-max of the edited row
     if (best_id) {
-        float bv = -INFINITY;
-        int bi = INT_MAX;
-        auto offer = [&](float v, int i, unsigned bit) {
-            v = bit ? 0.0f : v;
-            if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-        };
-        const int head = min((int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 2), W);
-        const int nvec = (W - head) >> 2;
-        const int tail0 = head + 4 * nvec;
-        if (tid < head) offer(row[tid], tid, (s_bm[tid >> 5] >> (tid & 31)) & 1u);
-        if (tid >= DDW_NT - 4 && tail0 + (tid - (DDW_NT - 4)) < W) {         // (the last threads: they carry one vector less)
-            const int i = tail0 + (tid - (DDW_NT - 4));
-            offer(row[i], i, (s_bm[i >> 5] >> (i & 31)) & 1u);
-        }
-        const float4* rowv = reinterpret_cast<const float4*>(row + head);
-        for (int v0 = tid; v0 < nvec; v0 += 4 * DDW_NT) {                    // four loads in flight per trip
-            float4 x[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) x[u] = rowv[min(v0 + u * DDW_NT, nvec - 1)];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int v = v0 + u * DDW_NT;
-                if (v < nvec) {
-                    const int i = head + 4 * v;
-                    const uint64_t two = ((uint64_t)s_bm[(i >> 5) + 1] << 32) | s_bm[i >> 5];
-                    const unsigned bits = (unsigned)(two >> (i & 31)) & 15u;
-                    offer(x[u].x, i, bits & 1u);
-                    offer(x[u].y, i + 1, bits & 2u);
-                    offer(x[u].z, i + 2, bits & 4u);
-                    offer(x[u].w, i + 3, bits & 8u);
-                }
-            }
-        }
-        block16_argmax(bv, bi, smf, smi);
-        if (tid == 0) { best_id[r] = bi == INT_MAX ? 0 : bi; best_p[r] = bv; }
+        ArgMax best;
+        stream_row_marked(row, W, tid, s_bm, [&](float v, int i, unsigned blocked) { best.offer(blocked ? 0.0f : v, i); });
+        best.reduce(smf, smi);
+        best.report(best_id, best_p, r);
     }
 
     // ---- 4. the stores: one 0.0f per set bit (bits exist only below W)
@@ -165,23 +125,15 @@ extern "C" int fira_constrain_dist(void* stream, const fira_dims* d, int R, int 
                                    int min_length, const int32_t* banned, int n_banned, float* dist, int32_t* best_id,
                                    float* best_p) {
     using namespace fira;
-    FIRA_REQUIRE(d, "fira_constrain_dist: null dims");
-    FIRA_REQUIRE(R >= 0, "fira_constrain_dist: R = %d is negative", R);
-    FIRA_REQUIRE(rows_per_commit >= 1 && R % rows_per_commit == 0,
-                 "fira_constrain_dist: rows_per_commit = %d must be >= 1 and divide R = %d", rows_per_commit, R);
-    FIRA_REQUIRE(d->tar_len >= 2 && d->tar_len <= CON_T, "fira_constrain_dist: tar_len = %d outside 2..%d (one lane per position)",
-                 d->tar_len, CON_T);
-    FIRA_REQUIRE(d->vocab >= 4 && d->vocab <= CON_MAX_V && d->sou_len >= 0 && d->sub_len >= 0 &&
-                     d->sou_len + d->sub_len <= CON_MAX_SLOTS,
-                 "fira_constrain_dist: vocabulary %d / %d memory slots outside 4..%d / 0..%d", d->vocab, d->sou_len + d->sub_len,
-                 CON_MAX_V, CON_MAX_SLOTS);
+    if (int e = require_row_geometry(d, rows_per_commit, R, best_id, best_p, "fira_constrain_dist")) return e;
+    FIRA_REQUIRE(d->tar_len >= 2 && d->tar_len <= ROW_MAX_T, "fira_constrain_dist: tar_len = %d outside 2..%d (one lane per position)",
+                 d->tar_len, ROW_MAX_T);
     FIRA_REQUIRE(no_repeat_ngram >= 0 && no_repeat_ngram <= d->tar_len, "fira_constrain_dist: no_repeat_ngram = %d outside 0..tar_len = %d",
                  no_repeat_ngram, d->tar_len);
     FIRA_REQUIRE(min_length >= 0 && min_length <= d->tar_len - 2, "fira_constrain_dist: min_length = %d outside 0..tar_len - 2 = %d",
                  min_length, d->tar_len - 2);
     FIRA_REQUIRE(n_banned >= 0 && n_banned <= CON_MAX_BAN, "fira_constrain_dist: n_banned = %d outside 0..%d", n_banned, CON_MAX_BAN);
     FIRA_REQUIRE(n_banned == 0 || banned, "fira_constrain_dist: n_banned = %d without a banned array", n_banned);
-    FIRA_REQUIRE((best_id == nullptr) == (best_p == nullptr), "fira_constrain_dist: best_id and best_p are given together or not at all");
     if (R == 0) return 0;
     FIRA_REQUIRE(gen && length && sou && sub_token && dist, "fira_constrain_dist: null pointer (gen, length, sou, sub_token or dist)");
     hipLaunchKernelGGL(constrain_dist_kernel, dim3(R), dim3(DDW_NT), 0, (hipStream_t)stream, d->tar_len, d->vocab, d->sou_len,

@@ -770,9 +770,8 @@ __global__ __launch_bounds__(256) void decode_dist_reg_kernel(int V, int S, cons
     }
 }
 // The decode loop's form: 1024 threads per hypothesis row (16 waves: the 64 rows of a greedy batch are 64 workgroups, and
-// with 256 threads each a CU ran one wave per SIMD behind 100 dependent-latency loads), the row's logits requested once
-// and kept in registers (25 per thread), and the 2-way gate LinearProb(x) formed here from the decoder row instead of
-// by its own [64 x 2 x 256] product launch.  First-occurrence arg-max as torch.argmax.
+// with 256 threads each a CU ran one wave per SIMD behind 100 dependent-latency loads).  The row is WideRow (decode_row.h):
+// logits in registers, and the 2-way gate formed from the decoder row instead of by its own [64 x 2 x 256] product launch.
 __global__ __launch_bounds__(DDW_NT) void decode_dist_wide_kernel(int V, int S, const float* __restrict__ logits, int ldl,
                                                                   const float* __restrict__ score,
                                                                   const int32_t* __restrict__ mem_valid, int qpk,
@@ -783,59 +782,14 @@ __global__ __launch_bounds__(DDW_NT) void decode_dist_wide_kernel(int V, int S, 
                                                                   int32_t* __restrict__ best_id, float* __restrict__ best_p) {
     __shared__ float smf[DDW_NT / 64];
     __shared__ int smi[DDW_NT / 64];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const rsrc_t rL = buf_rsrc(logits + (size_t)r * ldl, (unsigned)V * 4u);
-    float x[DDW_NPT];
-#pragma unroll
-    for (int i = 0; i < DDW_NPT; ++i) x[i] = buf_load_f32(rL, (unsigned)(tid + DDW_NT * i) * 4u);   // past V: 0, replaced below
-    const float* srow = score + (size_t)r * S;
-    const int32_t* mv = mem_valid + (size_t)(r / qpk) * S;
-    float z0, z1;
-    if (gate_logits) {
-        z0 = gate_logits[2 * r]; z1 = gate_logits[2 * r + 1];
-    } else {                                                   // gate = x wp^T + bp: two 256-long dot products
-        const float xv = tid < FIRA_D ? xrow[(size_t)r * FIRA_D + tid] : 0.f;
-        const float a0 = tid < FIRA_D ? xv * wp[tid] : 0.f, a1 = tid < FIRA_D ? xv * wp[FIRA_D + tid] : 0.f;
-        z0 = block16_sum(a0, smf) + bp[0];
-        z1 = block16_sum(a1, smf) + bp[1];
-    }
-    const float zm = fmaxf(z0, z1);
-    const float e0 = expf(z0 - zm), e1 = expf(z1 - zm);
-    const float g0 = e0 / (e0 + e1), g1 = e1 / (e0 + e1);
-    float cmax = -INFINITY, gmax = -INFINITY;
-    int cidx = 0x7fffffff, gidx = 0x7fffffff;
-    const float sv = tid < S ? (mv[tid] ? srow[tid] : -1e9f) : -INFINITY;       // S <= 1024: one slot per thread
-    if (tid < S) { cmax = sv; cidx = tid; }
-    block16_argmax(cmax, cidx, smf, smi);
-    const float ce = tid < S ? expf(sv - cmax) : 0.f;
-    const float csum = block16_sum(ce, smf);
-#pragma unroll
-    for (int i = 0; i < DDW_NPT; ++i) {                      // ascending index within the thread: first maximum wins
-        const int j = tid + DDW_NT * i;
-        x[i] = j < V ? x[i] : -INFINITY;
-        if (x[i] > gmax) { gmax = x[i]; gidx = j; }
-    }
-    block16_argmax(gmax, gidx, smf, smi);
-    float gsum = 0.f;
-#pragma unroll
-    for (int i = 0; i < DDW_NPT; ++i) {
-        x[i] = expf(x[i] - gmax);                            // exp(-inf) = 0 past V
-        gsum += x[i];
-    }
-    gsum = block16_sum(gsum, smf);
-    if (dist) {
-        float* drow = dist + (size_t)r * (V + S);
-        const float sg = g0 * (1.0f / gsum), sc = g1 * (1.0f / csum);
-        const rsrc_t rD = buf_rsrc(drow, (unsigned)V * 4u);
-#pragma unroll
-        for (int i = 0; i < DDW_NPT; ++i)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sg * x[i]), rD, (unsigned)(tid + DDW_NT * i) * 4u, 0, 0);
-        if (tid < S) drow[V + tid] = sc * ce;
-    }
-    if (tid == 0 && best_id) {
-        const float pg = g0 * (1.0f / gsum), pc = g1 * (1.0f / csum);
-        best_id[r] = pg >= pc ? gidx : V + cidx;
-        if (best_p) best_p[r] = pg >= pc ? pg : pc;
+    const int r = blockIdx.x;
+    WideRow row;
+    row.form(V, S, logits + (size_t)r * ldl, score + (size_t)r * S, mem_valid + (size_t)(r / qpk) * S, r,
+             gate_logits, xrow, wp, bp, smf, smi);
+    if (dist) row.store(dist + (size_t)r * (V + S), V, S);
+    if (threadIdx.x == 0 && best_id) {
+        best_id[r] = row.best(V);
+        if (best_p) best_p[r] = row.best_p();
     }
 }
 int decode_dist(hipStream_t s, int R, int V, int S, const float* logits, int ldl, const float* score,
@@ -844,7 +798,7 @@ int decode_dist(hipStream_t s, int R, int V, int S, const float* logits, int ldl
     ProfScope prof(s, PROF_HEAD, 0.0);
     if (R <= 0) return 0;
     FIRA_REQUIRE(gate_logits || (x && wp && bp), "decode_dist: needs the gate logits or the rows / weights to form them");
-    if (V <= DDW_NPT * DDW_NT && S <= DDW_NT) {      // the 1024-thread kernel wherever the row fits its registers
+    if (V <= ROW_MAX_V && S <= ROW_MAX_SLOTS) {          // the 1024-thread kernel wherever the row fits its registers
         hipLaunchKernelGGL(decode_dist_wide_kernel, dim3(R), dim3(DDW_NT), 0, s, V, S, logits, ldl, score, mem_valid, qpk,
                            gate_logits, x, wp, bp, dist, best_id, best_p);
         FIRA_CHECK_LAUNCH("decode_dist");

@@ -12,7 +12,7 @@
 // renormalised.  A masked slot holds exactly 0.0f and x + 0.0f == x for x >= 0, so mem_valid is not needed.
 //
 // One workgroup of 1024 threads per row, one slot per thread (L + S <= 1024):
-//   1. every thread requests the source id and the probability of "its" slot (indices clamped, nothing behind a branch) and puts
+//   1. every thread requests the source id (slot_word) and the probability of "its" slot (index clamped, no branch) and puts
 //      the pair in LDS (id -1 for a slot that is not folded); with best_id the bitmap of V bits is cleared.  One barrier.
 //   2. every thread requests the generator entry of its id (clamped: the round trip runs under the walk), then walks the slots
 //      0 .. L + S - 1 in order: 8-byte LDS reads at a wave-uniform address.  An equal id BEFORE the thread's slot means the
@@ -20,27 +20,22 @@
 //      in ascending slot order whatever the other waves do.  Waves past the last slot skip the walk.
 //   3. the leader stores acc + dist[r, w] (the word's only read-modify-write: no atomics, the same bits in every run and every
 //      graph replay); every thread with an id inside [0, V) stores its 0.0f.  Plain vector stores.
-//   4. with best_id / best_p: the arg-max of the row AS STORED under (value descending, index ascending), without reading back
-//      the stores of step 3: the leaders mark their generator entry in the bitmap (LDS atomics) and offer (merged value, w); one
-//      streaming pass over the generator part (16-byte loads between a scalar head and tail, so any row alignment works) skips
-//      the marked entries; a slot offers what it holds after the edit: 0.0f, or its own value where it was left alone.
+//   4. with best_id / best_p: the arg-max of the row AS STORED (ArgMax), without reading back the stores of step 3: the leaders
+//      mark their generator entry in the bitmap (LDS atomics) and offer (merged value, w); one stream_row_marked pass over the
+//      generator part skips the marked entries; a slot offers what it holds after the edit: 0.0f, or its own value where it was
+//      left alone.
 // Without best_id the generator part is never streamed: the call costs the slots, not the 100 KB of the row.  There is no
 // finished-row case: fira_beam_select ignores finished rows and fira_greedy_advance ignores rows that are not alive.
-#include <limits.h>
 #include "decode_row.h"
 
 namespace fira {
-
-constexpr int MRG_MAX_V = DDW_NPT * DDW_NT;     // 25 600 / 1 024: the limits constrain.hip, sample.hip and score.hip state
-constexpr int MRG_MAX_SLOTS = DDW_NT;
-constexpr int MRG_BM_WORDS = (MRG_MAX_V + 31) / 32 + 1;                      // + 1: a 4-bit field may straddle into the next word
 
 __global__ __launch_bounds__(DDW_NT) void merge_dist_kernel(int V, int L, int S, int rows_per_commit,
                                                             const int32_t* __restrict__ sou, const int32_t* __restrict__ sub,
                                                             float* __restrict__ dist, int32_t* __restrict__ best_id,
                                                             float* __restrict__ best_p) {
-    __shared__ int2 s_slot[MRG_MAX_SLOTS];                 // (id or -1, the bits of p)
-    __shared__ uint32_t s_bm[MRG_BM_WORDS];
+    __shared__ int2 s_slot[ROW_MAX_SLOTS];                 // (id or -1, the bits of p)
+    __shared__ uint32_t s_bm[bitmap_words(ROW_MAX_V)];
     __shared__ float smf[DDW_NT / 64];
     __shared__ int smi[DDW_NT / 64];
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -49,11 +44,8 @@ __global__ __launch_bounds__(DDW_NT) void merge_dist_kernel(int V, int L, int S,
     float* row = dist + (size_t)r * W;
 
     // ---- 1. requests (unconditional, indices clamped); (id, p) to LDS; the bitmap cleared
-    int src = L > 0 ? sou[b * L + min(tid, L - 1)] : 0;
-    int src_sub = S > 0 ? sub[b * S + min(max(tid - L, 0), S - 1)] : 0;
-    float p = NS > 0 ? row[V + min(tid, NS - 1)] : 0.0f;
-    asm volatile("" : "+v"(src), "+v"(src_sub), "+v"(p));  // all three loads in flight, none sunk under a select (bleu.hip)
-    src = tid < L ? src : src_sub;
+    const float p = NS > 0 ? row[V + min(tid, NS - 1)] : 0.0f;
+    const int src = slot_word(sou, sub, b, L, S, tid);     // (p is requested first: all three loads in flight)
     const bool mine = tid < NS;
     const bool in = mine && src >= 0 && src < V;           // an id outside [0, V) is never used as an index
     s_slot[tid] = make_int2(in ? src : -1, __float_as_int(p));
@@ -87,42 +79,14 @@ __global__ __launch_bounds__(DDW_NT) void merge_dist_kernel(int V, int L, int S,
     __syncthreads();
 
     // ---- 4. arg-max of the stored row: the leaders' values, the slots as they are now, the unmarked generator entries
-    float bv = -INFINITY;
-    int bi = INT_MAX;
-    auto offer = [&](float v, int i) {
-        if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-    };
-    if (lead) offer(merged, w_idx);
-    if (mine) offer(in ? 0.0f : p, V + tid);
-    const int head = min((int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 2), V);
-    const int nvec = (V - head) >> 2;
-    const int tail0 = head + 4 * nvec;
-    if (tid < head && !((s_bm[tid >> 5] >> (tid & 31)) & 1u)) offer(row[tid], tid);
-    if (tid >= DDW_NT - 4 && tail0 + (tid - (DDW_NT - 4)) < V) {             // (the last threads: they carry one vector less)
-        const int i = tail0 + (tid - (DDW_NT - 4));
-        if (!((s_bm[i >> 5] >> (i & 31)) & 1u)) offer(row[i], i);
-    }
-    const float4* rowv = reinterpret_cast<const float4*>(row + head);
-    for (int v0 = tid; v0 < nvec; v0 += 4 * DDW_NT) {                        // four loads in flight per trip
-        float4 x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = rowv[min(v0 + u * DDW_NT, nvec - 1)];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int v = v0 + u * DDW_NT;
-            if (v < nvec) {
-                const int i = head + 4 * v;
-                const uint64_t two = ((uint64_t)s_bm[(i >> 5) + 1] << 32) | s_bm[i >> 5];
-                const unsigned bits = (unsigned)(two >> (i & 31)) & 15u;
-                if (!(bits & 1u)) offer(x[u].x, i);
-                if (!(bits & 2u)) offer(x[u].y, i + 1);
-                if (!(bits & 4u)) offer(x[u].z, i + 2);
-                if (!(bits & 8u)) offer(x[u].w, i + 3);
-            }
-        }
-    }
-    block16_argmax(bv, bi, smf, smi);
-    if (tid == 0) { best_id[r] = bi == INT_MAX ? 0 : bi; best_p[r] = bv; }
+    ArgMax best;
+    if (lead) best.offer(merged, w_idx);
+    if (mine) best.offer(in ? 0.0f : p, V + tid);
+    stream_row_marked(row, V, tid, s_bm, [&](float v, int i, unsigned marked) {
+        if (!marked) best.offer(v, i);
+    });
+    best.reduce(smf, smi);
+    best.report(best_id, best_p, r);
 }
 
 }  // namespace fira
@@ -130,15 +94,7 @@ __global__ __launch_bounds__(DDW_NT) void merge_dist_kernel(int V, int L, int S,
 extern "C" int fira_merge_dist(void* stream, const fira_dims* d, int R, int rows_per_commit, const int32_t* sou,
                                const int32_t* sub_token, float* dist, int32_t* best_id, float* best_p) {
     using namespace fira;
-    FIRA_REQUIRE(d, "fira_merge_dist: null dims");
-    FIRA_REQUIRE(R >= 0, "fira_merge_dist: R = %d is negative", R);
-    FIRA_REQUIRE(rows_per_commit >= 1 && R % rows_per_commit == 0,
-                 "fira_merge_dist: rows_per_commit = %d must be >= 1 and divide R = %d", rows_per_commit, R);
-    FIRA_REQUIRE(d->vocab >= 4 && d->vocab <= MRG_MAX_V && d->sou_len >= 0 && d->sub_len >= 0 &&
-                     d->sou_len + d->sub_len <= MRG_MAX_SLOTS,
-                 "fira_merge_dist: vocabulary %d / %d memory slots outside 4..%d / 0..%d", d->vocab, d->sou_len + d->sub_len,
-                 MRG_MAX_V, MRG_MAX_SLOTS);
-    FIRA_REQUIRE((best_id == nullptr) == (best_p == nullptr), "fira_merge_dist: best_id and best_p are given together or not at all");
+    if (int e = require_row_geometry(d, rows_per_commit, R, best_id, best_p, "fira_merge_dist")) return e;
     if (R == 0) return 0;
     FIRA_REQUIRE(sou && sub_token && dist, "fira_merge_dist: null pointer (sou, sub_token or dist)");
     hipLaunchKernelGGL(merge_dist_kernel, dim3(R), dim3(DDW_NT), 0, (hipStream_t)stream, d->vocab, d->sou_len, d->sub_len,

@@ -12,14 +12,13 @@
 // them in.  The kernel is instantiated per member count, so the struct is indexed by constants only (scalar kernel-argument
 // loads, no scratch) and the member loop is unrolled.
 //
-// One workgroup of 1024 threads per row (merge_dist_kernel's layout).  The row is cut at the 16-byte boundaries of OUT: a scalar
-// head (up to 3 elements), a body of 4-element groups -- one 16-byte store each, and one 16-byte load per member whose row has
-// out's alignment phase (workgroup-uniform), four 4-byte loads otherwise -- and a scalar tail (up to 3 elements).  Two groups
-// per thread are in flight per trip (2 * n_members 16-byte loads).  out may be dists[0]: a thread stores only to elements it has
-// read itself, after reading them.
-// With best_id / best_p: every thread offers what it stores, and one block reduction (value descending, index ascending; NaN is
-// never larger than anything, so it never wins) reports the arg-max of the row as stored.  Without them no reduction runs.
-#include <limits.h>
+// One workgroup of 1024 threads per row.  The row is cut at the 16-byte boundaries of OUT (RowSplit, decode_row.h); the body
+// is this kernel's own, because it reads M rows and stores: per 4-element group one 16-byte store, and one 16-byte load per
+// member whose row has out's alignment phase (workgroup-uniform), four 4-byte loads otherwise.  Two groups per thread are in
+// flight per trip (2 * n_members 16-byte loads).  out may be dists[0]: a thread stores only to elements it has read itself, after
+// reading them.
+// With best_id / best_p: every thread offers what it stores to an ArgMax (NaN never wins), which reports the arg-max of the row as
+// stored.  Without them no reduction runs.
 #include <math.h>
 #include "decode_row.h"
 
@@ -52,9 +51,8 @@ __global__ __launch_bounds__(DDW_NT) void mix_dist_kernel(int W, MixArgs a, floa
     const int r = blockIdx.x, tid = threadIdx.x;
     const size_t off = (size_t)r * W;
     float* orow = out + off;
-    const int head = min((int)(((16u - (unsigned)((uintptr_t)orow & 15u)) & 15u) >> 2), W);
-    const int nvec = (W - head) >> 2;
-    const int tail0 = head + 4 * nvec;
+    const RowSplit c(orow, W);
+    const int head = c.head, nvec = c.nvec;
     const float* row[M];
     bool wide[M];
 #pragma unroll
@@ -63,21 +61,17 @@ __global__ __launch_bounds__(DDW_NT) void mix_dist_kernel(int W, MixArgs a, floa
         wide[m] = ((uintptr_t)(row[m] + head) & 15u) == 0;     // (workgroup-uniform)
     }
 
-    float bv = -INFINITY;
-    int bi = INT_MAX;
-    auto offer = [&](float v, int i) {
-        if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-    };
+    ArgMax best;
     auto scalar = [&](int i) {
         float x[M];
 #pragma unroll
         for (int m = 0; m < M; ++m) x[m] = row[m][i];
         const float y = mix_elem<M>(a, x);
         orow[i] = y;
-        offer(y, i);
+        best.offer(y, i);
     };
     if (tid < head) scalar(tid);
-    if (tid >= DDW_NT - 4 && tail0 + (tid - (DDW_NT - 4)) < W) scalar(tail0 + (tid - (DDW_NT - 4)));
+    if (tid >= DDW_NT - 4 && c.tail_of(tid) < W) scalar(c.tail_of(tid));
 
     for (int v0 = tid; v0 < nvec; v0 += 2 * DDW_NT) {
         float4 x[2][M];
@@ -101,16 +95,16 @@ __global__ __launch_bounds__(DDW_NT) void mix_dist_kernel(int W, MixArgs a, floa
                 for (int m = 0; m < M; ++m) { ex[m] = x[u][m].x; ey[m] = x[u][m].y; ez[m] = x[u][m].z; ew[m] = x[u][m].w; }
                 const float4 y = make_float4(mix_elem<M>(a, ex), mix_elem<M>(a, ey), mix_elem<M>(a, ez), mix_elem<M>(a, ew));
                 *reinterpret_cast<float4*>(orow + i) = y;
-                offer(y.x, i);
-                offer(y.y, i + 1);
-                offer(y.z, i + 2);
-                offer(y.w, i + 3);
+                best.offer(y.x, i);
+                best.offer(y.y, i + 1);
+                best.offer(y.z, i + 2);
+                best.offer(y.w, i + 3);
             }
         }
     }
     if (!best_id) return;                                      // (workgroup-uniform)
-    block16_argmax(bv, bi, smf, smi);
-    if (tid == 0) { best_id[r] = bi == INT_MAX ? 0 : bi; best_p[r] = bv; }
+    best.reduce(smf, smi);
+    best.report(best_id, best_p, r);
 }
 
 template <int M>
@@ -130,7 +124,7 @@ extern "C" int fira_mix_dist(void* stream, int R, int W, int n_members, const fl
     for (int m = 0; m < n_members; ++m)
         FIRA_REQUIRE(isfinite(weights[m]) && weights[m] >= 0.0f, "fira_mix_dist: weight %d = %g is negative or not finite", m,
                      (double)weights[m]);
-    FIRA_REQUIRE((best_id == nullptr) == (best_p == nullptr), "fira_mix_dist: best_id and best_p are given together or not at all");
+    if (int e = require_best_pair(best_id, best_p, "fira_mix_dist")) return e;
     if (R == 0) return 0;
     FIRA_REQUIRE(out, "fira_mix_dist: null pointer (out)");
     const size_t n = (size_t)R * W;

@@ -1,9 +1,7 @@
 // On-device sampling of the decode step's output distribution: temperature, top-k and top-p, drawn by Gumbel-max.
 //
-// One workgroup of 1024 threads per (commit, sample) row, in the register-resident form of decode_dist_wide_kernel
-// (copyhead.hip): the row's V generator logits are requested once and stay in registers (25 per thread), the S <= 1024
-// copy slots are one per thread.  The kernel forms the same distribution p over V + S entries with the same arithmetic in
-// the same order, so the optional `dist` row and `best_p` are bit-identical to what fira_decode_step writes.  Then:
+// One workgroup of 1024 threads per (commit, sample) row.  The row is WideRow (decode_row.h), the distribution p over V + S
+// entries that fira_decode_step writes; the optional `dist` row is stored from it.  What this kernel adds:
 //   top-k   tau_k = the k-th largest p counted with multiplicity: the largest t with #{p_i >= t} >= k
 //   top-p   over the entries top-k kept, w_i = p_i^(1/T) (relative to the row's maximum); tau_p = the largest t with
 //           sum{w_i : p_i >= t} >= top_p * sum{w_i}; both thresholds live in p-space (p -> p^(1/T) is monotone), and
@@ -40,56 +38,15 @@ __global__ __launch_bounds__(DDW_NT) void sample_dist_kernel(int V, int S, const
     __shared__ float smf[DDW_NT / 64];
     __shared__ int smi[DDW_NT / 64];
     const int r = blockIdx.x, tid = threadIdx.x;
-    const rsrc_t rL = buf_rsrc(logits + (size_t)r * ldl, (unsigned)V * 4u);
-    float x[DDW_NPT];
-#pragma unroll
-    for (int i = 0; i < DDW_NPT; ++i) x[i] = buf_load_f32(rL, (unsigned)(tid + DDW_NT * i) * 4u);   // past V: 0, replaced below
-    const float* srow = score + (size_t)r * S;
-    const int32_t* mv = mem_valid + (size_t)(r / n_sample) * S;
-    // ---- the distribution: decode_dist_wide_kernel's arithmetic, operation for operation
-    float z0, z1;
-    {                                                          // gate = x wp^T + bp: two 256-long dot products
-        const float xv = tid < FIRA_D ? xrow[(size_t)r * FIRA_D + tid] : 0.f;
-        const float a0 = tid < FIRA_D ? xv * wp[tid] : 0.f, a1 = tid < FIRA_D ? xv * wp[FIRA_D + tid] : 0.f;
-        z0 = block16_sum(a0, smf) + bp[0];
-        z1 = block16_sum(a1, smf) + bp[1];
-    }
-    const float zm = fmaxf(z0, z1);
-    const float e0 = expf(z0 - zm), e1 = expf(z1 - zm);
-    const float g0 = e0 / (e0 + e1), g1 = e1 / (e0 + e1);
-    float cmax = -INFINITY, gmax = -INFINITY;
-    int cidx = 0x7fffffff, gidx = 0x7fffffff;
-    const float sv = tid < S ? (mv[tid] ? srow[tid] : -1e9f) : -INFINITY;       // S <= 1024: one slot per thread
-    if (tid < S) { cmax = sv; cidx = tid; }
-    block16_argmax(cmax, cidx, smf, smi);
-    const float ce = tid < S ? expf(sv - cmax) : 0.f;
-    const float csum = block16_sum(ce, smf);
-#pragma unroll
-    for (int i = 0; i < DDW_NPT; ++i) {
-        const int j = tid + DDW_NT * i;
-        x[i] = j < V ? x[i] : -INFINITY;
-        if (x[i] > gmax) { gmax = x[i]; gidx = j; }
-    }
-    block16_argmax(gmax, gidx, smf, smi);
-    float gsum = 0.f;
-#pragma unroll
-    for (int i = 0; i < DDW_NPT; ++i) {
-        x[i] = expf(x[i] - gmax);                            // exp(-inf) = 0 past V
-        gsum += x[i];
-    }
-    gsum = block16_sum(gsum, smf);
-    const float sg = g0 * (1.0f / gsum), sc = g1 * (1.0f / csum);
+    WideRow row;
+    row.form(V, S, logits + (size_t)r * ldl, score + (size_t)r * S, mem_valid + (size_t)(r / n_sample) * S, r, nullptr, xrow, wp,
+             bp, smf, smi);
+    if (dist) row.store(dist + (size_t)r * (V + S), V, S);
+    const float sg = row.sg, sc = row.sc;
+    float(&x)[DDW_NPT] = row.x;
 #pragma unroll
     for (int i = 0; i < DDW_NPT; ++i) x[i] = sg * x[i];      // p of entry tid + 1024 i
-    float pc = sc * ce;                                      // p of entry V + tid
-    if (dist) {
-        float* drow = dist + (size_t)r * (V + S);
-        const rsrc_t rD = buf_rsrc(drow, (unsigned)V * 4u);
-#pragma unroll
-        for (int i = 0; i < DDW_NPT; ++i)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, x[i]), rD, (unsigned)(tid + DDW_NT * i) * 4u, 0, 0);
-        if (tid < S) drow[V + tid] = pc;
-    }
+    float pc = sc * row.ce;                                  // p of entry V + tid
     // entries past V / S: p = -1, below every threshold t >= 0 (the bits of a non-negative float order like its value)
 #pragma unroll
     for (int i = 0; i < DDW_NPT; ++i) x[i] = tid + DDW_NT * i < V ? x[i] : -1.f;
@@ -166,9 +123,9 @@ int sample_dist(hipStream_t s, int R, int n_sample, int V, int S, const float* l
                 int32_t* best_id, float* best_p) {
     ProfScope prof(s, PROF_HEAD, 0.0);
     if (R <= 0) return 0;
-    FIRA_REQUIRE(V <= DDW_NPT * DDW_NT && S <= DDW_NT,
-                 "sample_dist: vocabulary %d / %d memory slots exceed the register-resident row (%d / %d)", V, S,
-                 DDW_NPT * DDW_NT, DDW_NT);
+    FIRA_REQUIRE(V <= ROW_MAX_V && S <= ROW_MAX_SLOTS,
+                 "sample_dist: vocabulary %d / %d memory slots exceed the register-resident row (%d / %d)", V, S, ROW_MAX_V,
+                 ROW_MAX_SLOTS);
     hipLaunchKernelGGL(sample_dist_kernel, dim3(R), dim3(DDW_NT), 0, s, V, S, logits, ldl, score, mem_valid, n_sample, x, wp,
                        bp, T, step, key, seed_dev, 1.0f / temperature, top_k, top_p, dist, best_id, best_p);
     FIRA_CHECK_LAUNCH("sample_dist");

@@ -169,6 +169,72 @@ def test_ids_all_out_of_range_leave_every_bit_alone(geometry):
     assert torch.equal(bits(got), bits(dist))
 
 
+def editors_case():
+    """7 rows of the SMALL geometry on which merge, constrain and mix have nothing to edit: every slot id out of range, no
+    constraint, mix weights (1, 0).  The arg-max is placed per row: the first element, the last one, a slot, a generator / slot
+    tie, a tie across the generator / slot border, a tie inside one 16-byte group; row 6 is left as drawn."""
+    V, L, S = SMALL
+    rng = np.random.RandomState(11)
+    dist = rng.uniform(1e-6, 1.0, size=(7, V + L + S)).astype(np.float32)
+    ties = {2: (7, V + L + 1), 3: (V - 1, V), 5: (11, 12)}
+    for r, where in {0: (0,), 1: (V + L + S - 1,), 4: (V + 1,), **ties}.items():
+        dist[r, list(where)] = np.float32(2.0)
+    ids = rng.choice((V, -1, V + 3, -(1 << 31)), size=(7, L + S)).astype(np.int32)
+    return dist, np.ascontiguousarray(ids[:, :L]), np.ascontiguousarray(ids[:, L:]), ties
+
+
+def test_merge_constrain_and_mix_agree_where_none_of_them_edits():
+    """The three kernels that stream a row for its arg-max, held against one another and against the numpy arg-max, with rows
+    beginning at every 16-byte phase (W = 45, buffer offsets 0..3)."""
+    dist, sou, sub, ties = editors_case()
+    n_rows, W = dist.shape
+    best = [M.argmax_ref(dist[r]) for r in range(n_rows)]
+    want_id, want_p = [b[0] for b in best], np.array([b[1] for b in best], dtype=np.float32)
+    for r in range(n_rows):                                   # (on the reference alone) unique, or the constructed lower-index tie
+        at = np.flatnonzero(dist[r] == want_p[r]).tolist()
+        assert at == (list(ties[r]) if r in ties else [want_id[r]]), (r, at)
+    dev = "cuda"
+    dd = device_dims(SMALL)
+    gen = torch.zeros((n_rows, dd.tar_len), dtype=torch.int32, device=dev)
+    gen[:, 0] = START
+    length = torch.ones(n_rows, dtype=torch.int32, device=dev)
+    sou_d, sub_d = torch.from_numpy(sou).to(dev), torch.from_numpy(sub).to(dev)
+    for offset in range(4):
+        def buffer(fill):
+            buf = torch.zeros(n_rows * W + offset + 8, dtype=torch.float32, device=dev)
+            view = buf[offset:offset + n_rows * W].view(n_rows, W)
+            if fill is not None:
+                view.copy_(torch.from_numpy(fill))
+            return buf, view
+        got = {}
+        for name in ("merge", "constrain", "mix"):
+            buf, row = buffer(dist)
+            bid = torch.full((n_rows,), -7, dtype=torch.int32, device=dev)
+            bp = torch.full((n_rows,), -7.0, dtype=torch.float32, device=dev)
+            if name == "merge":
+                rc = _lib.lib().fira_merge_dist(_lib.cur_stream(), C.byref(dd), n_rows, 1, _lib.ptr(sou_d), _lib.ptr(sub_d), _lib.ptr(row),
+                                                _lib.ptr(bid), _lib.ptr(bp))
+            elif name == "constrain":
+                rc = _lib.lib().fira_constrain_dist(_lib.cur_stream(), C.byref(dd), n_rows, 1, _lib.ptr(gen), _lib.ptr(length),
+                                                    _lib.ptr(sou_d), _lib.ptr(sub_d), 0, 0, None, 0, _lib.ptr(row), _lib.ptr(bid), _lib.ptr(bp))
+            else:
+                (zbuf, zeros), (buf, out) = buffer(None), buffer(None)
+                ptrs = (C.c_void_p * 2)(row.data_ptr(), zeros.data_ptr())
+                rc = _lib.lib().fira_mix_dist(_lib.cur_stream(), n_rows, W, 2, ptrs, (C.c_float * 2)(1.0, 0.0), _lib.ptr(out),
+                                              _lib.ptr(bid), _lib.ptr(bp))
+                row = out
+            _lib.check(rc, "fira_%s_dist" % name)
+            torch.cuda.synchronize()
+            assert float(buf[:offset].abs().sum()) == 0 and float(buf[offset + n_rows * W:].abs().sum()) == 0, (name, offset)
+            assert torch.equal(bits(row.cpu()), bits(dist)), (name, offset)
+            got[name] = (bid.cpu().tolist(), bits(bp.cpu()))
+        for name, (gid, gp) in got.items():
+            assert gid == want_id, (name, offset, gid)
+            assert torch.equal(gp, bits(want_p)), (name, offset)
+        assert got["merge"][0] == got["constrain"][0] == got["mix"][0]
+        assert torch.equal(got["merge"][1], got["constrain"][1]) and torch.equal(got["merge"][1], got["mix"][1])
+
+
 # ------------------------------------------------------------------------------------------------ through the model
 CON = Constraints(2, 3, (UNK,))
 
