@@ -665,6 +665,14 @@ int linear_x3(hipStream_t s, int M, const float* X, int ldx, const uint16_t* Wx,
     return 0;
 }
 
+// one launch of the fused kernel `Kernel` (forward or backward) with its > 64 KB dynamic LDS request allowed first
+template <auto Kernel, typename Args>
+static int comb_fused_launch(hipStream_t s, size_t lds, const Args& a) {
+    if (int rc = raise_dynamic_lds<Kernel>(lds, "comb_fused")) return rc;
+    hipLaunchKernelGGL(Kernel, dim3(CF_GRID), dim3(CF_WAVES * 64), lds, s, a);
+    return 0;
+}
+
 int comb_fused_fwd(hipStream_t s, int n_rows, const float* Xc, const float* WqT, const float* WkT, const float* WoT,
                    const float* bqk, const float* bo, const float* vtab, int ldv, const int32_t* mark, float* qk, float* c,
                    const float* gamma, const float* beta, float* sum, float* y, const int32_t* y_rows, float* stats,
@@ -682,24 +690,13 @@ int comb_fused_fwd(hipStream_t s, int n_rows, const float* Xc, const float* WqT,
     a.mark = mark; a.qk = qk; a.c = c; a.gamma = gamma; a.beta = beta; a.sum = sum; a.y = y; a.stats = stats; a.y_rows = y_rows;
     a.p = dropout; a.inv_keep = dropout > 0.f ? 1.0f / (1.0f - dropout) : 1.0f; a.seed = seed; a.site_gate = site_gate;
     a.site_out = site_out;
-    static const int attr = [] {
-        hipError_t e = hipFuncSetAttribute((const void*)comb_fused_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF_LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)comb_fused_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF_LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)comb_fused_fwd_kernel<false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF_LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)comb_fused_fwd_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF_LDS);
-        return e == hipSuccess ? 0 : set_err("comb_fused: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    }();
-    if (attr) return attr;
+    int rc;
     if (Wx) {                            // bf16 planes (Wx: planes of Wq | Wk | Wo as stored): three terms in fp32 mode, one in bf16 mode
         a.WqT = reinterpret_cast<const float*>(Wx);
-        if (bf16) hipLaunchKernelGGL((comb_fused_fwd_kernel<false, 1>), dim3(CF_GRID), dim3(CF_WAVES * 64), CF_LDS, s, a);
-        else hipLaunchKernelGGL((comb_fused_fwd_kernel<false, 3>), dim3(CF_GRID), dim3(CF_WAVES * 64), CF_LDS, s, a);
+        rc = bf16 ? comb_fused_launch<comb_fused_fwd_kernel<false, 1>>(s, CF_LDS, a) : comb_fused_launch<comb_fused_fwd_kernel<false, 3>>(s, CF_LDS, a);
     } else
-    if (bf16) hipLaunchKernelGGL(comb_fused_fwd_kernel<true>, dim3(CF_GRID), dim3(CF_WAVES * 64), CF_LDS, s, a);
-    else hipLaunchKernelGGL(comb_fused_fwd_kernel<false>, dim3(CF_GRID), dim3(CF_WAVES * 64), CF_LDS, s, a);
+    rc = bf16 ? comb_fused_launch<comb_fused_fwd_kernel<true>>(s, CF_LDS, a) : comb_fused_launch<comb_fused_fwd_kernel<false>>(s, CF_LDS, a);
+    if (rc) return rc;
     FIRA_CHECK_LAUNCH("comb_fused_fwd");
     return 0;
 }
@@ -970,35 +967,20 @@ int comb_fused_bwd(hipStream_t s, int n_rows, float* dG, const int32_t* rows, co
     a.vtab = vtab; a.ldv = ldv; a.mark = mark; a.dYc = dYc; a.dqk = dqk; a.part_ln = part_ln; a.part_v = part_v;
     a.p = dropout; a.inv_keep = dropout > 0.f ? 1.0f / (1.0f - dropout) : 1.0f; a.seed = seed; a.site_gate = site_gate;
     a.site_out = site_out;
-    static const int attr = [] {
-        hipError_t e = hipFuncSetAttribute((const void*)comb_fused_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF_LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)comb_fused_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF_LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)comb_fused_bwd_kernel<false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CB_LDS_X3);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)comb_fused_bwd_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CB_LDS_X3);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)comb_fused_bwd_kernel<false, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CB_LDS_X3_2);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)comb_fused_bwd_kernel<false, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CB_LDS_X3_2);
-        return e == hipSuccess ? 0 : set_err("comb_fused: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    }();
-    if (attr) return attr;
+    int rc;
     if (WTx) {                           // bf16 planes (WTx: planes of Wq^T | Wk^T | Wo^T): three terms in fp32 mode, one in bf16 mode
         a.Wo = reinterpret_cast<const float*>(WTx);
         // two tiles per pass once some workgroup has more than one tile (every pass streams 1.15 MB of weight planes through
         // the CU): +1.1 % at fp32 batch 64, +0.9 % in bf16 at batch 64 (profiles/r6_probes.md)
         const int n_tiles = (n_rows + CF_TILE - 1) / CF_TILE;
-        if (n_tiles > CF_GRID) {
-            if (bf16) hipLaunchKernelGGL((comb_fused_bwd_kernel<false, 1, 2>), dim3(CF_GRID), dim3(CF_WAVES * 64), CB_LDS_X3_2, s, a);
-            else hipLaunchKernelGGL((comb_fused_bwd_kernel<false, 3, 2>), dim3(CF_GRID), dim3(CF_WAVES * 64), CB_LDS_X3_2, s, a);
-        } else
-        if (bf16) hipLaunchKernelGGL((comb_fused_bwd_kernel<false, 1>), dim3(CF_GRID), dim3(CF_WAVES * 64), CB_LDS_X3, s, a);
-        else hipLaunchKernelGGL((comb_fused_bwd_kernel<false, 3>), dim3(CF_GRID), dim3(CF_WAVES * 64), CB_LDS_X3, s, a);
+        if (n_tiles > CF_GRID)
+            rc = bf16 ? comb_fused_launch<comb_fused_bwd_kernel<false, 1, 2>>(s, CB_LDS_X3_2, a)
+                      : comb_fused_launch<comb_fused_bwd_kernel<false, 3, 2>>(s, CB_LDS_X3_2, a);
+        else
+            rc = bf16 ? comb_fused_launch<comb_fused_bwd_kernel<false, 1>>(s, CB_LDS_X3, a) : comb_fused_launch<comb_fused_bwd_kernel<false, 3>>(s, CB_LDS_X3, a);
     } else
-    if (bf16) hipLaunchKernelGGL(comb_fused_bwd_kernel<true>, dim3(CF_GRID), dim3(CF_WAVES * 64), CF_LDS, s, a);
-    else hipLaunchKernelGGL(comb_fused_bwd_kernel<false>, dim3(CF_GRID), dim3(CF_WAVES * 64), CF_LDS, s, a);
+    rc = bf16 ? comb_fused_launch<comb_fused_bwd_kernel<true>>(s, CF_LDS, a) : comb_fused_launch<comb_fused_bwd_kernel<false>>(s, CF_LDS, a);
+    if (rc) return rc;
     FIRA_CHECK_LAUNCH("comb_fused_bwd");
     return 0;
 }

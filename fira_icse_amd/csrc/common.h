@@ -1,6 +1,7 @@
 // Shared device/host helpers for libfira_hip (gfx950 only; wavefront = 64).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -25,6 +26,21 @@ int set_err(const char* fmt, ...);
     do {                                                                          \
         if (!(cond)) return fira::set_err(__VA_ARGS__);                           \
     } while (0)
+
+// A kernel that asks for more dynamic LDS than the 64 KB default needs its limit raised first, on every device it is launched
+// on (the attribute belongs to the device's copy of the kernel).  Call ahead of the launch: success is remembered per device
+// ordinal (the launch path pays one relaxed load), a failure is reported as `name: cannot raise ...` and tried again next time.
+template <auto Kernel>
+static inline int raise_dynamic_lds(size_t bytes, const char* name) {
+    static std::atomic<uint64_t> raised{0};                   // bit d: done on device d (ordinals past 63 are not remembered)
+    int dev = 0;
+    const uint64_t bit = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 ? 1ull << dev : 0;
+    if (raised.load(std::memory_order_relaxed) & bit) return 0;
+    const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return set_err("%s: cannot raise the dynamic LDS limit: %s", name, hipGetErrorString(e));
+    raised.fetch_or(bit, std::memory_order_relaxed);
+    return 0;
+}
 
 // ---------------------------------------------------------------- per-kernel-class event profiling
 // Off by default (one relaxed bool test per launch).  When enabled (fira_prof_enable), every launcher brackets

@@ -210,28 +210,65 @@ static int zero(hipStream_t s, void* p, size_t bytes) {
     return 0;
 }
 
-// Compute dtype of the model-level entry points (fira_train_opts.dtype / the dtype argument of fira_forward_dev):
-// 0 = fp32 MFMA (the reference's arithmetic), 1 = bf16 MFMA with fp32 accumulation and fp32 storage (BASELINE
-// configs[2]).  Only the nn.Linear products switch; LayerNorm, soft-max, the gate, the loss and Adam stay fp32, and
-// so do the products on parameters alone (the folded GCN weights) and the tiny ones gemm_bf16_ex forwards.
-static thread_local int g_dtype = 0;
-static thread_local int g_lanes = 1;            // commit-lanes of the running decoder pass (decoder_lanes)
-struct DtypeScope {
-    int prev;
-    explicit DtypeScope(int d) : prev(g_dtype) { g_dtype = d; }
-    ~DtypeScope() { g_dtype = prev; }
+// Deferred column reductions of the backward pass (rowops.hip: deferred_reduce): kernels park one partial row per
+// workgroup in Plan::red_buf; the table is flushed (ONE launch) before the mid-event for the decoder-side parameters
+// and at the end of the backward pass for the encoder-side ones.
+struct RedCollector {
+    float* buf = nullptr;
+    size_t cap = 0, used = 0;
+    RedTable tab;
+    void reset(float* b, size_t c) { buf = b; cap = c; used = 0; tab.n = 0; }
+    // nullptr: no room (floats, or the `entries` table rows the caller is going to add()) -> the kernel falls back to atomics
+    float* alloc(size_t n, int entries = 4) {
+        if (!buf || used + n > cap || tab.n + entries > RED_MAX) return nullptr;
+        float* p = buf + used;
+        used += (n + 63) / 64 * 64;
+        return p;
+    }
+    void add(float* dst, const float* src, int width, int n_part, int stride) {
+        tab.e[tab.n++] = RedEntry{dst, src, width, n_part, stride};
+    }
 };
-// bf16 weight shadows of the current call (workspace-resident, refreshed by one launch at the start of the call):
-// [g_P, g_P + g_total) is the fp32 parameter buffer they mirror, at identical offsets
-static thread_local const float* g_P = nullptr;
-static thread_local int64_t g_total = 0;
-static thread_local const uint16_t* g_Wb = nullptr;
-static thread_local const uint16_t* g_WbT = nullptr;
-static thread_local const ShadowTable* g_tab = nullptr;
-static thread_local const float* g_W21 = nullptr;          // folded GCN weights [nl, 256, 256] (workspace) and their shadows
-static thread_local int64_t g_W21n = 0;
-static thread_local const uint16_t* g_W21b = nullptr;
-static thread_local const uint16_t* g_W21bT = nullptr;
+// GCN layer as one fused launch per direction (gcn_fused.hip) instead of SpMM + product + add-LayerNorm (forward) /
+// product + SpMM (backward), where the batch's density allows (round 6): the fused kernels' gather is built for FIRA's graphs
+// (3-4 entries per computed row, the first 16 of a row in one batched round trip); rows beyond 16 entries take a 64-at-a-time
+// tail loop per row, and on BASELINE config 5's graphs (116 entries per row) the fused forward costs 518 us against 319 us for
+// aggregation + product + row kernel (bench.py: gcn_cfg5).  Batches averaging more than GCN_FUSED_MAX_DEG entries per computed
+// row run the separate kernels (Call::dense_graphs).
+// (The backward pass was measured unfused too -- V = A_hat dY by the CSR kernel, dX += V W21 by the product -- in bf16 at batch
+// 64, where the product is a few microseconds of MFMA time and the fused launch's phase latencies are exposed: 16 239 / 16 203
+// commits/s fused against 16 110 / 15 982.  Both directions follow the same rule.)
+static constexpr double GCN_FUSED_MAX_DEG = 48.0;
+static inline bool graphs_dense(const fira_batch* b) {
+    return b->n_nodes > 0 && (double)b->nnz > GCN_FUSED_MAX_DEG * (double)b->n_nodes;
+}
+// The mode every launch helper below depends on, owned by the call that runs them: a member of the call's Ctx (a step pending
+// between fira_train_step_begin and _end keeps its own in the copied Ctx), a local of the op-level entries and the decode step.
+// What stays thread-local in this file is per-thread resource or ABI state, not per-call mode: side() (the library's streams and
+// event pool), wait_probe() and g_pending; so are the queue builders inside gemm_f32.hip / gemm_bf16.hip / gemm_wgrad_panel.hip.
+struct Call {
+    // Compute dtype (fira_train_opts.dtype / the dtype argument of fira_forward_dev and the op-level entries): 0 = fp32 MFMA
+    // (the reference's arithmetic), 1 = bf16 MFMA with fp32 accumulation and fp32 storage (BASELINE configs[2]).  Only the
+    // nn.Linear products switch; LayerNorm, soft-max, the gate, the loss and Adam stay fp32, and so do the products on
+    // parameters alone (the folded GCN weights) and the tiny ones gemm_bf16_ex forwards.
+    int dtype = 0;
+    int lanes = 1;                    // commit-lanes of the running decoder pass: one until decoder_lanes decides
+    bool dense_graphs = false;        // the batch's graphs are too dense for the fused GCN kernels (graphs_dense)
+    // bf16 weight shadows (workspace-resident, refreshed by one launch at the start of the call): [P, P + total) is the fp32
+    // parameter buffer they mirror, at identical offsets.  Wb == nullptr: no shadows (fp32 mode)
+    const float* P = nullptr;
+    int64_t total = 0;
+    const uint16_t *Wb = nullptr, *WbT = nullptr;
+    const ShadowTable* tab = nullptr;
+    const float* W21 = nullptr;       // folded GCN weights [nl, 256, 256] (workspace) and their shadows (encoder_forward)
+    int64_t W21n = 0;
+    const uint16_t *W21b = nullptr, *W21bT = nullptr;
+    RedCollector red;                 // deferred column reductions of the backward pass
+    void shadows(const float* P_, int64_t total_, const uint16_t* wb, const uint16_t* wbt, const ShadowTable* t) {
+        P = P_; total = total_; Wb = wb; WbT = wbt; tab = t;
+    }
+    bool gcn_fused() const { return !dense_graphs; }
+};
 
 // every 2-D weight a GEMM of the training / dev path reads, in the shapes the engine multiplies them in
 static const ShadowTable* shadow_table(const Layout& L) {
@@ -271,47 +308,38 @@ static const ShadowTable* shadow_table(const Layout& L) {
     return t;
 }
 static int64_t shadow_wbt_elems(const Layout& L) { return shadow_table(L)->wbt_elems; }
-struct ShadowScope {            // publishes / withdraws the shadows of the running call
-    ShadowScope(const float* P, int64_t total, const uint16_t* wb, const uint16_t* wbt, const ShadowTable* tab) {
-        g_P = P; g_total = total; g_Wb = wb; g_WbT = wbt; g_tab = tab;
-    }
-    ~ShadowScope() {
-        g_P = nullptr; g_total = 0; g_Wb = nullptr; g_WbT = nullptr; g_tab = nullptr;
-        g_W21 = nullptr; g_W21n = 0; g_W21b = nullptr; g_W21bT = nullptr;
-    }
-};
 // shadow of the weight (or contiguous row slice of a weight) starting at W: as stored, or transposed (+ its row pitch)
-static bool shadow_of(const float* W, bool transposed, const uint16_t** out, int* ld) {
-    if (!g_Wb || !g_tab) return false;
-    if (g_W21b && W >= g_W21 && W < g_W21 + g_W21n) {           // a folded GCN weight: uniform [256,256] blocks
-        const int64_t off = W - g_W21;
+static bool shadow_of(const Call& call, const float* W, bool transposed, const uint16_t** out, int* ld) {
+    if (!call.Wb || !call.tab) return false;
+    if (call.W21b && W >= call.W21 && W < call.W21 + call.W21n) {           // a folded GCN weight: uniform [256,256] blocks
+        const int64_t off = W - call.W21;
         if (off % (FIRA_D * FIRA_D)) return false;
-        *out = (transposed ? g_W21bT : g_W21b) + off;
+        *out = (transposed ? call.W21bT : call.W21b) + off;
         *ld = FIRA_D;
         return true;
     }
-    if (W < g_P || W >= g_P + g_total) return false;
-    const int64_t off = W - g_P;
-    for (int i = 0; i < g_tab->n; ++i) {
-        const ShadowEntry& e = g_tab->e[i];
+    if (W < call.P || W >= call.P + call.total) return false;
+    const int64_t off = W - call.P;
+    for (int i = 0; i < call.tab->n; ++i) {
+        const ShadowEntry& e = call.tab->e[i];
         if (off < e.offset || off >= e.offset + (int64_t)e.rows * e.cols) continue;
         const int64_t rel = off - e.offset;
         if (rel % e.cols) return false;
-        if (!transposed) { *out = g_Wb + off; *ld = e.cols; }
-        else { *out = g_WbT + e.offset_t + rel / e.cols; *ld = e.pitch_t; }
+        if (!transposed) { *out = call.Wb + off; *ld = e.cols; }
+        else { *out = call.WbT + e.offset_t + rel / e.cols; *ld = e.pitch_t; }
         return true;
     }
     return false;
 }
-static inline int gemm_any(hipStream_t s, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B,
+static inline int gemm_any(const Call& call, hipStream_t s, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B,
                            int ldb, float* C, int ldc, const float* bias, int flags, int splitk, float* colsum,
                            const int32_t* c_rows = nullptr, const float* relu_mask = nullptr) {
-    if (g_dtype == 1) {
+    if (call.dtype == 1) {
         // forward (B = W [N,K]) and data gradient (B = W [K,N], reduced over its rows) read the bf16 shadows: the same
         // kernel with a k-contiguous bf16 B operand, half the weight bytes and no transposing loads
         const uint16_t* wb;
         int ldw;
-        if (!tA && !colsum && gemm_bf16_takes(M, N, K) && lda % 4 == 0 && shadow_of(B, !tB, &wb, &ldw) &&
+        if (!tA && !colsum && gemm_bf16_takes(M, N, K) && lda % 4 == 0 && shadow_of(call, B, !tB, &wb, &ldw) &&
             (tB ? ldb == K : ldb == N) && ldw % 8 == 0 && ((uintptr_t)wb % 16) == 0)
             return gemm_bf16_wb_ex(s, M, N, K, A, lda, wb, ldw, C, ldc, bias, flags, splitk, c_rows, relu_mask);
         return gemm_bf16_ex(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk, colsum, c_rows, relu_mask);
@@ -320,16 +348,16 @@ static inline int gemm_any(hipStream_t s, int tA, int tB, int M, int N, int K, c
 }
 
 // Y = X W^T + b
-static inline int linear(hipStream_t s, int M, int N, int K, const float* X, int ldx, const float* W, const float* b,
-                         float* Y, int ldy, int flags = 0) {
-    return gemm_any(s, 0, 1, M, N, K, X, ldx, W, K, Y, ldy, b, flags, 0, nullptr);
+static inline int linear(const Call& call, hipStream_t s, int M, int N, int K, const float* X, int ldx, const float* W,
+                         const float* b, float* Y, int ldy, int flags = 0) {
+    return gemm_any(call, s, 0, 1, M, N, K, X, ldx, W, K, Y, ldy, b, flags, 0, nullptr);
 }
 // y = LN(dropout(X W^T + b [+ r c^T]) + res): the closing step of every block.  By default the product followed by the row
 // kernel; one fused launch where that was measured to win -- bf16 mode, K = 256, encoder-sized blocks (the panel kernel's
 // LayerNorm epilogue, gemm_bf16_panel.hip).  (The fp32 "workgroup owns complete rows" kernels of round 2 lost in the step
 // and are gone; the decoder's blocks are split at their LayerNorm instead: linear_presum below.)
-static inline int linear_ln(hipStream_t s, int M, int K, const float* X, int ldx, const float* W, const float* b,
-                            const float* res, const float* gamma, const float* beta, float* sum, float* y, float* stats,
+static inline int linear_ln(const Call& call, hipStream_t s, int M, int K, const float* X, int ldx, const float* W,
+                            const float* b, const float* res, const float* gamma, const float* beta, float* sum, float* y, float* stats,
                             float p_drop, uint64_t seed, uint32_t st, const int32_t* y_rows = nullptr,
                             const float* r1_row = nullptr, const float* r1_col = nullptr,
                             // second, compact copy of the listed output rows: y2[k] = y[rows2[k]] for k < n2, slot2 = the
@@ -338,10 +366,10 @@ static inline int linear_ln(hipStream_t s, int M, int K, const float* X, int ldx
                             uint32_t idx0 = 0) {     // dropout element index of row 0 (the rows are a slice of the site's rows)
     bool fused = false;
     int rc = 0;
-    if (g_dtype != 0 && idx0 == 0 && g_lanes == 1) {   // bf16: the panel kernel with a LayerNorm epilogue (gemm_bf16_panel.hip)
+    if (call.dtype != 0 && idx0 == 0 && call.lanes == 1) {   // bf16: the panel kernel with a LayerNorm epilogue (gemm_bf16_panel.hip)
         const uint16_t* wb;
         int ldw;
-        fused = shadow_of(W, false, &wb, &ldw) && ldw == K &&
+        fused = shadow_of(call, W, false, &wb, &ldw) && ldw == K &&
                 linear_ln_bf16_try(s, M, K, X, ldx, wb, ldw, b, res, gamma, beta, sum, y, stats, p_drop, seed, st, y_rows, r1_row,
                                    r1_col, &rc);
     }
@@ -350,17 +378,17 @@ static inline int linear_ln(hipStream_t s, int M, int K, const float* X, int ldx
         if (y2 && n2 > 0) TRY(rows_move(s, 0, n2, FIRA_D, y2, y, rows2, nullptr));
         return 0;
     }
-    TRY(linear(s, M, FIRA_D, K, X, ldx, W, b, sum, FIRA_D));
+    TRY(linear(call, s, M, FIRA_D, K, X, ldx, W, b, sum, FIRA_D));
     return add_layernorm_fwd(s, M, sum, res, gamma, beta, y, stats, p_drop, seed, st, y_rows, r1_row, r1_col, slot2, y2, idx0);
 }
 // The same block with its LayerNorm moved into the CONSUMER (fp32, coalesced tile kernel): the closing product stores the
 // pre-norm sum  sum = dropout(X W^T + b) + res  (EpiRes epilogue) and the next product normalises its A rows itself
 // (gemm_tile32_ln_try) -- one launch less per block on the dependent chain.  Both return false when the shape is not
 // taken; the caller then runs linear_ln / linear.
-static inline bool linear_presum(hipStream_t s, int M, int K, const float* X, int ldx, const float* W, const float* b,
-                                 const float* res, float* sum, float p_drop, uint64_t seed, uint32_t st, int* rc,
+static inline bool linear_presum(const Call& call, hipStream_t s, int M, int K, const float* X, int ldx, const float* W,
+                                 const float* b, const float* res, float* sum, float p_drop, uint64_t seed, uint32_t st, int* rc,
                                  uint32_t idx0 = 0) {
-    if (g_dtype != 0 || !gemm_tile32_takes(1, M, FIRA_D, K, X, ldx, W, K)) return false;
+    if (call.dtype != 0 || !gemm_tile32_takes(1, M, FIRA_D, K, X, ldx, W, K)) return false;
     EpiRes er;
     er.res = res; er.ldr = FIRA_D; er.p = p_drop; er.inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
     er.seed = seed; er.site = st; er.idx0 = idx0;
@@ -368,9 +396,9 @@ static inline bool linear_presum(hipStream_t s, int M, int K, const float* X, in
     return gemm_tile32_try(s, 1, M, FIRA_D, K, X, ldx, W, K, sum, FIRA_D, b, 0, rc, nullptr, nullptr, nullptr, &er);
 }
 // dX (+)= dY W          (W stored [N,K]; reduce over N)
-static inline int linear_dgrad(hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* W, float* dX,
-                               int lddx, bool accum) {
-    return gemm_any(s, 0, 0, M, K, N, dY, lddy, W, K, dX, lddx, nullptr, accum ? FIRA_GEMM_ACCUM : 0, 0, nullptr);
+static inline int linear_dgrad(const Call& call, hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* W,
+                               float* dX, int lddx, bool accum) {
+    return gemm_any(call, s, 0, 0, M, K, N, dY, lddy, W, K, dX, lddx, nullptr, accum ? FIRA_GEMM_ACCUM : 0, 0, nullptr);
 }
 // Weight gradients are off the critical path of the backward pass (nothing downstream reads them), so they are
 // issued on a second HIP stream: each one waits for the event that marks its operands ready on the main stream and
@@ -506,110 +534,83 @@ static int main_wait(hipStream_t main_s, hipEvent_t e, int line = 0) {
 enum { PANEL_ENC = 1, PANEL_DEC = 2, PANEL_VOCAB = 4, PANEL_KV = 8 };
 // (measured, profiles/r6_probes.md: fp32 -- every class wins, mask 15; bf16 -- the decoder / head groups (K = the ~1 000 computed
 //  target rows) lose to the tiled grouped kernel, whose single-rounding MFMAs are already short: mask 13)
-static inline bool panel_takes(int cls, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx) {
-    const int mask = g_dtype == 1 ? 13 : 15;
+static inline bool panel_takes(const Call& call, int cls, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx) {
+    const int mask = call.dtype == 1 ? 13 : 15;
     return (mask & cls) && gemm_wgrad_panel_takes(N, K, M, dY, lddy, X, ldx, K);
 }
-static inline int panel_np() { return g_dtype == 1 ? 1 : 3; }
+static inline int panel_np(const Call& call) { return call.dtype == 1 ? 1 : 3; }
 
-static inline int linear_wgrad(hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx,
-                               float* dW, float* db, int panel_cls = 0) {
-    SideStream& sd = side();
+// dW [N,K] += dY^T X on stream ws, which already waits for its operands: panel product where the shape allows (panel_cls 0:
+// never), tiled otherwise
+static inline int wgrad_on(const Call& call, hipStream_t ws, int panel_cls, int M, int N, int K, const float* dY, int lddy,
+                           const float* X, int ldx, float* dW, float* db) {
+    if (gemm_wgrad_panel_pending() == 0 && panel_takes(call, panel_cls, M, N, K, dY, lddy, X, ldx))
+        return gemm_wgrad_panel(ws, panel_np(call), N, K, M, dY, lddy, X, ldx, dW, K, db);
+    return gemm_any(call, ws, 1, 0, N, K, M, dY, lddy, X, ldx, dW, K, nullptr, FIRA_GEMM_ACCUM, 0, db);
+}
+// ... behind a fork of its own from the caller's stream
+static inline int linear_wgrad(const Call& call, hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* X,
+                               int ldx, float* dW, float* db, int panel_cls = 0) {
     hipStream_t ws = s;
-    if (sd.stream && sd.enabled) {
+    if (side_on()) {
         TRY(side_fork(s));
-        ws = sd.stream;
+        ws = side().stream;
     }
-    if (panel_cls && gemm_wgrad_panel_pending() == 0 && panel_takes(panel_cls, M, N, K, dY, lddy, X, ldx))
-        return gemm_wgrad_panel(ws, panel_np(), N, K, M, dY, lddy, X, ldx, dW, K, db);
-    return gemm_any(ws, 1, 0, N, K, M, dY, lddy, X, ldx, dW, K, nullptr, FIRA_GEMM_ACCUM, 0, db);
+    return wgrad_on(call, ws, panel_cls, M, N, K, dY, lddy, X, ldx, dW, db);
 }
 
-// The same for the small reductions over the B*30 target rows (decoder layers, gate / target projections of the head):
-// queued and launched as ONE grouped kernel after the decoder's backward loop (gemm_f32.hip), instead of ~40 launches
-// of ~15 us that are mostly fill and drain.  Operands must stay untouched until then (they are per-layer slots).
-static inline int flush_grouped_wgrads(hipStream_t s);
+static inline int flush_wgrad_queues(const Call& call, hipStream_t ws) {     // the queued launches on the weight-gradient stream: tiled group, then panels
+    TRY(call.dtype == 1 ? gemm_bf16_group_flush(ws) : gemm_group_flush(ws));
+    return gemm_wgrad_panel_flush(ws, panel_np(call));
+}
+static inline int flush_grouped_wgrads(const Call& call, hipStream_t s) {
+    if (!side_on()) return 0;
+    TRY(side_fork(s));
+    return flush_wgrad_queues(call, side().stream);
+}
 // A full queue launches itself at the next add -- on the weight-gradient stream, WITHOUT a fork from the caller's stream, i.e.
 // possibly ahead of the kernels that write its operands (deeper models: > 40 queued problems).  Fork + flush first.
-static inline int group_make_room(hipStream_t s) {
-    if ((g_dtype == 1 ? gemm_bf16_group_full() : gemm_group_full()) || gemm_wgrad_panel_full()) return flush_grouped_wgrads(s);
+static inline int group_make_room(const Call& call, hipStream_t s) {
+    if ((call.dtype == 1 ? gemm_bf16_group_full() : gemm_group_full()) || gemm_wgrad_panel_full()) return flush_grouped_wgrads(call, s);
     return 0;
 }
-static inline int linear_wgrad_grouped(hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* X,
-                                       int ldx, float* dW, float* db, int max_split = 0) {
-    SideStream& sd = side();
-    if (!(sd.stream && sd.enabled)) return linear_wgrad(s, M, N, K, dY, lddy, X, ldx, dW, db);
-    TRY(group_make_room(s));
-    if (panel_takes(PANEL_DEC, M, N, K, dY, lddy, X, ldx)) return gemm_wgrad_panel_add(N, K, M, dY, lddy, X, ldx, dW, K, db);
-    if (g_dtype == 1) {
-        if (!gemm_bf16_takes(N, K, M)) return linear_wgrad(s, M, N, K, dY, lddy, X, ldx, dW, db);   // e.g. the 2-column gate
-        return gemm_bf16_group_add_wgrad(sd.stream, N, K, M, dY, lddy, X, ldx, dW, K, db, max_split);
+// The same product QUEUED: launched with the others of its queue as one grouped kernel at the next flush_grouped_wgrads
+// (one fork for all of them), as a panel product (class queue_cls) where the shape allows, a tiled one otherwise.  Operands
+// must stay untouched until then (they are per-layer slots).  `grouping` off: launched at once behind its own fork, with
+// the panel class direct_cls.
+static inline int wgrad_queued(const Call& call, hipStream_t s, bool grouping, int queue_cls, int direct_cls, int max_split, int M,
+                               int N, int K, const float* dY, int lddy, const float* X, int ldx, float* dW, float* db) {
+    if (!grouping) return linear_wgrad(call, s, M, N, K, dY, lddy, X, ldx, dW, db, direct_cls);
+    TRY(group_make_room(call, s));
+    if (panel_takes(call, queue_cls, M, N, K, dY, lddy, X, ldx)) return gemm_wgrad_panel_add(N, K, M, dY, lddy, X, ldx, dW, K, db);
+    if (call.dtype == 1) {
+        if (!gemm_bf16_takes(N, K, M)) return linear_wgrad(call, s, M, N, K, dY, lddy, X, ldx, dW, db);   // e.g. the 2-column gate
+        return gemm_bf16_group_add_wgrad(side().stream, N, K, M, dY, lddy, X, ldx, dW, K, db, max_split);
     }
-    return gemm_group_add_wgrad(sd.stream, N, K, M, dY, lddy, X, ldx, dW, K, db, max_split);
+    return gemm_group_add_wgrad(side().stream, N, K, M, dY, lddy, X, ldx, dW, K, db, max_split);
+}
+// The small reductions over the B*30 target rows (decoder layers, gate / target projections of the head): ONE grouped kernel
+// after the decoder's backward loop (gemm_f32.hip), instead of ~40 launches of ~15 us that are mostly fill and drain.
+static inline int linear_wgrad_grouped(const Call& call, hipStream_t s, int M, int N, int K, const float* dY, int lddy,
+                                       const float* X, int ldx, float* dW, float* db, int max_split = 0) {
+    return wgrad_queued(call, s, side_on(), PANEL_DEC, 0, max_split, M, N, K, dY, lddy, X, ldx, dW, db);
 }
 // One encoder layer's three weight gradients (folded GCN weight, Combination output and q|k projections): queued while
-// the layer's data-gradient chain runs, then issued as ONE grouped launch behind ONE fork (enc_wgrads_flush) -- every fork
+// the layer's data-gradient chain runs, then issued as ONE grouped launch behind ONE fork -- every fork
 // is an event record on the caller's stream, i.e. a barrier packet in the dependent chain (scripts/event_cost.py: ~4-5 us
 // each), and the layer used to pay four of them.  FIRA_ENC_WGRAD_GROUP=0: one fork + launch per gradient
 // (schedule switch: tests/test_model_gpu.py checks its gradients).
 static inline bool enc_group_on() {
     static const bool off = [] { const char* e = getenv("FIRA_ENC_WGRAD_GROUP"); return e && e[0] == '0'; }();
-    SideStream& sd = side();
-    return !off && sd.stream && sd.enabled;
+    return !off && side_on();
 }
-static inline int enc_wgrad(hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx, float* dW,
-                            float* db) {
-    if (!enc_group_on()) return linear_wgrad(s, M, N, K, dY, lddy, X, ldx, dW, db, PANEL_ENC);
-    SideStream& sd = side();
-    TRY(group_make_room(s));
-    if (panel_takes(PANEL_ENC, M, N, K, dY, lddy, X, ldx)) return gemm_wgrad_panel_add(N, K, M, dY, lddy, X, ldx, dW, K, db);
-    if (g_dtype == 1) {
-        if (!gemm_bf16_takes(N, K, M)) return linear_wgrad(s, M, N, K, dY, lddy, X, ldx, dW, db);
-        return gemm_bf16_group_add_wgrad(sd.stream, N, K, M, dY, lddy, X, ldx, dW, K, db, 32);
-    }
-    return gemm_group_add_wgrad(sd.stream, N, K, M, dY, lddy, X, ldx, dW, K, db, 32);
+static inline int enc_wgrad(const Call& call, hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* X,
+                            int ldx, float* dW, float* db) {
+    return wgrad_queued(call, s, enc_group_on(), PANEL_ENC, PANEL_ENC, 32, M, N, K, dY, lddy, X, ldx, dW, db);
 }
-// dW [N,K] += dY^T X on stream ws, which already waits for its operands: panel product where the shape allows, tiled otherwise
-static inline int wgrad_on(hipStream_t ws, int panel_cls, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx,
-                           float* dW, float* db) {
-    if (gemm_wgrad_panel_pending() == 0 && panel_takes(panel_cls, M, N, K, dY, lddy, X, ldx))
-        return gemm_wgrad_panel(ws, panel_np(), N, K, M, dY, lddy, X, ldx, dW, K, db);
-    return gemm_any(ws, 1, 0, N, K, M, dY, lddy, X, ldx, dW, K, nullptr, FIRA_GEMM_ACCUM, 0, db);
-}
-static inline int flush_wgrad_queues(hipStream_t ws) {     // the queued launches on the weight-gradient stream: tiled group, then panels
-    TRY(g_dtype == 1 ? gemm_bf16_group_flush(ws) : gemm_group_flush(ws));
-    return gemm_wgrad_panel_flush(ws, panel_np());
-}
-static inline int flush_grouped_wgrads(hipStream_t s) {
-    SideStream& sd = side();
-    if (!(sd.stream && sd.enabled)) return 0;
-    TRY(side_fork(s));
-    return flush_wgrad_queues(sd.stream);
-}
-
-// Deferred column reductions of the backward pass (rowops.hip: deferred_reduce): kernels park one partial row per
-// workgroup in Plan::red_buf; the table is flushed (ONE launch) before the mid-event for the decoder-side parameters
-// and at the end of the backward pass for the encoder-side ones.
-struct RedCollector {
-    float* buf = nullptr;
-    size_t cap = 0, used = 0;
-    RedTable tab;
-    void reset(float* b, size_t c) { buf = b; cap = c; used = 0; tab.n = 0; }
-    // nullptr: no room (floats, or the `entries` table rows the caller is going to add()) -> the kernel falls back to atomics
-    float* alloc(size_t n, int entries = 4) {
-        if (!buf || used + n > cap || tab.n + entries > RED_MAX) return nullptr;
-        float* p = buf + used;
-        used += (n + 63) / 64 * 64;
-        return p;
-    }
-    void add(float* dst, const float* src, int width, int n_part, int stride) {
-        tab.e[tab.n++] = RedEntry{dst, src, width, n_part, stride};
-    }
-};
-static RedCollector& red() { static thread_local RedCollector r; return r; }
 
 // LayerNorm backward with its dgamma / dbeta reduction deferred
-static int ln_bwd(hipStream_t s, int M, const float* dy, const float* sum, const float* stats, const float* gamma, float* ds,
+static int ln_bwd(Call& call, hipStream_t s, int M, const float* dy, const float* sum, const float* stats, const float* gamma, float* ds,
                   float* dx_drop, float* dgamma, float* dbeta, float dropout, uint64_t seed, uint32_t st,
                   const int32_t* rows = nullptr,
                   // optional (GCN blocks): the kernel also leaves sum_r dx[r,:] -> dsum and sum_r row_w[r] dx[r,:] -> dwsum
@@ -620,19 +621,19 @@ static int ln_bwd(hipStream_t s, int M, const float* dy, const float* sum, const
     // FIRA_LN_BWD_EXTRA=0: the GCN blocks' extra column sums in a separate launch (schedule switch: tests/test_model_gpu.py)
     static const bool no_extra = [] { const char* e = getenv("FIRA_LN_BWD_EXTRA"); return e && e[0] == '0'; }();
     const bool want = row_w && dsum && dwsum && !no_extra;
-    float* part = want ? red().alloc((size_t)nb * 4 * FIRA_D) : nullptr;
+    float* part = want ? call.red.alloc((size_t)nb * 4 * FIRA_D) : nullptr;
     const bool ex = part != nullptr;
-    if (!part) part = red().alloc((size_t)nb * 2 * FIRA_D);
+    if (!part) part = call.red.alloc((size_t)nb * 2 * FIRA_D);
     if (extras) *extras = ex;
     const int w = ex ? 4 * FIRA_D : 2 * FIRA_D;
     TRY(add_layernorm_bwd(s, M, dy, sum, stats, gamma, ds, dx_drop, dgamma, dbeta, dropout, seed, st, rows, part,
                           ex ? row_w : nullptr, idx0));
     if (part) {
-        red().add(dgamma, part, FIRA_D, nb, w);
-        red().add(dbeta, part + FIRA_D, FIRA_D, nb, w);
+        call.red.add(dgamma, part, FIRA_D, nb, w);
+        call.red.add(dbeta, part + FIRA_D, FIRA_D, nb, w);
         if (ex) {
-            red().add(dsum, part + 2 * FIRA_D, FIRA_D, nb, w);
-            red().add(dwsum, part + 3 * FIRA_D, FIRA_D, nb, w);
+            call.red.add(dsum, part + 2 * FIRA_D, FIRA_D, nb, w);
+            call.red.add(dwsum, part + 3 * FIRA_D, FIRA_D, nb, w);
         }
     }
     return 0;
@@ -641,46 +642,31 @@ static int ln_bwd(hipStream_t s, int M, const float* dy, const float* sum, const
 // LayerNorm backward of a decoder block + the data-gradient product that consumes its output, as ONE launch where the
 // coalesced tile kernel takes the shape (fp32, 256-wide rows: gemm_tile32_lnb_try) -- otherwise the row kernel followed by
 // the product.  dX[M,N] = dx_drop[M,256] . W[256,N] (W row-major [256,N]) (masked by relu_mask > 0); ds must not alias dy.
-static int ln_bwd_dgrad(hipStream_t s, int M, int N, const float* dy, const float* sum, const float* stats, const float* gamma,
+static int ln_bwd_dgrad(Call& call, hipStream_t s, int M, int N, const float* dy, const float* sum, const float* stats, const float* gamma,
                         float* ds, float* dx_drop, float* dgamma, float* dbeta, float dropout, uint64_t seed, uint32_t st,
                         const float* W, int ldw, float* dX, int lddx, const float* relu_mask, uint32_t idx0 = 0) {
     // Up to ~1 500 rows (batch 64): beyond, the prologue repeated in each of the N / 32 column tiles of a row block is no longer
     // hidden by idle CUs (batch 170, 2 700 rows: 20 177 -> 20 567 commits/s without it; batch 64 neutral, batch 32 +0.5 % with it)
     constexpr int lnb_max_rows = 1536;
-    if (g_dtype == 0 && M <= lnb_max_rows && ds != dy && gemm_tile32_takes(0, M, N, FIRA_D, dy, FIRA_D, W, ldw)) {
+    if (call.dtype == 0 && M <= lnb_max_rows && ds != dy && gemm_tile32_takes(0, M, N, FIRA_D, dy, FIRA_D, W, ldw)) {
         const int nb = gemm_tile32_lnb_blocks(M);
-        float* part = red().alloc((size_t)nb * 2 * FIRA_D);
+        float* part = call.red.alloc((size_t)nb * 2 * FIRA_D);
         int rc = 0;
         if (part && gemm_tile32_lnb_try(s, M, N, dy, W, ldw, dX, lddx, relu_mask, sum, stats, gamma, ds, dx_drop, part, dropout, seed,
                                         st, &rc, idx0)) {
             TRY(rc);
-            red().add(dgamma, part, FIRA_D, nb, 2 * FIRA_D);
-            red().add(dbeta, part + FIRA_D, FIRA_D, nb, 2 * FIRA_D);
+            call.red.add(dgamma, part, FIRA_D, nb, 2 * FIRA_D);
+            call.red.add(dbeta, part + FIRA_D, FIRA_D, nb, 2 * FIRA_D);
             return 0;
         }
     }
-    TRY(ln_bwd(s, M, dy, sum, stats, gamma, ds, dx_drop, dgamma, dbeta, dropout, seed, st, nullptr, nullptr, nullptr, nullptr, nullptr, idx0));
-    return gemm_any(s, 0, 0, M, N, FIRA_D, dx_drop, FIRA_D, W, ldw, dX, lddx, nullptr, 0, 0, nullptr, nullptr, relu_mask);
+    TRY(ln_bwd(call, s, M, dy, sum, stats, gamma, ds, dx_drop, dgamma, dbeta, dropout, seed, st, nullptr, nullptr, nullptr, nullptr, nullptr,
+               idx0));
+    return gemm_any(call, s, 0, 0, M, N, FIRA_D, dx_drop, FIRA_D, W, ldw, dX, lddx, nullptr, 0, 0, nullptr, nullptr, relu_mask);
 }
 
 // bf16 mode: the attention matmuls run on bf16 operands too (torch.autocast semantics)
-static inline int attn_bf16() { return g_dtype == 1; }
-
-// GCN layer as one fused launch per direction (gcn_fused.hip) instead of SpMM + product + add-LayerNorm (forward) /
-// product + SpMM (backward), where the batch's density allows (round 6): the fused kernels' gather is built for FIRA's graphs
-// (3-4 entries per computed row, the first 16 of a row in one batched round trip); rows beyond 16 entries take a 64-at-a-time
-// tail loop per row, and on BASELINE config 5's graphs (116 entries per row) the fused forward costs 518 us against 319 us for
-// aggregation + product + row kernel (bench.py: gcn_cfg5).  Batches averaging more than GCN_FUSED_MAX_DEG entries per computed
-// row run the separate kernels; set per call by check_batch.
-// (The backward pass was measured unfused too -- V = A_hat dY by the CSR kernel, dX += V W21 by the product -- in bf16 at batch
-// 64, where the product is a few microseconds of MFMA time and the fused launch's phase latencies are exposed: 16 239 / 16 203
-// commits/s fused against 16 110 / 15 982.  Both directions follow the same rule.)
-static constexpr double GCN_FUSED_MAX_DEG = 48.0;
-static thread_local bool g_dense_graphs = false;
-static inline bool gcn_fused_on() { return !g_dense_graphs; }
-static inline void note_graph_density(const fira_batch* b) {
-    g_dense_graphs = b->n_nodes > 0 && (double)b->nnz > GCN_FUSED_MAX_DEG * (double)b->n_nodes;
-}
+static inline int attn_bf16(const Call& call) { return call.dtype == 1; }
 
 // The Combination block runs as one fused launch per direction (comb_fused.hip) instead of product + gate kernel + product +
 // add-LayerNorm, in fp32 and in bf16 mode (operands rounded as the panel products round them), for layers 0..7.
@@ -762,8 +748,8 @@ struct Ctx {
     const ShadowTable* shadow_tab = nullptr;
     hipEvent_t ev_shadow = nullptr;
     // (round 6) commit-lanes of the decoder's chain: see decoder_lanes()
-    int n_lanes = 1;
     struct Lane { hipStream_t s; int b0, nb, r0, nr; } lanes[2] = {};
+    Call call;                       // what the launch helpers of this call depend on (dtype, lanes, density, shadows, reductions)
 };
 typedef Ctx::Lane Lane;
 
@@ -797,7 +783,7 @@ static int decoder_lanes(Ctx& c) {
     constexpr int DEC_LANES_MIN_ROWS = 768;
     static const int forced = [] { const char* e = getenv("FIRA_DEC_LANES"); return e ? (atoi(e) >= 2 ? 2 : 1) : 0; }();
     const int want = forced ? forced : (c.Td >= DEC_LANES_MIN_ROWS ? 2 : 1);
-    c.n_lanes = g_lanes = 1;
+    c.call.lanes = 1;
     c.lanes[0] = Lane{c.s, 0, c.pl->B, 0, c.Td};
     const fira_batch& bt = *c.bt;
     if (want < 2 || !c.dec_off || !bt.dec_off_host || bt.B < 2 || !side_on() || c.serial || !c.kv_ragged) return 0;
@@ -813,21 +799,21 @@ static int decoder_lanes(Ctx& c) {
     }
     const int rm = bt.dec_off_host[bm];
     if (rm <= 0 || rm >= c.Td || bt.dec_off_host[bt.B] != c.Td) return 0;
-    c.n_lanes = g_lanes = 2;
+    c.call.lanes = 2;
     c.lanes[0] = Lane{c.s, 0, bm, 0, rm};
     c.lanes[1] = Lane{sd.lane, bm, bt.B - bm, rm, c.Td - rm};
     return 0;
 }
 // lane 1 starts behind everything the caller's stream holds so far / the caller's stream continues behind lane 1
 static int lanes_fork(Ctx& c) {
-    for (int k = 1; k < c.n_lanes; ++k) {
+    for (int k = 1; k < c.call.lanes; ++k) {
         hipEvent_t e = side().ev();
         if (hipEventRecord(e, c.s) != hipSuccess || hipStreamWaitEvent(c.lanes[k].s, e, 0) != hipSuccess) return set_err("lane fork failed");
     }
     return 0;
 }
 static int lanes_join(Ctx& c) {
-    for (int k = 1; k < c.n_lanes; ++k) {
+    for (int k = 1; k < c.call.lanes; ++k) {
         hipEvent_t e = side().ev();
         if (hipEventRecord(e, c.lanes[k].s) != hipSuccess || hipStreamWaitEvent(c.s, e, 0) != hipSuccess) return set_err("lane join failed");
     }
@@ -835,7 +821,7 @@ static int lanes_join(Ctx& c) {
 }
 // `target` (the weight-gradient or the auxiliary stream) waits for everything enqueued on EVERY lane so far
 static int lanes_fork_to(Ctx& c, hipStream_t target) {
-    for (int k = 0; k < c.n_lanes; ++k) {
+    for (int k = 0; k < c.call.lanes; ++k) {
         hipEvent_t e = side().ev();
         if (hipEventRecord(e, c.lanes[k].s) != hipSuccess || hipStreamWaitEvent(target, e, 0) != hipSuccess) return set_err("lane -> side stream fork failed");
     }
@@ -855,7 +841,7 @@ static inline bool fold_one_launch(int nl) { return nl <= 10; }
 // that rounded fragments in every wave (+5.1 % at batch 64).  The planes of every layer are formed in one
 // launch, which bounds the depth.
 static inline bool comb_x3_on(int nl) { return nl <= 8; }
-static inline bool gcn_x3_on(int nl) { return gcn_fused_on() && fold_one_launch(nl); }
+static inline bool gcn_x3_on(const Call& call, int nl) { return call.gcn_fused() && fold_one_launch(nl); }
 // (round 6) the training step's K|V projection of the memory rows as linear_x3 (three-term planes in fp32 mode, one plane in
 // bf16 mode): two launches instead of one fp32 / bf16 GEMM launch per layer (+0.4 % at fp32 batch 64, +1.0 % in bf16)
 static inline bool kv_x3_on(int nl) { return nl * 2 <= 24; }
@@ -927,14 +913,14 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
         // (with the one-launch fold right behind it, ONE mark serves the first Combination block and the first GCN layer: every
         //  wait is a barrier packet in the caller's chain, and the fold is through ~25 us into the call, before the first
         //  Combination block starts)
-        if (ax && !(fold_one && (!g_Wb || gcn_fused_on()))) TRY(side_mark(&ev_comb));
+        if (ax && !(fold_one && (!c.call.Wb || c.call.gcn_fused()))) TRY(side_mark(&ev_comb));
         if (fold_one) {
             // (round 5) every layer's W21, its k-major copy and c21: ONE launch (gemm_small.hip: gcn_fold_weights).  The fused GCN
             // kernels read the fp32 matrices in both modes, so the mark behind this launch is all the first layer waits for
             const float *fW2[16], *fW1[16], *fb1[16];
             for (int l = 0; l < p.nl; ++l) { fW2[l] = c.P + L.enc[l].fc2w; fW1[l] = c.P + L.enc[l].fc1w; fb1[l] = c.P + L.enc[l].fc1b; }
-            TRY(gcn_fold_weights(fs, p.nl, fW2, fW1, fb1, p.W21, gcn_fused_on() ? p.W21t : nullptr, p.c21));
-            if (gcn_x3_on(p.nl)) {       // the planes of W21 (forward: out = U W21^T) and of W21^T (backward: out = V W21)
+            TRY(gcn_fold_weights(fs, p.nl, fW2, fW1, fb1, p.W21, c.call.gcn_fused() ? p.W21t : nullptr, p.c21));
+            if (gcn_x3_on(c.call, p.nl)) {       // the planes of W21 (forward: out = U W21^T) and of W21^T (backward: out = V W21)
                 const float* src[24];
                 uint16_t* dst[24];
                 int n = 0;
@@ -944,16 +930,16 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
                 }
                 TRY(gcn_split_planes(fs, n, src, dst));
             }
-            if (ax && (!g_Wb || gcn_fused_on())) TRY(side_mark(&ev_fold0));
+            if (ax && (!c.call.Wb || c.call.gcn_fused())) TRY(side_mark(&ev_fold0));
         } else
         for (int l = 0; l < p.nl; ++l) {
             const EncLayer& w = L.enc[l];
             TRY(gemm_f32_ex(fs, 0, 0, D, D, D, c.P + w.fc2w, D, c.P + w.fc1w, D, p.W21 + (size_t)l * D * D, D, nullptr, 0, 0, nullptr));
             TRY(gemm_f32_ex(fs, 0, 1, D, 1, D, c.P + w.fc2w, D, c.P + w.fc1b, D, p.c21 + (size_t)l * D, 1, nullptr, 0, 0, nullptr));
-            if (l == 0 && gcn_fused_on()) TRY(transpose256(fs, 1, p.W21, p.W21t));       // (layer 0's first: see ev_fold0)
-            if (ax && l == 0 && !g_Wb && p.nl > 1) TRY(side_mark(&ev_fold0));
+            if (l == 0 && c.call.gcn_fused()) TRY(transpose256(fs, 1, p.W21, p.W21t));       // (layer 0's first: see ev_fold0)
+            if (ax && l == 0 && !c.call.Wb && p.nl > 1) TRY(side_mark(&ev_fold0));
         }
-        if (g_Wb) {                                  // bf16 mode: shadows of the folded weights, on the same stream
+        if (c.call.Wb) {                                  // bf16 mode: shadows of the folded weights, on the same stream
             ShadowTable t21;
             for (int l = 0; l < p.nl && l < SHADOW_MAX; ++l) {
                 t21.e[l] = ShadowEntry{(int64_t)l * D * D, D, D, D, (int64_t)l * D * D};
@@ -961,12 +947,12 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
                 t21.n = l + 1;
             }
             TRY(weight_shadows(fs, t21, p.W21, p.w21b, p.w21bt));
-            g_W21 = p.W21; g_W21n = (int64_t)p.nl * D * D; g_W21b = p.w21b; g_W21bT = p.w21bt;
+            c.call.W21 = p.W21; c.call.W21n = (int64_t)p.nl * D * D; c.call.W21b = p.w21b; c.call.W21bT = p.w21bt;
         }
-        if (!fold_one && gcn_fused_on() && p.nl > 1) TRY(transpose256(fs, p.nl - 1, p.W21 + (size_t)D * D, p.W21t + (size_t)D * D));
+        if (!fold_one && c.call.gcn_fused() && p.nl > 1) TRY(transpose256(fs, p.nl - 1, p.W21 + (size_t)D * D, p.W21t + (size_t)D * D));
         // (the closing mark only where something follows the fold that the encoder's own launches read: the unfused GCN path's
         //  bf16 shadows of the folded weights, or the layer-by-layer fold)
-        if (ax && !(ev_fold0 && fold_one && gcn_fused_on())) TRY(side_mark(&ev_fold));
+        if (ax && !(ev_fold0 && fold_one && c.call.gcn_fused())) TRY(side_mark(&ev_fold));
         if (!ev_fold0) ev_fold0 = ev_fold;           // bf16 mode / one layer: a single mark
         if (c.shadow_tab) {                          // (see Ctx::shadow_tab)
             TRY(weight_shadows(fs, *c.shadow_tab, c.P, p.wb, p.wbt));
@@ -990,7 +976,7 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
     TRY(node_features(s, Nc, bt.node_rows, p.N, p.L, p.S, bt.sou, bt.sub_token, bt.ast_change, c.P + L.emb, c.P + L.ast_emb,
                       p.pos_code, p.X[0], p.code_slot, p.enc[0].Xc, &vw_emb));
     // value projection of the 4-row mark table for all layers at once: vtab_all [4, nl*256]
-    TRY(linear(s, 4, p.nl * D, D, c.P + L.mark_emb, D, c.P + L.w2_all, c.P + L.b2_all, p.vtab_all, p.nl * D));
+    TRY(linear(c.call, s, 4, p.nl * D, D, c.P + L.mark_emb, D, c.P + L.w2_all, c.P + L.b2_all, p.vtab_all, p.nl * D));
     for (int l = 0; l < p.nl; ++l) {
         const EncLayer& w = L.enc[l];
         EncSave& e = p.enc[l];
@@ -1003,16 +989,16 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
             const float* wt = p.WcT + (size_t)l * 3 * D * D;
             TRY(comb_fused_fwd(s, Cc, e.Xc, wt, wt + (size_t)D * D, wt + (size_t)2 * D * D, c.P + w.bqk, c.P + w.bo,
                                p.vtab_all + l * D, p.nl * D, bt.code_mark, e.qk, e.c, c.P + w.ln1g, c.P + w.ln1b, e.s1, X,
-                               bt.code_rows, e.st1, c.p_drop, c.seed, site(l, SITE_GATE), site(l, SITE_COMB_OUT), g_dtype == 1,
+                               bt.code_rows, e.st1, c.p_drop, c.seed, site(l, SITE_GATE), site(l, SITE_COMB_OUT), c.call.dtype == 1,
                                comb_x3_on(p.nl) ? p.WcX + (size_t)l * 9 * D * D : nullptr));
         } else {
-        TRY(linear(s, Cc, 2 * D, D, e.Xc, D, c.P + w.wqk, c.P + w.bqk, e.qk, 2 * D));
+        TRY(linear(c.call, s, Cc, 2 * D, D, e.Xc, D, c.P + w.wqk, c.P + w.bqk, e.qk, 2 * D));
         TRY(combination_fwd(s, Cc, e.qk, p.vtab_all + l * D, p.nl * D, bt.code_mark, e.c, c.p_drop, c.seed, site(l, SITE_GATE)));
-        TRY(linear_ln(s, Cc, D, e.c, D, c.P + w.wo, c.P + w.bo, e.Xc, c.P + w.ln1g, c.P + w.ln1b, e.s1, X, e.st1, c.p_drop,
+        TRY(linear_ln(c.call, s, Cc, D, e.c, D, c.P + w.wo, c.P + w.bo, e.Xc, c.P + w.ln1g, c.P + w.ln1b, e.s1, X, e.st1, c.p_drop,
                       c.seed, site(l, SITE_COMB_OUT), bt.code_rows));
         }
         // GCN in folded form: U = A_hat X -> U W21^T + b2 -> (+ r c^T) dropout, +X, LN
-        const bool fused = gcn_fused_on();
+        const bool fused = c.call.gcn_fused();
         if (!fused) TRY(csr_spmm_ex(s, Nc, bt.rowptr, bt.col, bt.val, X, D, e.Z, D, 0, 1, 0, l == 0 ? p.rsum : nullptr));
         if (l == 0 && ev_fold0 && !fold_waited) TRY(main_wait(s, ev_fold0, __LINE__));   // the product below is the first reader of W21 / c21
         if (l == 1 && ev_fold && ev_fold != ev_fold0) TRY(main_wait(s, ev_fold, __LINE__));
@@ -1025,9 +1011,9 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
             TRY(gcn_fused_fwd(s, Nc, bt.rowptr, bt.col, bt.val, X, p.W21t + (size_t)l * D * D, c.P + w.fc2b, p.c21 + (size_t)l * D,
                               c.P + w.ln2g, c.P + w.ln2b, e.s2, p.X[l + 1], e.st2, l == 0 ? p.rsum : nullptr,
                               last ? p.mem_slot : p.code_slot, last ? p.mem_c : p.enc[l + 1].Xc, c.p_gcn, c.seed,
-                              site(l, SITE_GCN), g_dtype == 1, gcn_x3_on(p.nl) ? p.W21x + (size_t)l * 3 * D * D : nullptr));
+                              site(l, SITE_GCN), c.call.dtype == 1, gcn_x3_on(c.call, p.nl) ? p.W21x + (size_t)l * 3 * D * D : nullptr));
         else
-        TRY(linear_ln(s, Nc, D, e.Z, D, p.W21 + (size_t)l * D * D, c.P + w.fc2b, X, c.P + w.ln2g, c.P + w.ln2b, e.s2,
+        TRY(linear_ln(c.call, s, Nc, D, e.Z, D, p.W21 + (size_t)l * D * D, c.P + w.fc2b, X, c.P + w.ln2g, c.P + w.ln2b, e.s2,
                       p.X[l + 1], e.st2, c.p_gcn, c.seed, site(l, SITE_GCN), nullptr, p.rsum, p.c21 + (size_t)l * D,
                       last ? p.mem_slot : p.code_slot, last ? p.mem_c : p.enc[l + 1].Xc, last ? Mc : Cc,
                       last ? bt.mem_rows : bt.code_rows));
@@ -1053,9 +1039,9 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
                 const int l1 = l == 0 ? std::min(2, p.nl) : p.nl;            // layers l .. l1 in this launch
                 if (l == 0 || l == std::min(2, p.nl))
                     TRY(linear_x3(ss, Mc, p.mem_c, D, p.WkvX + (size_t)l * 2 * 3 * D * D, (l1 - l) * 2, c.P + L.bkv_all + o, p.kv_all + o,
-                                  p.kvp, g_dtype == 1));
+                                  p.kvp, c.call.dtype == 1));
             } else
-            TRY(gemm_any(ss, 0, 1, Mc, 2 * D, D, p.mem_c, D, c.P + L.wkv_all + o * D, D, p.kv_all + o, p.kvp, c.P + L.bkv_all + o, 0,
+            TRY(gemm_any(c.call, ss, 0, 1, Mc, 2 * D, D, p.mem_c, D, c.P + L.wkv_all + o * D, D, p.kv_all + o, p.kvp, c.P + L.bkv_all + o, 0,
                          0, nullptr));
             // two marks (behind layers 1 and the last one) instead of one per layer: every wait is a barrier packet in the
             // decoder's dependent chain, and the projections (~10 us each) are far ahead of the layers that read them
@@ -1063,7 +1049,7 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
             if (l == std::min(1, p.nl - 1) || l == p.nl - 1) TRY(side_mark(&c.ev_kv[l]));
         }
         // (LinearSource: output rows straight to their dense [B,370] slots through the row map of the GEMM epilogue)
-        TRY(gemm_any(ss, 0, 1, Mc, D, D, p.mem_c, D, c.P + L.ws, D, p.src, D, nullptr, 0, 0, nullptr, bt.mem_dst));
+        TRY(gemm_any(c.call, ss, 0, 1, Mc, D, D, p.mem_c, D, c.P + L.ws, D, p.src, D, nullptr, 0, 0, nullptr, bt.mem_dst));
         TRY(side_mark(&c.ev_src));
         if (kvx && p.nl * 2 <= 24) {
             // the transposed blocks' planes for the backward pass's d-memory products: behind everything the forward pass waits for
@@ -1081,15 +1067,15 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
         // ... and, in bf16 mode, the plane of the generator projection's transposed row blocks (one 38 MB pass under the decoder's
         // forward chain) for its data gradient as dgrad_x3_splitk: +1.0 % at batch 64.  (fp32 mode keeps the fp32 MFMA launch: the
         // three-plane form streams 680 MB of planes through L2 per launch at batch 32 and LOST 0.9 % -- profiles/r6_probes.md.)
-        if (c.G && g_dtype == 1) {
+        if (c.G && c.call.dtype == 1) {
             TRY(split_planes_t(ss, c.P + L.wout, p.V, p.WoutTX, true));
             c.wout_planes = true;
         }
         c.deferred = true;
         return 0;
     }
-    TRY(gemm_any(s, 0, 1, Mc, KV, D, p.mem_c, D, c.P + L.wkv_all, D, p.kv_all, p.kvp, c.P + L.bkv_all, 0, 0, nullptr));
-    TRY(gemm_any(s, 0, 1, Mc, D, D, p.mem_c, D, c.P + L.ws, D, p.src, D, nullptr, 0, 0, nullptr, bt.mem_dst));
+    TRY(gemm_any(c.call, s, 0, 1, Mc, KV, D, p.mem_c, D, c.P + L.wkv_all, D, p.kv_all, p.kvp, c.P + L.bkv_all, 0, 0, nullptr));
+    TRY(gemm_any(c.call, s, 0, 1, Mc, D, D, p.mem_c, D, c.P + L.ws, D, p.src, D, nullptr, 0, 0, nullptr, bt.mem_dst));
     return 0;
 }
 
@@ -1122,12 +1108,12 @@ static int decoder_forward(Ctx& c) {
         float *pend_y = nullptr, *pend_st = nullptr;
         int kv_waited = 0;
     } state[2];
-    for (int k = 0; k < c.n_lanes; ++k) state[k].x = p.x0;
+    for (int k = 0; k < c.call.lanes; ++k) state[k].x = p.x0;
     for (int l = 0; l < p.nl; ++l) {
         const DecLayer& w = L.dec[l];
         DecSave& e = p.dec[l];
         const bool last = l + 1 == p.nl;
-        for (int k = 0; k < c.n_lanes; ++k) {
+        for (int k = 0; k < c.call.lanes; ++k) {
             const Lane& ln = c.lanes[k];
             LaneState& st = state[k];
             hipStream_t s = ln.s;
@@ -1147,7 +1133,7 @@ static int decoder_forward(Ctx& c) {
                     st.pend_sum = nullptr;
                     if (rc || fused) return rc;
                 }
-                return linear(s, nr, N, D, st.x + r0 * D, D, W, b, Y + r0 * N, N, flags);
+                return linear(c.call, s, nr, N, D, st.x + r0 * D, D, W, b, Y + r0 * N, N, flags);
             };
             // closing product of a block: y = LN(dropout(X W^T + b) + res); its LayerNorm is deferred to the next product when
             // the shapes allow it
@@ -1155,12 +1141,12 @@ static int decoder_forward(Ctx& c) {
                                    const float* be, float* sum, float* y, float* stt, uint32_t site_id, bool may_defer,
                                    const int32_t* slot2, float* y2, int n2, const int32_t* rows2) -> int {
                 int rc = 0;
-                if (may_defer && linear_presum(s, nr, K, X + r0 * K, K, W, b, res + r0 * D, sum + r0 * D, c.p_drop, c.seed, site_id,
+                if (may_defer && linear_presum(c.call, s, nr, K, X + r0 * K, K, W, b, res + r0 * D, sum + r0 * D, c.p_drop, c.seed, site_id,
                                                &rc, idx0)) {
                     st.pend_sum = sum; st.pend_g = g; st.pend_b = be; st.pend_y = y; st.pend_st = stt;
                     return rc;
                 }
-                return linear_ln(s, nr, K, X + r0 * K, K, W, b, res + r0 * D, g, be, sum + r0 * D, y + r0 * D, stt + r0 * 2, c.p_drop,
+                return linear_ln(c.call, s, nr, K, X + r0 * K, K, W, b, res + r0 * D, g, be, sum + r0 * D, y + r0 * D, stt + r0 * 2, c.p_drop,
                                  c.seed, site_id, nullptr, nullptr, nullptr, slot2 ? slot2 + r0 : nullptr, y2, n2, rows2, idx0);
             };
             // (a lane's commits: ranges of the ragged row lists start at its first commit; the dense key mask of the self
@@ -1168,7 +1154,7 @@ static int decoder_forward(Ctx& c) {
             const int32_t* q_off = c.dec_off ? c.dec_off + ln.b0 : nullptr;
             TRY(consume(3 * D, c.P + w.wqkv, c.P + w.bqkv, e.qkv, 0));
             TRY(attention_fwd(s, ln.nb, H, p.T, p.T, e.qkv, 3 * D, e.qkv + D, 3 * D, e.qkv + 2 * D, 3 * D, p.tar_valid + (size_t)ln.b0 * p.T,
-                              1, 0, e.ao, D, q_off, 1, attn_bf16()));
+                              1, 0, e.ao, D, q_off, 1, attn_bf16(c.call)));
             TRY(close_block(D, e.ao, c.P + w.wo_s, c.P + w.bo_s, st.x, c.P + w.lns_g, c.P + w.lns_b, e.s_a, e.x_a, e.st_a,
                             site(l, SITE_SELF), true, nullptr, nullptr, 0, nullptr));
             st.x = e.x_a;
@@ -1183,7 +1169,7 @@ static int decoder_forward(Ctx& c) {
                 }
             }
             TRY(attention_fwd(s, ln.nb, H, p.T, Sm, e.qc, D, p.kv_all + l * 2 * D, p.kvp, p.kv_all + l * 2 * D + D, p.kvp,
-                              c.kv_ragged ? p.mem_valid_c : p.mem_valid, 0, 0, e.ao2, D, q_off, 0, attn_bf16(),
+                              c.kv_ragged ? p.mem_valid_c : p.mem_valid, 0, 0, e.ao2, D, q_off, 0, attn_bf16(c.call),
                               c.kv_ragged ? p.mem_off + ln.b0 : nullptr));
             TRY(close_block(D, e.ao2, c.P + w.wo_c, c.P + w.bo_c, e.x_a, c.P + w.lnc_g, c.P + w.lnc_b, e.s_c, e.x_c, e.st_c,
                             site(l, SITE_CROSS), true, nullptr, nullptr, 0, nullptr));
@@ -1219,16 +1205,16 @@ static int head_forward(Ctx& c, int R, const int32_t* rows, float* loss_sum, int
     }
     // (round 6) fp32 mode: the generator projection as three bf16 terms per operand (head_x3.hip) instead of the fp32 tiled kernel
     // (1.55x stand-alone; +-0 on the step at batch 32, +0.2 % at batch 64)
-    if (g_dtype == 0 && R >= 64 && R <= p.TB)
+    if (c.call.dtype == 0 && R >= 64 && R <= p.TB)
         TRY(head_logits_x3(s, R, p.V, dec_rows, D, c.P + L.wout, c.P + L.bout, p.logits, p.ldl, p.xh_planes));
     else
-    TRY(linear(s, R, p.V, D, dec_rows, D, c.P + L.wout, c.P + L.bout, p.logits, p.ldl));
-    TRY(gemm_any(s, 0, 1, c.Td, D, D, dec, D, c.P + L.wt, D, p.tgt, D, nullptr, 0, 0, nullptr));
+    TRY(linear(c.call, s, R, p.V, D, dec_rows, D, c.P + L.wout, c.P + L.bout, p.logits, p.ldl));
+    TRY(gemm_any(c.call, s, 0, 1, c.Td, D, D, dec, D, c.P + L.wt, D, p.tgt, D, nullptr, 0, 0, nullptr));
     if (c.deferred) TRY(main_wait(s, c.ev_src, __LINE__));                   // LinearSource(memory) (side stream)
     // teacher-forced ids (dev) need every row's copy distribution; the training loss only the copy-labelled rows
     TRY(copy_score_fwd_ex(s, p.B, p.T, Sm, p.src, p.tgt, c.P + L.wres, c.P + L.bres, p.score, 1, p.mem_valid,
                           argmax_out ? nullptr : c.bt->tar_label, p.V, c.dec_off));
-    TRY(linear(s, c.Td, 2, D, dec, D, c.P + L.wp, c.P + L.bp, p.gate, 2));
+    TRY(linear(c.call, s, c.Td, 2, D, dec, D, c.P + L.wp, c.P + L.bp, p.gate, 2));
     TRY(head_loss(s, c.Td, p.T, p.V, Sm, p.compact_row, p.logits, p.ldl, p.score, p.mem_valid, p.gate,
                   c.bt->tar_label, loss_sum, n_tok, argmax_out, want_grad, c.row_bt));
     return 0;
@@ -1286,7 +1272,7 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     gemm_bf16_group_reset();
     gemm_wgrad_panel_reset();
     gemm_wgrad_panel_scratch(p.panel_scratch, p.panel_floats);
-    red().reset(p.red_buf, p.red_cap);
+    c.call.red.reset(p.red_buf, p.red_cap);
     // ---- head: p.logits / p.score / p.gate now hold dlogits / dscore / dgate_logits -------------------------
     // The vocabulary dgrad ([R, V] x [V, 256], the head's largest product) and the copy branch are independent until
     // both land in ddec: the former runs on the side stream under the latter.
@@ -1300,41 +1286,41 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     if (R > 0) {
         if (so) TRY(aux_fork(s));
         // ddec_rows = dlogits W_out, split over the vocabulary axis
-        if (c.wout_planes) TRY(dgrad_x3_splitk(ss, R, p.V, p.logits, p.ldl, p.WoutTX, p.ddec_c, D, g_dtype == 1));
+        if (c.wout_planes) TRY(dgrad_x3_splitk(ss, R, p.V, p.logits, p.ldl, p.WoutTX, p.ddec_c, D, c.call.dtype == 1));
         else
-        TRY(gemm_any(ss, 0, 0, R, D, p.V, p.logits, p.ldl, c.P + L.wout, D, p.ddec_c, D, nullptr, FIRA_GEMM_ACCUM, 0,
+        TRY(gemm_any(c.call, ss, 0, 0, R, D, p.V, p.logits, p.ldl, c.P + L.wout, D, p.ddec_c, D, nullptr, FIRA_GEMM_ACCUM, 0,
                         nullptr));
         if (so) TRY(side_mark(&ev_dfc));
     }
     // (the vocabulary projection's weight gradient, the step's largest product, is forked HERE, under the copy branch: forked
     // behind the join of the head it ran under the decoder layers' small launches instead and the step lost 0.6 %, same box)
     if (R > 0)
-        TRY(linear_wgrad(s, R, p.V, D, p.logits, p.ldl, (c.rows != nullptr && rows == c.rows) ? p.dec_c : dec, D, G + L.wout,
+        TRY(linear_wgrad(c.call, s, R, p.V, D, p.logits, p.ldl, (c.rows != nullptr && rows == c.rows) ? p.dec_c : dec, D, G + L.wout,
                          G + L.bout, PANEL_VOCAB));
-    if (g_dtype == 0) TRY(rank2_rows(s, c.Td, p.gate, c.P + L.wp, p.ddec));        // ddec = dgate Wp: a rank-2 row kernel
-    else TRY(linear_dgrad(s, c.Td, 2, D, p.gate, 2, c.P + L.wp, p.ddec, D, false));
-    TRY(linear_wgrad_grouped(s, c.Td, 2, D, p.gate, 2, dec, D, G + L.wp, G + L.bp));
+    if (c.call.dtype == 0) TRY(rank2_rows(s, c.Td, p.gate, c.P + L.wp, p.ddec));        // ddec = dgate Wp: a rank-2 row kernel
+    else TRY(linear_dgrad(c.call, s, c.Td, 2, D, p.gate, 2, c.P + L.wp, p.ddec, D, false));
+    TRY(linear_wgrad_grouped(c.call, s, c.Td, 2, D, p.gate, 2, dec, D, G + L.wp, G + L.bp));
     {
         const int nb = copy_score_bwd_blocks(p.B, Sm);
-        float* part = red().alloc((size_t)nb * COPY_PART_STRIDE);
+        float* part = c.call.red.alloc((size_t)nb * COPY_PART_STRIDE);
         TRY(copy_score_bwd_ex(s, p.B, p.T, Sm, p.src, p.tgt, c.P + L.wres, p.score, p.dsrc, p.dtgt, G + L.wres, G + L.bres,
                               p.mem_valid, part, c.dec_off));
         if (part) {
-            red().add(G + L.wres, part, D, nb, COPY_PART_STRIDE);
-            red().add(G + L.bres, part + D, 1, nb, COPY_PART_STRIDE);
+            c.call.red.add(G + L.wres, part, D, nb, COPY_PART_STRIDE);
+            c.call.red.add(G + L.bres, part + D, 1, nb, COPY_PART_STRIDE);
         }
     }
-    TRY(linear_dgrad(s, c.Td, D, D, p.dtgt, D, c.P + L.wt, p.ddec, D, true));
-    TRY(linear_wgrad_grouped(s, c.Td, D, D, p.dtgt, D, dec, D, G + L.wt, nullptr));
+    TRY(linear_dgrad(c.call, s, c.Td, D, D, p.dtgt, D, c.P + L.wt, p.ddec, D, true));
+    TRY(linear_wgrad_grouped(c.call, s, c.Td, D, D, p.dtgt, D, dec, D, G + L.wt, nullptr));
     TRY(rows_move(s, 0, Mc, D, p.dsrc_c, p.dsrc, bt.mem_dst, nullptr));
     // d memory (compact rows) = dsrc Ws + sum_l dKV_l Wkv_l: nothing reads it before the encoder's backward pass, so
     // the whole accumulation lives on the side stream (in order: this product initialises dmem_c, the per-layer
     // products of the decoder loop below add to it)
     if (so) TRY(aux_fork(s));
-    TRY(linear_dgrad(ss, Mc, D, D, p.dsrc_c, D, c.P + L.ws, p.dmem_c, D, false));
+    TRY(linear_dgrad(c.call, ss, Mc, D, D, p.dsrc_c, D, c.P + L.ws, p.dmem_c, D, false));
     // (round 5: LinearSource's weight gradient rides in the decoder's grouped launch -- its own fork was an event record on the
     //  caller's stream right behind the auxiliary stream's)
-    TRY(linear_wgrad_grouped(s, Mc, D, D, p.dsrc_c, D, p.mem_c, D, G + L.ws, nullptr, 8));
+    TRY(linear_wgrad_grouped(c.call, s, Mc, D, D, p.dsrc_c, D, p.mem_c, D, G + L.ws, nullptr, 8));
     if (R > 0) {
         if (ev_dfc) TRY(main_wait(s, ev_dfc, __LINE__));
         TRY(rows_scatter_add_idx(s, R, p.ddec_c, p.ddec, rows));
@@ -1367,13 +1353,13 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     ProfScope prof_region(s, PROF_DEC_REGION, 0.0);      // wall time of the decoder's backward layers (see decoder_forward)
     TRY(lanes_fork(c));                        // (lane 1 starts behind the head's backward kernels)
     // the other streams' launches inside the loop read rows of EVERY lane: they fork from all of them
-    auto aux_fork_all = [&]() -> int { return c.n_lanes > 1 ? lanes_fork_to(c, side().aux) : aux_fork(s); };
+    auto aux_fork_all = [&]() -> int { return c.call.lanes > 1 ? lanes_fork_to(c, side().aux) : aux_fork(s); };
     auto flush_wgrads_all = [&]() -> int {
-        if (c.n_lanes == 1) return flush_grouped_wgrads(s);
+        if (c.call.lanes == 1) return flush_grouped_wgrads(c.call, s);
         SideStream& sd = side();
         if (!(sd.stream && sd.enabled)) return 0;
         TRY(lanes_fork_to(c, sd.stream));
-        return flush_wgrad_queues(sd.stream);
+        return flush_wgrad_queues(c.call, sd.stream);
     };
     for (int l = p.nl - 1; l >= 0; --l) {
         ProfDecoderTag prof_tag;               // data gradients of the M = B*30 products (the grouped wgrads flush later)
@@ -1393,8 +1379,8 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
             if (!(so && (l % 2 == 0 || l == 0))) return 0;
             const int nlay = std::min(2, p.nl - l);
             const size_t o = (size_t)l * 2 * D;
-            if (c.n_lanes > 1 && ev_kv_done[0] && ev_kv_done[1]) {
-                for (int k = 0; k < c.n_lanes; ++k)
+            if (c.call.lanes > 1 && ev_kv_done[0] && ev_kv_done[1]) {
+                for (int k = 0; k < c.call.lanes; ++k)
                     if (hipStreamWaitEvent(ss, ev_kv_done[k], 0) != hipSuccess) return set_err("lane -> auxiliary stream fork failed");
             } else
             TRY(aux_fork_all());
@@ -1402,12 +1388,12 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
             // (round 6) linear_x3_kacc on the planes of the transposed K|V blocks when encoder_forward formed them (kv_x3_on):
             // +1.2 % / +0.9 % at fp32 batch 32 / 64, +1.6 % in bf16; otherwise the fp32 / bf16 GEMM launch
             const int rc_kv = c.kv_planes
-                    ? linear_x3_kacc(ss, Mc, p.dkv_all + o, p.kvp, p.WkvTX + (size_t)l * 2 * 3 * D * D, nlay * 2, p.dmem_c, D, true, g_dtype == 1)
-                    : linear_dgrad(ss, Mc, nlay * 2 * D, D, p.dkv_all + o, p.kvp, c.P + L.wkv_all + o * D, p.dmem_c, D, true);
+                    ? linear_x3_kacc(ss, Mc, p.dkv_all + o, p.kvp, p.WkvTX + (size_t)l * 2 * 3 * D * D, nlay * 2, p.dmem_c, D, true, c.call.dtype == 1)
+                    : linear_dgrad(c.call, ss, Mc, nlay * 2 * D, D, p.dkv_all + o, p.kvp, c.P + L.wkv_all + o * D, p.dmem_c, D, true);
             prof_decoder_tag(+1);
             return rc_kv;
         };
-        for (int k = 0; k < c.n_lanes; ++k) {
+        for (int k = 0; k < c.call.lanes; ++k) {
             const Lane& ln = c.lanes[k];
             hipStream_t ls = ln.s;
             const size_t r0 = (size_t)ln.r0;
@@ -1417,40 +1403,40 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
             const bool q = k == 0;             // the weight gradients read the rows of all lanes: queued once
             // FeedForward (gnn_transformer.py:170-174): LayerNorm backward + d hidden = (dYf W2) masked by the saved activation > 0
             // (ReLU backward in the GEMM epilogue)
-            TRY(ln_bwd_dgrad(ls, nr, p.F, bx + r0 * D, e.s_f + r0 * D, e.st_f + r0 * 2, c.P + w.lnf_g, by + r0 * D, g.dYf + r0 * D,
+            TRY(ln_bwd_dgrad(c.call, ls, nr, p.F, bx + r0 * D, e.s_f + r0 * D, e.st_f + r0 * 2, c.P + w.lnf_g, by + r0 * D, g.dYf + r0 * D,
                              G + w.lnf_g, G + w.lnf_b, c.p_drop, c.seed, site(l, SITE_FFN), c.P + w.w2, p.F, g.dh + r0 * p.F, p.F,
                              e.h + r0 * p.F, idx0));
-            if (q) TRY(linear_wgrad_grouped(s, c.Td, D, p.F, g.dYf, D, e.h, p.F, G + w.w2, G + w.b2));
-            if (q) TRY(linear_wgrad_grouped(s, c.Td, p.F, D, g.dh, p.F, e.x_c, D, G + w.w1, G + w.b1));
-            TRY(linear_dgrad(ls, nr, p.F, D, g.dh + r0 * p.F, p.F, c.P + w.w1, by + r0 * D, D, true));               // by = d x_c
+            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, D, p.F, g.dYf, D, e.h, p.F, G + w.w2, G + w.b2));
+            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, p.F, D, g.dh, p.F, e.x_c, D, G + w.w1, G + w.b1));
+            TRY(linear_dgrad(c.call, ls, nr, p.F, D, g.dh + r0 * p.F, p.F, c.P + w.w1, by + r0 * D, D, true));               // by = d x_c
             // cross attention: LayerNorm backward + d ao2 = dYc Wo_c
-            TRY(ln_bwd_dgrad(ls, nr, D, by + r0 * D, e.s_c + r0 * D, e.st_c + r0 * 2, c.P + w.lnc_g, bz + r0 * D, g.dYc + r0 * D,
+            TRY(ln_bwd_dgrad(c.call, ls, nr, D, by + r0 * D, e.s_c + r0 * D, e.st_c + r0 * 2, c.P + w.lnc_g, bz + r0 * D, g.dYc + r0 * D,
                              G + w.lnc_g, G + w.lnc_b, c.p_drop, c.seed, site(l, SITE_CROSS), c.P + w.wo_c, D, bx + r0 * D, D, nullptr,
                              idx0));                                                                              // bx = d ao2
-            if (q) TRY(linear_wgrad_grouped(s, c.Td, D, D, g.dYc, D, e.ao2, D, G + w.wo_c, G + w.bo_c));
+            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, D, D, g.dYc, D, e.ao2, D, G + w.wo_c, G + w.bo_c));
             // (ragged key rows: dkv_all holds the computed memory rows only, every one of them written by this launch)
             TRY(attention_bwd(ls, ln.nb, H, p.T, Sm, e.qc, D, p.kv_all + l * 2 * D, p.kvp, p.kv_all + l * 2 * D + D, p.kvp,
                               p.mem_valid_c, 0, 0, e.ao2, D, bx, D, g.dq, D, p.dkv_all + l * 2 * D, p.kvp,
-                              p.dkv_all + l * 2 * D + D, p.kvp, q_off, 0, attn_bf16(), p.mem_off + ln.b0));
-            if (c.n_lanes == 1) TRY(dmem_pair());
+                              p.dkv_all + l * 2 * D + D, p.kvp, q_off, 0, attn_bf16(c.call), p.mem_off + ln.b0));
+            if (c.call.lanes == 1) TRY(dmem_pair());
             else if (so && l % 2 == 0 && k < 2) {
                 ev_kv_done[k] = side().ev();
                 if (hipEventRecord(ev_kv_done[k], ls) != hipSuccess) return set_err("lane event record failed");
             }
-            if (q) TRY(linear_wgrad_grouped(s, c.Td, D, D, g.dq, D, e.x_a, D, G + w.wq_c, G + w.bq_c));
-            TRY(linear_dgrad(ls, nr, D, D, g.dq + r0 * D, D, c.P + w.wq_c, bz + r0 * D, D, true));                 // bz = d x_a
+            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, D, D, g.dq, D, e.x_a, D, G + w.wq_c, G + w.bq_c));
+            TRY(linear_dgrad(c.call, ls, nr, D, D, g.dq + r0 * D, D, c.P + w.wq_c, bz + r0 * D, D, true));                 // bz = d x_a
             // self attention: LayerNorm backward + d ao = dYs Wo_s
-            TRY(ln_bwd_dgrad(ls, nr, D, bz + r0 * D, e.s_a + r0 * D, e.st_a + r0 * 2, c.P + w.lns_g, by + r0 * D, g.dYs + r0 * D,
+            TRY(ln_bwd_dgrad(c.call, ls, nr, D, bz + r0 * D, e.s_a + r0 * D, e.st_a + r0 * 2, c.P + w.lns_g, by + r0 * D, g.dYs + r0 * D,
                              G + w.lns_g, G + w.lns_b, c.p_drop, c.seed, site(l, SITE_SELF), c.P + w.wo_s, D, bx + r0 * D, D, nullptr,
                              idx0));                                                                              // bx = d ao
-            if (q) TRY(linear_wgrad_grouped(s, c.Td, D, D, g.dYs, D, e.ao, D, G + w.wo_s, G + w.bo_s));
+            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, D, D, g.dYs, D, e.ao, D, G + w.wo_s, G + w.bo_s));
             TRY(attention_bwd(ls, ln.nb, H, p.T, p.T, e.qkv, 3 * D, e.qkv + D, 3 * D, e.qkv + 2 * D, 3 * D,
                               p.tar_valid + (size_t)ln.b0 * p.T, 1, 0, e.ao, D, bx, D, g.dqkv, 3 * D, g.dqkv + D, 3 * D, g.dqkv + 2 * D,
-                              3 * D, q_off, 1, attn_bf16()));
-            if (q) TRY(linear_wgrad_grouped(s, c.Td, 3 * D, D, g.dqkv, 3 * D, x_in, D, G + w.wqkv, G + w.bqkv));
-            TRY(linear_dgrad(ls, nr, 3 * D, D, g.dqkv + r0 * 3 * D, 3 * D, c.P + w.wqkv, by + r0 * D, D, true));   // by = d x_in
+                              3 * D, q_off, 1, attn_bf16(c.call)));
+            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, 3 * D, D, g.dqkv, 3 * D, x_in, D, G + w.wqkv, G + w.bqkv));
+            TRY(linear_dgrad(c.call, ls, nr, 3 * D, D, g.dqkv + r0 * 3 * D, 3 * D, c.P + w.wqkv, by + r0 * D, D, true));   // by = d x_in
         }
-        if (c.n_lanes > 1) TRY(dmem_pair());   // (behind the layer of every lane: dkv_all's column block is complete)
+        if (c.call.lanes > 1) TRY(dmem_pair());   // (behind the layer of every lane: dkv_all's column block is complete)
         if (dec_every > 0 && l % dec_every == 0 && side().stream && side().enabled) {
             // the weight gradients of the last dec_every layers: one grouped launch + their row block of the stacked K|V weight
             const int nlay = std::min(dec_every, p.nl - l);
@@ -1458,7 +1444,7 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
             prof_decoder_tag(-1);               // weight gradients: not among the decoder's forward / data-gradient products
             int rc_w = flush_wgrads_all();
             if (!rc_w)
-                rc_w = wgrad_on(side().stream, PANEL_KV, Mc, nlay * 2 * D, D, p.dkv_all + o, p.kvp, p.mem_c, D, G + L.wkv_all + o * D,
+                rc_w = wgrad_on(c.call, side().stream, PANEL_KV, Mc, nlay * 2 * D, D, p.dkv_all + o, p.kvp, p.mem_c, D, G + L.wkv_all + o * D,
                                 G + L.bkv_all + o);
             prof_decoder_tag(+1);
             TRY(rc_w);
@@ -1468,7 +1454,7 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     TRY(lanes_join(c));
     }
     const float* dy = bx;
-    TRY(flush_grouped_wgrads(s));                                  // the decoder's and the head's small weight gradients
+    TRY(flush_grouped_wgrads(c.call, s));                                  // the decoder's and the head's small weight gradients
     // decoder embedding.  The table has no padding_idx (gnn_transformer.py:92-93), but rows of padded target positions
     // carry an exactly-zero gradient (never attended as keys, zero loss weight): skipping id 0 only drops the
     // hundreds of serialised atomic additions of 0.0 onto table row 0.
@@ -1484,17 +1470,17 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     if (so) {
         TRY(side_mark(&ev_dmem));                // dmem_c is complete at this point of the auxiliary stream
     } else {
-        TRY(linear_dgrad(s, Mc, KV, D, p.dkv_all, p.kvp, c.P + L.wkv_all, p.dmem_c, D, true));
+        TRY(linear_dgrad(c.call, s, Mc, KV, D, p.dkv_all, p.kvp, c.P + L.wkv_all, p.dmem_c, D, true));
     }
     // (round 5: no fork of its own -- the weight-gradient stream waited for the caller's stream at the grouped launch above, and
     //  dkv_all was complete by then; with dec_every > 0 it went out in row blocks inside the loop)
     if (!(side().stream && side().enabled))
-        TRY(linear_wgrad(s, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all, PANEL_KV));
+        TRY(linear_wgrad(c.call, s, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all, PANEL_KV));
     else if (dec_every == 0)
-        TRY(wgrad_on(side().stream, PANEL_KV, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all));
+        TRY(wgrad_on(c.call, side().stream, PANEL_KV, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all));
     // decoder LayerNorms, copy head: their partial rows were written before the fork of the weight gradient above, and only
     // the end of the step (or the mid-event below, which waits for this stream) reads the sums: off the dependent chain
-    TRY(deferred_reduce(side().stream && side().enabled ? side().stream : s, red().tab));
+    TRY(deferred_reduce(side().stream && side().enabled ? side().stream : s, c.call.red.tab));
     // every gradient of [0, split) is final once the weight-gradient stream has passed this point (its launches above: the
     // vocabulary / copy / decoder weight gradients, the decoder embedding, the stacked K|V weight, the deferred column sums;
     // the auxiliary stream writes data gradients only)
@@ -1552,7 +1538,7 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         float* dc21 = p.dc21 + (size_t)l * D;
         bool sums = false;
         const bool room = unfold_tab.n < 16;     // (asked for only when the closing unfold launch can take the layer)
-        TRY(ln_bwd(s, Nc, dXn, e.s2, e.st2, c.P + w.ln2g, other, g.dY2, G + w.ln2g, G + w.ln2b, c.p_gcn,
+        TRY(ln_bwd(c.call, s, Nc, dXn, e.s2, e.st2, c.P + w.ln2g, other, g.dY2, G + w.ln2g, G + w.ln2b, c.p_gcn,
                               c.seed, site(l, SITE_GCN), nullptr, room ? p.rsum : nullptr, G + w.fc2b, dc21, &sums));
         if (sums) unfold_tab.e[unfold_tab.n++] = UnfoldEntry{c.P + w.fc2w, c.P + w.fc1b, dc21, G + w.fc2w, G + w.fc1b};
         // GCN, folded form (see encoder_forward): Y = U W21^T + r c^T + b2 with U = A_hat X
@@ -1583,18 +1569,18 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
             if (!sums) TRY(gcn_bias_unfold(ws, c.P + w.fc2w, c.P + w.fc1b, dc21, G + w.fc2w, G + w.fc1b));
             return 0;
         };
-        if (gcn_fused_on()) {
+        if (c.call.gcn_fused()) {
             // one launch: V = A_hat dY (stored in e.Z, which the fused forward pass does not use), other = ds + V W21.
             // The weight gradient follows from the same V: dW21 = dY^T (A_hat X) = (A_hat dY)^T X = V^T X
-            TRY(gcn_fused_bwd(s, Nc, bt.rowptr, bt.col, bt.val, g.dY2, p.W21 + (size_t)l * D * D, e.Z, other, g_dtype == 1,
-                              gcn_x3_on(p.nl) ? p.W21tx + (size_t)l * 3 * D * D : nullptr));
-            TRY(enc_wgrad(s, Nc, D, D, e.Z, D, p.X[l], D, dW21, nullptr));
+            TRY(gcn_fused_bwd(s, Nc, bt.rowptr, bt.col, bt.val, g.dY2, p.W21 + (size_t)l * D * D, e.Z, other, c.call.dtype == 1,
+                              gcn_x3_on(c.call, p.nl) ? p.W21tx + (size_t)l * 3 * D * D : nullptr));
+            TRY(enc_wgrad(c.call, s, Nc, D, D, e.Z, D, p.X[l], D, dW21, nullptr));
             if (!sums) TRY(colsum(s, Nc, D, g.dY2, D, G + w.fc2b));     // (db2 = column sums of dY, not of V)
             if (!grouped) TRY(unfold());
         } else {
-        TRY(enc_wgrad(s, Nc, D, D, g.dY2, D, e.Z, D, dW21, sums ? nullptr : G + w.fc2b));
+        TRY(enc_wgrad(c.call, s, Nc, D, D, g.dY2, D, e.Z, D, dW21, sums ? nullptr : G + w.fc2b));
         if (!grouped) TRY(unfold());
-        TRY(linear_dgrad(s, Nc, D, D, g.dY2, D, p.W21 + (size_t)l * D * D, p.dNB2, D, false));  // dU
+        TRY(linear_dgrad(c.call, s, Nc, D, D, g.dY2, D, p.W21 + (size_t)l * D * D, p.dNB2, D, false));  // dU
         TRY(csr_spmm_ex(s, Nc, bt.rowptr, bt.col, bt.val, p.dNB2, D, other, D, 0, 1, 1, nullptr));   // other = ds + A_hat dU
         }
         // Combination on the code rows, in place inside `other` through the code-row map: the LayerNorm backward reads
@@ -1603,42 +1589,42 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         // deferred reduction has room for its partial rows (both blocks or neither: six table rows and nb * 6 * D floats asked
         // for at once); otherwise the four launches.
         const int nb_comb = comb_fused_bwd_parts();
-        float* part_ln = red().alloc((size_t)nb_comb * 6 * D, 6);
+        float* part_ln = c.call.red.alloc((size_t)nb_comb * 6 * D, 6);
         const bool comb_done = part_ln != nullptr;
         if (comb_done) {
             float* part_v = part_ln + (size_t)nb_comb * 2 * D;
             TRY(comb_fused_bwd(s, Cc, other, bt.code_rows, e.s1, e.st1, c.P + w.ln1g, c.P + w.wo, c.P + w.wqk, e.qk,
                                p.vtab_all + l * D, p.nl * D, bt.code_mark, g.dYc, g.dqk, part_ln, part_v, c.p_drop, c.seed,
-                               site(l, SITE_GATE), site(l, SITE_COMB_OUT), g_dtype == 1,
+                               site(l, SITE_GATE), site(l, SITE_COMB_OUT), c.call.dtype == 1,
                                comb_x3_on(p.nl) ? p.WcTX + (size_t)l * 9 * D * D : nullptr));
-            red().add(G + w.ln1g, part_ln, D, nb_comb, 2 * D);
-            red().add(G + w.ln1b, part_ln + D, D, nb_comb, 2 * D);
+            c.call.red.add(G + w.ln1g, part_ln, D, nb_comb, 2 * D);
+            c.call.red.add(G + w.ln1b, part_ln + D, D, nb_comb, 2 * D);
             for (int k = 0; k < 4; ++k)
-                red().add(p.dvtab_all + (size_t)k * p.nl * D + l * D, part_v + k * D, D, nb_comb, 4 * D);
-            TRY(enc_wgrad(s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
+                c.call.red.add(p.dvtab_all + (size_t)k * p.nl * D + l * D, part_v + k * D, D, nb_comb, 4 * D);
+            TRY(enc_wgrad(c.call, s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
         } else {
-        TRY(ln_bwd(s, Cc, other, e.s1, e.st1, c.P + w.ln1g, other, g.dYc, G + w.ln1g, G + w.ln1b, c.p_drop,
+        TRY(ln_bwd(c.call, s, Cc, other, e.s1, e.st1, c.P + w.ln1g, other, g.dYc, G + w.ln1g, G + w.ln1b, c.p_drop,
                               c.seed, site(l, SITE_COMB_OUT), bt.code_rows));
-        TRY(enc_wgrad(s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
-        TRY(linear_dgrad(s, Cc, D, D, g.dYc, D, c.P + w.wo, p.dCB_a, D, false));               // d c
+        TRY(enc_wgrad(c.call, s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
+        TRY(linear_dgrad(c.call, s, Cc, D, D, g.dYc, D, c.P + w.wo, p.dCB_a, D, false));               // d c
         {
             const int nb = combination_bwd_blocks(Cc);
-            float* part = red().alloc((size_t)nb * 4 * D);
+            float* part = c.call.red.alloc((size_t)nb * 4 * D);
             TRY(combination_bwd(s, Cc, e.qk, p.vtab_all + l * D, p.nl * D, bt.code_mark, p.dCB_a, g.dqk,
                                 p.dvtab_all + l * D, p.nl * D, c.p_drop, c.seed, site(l, SITE_GATE), part));
             if (part)
                 for (int k = 0; k < 4; ++k)
-                    red().add(p.dvtab_all + (size_t)k * p.nl * D + l * D, part + k * D, D, nb, 4 * D);
+                    c.call.red.add(p.dvtab_all + (size_t)k * p.nl * D + l * D, part + k * D, D, nb, 4 * D);
         }
         }
-        TRY(enc_wgrad(s, Cc, 2 * D, D, g.dqk, 2 * D, e.Xc, D, G + w.wqk, G + w.bqk));
+        TRY(enc_wgrad(c.call, s, Cc, 2 * D, D, g.dqk, 2 * D, e.Xc, D, G + w.wqk, G + w.bqk));
         if (grouped) {                           // the layer's three weight gradients: one fork, one launch, then the unfold
             // (one launch for every n layers' gradients: enc_wgrad_every)
-            if ((p.nl - l) % wgrad_every == 0 || l == 0) { TRY(flush_grouped_wgrads(s)); flushed = true; }
+            if ((p.nl - l) % wgrad_every == 0 || l == 0) { TRY(flush_grouped_wgrads(c.call, s)); flushed = true; }
             TRY(unfold());
         }
         if (!comb_done)
-            TRY(gemm_any(s, 0, 0, Cc, D, 2 * D, g.dqk, 2 * D, c.P + w.wqk, D, other, D, nullptr, FIRA_GEMM_ACCUM, 0, nullptr,
+            TRY(gemm_any(c.call, s, 0, 0, Cc, D, 2 * D, g.dqk, 2 * D, c.P + w.wqk, D, other, D, nullptr, FIRA_GEMM_ACCUM, 0, nullptr,
                          bt.code_rows));                                                       // other = dX[l]
         float* tmp = dXn; dXn = other; other = tmp;
     }
@@ -1651,7 +1637,7 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         const bool ax = side_on();
         hipStream_t rs = ax ? side().aux : s;
         if (ax) TRY(aux_fork(s));
-        TRY(deferred_reduce(rs, red().tab));
+        TRY(deferred_reduce(rs, c.call.red.tab));
         // value projection of the mark table: vtab_all = mark_emb W2_all^T + b2_all
         TRY(gemm_f32_ex(rs, 1, 0, p.nl * D, D, 4, p.dvtab_all, p.nl * D, c.P + L.mark_emb, D, G + L.w2_all, D, nullptr,
                         FIRA_GEMM_ACCUM, 1, G + L.b2_all));
@@ -1774,7 +1760,6 @@ static int check_batch(const fira_batch* b) {
                  "batch has null node lists (node_rows / code_rows / code_mark / mem_rows / mem_dst)");
     FIRA_REQUIRE(b->n_nodes > 0 && b->n_code > 0 && b->n_mem > 0 && b->n_code <= b->n_nodes && b->n_mem <= b->n_nodes,
                  "inconsistent node counts %d / %d / %d", b->n_nodes, b->n_code, b->n_mem);
-    note_graph_density(b);
     return 0;
 }
 static int check_counts(const fira_batch* b, const Plan& p) {
@@ -1833,19 +1818,14 @@ size_t fira_decode_workspace_bytes_ex(const fira_dims* d, int B, int n_beam, int
 
 // fira_train_step_begin leaves its step here (per thread) for fira_train_step_end: the plan of the workspace, the call's
 // context (a copy of the batch descriptor: its arrays must stay valid until the second call) and what the two halves of the
-// backward pass share.  The dtype / shadow scopes of the first call are re-entered by the second.
+// backward pass share.  The step owns its state (Ctx::call travels with the copy): other library calls may run on the thread
+// between the two halves.
 struct PendingStep {
     bool active = false;
     Plan plan;
     fira_batch batch;
     Ctx ctx{};
     BwdMid mid;
-    int dtype = 0;
-    const float* params = nullptr;
-    const ShadowTable* tab = nullptr;
-    const float* W21 = nullptr;
-    int64_t W21n = 0;
-    const uint16_t *W21b = nullptr, *W21bT = nullptr;
 };
 static thread_local PendingStep g_pending;
 
@@ -1866,14 +1846,15 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
           opts ? opts->seed : 0};
     FIRA_REQUIRE(c.p_drop >= 0.f && c.p_drop < 1.f && c.p_gcn >= 0.f && c.p_gcn < 1.f, "dropout must be in [0,1)");
     FIRA_REQUIRE(!opts || opts->dtype == 0 || opts->dtype == 1, "fira_train_opts.dtype must be 0 (fp32) or 1 (bf16)");
-    DtypeScope dtype_scope(opts ? opts->dtype : 0);
     TRY(side().init());
     const bool bf16 = opts && opts->dtype == 1;
     const ShadowTable* tab = bf16 ? shadow_table(*L) : nullptr;
-    ShadowScope shadow_scope(params, L->total, bf16 ? p.wb : nullptr, bf16 ? p.wbt : nullptr, tab);
+    c.call.dtype = bf16 ? 1 : 0;
+    c.call.dense_graphs = graphs_dense(batch);
+    c.call.shadows(params, L->total, bf16 ? p.wb : nullptr, bf16 ? p.wbt : nullptr, tab);
     // (round 5) the shadow refresh on the auxiliary stream (see Ctx::shadow_tab) where the fused Combination / GCN kernels of every
     // layer read the fp32 weights themselves; otherwise at the head of the caller's stream
-    const bool defer_sh = bf16 && side_on() && gcn_fused_on() && L->d.n_layer <= 8;
+    const bool defer_sh = bf16 && side_on() && c.call.gcn_fused() && L->d.n_layer <= 8;
     if (bf16 && !defer_sh) TRY(weight_shadows(c.s, *tab, params, p.wb, p.wbt));
     if (defer_sh) c.shadow_tab = tab;
     // computed target rows: the decoder / head run on the prefix rows the batch lists (fira_batch.dec_off)
@@ -1936,10 +1917,6 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
         ps.ctx = c;
         ps.ctx.pl = &ps.plan;
         ps.ctx.bt = &ps.batch;
-        ps.dtype = opts ? opts->dtype : 0;
-        ps.params = params;
-        ps.tab = tab;
-        ps.W21 = g_W21; ps.W21n = g_W21n; ps.W21b = g_W21b; ps.W21bT = g_W21bT;
         ps.active = true;
         return 0;
     }
@@ -1962,11 +1939,12 @@ int fira_ffn_fwd(void* stream, int M, int F, const float* x, const float* w1, co
                  uint64_t seed, uint32_t site_id, int dtype) {
     FIRA_REQUIRE(x && w1 && b1 && w2 && b2 && gamma && beta && h && sum && y && stats && M > 0 && F > 0, "fira_ffn_fwd: bad argument");
     FIRA_REQUIRE(dropout >= 0.f && dropout < 1.f && (dtype == 0 || dtype == 1), "fira_ffn_fwd: bad dropout / dtype");
-    DtypeScope dtype_scope(dtype);
+    Call call;
+    call.dtype = dtype;
     hipStream_t s = (hipStream_t)stream;
     const int D = FIRA_D;
-    TRY(linear(s, M, F, D, x, D, w1, b1, h, F, FIRA_GEMM_RELU));
-    return linear_ln(s, M, F, h, F, w2, b2, x, gamma, beta, sum, y, stats, dropout, seed, site_id);
+    TRY(linear(call, s, M, F, D, x, D, w1, b1, h, F, FIRA_GEMM_RELU));
+    return linear_ln(call, s, M, F, h, F, w2, b2, x, gamma, beta, sum, y, stats, dropout, seed, site_id);
 }
 // Its backward: dy = gradient w.r.t. y.  dx [M,256] is WRITTEN (gradient w.r.t. x: residual branch + through the two
 // products); dw1 [F,256], db1 [F], dw2 [256,F], db2 [256], dgamma, dbeta [256] are ACCUMULATED into.  dyf_ws [M,256] and
@@ -1979,15 +1957,15 @@ int fira_ffn_bwd(void* stream, int M, int F, const float* dy, const float* x, co
                  dbeta && M > 0 && F > 0, "fira_ffn_bwd: bad argument");
     FIRA_REQUIRE(dx != dy, "fira_ffn_bwd: dx must not alias dy");
     FIRA_REQUIRE(dropout >= 0.f && dropout < 1.f && (dtype == 0 || dtype == 1), "fira_ffn_bwd: bad dropout / dtype");
-    DtypeScope dtype_scope(dtype);
+    Call call;                                  // (stand-alone: its collector has no buffer -- column sums by atomics, nothing deferred)
+    call.dtype = dtype;
     hipStream_t s = (hipStream_t)stream;
     const int D = FIRA_D;
-    red().reset(nullptr, 0);                    // stand-alone: column sums by atomics, nothing deferred
     // LayerNorm backward (residual-branch gradient -> dx, un-dropped branch gradient -> dyf_ws) + d hidden = (dyf W2) where h > 0
-    TRY(ln_bwd_dgrad(s, M, F, dy, sum, stats, gamma, dx, dyf_ws, dgamma, dbeta, dropout, seed, site_id, w2, F, dh_ws, F, h));
-    TRY(gemm_any(s, 1, 0, D, F, M, dyf_ws, D, h, F, dw2, F, nullptr, FIRA_GEMM_ACCUM, 0, db2));     // dW2 += dyf^T h, db2 += colsum
-    TRY(gemm_any(s, 1, 0, F, D, M, dh_ws, F, x, D, dw1, D, nullptr, FIRA_GEMM_ACCUM, 0, db1));      // dW1 += dh^T x, db1 += colsum
-    return linear_dgrad(s, M, F, D, dh_ws, F, w1, dx, D, true);                                      // dx += dh W1
+    TRY(ln_bwd_dgrad(call, s, M, F, dy, sum, stats, gamma, dx, dyf_ws, dgamma, dbeta, dropout, seed, site_id, w2, F, dh_ws, F, h));
+    TRY(gemm_any(call, s, 1, 0, D, F, M, dyf_ws, D, h, F, dw2, F, nullptr, FIRA_GEMM_ACCUM, 0, db2));     // dW2 += dyf^T h, db2 += colsum
+    TRY(gemm_any(call, s, 1, 0, F, D, M, dh_ws, F, x, D, dw1, D, nullptr, FIRA_GEMM_ACCUM, 0, db1));      // dW1 += dh^T x, db1 += colsum
+    return linear_dgrad(call, s, M, F, D, dh_ws, F, w1, dx, D, true);                                      // dx += dh W1
 }
 // Output head for teacher-forced / search decoding (Model.py:54 + the arg-max of Model.py:85, run_model.py:305): logits =
 // x Wout^T + bout into logits_ws [R, ldl >= V] and, per row, the k largest logits (value descending, ties by ascending id).
@@ -1995,9 +1973,10 @@ int fira_head_topk(void* stream, int R, int V, int k, const float* x, const floa
                    int ldl, int32_t* ids, float* vals, int dtype) {
     FIRA_REQUIRE(x && wout && logits_ws && ids && vals && R > 0 && V > 0 && ldl >= V, "fira_head_topk: bad argument");
     FIRA_REQUIRE(dtype == 0 || dtype == 1, "fira_head_topk: bad dtype");
-    DtypeScope dtype_scope(dtype);
+    Call call;
+    call.dtype = dtype;
     hipStream_t s = (hipStream_t)stream;
-    TRY(linear(s, R, V, FIRA_D, x, FIRA_D, wout, bout, logits_ws, ldl));
+    TRY(linear(call, s, R, V, FIRA_D, x, FIRA_D, wout, bout, logits_ws, ldl));
     return row_topk(s, R, V, k, logits_ws, ldl, ids, vals);
 }
 
@@ -2012,7 +1991,6 @@ int fira_train_step_begin(void* stream, const fira_dims* d, const fira_batch* ba
 // (v10) the data-parallel step with the row-sparse update of the word tables: _begin_rows takes the optimizer's values for the
 // lazy reads of its forward pass (nothing is updated there), _end_rows updates decoder.embedding by rows inside the library;
 // encoder.embedding is the caller's (fira_adam_rows_step with tables = 2 behind the late bucket's all-reduce)
-static thread_local int32_t* g_end_row_step = nullptr;
 int fira_train_step_begin_rows(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
                                void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
                                int32_t* n_tok, void* mid_event, const fira_adam_opts* adam, int32_t* row_step) {
@@ -2024,36 +2002,34 @@ int fira_train_step_begin_rows(void* stream, const fira_dims* d, const fira_batc
     return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, mid_event, nullptr,
                       adam, true, row_step);
 }
-int fira_train_step_end_rows(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count,
-                             int32_t* row_step) {
-    FIRA_REQUIRE(adam && row_step, "fira_train_step_end_rows: bad argument");
-    g_end_row_step = row_step;
-    const int rc = fira_train_step_end(stream, params, adam, early_event, count);
-    g_end_row_step = nullptr;
-    return rc;
-}
-int fira_train_step_end(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count) {
+// the second half of the step begun on this thread; row_step: see fira_train_step_end_rows
+static int train_step_end(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count,
+                          int32_t* row_step) {
     PendingStep& ps = g_pending;
     FIRA_REQUIRE(ps.active, "fira_train_step_end: no step begun on this thread (fira_train_step_begin)");
     ps.active = false;
     FIRA_REQUIRE((hipStream_t)stream == ps.ctx.s, "fira_train_step_end: not the stream the step was begun on");
     FIRA_REQUIRE(!adam || (adam->m && adam->v && adam->step >= 1 && params), "fira_train_step_end: bad Adam arguments");
     TRY(adam_sched_check(adam));
-    FIRA_REQUIRE(!params || params == ps.params, "fira_train_step_end: not the parameter buffer the step was begun with");
-    DtypeScope dtype_scope(ps.dtype);
-    const bool bf16 = ps.dtype == 1;
-    ShadowScope shadow_scope(ps.params, ps.ctx.L->total, bf16 ? ps.plan.wb : nullptr, bf16 ? ps.plan.wbt : nullptr, ps.tab);
-    g_W21 = ps.W21; g_W21n = ps.W21n; g_W21b = ps.W21b; g_W21bT = ps.W21bT;
-    Ctx& c = ps.ctx;
+    FIRA_REQUIRE(!params || params == ps.ctx.P, "fira_train_step_end: not the parameter buffer the step was begun with");
+    Ctx& c = ps.ctx;                         // (the step's own state: dtype, shadows, graph density and pending reductions included)
     c.adam = adam;
     c.Pw = params;
-    c.row_step = g_end_row_step;             // (fira_train_step_end_rows; nullptr: every row of decoder.embedding, as before)
+    c.row_step = row_step;                   // (fira_train_step_end_rows; nullptr: every row of decoder.embedding, as before)
     c.adam_a_only = true;
     c.ev_early = (hipEvent_t)early_event;
     c.count = count;
     TRY(backward_encoder(c, ps.mid));
     if (wait_probe().enabled() && ++wait_probe().calls == 20) wait_probe().report();
     return 0;
+}
+int fira_train_step_end_rows(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count,
+                             int32_t* row_step) {
+    FIRA_REQUIRE(adam && row_step, "fira_train_step_end_rows: bad argument");
+    return train_step_end(stream, params, adam, early_event, count, row_step);
+}
+int fira_train_step_end(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count) {
+    return train_step_end(stream, params, adam, early_event, count, nullptr);
 }
 
 int fira_train_step(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads, void* workspace,
@@ -2143,7 +2119,6 @@ int fira_forward_dev(void* stream, const fira_dims* d, const fira_batch* batch, 
     const Layout* L = get_layout(d);
     if (!L) return 1;
     FIRA_REQUIRE(dtype == 0 || dtype == 1, "fira_forward_dev: dtype must be 0 (fp32) or 1 (bf16)");
-    DtypeScope dtype_scope(dtype);
     TRY(check_batch(batch));
     FIRA_REQUIRE(batch->tar && batch->tar_label && params && workspace && ids_out, "null pointer argument");
     Plan p;
@@ -2155,7 +2130,9 @@ int fira_forward_dev(void* stream, const fira_dims* d, const fira_batch* batch, 
     c.loss_sum = loss_sum;
     c.n_tok = n_tok;
     const ShadowTable* tab = dtype == 1 ? shadow_table(*L) : nullptr;
-    ShadowScope shadow_scope(params, L->total, dtype == 1 ? p.wb : nullptr, dtype == 1 ? p.wbt : nullptr, tab);
+    c.call.dtype = dtype;
+    c.call.dense_graphs = graphs_dense(batch);
+    c.call.shadows(params, L->total, dtype == 1 ? p.wb : nullptr, dtype == 1 ? p.wbt : nullptr, tab);
     if (dtype == 1) TRY(weight_shadows(c.s, *tab, params, p.wb, p.wbt));
     TRY(encoder_forward(c, true));
     TRY(decoder_forward(c));
@@ -2183,6 +2160,7 @@ int fira_decode_begin_ex(void* stream, const fira_dims* d, const fira_batch* bat
     b2.tar = nullptr;
     Ctx c{(hipStream_t)stream, L, &b2, params, nullptr, &p, 0.f, 0.f, 0};
     c.serial = true;
+    c.call.dense_graphs = graphs_dense(batch);
     TRY(check_counts(batch, p));
     TRY(encoder_forward(c, false));     // also leaves kv_all (cross K|V of all layers) and src = LinearSource(memory)
     TRY(rows_move(c.s, 1, b2.n_mem, FIRA_D, p.mem, p.mem_c, nullptr, b2.mem_dst));   // dense memory view for callers
@@ -2219,6 +2197,7 @@ static int decode_step_body(hipStream_t s, const fira_dims* d, const float* para
     const Layout* Lp = get_layout(d);
     if (!Lp) return 1;
     const Layout& L = *Lp;
+    const Call call{};                          // fp32: the search runs the reference's arithmetic
     FIRA_REQUIRE(params && workspace && tokens && B > 0 && n_beam >= 1, "bad argument");
     FIRA_REQUIRE(step >= 0 && step < d->tar_len, "step %d out of range", step);
     FIRA_REQUIRE((flags & ~FIRA_DECODE_KV_BF16) == 0, "%s: unknown flags %d", who, flags);
@@ -2239,7 +2218,6 @@ static int decode_step_body(hipStream_t s, const fira_dims* d, const float* para
     const float *pend_g = nullptr, *pend_b = nullptr;
     float* pend_y = nullptr;
     bool pending = false;
-    DtypeScope dtype_scope(0);                  // the search runs the reference's fp32 arithmetic
     // (round 6) the self-attention block as one launch per layer (decode_self_block: 0.359 -> 0.333 ms per greedy step at batch
     // 64); it needs the model's 8 x 32 heads and <= 32 keys -- otherwise the three launches
     const bool self_block = H * FIRA_DH == FIRA_D && H == 8 && T <= 32 && p.nl <= 12;
@@ -2251,16 +2229,16 @@ static int decode_step_body(hipStream_t s, const fira_dims* d, const float* para
             pending = false;
             if (rc || fused) return rc;
         }
-        return linear(s, BR, N, D, xin, D, W, b, Y, N, flags);
+        return linear(call, s, BR, N, D, xin, D, W, b, Y, N, flags);
     };
     auto close_block = [&](int K, const float* X, const float* W, const float* b, const float* res, const float* g, const float* be,
                            float* y, bool may_defer) -> int {
         int rc = 0;
-        if (may_defer && linear_presum(s, BR, K, X, K, W, b, res, dp.s, 0.f, 0, 0, &rc)) {
+        if (may_defer && linear_presum(call, s, BR, K, X, K, W, b, res, dp.s, 0.f, 0, 0, &rc)) {
             pending = true; pend_g = g; pend_b = be; pend_y = y;
             return rc;
         }
-        return linear_ln(s, BR, K, X, K, W, b, res, g, be, dp.s, y, nullptr, 0.f, 0, 0);
+        return linear_ln(call, s, BR, K, X, K, W, b, res, g, be, dp.s, y, nullptr, 0.f, 0, 0);
     };
     for (int l = 0; l < p.nl; ++l) {
         const DecLayer& w = L.dec[l];
@@ -2297,7 +2275,7 @@ static int decode_step_body(hipStream_t s, const fira_dims* d, const float* para
         // CU's L2 port, 128 MB per launch at 64 rows, where the 32-row tiles amortise them; profiles/r6_probes.md)
     }
     TRY(consume(D, dp.x, params + L.wt, nullptr, dp.tgt, 0));      // LinearTarget(LN(..)) [+ x materialised]
-    TRY(linear(s, BR, p.V, D, dp.x, D, params + L.wout, params + L.bout, dp.logits, p.ldl));
+    TRY(linear(call, s, BR, p.V, D, dp.x, D, params + L.wout, params + L.bout, dp.logits, p.ldl));
     TRY(copy_score_fwd_ex(s, BR, 1, Sm, p.src, dp.tgt, params + L.wres, params + L.bres, dp.score, n_beam, p.mem_valid));
     return 0;
 }
@@ -2385,7 +2363,7 @@ int fira_decoder_forward(void* stream, const fira_dims* d, const float* params, 
     hipError_t e = hipMemcpyAsync(p.mem_valid, mem_valid, (size_t)p.MB * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return set_err("hipMemcpyAsync: %s", hipGetErrorString(e));
     TRY(tar_mask(s, p.TB, tar, p.tar_valid));
-    TRY(linear(s, p.MB, KV, D, memory, D, params + L->wkv_all, params + L->bkv_all, p.kv_all, p.kvp));
+    TRY(linear(c.call, s, p.MB, KV, D, memory, D, params + L->wkv_all, params + L->bkv_all, p.kv_all, p.kvp));
     TRY(decoder_forward(c));
     e = hipMemcpyAsync(out, p.dec[p.nl - 1].x_f, (size_t)p.TB * D * sizeof(float), hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return set_err("hipMemcpyAsync: %s", hipGetErrorString(e));

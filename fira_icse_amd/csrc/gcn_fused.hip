@@ -392,10 +392,12 @@ __global__ __launch_bounds__(GF_WAVES * 64) void gcn_fused_kernel(const GcnFused
 static double gcn_fused_bytes(int n_rows, bool bwd) {
     return 4.0 * (n_rows + 1) + (bwd ? 4.0 : 3.0) * n_rows * FIRA_D * 4.0;
 }
-template <typename K>
-static int gcn_fused_lds(K kernel, size_t bytes = GF_LDS) {            // once per kernel: allow the > 64 KB dynamic LDS request
-    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e == hipSuccess ? 0 : set_err("gcn_fused: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
+// one launch of the fused kernel `Kernel` with its > 64 KB dynamic LDS request allowed first
+template <auto Kernel>
+static int gcn_fused_launch(hipStream_t s, size_t lds, const GcnFusedArgs& a) {
+    if (int rc = raise_dynamic_lds<Kernel>(lds, "gcn_fused")) return rc;
+    hipLaunchKernelGGL(Kernel, dim3(GF_GRID), dim3(GF_WAVES * 64), lds, s, a);
+    return 0;
 }
 
 int gcn_fused_fwd(hipStream_t s, int n_rows, const int32_t* rowptr, const int32_t* col, const float* val, const float* X,
@@ -413,17 +415,13 @@ int gcn_fused_fwd(hipStream_t s, int n_rows, const int32_t* rowptr, const int32_
     a.bias = bias; a.r1_col = r1_col; a.res = X; a.gamma = gamma; a.beta = beta;
     a.sum = sum; a.y = y; a.stats = stats; a.rowsum_out = rowsum_out; a.slot2 = y2 ? slot2 : nullptr; a.y2 = y2;
     a.p = dropout; a.inv_keep = dropout > 0.f ? 1.0f / (1.0f - dropout) : 1.0f; a.seed = seed; a.site = site;
-    static const int attr = gcn_fused_lds(gcn_fused_kernel<true, false>) | gcn_fused_lds(gcn_fused_kernel<false, false>) |
-                            gcn_fused_lds(gcn_fused_kernel<false, false, 3>, GF_LDS_X3) |
-                            gcn_fused_lds(gcn_fused_kernel<false, false, 1>, GF_LDS_X3);
-    if (attr) return attr;
+    int rc;
     if (Wx) {                            // the product on bf16 planes (Wx: the weight's planes, gcn_split_planes): three terms in
         a.W = reinterpret_cast<const float*>(Wx);                                    // fp32 mode, one in bf16 mode
-        if (bf16) hipLaunchKernelGGL((gcn_fused_kernel<false, false, 1>), dim3(GF_GRID), dim3(GF_WAVES * 64), GF_LDS_X3, s, a);
-        else hipLaunchKernelGGL((gcn_fused_kernel<false, false, 3>), dim3(GF_GRID), dim3(GF_WAVES * 64), GF_LDS_X3, s, a);
+        rc = bf16 ? gcn_fused_launch<gcn_fused_kernel<false, false, 1>>(s, GF_LDS_X3, a) : gcn_fused_launch<gcn_fused_kernel<false, false, 3>>(s, GF_LDS_X3, a);
     } else
-    if (bf16) hipLaunchKernelGGL((gcn_fused_kernel<true, false>), dim3(GF_GRID), dim3(GF_WAVES * 64), GF_LDS, s, a);
-    else hipLaunchKernelGGL((gcn_fused_kernel<false, false>), dim3(GF_GRID), dim3(GF_WAVES * 64), GF_LDS, s, a);
+    rc = bf16 ? gcn_fused_launch<gcn_fused_kernel<true, false>>(s, GF_LDS, a) : gcn_fused_launch<gcn_fused_kernel<false, false>>(s, GF_LDS, a);
+    if (rc) return rc;
     FIRA_CHECK_LAUNCH("gcn_fused_fwd");
     return 0;
 }
@@ -438,17 +436,13 @@ int gcn_fused_bwd(hipStream_t s, int n_rows, const int32_t* rowptr, const int32_
     GcnFusedArgs a{};
     a.n_rows = n_rows; a.rowptr = rowptr; a.col = col; a.val = val; a.X = dY; a.W = Wk;
     a.u_out = u_out; a.acc_out = acc_out;
-    static const int attr = gcn_fused_lds(gcn_fused_kernel<true, true>) | gcn_fused_lds(gcn_fused_kernel<false, true>) |
-                            gcn_fused_lds(gcn_fused_kernel<false, true, 3>, GF_LDS_X3) |
-                            gcn_fused_lds(gcn_fused_kernel<false, true, 1>, GF_LDS_X3);
-    if (attr) return attr;
+    int rc;
     if (Wx) {
         a.W = reinterpret_cast<const float*>(Wx);
-        if (bf16) hipLaunchKernelGGL((gcn_fused_kernel<false, true, 1>), dim3(GF_GRID), dim3(GF_WAVES * 64), GF_LDS_X3, s, a);
-        else hipLaunchKernelGGL((gcn_fused_kernel<false, true, 3>), dim3(GF_GRID), dim3(GF_WAVES * 64), GF_LDS_X3, s, a);
+        rc = bf16 ? gcn_fused_launch<gcn_fused_kernel<false, true, 1>>(s, GF_LDS_X3, a) : gcn_fused_launch<gcn_fused_kernel<false, true, 3>>(s, GF_LDS_X3, a);
     } else
-    if (bf16) hipLaunchKernelGGL((gcn_fused_kernel<true, true>), dim3(GF_GRID), dim3(GF_WAVES * 64), GF_LDS, s, a);
-    else hipLaunchKernelGGL((gcn_fused_kernel<false, true>), dim3(GF_GRID), dim3(GF_WAVES * 64), GF_LDS, s, a);
+    rc = bf16 ? gcn_fused_launch<gcn_fused_kernel<true, true>>(s, GF_LDS, a) : gcn_fused_launch<gcn_fused_kernel<false, true>>(s, GF_LDS, a);
+    if (rc) return rc;
     FIRA_CHECK_LAUNCH("gcn_fused_bwd");
     return 0;
 }

@@ -496,9 +496,8 @@ template <bool B_KCONTIG, int NCH, int NW>
 static int tile32_launch_wide_t(hipStream_t s, dim3 grid, int M, int N, const float* A, int lda, const float* B, int ldb, float* C,
                                 int ldc, const float* bias, int flags, const int32_t* c_rows, const float* relu_mask,
                                 const int32_t* a_rows, int tiles_n, const EpiRes& er) {
-    auto kern = gemm_tile32_kernel<B_KCONTIG, NCH, false, false, NW>;
-    static const hipError_t attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, NW * 8192);
-    if (attr != hipSuccess) return set_err("gemm_tile32: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
+    constexpr auto kern = gemm_tile32_kernel<B_KCONTIG, NCH, false, false, NW>;
+    if (int rc = raise_dynamic_lds<kern>(NW * 8192, "gemm_tile32")) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), NW * 8192, s, M, N, A, lda, B, ldb, C, ldc, bias, flags, c_rows, relu_mask, a_rows,
                        tiles_n, er, LnA(), LnB());
     hipError_t e = hipGetLastError();

@@ -380,12 +380,11 @@ int gemm_wgrad_panel_flush(hipStream_t s, int np) {
     }
     ProfScope prof(s, PROF_GEMM, flop, bytes);
     const size_t lds = (size_t)2 * 2 * np * PN_PART;
-    static bool attr_set[2] = {false, false};
     if (np == 3) {
-        if (!attr_set[1]) { (void)hipFuncSetAttribute((const void*)wgrad_panel_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set[1] = true; }
+        if (int rc = raise_dynamic_lds<wgrad_panel_kernel<3>>(lds, "wgrad_panel")) return rc;
         hipLaunchKernelGGL(wgrad_panel_kernel<3>, dim3(t.wg_start[t.n]), dim3(512), lds, s, t);
     } else {
-        if (!attr_set[0]) { (void)hipFuncSetAttribute((const void*)wgrad_panel_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set[0] = true; }
+        if (int rc = raise_dynamic_lds<wgrad_panel_kernel<1>>(lds, "wgrad_panel")) return rc;
         hipLaunchKernelGGL(wgrad_panel_kernel<1>, dim3(t.wg_start[t.n]), dim3(512), lds, s, t);
     }
     if (bands > 0) hipLaunchKernelGGL(wgrad_panel_reduce_kernel, dim3(bands), dim3(256), 0, s, t);

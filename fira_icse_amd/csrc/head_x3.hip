@@ -193,9 +193,7 @@ int head_logits_x3(hipStream_t s, int R, int V, const float* x, int ldx, const f
     FIRA_REQUIRE((size_t)Rpad * FIRA_D * 6 < (1ull << 31), "head_logits_x3: %d rows exceed the 2 GiB the kernel addresses", R);
     ProfScope prof(s, PROF_GEMM, 2.0 * R * (double)V * FIRA_D, 4.0 * ((double)R * FIRA_D + (double)V * FIRA_D + (double)R * V));
     hipLaunchKernelGGL(rows_split_planes_kernel, dim3((Rpad * 32 + 255) / 256), dim3(256), 0, s, R, Rpad, x, ldx, xplanes);
-    static const hipError_t attr = hipFuncSetAttribute((const void*)head_logits_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)HX_LDS);
-    if (attr != hipSuccess) return set_err("head_logits_x3: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
+    if (int rc = raise_dynamic_lds<head_logits_x3_kernel>(HX_LDS, "head_logits_x3")) return rc;
     hipLaunchKernelGGL(head_logits_x3_kernel, dim3(HX_GRID), dim3(HX_WAVES * 64), HX_LDS, s, R, Rpad, V, W, bias, xplanes, out, ldo);
     FIRA_CHECK_LAUNCH("head_logits_x3");
     return 0;

@@ -779,13 +779,7 @@ int embed_gather_bwd_small(hipStream_t s, int B, int L, const int32_t* idx, floa
     if (rows <= 0) return 0;
     FIRA_REQUIRE(table_rows > 0 && table_rows * FIRA_D * 4 <= 150 * 1024, "embed_gather_bwd_small: table of %d rows does not fit LDS", table_rows);
     ProfScope prof(s, PROF_ROWOPS, 0.0);
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t ae = hipFuncSetAttribute((const void*)embed_gather_bwd_small_kernel,
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        FIRA_REQUIRE(ae == hipSuccess, "embed_gather_bwd_small: cannot raise the dynamic LDS limit: %s", hipGetErrorString(ae));
-        attr_set = true;
-    }
+    if (int rc = raise_dynamic_lds<embed_gather_bwd_small_kernel>(150 * 1024, "embed_gather_bwd_small")) return rc;
     const int rpb = std::max(64, cdiv(rows, 96));
     hipLaunchKernelGGL(embed_gather_bwd_small_kernel, dim3(cdiv(rows, rpb)), dim3(256),
                        (size_t)table_rows * FIRA_D * sizeof(float), s, rows, L, idx, dtable, dout, out_bstride, out_off,

@@ -328,13 +328,7 @@ int csr_spmm_ex(hipStream_t s, int n_rows, const int32_t* rowptr, const int32_t*
         const size_t lds = (size_t)graph_rows * SLAB * sizeof(float) + (size_t)LDS_WAVES * 4 * STAGE * sizeof(int2);
         FIRA_REQUIRE(graph_rows > 0 && n_rows % graph_rows == 0 && lds <= 160 * 1024,
                      "csr_spmm: LDS variant needs rows-per-graph (%d) dividing n_rows and <= 512", graph_rows);
-        static bool attr_set = false;
-        if (!attr_set) {
-            const hipError_t ae = hipFuncSetAttribute((const void*)spmm_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      160 * 1024);
-            FIRA_REQUIRE(ae == hipSuccess, "csr_spmm: cannot raise the dynamic LDS limit: %s", hipGetErrorString(ae));
-            attr_set = true;
-        }
+        if (int rc = raise_dynamic_lds<spmm_lds_kernel>(160 * 1024, "csr_spmm")) return rc;
         hipLaunchKernelGGL(spmm_lds_kernel, dim3(FIRA_D / SLAB, n_rows / graph_rows), dim3(LDS_WAVES * 64), lds, s, graph_rows,
                            rowptr, col, val, X, ldx, Y, ldy);
     } else {

@@ -301,15 +301,6 @@ __global__ __launch_bounds__(NW * 64) void spmm_dense_f32_kernel(int graph_rows,
 }
 
 
-template <typename K>
-static int raise_lds(K kernel, bool* done) {
-    if (*done) return 0;
-    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    FIRA_REQUIRE(e == hipSuccess, "csr_spmm: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    *done = true;
-    return 0;
-}
-
 // bf16 != 0: bf16 operands (fp32 accumulate); otherwise fp32 MFMA.  Shape of the workgroup: 128-row (bf16) / 64-row (fp32)
 // slices, 8 waves, one workgroup per CU (H re-read from L2 4x / 8x per graph); graphs of <= 64 / 32 rows take 64 / 32 rows,
 // 4 waves, two workgroups per CU (8x / 16x).  Measured (profiles/r3_spmm_crossover.md): the large shape is 5-10 % ahead of
@@ -330,18 +321,17 @@ int csr_spmm_dense(hipStream_t s, int n_rows, const int32_t* rowptr, const int32
     const int n_items = (n_rows / graph_rows) * nrb;
     const int chunk = cdiv(n_items, 8);
     const size_t lds = (size_t)R * (bf16 ? KP * 2 + 16 : KP * 4 + 16);
-    static bool a0 = false, a1 = false, a2 = false, a3 = false;
     ProfScope prof(s, PROF_SPMM, 4.0 * (n_rows + 1) + 2.0 * n_rows * FIRA_D * 4.0);
-#define FIRA_DENSE_GO(KERNEL, NW, FLAG)                                                                              \
+#define FIRA_DENSE_GO(KERNEL, NW)                                                                                    \
     do {                                                                                                           \
-        if (int rc = raise_lds(KERNEL, &FLAG)) return rc;                                                          \
+        if (int rc = raise_dynamic_lds<KERNEL>(150 * 1024, "csr_spmm")) return rc;                                 \
         hipLaunchKernelGGL(KERNEL, dim3(8 * chunk), dim3(NW * 64), lds, s, graph_rows, KP, rowptr, col, val, X, ldx, Y, ldy, \
                            nrb, n_items, chunk);                                                                   \
     } while (0)
-    if (bf16 && big) FIRA_DENSE_GO((spmm_dense_bf16_kernel<4, 8>), 8, a0);
-    else if (bf16) FIRA_DENSE_GO((spmm_dense_bf16_kernel<2, 4>), 4, a1);
-    else if (big) FIRA_DENSE_GO((spmm_dense_f32_kernel<2, 8>), 8, a2);
-    else FIRA_DENSE_GO((spmm_dense_f32_kernel<1, 4>), 4, a3);
+    if (bf16 && big) FIRA_DENSE_GO((spmm_dense_bf16_kernel<4, 8>), 8);
+    else if (bf16) FIRA_DENSE_GO((spmm_dense_bf16_kernel<2, 4>), 4);
+    else if (big) FIRA_DENSE_GO((spmm_dense_f32_kernel<2, 8>), 8);
+    else FIRA_DENSE_GO((spmm_dense_f32_kernel<1, 4>), 4);
 #undef FIRA_DENSE_GO
     FIRA_CHECK_LAUNCH("csr_spmm_dense");
     return 0;

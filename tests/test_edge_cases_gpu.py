@@ -70,27 +70,34 @@ def test_greedy_early_stop_and_single_commit(model_sd):
         assert float(prob.min()) > 0.99
 
 
+_dense = {}
+
+
+def _dense_host_batch(cfg):
+    """Three synthetic commits with thousands of random AST-AST and AST-code edges added (~70 entries per computed row);
+    built once per module."""
+    if "hb" not in _dense:
+        raw = synth.generate_dataset(3, seed=31)
+        rng = np.random.default_rng(5)
+        for i in range(3):
+            n_a, n_d = len(raw["ast"][i]), len(raw["difftoken"][i])
+            pairs = rng.integers(0, n_a, size=(9000, 2))
+            raw["edge_ast"][i] = raw["edge_ast"][i] + [[int(a), int(b)] for a, b in pairs if a != b]
+            ac = np.stack([rng.integers(0, n_a, 3000), rng.integers(0, n_d, 3000)], 1)
+            raw["edge_ast_code"][i] = raw["edge_ast_code"][i] + [[int(a), int(b)] for a, b in ac]
+        _dense["hb"] = data.process_raw(cfg, raw).batch([0, 1, 2])
+    return _dense["hb"]
+
+
 def test_dense_graphs_take_the_unfused_gcn_path_and_match_the_oracle():
     """Graphs far denser than FIRA's (BASELINE config 5's regime: here ~70 entries per computed row from thousands of random
     AST-AST and AST-code edges) make the engine run the GCN layers as aggregation + product + row kernel instead of the fused
-    launch (engine.hip: note_graph_density).  Loss and every gradient tensor against the oracle on the dense float64
+    launch (engine.hip: graphs_dense).  Loss and every gradient tensor against the oracle on the dense float64
     adjacency, as for the sparse fixtures."""
-    import numpy as np
     from oracle import fira_oracle as O
-    from fira_icse_amd import data, synth
-    from fira_icse_amd.config import FiraConfig
     from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
     cfg = FiraConfig()
-    raw = synth.generate_dataset(3, seed=31)
-    rng = np.random.default_rng(5)
-    for i in range(3):
-        n_a, n_d = len(raw["ast"][i]), len(raw["difftoken"][i])
-        pairs = rng.integers(0, n_a, size=(9000, 2))
-        raw["edge_ast"][i] = raw["edge_ast"][i] + [[int(a), int(b)] for a, b in pairs if a != b]
-        ac = np.stack([rng.integers(0, n_a, 3000), rng.integers(0, n_d, 3000)], 1)
-        raw["edge_ast_code"][i] = raw["edge_ast_code"][i] + [[int(a), int(b)] for a, b in ac]
-    store = data.process_raw(cfg, raw)
-    hb = store.batch([0, 1, 2])
+    hb = _dense_host_batch(cfg)
     db = DeviceBatch(hb, cfg)
     assert db.nnz > 48 * db.n_nodes, (db.nnz, db.n_nodes)          # beyond the fused kernels' density limit
     torch.manual_seed(0)
@@ -120,3 +127,72 @@ def test_dense_graphs_take_the_unfused_gcn_path_and_match_the_oracle():
         want = O.forward(sd, cfg, tb["sou"], tb["tar"], tb["mark"], tb["ast_change"], tb["edge"], tb["tar_label"],
                          tb["sub_token"], "dev")
     assert torch.equal(ids.long(), want.long())
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_a_pending_step_owns_its_state(model_sd, dtype):
+    """A step pending between train_step_begin and train_step_end keeps its own mode (engine.hip: Ctx::call): other library
+    calls on the thread in between must not change its second half.  The step is begun on a sparse batch (fused GCN kernels);
+    a dense batch evaluated in between (another model, its own workspaces) once switched the pending encoder backward to the
+    unfused branch, which reads an aggregation the fused forward never wrote -- wrong gcn_list fc1 / fc2 gradients, no error;
+    fira_ffn_bwd in between once reset the pending step's deferred column reductions.
+    Bounds: those of test_encoder_wgrad_schedules_give_the_same_gradient (f32) and test_two_commit_lanes_equal_one (bf16)."""
+    from fira_icse_amd import ops
+    from fira_icse_amd.model import TransModel, DeviceBatch
+    cfg, _, sd = model_sd
+    store = data.process_raw(cfg, util.load_golden_raw())
+    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
+    db_sparse = DeviceBatch(store.batch(idx["train"][:util.GOLDEN_B]), cfg)
+    db_dense = DeviceBatch(_dense_host_batch(cfg), cfg)
+    assert db_dense.nnz > 48 * db_dense.n_nodes, (db_dense.nnz, db_dense.n_nodes)
+    assert db_sparse.nnz < 48 * db_sparse.n_nodes, (db_sparse.nnz, db_sparse.n_nodes)
+    models = []
+    for _ in range(2):
+        m = TransModel(cfg, init=False)
+        m.load_state_dict(sd)
+        m.eval()
+        m.compute_dtype = dtype
+        models.append(m)
+    model, other = models
+    ev = torch.cuda.Event()
+    ev.record()
+
+    def ffn_bwd_call():
+        g = torch.Generator().manual_seed(7)
+        r = lambda *s: (0.1 * torch.randn(*s, generator=g)).cuda()
+        M, F = 64, 1024
+        x, w1, b1, w2, b2, gamma, beta = r(M, 256), r(F, 256), r(F), r(256, F), r(256), 1.0 + r(256), r(256)
+        h, summ, y, stats = ops.ffn_fwd(x, w1, b1, w2, b2, gamma, beta)
+        ops.ffn_bwd(r(M, 256), x, h, summ, stats, w1, w2, gamma)
+
+    def step(between):
+        model.train_step_begin(db_sparse, ev)
+        if between is not None:
+            between()
+        model.train_step_end(None, None, 0.0, 1, update=False)
+        return model.gbuf[:model.layout.live].cpu().double()
+
+    want = step(None)
+    cases = {"dense forward_dev": lambda: other.forward_dev(db_dense)}
+    if dtype == "f32":
+        cases["ffn_bwd"] = ffn_bwd_call
+    tol, tol_gcn = (1e-5, 2e-5) if dtype == "f32" else (3e-3, 3e-3)
+    base = model.gbuf.data_ptr()
+    for name, between in cases.items():
+        got = step(between)
+        rel = float((got - want).norm() / want.norm())
+        worst = ("", 0.0)
+        bad = []
+        for k, v in model.grad_views().items():
+            if "gcn_list" not in k:
+                continue
+            o = (v.data_ptr() - base) // 4
+            a, b = got[o:o + v.numel()], want[o:o + v.numel()]
+            err, ref = float((a - b).norm()), float(b.norm())
+            if ref > 0 and err / ref > worst[1]:
+                worst = (k, err / ref)
+            if err > tol_gcn * ref + 1e-12:
+                bad.append((k, err, ref))
+        print("%s [%s]: whole gradient rel %.3g, worst gcn_list tensor %s rel %.3g" % (name, dtype, rel, worst[0], worst[1]))
+        assert rel < tol, (name, rel)
+        assert not bad, (name, bad[:4])
