@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# FIRA_HIP_LIB: load another build of the same ABI (version 10) instead (A/B timing of two builds on one GPU box)
+# FIRA_HIP_LIB: load another build of the same ABI (version 11) instead (A/B timing of two builds on one GPU box)
 LIB_PATH = os.environ.get("FIRA_HIP_LIB") or os.path.join(HERE, "libfira_hip.so")
 
 
@@ -61,6 +61,12 @@ class ClipState(C.Structure):
     """fira_clip_state as the device holds it (64 bytes): read back with ``ClipState.from_buffer_copy``."""
     _fields_ = [("sq", C.c_float * 4), ("norm", C.c_float), ("coef", C.c_float), ("zero_flag", C.c_int32),
                 ("n_clipped", C.c_int32), ("n_nonfinite", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class RedEntry(C.Structure):
+    """fira_red_entry: one deferred column reduction, dst[c] += sum_p src[p * stride + c]."""
+    _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("width", C.c_int32), ("n_part", C.c_int32),
+                ("stride", C.c_int32)]
 
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
@@ -117,6 +123,21 @@ SIGNATURES = {
     "fira_copy_score_fwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "fira_copy_score_bwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_head_loss": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I]),
+    "fira_copy_score_fwd_ex": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P]),
+    "fira_copy_score_bwd_ex": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fira_copy_score_bwd_blocks": (_I, [_I, _I]),
+    "fira_copy_part_stride": (_I, []),
+    "fira_head_loss_ex": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "fira_deferred_reduce_max": (_I, []),
+    "fira_deferred_reduce": (_I, [_P, _I, C.POINTER(RedEntry)]),
+    "fira_rows_move": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P]),
+    "fira_rank2_rows": (_I, [_P, _I, _P, _P, _P]),
+    "fira_colsum_weighted": (_I, [_P, _I, _I, _P, _I, _P, _P]),
+    "fira_embed_rows_fwd": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
+    "fira_embed_rows_bwd": (_I, [_P, _I, _P, _P, _P, _P, _I]),
+    "fira_embed_grouped_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    "fira_embed_list_bwd_small": (_I, [_P, _I, _P, _P, _P, _P, _I]),
+    "fira_embed_gather_bwd_small": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I]),
     "fira_adam_step": (_I, [_P, _L, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P]),
     "fira_adam_step_mb": (_I, [_P, _L, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P, _P]),
     "fira_inv_count": (_I, [_P, _P, _P]),
@@ -201,7 +222,7 @@ def load():
             "fira_icse_amd: %s is missing and could not be built (%s). Build it with `python -m fira_icse_amd.build` "
             "(needs hipcc, gfx950). There is no CPU fallback." % (LIB_PATH, e))
     lib = C.CDLL(LIB_PATH)
-    if lib.fira_abi_version() != 10:
+    if lib.fira_abi_version() != 11:
         raise ImportError("libfira_hip.so ABI version mismatch")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export a declared symbol

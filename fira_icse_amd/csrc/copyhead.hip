@@ -961,6 +961,40 @@ int fira_head_loss(void* stream, int BT, int T, int V, int S, const int32_t* com
     return fira::head_loss((hipStream_t)stream, BT, T, V, S, compact_row, logits, ldl, score, mem_valid, gate_logits,
                            tar_label, loss_sum, n_tok, argmax_out, want_grad);
 }
+// The forms the engine calls (head_forward / backward_decoder / the decode step): test surface, same launches.
+int fira_copy_score_fwd_ex(void* stream, int B, int T, int S, const float* src, const float* tgt, const float* w,
+                           const float* bias, float* score, int qpk, const int32_t* mem_valid, const int32_t* tar_label,
+                           int V, const int32_t* t_off) {
+    FIRA_REQUIRE(src && tgt && w && bias && score, "fira_copy_score_fwd_ex: null pointer argument");
+    FIRA_REQUIRE(B >= 0 && T >= 1 && T <= fira::T_MAX && S >= 1, "fira_copy_score_fwd_ex: bad size B=%d T=%d S=%d", B, T, S);
+    FIRA_REQUIRE(qpk >= 1 && B % qpk == 0, "fira_copy_score_fwd_ex: qpk = %d must be >= 1 and divide B = %d", qpk, B);
+    FIRA_REQUIRE(!tar_label || V >= 1, "fira_copy_score_fwd_ex: tar_label needs the vocabulary size (V = %d)", V);
+    return fira::copy_score_fwd_ex((hipStream_t)stream, B, T, S, src, tgt, w, bias, score, qpk, mem_valid, tar_label, V, t_off);
+}
+int fira_copy_score_bwd_ex(void* stream, int B, int T, int S, const float* src, const float* tgt, const float* w,
+                           const float* dscore, float* dsrc, float* dtgt, float* dw, float* dbias,
+                           const int32_t* mem_valid, float* part, const int32_t* t_off) {
+    FIRA_REQUIRE(src && tgt && w && dscore && dsrc && dtgt, "fira_copy_score_bwd_ex: null pointer argument");
+    FIRA_REQUIRE(part || (dw && dbias), "fira_copy_score_bwd_ex: needs part or dw and dbias");
+    FIRA_REQUIRE(B >= 0 && T >= 1 && T <= fira::T_MAX && S >= 1, "fira_copy_score_bwd_ex: bad size B=%d T=%d S=%d", B, T, S);
+    return fira::copy_score_bwd_ex((hipStream_t)stream, B, T, S, src, tgt, w, dscore, dsrc, dtgt, dw, dbias, mem_valid, part,
+                                   t_off);
+}
+int fira_copy_score_bwd_blocks(int B, int S) {
+    FIRA_REQUIRE(B >= 0 && S >= 1, "fira_copy_score_bwd_blocks: bad size B=%d S=%d", B, S);
+    return fira::copy_score_bwd_blocks(B, S);
+}
+int fira_copy_part_stride(void) { return fira::COPY_PART_STRIDE; }
+int fira_head_loss_ex(void* stream, int BT, int T, int V, int S, const int32_t* compact_row, float* logits, int ldl,
+                      float* score, const int32_t* mem_valid, float* gate_logits, const int32_t* tar_label,
+                      float* loss_sum, int32_t* n_tok, int32_t* argmax_out, int want_grad, const int32_t* row_bt) {
+    FIRA_REQUIRE(logits && score && mem_valid && gate_logits && tar_label, "fira_head_loss_ex: null pointer argument");
+    FIRA_REQUIRE((loss_sum == nullptr) == (n_tok == nullptr), "fira_head_loss_ex: loss_sum and n_tok are given together");
+    FIRA_REQUIRE(BT >= 0 && T >= 1 && V >= 1 && S >= 1 && ldl >= V, "fira_head_loss_ex: bad size BT=%d T=%d V=%d S=%d ldl=%d",
+                 BT, T, V, S, ldl);
+    return fira::head_loss((hipStream_t)stream, BT, T, V, S, compact_row, logits, ldl, score, mem_valid, gate_logits,
+                           tar_label, loss_sum, n_tok, argmax_out, want_grad, row_bt);
+}
 int fira_adam_step_mb(void* stream, int64_t n, float* p, const float* g0, const float* g1, float* m, float* v, float lr,
                       float beta1, float beta2, float eps, int step, const int32_t* n_tok0, const int32_t* n_tok1) {
     FIRA_REQUIRE(p && g0 && m && v && n_tok0 && step >= 1, "fira_adam_step_mb: bad argument");

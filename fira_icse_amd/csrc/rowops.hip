@@ -1109,4 +1109,70 @@ int fira_add_layernorm_bwd(void* stream, int M, const float* dy, const float* su
 int fira_colsum_f32(void* stream, int M, int N, const float* X, int ldx, float* out) {
     return fira::colsum((hipStream_t)stream, M, N, X, ldx, out);
 }
+// The training step's tail as the engine calls it: test surface, same launches.
+int fira_colsum_weighted(void* stream, int M, int N, const float* X, int ldx, float* out, const float* row_weight) {
+    FIRA_REQUIRE(X && out, "fira_colsum_weighted: null pointer argument");
+    FIRA_REQUIRE(M >= 0 && N >= 0 && ldx >= N, "fira_colsum_weighted: bad size M=%d N=%d ldx=%d", M, N, ldx);
+    return fira::colsum((hipStream_t)stream, M, N, X, ldx, out, row_weight);
+}
+int fira_deferred_reduce_max(void) { return fira::RED_MAX; }
+int fira_deferred_reduce(void* stream, int n, const fira_red_entry* entries) {
+    FIRA_REQUIRE(n >= 0 && n <= fira::RED_MAX, "fira_deferred_reduce: %d entries (at most %d)", n, fira::RED_MAX);
+    FIRA_REQUIRE(entries || n == 0, "fira_deferred_reduce: null entry list");
+    fira::RedTable tab;
+    for (int i = 0; i < n; ++i) {
+        const fira_red_entry& q = entries[i];
+        FIRA_REQUIRE(q.dst && q.src, "fira_deferred_reduce: entry %d has a null pointer", i);
+        FIRA_REQUIRE(q.width >= 1 && q.n_part >= 1 && q.stride >= q.width, "fira_deferred_reduce: entry %d: bad width %d / n_part %d / stride %d",
+                     i, q.width, q.n_part, q.stride);
+        tab.e[i] = fira::RedEntry{q.dst, q.src, q.width, q.n_part, q.stride};
+    }
+    tab.n = n;
+    return fira::deferred_reduce((hipStream_t)stream, tab);
+}
+int fira_rows_move(void* stream, int mode, int R, int W, float* out, int ld_out, const float* in, int ld_in,
+                   const int32_t* src, const int32_t* dst) {
+    FIRA_REQUIRE(out && in, "fira_rows_move: null pointer argument");
+    FIRA_REQUIRE(mode >= 0 && mode <= 3, "fira_rows_move: mode %d", mode);
+    FIRA_REQUIRE(mode == 0 || dst, "fira_rows_move: mode %d needs the dst list", mode);
+    FIRA_REQUIRE(R >= 0 && W >= 256 && ld_out >= W && ld_in >= W, "fira_rows_move: bad size R=%d W=%d ld_out=%d ld_in=%d", R, W,
+                 ld_out, ld_in);
+    FIRA_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)in % 16 == 0, "fira_rows_move: rows must be 16-byte aligned");
+    return fira::rows_move_ld((hipStream_t)stream, mode, R, W, out, ld_out, in, ld_in, src, dst);
+}
+int fira_rank2_rows(void* stream, int M, const float* g, const float* w, float* out) {
+    FIRA_REQUIRE(g && w && out && M >= 0, "fira_rank2_rows: bad argument");
+    return fira::rank2_rows((hipStream_t)stream, M, g, w, out);
+}
+int fira_embed_rows_fwd(void* stream, int R, int T, const int32_t* row_bt, const int32_t* idx, const float* table,
+                        const float* pos, float* out) {
+    FIRA_REQUIRE(row_bt && idx && table && pos && out, "fira_embed_rows_fwd: null pointer argument");
+    FIRA_REQUIRE(R >= 0 && T >= 1, "fira_embed_rows_fwd: bad size R=%d T=%d", R, T);
+    return fira::embed_rows_fwd((hipStream_t)stream, R, T, row_bt, idx, table, pos, out, nullptr);
+}
+int fira_embed_rows_bwd(void* stream, int R, const int32_t* row_bt, const int32_t* idx, float* dtable, const float* dout,
+                        int padding_idx) {
+    FIRA_REQUIRE(row_bt && idx && dtable && dout && R >= 0, "fira_embed_rows_bwd: bad argument");
+    return fira::embed_rows_bwd((hipStream_t)stream, R, row_bt, idx, dtable, dout, padding_idx);
+}
+int fira_embed_grouped_bwd(void* stream, int n_items, const int32_t* item_tok, const int32_t* item_ptr, const int32_t* rows,
+                           float* dtable, const float* dnode) {
+    FIRA_REQUIRE(n_items >= 0, "fira_embed_grouped_bwd: n_items = %d", n_items);
+    FIRA_REQUIRE(n_items == 0 || (item_tok && item_ptr && rows && dtable && dnode), "fira_embed_grouped_bwd: null pointer argument");
+    return fira::embed_grouped_bwd((hipStream_t)stream, n_items, item_tok, item_ptr, rows, dtable, dnode);
+}
+int fira_embed_list_bwd_small(void* stream, int n, const int32_t* rows, const int32_t* ids, float* dtable, const float* dnode,
+                              int table_rows) {
+    FIRA_REQUIRE(n >= 0, "fira_embed_list_bwd_small: n = %d", n);
+    FIRA_REQUIRE(n == 0 || (rows && ids && dtable && dnode), "fira_embed_list_bwd_small: null pointer argument");
+    return fira::embed_list_bwd_small((hipStream_t)stream, n, rows, ids, dtable, dnode, table_rows);
+}
+int fira_embed_gather_bwd_small(void* stream, int B, int L, const int32_t* idx, float* dtable, const float* dout,
+                                int out_bstride, int out_off, int padding_idx, int table_rows) {
+    FIRA_REQUIRE(idx && dtable && dout, "fira_embed_gather_bwd_small: null pointer argument");
+    FIRA_REQUIRE(B >= 0 && L >= 0 && out_off >= 0 && out_bstride >= out_off + L, "fira_embed_gather_bwd_small: bad size B=%d L=%d out_bstride=%d out_off=%d",
+                 B, L, out_bstride, out_off);
+    return fira::embed_gather_bwd_small((hipStream_t)stream, B, L, idx, dtable, dout, out_bstride, out_off, padding_idx,
+                                        table_rows);
+}
 }

@@ -439,6 +439,126 @@ def head_loss(logits, score, mem_valid, gate_logits, tar_label, V, compact_row=N
     return loss, ntok, ids
 
 
+# ---- the forms the engine calls (fira_*_ex and the row kernels of the step's tail).  They allocate nothing: the caller owns
+# every buffer, so that a test can pre-fill it with sentinels.
+def copy_score_fwd_ex(src, tgt, w, bias, score, T, qpk=1, mem_valid=None, tar_label=None, V=0, t_off=None):
+    """src [B/qpk, S, 256]; tgt / score: B*T rows, or (t_off [B+1]) the ragged rows t_off[b] .. t_off[b+1]; written in place."""
+    S = src.shape[1]
+    B = src.shape[0] * qpk
+    opt = lambda t: None if t is None else _i32(t)
+    check(_lib.lib().fira_copy_score_fwd_ex(cur_stream(), B, T, S, ptr(_f32(src)), ptr(_f32(tgt)), ptr(_f32(w)),
+                                            ptr(_f32(bias)), ptr(_f32(score)), qpk, ptr(opt(mem_valid)), ptr(opt(tar_label)),
+                                            V, ptr(opt(t_off))), "fira_copy_score_fwd_ex")
+    return score
+
+
+def copy_score_bwd_blocks(B, S):
+    n = _lib.lib().fira_copy_score_bwd_blocks(B, S)
+    if n < 0:
+        check(n, "fira_copy_score_bwd_blocks")
+    return n
+
+
+def copy_part_stride():
+    return _lib.lib().fira_copy_part_stride()
+
+
+def copy_score_bwd_ex(src, tgt, w, dscore, dsrc, dtgt, dw, dbias, T, mem_valid=None, part=None, t_off=None):
+    """dsrc is overwritten; dtgt (and dw / dbias, or with ``part`` the partial rows instead) are accumulated into."""
+    B, S = src.shape[0], src.shape[1]
+    opt = lambda t: None if t is None else _i32(t)
+    optf = lambda t: None if t is None else _f32(t)
+    check(_lib.lib().fira_copy_score_bwd_ex(cur_stream(), B, T, S, ptr(_f32(src)), ptr(_f32(tgt)), ptr(_f32(w)),
+                                            ptr(_f32(dscore)), ptr(_f32(dsrc)), ptr(_f32(dtgt)), ptr(optf(dw)),
+                                            ptr(optf(dbias)), ptr(opt(mem_valid)), ptr(optf(part)), ptr(opt(t_off))),
+          "fira_copy_score_bwd_ex")
+
+
+def head_loss_ex(logits, score, mem_valid, gate_logits, tar_label, V, compact_row=None, row_bt=None, want_grad=True,
+                 argmax=False):
+    """fira_head_loss on the rows of ``score`` (row r = flat position row_bt[r]; None: r itself).  In place as head_loss."""
+    B, T = tar_label.shape
+    R, S = score.shape
+    loss = torch.zeros(1, dtype=torch.float32, device=logits.device)
+    ntok = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    ids = torch.empty(R, dtype=torch.int32, device=logits.device) if argmax else None
+    opt = lambda t: None if t is None else _i32(t)
+    check(_lib.lib().fira_head_loss_ex(cur_stream(), R, T, V, S, ptr(opt(compact_row)), ptr(_f32(logits)), logits.stride(0),
+                                       ptr(_f32(score)), ptr(_i32(mem_valid)), ptr(_f32(gate_logits)), ptr(_i32(tar_label)),
+                                       ptr(loss), ptr(ntok), ptr(ids), int(want_grad), ptr(opt(row_bt))),
+          "fira_head_loss_ex")
+    return loss, ntok, ids
+
+
+def deferred_reduce_max():
+    return _lib.lib().fira_deferred_reduce_max()
+
+
+def deferred_reduce(entries):
+    """entries: (dst [width], src partial rows, width, n_part, stride) tuples; one launch: dst[c] += sum_p src[p*stride + c]."""
+    arr = (_lib.RedEntry * max(len(entries), 1))()
+    for i, (dst, src, width, n_part, stride) in enumerate(entries):       # (views allowed: src may start inside a wider row)
+        assert dst.is_cuda and src.is_cuda and dst.dtype == src.dtype == torch.float32
+        arr[i] = _lib.RedEntry(dst.data_ptr(), src.data_ptr(), width, n_part, stride)
+    check(_lib.lib().fira_deferred_reduce(cur_stream(), len(entries), arr), "fira_deferred_reduce")
+
+
+def rows_move(mode, R, W, out, ld_out, inp, ld_in, src=None, dst=None):
+    """fira_rows_move on views: ``out`` / ``inp`` start at the first moved column of their (wider) matrices."""
+    opt = lambda t: None if t is None else _i32(t)
+    assert out.is_cuda and inp.is_cuda and out.dtype == inp.dtype == torch.float32
+    check(_lib.lib().fira_rows_move(cur_stream(), mode, R, W, ptr(out), ld_out, ptr(inp), ld_in, ptr(opt(src)),
+                                    ptr(opt(dst))), "fira_rows_move")
+
+
+def rank2_rows(g, w):
+    out = torch.empty((g.shape[0], 256), dtype=torch.float32, device=g.device)
+    check(_lib.lib().fira_rank2_rows(cur_stream(), g.shape[0], ptr(_f32(g)), ptr(_f32(w)), ptr(out)), "fira_rank2_rows")
+    return out
+
+
+def colsum_weighted(X, N, out, row_weight=None):
+    """out[:N] += sum_m row_weight[m] * X[m, :N]; X [M, ldx >= N]."""
+    check(_lib.lib().fira_colsum_weighted(cur_stream(), X.shape[0], N, ptr(_f32(X)), X.stride(0), ptr(_f32(out)),
+                                          ptr(None if row_weight is None else _f32(row_weight))), "fira_colsum_weighted")
+    return out
+
+
+def embed_rows_fwd(row_bt, idx, table, pos):
+    R, T = row_bt.numel(), idx.shape[1]
+    out = torch.empty((R, 256), dtype=torch.float32, device=table.device)
+    check(_lib.lib().fira_embed_rows_fwd(cur_stream(), R, T, ptr(_i32(row_bt)), ptr(_i32(idx)), ptr(_f32(table)),
+                                         ptr(_f32(pos)), ptr(out)), "fira_embed_rows_fwd")
+    return out
+
+
+def embed_rows_bwd(row_bt, idx, dtable, dout, padding_idx=0):
+    check(_lib.lib().fira_embed_rows_bwd(cur_stream(), row_bt.numel(), ptr(_i32(row_bt)), ptr(_i32(idx)), ptr(_f32(dtable)),
+                                         ptr(_f32(dout)), padding_idx), "fira_embed_rows_bwd")
+    return dtable
+
+
+def embed_grouped_bwd(item_tok, item_ptr, rows, dtable, dnode):
+    check(_lib.lib().fira_embed_grouped_bwd(cur_stream(), item_tok.numel(), ptr(_i32(item_tok)), ptr(_i32(item_ptr)),
+                                            ptr(_i32(rows)), ptr(_f32(dtable)), ptr(_f32(dnode))), "fira_embed_grouped_bwd")
+    return dtable
+
+
+def embed_list_bwd_small(rows, ids, dtable, dnode):
+    check(_lib.lib().fira_embed_list_bwd_small(cur_stream(), rows.numel(), ptr(_i32(rows)), ptr(_i32(ids)), ptr(_f32(dtable)),
+                                               ptr(_f32(dnode)), dtable.shape[0]), "fira_embed_list_bwd_small")
+    return dtable
+
+
+def embed_scatter_add_small(idx, dtable, dout, out_bstride, out_off, padding_idx):
+    """embed_scatter_add through the LDS-table kernel (fira_embed_gather_bwd_small)."""
+    B, L = idx.shape
+    check(_lib.lib().fira_embed_gather_bwd_small(cur_stream(), B, L, ptr(_i32(idx)), ptr(_f32(dtable)), ptr(_f32(dout)),
+                                                 out_bstride, out_off, padding_idx, dtable.shape[0]),
+          "fira_embed_gather_bwd_small")
+    return dtable
+
+
 def adam_step(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, inv_scale=None):
     check(_lib.lib().fira_adam_step(cur_stream(), p.numel(), ptr(_f32(p)), ptr(_f32(g)), ptr(_f32(m)), ptr(_f32(v)),
                                     lr, beta1, beta2, eps, step, ptr(inv_scale)), "fira_adam_step")

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define FIRA_ABI_VERSION 10
+#define FIRA_ABI_VERSION 11
 
 /* ---- model geometry: reference run_model.py:30-46 (args) ---------------------------------- */
 typedef struct fira_dims {
@@ -420,6 +420,76 @@ int fira_head_loss(void* stream, int BT, int T, int V, int S, const int32_t* com
                    float* logits, int ldl, float* score /* [BT,S] */, const int32_t* mem_valid /* [B,S] */,
                    float* gate_logits /* [BT,2] */, const int32_t* tar_label /* [B,T] */,
                    float* loss_sum, int32_t* n_tok, int32_t* argmax_out, int want_grad);
+
+/* (v11) The forms of the copy head and the loss that the engine calls (test surface: the same launches, no other kernel):
+ *   qpk       (>= 1, divides B) qpk consecutive target batches share one memory: row b reads src / mem_valid entry b / qpk
+ *             (the decode step: T = 1, qpk = hypotheses per commit).
+ *   mem_valid (optional, [B/qpk, S] forward, [B, S] backward) key mask of the memory slots.  Forward: a masked slot is not
+ *             computed, its score is stored as exactly 0 (fira_head_loss replaces it by -1e9).  Backward: dscore of a masked
+ *             slot is never read as a gradient (masked_fill passes none) and its dsrc row is exactly 0.
+ *   tar_label (optional, [B, T] dense, with V = vocabulary size) training: only the rows t whose shifted label
+ *             tar_label[b, t+1] is a copy id (>= V) are computed.  Every other row is left UNWRITTEN, except that masked
+ *             slots are still stored as 0 by the workgroups that own a copy row; a commit without any copy label is not
+ *             touched at all.  fira_head_loss neither reads nor propagates the unwritten rows: with want_grad it
+ *             overwrites all of them with their (zero) gradient.
+ *   t_off     (optional, [B+1]) ragged target rows: commit b's rows are t_off[b] .. t_off[b+1] of tgt / score / dscore / dtgt
+ *             (at most T of them, position t = row - t_off[b]; fira_batch.dec_off); labels stay dense [B, T].  Rows past
+ *             t_off[B] are never touched.
+ *   part      (optional, [fira_copy_score_bwd_blocks(B, S), fira_copy_part_stride()] floats) the backward stores one partial
+ *             row {dw[256] | dbias} per workgroup -- every row is written, those of all-zero tiles as zeros -- instead of
+ *             adding to dw / dbias (which are then not touched and may be NULL); fira_deferred_reduce sums the rows.
+ *   row_bt    (optional, [BT]) fira_head_loss on BT computed target rows: row r of score / gate_logits / compact_row is the
+ *             flat position row_bt[r] = b*T + t (NULL: r itself).                                                        */
+int fira_copy_score_fwd_ex(void* stream, int B, int T, int S, const float* src, const float* tgt, const float* w,
+                           const float* bias, float* score, int qpk, const int32_t* mem_valid, const int32_t* tar_label,
+                           int V, const int32_t* t_off);
+int fira_copy_score_bwd_ex(void* stream, int B, int T, int S, const float* src, const float* tgt, const float* w,
+                           const float* dscore, float* dsrc /* = */, float* dtgt /* += */, float* dw /* += */,
+                           float* dbias /* += */, const int32_t* mem_valid, float* part, const int32_t* t_off);
+int fira_copy_score_bwd_blocks(int B, int S);   /* workgroups (= partial rows) of the backward launch; negative on bad sizes */
+int fira_copy_part_stride(void);                /* floats between two partial rows (>= 257)                                  */
+int fira_head_loss_ex(void* stream, int BT, int T, int V, int S, const int32_t* compact_row, float* logits, int ldl,
+                      float* score, const int32_t* mem_valid, float* gate_logits, const int32_t* tar_label,
+                      float* loss_sum, int32_t* n_tok, int32_t* argmax_out, int want_grad, const int32_t* row_bt);
+
+/* (v11) The row kernels of the training step's tail, as the engine calls them (test surface, same launches):
+ *   fira_deferred_reduce     dst[c] += sum_p src[p * stride + c], c < width, p < n_part, for n <= fira_deferred_reduce_max()
+ *                            entries in ONE launch (`entries` is a HOST array, read during the call): the sums of the partial
+ *                            rows that the backward kernels park per workgroup (LayerNorm gamma / beta, the copy head's w / bias).
+ *   fira_rows_move           W floats (a multiple of 256) of each of R rows, rows ld_out / ld_in floats apart (a column block of
+ *                            a wider matrix; multiples of 4):  mode 0 out[r] = in[src[r]] (src NULL: identity), 1 out[dst[r]] = in[r],
+ *                            2 out[dst[r]] += in[r], 3 out[dst[r]] = in[src[r]].  dst holds no duplicates (plain stores).
+ *   fira_rank2_rows          out[M,256] = g[M,2] w[2,256]: the data gradient of the 2-way copy gate (Model.py:19).
+ *   fira_colsum_weighted     out[n] += sum_m row_weight[m] * X[m,n]  (row_weight NULL: all 1; X rows ldx floats apart).
+ *   fira_embed_rows_fwd/bwd  the decoder's token embedding on computed target rows: compact row r is the flat position
+ *                            row_bt[r] = b*T + t;  out[r] = table[idx[row_bt[r]]] + pos[t] ;  dtable[idx[row_bt[r]]] += dout[r]
+ *                            (rows whose id is padding_idx skipped).  The table is read as stored (no row-sparse Adam view).
+ *   fira_embed_grouped_bwd   dtable[item_tok[i]] += sum of the rows rows[item_ptr[i] .. item_ptr[i+1]) of dnode [*,256], one
+ *                            wave per item (fira_batch.emb_*: at most 32 rows per item -- more than 64 are NOT summed -- and the
+ *                            items of one word ADJACENT: a word with a single item is written without atomics).
+ *   fira_embed_list_bwd_small   dtable[ids[k]] += dnode[rows[k]] for k < n, ids in [0, table_rows) (fira_batch.ast_*).
+ *   fira_embed_gather_bwd_small fira_embed_gather_bwd for a table of table_rows rows that fits LDS (<= 150 rows).             */
+typedef struct fira_red_entry {
+    float*       dst;        /* [width]  accumulated into                      */
+    const float* src;        /* [n_part, stride] partial rows                  */
+    int32_t      width, n_part, stride;
+} fira_red_entry;
+int fira_deferred_reduce_max(void);
+int fira_deferred_reduce(void* stream, int n, const fira_red_entry* entries /* host */);
+int fira_rows_move(void* stream, int mode, int R, int W, float* out, int ld_out, const float* in, int ld_in,
+                   const int32_t* src, const int32_t* dst);
+int fira_rank2_rows(void* stream, int M, const float* g, const float* w, float* out);
+int fira_colsum_weighted(void* stream, int M, int N, const float* X, int ldx, float* out, const float* row_weight);
+int fira_embed_rows_fwd(void* stream, int R, int T, const int32_t* row_bt, const int32_t* idx, const float* table,
+                        const float* pos, float* out);
+int fira_embed_rows_bwd(void* stream, int R, const int32_t* row_bt, const int32_t* idx, float* dtable, const float* dout,
+                        int padding_idx);
+int fira_embed_grouped_bwd(void* stream, int n_items, const int32_t* item_tok, const int32_t* item_ptr, const int32_t* rows,
+                           float* dtable, const float* dnode);
+int fira_embed_list_bwd_small(void* stream, int n, const int32_t* rows, const int32_t* ids, float* dtable, const float* dnode,
+                              int table_rows);
+int fira_embed_gather_bwd_small(void* stream, int B, int L, const int32_t* idx, float* dtable, const float* dout,
+                                int out_bstride, int out_off, int padding_idx, int table_rows);
 
 /* Adam (run_model.py:396 torch.optim.Adam defaults) over a flat buffer.  grad_scale (device scalar,
  * may be NULL) multiplies g first: 1/n_tok of run_model.py:105 without a host sync.              */

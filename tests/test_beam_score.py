@@ -169,9 +169,9 @@ def test_beam_scoring_check_against_the_beam():
 def test_header_declares_and_library_exports_the_entry():
     header = open(os.path.join(util.REPO, "include", "fira_hip.h")).read()
     assert re.search(r"\bint\s+fira_beam_select_scored\s*\(", header)
-    assert "#define FIRA_ABI_VERSION 10" in header
+    assert "#define FIRA_ABI_VERSION 11" in header
     lib = _lib.lib()
-    assert lib.fira_abi_version() == 10 and hasattr(lib, "fira_beam_select_scored") and "fira_beam_select_scored" in _lib.SIGNATURES
+    assert lib.fira_abi_version() == 11 and hasattr(lib, "fira_beam_select_scored") and "fira_beam_select_scored" in _lib.SIGNATURES
 
 
 def dims(**kw):

@@ -114,9 +114,9 @@ def test_bad_weights_are_value_errors(bad, word):
 def test_header_declares_and_library_exports_the_entry():
     header = open(os.path.join(util.REPO, "include", "fira_hip.h")).read()
     assert re.search(r"\bint\s+fira_mix_dist\s*\(", header)
-    assert "#define FIRA_ABI_VERSION 10" in header
+    assert "#define FIRA_ABI_VERSION 11" in header
     lib = _lib.lib()
-    assert lib.fira_abi_version() == 10 and hasattr(lib, "fira_mix_dist") and "fira_mix_dist" in _lib.SIGNATURES
+    assert lib.fira_abi_version() == 11 and hasattr(lib, "fira_mix_dist") and "fira_mix_dist" in _lib.SIGNATURES
 
 
 def call(R_=6, W=16, n=2, ptrs=None, weights=None, out=4096, best_id=16, best_p=16, null_arrays=False):

@@ -119,4 +119,4 @@ def test_entry_is_declared_exported_and_bound(lib):
     assert re.search(r"\bint\s+fira_mbr_bleu_stats\s*\(", code)
     assert hasattr(lib, "fira_mbr_bleu_stats")
     assert "fira_mbr_bleu_stats" in _lib.SIGNATURES and len(_lib.SIGNATURES["fira_mbr_bleu_stats"][1]) == 7
-    assert lib.fira_abi_version() == int(re.search(r"#define FIRA_ABI_VERSION (\d+)", header).group(1)) == 10
+    assert lib.fira_abi_version() == int(re.search(r"#define FIRA_ABI_VERSION (\d+)", header).group(1)) == 11

@@ -91,9 +91,9 @@ def test_rows_per_commit_selects_the_commits_sources():
 def test_header_declares_and_library_exports_the_entry():
     header = open(os.path.join(util.REPO, "include", "fira_hip.h")).read()
     assert re.search(r"\bint\s+fira_merge_dist\s*\(", header)
-    assert "#define FIRA_ABI_VERSION 10" in header
+    assert "#define FIRA_ABI_VERSION 11" in header
     lib = _lib.lib()
-    assert lib.fira_abi_version() == 10 and hasattr(lib, "fira_merge_dist") and "fira_merge_dist" in _lib.SIGNATURES
+    assert lib.fira_abi_version() == 11 and hasattr(lib, "fira_merge_dist") and "fira_merge_dist" in _lib.SIGNATURES
 
 
 def dims(**kw):
