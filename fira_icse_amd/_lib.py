@@ -180,6 +180,7 @@ SIGNATURES = {
     "fira_mbr_bleu_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "fira_constrain_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P]),
     "fira_merge_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P]),
+    "fira_force_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_mix_dist": (_I, [_P, _I, _I, _I, C.POINTER(_P), C.POINTER(_F), _P, _P, _P]),
     "fira_decode_begin": (_I, [_P, _DP, _BP, _P, _P, _Z, _I]),
     "fira_decode_begin_ex": (_I, [_P, _DP, _BP, _P, _P, _Z, _I, _I]),

@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import gc
+import numbers
 from typing import List, Optional, Tuple
 
 import torch
@@ -255,12 +257,23 @@ class _Loop:
                 # warm-up outside capture (lazy initialisation inside the library / torch), then capture every chunk
                 steps(0, 1)
                 torch.cuda.synchronize()
+                # No destructor of a device object may run inside a capture: destroying a captured graph or freeing its memory
+                # there makes the runtime abort the process.  Reference counting frees nothing of that kind in ``steps``, but
+                # the cyclic collector may start at any allocation and free a dead cycle that owns graphs and buffers (torch
+                # no longer collects when a capture begins).  So: collect now, and keep the collector off while capturing.
+                gc.collect()
+                gc_was_on = gc.isenabled()
+                gc.disable()
                 graphs = []
-                for lo, hi in self.bounds:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        steps(lo, hi)
-                    graphs.append(g)
+                try:
+                    for lo, hi in self.bounds:
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g):
+                            steps(lo, hi)
+                        graphs.append(g)
+                finally:
+                    if gc_was_on:
+                        gc.enable()
                 st.update(graphs=graphs, chunk=self.chunk, bounds=self.bounds)
                 reset()
         self.n = sum(lo < self.n_steps for lo, _ in self.bounds)      # chunks this loop runs at most
@@ -406,11 +419,62 @@ class Searcher:
                                               _lib.ptr(st["sub"]), _lib.ptr(st["dist"]), _lib.ptr(best_id), _lib.ptr(best_p)),
                    "fira_merge_dist")
 
+    def _force(self, st, R, rows_per_commit, gen, length, best_id, best_p):
+        """fira_force_dist on st["dist"]: the rows still inside their commit's prefix keep the entries of the prefix word only
+        (DESIGN.md section 6q).  The prefix is read from st["prefix"] / st["prefix_len"] when the kernel runs."""
+        _lib.check(_lib.lib().fira_force_dist(_lib.cur_stream(), C.byref(self.model.dims), R, rows_per_commit, _lib.ptr(gen),
+                                              _lib.ptr(length), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["prefix"]),
+                                              _lib.ptr(st["prefix_len"]), _lib.ptr(st["dist"]), _lib.ptr(best_id),
+                                              _lib.ptr(best_p)), "fira_force_dist")
+
+    def _prefix_rows(self, prefix, B: int, con: Optional[Constraints]):
+        """None for "no prefix" (None, or every sequence empty: today's launches, buffers and graphs), else the checked prefix as
+        B lists of vocabulary ids.  Raises ``ValueError`` naming the commit and the reason; nothing is launched before."""
+        if prefix is None:
+            return None
+        cfg = self.cfg
+        try:
+            rows = [list(p) for p in prefix]
+        except TypeError:
+            raise ValueError("prefix: expected one sequence of vocabulary ids per commit, got %r" % (prefix,)) from None
+        if len(rows) != B:
+            raise ValueError("prefix: %d sequences for a batch of %d commits" % (len(rows), B))
+        for b, row in enumerate(rows):
+            for w in row:
+                if isinstance(w, bool) or not isinstance(w, numbers.Integral):
+                    raise ValueError("prefix: commit %d: id %r is not an integer" % (b, w))
+                if not UNK <= w < cfg.vocab_size:
+                    raise ValueError("prefix: commit %d: id %d outside [%d, %d) (<pad>, <eos> and <start> cannot be forced)"
+                                     % (b, w, UNK, cfg.vocab_size))
+            rows[b] = row = [int(w) for w in row]
+            if len(row) > cfg.tar_len - 2:
+                raise ValueError("prefix: commit %d: %d words, more than tar_len - 2 = %d" % (b, len(row), cfg.tar_len - 2))
+            if con is not None:                               # the constraint kernel would zero the forced word: an all-zero row
+                hit = sorted(set(row) & set(con.banned))
+                if hit:
+                    raise ValueError("prefix: commit %d: id %d is banned by the constraints" % (b, hit[0]))
+                n = con.no_repeat_ngram
+                grams = [tuple(row[i:i + n]) for i in range(len(row) - n + 1)] if n >= 1 else []
+                if len(set(grams)) != len(grams):
+                    raise ValueError("prefix: commit %d: the prefix itself repeats a %d-gram, which no_repeat_ngram = %d forbids"
+                                     % (b, n, n))
+        return rows if any(rows) else None
+
+    def _fill_prefix(self, st, rows):
+        """The checked prefix into the state's device buffers (every call, the way ``_state`` fills sou / sub)."""
+        T = self.cfg.tar_len
+        host = torch.zeros((len(rows), T), dtype=torch.int32)
+        for b, row in enumerate(rows):
+            host[b, :len(row)] = torch.tensor(row, dtype=torch.int32)
+        st["prefix"].copy_(host)
+        st["prefix_len"].copy_(torch.tensor([len(row) for row in rows], dtype=torch.int32))
+
     @staticmethod
-    def _key(base, merge: bool, con, scoring=None):
+    def _key(base, merge: bool, con, scoring=None, forced: bool = False):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
-        so merged and unmerged searches own separate buffers and graphs; an active BeamScoring value comes last."""
-        return (base + (("merge",) if merge else ()) + ((con,) if con is not None else ())
+        so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
+        marker only: the prefix values live in device buffers); an active BeamScoring value comes last."""
+        return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + ((con,) if con is not None else ())
                 + ((scoring,) if scoring is not None else ()))
 
     def _banned_buffer(self, c: Constraints):
@@ -450,13 +514,16 @@ class Searcher:
         arg-max of the output distribution, then the hypothesis bookkeeping), no torch op, no host round trip."""
         lib, s = _lib.lib(), _lib.cur_stream()
         for step in range(lo, hi):
-            con, merge = st["con"], st.get("merge", False)
-            if con is None and not merge:
+            con, merge, forced = st["con"], st.get("merge", False), "prefix" in st
+            if con is None and not merge and not forced:
                 self._step(ws, B, 1, step, st["tok"], None, None, st["best_id"], st["best_p"])
             else:       # the step writes the distribution; the last kernel that edits it takes the arg-max of what is left
                 self._step(ws, B, 1, step, st["tok"], None, st["dist"], None, None)
+                best, none = (st["best_id"], st["best_p"]), (None, None)
                 if merge:                                    # words first: a blocked word's mass then sits on its generator entry
-                    self._merge(st, B, 1, *((st["best_id"], st["best_p"]) if con is None else (None, None)))
+                    self._merge(st, B, 1, *(best if con is None and not forced else none))
+                if forced:                                   # the prefix word's entries only, while the row is inside its prefix
+                    self._force(st, B, 1, st["out"], st["length"], *(best if con is None else none))
                 if con is not None:
                     self._constrain(st, B, 1, st["out"], st["length"], st["best_id"], st["best_p"])
             _lib.check(lib.fira_greedy_advance(s, C.byref(self.model.dims), B, step, _lib.ptr(st["best_id"]),
@@ -466,26 +533,32 @@ class Searcher:
                        "fira_greedy_advance")
 
     def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
-                     merge_copies: bool = False) -> _Loop:
+                     merge_copies: bool = False, prefix=None) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  With
         active constraints the state (and so its graphs: the scalars are baked into the captured launches) is keyed by their
         value and also owns the [B, out_len] distribution the constraint kernel edits and the banned ids.  ``merge_copies``
-        is part of the key too (("greedy", B, "merge"), ("greedy", B, "merge", constraints)) and brings the distribution."""
+        is part of the key too (("greedy", B, "merge"), ("greedy", B, "merge", constraints)) and brings the distribution.  An
+        active ``prefix`` adds the "prefix" marker to the key, and the distribution and the two prefix buffers to the state."""
         B = db.B
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
+        rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
 
         def make(i32, f32):
             st = dict(self._hypothesis_rows(i32, f32, B), con=con)
             if merge:
                 st["merge"] = True
-            if con is not None or merge:
+            if con is not None or merge or rows is not None:
                 st["dist"] = f32(B, self.cfg.out_len)
             if con is not None:
                 st["banned"] = self._banned_buffer(con)
+            if rows is not None:
+                st.update(prefix=i32(B, self.cfg.tar_len), prefix_len=i32(B))
             return st
-        loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con), make, chunk, use_graphs)
+        loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
+        if rows is not None:
+            self._fill_prefix(st, rows)
         return loop.start(lambda lo, hi: self._greedy_steps(st, ws, B, lo, hi), lambda: self._greedy_reset(st),
                           lambda hi: self._none_alive(st, hi))
 
@@ -500,7 +573,7 @@ class Searcher:
 
     @torch.no_grad()
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
-               merge_copies: bool = False):
+               merge_copies: bool = False, prefix=None):
         """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``: a ``Constraints``
         value; the step then writes its distribution, ``fira_constrain_dist`` zeroes the blocked words' entries and takes the
         arg-max of the rest (probability = the product of the UNnormalised entries taken); None or inactive: today's loop.
@@ -512,14 +585,25 @@ class Searcher:
         exact, because the next step depends on the resolved ids only -- and no longer the product of the entries taken.
         False: today's loop, keys, buffers and graphs.
 
+        ``prefix``: how every message begins -- a sequence of B sequences of vocabulary ids in [UNK, vocab), without <start>, at
+        most tar_len - 2 long; an empty one means no prefix for that commit.  While a hypothesis is inside its commit's prefix,
+        ``fira_force_dist`` (after the merge, before the constraints) zeroes every entry of the step's distribution that does not
+        resolve to the prefix word, so the search can only take that word -- through its generator entry or a copy slot -- and then
+        continues freely.  The returned probability is the JOINT probability of prefix and continuation (nothing is divided
+        out; the ranking within a commit is unaffected).  ``merge_copies`` is recommended with a prefix: without it the forced
+        word's mass stays split over its entries and the search takes the largest one.  The state is keyed by a "prefix" marker,
+        not by the values (device buffers read when the kernels run: one capture serves every prefix).  A ``ValueError`` before
+        anything is launched on a wrong count, a non-integer id, an id outside [UNK, vocab), a prefix that is too long, or --
+        with ``constraints`` -- one that holds a banned id or itself repeats an n-gram.  None or all empty: today's loop.
+
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
-        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies).run())
+        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix).run())
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
-                    merge_copies: bool = False):
+                    merge_copies: bool = False, prefix=None):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -531,14 +615,27 @@ class Searcher:
         the other.  On 8 queues (run_model.py / bench.py / this package set GPU_MAX_HW_QUEUES=8 before HIP initialises) three
         lanes give x2.06 and four x2.35 in a process that trained first; six collapse again (profiles/r6_probes.md).
         Same arithmetic, same ids as ``greedy`` batch by batch, ``constraints`` and ``merge_copies`` included (with
-        ``merge_copies`` the probability is that of the word sequence, summed over every entry path that spells it)."""
+        ``merge_copies`` the probability is that of the word sequence, summed over every entry path that spells it).
+        ``prefix``: one prefix argument of ``greedy`` per batch (a sequence as long as ``dbs``; an entry may be None); the
+        returned probability is then the joint probability of prefix and continuation."""
         dbs = list(dbs)
-        self._active(constraints)                            # raises before a lane starts
+        con = self._active(constraints)                      # raises before a lane starts
+        if prefix is not None:
+            try:
+                prefix = list(prefix)
+            except TypeError:
+                raise ValueError("prefix: expected one prefix argument per batch, got %r" % (prefix,)) from None
+            if len(prefix) != len(dbs):
+                raise ValueError("prefix: %d prefix arguments for %d batches" % (len(prefix), len(dbs)))
+            for db, p in zip(dbs, prefix):
+                self._prefix_rows(p, db.B, con)              # every batch's, before a lane starts
         n_lane = max(1, min(in_flight, len(dbs)))
         if not hasattr(self, "_lanes") or len(self._lanes) < n_lane:
             streams = concurrent_streams(n_lane, self.model.device_)
             old = getattr(self, "_lanes", [])
-            self._lanes = [(old[k][0] if k < len(old) else (self._lane() if k else self),
+            # (lane 0 is this Searcher, kept as None: a reference to itself would make it a cycle that only the cyclic
+            # collector frees, graphs and buffers included)
+            self._lanes = [(old[k][0] if k < len(old) else (self._lane() if k else None),
                             streams[k]) for k in range(n_lane)]
         main = torch.cuda.current_stream()
         results = [None] * len(dbs)
@@ -550,6 +647,7 @@ class Searcher:
             busy = False
             for k in range(n_lane):
                 lane, stream = self._lanes[k]
+                lane = self if lane is None else lane
                 with torch.cuda.stream(stream):
                     if active[k] is not None:
                         j, loop = active[k]
@@ -561,7 +659,8 @@ class Searcher:
                         else:
                             loop.launch()
                     if active[k] is None and nxt < len(dbs):
-                        loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies)
+                        loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies,
+                                                 None if prefix is None else prefix[nxt])
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -825,8 +924,8 @@ class Searcher:
         st["done"].zero_()
 
     def _beam_steps(self, st, ws, B, beam, lo, hi):
-        """Steps lo..hi-1 of run_model.py:225-340: prepare -> KV-cached decoder step -> (merge, then constraints, when the state
-        has them) -> select, all on the device."""
+        """Steps lo..hi-1 of run_model.py:225-340: prepare -> KV-cached decoder step -> (merge, then the prefix, then constraints,
+        when the state has them) -> select, all on the device."""
         lib, s, T = _lib.lib(), _lib.cur_stream(), self.cfg.tar_len
         for step in range(lo, hi):
             cur, nxt = step & 1, (step + 1) & 1
@@ -836,6 +935,8 @@ class Searcher:
             self._step(ws, B, beam, step, st["tok"], st["parent"] if step > 0 else None, st["dist"], None, None)
             if st.get("merge", False):
                 self._merge(st, B * beam, beam, None, None)
+            if "prefix" in st:
+                self._force(st, B * beam, beam, st["gen"][cur], st["length"][cur], None, None)
             if st["con"] is not None:
                 self._constrain(st, B * beam, beam, st["gen"][cur], st["length"][cur], None, None)
             state = (_lib.ptr(st["dist"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]), _lib.ptr(st["done"]),
@@ -852,7 +953,7 @@ class Searcher:
     @torch.no_grad()
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
-             scoring: Optional[BeamScoring] = None):
+             scoring: Optional[BeamScoring] = None, prefix=None):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``: a ``Constraints``
         value; one ``fira_constrain_dist`` call per step then zeroes the blocked words' entries of every row between the step
         and the selection (nothing is renormalised); None or inactive: today's three calls per step and today's graphs.
@@ -873,6 +974,15 @@ class Searcher:
         buffer, and its reset seeds the first slot of every group.  None or an inactive value: today's key, buffers,
         launches, graphs and three tensors.  A beam of 1 with ``scoring`` given is a ``ValueError``.
 
+        ``prefix``: how every message begins, as for ``greedy``: B sequences of vocabulary ids without <start> (empty: none for
+        that commit).  One ``fira_force_dist`` call per step, after the merge and before the constraints, leaves a row that is
+        still inside its commit's prefix the entries of the prefix word only -- every running row of every group -- so each
+        hypothesis of positive probability starts with the prefix.  The returned probability is the JOINT probability of prefix
+        and continuation (nothing is divided out; the ranking within a commit is unaffected).  Without ``merge_copies`` the
+        beam may spend slots on several entries of the same forced word, exactly as it does on unforced steps: ``merge_copies``
+        is recommended with a prefix.  The key gains a "prefix" marker, not the values; the checks and their ``ValueError`` are
+        those of ``greedy``.  None or all empty: today's calls, keys, buffers and graphs.
+
         Per step: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library calls, no torch
         op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam) shape, and
         the ``done`` latch is read back between chunks (run_model.py:276-279)."""
@@ -884,6 +994,7 @@ class Searcher:
             if not isinstance(scoring, BeamScoring):
                 raise ValueError("scoring: expected decode.BeamScoring or None, got %r" % (scoring,))
             scoring = scoring.check(beam) if scoring.active() or beam < 2 else None
+        rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
 
         def make(i32, f32):
             st = dict(gen=[i32(BR, T), i32(BR, T)], length=[i32(BR), i32(BR)], prob=[f32(BR), f32(BR)], tok=i32(BR),
@@ -892,13 +1003,17 @@ class Searcher:
                 st["merge"] = True
             if con is not None:
                 st["banned"] = self._banned_buffer(con)
+            if rows is not None:
+                st.update(prefix=i32(B, T), prefix_len=i32(B))
             if scoring is not None:
                 st.update(scoring=scoring, key=f32(BR),
                           inv_lp=torch.tensor(scoring.inv_lp(T), dtype=torch.float64).to(torch.float32).to(self.model.device_))
             return st
         # (a captured graph bakes the constraint scalars, the merge launch and the scoring scalars: they are part of the key)
-        loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring), make, chunk, use_graphs)
+        loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring, rows is not None), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
+        if rows is not None:
+            self._fill_prefix(st, rows)
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
         cur = loop.hi & 1                                    # the ping-pong buffer the last step run wrote

@@ -897,6 +897,33 @@ int fira_merge_dist(void* stream, const fira_dims* d, int R, int rows_per_commit
                     float* dist /* [R, vocab + sou_len + sub_len], in place */,
                     int32_t* best_id, float* best_p /* both NULL or both given */);
 
+/* Prefix-forced search (csrc/force.hip; additive, the ABI version is unchanged): cuts the step's distribution down to the word a
+ * given message start asks for, in place, between fira_decode_step (fira_mix_dist, fira_merge_dist, if any) and fira_constrain_dist,
+ * if any, then the selection.  The mirror image of fira_constrain_dist, with its definitions: W = vocab + sou_len + sub_len, entry i
+ * resolves to the word w(i), row r belongs to commit b = r / rows_per_commit, len = length[r] clamped to 1 .. tar_len, m = len - 1
+ * words emitted, and a row with gen[r, len - 1] == <eos> (1) is finished.  prefix[b, 0 .. prefix_len[b]) are the words the commit's
+ * message begins with (no <start>); a negative prefix_len counts as 0, one above tar_len as tar_len.
+ *   forced row   not finished and m < min(prefix_len[b], tar_len); its word is y = prefix[b, m].  Every entry i with w(i) != y is
+ *                set to exactly +0.0f; every entry with w(i) == y keeps its bits: the generator entry y if 0 <= y < vocab, and every
+ *                copy slot that carries y.  Nothing is renormalised.  A y outside [0, vocab) is never used as an index: it matches
+ *                slots only (and, where no slot carries it, leaves an all-zero row).
+ *   other rows   untouched.
+ * best_id / best_p (both NULL, or both [R]): the arg-max of the row as it stands after the edit and its value, under (value
+ * descending, index ascending) -- the order of fira_constrain_dist; NaN never wins.  A forced row whose kept entries are all 0
+ * reports entry 0 (every candidate ties at 0).  Where no row is forced they equal the step's own bit for bit.  A forced row is not
+ * read beyond its kept entries: its arg-max needs only those, and its zeros are plain stores (16-byte ones where the address allows,
+ * 4-byte ones at the row's edges and around a kept entry).  A row that is not forced is read once with best_id, else not at all.
+ * prefix and prefix_len are DEVICE arrays read when the kernel runs, so one captured launch serves every prefix.
+ * tar_len <= 64, vocab in 4 .. 25 600, sou_len + sub_len <= 1 024, rows_per_commit >= 1 divides R; R == 0 is a no-op.  Any row
+ * width and any 4-byte alignment of dist; vector stores only, no atomics on global memory.                                    */
+int fira_force_dist(void* stream, const fira_dims* d, int R, int rows_per_commit, const int32_t* gen /* [R, tar_len] */,
+                    const int32_t* length /* [R] */, const int32_t* sou /* [R / rows_per_commit, sou_len] */,
+                    const int32_t* sub_token /* [R / rows_per_commit, sub_len] */,
+                    const int32_t* prefix /* device, [R / rows_per_commit, tar_len]: words only, no <start> */,
+                    const int32_t* prefix_len /* device, [R / rows_per_commit] */,
+                    float* dist /* [R, vocab + sou_len + sub_len], in place */,
+                    int32_t* best_id, float* best_p /* both NULL or both [R] */);
+
 /* Ensemble decoding (csrc/mix.hip; additive, the ABI version is unchanged): mixes the step distributions of n_members models into
  * one, between the members' fira_decode_step calls and whatever takes a distribution next (fira_merge_dist, fira_constrain_dist,
  * fira_beam_select / fira_beam_select_scored / fira_greedy_advance).  For every element i of the [R, W] rows, in member order,

@@ -129,6 +129,12 @@ def parse_args(argv):
                     "file in the layout of best_model.pt, which stays member 0 (up to 8 models in all)")
     ap.add_argument("--ensemble-weights", default=None, metavar="W0,W1,...", help="with --ensemble: one weight >= 0 per model, "
                     "best_model.pt first; normalised to sum 1 (default: uniform)")
+    ap.add_argument("--prefix", default=None, metavar="WORDS", help="test: every message of the search (any --beam) begins "
+                    "with these words; a word is forced through its generator id or a copy slot that carries it, identifiers go "
+                    "through the commit's variable map, a word the vocabulary lacks is forced as <unkm>; at most tar_len - 2 "
+                    "words; --merge-copies is recommended with it")
+    ap.add_argument("--prefix-file", default=None, metavar="PATH", help="test: as --prefix, with one line per test commit in "
+                    "all_index['test'] order (an empty line: no prefix for that commit)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
@@ -159,6 +165,7 @@ def parse_args(argv):
         check_constraint_args(a)
         check_merge_args(a)
         check_scoring_args(a)
+        check_prefix_args(a)
         check_ensemble_args(a)
         check_sample_args(a)
     except ValueError as e:
@@ -393,6 +400,63 @@ def scoring_from_args(a):
         return None
     sc = BeamScoring(length_alpha=a.length_penalty or 0.0, groups=a.beam_groups or 1, diversity=a.diversity_penalty or 0.0)
     return sc.check(a.beam) if sc.active() else None
+
+
+def check_prefix_args(a):
+    """Validates --prefix / --prefix-file against the other options and the file system (no GPU, no DataSet needed); raises
+    ValueError on a conflict.  The words are looked up later (prefixes_from_args)."""
+    words, path = getattr(a, "prefix", None), getattr(a, "prefix_file", None)
+    given = [flag for v, flag in ((words, "--prefix"), (path, "--prefix-file")) if v is not None]
+    if not given:
+        return a
+    if len(given) == 2:
+        raise ValueError("--prefix and --prefix-file are mutually exclusive")
+    if a.stage != "test":
+        raise ValueError("%s only apply to the test stage" % ", ".join(given))
+    if a.sample is not None:
+        raise ValueError("%s begin the messages of a search: they do not combine with --sample" % ", ".join(given))
+    if a.score is not None:
+        raise ValueError("%s begin the messages of a search: they do not combine with --score" % ", ".join(given))
+    if words is not None and not words.split():
+        raise ValueError("--prefix: no word given")
+    if path is not None and not os.path.isfile(path):
+        raise ValueError("--prefix-file %s: no such file" % path)
+    return a
+
+
+def read_prefix_lines(path, n_commits):
+    """The lines of ``--prefix-file PATH``, one per test commit (an empty line: no prefix).  Raises ValueError on a wrong line
+    count."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    if len(lines) != n_commits:
+        raise ValueError("--prefix-file %s: %d lines for %d test commits" % (path, len(lines), n_commits))
+    return lines
+
+
+def prefixes_from_args(a, vocab, var_maps, tar_len):
+    """The forced message starts of the command line: (None, 0) without the options, else (one list of vocabulary ids per test
+    commit, the number of words that became <unkm> because the vocabulary lacks them).  ``var_maps``: the commits' variable
+    maps in test order; its length is the number of test commits.  Lines are tokenised with text.tokenize_message (the
+    commit's identifiers to their placeholders), <start> / <eos> stripped.  Raises ValueError on a wrong line count or a
+    prefix of more than tar_len - 2 words, naming the line."""
+    words, path = getattr(a, "prefix", None), getattr(a, "prefix_file", None)
+    if words is None and path is None:
+        return None, 0
+    n = len(var_maps)
+    lines = [words] * n if words is not None else read_prefix_lines(path, n)
+    out, n_unk = [], 0
+    for k, (line, var_map) in enumerate(zip(lines, var_maps)):
+        toks = line.split()
+        if len(toks) > tar_len - 2:
+            where = "--prefix" if words is not None else "--prefix-file %s: line %d" % (path, k + 1)
+            raise ValueError("%s: %d words, more than tar_len - 2 = %d" % (where, len(toks), tar_len - 2))
+        ids = text.tokenize_message(line, vocab, var_map, len(toks) + 2)[1:-1]
+        n_unk += sum(1 for w in toks if w != text.UNK_EMOJI and var_map.get(w, w) not in vocab)
+        out.append(ids)
+    return out, n_unk
 
 
 def check_ensemble_args(a):
@@ -663,6 +727,9 @@ class Run:
         if self.a.score is not None and self.a.score != "refs":
             given = read_score_lines(self.a.score, len(store))   # a wrong line count is an error before the model loads
         constraints = constraints_from_args(self.a, self.vocab, cfg)       # an unknown word too
+        prefixes, n_unk = prefixes_from_args(self.a, self.vocab, [self.var_maps[i] for i in test_index], cfg.tar_len)
+        if n_unk and self.rank == 0:                         # (a wrong line count or a line too long: an error before the model loads)
+            print("warning: %d prefix words are not in the vocabulary and are forced as <unkm>" % n_unk, file=sys.stderr, flush=True)
         scoring = scoring_from_args(self.a)
         self.model = TransModel(cfg, device="cuda:%d" % self.local, init=False)
         self.model.load_state_dict(torch.load(os.path.join(self.root, "best_model.pt"), map_location="cpu"))
@@ -691,17 +758,20 @@ class Run:
         for g0 in range(0, len(starts), group):
             idxs = [mine[lo:lo + cfg.test_batch_size] for lo in starts[g0:g0 + group]]
             dbs = [self.device_batch(store, idx) for idx in idxs]
+            # (--prefix / --prefix-file: the commits' forced message starts, batch by batch; without them no argument at all)
+            forced = {} if prefixes is None else {"prefix": [[prefixes[i] for i in idx] for idx in idxs]}
             if cfg.beam_size == 1:
                 outs = [search.best(*r) for r in search.greedy_many(dbs, in_flight=group, constraints=constraints,
-                                                                    merge_copies=merge)]
+                                                                    merge_copies=merge, **forced)]
             else:
                 keys = None
+                forced = {k: v[0] for k, v in forced.items()}
                 if scoring is None:
-                    gen, length, prob = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge)
+                    gen, length, prob = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge, **forced)
                     outs = [search.best(gen, length, prob)]
                 else:                                        # ranked by key: the best slot of positive probability, lowest on ties
                     gen, length, prob, keys = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge,
-                                                          scoring=scoring)
+                                                          scoring=scoring, **forced)
                     outs = [search.best(gen, length, keys)]
                     keys = keys.tolist()
                 if want_nbest:                               # the whole beam of every commit, best first
