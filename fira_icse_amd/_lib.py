@@ -143,6 +143,9 @@ SIGNATURES = {
     "fira_inv_count": (_I, [_P, _P, _P]),
     "fira_adam_step_count": (_I, [_P, _L, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P]),
     "fira_pack_stats": (_I, [_P, _P, _P, _P]),
+    "fira_accum_stats": (_I, [_P, _P, _P, _P, _P, _I]),
+    "fira_train_accum_micro": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, C.POINTER(AdamOpts), _P]),
+    "fira_train_accum_last": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, C.POINTER(AdamOpts), _P, _P, _P, _F, _P, _P]),
     "fira_debug_chain": (_I, [_P, _I, _I, _P]),
     "fira_train_fwd_bwd": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, _P]),
     "fira_train_step": (_I, [_P, _DP, _BP, _P, _P, _P, _Z, _OP, _P, _P, C.POINTER(AdamOpts)]),

@@ -285,6 +285,8 @@ int decode_dist(hipStream_t s, int R, int V, int S, const float* logits, int ldl
                 const int32_t* mem_valid, int qpk, const float* gate_logits, float* dist, int32_t* best_id,
                 float* best_p, const float* x = nullptr, const float* wp = nullptr, const float* bp = nullptr);
 int inv_count(hipStream_t s, const int32_t* n_tok, float* out);
+// rowops.hip: stats = {loss_sum, float(n_tok)} summed over an optimizer step's micro-batches (fira_accum_stats)
+int accum_stats(hipStream_t s, const float* loss_sum, const int32_t* n_tok, float* stats, int32_t* n_tok_total, int first);
 // sample.hip: the same distribution row as decode_dist (inline gate form, bit-identical dist), then temperature / top-k / top-p
 // and a Gumbel-max draw per (commit, sample) row; best_id / best_p as decode_dist writes them (see fira_decode_step_sample)
 int sample_dist(hipStream_t s, int R, int n_sample, int V, int S, const float* logits, int ldl, const float* score,

@@ -738,6 +738,7 @@ struct Ctx {
     bool adam_a_only = false;
     hipEvent_t ev_early = nullptr;
     const float* count = nullptr;
+    // (gradient accumulation, fira_train_accum_last: `count` = the accumulated token count normalises the one-device update too)
     // fira_train_step_clip: the update clipped by the global gradient norm (gradnorm.hip).  Every update depends on every
     // gradient, so nothing is updated ahead of the final join (c.adam stays null: no early Adam); the sum of squares of
     // [0, split) runs on the auxiliary stream where mid_event would fire, beside the encoder's backward pass.
@@ -1503,6 +1504,16 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     return 0;
 }
 
+// the one-device step's dense update of [lo, hi): normalised by the call's own token counter or -- the last micro-batch of an
+// accumulated step (Ctx::count) -- by the accumulated count
+static int adam_own(Ctx& c, hipStream_t s, const fira_adam_opts& ad, int64_t lo, int64_t hi) {
+    const float lr = adam_lr(ad).at(ad.step);
+    if (c.count)
+        return adam_step(s, hi - lo, c.Pw + lo, c.G + lo, ad.m + lo, ad.v + lo, lr, ad.beta1, ad.beta2, ad.eps, ad.step, c.count, 1);
+    return adam_step_mb(s, hi - lo, c.Pw + lo, c.G + lo, nullptr, ad.m + lo, ad.v + lo, lr, ad.beta1, ad.beta2, ad.eps, ad.step, c.n_tok,
+                        nullptr);
+}
+
 static int backward_encoder(Ctx& c, BwdMid& mid) {
     Plan& p = *c.pl;
     const Layout& L = *c.L;
@@ -1692,8 +1703,7 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         if (ev_groupA) TRY(main_wait(s, ev_groupA, __LINE__));
         // (row-sparse tables: decoder.embedding is the head of [0, split) -- layout.cpp -- and is left to the rows launch below)
         const int64_t a0 = c.row_step ? L.dec_emb + (int64_t)L.d.vocab * D : 0;
-        TRY(adam_step_mb(s, L.split - a0, c.Pw + a0, G + a0, nullptr, ad.m + a0, ad.v + a0, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps,
-                         ad.step, c.n_tok, nullptr));
+        TRY(adam_own(c, s, ad, a0, L.split));
         }
         // ... and the encoder's two embedding tables (the head of group B: layout.cpp), whose gradients the two launches above
         // on this stream have just completed -- also ahead of the join (+0.4 % against behind it, profiles/r5_probes.md)
@@ -1702,12 +1712,11 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
             // both vocabulary-sized tables as ONE launch over the rows whose gradient row is not zero (the gradient rows are
             // inspected: 2 x 25 MB read instead of 2 x 177 MB moved); the 71-row table joins the closing launch
             TRY(adam_rows_step(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, adam_lr(ad), ad.beta1, ad.beta2, ad.eps, ad.step,
-                               c.n_tok, nullptr));
+                               c.count ? nullptr : c.n_tok, c.count));
             adam_b0 = L.ast_emb;
         } else
         if (adam_b0 > L.split)
-        TRY(adam_step_mb(s, adam_b0 - L.split, c.Pw + L.split, G + L.split, nullptr, ad.m + L.split, ad.v + L.split, adam_lr(ad).at(ad.step), ad.beta1,
-                         ad.beta2, ad.eps, ad.step, c.n_tok, nullptr));
+        TRY(adam_own(c, s, ad, L.split, adam_b0));
     }
     if (ev_tail) TRY(main_wait(s, ev_tail, __LINE__));
     if (side().stream && side().enabled) TRY(side_join(s, __LINE__));        // every weight gradient is complete past this point
@@ -1716,8 +1725,7 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
     TRY(gcn_bias_unfold_all(s, unfold_tab));
     if (c.adam && !c.adam_a_only) {
         const fira_adam_opts& ad = *c.adam;
-        TRY(adam_step_mb(s, L.live - adam_b0, c.Pw + adam_b0, G + adam_b0, nullptr, ad.m + adam_b0, ad.v + adam_b0, adam_lr(ad).at(ad.step), ad.beta1,
-                         ad.beta2, ad.eps, ad.step, c.n_tok, nullptr));
+        TRY(adam_own(c, s, ad, adam_b0, L.live));
     }
     if (c.clip) {
         // every gradient of [0, live) is final here (and the auxiliary stream's sum over [0, split) precedes ev_tail): the sum
@@ -1725,16 +1733,17 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         // when row_step is given, the rest as dense launches over the gaps between them
         const ClipStep& cl = *c.clip;
         const fira_adam_opts& ad = *cl.adam;
-        const ClipClose fin{c.n_tok, nullptr, cl.max_norm, 2};
+        const int32_t* n_own = c.count ? nullptr : c.n_tok;      // (an accumulated step: norm and updates by the accumulated count)
+        const ClipClose fin{n_own, c.count, cl.max_norm, 2};
         TRY(grad_sqsum(s, L.live - L.split, G + L.split, cl.state, 1, cl.scratch, &fin));
         auto dense = [&](int64_t lo, int64_t hi) {
             return adam_step_clip(s, hi - lo, c.Pw + lo, G + lo, ad.m + lo, ad.v + lo, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps, ad.step,
-                                  c.n_tok, nullptr, cl.state);
+                                  n_own, c.count, cl.state);
         };
         if (c.row_step) {
             const int64_t tab = (int64_t)L.d.vocab * D;
             TRY(adam_rows_step_clip(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, adam_lr(ad), ad.beta1, ad.beta2, ad.eps, ad.step,
-                                    c.n_tok, nullptr, 3, cl.state));
+                                    n_own, c.count, 3, cl.state));
             const int64_t t0 = std::min(L.dec_emb, L.emb), t1 = std::max(L.dec_emb, L.emb);
             TRY(dense(0, t0));
             TRY(dense(t0 + tab, t1));
@@ -1829,10 +1838,17 @@ struct PendingStep {
 };
 static thread_local PendingStep g_pending;
 
+// gradient accumulation (fira_train_accum_micro / _last): which micro-batch of an optimizer step a call runs
+struct AccumStep {
+    bool last;               // false: forward + backward only (adam serves the lazy reads of lagging word-table rows)
+    float* stats;            // last: the running {loss_sum, float(n_tok)} pair ...
+    int32_t* total;          // ... and the exact token total the call adds its own scalars to
+};
+
 static int train_call(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
                       void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
                       int32_t* n_tok, void* mid_event, float* params_w, const fira_adam_opts* adam, bool begin_only = false,
-                      int32_t* row_step = nullptr, const ClipStep* clip = nullptr) {
+                      int32_t* row_step = nullptr, const ClipStep* clip = nullptr, const AccumStep* acc = nullptr) {
     const Layout* L = get_layout(d);
     if (!L) return 1;
     TRY(check_batch(batch));
@@ -1890,6 +1906,7 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
     c.dp_begin = begin_only;
     if (begin_only) c.adam = nullptr;        // (fira_train_step_begin_rows: the optimizer's values serve the lazy reads only)
     if (clip) { c.adam = nullptr; c.clip = clip; }      // (clipped step: the update follows the final join, see backward_encoder)
+    if (acc && !acc->last) c.adam = nullptr; // (a micro-batch ahead of the last: nothing is updated)
     TRY(encoder_forward(c, true));
     if (side_on()) {
         // the buffers the backward pass accumulates into are cleared on the auxiliary stream beside the forward pass (they
@@ -1906,6 +1923,12 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
     if (c.ev_shadow) TRY(main_wait(c.s, c.ev_shadow, __LINE__));      // the decoder's products read the bf16 shadows
     TRY(decoder_forward(c));
     TRY(head_forward(c, R, rows, loss_sum, n_tok, nullptr, 1));
+    if (acc && acc->last) {
+        // the step's scalars are final on the caller's stream: add them to the optimizer step's pair here, ahead of every update
+        // launch of this call (all of them are enqueued behind this point of the caller's stream)
+        TRY(accum_stats(c.s, loss_sum, n_tok, acc->stats, acc->total, 0));
+        c.count = acc->stats + 1;
+    }
     if (begin_only) {
         // first half of a data-parallel step: up to the point where the gradients of [0, split) are final (mid_event)
         PendingStep& ps = g_pending;
@@ -1997,7 +2020,8 @@ int fira_train_step_begin_rows(void* stream, const fira_dims* d, const fira_batc
     FIRA_REQUIRE(mid_event, "fira_train_step_begin_rows: mid_event missing (the caller's collective waits for it)");
     FIRA_REQUIRE(adam && adam->m && adam->v && adam->step >= 1 && row_step, "fira_train_step_begin_rows: bad Adam arguments");
     TRY(adam_sched_check(adam));
-    FIRA_REQUIRE(opts && opts->zero_grads, "fira_train_step_begin_rows: needs opts.zero_grads");
+    // (opts.zero_grads = 0: the last micro-batch of an accumulated step -- the gradient holds this step's earlier micro-batches,
+    //  cleared by the first of them: include/fira_hip.h, gradient accumulation)
     // (adam only parameterises the lazy reads; train_call(begin_only) returns before any update)
     return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, mid_event, nullptr,
                       adam, true, row_step);
@@ -2066,6 +2090,39 @@ int fira_train_step_clip(void* stream, const fira_dims* d, const fira_batch* bat
     const ClipStep clip{adam, max_norm, state, scratch};
     return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
                       false, row_step, &clip);
+}
+// Gradient accumulation (include/fira_hip.h): compositions of train_call's existing forms.  A micro-batch ahead of the last is
+// fira_train_fwd_bwd with the lazy reads of fira_train_step_begin_rows; the last one is the one-call step with the accumulated
+// count in place of its own token counter.
+int fira_train_accum_micro(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
+                           void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok,
+                           const fira_adam_opts* adam, int32_t* row_step) {
+    FIRA_REQUIRE((adam != nullptr) == (row_step != nullptr), "fira_train_accum_micro: adam and row_step are given together");
+    FIRA_REQUIRE(!adam || (adam->m && adam->v && adam->step >= 1), "fira_train_accum_micro: bad Adam arguments");
+    TRY(adam_sched_check(adam));
+    const AccumStep acc{false, nullptr, nullptr};
+    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, nullptr, adam,
+                      false, row_step, nullptr, &acc);
+}
+int fira_train_accum_last(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads, void* workspace,
+                          size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok,
+                          const fira_adam_opts* adam, int32_t* row_step, float* stats, int32_t* n_tok_total, float max_norm,
+                          fira_clip_state* clip_state, void* clip_scratch) {
+    FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_accum_last: Adam moments missing");
+    FIRA_REQUIRE(adam->step >= 1, "fira_train_accum_last: the Adam step counter starts at 1");
+    TRY(adam_sched_check(adam));
+    FIRA_REQUIRE(stats && n_tok_total, "fira_train_accum_last: the accumulated stats pair / token total is missing");
+    FIRA_REQUIRE((const void*)stats != (const void*)loss_sum && (const void*)n_tok_total != (const void*)n_tok,
+                 "fira_train_accum_last: the totals must not alias the micro-batch's scalars");
+    const AccumStep acc{true, stats, n_tok_total};
+    if (!clip_state)
+        return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
+                          false, row_step, nullptr, &acc);
+    FIRA_REQUIRE(max_norm > 0.f, "fira_train_accum_last: max_norm must be > 0 (inf allowed)");
+    FIRA_REQUIRE(clip_scratch && (uintptr_t)clip_scratch % 8 == 0, "fira_train_accum_last: clip scratch missing");
+    const ClipStep clip{adam, max_norm, clip_state, clip_scratch};
+    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
+                      false, row_step, &clip, &acc);
 }
 int fira_adam_rows_step_clip(void* stream, const fira_dims* d, float* params, const float* grads, const fira_adam_opts* adam,
                              int32_t* row_step, const int32_t* n_tok, const float* count, int tables,

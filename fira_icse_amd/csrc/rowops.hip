@@ -1058,9 +1058,31 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(int64_t n, float* __r
     if (i < n) out[i] = p > 0.f ? dropout_scale(seed, site, (uint32_t)i, p, inv_keep) : 1.f;
 }
 
+// gradient accumulation: the running {loss_sum, float(n_tok)} pair of an optimizer step's micro-batches (fira_pack_stats'
+// layout) and the exact int32 token total behind it.  One lane, ordinary stores: the stream orders the micro-batches.
+__global__ void accum_stats_kernel(const float* __restrict__ loss_sum, const int32_t* __restrict__ n_tok, float* __restrict__ stats,
+                                   int32_t* __restrict__ n_tok_total, int first) {
+    const float l0 = first ? 0.f : stats[0];
+    const int32_t total = (first ? 0 : *n_tok_total) + *n_tok;
+    stats[0] = l0 + *loss_sum;
+    stats[1] = (float)total;
+    *n_tok_total = total;
+}
+int accum_stats(hipStream_t s, const float* loss_sum, const int32_t* n_tok, float* stats, int32_t* n_tok_total, int first) {
+    hipLaunchKernelGGL(accum_stats_kernel, dim3(1), dim3(1), 0, s, loss_sum, n_tok, stats, n_tok_total, first);
+    FIRA_CHECK_LAUNCH("accum_stats");
+    return 0;
+}
+
 }  // namespace fira
 
 extern "C" {
+int fira_accum_stats(void* stream, const float* loss_sum, const int32_t* n_tok, float* stats, int32_t* n_tok_total, int first) {
+    FIRA_REQUIRE(loss_sum && n_tok && stats && n_tok_total, "fira_accum_stats: null pointer argument");
+    FIRA_REQUIRE((const void*)stats != (const void*)loss_sum && (const void*)n_tok_total != (const void*)n_tok,
+                 "fira_accum_stats: the totals must not alias the micro-batch's scalars");
+    return fira::accum_stats((hipStream_t)stream, loss_sum, n_tok, stats, n_tok_total, first);
+}
 int fira_f32_to_bf16(void* stream, int64_t n, const float* in, uint16_t* out) {
     FIRA_REQUIRE(in && out && n >= 0, "fira_f32_to_bf16: bad argument");
     return fira::rows_to_bf16((hipStream_t)stream, n, in, out);

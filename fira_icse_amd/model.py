@@ -539,11 +539,63 @@ class TransModel(nn.Module):
                    "fira_train_step")
         return self.loss_sum, self.n_tok
 
+    def train_accum_micro(self, db: DeviceBatch, zero_grad: bool, rows=None, sched=None, dropout: Optional[float] = None,
+                          gcn_dropout: Optional[float] = None):
+        """A micro-batch of an accumulated step that is not its last (fira_train_accum_micro): :meth:`train_fwd_bwd` --
+        ``self.gbuf`` is added to unless ``zero_grad`` (the first micro-batch) -- that, with ``rows`` (as
+        :meth:`train_step_begin` takes them), reads the word-table rows the row-sparse Adam still owes lazily.  Updates nothing."""
+        lib = _lib.lib()
+        if rows is None:
+            self.sync_params()
+        db.wait_ready()
+        p = (self.cfg.dropout_rate if self.training else 0.0) if dropout is None else dropout
+        pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
+        self.dropout_step += 1                                   # every micro-batch draws its own masks
+        opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
+                              1 if self.compact_dec else 0, 1 if zero_grad else 0)
+        ws = self.workspace(db.B, 1)
+        adam, row_step = None, None
+        if rows is not None:
+            m_, v_, lr, step, b1, b2, eps, row_step = rows
+            adam = C.byref(_lib.AdamOpts(lr, b1, b2, eps, int(step), _lib.ptr(m_), _lib.ptr(v_), _lib.sched_ptr(sched)))
+        _lib.check(lib.fira_train_accum_micro(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
+                                              _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
+                                              C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), adam,
+                                              _lib.ptr(row_step)), "fira_train_accum_micro")
+        return self.loss_sum, self.n_tok
+
+    def train_accum_last(self, db: DeviceBatch, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, stats: torch.Tensor,
+                         n_tok_total: torch.Tensor, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                         dropout: Optional[float] = None, gcn_dropout: Optional[float] = None,
+                         row_step: Optional[torch.Tensor] = None, clip=None, sched=None):
+        """The last micro-batch of an accumulated step (fira_train_accum_last): :meth:`train_step` on a gradient buffer that
+        holds the earlier micro-batches; the library adds this one's scalars to ``stats`` / ``n_tok_total``
+        (``ops.accum_stats``) and normalises the update -- and a clipped step's norm -- by the accumulated count."""
+        lib = _lib.lib()
+        if row_step is None:
+            self.sync_params()
+        db.wait_ready()
+        p = (self.cfg.dropout_rate if self.training else 0.0) if dropout is None else dropout
+        pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
+        self.dropout_step += 1
+        opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
+                              1 if self.compact_dec else 0, 0)
+        adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v), _lib.sched_ptr(sched))
+        ws = self.workspace(db.B, 1)
+        max_norm, state, scratch = (0.0, None, None) if clip is None else clip
+        _lib.check(lib.fira_train_accum_last(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
+                                             _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
+                                             C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), C.byref(adam),
+                                             _lib.ptr(row_step), _lib.ptr(stats), _lib.ptr(n_tok_total), float(max_norm),
+                                             _lib.ptr(state), _lib.ptr(scratch)), "fira_train_accum_last")
+        return self.loss_sum, self.n_tok
+
     def train_step_begin(self, db: DeviceBatch, mid_event, dropout: Optional[float] = None,
-                         gcn_dropout: Optional[float] = None, rows=None, sched=None):
+                         gcn_dropout: Optional[float] = None, rows=None, sched=None, zero_grad: bool = True):
         """First half of a data-parallel step (fira_train_step_begin): forward + the backward pass of the head and the decoder;
         ``mid_event`` fires when the gradients of ``[0, split)`` are final.  The step stays pending until
-        :meth:`train_step_end`; ``db`` must stay alive until then."""
+        :meth:`train_step_end`; ``db`` must stay alive until then.  ``zero_grad=False``: the last micro-batch of an accumulated
+        step -- ``self.gbuf`` holds the earlier ones."""
         lib = _lib.lib()
         if rows is None:
             self.sync_params()
@@ -552,7 +604,7 @@ class TransModel(nn.Module):
         pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
         self.dropout_step += 1
         opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
-                              1 if self.compact_dec else 0, 1)
+                              1 if self.compact_dec else 0, 1 if zero_grad else 0)
         ws = self.workspace(db.B, 1)
         self._pending_db = db
         if rows is not None:

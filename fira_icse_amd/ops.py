@@ -576,6 +576,35 @@ def pack_stats(loss_sum, n_tok, out2):
     return out2
 
 
+ACCUM_MAX = 64
+
+
+def accum_check(k):
+    """Validates a number of micro-batches per optimizer step, ``1 <= K <= ACCUM_MAX`` (``None`` = 1); raises ``ValueError``."""
+    if k is None:
+        return 1
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ACCUM_MAX:
+        raise ValueError("accum steps %r: must be an integer in [1, %d]" % (k, ACCUM_MAX))
+    return int(k)
+
+
+def accum_split(lo: int, hi: int, k: int):
+    """The K micro-batches of a rank's shard ``[lo, hi)`` of the global batch: K ranges of ``ceil((hi - lo) / K)`` commits in
+    order.  A short shard leaves the last ones smaller or empty (``(hi, hi)``): every rank still makes K entries.  Host only."""
+    k = accum_check(k)
+    n = max(hi - lo, 0)
+    size = -(-n // k)
+    return [(min(lo + i * size, hi), min(lo + (i + 1) * size, hi)) for i in range(k)]
+
+
+def accum_stats(loss_sum, n_tok, stats, n_tok_total, first: bool):
+    """``stats = [loss_sum, float(n_tok)]`` summed over an optimizer step's micro-batches (fira_accum_stats; ``pack_stats``'
+    layout), the exact token total in the int32 ``n_tok_total``; ``first`` starts a new sum whatever the buffers hold."""
+    check(_lib.lib().fira_accum_stats(cur_stream(), ptr(_f32(loss_sum)), ptr(_i32(n_tok)), ptr(_f32(stats)),
+                                      ptr(_i32(n_tok_total)), 1 if first else 0), "fira_accum_stats")
+    return stats
+
+
 def adam_step_mb(p, g0, g1, m, v, lr, step, n_tok0, n_tok1=None, beta1=0.9, beta2=0.999, eps=1e-8):
     """Adam on g0 (+ g1) / max(n_tok0 (+ n_tok1), 1): one launch, normaliser formed on the device."""
     check(_lib.lib().fira_adam_step_mb(cur_stream(), p.numel(), ptr(_f32(p)), ptr(_f32(g0)), ptr(g1), ptr(_f32(m)),

@@ -22,7 +22,7 @@ class Trainer:
     def __init__(self, model: TransModel, lr: Optional[float] = None, betas=(0.9, 0.999), eps: float = 1e-8,
                  distributed: bool = False, zero1: bool = False, grad_wire: str = "f32",
                  clip_grad_norm: Optional[float] = None, lr_schedule=None, ema_decay: Optional[float] = None,
-                 ema_every: int = 32):
+                 ema_every: int = 32, accum_steps: Optional[int] = None):
         """``zero1`` (with ``distributed``): reduce-scatter + Adam on the owned 1/world shard + all-gather instead of
         all-reduce + replicated Adam; Adam moments exist only for the owned shard (parallel.ShardedOptimizerComm).
         ``grad_wire`` (with ``distributed``, all-reduce path): "f32", or "bf16" = the two gradient buckets travel as bf16
@@ -39,7 +39,12 @@ class Trainer:
         correction -- and after every ``ema_every``-th step (K, default 32: the cadence at which the row-sparse update has
         just written every row) moves toward them by ``w = ops.ema_weight(D, K) = float32(1 - D**K)``:
         ``e += w * (p - e)``, each operation rounded to fp32 on its own.  Embedding rows the row-sparse Adam still owes updates
-        are read as the forward pass reads them (fira_ema_update_rows): nothing is synced.  See :meth:`averaged`."""
+        are read as the forward pass reads them (fira_ema_update_rows): nothing is synced.  See :meth:`averaged`.
+        ``accum_steps`` (``None`` = 1): how many micro-batches the command line cuts a rank's shard of the global batch into
+        (``ops.accum_check``); kept for the caller only -- :meth:`step_many` takes a sequence of any length and :meth:`step`
+        never looks at it."""
+        self.accum_steps = ops.accum_check(accum_steps)
+        self._acc_last = False                                   # the last step was accumulated: last_loss reads self.stats
         self.ema = None
         self.ema_cfg = None
         self.ema_updates = 0                                     # updates behind self.ema (a loaded state: t // K)
@@ -96,6 +101,7 @@ class Trainer:
             self.ema = model.flat.data.clone()
         self.inv = torch.zeros(1, dtype=torch.float32, device=model.gbuf.device)
         self.stats = torch.zeros(2, dtype=torch.float32, device=model.gbuf.device)
+        self.n_tok_total = torch.zeros(1, dtype=torch.int32, device=model.gbuf.device)   # step_many: the exact int32 behind stats[1]
         self.reducer = GradReducer(model.layout.split, model.layout.live, wire=grad_wire) if distributed else None
         self.mid_event = None
         if distributed:
@@ -114,6 +120,65 @@ class Trainer:
         self._step(db)
         if self.ema is not None and self.t != t:
             self._ema_update()
+
+    def step_many(self, dbs):
+        """ONE optimisation step over the micro-batches ``dbs`` (a non-empty sequence of ``DeviceBatch`` or ``None``): the
+        gradient of the loss SUM is accumulated over them on the device and the update is normalised by the sum of their token
+        counts -- the step of their concatenation, in the memory of the largest of them.  ``self.t``, the learning-rate
+        schedule, the EMA cadence, the clip counters and the ``row_step`` stamps advance by one; the dropout masks are drawn per
+        micro-batch (``model.dropout_step`` advances with every pass).  ``None`` entries (empty micro-batches) are skipped;
+        with one entry left this IS :meth:`step` -- the same library calls -- and with none it is ``step(None)``.  On the
+        data-parallel paths only the last micro-batch meets the collectives, which carry the accumulated gradient and stats."""
+        dbs = list(dbs)
+        if not dbs:
+            raise ValueError("Trainer.step_many: needs at least one micro-batch (None = an empty one)")
+        live = [db for db in dbs if db is not None]
+        if len(live) <= 1:
+            return self.step(live[0] if live else None)
+        if self._raw is not None:
+            raise RuntimeError("Trainer.step_many inside Trainer.averaged(): the model holds the averaged weights")
+        self._step_accum(live)
+        if self.ema is not None:
+            self._ema_update()
+
+    def _step_accum(self, live):
+        """:meth:`step_many` with two or more non-empty micro-batches: K - 1 passes that only add to ``model.gbuf`` and to the
+        stats pair (fira_train_accum_micro / fira_accum_stats, no collective), then the last one on the schedule :meth:`_step`
+        runs its only one on."""
+        m = self.model
+        dp = self.reducer is not None and self.reducer.world > 1
+        zero_dp = self.zero is not None and self.zero.world > 1
+        self._rows_check_hyper()
+        sched = self._sched_struct()
+        b1, b2 = self.betas
+        step = self.t + 1
+        one_call = self.fused_step and self.reducer is None and self.zero is None
+        fused_dp = dp and self.fused_dp and self.zero is None
+        rows = None
+        if self.row_step is not None and (one_call or fused_dp):
+            rows = (self.m, self.v, self._rate_of(step), step, b1, b2, self.eps, self.row_step)
+        for k, db in enumerate(live[:-1]):
+            if one_call or fused_dp:
+                loss_sum, n_tok = m.train_accum_micro(db, zero_grad=(k == 0), rows=rows, sched=sched)
+            else:
+                loss_sum, n_tok = m.train_fwd_bwd(db, zero_grad=(k == 0))
+            ops.accum_stats(loss_sum, n_tok, self.stats, self.n_tok_total, k == 0)
+        db = live[-1]
+        self._acc_last = True
+        if one_call:
+            self.t += 1
+            clip = None if self.clip is None else (self.clip, self.clip_state, self.clip_scratch)
+            m.train_accum_last(db, self.m, self.v, self._rate(), self.t, self.stats, self.n_tok_total, beta1=b1, beta2=b2,
+                               eps=self.eps, row_step=self.row_step, clip=clip, sched=sched)
+            self._rows_dirty = self.row_step is not None
+            return
+        if fused_dp:
+            loss_sum, n_tok = m.train_step_begin(db, self.mid_event, rows=rows, sched=sched, zero_grad=False)
+        else:
+            loss_sum, n_tok = m.train_fwd_bwd(db, zero_grad=False, mid_event=self.mid_event)
+            if zero_dp or not dp:                                # (all-reduce data parallel: the reducer adds it on its stream)
+                ops.accum_stats(loss_sum, n_tok, self.stats, self.n_tok_total, False)
+        self._apply(loss_sum, n_tok, dp, fused_dp, acc=True)
 
     def _ema_update(self):
         """``self.ema`` toward the parameters as they stand after step ``self.t``, if that step is on the cadence.  One launch on
@@ -165,6 +230,7 @@ class Trainer:
         m = self.model
         dp = self.reducer is not None and self.reducer.world > 1
         fused_dp = False
+        self._acc_last = False
         # once per step, before t advances -- also on a rank whose shard is empty: a sync that a changed hyper-parameter forces
         # brings the rows up to the LAST completed step
         self._rows_check_hyper()
@@ -191,16 +257,28 @@ class Trainer:
             loss_sum, n_tok = m.train_step_begin(db, self.mid_event, rows=rows, sched=sched)
         else:
             loss_sum, n_tok = m.train_fwd_bwd(db, zero_grad=True, mid_event=self.mid_event)
+        self._apply(loss_sum, n_tok, dp, fused_dp)
+
+    def _apply(self, loss_sum, n_tok, dp: bool, fused_dp: bool, acc: bool = False):
+        """The collectives and the update behind a backward pass that left the (rank's) loss-sum gradient in ``model.gbuf``.
+        ``acc`` (:meth:`step_many`): ``loss_sum`` / ``n_tok`` are the LAST micro-batch's and ``self.stats`` /
+        ``self.n_tok_total`` hold the pair accumulated over the ones before it -- every micro-batch's on the paths whose last
+        one ran through ``train_fwd_bwd`` (ZeRO-1, one device without the one-call step)."""
+        m = self.model
         b1, b2 = self.betas
+        sched = self._sched_struct()
         if self.zero is not None and self.zero.world > 1:
-            self._step_zero1(loss_sum, n_tok)
+            self._step_zero1(loss_sum, n_tok, packed=acc)
             return
         if dp:
             red, split, live = self.reducer, m.layout.split, m.layout.live
             # stats pair + head/decoder bucket on the communication stream behind the mid-backward event (beside the encoder's
             # backward pass).  One launch packs {loss_sum, float(n_tok)} (exact below 2^24 tokens); the update kernels form
             # 1 / max(count, 1) from the all-reduced pair themselves: no torch arithmetic between the collective and Adam
-            ev = red.reduce_early(m.gbuf, self.stats, self.mid_event, pack=lambda: ops.pack_stats(loss_sum, n_tok, self.stats))
+            # (accumulating: the same launch slot adds the last micro-batch to the pair of the earlier ones instead)
+            pack = (lambda: ops.accum_stats(loss_sum, n_tok, self.stats, self.n_tok_total, False)) if acc else \
+                (lambda: ops.pack_stats(loss_sum, n_tok, self.stats))
+            ev = red.reduce_early(m.gbuf, self.stats, self.mid_event, pack=pack)
             self.t += 1
             lr = self._rate()
             count = self.stats[1:2]
@@ -242,6 +320,16 @@ class Trainer:
         # overlaps; profiles/r2_probes.md.)
         n = m.layout.live
         lr = self._rate()
+        if acc:
+            count = self.stats[1:2]                              # (every micro-batch is in the pair: _step_accum)
+            if self.clip is not None:
+                ops.grad_sqsum(m.gbuf[:n], self.clip_state, 0, self.clip_scratch)
+                ops.clip_finish(self.clip_state, 1, self.clip, count=count)
+                ops.adam_step_clip(m.flat.data[:n], m.gbuf[:n], self.m[:n], self.v[:n], lr, self.t, self.clip_state,
+                                   count=count, beta1=b1, beta2=b2, eps=self.eps)
+                return
+            ops.adam_step_count(m.flat.data[:n], m.gbuf[:n], self.m[:n], self.v[:n], lr, self.t, count, b1, b2, self.eps)
+            return
         if self.clip is not None:
             ops.grad_sqsum(m.gbuf[:n], self.clip_state, 0, self.clip_scratch)
             ops.clip_finish(self.clip_state, 1, self.clip, n_tok=n_tok)
@@ -251,16 +339,18 @@ class Trainer:
         ops.adam_step_mb(m.flat.data[:n], m.gbuf[:n], None, self.m[:n], self.v[:n], lr, self.t, n_tok, None, b1, b2,
                          self.eps)
 
-    def _step_zero1(self, loss_sum, n_tok):
+    def _step_zero1(self, loss_sum, n_tok, packed: bool = False):
         """reduce-scatter -> Adam on the owned shard -> all-gather, per readiness bucket, on a side stream: the head+decoder
-        bucket's reduce-scatter starts at the mid-backward event, beside the encoder's backward pass."""
+        bucket's reduce-scatter starts at the mid-backward event, beside the encoder's backward pass.  ``packed``:
+        ``self.stats`` already holds this rank's pair (accumulated over the step's micro-batches)."""
         m, z, zs = self.model, self.zero, self.zstream
         b1, b2 = self.betas
         main = torch.cuda.current_stream()
         zs.wait_event(self.mid_event)
         with torch.cuda.stream(zs):
             z.reduce_scatter(0, m.gbuf, self.g_sh[0])
-        ops.pack_stats(loss_sum, n_tok, self.stats)           # {loss_sum, float(n_tok)}: exact below 2^24 tokens
+        if not packed:
+            ops.pack_stats(loss_sum, n_tok, self.stats)       # {loss_sum, float(n_tok)}: exact below 2^24 tokens
         torch.distributed.all_reduce(self.stats, op=torch.distributed.ReduceOp.SUM, group=z.group)
         self.end_event.record(main)                            # backward pass done, global token count known
         self.t += 1
@@ -373,8 +463,8 @@ class Trainer:
 
     def last_loss(self) -> float:
         """Mean token loss of the last (global) batch; synchronises."""
-        if self.reducer is not None and self.reducer.world > 1:
-            s = self.stats.tolist()
+        if (self.reducer is not None and self.reducer.world > 1) or self._acc_last:
+            s = self.stats.tolist()                              # (all-reduced, or accumulated over a step's micro-batches)
         else:
             s = [float(self.model.loss_sum.item()), float(self.model.n_tok.item())]
         return s[0] / max(s[1], 1.0)

@@ -729,6 +729,46 @@ int fira_train_step_clip(void* stream, const fira_dims* d, const fira_batch* bat
                          int32_t* n_tok, const fira_adam_opts* adam, int32_t* row_step /* may be NULL */, float max_norm,
                          fira_clip_state* state, void* scratch);
 
+/* Gradient accumulation: ONE optimizer step over K micro-batches (additive, the ABI version is unchanged).  Every model-level
+ * call leaves the gradient of its batch's loss SUM in grads (+= unless opts->zero_grads) and the update kernels form
+ * 1 / max(count, 1) themselves, so the sum of the K gradients with the sum of the K token counts IS the step of the big batch:
+ * no per-micro-batch weight exists.
+ *   fira_accum_stats        stats[0] = (first ? 0 : stats[0]) + *loss_sum ;  total = (first ? 0 : *n_tok_total) + *n_tok ;
+ *                           *n_tok_total = total ;  stats[1] = (float) total.  One lane, plain stores, no atomic: the caller's
+ *                           stream orders the K calls.  The layout is fira_pack_stats': what takes count = stats + 1 takes this.
+ *                           The count is exact as a float below 2^24 tokens (above, (float) total is the int32 rounded to nearest
+ *                           even once, never a sum of rounded floats); the int32 total is exact always (below 2^31).  The loss
+ *                           sum is a chain of fp32 additions in call order.  first != 0 ignores what the buffers hold.
+ *   fira_train_accum_micro  forward + backward of one micro-batch that is NOT the last: fira_train_fwd_bwd, with the word-table
+ *                           rows the row-sparse Adam still owes read as fira_train_step_begin_rows reads them (adam, row_step:
+ *                           the values of the step being accumulated, adam->step = its number; both NULL = tables up to date).
+ *                           grads += (opts->zero_grads = 1 on the first micro-batch only), loss_sum / n_tok overwritten; NOTHING is
+ *                           updated, row_step included.  The caller follows it with fira_accum_stats.
+ *   fira_train_accum_last   the last micro-batch, run as fira_train_step / _rows (row_step given) / _clip (clip_state given) run
+ *                           theirs: behind its loss the call itself adds (*loss_sum, *n_tok) to stats / n_tok_total as
+ *                           fira_accum_stats(first = 0) does -- the update is enqueued by the same call, so no caller could --
+ *                           and every update (the head + decoder slice beside the last weight gradients, the rows launch, the
+ *                           rest behind the join; clipped: everything behind the join) is normalised by
+ *                           1 / max(stats[1], 1), the norm of a clipped step included.  With K = 1 use the plain entries.
+ * Why micro-batches 2..K need no cleared gradient although fira_train_step_rows "needs opts->zero_grads = 1": the rows update
+ * takes "gradient row all zero" for "row untouched", so the tables' gradient must hold nothing but THIS step's sums -- a stale
+ * row left by an earlier step would be applied again.  Cleared on the first micro-batch, the accumulated table shows as
+ * non-zero rows exactly the UNION of the micro-batches' touched rows (the argument of the all-reduced gradient in data
+ * parallel).  A row whose contributions cancel to an all-zero row is taken for untouched and gets its zero-gradient update
+ * later -- the same bits, since that is what a dense Adam would apply.  The lazy reads of micro-batches 2..K see rows at
+ * step - 1, as the first does: nothing is updated between them.  Data parallel: K - 1 x fira_train_accum_micro, then
+ * fira_train_step_begin(_rows) with opts->zero_grads = 0 and the collectives as ever, on the accumulated stats pair.          */
+int fira_accum_stats(void* stream, const float* loss_sum, const int32_t* n_tok, float* stats /* [2] */,
+                     int32_t* n_tok_total, int first);
+int fira_train_accum_micro(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
+                           void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
+                           int32_t* n_tok, const fira_adam_opts* adam /* may be NULL */, int32_t* row_step /* may be NULL */);
+int fira_train_accum_last(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads,
+                          void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
+                          int32_t* n_tok, const fira_adam_opts* adam, int32_t* row_step /* may be NULL */,
+                          float* stats /* [2] */, int32_t* n_tok_total, float max_norm /* read with clip_state only */,
+                          fira_clip_state* clip_state /* NULL: not clipped */, void* clip_scratch);
+
 /* (v8) bf16 wire format of a gradient bucket (BASELINE configs[2]: 55.6 MB instead of 111.2 MB per step on xGMI):
  * out[i] = bf16(in[i]) (round to nearest even) / out[i] = float(in[i]).  n % 4 == 0, 16-byte aligned buffers. */
 int fira_f32_to_bf16(void* stream, int64_t n, const float* in, uint16_t* out);

@@ -156,8 +156,14 @@ def parse_args(argv):
     ap.add_argument("--ema-every", type=int, default=None, metavar="K", help="with --ema-decay: update the average every K-th "
                     "step by the weight 1 - D^K (default 32, the cadence at which the row-sparse Adam has just written every "
                     "row; 1 = the per-step average)")
+    ap.add_argument("--accum-steps", type=int, default=None, metavar="K", help="train: gradient accumulation -- every "
+                    "optimisation step runs each rank's shard of the GLOBAL --batch-size as K micro-batches of ceil(shard / K) "
+                    "commits (1 <= K <= 64) and updates once, normalised by their total token count: the step of the whole "
+                    "batch in the memory of one micro-batch.  --max-steps, --warmup-steps, --lr-decay-steps and --ema-every "
+                    "count optimisation steps; every --loss-log line then carries micro = K.  Default: off (one pass per step)")
     a = ap.parse_args(argv)
     try:
+        check_accum_args(a)
         check_clip_args(a)
         check_ema_args(a)
         check_lr_schedule_args(a)
@@ -175,6 +181,41 @@ def parse_args(argv):
 
 RERANK_KEYS = ("logp_word", "mean_logp_word", "mbr_bleu")
 LR_SCHEDULES = ("constant", "inv-sqrt", "cosine", "linear")
+
+
+def check_accum_args(a):
+    """Validates --accum-steps (no GPU, no DataSet needed); raises ValueError on a conflict or an out-of-range value."""
+    if a.accum_steps is None:
+        return a
+    if a.stage != "train":
+        raise ValueError("--accum-steps only applies to the train stage")
+    from fira_icse_amd import ops
+    try:
+        ops.accum_check(a.accum_steps)
+    except ValueError as e:
+        raise ValueError("--accum-steps: %s" % e)
+    return a
+
+
+def micro_batches(mine, k):
+    """A rank's shard ``mine`` (a list of train-split positions) of one global batch as the K micro-batches of --accum-steps:
+    ceil(len / K) positions each, in order; a short shard leaves the last ones smaller or empty -- always K lists."""
+    from fira_icse_amd import ops
+    return [list(mine[lo:hi]) for lo, hi in ops.accum_split(0, len(mine), k)]
+
+
+def loss_log_record(epoch, batch, gidx, loss, micro=None, grad=None, lr=None):
+    """One --loss-log line (a dict): the positions of the whole global batch and its mean token loss; ``grad`` =
+    ``(grad_norm, clip_coef)`` with --clip-grad-norm, ``lr`` with --lr-schedule, ``micro`` = K with --accum-steps (the loss is
+    then the one accumulated over the K micro-batches).  Keys a run did not ask for are absent."""
+    rec = {"epoch": epoch, "batch": batch, "index": [int(i) for i in gidx], "loss": loss}
+    if grad is not None:
+        rec["grad_norm"], rec["clip_coef"] = grad
+    if lr is not None:
+        rec["lr"] = lr
+    if micro is not None:
+        rec["micro"] = int(micro)
+    return rec
 
 
 def check_clip_args(a):
@@ -633,11 +674,12 @@ class Run:
             # a run with --ema-decay wrote the AVERAGED weights to best_model.pt; training continues from the raw ones
             self.model.flat.data.copy_(state["params"])
         n_batches = -(-len(store) // cfg.batch_size)
+        accum = getattr(a, "accum_steps", None)                    # None: the one-pass step; K is not optimizer state (a resume may change it)
         # (no --lr-schedule: no schedule object, the constant-rate path; a resumed state then brings its own, if it has one)
         schedule = lr_schedule_from_args(a, a.max_steps if a.max_steps else cfg.epoches * n_batches,
                                          int(state["t"]) if state is not None else 0)
         trainer = Trainer(self.model, lr=cfg.lr, distributed=self.world > 1, zero1=a.zero1, grad_wire=wire,
-                          clip_grad_norm=a.clip_grad_norm, lr_schedule=schedule,
+                          clip_grad_norm=a.clip_grad_norm, lr_schedule=schedule, accum_steps=accum,
                           **({} if a.ema_decay is None else {"ema_decay": a.ema_decay, "ema_every": a.ema_every}))
         # with --ema-decay the dev passes and every best_model.pt are taken on the averaged weights
         averaged = contextlib.nullcontext if a.ema_decay is None else trainer.averaged
@@ -653,6 +695,8 @@ class Run:
             total_data, t0 = 0, time.time()
             def prepare(gidx):                                     # worker thread: collate + H2D of this rank's shard
                 mine = shard_indices(gidx, self.rank, self.world)   # DataParallel.scatter's contiguous chunks
+                if accum is not None:                              # --accum-steps: K micro-batches, empty ones as None
+                    return gidx, [self.device_batch(store, mb) if mb else None for mb in micro_batches(mine, accum)]
                 return gidx, (self.device_batch(store, mine) if mine else None)
 
             batches = prefetch(data.iterate_batches(len(store), cfg.batch_size, shuffle=True), prepare, depth=2,
@@ -676,15 +720,16 @@ class Run:
                                 with open(self.out("dev_output"), "w") as f:
                                     f.write(output_str)
                     self.model.train(not a.no_dropout)
-                trainer.step(db)                     # db None (empty shard of a short tail batch): still joins the collectives
+                if accum is not None:
+                    trainer.step_many(db)            # one update over this rank's K micro-batches (all None: as step(None))
+                else:
+                    trainer.step(db)                 # db None (empty shard of a short tail batch): still joins the collectives
                 total_data += len(gidx)
                 steps += 1
                 if a.loss_log and self.rank == 0:
-                    rec = {"epoch": epoch, "batch": idx_b, "index": [int(i) for i in gidx], "loss": trainer.last_loss()}
-                    if a.clip_grad_norm is not None:
-                        rec["grad_norm"], rec["clip_coef"] = trainer.last_grad_norm()[:2]
-                    if scheduled:
-                        rec["lr"] = trainer.last_lr()
+                    rec = loss_log_record(epoch, idx_b, gidx, trainer.last_loss(), micro=accum,
+                                          grad=trainer.last_grad_norm()[:2] if a.clip_grad_norm is not None else None,
+                                          lr=trainer.last_lr() if scheduled else None)
                     with open(a.loss_log, "a") as f:
                         f.write(json.dumps(rec) + "\n")
                 if idx_b % 10 == 0 and self.rank == 0:
