@@ -245,7 +245,8 @@ static inline bool graphs_dense(const fira_batch* b) {
 // The mode every launch helper below depends on, owned by the call that runs them: a member of the call's Ctx (a step pending
 // between fira_train_step_begin and _end keeps its own in the copied Ctx), a local of the op-level entries and the decode step.
 // What stays thread-local in this file is per-thread resource or ABI state, not per-call mode: side() (the library's streams and
-// event pool), wait_probe() and g_pending; so are the queue builders inside gemm_f32.hip / gemm_bf16.hip / gemm_wgrad_panel.hip.
+// event pool), wait_probe() and g_pending (the step between the two calls of the data-parallel ABI).  Outside it: the queue builders
+// and the panel scratch of gemm_f32.hip / gemm_bf16.hip / gemm_wgrad_panel.hip, the error text and the profiler's decoder tag (layout.cpp).
 struct Call {
     // Compute dtype (fira_train_opts.dtype / the dtype argument of fira_forward_dev and the op-level entries): 0 = fp32 MFMA
     // (the reference's arithmetic), 1 = bf16 MFMA with fp32 accumulation and fp32 storage (BASELINE configs[2]).  Only the
@@ -481,6 +482,7 @@ struct WaitProbe {
         fprintf(stderr, "  | total %.1f\n", tot);
         calls = 0;
     }
+    void tick() { if (enabled() && ++calls == 20) report(); }      // the end of a training call: every 20th reports
 };
 static WaitProbe& wait_probe() { static thread_local WaitProbe w; return w; }
 static int stream_wait_probed(hipStream_t main_s, hipEvent_t e, int line) {
@@ -674,11 +676,48 @@ static inline int attn_bf16(const Call& call) { return call.dtype == 1; }
 enum Site { SITE_GATE = 0, SITE_COMB_OUT = 1, SITE_GCN = 2, SITE_SELF = 3, SITE_CROSS = 4, SITE_FFN = 5 };
 static inline uint32_t site(int layer, int kind) { return (uint32_t)(layer * 8 + kind + 1); }
 
-struct ClipStep {
-    const fira_adam_opts* adam;
-    float max_norm;
-    fira_clip_state* state;
-    void* scratch;
+// ---- the form of a training call, ONE value: built by the public entry, validated by check_step, dispatched by update_early /
+// update_close (the entries' forms: DESIGN.md 6s).  Held by value in Ctx: a pending step owns its copy, nothing points at an entry's frame.
+// An entry's optimizer values, copied (the schedule folded into `lr`: ad.sched is nulled, ad.lr / ad.sched are not read), with the
+// row-sparse Adam's stamps (round 6, copyhead.hip): rows [2 * vocab] = the step up to which each row of the two word tables is current
+struct AdamVals {
+    bool given = false;
+    fira_adam_opts ad{};
+    AdamLr lr;
+    int32_t* rows = nullptr;
+    AdamVals(const fira_adam_opts* a = nullptr, int32_t* row_step = nullptr) : given(a != nullptr), rows(row_step) {
+        if (a) { ad = *a; lr = adam_lr(*a); ad.sched = nullptr; }
+    }
+};
+// what an update divides by: the call's own token counter unless a count (a device float: the accumulated count of
+// fira_train_accum_last, the all-reduced count of a data-parallel step) is given
+struct Norm {
+    const int32_t* n_tok = nullptr;
+    const float* count = nullptr;
+    static Norm of(const int32_t* own, const float* given) { Norm n; n.n_tok = given ? nullptr : own; n.count = given; return n; }
+};
+struct Step {
+    // -- lazy rows (forward side): the forward gathers replay, up to step - 1, the updates the word-table rows this batch reads
+    // still owe.  lazy.rows == nullptr: off.
+    AdamVals lazy;
+    // -- update (backward side; what each kind launches and where: update_early / update_close).  Own: the one-device step
+    // (round 5).  DpEarly: second half of a data-parallel step (round 6) -- the caller all-reduces the gradients of [0, split)
+    // between the two calls, ev_early is its event behind that collective; [split, live) is the caller's.  Clipped: by the global
+    // gradient norm (gradnorm.hip) -- every update depends on every gradient, so all of it follows the final join.
+    enum Kind { None, Own, DpEarly, Clipped } kind = None;
+    AdamVals adam;                   // (adam.rows: the two word tables are updated on the rows whose gradient row is not zero)
+    float* Pw = nullptr;             // the parameters, writable (nothing reads [0, split) after the decoder's backward pass)
+    bool need_rows = false;          // a `_rows` entry: the optimizer's values and row_step are part of its contract
+    hipEvent_t ev_early = nullptr;
+    float max_norm = 0.f;            // Clipped: the threshold, the state and the scratch of gradnorm.hip
+    fira_clip_state* clip_state = nullptr; void* clip_scratch = nullptr;
+    Norm norm;
+    // -- phase: the whole call; its first half, up to where the gradients of [0, split) are final (mid_event, optional in a whole
+    // call); or a whole call that is the last micro-batch of an accumulated step and adds its scalars to stats / total
+    enum Phase { Whole, FirstHalf, AccumLast } phase = Whole;
+    hipEvent_t mid_event = nullptr;
+    float* stats = nullptr;          // the running {loss_sum, float(n_tok)} pair ...
+    int32_t* total = nullptr;        // ... and the exact token total
 };
 struct Ctx {
     hipStream_t s;
@@ -715,34 +754,9 @@ struct Ctx {
     int kv_waited = 0;
     hipEvent_t ev_src = nullptr;
     hipEvent_t ev_zero = nullptr;   // the backward pass's zero-initialised buffers were cleared on the auxiliary stream
-    // fira_train_step (round 5): the optimizer update is part of the call.  Adam is element-wise, so the head + decoder slice
-    // [0, split) is updated as soon as the caller's stream has finished the encoder's backward chain -- while the weight-gradient
-    // and auxiliary streams still work on the encoder's last gradients -- and [split, live) after the join.  Pw = the parameters,
-    // writable (nothing reads [0, split) after the decoder's backward pass; see backward()).
-    const fira_adam_opts* adam = nullptr;
-    float* Pw = nullptr;
-    // (round 6) row-sparse Adam of the two vocabulary-sized embedding tables (fira_train_step_rows; copyhead.hip:
-    // adam_rows_kernel): row_step [2 * vocab] = the step up to which each row of decoder.embedding / encoder.embedding is
-    // current.  The rows this batch gathers are brought up to step - 1 ahead of the forward pass; the update itself runs on
-    // the rows whose gradient row is not zero.
-    bool dp_begin = false;           // fira_train_step_begin(_rows): the first half of a data-parallel step (see backward_decoder: dec_every)
     bool wout_planes = false;        // (round 6) WoutTX holds this step's planes: the vocabulary data gradient runs as dgrad_x3_splitk
     bool kv_planes = false;          // (round 6) WkvTX holds this step's planes: the d-memory products run as linear_x3_kacc
-    int32_t* row_step = nullptr;
-    fira_adam_opts rows_ad{};        // beta / eps / step / moments the lazy reads use (a COPY: a begun data-parallel step outlives the call)
-    AdamLr rows_lr;                  // ... and the rate of every step they replay (rows_ad.lr / rows_ad.sched are not read)
-    // data-parallel form of the same (fira_train_step_begin / _end, round 6): the gradients of [0, split) are all-reduced by the
-    // caller between the two calls -- Adam of [0, split) waits for ev_early (the caller's event behind that collective) instead of
-    // the local weight-gradient mark, scales by the all-reduced token count `count` (a device float), and [split, live) is the
-    // caller's (its bucket is reduced after the call)
-    bool adam_a_only = false;
-    hipEvent_t ev_early = nullptr;
-    const float* count = nullptr;
-    // (gradient accumulation, fira_train_accum_last: `count` = the accumulated token count normalises the one-device update too)
-    // fira_train_step_clip: the update clipped by the global gradient norm (gradnorm.hip).  Every update depends on every
-    // gradient, so nothing is updated ahead of the final join (c.adam stays null: no early Adam); the sum of squares of
-    // [0, split) runs on the auxiliary stream where mid_event would fire, beside the encoder's backward pass.
-    const ClipStep* clip = nullptr;
+    Step step;                       // what this call does with its rows and its gradients
     // bf16 mode (round 5): the refresh of the bf16 weight shadows (one 46 us launch) runs on the auxiliary stream behind the GCN
     // fold instead of at the head of the caller's stream -- with the fused Combination / GCN kernels (which round the fp32
     // weights themselves) the first reader of a shadow is the decoder (and the auxiliary stream's own K|V projections)
@@ -847,12 +861,18 @@ static inline bool gcn_x3_on(const Call& call, int nl) { return call.gcn_fused()
 // bf16 mode): two launches instead of one fp32 / bf16 GEMM launch per layer (+0.4 % at fp32 batch 64, +1.0 % in bf16)
 static inline bool kv_x3_on(int nl) { return nl * 2 <= 24; }
 
+// the lazy view of word table `table` (0 decoder.embedding, 1 encoder.embedding): empty unless the call reads lagging rows lazily
+static AdamRowsView lazy_view(const Ctx& c, int table) {
+    const AdamVals& lz = c.step.lazy;
+    if (!lz.rows) return AdamRowsView();
+    return adam_rows_view(adam_rows_tables(*c.L, nullptr, lz.ad, lz.rows), table, lz.lr, lz.ad.beta1, lz.ad.beta2, lz.ad.eps, lz.ad.step - 1);
+}
 // the target-word rows this batch's decoder gathers, brought up to step - 1 in memory (the dense-target-row path only: the
 // compact paths read lazily, adam_rows_load)
 static int adam_rows_prefetch(Ctx& c, hipStream_t st) {
     const fira_batch& bt = *c.bt;
     const Plan& p = *c.pl;
-    const fira_adam_opts& ad = c.rows_ad;
+    const fira_adam_opts& ad = c.step.lazy.ad;
     AdamRowsLists ls{};
     auto add = [&](const int32_t* ids, int n, int table) {
         if (!ids || n <= 0) return;
@@ -861,7 +881,7 @@ static int adam_rows_prefetch(Ctx& c, hipStream_t st) {
         ls.end[k] = (k ? ls.end[k - 1] : 0) + n;
     };
     add(bt.tar, p.B * p.T, 0);
-    return adam_rows_catchup(st, adam_rows_tables(*c.L, const_cast<float*>(c.P), ad, c.row_step), &ls, c.rows_lr, ad.beta1, ad.beta2, ad.eps,
+    return adam_rows_catchup(st, adam_rows_tables(*c.L, const_cast<float*>(c.P), ad, c.step.lazy.rows), &ls, c.step.lazy.lr, ad.beta1, ad.beta2, ad.eps,
                              ad.step - 1);
 }
 
@@ -970,10 +990,7 @@ static int encoder_forward(Ctx& c, bool defer_memory_proj) {
     // layer 0's code rows are also stored compactly (Xc of the first Combination): no gather launch on the chain
     // (row-sparse Adam: a word row the last steps did not touch is read with the zero-gradient updates it still owes applied in
     //  registers -- adam_rows.h; the view is empty otherwise)
-    AdamRowsView vw_emb;
-    if (c.row_step)
-        vw_emb = adam_rows_view(adam_rows_tables(L, nullptr, c.rows_ad, c.row_step), 1, c.rows_lr, c.rows_ad.beta1, c.rows_ad.beta2,
-                                c.rows_ad.eps, c.rows_ad.step - 1);
+    const AdamRowsView vw_emb = lazy_view(c, 1);
     TRY(node_features(s, Nc, bt.node_rows, p.N, p.L, p.S, bt.sou, bt.sub_token, bt.ast_change, c.P + L.emb, c.P + L.ast_emb,
                       p.pos_code, p.X[0], p.code_slot, p.enc[0].Xc, &vw_emb));
     // value projection of the 4-row mark table for all layers at once: vtab_all [4, nl*256]
@@ -1086,13 +1103,10 @@ static int decoder_forward(Ctx& c) {
     const Layout& L = *c.L;
     const int D = FIRA_D, H = L.d.n_head, Sm = p.L + p.S;
     if (c.row_bt) {
-        AdamRowsView vw;                          // (see encoder_forward: the target-word table under a row-sparse Adam)
-        if (c.row_step)
-            vw = adam_rows_view(adam_rows_tables(L, nullptr, c.rows_ad, c.row_step), 0, c.rows_lr, c.rows_ad.beta1, c.rows_ad.beta2,
-                                c.rows_ad.eps, c.rows_ad.step - 1);
+        const AdamRowsView vw = lazy_view(c, 0);  // (see encoder_forward: the target-word table under a row-sparse Adam)
         TRY(embed_rows_fwd(c.s, c.Td, p.T, c.row_bt, c.bt->tar, c.P + L.dec_emb, p.pos_tar, p.x0, &vw));
     } else {
-        if (c.row_step) TRY(adam_rows_prefetch(c, c.s));      // dense target rows: the batch's rows brought up to date first
+        if (c.step.lazy.rows) TRY(adam_rows_prefetch(c, c.s));      // dense target rows: the batch's rows brought up to date first
         TRY(embed_gather_fwd(c.s, p.B, p.T, c.bt->tar, c.P + L.dec_emb, p.pos_tar, p.x0, p.T, 0));
     }
     ProfDecoderTag prof_tag;                   // the M = B*30 products below are reported as their own class
@@ -1259,8 +1273,9 @@ struct BwdMid {
     hipEvent_t ev_groupA = nullptr;    // every gradient of [0, split) is final (weight-gradient stream)
 };
 
-static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_event, BwdMid& mid) {
+static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
     Plan& p = *c.pl;
+    const Step& st = c.step;
     const Layout& L = *c.L;
     hipStream_t s = c.s;
     const int D = FIRA_D, H = L.d.n_head, KV = p.nl * 2 * D, Sm = p.L + p.S;
@@ -1486,32 +1501,110 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_e
     // vocabulary / copy / decoder weight gradients, the decoder embedding, the stacked K|V weight, the deferred column sums;
     // the auxiliary stream writes data gradients only)
     hipEvent_t& ev_groupA = mid.ev_groupA;
-    if (c.adam && side().stream && side().enabled) {
+    if ((st.kind == Step::Own || st.kind == Step::DpEarly) && side().stream && side().enabled) {
         ev_groupA = side().ev();
         if (hipEventRecord(ev_groupA, side().stream) != hipSuccess) return set_err("group-A mark failed");
     }
-    if (mid_event || c.clip) {               // gradients of [0, split) are final from here on
+    if (st.mid_event || st.kind == Step::Clipped) {       // gradients of [0, split) are final from here on
         hipStream_t es = nullptr;
         TRY(group_a_final_stream(s, &es));
-        if (mid_event) {
-            hipError_t e = hipEventRecord(mid_event, es);
+        if (st.mid_event) {
+            hipError_t e = hipEventRecord(st.mid_event, es);
             if (e != hipSuccess) return set_err("hipEventRecord: %s", hipGetErrorString(e));
         }
         // clipped step: the sum of squares of [0, split) there, beside the encoder's backward pass; the caller's stream meets
         // it again at the auxiliary stream's tail mark ahead of the final join
-        if (c.clip) TRY(grad_sqsum(es, L.split, G, c.clip->state, 0, c.clip->scratch, nullptr));
+        if (st.kind == Step::Clipped) TRY(grad_sqsum(es, L.split, G, st.clip_state, 0, st.clip_scratch, nullptr));
     }
     return 0;
 }
 
-// the one-device step's dense update of [lo, hi): normalised by the call's own token counter or -- the last micro-batch of an
-// accumulated step (Ctx::count) -- by the accumulated count
-static int adam_own(Ctx& c, hipStream_t s, const fira_adam_opts& ad, int64_t lo, int64_t hi) {
-    const float lr = adam_lr(ad).at(ad.step);
-    if (c.count)
-        return adam_step(s, hi - lo, c.Pw + lo, c.G + lo, ad.m + lo, ad.v + lo, lr, ad.beta1, ad.beta2, ad.eps, ad.step, c.count, 1);
-    return adam_step_mb(s, hi - lo, c.Pw + lo, c.G + lo, nullptr, ad.m + lo, ad.v + lo, lr, ad.beta1, ad.beta2, ad.eps, ad.step, c.n_tok,
-                        nullptr);
+// the dense update of [lo, hi), by the step's normaliser (Own and DpEarly)
+static int adam_own(Ctx& c, int64_t lo, int64_t hi) {
+    const Step& st = c.step;
+    const fira_adam_opts& ad = st.adam.ad;
+    float *p = st.Pw + lo, *g = c.G + lo, *m = ad.m + lo, *v = ad.v + lo;
+    const float lr = st.adam.lr.at(ad.step);
+    if (st.norm.count) return adam_step(c.s, hi - lo, p, g, m, v, lr, ad.beta1, ad.beta2, ad.eps, ad.step, st.norm.count, 1);
+    return adam_step_mb(c.s, hi - lo, p, g, nullptr, m, v, lr, ad.beta1, ad.beta2, ad.eps, ad.step, st.norm.n_tok, nullptr);
+}
+// The update launches of the early point: behind the embedding backward launches on the caller's stream, ahead of ev_tail and the
+// final join.  *adam_b0 (preset to split): the first parameter the closing launch of an Own step still has to update.
+static int update_early(Ctx& c, hipEvent_t ev_groupA, int64_t* adam_b0) {
+    const Step& st = c.step;
+    const Layout& L = *c.L;
+    const fira_adam_opts& ad = st.adam.ad;
+    // (row-sparse tables: decoder.embedding is the head of [0, split) -- layout.cpp -- and is left to the rows launch below)
+    const int64_t a0 = st.adam.rows ? L.dec_emb + (int64_t)L.d.vocab * FIRA_D : 0;
+    switch (st.kind) {
+    case Step::None: case Step::Clipped: return 0;      // (Clipped: nothing ahead of the final join)
+    case Step::DpEarly:
+        // data parallel: the bucket's all-reduce (enqueued by the caller between the two calls) has passed ev_early; the
+        // normaliser is the all-reduced token count
+        if (st.ev_early) TRY(main_wait(c.s, st.ev_early, __LINE__));
+        TRY(adam_own(c, a0, L.split));
+        // (row-sparse tables, data parallel: decoder.embedding -- the head of this slice -- by the rows of the ALL-REDUCED
+        //  gradient that are not zero: the union of the ranks' touched rows, the same on every rank)
+        if (st.adam.rows)
+            TRY(adam_rows_step(c.s, adam_rows_tables(L, st.Pw, ad, st.adam.rows), c.G, st.adam.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+                               st.norm.n_tok, st.norm.count, 1));
+        return 0;
+    case Step::Own:
+        // INVARIANT this early update rests on (ADVICE r5; tests/test_model_gpu.py::test_one_call_step_equals_backward_then_adam
+        // compares with the two-call path in fp32 and bf16): behind the decoder's backward pass NOTHING, on any stream, reads a
+        // parameter of [0, mark_emb) -- the encoder's backward kernels read encoder weights of [mark_emb, live) and workspace
+        // copies (W21, WcT, the bf16 shadows), the weight-gradient stream reads activations only, the auxiliary stream's reads of
+        // wkv_all / ws precede ev_dmem, which the caller's stream has waited for -- and the gradients of [0, split) are final at
+        // ev_groupA, those of the two embedding tables when the two launches above have run.  A new kernel that breaks either
+        // half must move this update behind the final join.
+        // Adam on [0, split) (69 % of the live parameters) HERE: the caller's stream would otherwise stand waiting for the last
+        // grouped weight gradient / the unfold products / the deferred reductions of the other two streams (timeline: 30-60 us)
+        // and then run the whole update alone.  Nothing enqueued after the decoder's backward pass reads a parameter of
+        // [0, split): the encoder's backward kernels read encoder weights, the weight-gradient stream reads activations.
+        if (ev_groupA) TRY(main_wait(c.s, ev_groupA, __LINE__));
+        TRY(adam_own(c, a0, L.split));
+        // ... and the encoder's two embedding tables (the head of group B: layout.cpp), whose gradients the two launches above
+        // on this stream have just completed -- also ahead of the join (+0.4 % against behind it, profiles/r5_probes.md)
+        if (st.adam.rows) {
+            // both vocabulary-sized tables as ONE launch over the rows whose gradient row is not zero (the gradient rows are
+            // inspected: 2 x 25 MB read instead of 2 x 177 MB moved); the 71-row table joins the closing launch
+            TRY(adam_rows_step(c.s, adam_rows_tables(L, st.Pw, ad, st.adam.rows), c.G, st.adam.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+                               st.norm.n_tok, st.norm.count));
+            *adam_b0 = L.ast_emb;
+            return 0;
+        }
+        *adam_b0 = L.mark_emb;
+        return *adam_b0 > L.split ? adam_own(c, L.split, *adam_b0) : 0;
+    }
+}
+// The update launches of the closing point: behind gcn_bias_unfold_all, where every gradient of [0, live) is final
+static int update_close(Ctx& c, int64_t adam_b0) {
+    const Step& st = c.step;
+    const Layout& L = *c.L;
+    const fira_adam_opts& ad = st.adam.ad;
+    switch (st.kind) {
+    case Step::None: case Step::DpEarly: return 0;      // (DpEarly: [split, live) is the caller's)
+    case Step::Own: return adam_own(c, adam_b0, L.live);
+    case Step::Clipped: {
+        // (the auxiliary stream's sum over [0, split) precedes ev_tail): the sum over [split, live) with the closing step in its
+        // second launch, then the whole update -- the two word tables by rows when row_step is given, the rest as dense launches
+        // over the gaps between them (an accumulated step: norm and updates by the accumulated count)
+        const ClipClose fin{st.norm.n_tok, st.norm.count, st.max_norm, 2};
+        TRY(grad_sqsum(c.s, L.live - L.split, c.G + L.split, st.clip_state, 1, st.clip_scratch, &fin));
+        auto dense = [&](int64_t lo, int64_t hi) {
+            return adam_step_clip(c.s, hi - lo, st.Pw + lo, c.G + lo, ad.m + lo, ad.v + lo, st.adam.lr.at(ad.step), ad.beta1, ad.beta2, ad.eps,
+                                  ad.step, st.norm.n_tok, st.norm.count, st.clip_state);
+        };
+        if (!st.adam.rows) return dense(0, L.live);
+        const int64_t tab = (int64_t)L.d.vocab * FIRA_D;
+        TRY(adam_rows_step_clip(c.s, adam_rows_tables(L, st.Pw, ad, st.adam.rows), c.G, st.adam.lr, ad.beta1, ad.beta2, ad.eps, ad.step,
+                                st.norm.n_tok, st.norm.count, 3, st.clip_state));
+        const int64_t t0 = std::min(L.dec_emb, L.emb), t1 = std::max(L.dec_emb, L.emb);
+        TRY(dense(0, t0));
+        TRY(dense(t0 + tab, t1));
+        return dense(t1 + tab, L.live);
+    }
+    }
 }
 
 static int backward_encoder(Ctx& c, BwdMid& mid) {
@@ -1674,91 +1767,13 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         else
             TRY(embed_gather_bwd(s, p.B, p.A, bt.ast_change, G + L.ast_emb, p.H, p.N, p.L + p.S, 0));
     }
-    if (c.adam) {
-        // INVARIANT this early update rests on (ADVICE r5; tests/test_model_gpu.py::test_one_call_step_equals_backward_then_adam
-        // compares with the two-call path in fp32 and bf16): behind the decoder's backward pass NOTHING, on any stream, reads a
-        // parameter of [0, mark_emb) -- the encoder's backward kernels read encoder weights of [mark_emb, live) and workspace
-        // copies (W21, WcT, the bf16 shadows), the weight-gradient stream reads activations only, the auxiliary stream's reads of
-        // wkv_all / ws precede ev_dmem, which the caller's stream has waited for -- and the gradients of [0, split) are final at
-        // ev_groupA, those of the two embedding tables when the two launches above have run.  A new kernel that breaks either
-        // half must move this update behind the final join.
-        // Adam on [0, split) (69 % of the live parameters) HERE: the caller's stream would otherwise stand waiting for the last
-        // grouped weight gradient / the unfold products / the deferred reductions of the other two streams (timeline: 30-60 us)
-        // and then run the whole update alone.  Nothing enqueued after the decoder's backward pass reads a parameter of
-        // [0, split): the encoder's backward kernels read encoder weights, the weight-gradient stream reads activations.
-        const fira_adam_opts& ad = *c.adam;
-        if (c.adam_a_only) {
-            // data parallel: the bucket's all-reduce (enqueued by the caller between the two calls) has passed ev_early; the
-            // normaliser is the all-reduced token count
-            if (c.ev_early) TRY(main_wait(s, c.ev_early, __LINE__));
-            // (row-sparse tables, data parallel: decoder.embedding -- the head of this slice -- by the rows of the ALL-REDUCED
-            //  gradient that are not zero: the union of the ranks' touched rows, the same on every rank)
-            const int64_t a0 = c.row_step ? L.dec_emb + (int64_t)L.d.vocab * D : 0;
-            if (c.count) TRY(adam_step(s, L.split - a0, c.Pw + a0, G + a0, ad.m + a0, ad.v + a0, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps, ad.step, c.count, 1));
-            else TRY(adam_step_mb(s, L.split - a0, c.Pw + a0, G + a0, nullptr, ad.m + a0, ad.v + a0, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps, ad.step, c.n_tok, nullptr));
-            if (c.row_step)
-                TRY(adam_rows_step(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, adam_lr(ad), ad.beta1, ad.beta2, ad.eps, ad.step,
-                                   c.count ? nullptr : c.n_tok, c.count, 1));
-        } else {
-        if (ev_groupA) TRY(main_wait(s, ev_groupA, __LINE__));
-        // (row-sparse tables: decoder.embedding is the head of [0, split) -- layout.cpp -- and is left to the rows launch below)
-        const int64_t a0 = c.row_step ? L.dec_emb + (int64_t)L.d.vocab * D : 0;
-        TRY(adam_own(c, s, ad, a0, L.split));
-        }
-        // ... and the encoder's two embedding tables (the head of group B: layout.cpp), whose gradients the two launches above
-        // on this stream have just completed -- also ahead of the join (+0.4 % against behind it, profiles/r5_probes.md)
-        if (!c.adam_a_only) adam_b0 = L.mark_emb;
-        if (c.row_step && !c.adam_a_only) {
-            // both vocabulary-sized tables as ONE launch over the rows whose gradient row is not zero (the gradient rows are
-            // inspected: 2 x 25 MB read instead of 2 x 177 MB moved); the 71-row table joins the closing launch
-            TRY(adam_rows_step(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, adam_lr(ad), ad.beta1, ad.beta2, ad.eps, ad.step,
-                               c.count ? nullptr : c.n_tok, c.count));
-            adam_b0 = L.ast_emb;
-        } else
-        if (adam_b0 > L.split)
-        TRY(adam_own(c, s, ad, L.split, adam_b0));
-    }
+    TRY(update_early(c, ev_groupA, &adam_b0));
     if (ev_tail) TRY(main_wait(s, ev_tail, __LINE__));
     if (side().stream && side().enabled) TRY(side_join(s, __LINE__));        // every weight gradient is complete past this point
     // dc of every GCN layer is final (deferred reduction above) and so are the side stream's additions to dW2: back to the
     // reference's fc2.weight / fc1.bias gradients, one launch for all layers
     TRY(gcn_bias_unfold_all(s, unfold_tab));
-    if (c.adam && !c.adam_a_only) {
-        const fira_adam_opts& ad = *c.adam;
-        TRY(adam_own(c, s, ad, adam_b0, L.live));
-    }
-    if (c.clip) {
-        // every gradient of [0, live) is final here (and the auxiliary stream's sum over [0, split) precedes ev_tail): the sum
-        // over [split, live) with the closing step in its second launch, then the whole update -- the two word tables by rows
-        // when row_step is given, the rest as dense launches over the gaps between them
-        const ClipStep& cl = *c.clip;
-        const fira_adam_opts& ad = *cl.adam;
-        const int32_t* n_own = c.count ? nullptr : c.n_tok;      // (an accumulated step: norm and updates by the accumulated count)
-        const ClipClose fin{n_own, c.count, cl.max_norm, 2};
-        TRY(grad_sqsum(s, L.live - L.split, G + L.split, cl.state, 1, cl.scratch, &fin));
-        auto dense = [&](int64_t lo, int64_t hi) {
-            return adam_step_clip(s, hi - lo, c.Pw + lo, G + lo, ad.m + lo, ad.v + lo, adam_lr(ad).at(ad.step), ad.beta1, ad.beta2, ad.eps, ad.step,
-                                  n_own, c.count, cl.state);
-        };
-        if (c.row_step) {
-            const int64_t tab = (int64_t)L.d.vocab * D;
-            TRY(adam_rows_step_clip(s, adam_rows_tables(L, c.Pw, ad, c.row_step), G, adam_lr(ad), ad.beta1, ad.beta2, ad.eps, ad.step,
-                                    n_own, c.count, 3, cl.state));
-            const int64_t t0 = std::min(L.dec_emb, L.emb), t1 = std::max(L.dec_emb, L.emb);
-            TRY(dense(0, t0));
-            TRY(dense(t0 + tab, t1));
-            TRY(dense(t1 + tab, L.live));
-        } else {
-            TRY(dense(0, L.live));
-        }
-    }
-    return 0;
-}
-
-static int backward(Ctx& c, int R, const int32_t* rows, hipEvent_t mid_event) {
-    BwdMid mid;
-    TRY(backward_decoder(c, R, rows, mid_event, mid));
-    return backward_encoder(c, mid);
+    return update_close(c, adam_b0);
 }
 
 static int check_batch(const fira_batch* b) {
@@ -1838,17 +1853,33 @@ struct PendingStep {
 };
 static thread_local PendingStep g_pending;
 
-// gradient accumulation (fira_train_accum_micro / _last): which micro-batch of an optimizer step a call runs
-struct AccumStep {
-    bool last;               // false: forward + backward only (adam serves the lazy reads of lagging word-table rows)
-    float* stats;            // last: the running {loss_sum, float(n_tok)} pair ...
-    int32_t* total;          // ... and the exact token total the call adds its own scalars to
-};
+// Every argument check of the training entries on a call's form, once each, ahead of any launch; `who` = the public entry.
+// opts, loss_sum, n_tok: the call's own (nullptr in the second half of a two-call step, which takes none).
+static int check_step(const Step& st, const char* who, const fira_train_opts* opts, const float* loss_sum, const int32_t* n_tok) {
+    const bool updates = st.kind != Step::None;
+    const AdamVals& av = updates ? st.adam : st.lazy;        // (a call that updates nothing takes them for its lazy reads alone)
+    FIRA_REQUIRE(st.phase != Step::FirstHalf || st.mid_event, "%s: mid_event missing (the caller's collective waits for it)", who);
+    FIRA_REQUIRE((!updates || av.given) && (!av.given || (av.ad.m && av.ad.v)), "%s: Adam moments missing", who);
+    FIRA_REQUIRE(!av.given || av.ad.step >= 1, "%s: the Adam step counter starts at 1", who);
+    FIRA_REQUIRE(!updates || st.Pw, "%s: the update needs the parameter buffer", who);
+    if (av.lr.scheduled) TRY(fira_lr_schedule_check(&av.lr.sched));
+    FIRA_REQUIRE(!st.need_rows || (av.given && av.rows), "%s: adam / row_step missing", who);
+    FIRA_REQUIRE(updates || av.given == (av.rows != nullptr), "%s: adam and row_step are given together", who);
+    const bool clipped = st.kind == Step::Clipped, acc = st.phase == Step::AccumLast;
+    FIRA_REQUIRE(!clipped || st.max_norm > 0.f, "%s: max_norm must be > 0 (inf allowed)", who);
+    FIRA_REQUIRE(!clipped || (st.clip_state && st.clip_scratch && (uintptr_t)st.clip_scratch % 8 == 0), "%s: clip state / scratch missing", who);
+    // (an accumulated step's last micro-batch adds to the gradient its first one cleared; DpEarly: the first half's business)
+    FIRA_REQUIRE(!(st.adam.rows && !acc && (st.kind == Step::Own || clipped)) || (opts && opts->zero_grads),
+                 "%s: row_step needs opts.zero_grads (an all-zero gradient row = an untouched row)", who);
+    FIRA_REQUIRE(!acc || (st.stats && st.total), "%s: the accumulated stats pair / token total is missing", who);
+    FIRA_REQUIRE(!acc || ((const void*)st.stats != (const void*)loss_sum && (const void*)st.total != (const void*)n_tok),
+                 "%s: the totals must not alias the micro-batch's scalars", who);
+    return 0;
+}
 
-static int train_call(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
-                      void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
-                      int32_t* n_tok, void* mid_event, float* params_w, const fira_adam_opts* adam, bool begin_only = false,
-                      int32_t* row_step = nullptr, const ClipStep* clip = nullptr, const AccumStep* acc = nullptr) {
+static int train_call(const char* who, const Step& st, void* stream, const fira_dims* d, const fira_batch* batch, const float* params,
+                      float* grads, void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok) {
+    TRY(check_step(st, who, opts, loss_sum, n_tok));
     const Layout* L = get_layout(d);
     if (!L) return 1;
     TRY(check_batch(batch));
@@ -1893,20 +1924,10 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
     }
     c.loss_sum = loss_sum;
     c.n_tok = n_tok;
-    c.adam = adam;
-    c.Pw = params_w;
+    c.step = st;
+    if (L->d.d_model != FIRA_D) c.step.lazy.rows = nullptr;    // (the forward gathers read lagging rows lazily: adam_rows_load)
     const bool zero_g = opts && opts->zero_grads;
     if (!side_on() && zero_g) TRY(zero(c.s, grads, (size_t)L->live * sizeof(float)));
-    if (adam && row_step && L->d.d_model == FIRA_D) {        // (the forward gathers read lagging rows lazily: adam_rows_load)
-        c.row_step = row_step;
-        c.rows_ad = *adam;
-        c.rows_lr = adam_lr(*adam);
-        c.rows_ad.sched = nullptr;
-    }
-    c.dp_begin = begin_only;
-    if (begin_only) c.adam = nullptr;        // (fira_train_step_begin_rows: the optimizer's values serve the lazy reads only)
-    if (clip) { c.adam = nullptr; c.clip = clip; }      // (clipped step: the update follows the final join, see backward_encoder)
-    if (acc && !acc->last) c.adam = nullptr; // (a micro-batch ahead of the last: nothing is updated)
     TRY(encoder_forward(c, true));
     if (side_on()) {
         // the buffers the backward pass accumulates into are cleared on the auxiliary stream beside the forward pass (they
@@ -1923,18 +1944,15 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
     if (c.ev_shadow) TRY(main_wait(c.s, c.ev_shadow, __LINE__));      // the decoder's products read the bf16 shadows
     TRY(decoder_forward(c));
     TRY(head_forward(c, R, rows, loss_sum, n_tok, nullptr, 1));
-    if (acc && acc->last) {
-        // the step's scalars are final on the caller's stream: add them to the optimizer step's pair here, ahead of every update
-        // launch of this call (all of them are enqueued behind this point of the caller's stream)
-        TRY(accum_stats(c.s, loss_sum, n_tok, acc->stats, acc->total, 0));
-        c.count = acc->stats + 1;
-    }
-    if (begin_only) {
+    // (an accumulated step: the call's scalars are final on the caller's stream -- added to the optimizer step's pair here, ahead
+    //  of every update launch of this call, all of which are enqueued behind this point of the caller's stream)
+    if (st.phase == Step::AccumLast) TRY(accum_stats(c.s, loss_sum, n_tok, st.stats, st.total, 0));
+    if (st.phase == Step::FirstHalf) {
         // first half of a data-parallel step: up to the point where the gradients of [0, split) are final (mid_event)
         PendingStep& ps = g_pending;
         ps.active = false;
         ps.mid = BwdMid();
-        TRY(backward_decoder(c, R, rows, (hipEvent_t)mid_event, ps.mid));
+        TRY(backward_decoder(c, R, rows, ps.mid));
         ps.plan = p;
         ps.batch = *batch;
         ps.ctx = c;
@@ -1943,16 +1961,18 @@ static int train_call(void* stream, const fira_dims* d, const fira_batch* batch,
         ps.active = true;
         return 0;
     }
-    TRY(backward(c, R, rows, (hipEvent_t)mid_event));
-    if (wait_probe().enabled() && ++wait_probe().calls == 20) wait_probe().report();
+    BwdMid mid;
+    TRY(backward_decoder(c, R, rows, mid));
+    TRY(backward_encoder(c, mid));
+    wait_probe().tick();
     return 0;
 }
 
 int fira_train_fwd_bwd(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
                        void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
                        int32_t* n_tok, void* mid_event) {
-    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, mid_event, nullptr,
-                      nullptr);
+    Step st; st.mid_event = (hipEvent_t)mid_event;
+    return train_call("fira_train_fwd_bwd", st, stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok);
 }
 
 // ---- op-level entries named by SURVEY.md 8(b) that the model-level calls compose from smaller launches ------------------
@@ -2003,126 +2023,105 @@ int fira_head_topk(void* stream, int R, int V, int k, const float* x, const floa
     return row_topk(s, R, V, k, logits_ws, ldl, ids, vals);
 }
 
+// the one-call forms that update: Own, or Clipped where a clip state is given; count: see Norm
+static Step own_step(const fira_adam_opts* adam, float* params, int32_t* row_step, const int32_t* n_tok, const float* count,
+                     float max_norm = 0.f, fira_clip_state* clip_state = nullptr, void* clip_scratch = nullptr) {
+    Step st;
+    st.kind = clip_state ? Step::Clipped : Step::Own;
+    st.adam = AdamVals(adam, row_step); st.Pw = params;
+    if (row_step) st.lazy = st.adam;
+    st.norm = Norm::of(n_tok, count);
+    st.max_norm = max_norm; st.clip_state = clip_state; st.clip_scratch = clip_scratch;
+    return st;
+}
 int fira_train_step_begin(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
                           void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
                           int32_t* n_tok, void* mid_event) {
-    FIRA_REQUIRE(mid_event, "fira_train_step_begin: mid_event missing (the caller's collective waits for it)");
-    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, mid_event, nullptr,
-                      nullptr, true);
+    Step st;
+    st.phase = Step::FirstHalf; st.mid_event = (hipEvent_t)mid_event;
+    return train_call("fira_train_step_begin", st, stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok);
 }
-
 // (v10) the data-parallel step with the row-sparse update of the word tables: _begin_rows takes the optimizer's values for the
 // lazy reads of its forward pass (nothing is updated there), _end_rows updates decoder.embedding by rows inside the library;
 // encoder.embedding is the caller's (fira_adam_rows_step with tables = 2 behind the late bucket's all-reduce)
+// (opts.zero_grads = 0: the last micro-batch of an accumulated step -- the gradient holds this step's earlier micro-batches,
+//  cleared by the first of them: include/fira_hip.h, gradient accumulation)
 int fira_train_step_begin_rows(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
                                void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum,
                                int32_t* n_tok, void* mid_event, const fira_adam_opts* adam, int32_t* row_step) {
-    FIRA_REQUIRE(mid_event, "fira_train_step_begin_rows: mid_event missing (the caller's collective waits for it)");
-    FIRA_REQUIRE(adam && adam->m && adam->v && adam->step >= 1 && row_step, "fira_train_step_begin_rows: bad Adam arguments");
-    TRY(adam_sched_check(adam));
-    // (opts.zero_grads = 0: the last micro-batch of an accumulated step -- the gradient holds this step's earlier micro-batches,
-    //  cleared by the first of them: include/fira_hip.h, gradient accumulation)
-    // (adam only parameterises the lazy reads; train_call(begin_only) returns before any update)
-    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, mid_event, nullptr,
-                      adam, true, row_step);
+    Step st;
+    st.phase = Step::FirstHalf; st.mid_event = (hipEvent_t)mid_event;
+    st.lazy = AdamVals(adam, row_step); st.need_rows = true;
+    return train_call("fira_train_step_begin_rows", st, stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok);
 }
-// the second half of the step begun on this thread; row_step: see fira_train_step_end_rows
-static int train_step_end(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count,
-                          int32_t* row_step) {
+// the second half of the step begun on this thread: DpEarly, or nothing (adam == NULL: the caller updates everything itself);
+// row_step: fira_train_step_end_rows (nullptr: every row of decoder.embedding).  A rejected call drops the step.
+static int train_step_end(const char* who, void* stream, float* params, const fira_adam_opts* adam, void* early_event,
+                          const float* count, int32_t* row_step, bool need_rows) {
     PendingStep& ps = g_pending;
-    FIRA_REQUIRE(ps.active, "fira_train_step_end: no step begun on this thread (fira_train_step_begin)");
+    const bool begun = ps.active;
     ps.active = false;
-    FIRA_REQUIRE((hipStream_t)stream == ps.ctx.s, "fira_train_step_end: not the stream the step was begun on");
-    FIRA_REQUIRE(!adam || (adam->m && adam->v && adam->step >= 1 && params), "fira_train_step_end: bad Adam arguments");
-    TRY(adam_sched_check(adam));
-    FIRA_REQUIRE(!params || params == ps.ctx.P, "fira_train_step_end: not the parameter buffer the step was begun with");
     Ctx& c = ps.ctx;                         // (the step's own state: dtype, shadows, graph density and pending reductions included)
-    c.adam = adam;
-    c.Pw = params;
-    c.row_step = row_step;                   // (fira_train_step_end_rows; nullptr: every row of decoder.embedding, as before)
-    c.adam_a_only = true;
-    c.ev_early = (hipEvent_t)early_event;
-    c.count = count;
+    Step st;
+    st.kind = adam ? Step::DpEarly : Step::None;
+    st.adam = AdamVals(adam, row_step); st.Pw = params; st.need_rows = need_rows;
+    st.ev_early = (hipEvent_t)early_event;
+    st.norm = Norm::of(c.n_tok, count);
+    TRY(check_step(st, who, nullptr, nullptr, nullptr));
+    FIRA_REQUIRE(begun, "%s: no step begun on this thread (fira_train_step_begin)", who);
+    FIRA_REQUIRE((hipStream_t)stream == c.s, "%s: not the stream the step was begun on", who);
+    FIRA_REQUIRE(!params || params == c.P, "%s: not the parameter buffer the step was begun with", who);
+    st.lazy = c.step.lazy;                   // (lazy rows: as begun)
+    c.step = st;
     TRY(backward_encoder(c, ps.mid));
-    if (wait_probe().enabled() && ++wait_probe().calls == 20) wait_probe().report();
+    wait_probe().tick();
     return 0;
 }
 int fira_train_step_end_rows(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count,
                              int32_t* row_step) {
-    FIRA_REQUIRE(adam && row_step, "fira_train_step_end_rows: bad argument");
-    return train_step_end(stream, params, adam, early_event, count, row_step);
+    return train_step_end("fira_train_step_end_rows", stream, params, adam, early_event, count, row_step, true);
 }
 int fira_train_step_end(void* stream, float* params, const fira_adam_opts* adam, void* early_event, const float* count) {
-    return train_step_end(stream, params, adam, early_event, count, nullptr);
+    return train_step_end("fira_train_step_end", stream, params, adam, early_event, count, nullptr, false);
 }
 
 int fira_train_step(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads, void* workspace,
                     size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok,
                     const fira_adam_opts* adam) {
-    FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_step: Adam moments missing");
-    FIRA_REQUIRE(adam->step >= 1, "fira_train_step: the Adam step counter starts at 1");
-    TRY(adam_sched_check(adam));
-    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam);
+    return train_call("fira_train_step", own_step(adam, params, nullptr, n_tok, nullptr), stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok);
 }
-
 int fira_train_step_rows(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads, void* workspace,
                          size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok,
                          const fira_adam_opts* adam, int32_t* row_step) {
-    FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_step_rows: Adam moments missing");
-    FIRA_REQUIRE(adam->step >= 1, "fira_train_step_rows: the Adam step counter starts at 1");
-    TRY(adam_sched_check(adam));
-    FIRA_REQUIRE(row_step, "fira_train_step_rows: row_step missing");
-    FIRA_REQUIRE(opts && opts->zero_grads, "fira_train_step_rows: needs opts.zero_grads (an all-zero gradient row = an untouched row)");
-    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
-                      false, row_step);
+    Step st = own_step(adam, params, row_step, n_tok, nullptr);
+    st.need_rows = true;
+    return train_call("fira_train_step_rows", st, stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok);
 }
 // The one-call step with the update clipped by the global gradient norm (include/fira_hip.h; gradnorm.hip)
 int fira_train_step_clip(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads, void* workspace,
                          size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok,
                          const fira_adam_opts* adam, int32_t* row_step, float max_norm, fira_clip_state* state, void* scratch) {
-    FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_step_clip: Adam moments missing");
-    FIRA_REQUIRE(adam->step >= 1, "fira_train_step_clip: the Adam step counter starts at 1");
-    TRY(adam_sched_check(adam));
-    FIRA_REQUIRE(max_norm > 0.f, "fira_train_step_clip: max_norm must be > 0 (inf allowed)");
-    FIRA_REQUIRE(state && scratch && (uintptr_t)scratch % 8 == 0, "fira_train_step_clip: clip state / scratch missing");
-    FIRA_REQUIRE(!row_step || (opts && opts->zero_grads),
-                 "fira_train_step_clip: row_step needs opts.zero_grads (an all-zero gradient row = an untouched row)");
-    const ClipStep clip{adam, max_norm, state, scratch};
-    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
-                      false, row_step, &clip);
+    Step st = own_step(adam, params, row_step, n_tok, nullptr, max_norm, state, scratch);
+    st.kind = Step::Clipped;                 // (a missing state is an error here, not the unclipped form)
+    return train_call("fira_train_step_clip", st, stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok);
 }
-// Gradient accumulation (include/fira_hip.h): compositions of train_call's existing forms.  A micro-batch ahead of the last is
-// fira_train_fwd_bwd with the lazy reads of fira_train_step_begin_rows; the last one is the one-call step with the accumulated
-// count in place of its own token counter.
+// Gradient accumulation (include/fira_hip.h): compositions of the forms above.  A micro-batch ahead of the last is
+// fira_train_fwd_bwd with the lazy reads of fira_train_step_begin_rows; the last one is the one-call step (clipped where a clip
+// state is given) with the accumulated count in place of its own token counter.
 int fira_train_accum_micro(void* stream, const fira_dims* d, const fira_batch* batch, const float* params, float* grads,
                            void* workspace, size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok,
                            const fira_adam_opts* adam, int32_t* row_step) {
-    FIRA_REQUIRE((adam != nullptr) == (row_step != nullptr), "fira_train_accum_micro: adam and row_step are given together");
-    FIRA_REQUIRE(!adam || (adam->m && adam->v && adam->step >= 1), "fira_train_accum_micro: bad Adam arguments");
-    TRY(adam_sched_check(adam));
-    const AccumStep acc{false, nullptr, nullptr};
-    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, nullptr, adam,
-                      false, row_step, nullptr, &acc);
+    Step st;
+    st.lazy = AdamVals(adam, row_step);
+    return train_call("fira_train_accum_micro", st, stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok);
 }
 int fira_train_accum_last(void* stream, const fira_dims* d, const fira_batch* batch, float* params, float* grads, void* workspace,
                           size_t workspace_bytes, const fira_train_opts* opts, float* loss_sum, int32_t* n_tok,
                           const fira_adam_opts* adam, int32_t* row_step, float* stats, int32_t* n_tok_total, float max_norm,
                           fira_clip_state* clip_state, void* clip_scratch) {
-    FIRA_REQUIRE(adam && adam->m && adam->v, "fira_train_accum_last: Adam moments missing");
-    FIRA_REQUIRE(adam->step >= 1, "fira_train_accum_last: the Adam step counter starts at 1");
-    TRY(adam_sched_check(adam));
-    FIRA_REQUIRE(stats && n_tok_total, "fira_train_accum_last: the accumulated stats pair / token total is missing");
-    FIRA_REQUIRE((const void*)stats != (const void*)loss_sum && (const void*)n_tok_total != (const void*)n_tok,
-                 "fira_train_accum_last: the totals must not alias the micro-batch's scalars");
-    const AccumStep acc{true, stats, n_tok_total};
-    if (!clip_state)
-        return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
-                          false, row_step, nullptr, &acc);
-    FIRA_REQUIRE(max_norm > 0.f, "fira_train_accum_last: max_norm must be > 0 (inf allowed)");
-    FIRA_REQUIRE(clip_scratch && (uintptr_t)clip_scratch % 8 == 0, "fira_train_accum_last: clip scratch missing");
-    const ClipStep clip{adam, max_norm, clip_state, clip_scratch};
-    return train_call(stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok, nullptr, params, adam,
-                      false, row_step, &clip, &acc);
+    Step st = own_step(adam, params, row_step, n_tok, stats ? stats + 1 : nullptr, max_norm, clip_state, clip_scratch);
+    st.phase = Step::AccumLast; st.stats = stats; st.total = n_tok_total;
+    return train_call("fira_train_accum_last", st, stream, d, batch, params, grads, workspace, workspace_bytes, opts, loss_sum, n_tok);
 }
 int fira_adam_rows_step_clip(void* stream, const fira_dims* d, float* params, const float* grads, const fira_adam_opts* adam,
                              int32_t* row_step, const int32_t* n_tok, const float* count, int tables,

@@ -474,27 +474,43 @@ class TransModel(nn.Module):
                 self._ws[key].fill_(0xFF)            # scratch it never wrote (or wrote on another stream) shows up at once
         return self._ws[key]
 
+    # ---- what the six train_* methods share -------------------------------------------------------------------------------
+    def _train_prologue(self, db: DeviceBatch, zero_grad: bool, dropout, gcn_dropout, lazy_rows: bool = False):
+        """Ahead of every training call: parameters synced (unless the call reads lagging word-table rows lazily), the batch
+        on the device, the dropout rates (they follow ``self.training`` unless given), ONE advance of the mask stream.
+        Returns the call's ``TrainOpts`` and its workspace."""
+        _lib.lib()
+        if not lazy_rows:
+            self.sync_params()
+        db.wait_ready()
+        p = (self.cfg.dropout_rate if self.training else 0.0) if dropout is None else dropout
+        pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
+        self.dropout_step += 1                                   # every call draws its own masks
+        # zero_grads: the library clears gbuf[0, live) itself, beside the encoder's forward pass; tensors past `live` never
+        # receive a gradient (SURVEY.md F6)
+        opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
+                              1 if self.compact_dec else 0, 1 if zero_grad else 0)
+        return opts, self.workspace(db.B, 1)
+
+    @staticmethod
+    def _adam_opts(m, v, lr, step, beta1, beta2, eps, sched=None):
+        """``fira_adam_opts`` from the keyword form, or from the head of a ``rows`` tuple
+        ``(m, v, lr, step, beta1, beta2, eps, row_step)``: ``_adam_opts(*rows[:7], sched)``."""
+        return _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v), _lib.sched_ptr(sched))
+
+    def _train_call(self, name: str, db: DeviceBatch, opts, ws, *tail):
+        """``lib.<name>(stream, dims, batch, params, grads, workspace, bytes, opts, loss_sum, n_tok, *tail)``."""
+        _lib.check(getattr(_lib.lib(), name)(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct), _lib.ptr(self.flat.data),
+                                             _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(), C.byref(opts),
+                                             _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), *tail), name)
+        return self.loss_sum, self.n_tok
+
     def train_fwd_bwd(self, db: DeviceBatch, zero_grad: bool = True, dropout: Optional[float] = None,
                       gcn_dropout: Optional[float] = None, mid_event=None):
         """loss_sum, n_tok (device scalars) and d(loss_sum)/d(params) into ``self.gbuf`` (reference
         run_model.py:104-108 minus the optimizer).  Dropout follows ``self.training`` unless given."""
-        lib = _lib.lib()
-        self.sync_params()
-        db.wait_ready()
-        # zero_grad: the library clears gbuf[0, live) itself (opts.zero_grads), beside the encoder's forward pass; tensors
-        # past `live` never receive a gradient (SURVEY.md F6)
-        p = (self.cfg.dropout_rate if self.training else 0.0) if dropout is None else dropout
-        pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
-        self.dropout_step += 1
-        opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
-                              1 if self.compact_dec else 0, 1 if zero_grad else 0)
-        ws = self.workspace(db.B, 1)
-        _lib.check(lib.fira_train_fwd_bwd(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
-                                          _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
-                                          C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok),
-                                          self._event_handle(mid_event)),
-                   "fira_train_fwd_bwd")
-        return self.loss_sum, self.n_tok
+        opts, ws = self._train_prologue(db, zero_grad, dropout, gcn_dropout)
+        return self._train_call("fira_train_fwd_bwd", db, opts, ws, self._event_handle(mid_event))
 
     def train_step(self, db: DeviceBatch, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, beta1: float = 0.9,
                    beta2: float = 0.999, eps: float = 1e-8, dropout: Optional[float] = None,
@@ -508,61 +524,26 @@ class TransModel(nn.Module):
         gradient norm, a non-finite gradient applied as a zero-gradient step; with or without ``row_step``.
         ``sched`` (an ``_lib.LrSchedule``): ``lr`` is ignored and step j uses ``fira_lr_at(sched, j)`` -- this step and every
         update a lagging row still owes."""
-        lib = _lib.lib()
-        if row_step is None:
-            self.sync_params()
-        db.wait_ready()
-        p = (self.cfg.dropout_rate if self.training else 0.0) if dropout is None else dropout
-        pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
-        self.dropout_step += 1
-        opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
-                              1 if self.compact_dec else 0, 1)
-        adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v), _lib.sched_ptr(sched))
-        ws = self.workspace(db.B, 1)
+        opts, ws = self._train_prologue(db, True, dropout, gcn_dropout, lazy_rows=row_step is not None)
+        adam = self._adam_opts(m, v, lr, step, beta1, beta2, eps, sched)
         if clip is not None:
             max_norm, state, scratch = clip
-            _lib.check(lib.fira_train_step_clip(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
-                                                _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
-                                                C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), C.byref(adam),
-                                                _lib.ptr(row_step), float(max_norm), _lib.ptr(state), _lib.ptr(scratch)),
-                       "fira_train_step_clip")
-            return self.loss_sum, self.n_tok
+            return self._train_call("fira_train_step_clip", db, opts, ws, C.byref(adam), _lib.ptr(row_step), float(max_norm),
+                                    _lib.ptr(state), _lib.ptr(scratch))
         if row_step is not None:
-            _lib.check(lib.fira_train_step_rows(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
-                                                _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
-                                                C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), C.byref(adam),
-                                                _lib.ptr(row_step)), "fira_train_step_rows")
-            return self.loss_sum, self.n_tok
-        _lib.check(lib.fira_train_step(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct), _lib.ptr(self.flat.data),
-                                       _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(), C.byref(opts),
-                                       _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), C.byref(adam)),
-                   "fira_train_step")
-        return self.loss_sum, self.n_tok
+            return self._train_call("fira_train_step_rows", db, opts, ws, C.byref(adam), _lib.ptr(row_step))
+        return self._train_call("fira_train_step", db, opts, ws, C.byref(adam))
 
     def train_accum_micro(self, db: DeviceBatch, zero_grad: bool, rows=None, sched=None, dropout: Optional[float] = None,
                           gcn_dropout: Optional[float] = None):
         """A micro-batch of an accumulated step that is not its last (fira_train_accum_micro): :meth:`train_fwd_bwd` --
         ``self.gbuf`` is added to unless ``zero_grad`` (the first micro-batch) -- that, with ``rows`` (as
         :meth:`train_step_begin` takes them), reads the word-table rows the row-sparse Adam still owes lazily.  Updates nothing."""
-        lib = _lib.lib()
-        if rows is None:
-            self.sync_params()
-        db.wait_ready()
-        p = (self.cfg.dropout_rate if self.training else 0.0) if dropout is None else dropout
-        pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
-        self.dropout_step += 1                                   # every micro-batch draws its own masks
-        opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
-                              1 if self.compact_dec else 0, 1 if zero_grad else 0)
-        ws = self.workspace(db.B, 1)
+        opts, ws = self._train_prologue(db, zero_grad, dropout, gcn_dropout, lazy_rows=rows is not None)
         adam, row_step = None, None
         if rows is not None:
-            m_, v_, lr, step, b1, b2, eps, row_step = rows
-            adam = C.byref(_lib.AdamOpts(lr, b1, b2, eps, int(step), _lib.ptr(m_), _lib.ptr(v_), _lib.sched_ptr(sched)))
-        _lib.check(lib.fira_train_accum_micro(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
-                                              _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
-                                              C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), adam,
-                                              _lib.ptr(row_step)), "fira_train_accum_micro")
-        return self.loss_sum, self.n_tok
+            adam, row_step = C.byref(self._adam_opts(*rows[:7], sched)), rows[7]
+        return self._train_call("fira_train_accum_micro", db, opts, ws, adam, _lib.ptr(row_step))
 
     def train_accum_last(self, db: DeviceBatch, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, stats: torch.Tensor,
                          n_tok_total: torch.Tensor, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
@@ -571,24 +552,11 @@ class TransModel(nn.Module):
         """The last micro-batch of an accumulated step (fira_train_accum_last): :meth:`train_step` on a gradient buffer that
         holds the earlier micro-batches; the library adds this one's scalars to ``stats`` / ``n_tok_total``
         (``ops.accum_stats``) and normalises the update -- and a clipped step's norm -- by the accumulated count."""
-        lib = _lib.lib()
-        if row_step is None:
-            self.sync_params()
-        db.wait_ready()
-        p = (self.cfg.dropout_rate if self.training else 0.0) if dropout is None else dropout
-        pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
-        self.dropout_step += 1
-        opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
-                              1 if self.compact_dec else 0, 0)
-        adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v), _lib.sched_ptr(sched))
-        ws = self.workspace(db.B, 1)
+        opts, ws = self._train_prologue(db, False, dropout, gcn_dropout, lazy_rows=row_step is not None)
+        adam = self._adam_opts(m, v, lr, step, beta1, beta2, eps, sched)
         max_norm, state, scratch = (0.0, None, None) if clip is None else clip
-        _lib.check(lib.fira_train_accum_last(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
-                                             _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
-                                             C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok), C.byref(adam),
-                                             _lib.ptr(row_step), _lib.ptr(stats), _lib.ptr(n_tok_total), float(max_norm),
-                                             _lib.ptr(state), _lib.ptr(scratch)), "fira_train_accum_last")
-        return self.loss_sum, self.n_tok
+        return self._train_call("fira_train_accum_last", db, opts, ws, C.byref(adam), _lib.ptr(row_step), _lib.ptr(stats),
+                                _lib.ptr(n_tok_total), float(max_norm), _lib.ptr(state), _lib.ptr(scratch))
 
     def train_step_begin(self, db: DeviceBatch, mid_event, dropout: Optional[float] = None,
                          gcn_dropout: Optional[float] = None, rows=None, sched=None, zero_grad: bool = True):
@@ -596,34 +564,16 @@ class TransModel(nn.Module):
         ``mid_event`` fires when the gradients of ``[0, split)`` are final.  The step stays pending until
         :meth:`train_step_end`; ``db`` must stay alive until then.  ``zero_grad=False``: the last micro-batch of an accumulated
         step -- ``self.gbuf`` holds the earlier ones."""
-        lib = _lib.lib()
-        if rows is None:
-            self.sync_params()
-        db.wait_ready()
-        p = (self.cfg.dropout_rate if self.training else 0.0) if dropout is None else dropout
-        pg = (0.2 if self.training else 0.0) if gcn_dropout is None else gcn_dropout
-        self.dropout_step += 1
-        opts = _lib.TrainOpts(p, pg, self.dropout_seed, 1 if self.compact_head else 0, self._dtype_code(),
-                              1 if self.compact_dec else 0, 1 if zero_grad else 0)
-        ws = self.workspace(db.B, 1)
+        opts, ws = self._train_prologue(db, zero_grad, dropout, gcn_dropout, lazy_rows=rows is not None)
         self._pending_db = db
-        if rows is not None:
-            # row-sparse Adam of the word tables (fira_train_step_begin_rows): rows = (m, v, lr, step, beta1, beta2, eps, row_step)
-            # -- the optimizer's values (and `sched`, the schedule that replaces lr) parameterise the forward pass's lazy reads
-            # of lagging rows; nothing is updated here
-            m_, v_, lr, step, b1, b2, eps, row_step = rows
-            adam = _lib.AdamOpts(lr, b1, b2, eps, int(step), _lib.ptr(m_), _lib.ptr(v_), _lib.sched_ptr(sched))
-            _lib.check(lib.fira_train_step_begin_rows(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
-                                                      _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
-                                                      C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok),
-                                                      self._event_handle(mid_event), C.byref(adam), _lib.ptr(row_step)),
-                       "fira_train_step_begin_rows")
-            return self.loss_sum, self.n_tok
-        _lib.check(lib.fira_train_step_begin(_lib.cur_stream(), C.byref(self.dims), C.byref(db.struct),
-                                             _lib.ptr(self.flat.data), _lib.ptr(self.gbuf), _lib.ptr(ws), ws.numel(),
-                                             C.byref(opts), _lib.ptr(self.loss_sum), _lib.ptr(self.n_tok),
-                                             self._event_handle(mid_event)), "fira_train_step_begin")
-        return self.loss_sum, self.n_tok
+        if rows is None:
+            return self._train_call("fira_train_step_begin", db, opts, ws, self._event_handle(mid_event))
+        # row-sparse Adam of the word tables (fira_train_step_begin_rows): rows = (m, v, lr, step, beta1, beta2, eps, row_step)
+        # -- the optimizer's values (and `sched`, the schedule that replaces lr) parameterise the forward pass's lazy reads
+        # of lagging rows; nothing is updated here
+        adam = self._adam_opts(*rows[:7], sched)
+        return self._train_call("fira_train_step_begin_rows", db, opts, ws, self._event_handle(mid_event), C.byref(adam),
+                                _lib.ptr(rows[7]))
 
     def train_step_end(self, m: torch.Tensor, v: torch.Tensor, lr: float, step: int, early_event=None, count=None,
                        beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, row_step=None, update: bool = True,
@@ -632,7 +582,7 @@ class TransModel(nn.Module):
         passed ``early_event`` (the caller's event behind the all-reduce of that slice), scaled by ``1 / count`` (a device
         float, the all-reduced token count).  ``[split, live)`` is left to the caller (its bucket is reduced afterwards).
         ``update=False``: the backward pass only (adam = NULL) -- the caller updates both slices itself (clipped steps)."""
-        adam = _lib.AdamOpts(lr, beta1, beta2, eps, int(step), _lib.ptr(m), _lib.ptr(v), _lib.sched_ptr(sched))
+        adam = self._adam_opts(m, v, lr, step, beta1, beta2, eps, sched)
         if not update:
             _lib.check(_lib.lib().fira_train_step_end(_lib.cur_stream(), None, None, None, None), "fira_train_step_end")
         elif row_step is not None:
