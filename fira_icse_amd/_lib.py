@@ -191,6 +191,7 @@ SIGNATURES = {
     "fira_beam_prepare": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "fira_beam_select": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_beam_select_scored": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P]),
+    "fira_beam_select_gumbel": (_I, [_P, _DP, _I, _I, _I, _F] + [_P] * 18),
     "fira_greedy_advance": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_decode_step": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _P, _P]),
     "fira_decode_step_sample": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _F, _I, _F, _P, _P, _P, _I]),

@@ -7,6 +7,7 @@
 //               body, so the three kernels' rows are bit-identical by construction
 //   words       slot_word (copy slot -> source id), entry_word (entry -> vocabulary id)
 //   streaming   RowSplit, stream_row_marked: a row read once in 16-byte loads whatever its alignment
+//   noise       noise_stream, gumbel_noise: the counter-hash Gumbel perturbation of the sampler and the stochastic beam
 //   selection   TopList, pass_through_done, write_hypotheses: the two beam-select kernels' bookkeeping
 #pragma once
 #include <limits.h>
@@ -173,6 +174,20 @@ __device__ __forceinline__ int entry_word(int w, const int32_t* __restrict__ sou
     if (w >= V + L) nt = sub[b * S + min(w - V - L, S - 1)];
     else if (w >= V) nt = sou[b * L + (w - V)];
     return nt;
+}
+
+// ---------------------------------------------------------------- noise
+// The noise stream of row j (sample or beam slot) of the commit with `key` at `step`, T = tar_len, and the Gumbel perturbation
+// of entry i under it (include/fira_hip.h, fira_decode_step_sample; the numpy twin: tests/sample_ref.py).
+__device__ __forceinline__ uint32_t noise_stream(uint32_t key, uint64_t seed, int j, int T, int step) {
+    const uint32_t base = mix32(key ^ mix32((uint32_t)seed ^ mix32((uint32_t)(seed >> 32) + 0x632BE5ABu)));
+    return mix32(base + 0x9E3779B9u * (uint32_t)(j * T + step + 1));
+}
+__device__ __forceinline__ float gumbel_noise(uint32_t stream, uint32_t i) {
+    const uint32_t h = mix32(i ^ stream);
+    // (m + 0.5) * 2^-24 with m = h >> 8; m = 2^24 - 1 rounds to 1.0 in fp32 -- clamp to the largest float below 1
+    const float u = fminf(((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+    return -logf(-logf(u));
 }
 
 // ---------------------------------------------------------------- streaming one row

@@ -18,14 +18,6 @@
 
 namespace fira {
 
-// the Gumbel perturbation of entry i under a row's noise stream (the numpy twin: tests/sample_ref.py)
-__device__ __forceinline__ float gumbel_noise(uint32_t stream, uint32_t i) {
-    const uint32_t h = mix32(i ^ stream);
-    // (m + 0.5) * 2^-24 with m = h >> 8; m = 2^24 - 1 rounds to 1.0 in fp32 -- clamp to the largest float below 1
-    const float u = fminf(((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
-    return -logf(-logf(u));
-}
-
 __global__ __launch_bounds__(DDW_NT) void sample_dist_kernel(int V, int S, const float* __restrict__ logits, int ldl,
                                                              const float* __restrict__ score,
                                                              const int32_t* __restrict__ mem_valid, int n_sample,
@@ -93,8 +85,7 @@ __global__ __launch_bounds__(DDW_NT) void sample_dist_kernel(int V, int S, const
     // ---- Gumbel-max over the kept entries (p = 0 entries have score -inf and are skipped)
     const uint64_t seed = *seed_dev;
     const int b = r / n_sample, jsample = r - b * n_sample;
-    const uint32_t base = mix32((uint32_t)key[b] ^ mix32((uint32_t)seed ^ mix32((uint32_t)(seed >> 32) + 0x632BE5ABu)));
-    const uint32_t stream = mix32(base + 0x9E3779B9u * (uint32_t)(jsample * T + step + 1));
+    const uint32_t stream = noise_stream((uint32_t)key[b], seed, jsample, T, step);
     float best = -INFINITY, bp_own = 0.f;
     int bi = 0x7fffffff;
 #pragma unroll

@@ -1021,6 +1021,98 @@ class Searcher:
                st["prob"][cur].view(B, beam).clone())
         return res if scoring is None else res + (st["key"].view(B, beam).clone(),)
 
+    # ------------------------------------------------------------------ stochastic beam search: n samples without replacement
+    def _sbs_reset(self, st, B, n):
+        for k in ("gen", "length"):
+            st[k][0].zero_()
+            st[k][1].zero_()
+        st["gen"][0][:, 0] = START
+        st["length"][0].fill_(1)
+        for k in ("phi", "G", "logp"):
+            st[k][0].fill_(float("-inf"))
+            st[k][1].fill_(float("-inf"))
+            st[k][0].view(B, n)[:, 0] = 0.0                   # slot 0 of every commit is the empty message; the others are void
+        st["done"].zero_()
+
+    def _sbs_steps(self, st, ws, B, n, lo, hi, temperature):
+        """Steps lo..hi-1 of the beam's loop with fira_beam_select_gumbel as the selection: prepare -> KV-cached decoder step
+        (the members' steps and the mix, for an ensemble) -> merge -> constraints -> select, all on the device."""
+        lib, s, T = _lib.lib(), _lib.cur_stream(), self.cfg.tar_len
+        for step in range(lo, hi):
+            cur, nxt = step & 1, (step + 1) & 1
+            _lib.check(lib.fira_beam_prepare(s, B, n, T, step, _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]),
+                                             _lib.ptr(st["tok"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]),
+                                             _lib.ptr(st["done"])), "fira_beam_prepare")
+            self._step(ws, B, n, step, st["tok"], st["parent"] if step > 0 else None, st["dist"], None, None)
+            if st.get("merge", False):
+                self._merge(st, B * n, n, None, None)
+            if st["con"] is not None:
+                self._constrain(st, B * n, n, st["gen"][cur], st["length"][cur], None, None)
+            _lib.check(lib.fira_beam_select_gumbel(
+                s, C.byref(self.model.dims), B, n, step, float(temperature), _lib.ptr(st["dist"]), _lib.ptr(st["fin"]),
+                _lib.ptr(st["done"]), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["key"]), _lib.ptr(st["seed"]),
+                _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]), _lib.ptr(st["phi"][cur]), _lib.ptr(st["G"][cur]),
+                _lib.ptr(st["logp"][cur]), _lib.ptr(st["gen"][nxt]), _lib.ptr(st["length"][nxt]), _lib.ptr(st["phi"][nxt]),
+                _lib.ptr(st["G"][nxt]), _lib.ptr(st["logp"][nxt]), _lib.ptr(st["parent"])), "fira_beam_select_gumbel")
+
+    @torch.no_grad()
+    def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
+                        merge_copies: bool = True, constraints: Optional[Constraints] = None, chunk: int = 4,
+                        use_graphs: bool = True):
+        """``n`` messages per commit sampled WITHOUT replacement: stochastic beam search (Kool, van Hoof and Welling 2019;
+        ``fira_beam_select_gumbel``).  A beam search whose ranking key is the Gumbel-perturbed
+        log-probability of the hypothesis, a child's key conditioned on its parent's; the n hypotheses it ends with are an exact
+        sample without replacement from the model's distribution over messages, and slot 0 is an ordinary ancestral sample.
+
+        Returns (tokens [B,n,T] int64 starting with <start>, lengths [B,n], logp [B,n], phi [B,n], key [B,n]); slots are in key
+        order, best first.  ``logp`` is the untempered sum of the log-probabilities of the entries taken (comparable with
+        ``sample``'s), ``phi`` the log-probability under the sampling model q ~ p^(1/temperature), renormalised over the
+        positive entries of every step's row as merge and constraints leave it.  A commit with fewer than n possible
+        messages leaves VOID slots: length 1, <start> alone, logp = phi = key = -inf.
+
+        The noise is the sampler's counter hash of (``seed``, ``keys[b]``, slot, step, entry): a commit's result depends on its
+        key (default: its row in the batch), not on the batch it lands in; with n = 1 and ``merge_copies=False`` the result is
+        ``sample(db, 1, ...)``'s, bit for bit.  ``merge_copies`` (default on): sample WORDS -- the hypotheses of finite key are
+        then pairwise distinct word sequences.  Off, they are distinct ENTRY paths, and one message may appear twice (spelled
+        once through the generator and once through a copy slot).  ``constraints`` as for ``beam``; an ensemble (``members=``)
+        samples from the mix.  The loop is the beam's (``_Loop``): prepare, step, merge, constraints, selection, captured into
+        hipGraphs of ``chunk`` steps; the state is keyed ("sbs", B, n, merge, constraints, temperature) -- the temperature
+        is baked into the captured launches; the seed and the keys are device values: one capture serves them all."""
+        B, T = db.B, self.cfg.tar_len
+        con = self._active(constraints)                      # raises before anything is launched
+        merge = bool(merge_copies)
+        keys = torch.arange(B) if keys is None else torch.as_tensor(keys)
+        if keys.numel() != B:                                 # raises before anything is launched
+            raise ValueError("keys: %d values for a batch of %d commits" % (keys.numel(), B))
+        temperature = float(temperature)
+        # the kernel's own limits, before the encoder pass or any other launch
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 8:
+            raise ValueError("sample_distinct: n = %r outside 1..8" % (n,))
+        if not 0.0 < temperature < float("inf"):              # (also refuses nan)
+            raise ValueError("sample_distinct: temperature = %r must be finite and > 0" % (temperature,))
+        BR = B * n
+
+        def make(i32, f32):
+            st = dict(gen=[i32(BR, T), i32(BR, T)], length=[i32(BR), i32(BR)], phi=[f32(BR), f32(BR)], G=[f32(BR), f32(BR)],
+                      logp=[f32(BR), f32(BR)], tok=i32(BR), parent=i32(BR), fin=i32(BR), active=i32(9), done=i32(1),
+                      dist=f32(BR, self.cfg.out_len), con=con, key=i32(B),
+                      seed=torch.zeros(1, dtype=torch.int64, device=self.model.device_))
+            if merge:
+                st["merge"] = True
+            if con is not None:
+                st["banned"] = self._banned_buffer(con)
+            return st
+        loop = _Loop(self, db, n, ("sbs", B, n, merge, con, temperature), make, chunk, use_graphs)
+        st, ws = loop.st, loop.ws
+        st["key"].copy_(keys.reshape(B).to(torch.int32))
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)     # the uint64 bits in an int64 tensor
+        loop.start(lambda lo, hi: self._sbs_steps(st, ws, B, n, lo, hi, temperature), lambda: self._sbs_reset(st, B, n),
+                   lambda hi: bool(st["done"].item())).run()
+        cur = loop.hi & 1                                    # the ping-pong buffer the last step run wrote
+        return (st["gen"][cur].view(B, n, T).long(), st["length"][cur].view(B, n).long(), st["logp"][cur].view(B, n).clone(),
+                st["phi"][cur].view(B, n).clone(), st["G"][cur].view(B, n).clone())
+
     def best(self, gen, length, prob) -> List[List[int]]:
         """argmax-probability hypothesis per item, first on ties (run_model.py:351-352)."""
         if gen.dim() == 2:

@@ -871,6 +871,45 @@ int fira_beam_select_scored(void* stream, const fira_dims* d, int B, int n_beam,
                             const float* inv_lp /* device, [tar_len + 1] */, int n_groups, float diversity,
                             float* key_out /* [B*n_beam] or NULL */);
 
+/* Stochastic beam search: fira_beam_select with a Gumbel-perturbed key (csrc/beam_gumbel.hip; additive, the ABI version is
+ * unchanged; Kool, van Hoof and Welling 2019).  It takes fira_beam_select's place in the step loop, after fira_beam_prepare, the
+ * step (fira_mix_dist), fira_merge_dist and fira_constrain_dist; the n_beam hypotheses a search ends with are a sample WITHOUT
+ * replacement from the model's distribution over messages, best key first, and slot 0 is an ordinary ancestral sample.
+ * State per slot, double-buffered by the caller: gen, length and parent as fira_beam_select has them, and three fp32 values in
+ * place of prob: phi (log-probability under the sampling model), G (the perturbed key; -inf marks the slot VOID) and logp (the
+ * untempered sum of logf(p_entry) of the entries taken -- what fira_sample_advance accumulates).  The caller seeds slot 0 of
+ * every commit with phi = G = logp = 0 and the other slots with G = -inf.
+ * Per commit b, slot j RUNS if G_j > -inf and finished[b * n_beam + j] == 0.  Its row p = dist[b * n_beam + j, :] is taken as it
+ * stands; an entry is VALID if 0 < p_i <= FLT_MAX (a zero, a NaN, an inf are void).  Over the valid entries, all in fp32:
+ *     sampling model  q_i = p_i^(1/T) / Z:  u_i = logf(p_i) * (1/T),  um = logf(max_i p_i) * (1/T),
+ *                     lnZ = um + logf(sum_i expf(u_i - um))          (always applied, at T = 1 too; fixed summation order)
+ *     noise           g_i of fira_decode_step_sample with stream = mix32(base(key[b], seed) + 0x9E3779B9 * (j * tar_len + step + 1))
+ *     row score       s_i = fmaf(logf(p_i), 1/T, g_i) -- the sampler's own expression and rounding: the row's arg-max a (lowest
+ *                     index on ties) is the sampler's draw for the same (key, seed, j, step), bit for bit
+ *     c = phi_j - lnZ,  g_i = c + s_i,  Zmax = c + s_a
+ *     key             of a: G_j, by definition.  Of i != a, with d = g_i - Zmax:  G_j where d >= 0 (a tie with a), else
+ *                     v = (G_j - g_i) + log1pf(-expf(d)),   key_i = (G_j - fmaxf(0, v)) - log1pf(expf(-fabsf(v)))
+ *                     -- the stable form of -log(exp(-G_j) - exp(-Zmax) + exp(-g_i)); no operand of it is infinite
+ *     child           length + 1, the id entry i resolves to (sou / sub_token for a copy entry) appended, key as above,
+ *                     logp = logp_j + logf(p_i),  phi = phi_j + (logf(p_i) * (1/T) - lnZ),  parent = the row of j
+ * A finished hypothesis with G > -inf is CARRIED: it competes with its own (phi, G, logp) unchanged.  Void candidates: the
+ * entries that are not valid, and every entry of a void or finished slot's row.  Total order per commit: void last, then key
+ * descending, then a row's arg-max entry before every other candidate, then fira_beam_select's flattened index ascending
+ * (running slots in slot order, then the carried hypotheses in slot order).  The n_beam best go to slots 0 .. n_beam - 1, best
+ * first; where fewer than n_beam candidates are not void the remaining slots are void: G = phi = logp = -inf, length = 1,
+ * gen = <start> alone, parent = the slot's own row.  (A void slot never counts as finished, so `done` does not latch while a
+ * commit has one: such a search runs its tar_len - 1 steps.)  Once `done` is set the state is copied through.
+ * key [B] int32 per commit; seed_dev a DEVICE uint64 read when the kernel runs (one captured graph serves every seed).
+ * 1 <= n_beam <= 8, 2 <= tar_len <= 64, 0 <= step <= tar_len - 2, vocab in 9 .. 25 600, sou_len + sub_len <= 1 024, temperature
+ * finite and > 0; anything else returns non-zero with the reason in fira_last_error() and nothing is launched.  One workgroup
+ * per commit; a running row is read once and kept in registers; vector stores only, no atomics on global memory.          */
+int fira_beam_select_gumbel(void* stream, const fira_dims* d, int B, int n_beam, int step, float temperature,
+                            const float* dist, const int32_t* finished, const int32_t* done, const int32_t* sou,
+                            const int32_t* sub_token, const int32_t* key /* [B] */, const uint64_t* seed_dev,
+                            const int32_t* gen_in, const int32_t* len_in, const float* phi_in, const float* G_in,
+                            const float* logp_in, int32_t* gen_out, int32_t* len_out, float* phi_out, float* G_out,
+                            float* logp_out, int32_t* parent);
+
 /* Greedy search bookkeeping (the same loop at beam 1 without the [B, vocab+S] distribution): consumes the arg-max
  * index / probability fira_decode_step wrote, resolves copy indices through sou / sub_token, appends the id at
  * out[b, step+1], multiplies prob, bumps length, clears alive[b] at <eos>, writes the next step's input ids to `tokens`

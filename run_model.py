@@ -90,6 +90,11 @@ def parse_args(argv):
     ap.add_argument("--top-k", type=int, default=None, help="with --sample: keep the k most probable entries (default 0 = off)")
     ap.add_argument("--top-p", type=float, default=None, help="with --sample: nucleus mass in (0, 1] (default 1 = off)")
     ap.add_argument("--sample-seed", type=int, default=None, help="with --sample: seed of the sampling noise (default 0)")
+    ap.add_argument("--without-replacement", action="store_true", help="with --sample: draw the N candidates WITHOUT "
+                    "replacement by stochastic beam search on the device -- N distinct messages for the cost of one beam "
+                    "search, the first an ordinary sample; implies --merge-copies; combines with --temperature, --sample-seed, "
+                    "--no-repeat-ngram, --min-length, --ban-words, --ensemble and --rerank, not with --top-k / --top-p; every "
+                    "line of OUTPUT/output_fira_samples then carries the candidates' keys under \"key\", best first")
     ap.add_argument("--score", default=None, metavar="refs|PATH", help="test: instead of searching, score given messages "
                     "teacher-forced on the device: 'refs' = the test split's own messages, PATH = a file with one line per test "
                     "commit in all_index['test'] order (plain text as in OUTPUT/output_fira, or the JSON lines of "
@@ -167,6 +172,7 @@ def parse_args(argv):
         check_clip_args(a)
         check_ema_args(a)
         check_lr_schedule_args(a)
+        check_without_replacement_args(a)
         check_score_args(a)
         check_constraint_args(a)
         check_merge_args(a)
@@ -293,6 +299,35 @@ def lr_schedule_from_args(a, planned_steps: int, done_steps: int = 0):
             "min_lr": (a.lr_min or 0.0) if decays else 0.0}
 
 
+def check_without_replacement_args(a):
+    """Validates --without-replacement against the other options (no GPU, no DataSet needed); raises ValueError naming the
+    option on a conflict.  The options it combines with pass their own checks (they let --sample through when it is given)."""
+    if not getattr(a, "without_replacement", False):
+        return a
+    wr = "--without-replacement"
+    if a.stage != "test":
+        raise ValueError("%s only applies to the test stage" % wr)
+    if a.sample is None:
+        raise ValueError("%s draws the candidates of --sample without replacement: it needs --sample" % wr)
+    for name, flag in (("top_k", "--top-k"), ("top_p", "--top-p")):
+        if getattr(a, name, None) is not None:
+            raise ValueError("%s samples from the whole tempered distribution: it does not combine with %s" % (wr, flag))
+    if a.beam is not None and a.beam > 1:
+        raise ValueError("%s is a search of its own over --sample slots: it does not combine with --beam %d" % (wr, a.beam))
+    if getattr(a, "score", None) is not None:
+        raise ValueError("%s draws messages: it does not combine with --score" % wr)
+    for name, flag in (("prefix", "--prefix"), ("prefix_file", "--prefix-file"), ("length_penalty", "--length-penalty"),
+                       ("beam_groups", "--beam-groups"), ("diversity_penalty", "--diversity-penalty")):
+        if getattr(a, name, None) is not None:
+            raise ValueError("%s ranks by a random key of the whole message: it does not combine with %s" % (wr, flag))
+    if getattr(a, "nbest", False):
+        raise ValueError("%s writes its candidates to output_fira_samples: it does not combine with --nbest" % wr)
+    if getattr(a, "ensemble", None) is not None and a.rerank in ("logp_word", "mean_logp_word"):
+        raise ValueError("%s with --ensemble: --rerank %s scores with one model and does not combine with an ensemble "
+                         "(--rerank mbr_bleu does)" % (wr, a.rerank))
+    return a
+
+
 def check_score_args(a):
     """Validates --score / --rerank against the other options (no GPU, no DataSet needed); raises ValueError on a conflict."""
     if a.rerank is not None and a.sample is None:
@@ -348,7 +383,7 @@ def check_constraint_args(a):
         return a
     if a.stage != "test":
         raise ValueError("%s only apply to the test stage" % ", ".join(given))
-    if a.sample is not None:
+    if a.sample is not None and not getattr(a, "without_replacement", False):
         raise ValueError("%s constrain a search: they do not combine with --sample" % ", ".join(given))
     if a.score is not None:
         raise ValueError("%s constrain a search: they do not combine with --score" % ", ".join(given))
@@ -390,7 +425,7 @@ def check_merge_args(a):
         return a
     if a.stage != "test":
         raise ValueError("%s only apply to the test stage" % ", ".join(given))
-    if a.sample is not None:
+    if a.sample is not None and not (getattr(a, "without_replacement", False) and not nbest):
         raise ValueError("%s belong to a search: they do not combine with --sample" % ", ".join(given))
     if a.score is not None:
         raise ValueError("%s belong to a search: they do not combine with --score" % ", ".join(given))
@@ -512,7 +547,7 @@ def check_ensemble_args(a):
         return a
     if a.stage != "test":
         raise ValueError("--ensemble only applies to the test stage")
-    if a.sample is not None:
+    if a.sample is not None and not getattr(a, "without_replacement", False):
         raise ValueError("--ensemble mixes the distributions of a search: it does not combine with --sample")
     if a.score is not None:
         raise ValueError("--ensemble mixes the distributions of a search: it does not combine with --score")
@@ -789,6 +824,8 @@ class Run:
             members.append(m)
         search = Searcher(self.model, members=members, weights=getattr(self.a, "ensemble_weights", None))
         mine = shard_indices(list(range(len(store))), self.rank, self.world)
+        if self.a.sample is not None and getattr(self.a, "without_replacement", False):
+            return self.test_sample_distinct(search, store, mine, constraints)
         if self.a.sample is not None:
             return self.test_sample(search, store, mine)
         if self.a.score is not None:
@@ -883,8 +920,56 @@ class Run:
                 f.write("".join(l + "\n" for l in samples))
         return lines
 
+    def test_sample_distinct(self, search, store, mine, constraints):
+        """--sample N --without-replacement: N distinct messages per commit by stochastic beam search on the device
+        (decode.Searcher.sample_distinct, over words); the noise of a commit is keyed by its index in the test split.  The
+        files are --sample's; a line of output_fira_samples also carries the candidates' keys, best first, and leaves out the
+        void slots of a commit that has fewer than N possible messages."""
+        a, cfg = self.a, self.cfg
+        test_index = self.all_index["test"]
+        ninf = float("-inf")
+        lines, samples, n_tok, t0 = [], [], 0, time.time()
+        for lo in range(0, len(mine), cfg.test_batch_size):
+            idx = mine[lo:lo + cfg.test_batch_size]
+            db = self.device_batch(store, idx)
+            toks, lens, logp, _, key = search.sample_distinct(db, a.sample, temperature=a.temperature, seed=a.sample_seed,
+                                                              keys=idx, merge_copies=True, constraints=constraints)
+            live = key > ninf                                # void slots come last: they are never picked, never written
+            best = search.best_sample(toks, lens, logp)      # (a void slot's logp is -inf)
+            values = None
+            if a.rerank == "mbr_bleu":                       # a void slot is an empty message: it lowers every mean alike
+                _, util = search.mbr(toks, lens, logp)
+                masked = torch.where(live.cpu(), util, torch.full_like(util, ninf))
+                top = masked.max(1, keepdim=True).values
+                tie = torch.where(masked == top, logp.cpu().double(), torch.full_like(util, ninf))
+                pick = torch.argmax(tie, dim=1).tolist()     # the utility, then the log-probability, then the lower slot
+                best = [toks[k, j, :int(lens[k, j])].tolist() for k, j in enumerate(pick)]
+                values = util.tolist()
+            elif a.rerank is not None:
+                best, values = self.rerank(search, db, toks, lens, live)
+            toks, lens, logp, key, live = toks.tolist(), lens.tolist(), logp.tolist(), key.tolist(), live.tolist()
+            for k, i in enumerate(idx):
+                var_map = self.var_maps[test_index[i]]
+                lines.append(text.detokenize(best[k], self.r_vocab, var_map))
+                slots = [j for j in range(a.sample) if live[k][j]]
+                rec = {"candidates": [text.detokenize(toks[k][j][:lens[k][j]], self.r_vocab, var_map) for j in slots],
+                       "logp": [logp[k][j] for j in slots], "key": [key[k][j] for j in slots]}
+                if values is not None:
+                    rec[a.rerank] = [values[k][j] for j in slots]
+                samples.append(json.dumps(rec))
+                n_tok += sum(max(lens[k][j] - 1, 0) for j in slots)
+            if self.rank == 0:
+                print("data: %d/%d  (%.1f tokens/s)" % (min(len(mine), lo + cfg.test_batch_size), len(mine),
+                                                        n_tok / max(time.time() - t0, 1e-9)), flush=True)
+        lines, samples = gather_lines(lines), gather_lines(samples)
+        if self.rank == 0:
+            with open(self.out("output_fira"), "w") as f:
+                f.write("".join(l + "\n" for l in lines))
+            with open(self.out("output_fira_samples"), "w") as f:
+                f.write("".join(l + "\n" for l in samples))
+        return lines
 
-    def rerank(self, search, db, toks, lens):
+    def rerank(self, search, db, toks, lens, live=None):
         """--rerank: the drawn candidates scored teacher-forced (decode.Searcher.score) and the best one per commit under the
         key.  A candidate in which <pad> or <start> was drawn mid-message cannot be scored (its text drops that id): it is
         scored up to there, reported as null and never preferred to a candidate that can."""
@@ -896,6 +981,8 @@ class Run:
         sc = search.score(db, toks, lengths=cut)
         vals = rank_values(sc, self.a.rerank).cpu()
         vals = torch.where(cut.cpu() < lens.cpu(), torch.full_like(vals, float("-inf")), vals)
+        if live is not None:                                 # (--without-replacement: a void slot is never preferred)
+            vals = torch.where(live.cpu(), vals, torch.full_like(vals, float("-inf")))
         pick = torch.argmax(vals, dim=1).tolist()
         best = [toks[k, j, :int(lens[k, j])].tolist() for k, j in enumerate(pick)]
         return best, [[v if v != float("-inf") else None for v in row] for row in vals.tolist()]
