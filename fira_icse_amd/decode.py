@@ -305,6 +305,34 @@ class _Loop:
 
 
 class Searcher:
+    """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many`` and ``beam`` take three options that edit the
+    step's distribution before a word is chosen (``sample_distinct`` takes the first two); ``_edit`` is the one place that
+    issues their kernels, in the order merge, prefix, constraints.  Each is off by default, and off -- None, False, an inactive
+    value, an all-empty prefix -- means the calls, keys, buffers and graphs of a search without it.
+
+    ``constraints``: a ``Constraints`` value.  ``fira_constrain_dist`` zeroes the blocked words' entries of every row between
+    the step and the selection; nothing is renormalised (greedy: probability = the product of the UNnormalised entries taken).
+    The value joins the state key: its scalars are baked into the captured launches.
+
+    ``merge_copies``: search over WORDS instead of entries.  ``fira_merge_dist`` folds every copy entry into the generator entry
+    of the word it resolves to, so a word is one candidate however many entries carry it: greedy takes the most probable word,
+    not the largest single entry, and the beam's slots of positive probability hold pairwise distinct word sequences.  The
+    returned probability is then the probability of the WORD SEQUENCE: the sum over every entry path that spells it -- exact,
+    because the next step depends on the resolved ids only -- and no longer the product of the entries taken.  "merge" joins the
+    state key (``_key``), so merged and unmerged searches own separate buffers and graphs.
+
+    ``prefix``: how every message begins -- a sequence of B sequences of vocabulary ids in [UNK, vocab), without <start>, at most
+    tar_len - 2 long; an empty one means no prefix for that commit.  While a hypothesis (every running row of every beam group)
+    is inside its commit's prefix, ``fira_force_dist`` zeroes every entry of the step's distribution that does not resolve to the
+    prefix word, so the search can only take that word -- through its generator entry or a copy slot -- and then continues
+    freely: each hypothesis of positive probability starts with the prefix.  The returned probability is the JOINT probability
+    of prefix and continuation (nothing is divided out; the ranking within a commit is unaffected).  ``merge_copies`` is
+    recommended with a prefix: without it the forced word's mass stays split over its entries; greedy takes the largest one
+    and the beam may spend slots on several of them, exactly as it does on unforced steps.  The state is keyed by a "prefix"
+    marker, not by the values (device buffers read when the kernels run: one capture serves every prefix).  A ``ValueError``
+    before anything is launched on a wrong count, a non-integer id, an id outside [UNK, vocab), a prefix that is too long, or --
+    with ``constraints`` -- one that holds a banned id or itself repeats an n-gram."""
+
     def __init__(self, model: TransModel, kv_bf16: bool = False, members=(), weights=None):
         """``kv_bf16``: stream a bf16 copy of the cross-attention K|V in the step loop (FIRA_DECODE_KV_BF16: half of the
         bytes a step moves; ids no longer bit-identical to the fp32 search -- off by default).
@@ -405,27 +433,52 @@ class Searcher:
             raise ValueError("constraints: expected decode.Constraints or None, got %r" % (constraints,))
         return constraints.check(self.cfg) if constraints.active else None
 
-    def _constrain(self, st, R, rows_per_commit, gen, length, best_id, best_p):
-        """fira_constrain_dist on st["dist"] with the constraints of the state ``st`` (scalars baked into a captured graph)."""
-        c = st["con"]
-        _lib.check(_lib.lib().fira_constrain_dist(_lib.cur_stream(), C.byref(self.model.dims), R, rows_per_commit, _lib.ptr(gen),
-                                                  _lib.ptr(length), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), c.no_repeat_ngram,
-                                                  c.min_length, _lib.ptr(st["banned"]), len(c.banned), _lib.ptr(st["dist"]),
-                                                  _lib.ptr(best_id), _lib.ptr(best_p)), "fira_constrain_dist")
+    def _edit(self, st, R, rows_per_commit, gen, length, best):
+        """The edit chain: the kernels that edit the step's distribution st["dist"] ([R, out_len], ``rows_per_commit`` rows per
+        commit) between the decoder step and the selection, for whatever the state ``st`` carries, in this order:
 
-    def _merge(self, st, R, rows_per_commit, best_id, best_p):
-        """fira_merge_dist on st["dist"]: every copy entry folded into the generator entry of its word."""
-        _lib.check(_lib.lib().fira_merge_dist(_lib.cur_stream(), C.byref(self.model.dims), R, rows_per_commit, _lib.ptr(st["sou"]),
-                                              _lib.ptr(st["sub"]), _lib.ptr(st["dist"]), _lib.ptr(best_id), _lib.ptr(best_p)),
-                   "fira_merge_dist")
+        merge (st["merge"]): ``fira_merge_dist`` folds every copy entry into the generator entry of the word it resolves to
+        (DESIGN.md section 6l).  Words first: a blocked word's mass then sits on its generator entry.
+        force ("prefix" in st): ``fira_force_dist`` leaves the rows still inside their commit's prefix the entries of the prefix
+        word only (section 6q); ``gen`` / ``length`` say where a row is.  The prefix is read from st["prefix"] / st["prefix_len"]
+        when the kernel runs.
+        constrain (st["con"]): ``fira_constrain_dist`` zeroes the blocked words' entries (section 6k); nothing is renormalised.
+        Its scalars are baked into a captured graph.
 
-    def _force(self, st, R, rows_per_commit, gen, length, best_id, best_p):
-        """fira_force_dist on st["dist"]: the rows still inside their commit's prefix keep the entries of the prefix word only
-        (DESIGN.md section 6q).  The prefix is read from st["prefix"] / st["prefix_len"] when the kernel runs."""
-        _lib.check(_lib.lib().fira_force_dist(_lib.cur_stream(), C.byref(self.model.dims), R, rows_per_commit, _lib.ptr(gen),
-                                              _lib.ptr(length), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["prefix"]),
-                                              _lib.ptr(st["prefix_len"]), _lib.ptr(st["dist"]), _lib.ptr(best_id),
-                                              _lib.ptr(best_p)), "fira_force_dist")
+        ``best``: (best_id, best_p) or None.  The last kernel that edits the distribution takes the arg-max of what is left: a
+        pair goes to the last call the chain makes, every other call gets NULL for both (greedy); None: NULL for all (the beam
+        family, whose selection reads the distribution itself).  This is the one place that knows the order and that rule."""
+        lib, s, dims, c = _lib.lib(), _lib.cur_stream(), C.byref(self.model.dims), st["con"]
+        sou, sub, dist = _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["dist"])
+        chain = []
+        if st.get("merge", False):
+            chain.append(("fira_merge_dist", lambda *b: lib.fira_merge_dist(s, dims, R, rows_per_commit, sou, sub, dist, *b)))
+        if "prefix" in st:
+            chain.append(("fira_force_dist", lambda *b: lib.fira_force_dist(
+                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["prefix"]),
+                _lib.ptr(st["prefix_len"]), dist, *b)))
+        if c is not None:
+            chain.append(("fira_constrain_dist", lambda *b: lib.fira_constrain_dist(
+                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, c.no_repeat_ngram, c.min_length,
+                _lib.ptr(st["banned"]), len(c.banned), dist, *b)))
+        for k, (name, call) in enumerate(chain):
+            last = best is not None and k == len(chain) - 1
+            _lib.check(call(*((_lib.ptr(best[0]), _lib.ptr(best[1])) if last else (None, None))), name)
+
+    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False):
+        """What the edit chain (``_edit``) owns in a state of R rows over B commits: ``con`` always (None: no constraint);
+        ``merge`` only when merging; the [R, out_len] distribution when an edit is active (``dist=True``: in any case, for the
+        beam family, whose selection reads it); the banned ids with constraints; the two prefix buffers with a prefix ``rows``."""
+        st = dict(con=con)
+        if merge:
+            st["merge"] = True
+        if dist or con is not None or merge or rows is not None:
+            st["dist"] = f32(R, self.cfg.out_len)
+        if con is not None:
+            st["banned"] = torch.tensor(list(con.banned) or [0], dtype=torch.int32, device=self.model.device_)
+        if rows is not None:
+            st.update(prefix=i32(B, self.cfg.tar_len), prefix_len=i32(B))
+        return st
 
     def _prefix_rows(self, prefix, B: int, con: Optional[Constraints]):
         """None for "no prefix" (None, or every sequence empty: today's launches, buffers and graphs), else the checked prefix as
@@ -477,8 +530,11 @@ class Searcher:
         return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + ((con,) if con is not None else ())
                 + ((scoring,) if scoring is not None else ()))
 
-    def _banned_buffer(self, c: Constraints):
-        return torch.tensor(list(c.banned) or [0], dtype=torch.int32, device=self.model.device_)
+    @staticmethod
+    def _sbs_key(B: int, n: int, merge: bool, con, temperature: float):
+        """The state key of ``sample_distinct``: fixed positions (the merge flag and the Constraints value or None as they are),
+        and the temperature last -- it is baked into the captured launches."""
+        return ("sbs", B, n, merge, con, temperature)
 
     def _state(self, key, db: DeviceBatch, make):
         """The static device buffers of one search loop (its captured hipGraphs live beside them), built on first use as
@@ -499,6 +555,26 @@ class Searcher:
         return dict(out=i32(R, self.cfg.tar_len), length=i32(R), prob=f32(R), alive=i32(R), tok=i32(R),
                     n_alive=i32(self.cfg.tar_len), best_id=i32(R), best_p=f32(R))
 
+    def _beam_rows(self, i32, f32, R):
+        """The per-row state of ``fira_beam_prepare`` and the selections over R rows; ``gen`` / ``length`` are ping-pong pairs."""
+        T = self.cfg.tar_len
+        return dict(gen=[i32(R, T), i32(R, T)], length=[i32(R), i32(R)], tok=i32(R), parent=i32(R), fin=i32(R), active=i32(9),
+                    done=i32(1))
+
+    def _noise(self, keys, seed, B: int):
+        """The noise inputs of ``sample`` / ``sample_distinct``: checks ``keys`` (default: the commit's row in the batch) now, before
+        anything is launched; returns (the state's entries for ``make``, ``fill(st)`` that writes keys and seed into them)."""
+        keys = torch.arange(B) if keys is None else torch.as_tensor(keys)
+        if keys.numel() != B:
+            raise ValueError("keys: %d values for a batch of %d commits" % (keys.numel(), B))
+
+        def fill(st):
+            st["key"].copy_(keys.reshape(B).to(torch.int32))
+            bits = int(seed) & 0xFFFFFFFFFFFFFFFF
+            st["seed"].fill_(bits - (1 << 64) if bits >= 1 << 63 else bits)     # the uint64 bits in an int64 tensor
+        rows = lambda i32: dict(key=i32(B), seed=torch.zeros(1, dtype=torch.int64, device=self.model.device_))
+        return rows, fill
+
     # ------------------------------------------------------------------ greedy (beam 1): no sort, no dist tensor
     def _greedy_reset(self, st):
         st["out"].zero_()
@@ -511,21 +587,15 @@ class Searcher:
 
     def _greedy_steps(self, st, ws, B, lo, hi):
         """Steps lo..hi-1 of run_model.py:225-340 at beam 1: two library calls per step (KV-cached decoder step with the
-        arg-max of the output distribution, then the hypothesis bookkeeping), no torch op, no host round trip."""
+        arg-max of the output distribution, then the hypothesis bookkeeping), no torch op, no host round trip.  A state with
+        edits (it owns ``dist``): the step writes the distribution instead and the edit chain reports the arg-max."""
         lib, s = _lib.lib(), _lib.cur_stream()
         for step in range(lo, hi):
-            con, merge, forced = st["con"], st.get("merge", False), "prefix" in st
-            if con is None and not merge and not forced:
+            if "dist" not in st:
                 self._step(ws, B, 1, step, st["tok"], None, None, st["best_id"], st["best_p"])
-            else:       # the step writes the distribution; the last kernel that edits it takes the arg-max of what is left
+            else:
                 self._step(ws, B, 1, step, st["tok"], None, st["dist"], None, None)
-                best, none = (st["best_id"], st["best_p"]), (None, None)
-                if merge:                                    # words first: a blocked word's mass then sits on its generator entry
-                    self._merge(st, B, 1, *(best if con is None and not forced else none))
-                if forced:                                   # the prefix word's entries only, while the row is inside its prefix
-                    self._force(st, B, 1, st["out"], st["length"], *(best if con is None else none))
-                if con is not None:
-                    self._constrain(st, B, 1, st["out"], st["length"], st["best_id"], st["best_p"])
+                self._edit(st, B, 1, st["out"], st["length"], (st["best_id"], st["best_p"]))
             _lib.check(lib.fira_greedy_advance(s, C.byref(self.model.dims), B, step, _lib.ptr(st["best_id"]),
                                                _lib.ptr(st["best_p"]), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]),
                                                _lib.ptr(st["out"]), _lib.ptr(st["length"]), _lib.ptr(st["prob"]),
@@ -534,27 +604,14 @@ class Searcher:
 
     def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
                      merge_copies: bool = False, prefix=None) -> _Loop:
-        """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  With
-        active constraints the state (and so its graphs: the scalars are baked into the captured launches) is keyed by their
-        value and also owns the [B, out_len] distribution the constraint kernel edits and the banned ids.  ``merge_copies``
-        is part of the key too (("greedy", B, "merge"), ("greedy", B, "merge", constraints)) and brings the distribution.  An
-        active ``prefix`` adds the "prefix" marker to the key, and the distribution and the two prefix buffers to the state."""
+        """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  The
+        active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, constraints]), and so own their graphs)
+        and add what ``_edit_state`` lists to the state -- the [B, out_len] distribution with any of them."""
         B = db.B
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
-
-        def make(i32, f32):
-            st = dict(self._hypothesis_rows(i32, f32, B), con=con)
-            if merge:
-                st["merge"] = True
-            if con is not None or merge or rows is not None:
-                st["dist"] = f32(B, self.cfg.out_len)
-            if con is not None:
-                st["banned"] = self._banned_buffer(con)
-            if rows is not None:
-                st.update(prefix=i32(B, self.cfg.tar_len), prefix_len=i32(B))
-            return st
+        make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **self._edit_state(i32, f32, B, B, con, merge, rows))
         loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
         if rows is not None:
@@ -574,27 +631,9 @@ class Searcher:
     @torch.no_grad()
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
                merge_copies: bool = False, prefix=None):
-        """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``: a ``Constraints``
-        value; the step then writes its distribution, ``fira_constrain_dist`` zeroes the blocked words' entries and takes the
-        arg-max of the rest (probability = the product of the UNnormalised entries taken); None or inactive: today's loop.
-
-        ``merge_copies``: search over WORDS instead of entries.  The step writes its distribution and ``fira_merge_dist`` folds
-        every copy entry into the generator entry of the word it resolves to, so the arg-max is the most probable word, not the
-        largest single entry (with constraints: step, merge, then the constraint kernel, which reports the arg-max).  The
-        returned probability is then the probability of the WORD SEQUENCE: the sum over every entry path that spells it --
-        exact, because the next step depends on the resolved ids only -- and no longer the product of the entries taken.
-        False: today's loop, keys, buffers and graphs.
-
-        ``prefix``: how every message begins -- a sequence of B sequences of vocabulary ids in [UNK, vocab), without <start>, at
-        most tar_len - 2 long; an empty one means no prefix for that commit.  While a hypothesis is inside its commit's prefix,
-        ``fira_force_dist`` (after the merge, before the constraints) zeroes every entry of the step's distribution that does not
-        resolve to the prefix word, so the search can only take that word -- through its generator entry or a copy slot -- and then
-        continues freely.  The returned probability is the JOINT probability of prefix and continuation (nothing is divided
-        out; the ranking within a commit is unaffected).  ``merge_copies`` is recommended with a prefix: without it the forced
-        word's mass stays split over its entries and the search takes the largest one.  The state is keyed by a "prefix" marker,
-        not by the values (device buffers read when the kernels run: one capture serves every prefix).  A ``ValueError`` before
-        anything is launched on a wrong count, a non-integer id, an id outside [UNK, vocab), a prefix that is too long, or --
-        with ``constraints`` -- one that holds a banned id or itself repeats an n-gram.  None or all empty: today's loop.
+        """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``, ``merge_copies``
+        and ``prefix`` are the class's options: with any of them the step writes its distribution instead of taking its fused
+        arg-max, and the last kernel of the edit chain (``_edit``) takes the arg-max of what is left.
 
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
@@ -708,16 +747,11 @@ class Searcher:
         self._no_ensemble("sample")                           # raises before anything is launched
         B, T = db.B, self.cfg.tar_len
         R = B * n
-        keys = torch.arange(B) if keys is None else torch.as_tensor(keys)
-        if keys.numel() != B:                                 # raises before anything is launched
-            raise ValueError("keys: %d values for a batch of %d commits" % (keys.numel(), B))
-        make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), key=i32(B),
-                                     seed=torch.zeros(1, dtype=torch.int64, device=self.model.device_))
+        noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched
+        make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), **noise_rows(i32))
         loop = _Loop(self, db, n, ("sample", B, n, float(temperature), int(top_k), float(top_p)), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
-        st["key"].copy_(keys.reshape(B).to(torch.int32))
-        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)     # the uint64 bits in an int64 tensor
+        fill_noise(st)
         loop.start(lambda lo, hi: self._sample_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p),
                    lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
@@ -910,22 +944,23 @@ class Searcher:
         return torch.argmax(rank_values(scores, by), dim=1).tolist()
 
     # ------------------------------------------------------------------ beam search with the reference's semantics
-    def _beam_reset(self, st, B, beam):
-        for k in ("gen", "length", "prob"):
+    def _family_reset(self, st, values, void):
+        """The reset of the beam family (``beam``, ``sample_distinct``): both ping-pong buffers of ``gen`` / ``length`` empty, then
+        <start> at length 1 in the first, the per-slot ``values`` at ``void`` and ``done`` clear; the caller seeds its live slots."""
+        for k in ("gen", "length"):
             st[k][0].zero_()
             st[k][1].zero_()
         st["gen"][0][:, 0] = START
         st["length"][0].fill_(1)
-        sc = st.get("scoring")
-        if sc is None:
-            st["prob"][0].view(B, beam)[:, 0] = 1.0
-        else:
-            st["prob"][0].view(B, beam)[:, ::beam // sc.groups] = 1.0       # the first slot of every group
+        for k in values:
+            st[k][0].fill_(void)
+            st[k][1].fill_(void)
         st["done"].zero_()
 
-    def _beam_steps(self, st, ws, B, beam, lo, hi):
-        """Steps lo..hi-1 of run_model.py:225-340: prepare -> KV-cached decoder step -> (merge, then the prefix, then constraints,
-        when the state has them) -> select, all on the device."""
+    def _family_steps(self, st, ws, B, beam, lo, hi, select):
+        """Steps lo..hi-1 of the beam family: prepare -> KV-cached decoder step (the members' steps and the mix, for an
+        ensemble) -> edit chain -> ``select(lib, s, step, cur, nxt)``, the caller's selection call from the ``cur`` ping-pong
+        buffers into the ``nxt`` ones; all on the device."""
         lib, s, T = _lib.lib(), _lib.cur_stream(), self.cfg.tar_len
         for step in range(lo, hi):
             cur, nxt = step & 1, (step + 1) & 1
@@ -933,40 +968,47 @@ class Searcher:
                                              _lib.ptr(st["tok"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]),
                                              _lib.ptr(st["done"])), "fira_beam_prepare")
             self._step(ws, B, beam, step, st["tok"], st["parent"] if step > 0 else None, st["dist"], None, None)
-            if st.get("merge", False):
-                self._merge(st, B * beam, beam, None, None)
-            if "prefix" in st:
-                self._force(st, B * beam, beam, st["gen"][cur], st["length"][cur], None, None)
-            if st["con"] is not None:
-                self._constrain(st, B * beam, beam, st["gen"][cur], st["length"][cur], None, None)
+            self._edit(st, B * beam, beam, st["gen"][cur], st["length"][cur], None)
+            select(lib, s, step, cur, nxt)
+
+    def _family_result(self, loop, B, beam, values):
+        """(hypotheses [B,beam,T] int64, lengths [B,beam], the per-slot ``values`` [B,beam]) of a finished beam-family loop."""
+        st, cur = loop.st, loop.hi & 1                       # the ping-pong buffer the last step run wrote
+        return (st["gen"][cur].view(B, beam, self.cfg.tar_len).long(), st["length"][cur].view(B, beam).long()) + tuple(
+            st[k][cur].view(B, beam).clone() for k in values)
+
+    def _beam_reset(self, st, B, beam):
+        self._family_reset(st, ("prob",), 0.0)
+        sc = st.get("scoring")                               # the first slot of the beam, or of every group
+        st["prob"][0].view(B, beam)[:, ::beam if sc is None else beam // sc.groups] = 1.0
+
+    def _beam_steps(self, st, ws, B, beam, lo, hi):
+        """Steps lo..hi-1 of run_model.py:225-340 (``_family_steps``) with fira_beam_select, or under a BeamScoring
+        fira_beam_select_scored, as the selection."""
+        sc, dims = st.get("scoring"), C.byref(self.model.dims)
+
+        def select(lib, s, step, cur, nxt):
             state = (_lib.ptr(st["dist"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]), _lib.ptr(st["done"]),
                      _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]),
                      _lib.ptr(st["prob"][cur]), _lib.ptr(st["gen"][nxt]), _lib.ptr(st["length"][nxt]),
                      _lib.ptr(st["prob"][nxt]), _lib.ptr(st["parent"]))
-            sc = st.get("scoring")
             if sc is None:
-                _lib.check(lib.fira_beam_select(s, C.byref(self.model.dims), B, beam, *state), "fira_beam_select")
+                _lib.check(lib.fira_beam_select(s, dims, B, beam, *state), "fira_beam_select")
             else:
-                _lib.check(lib.fira_beam_select_scored(s, C.byref(self.model.dims), B, beam, *state, _lib.ptr(st["inv_lp"]),
-                                                       sc.groups, sc.diversity, _lib.ptr(st["key"])), "fira_beam_select_scored")
+                _lib.check(lib.fira_beam_select_scored(s, dims, B, beam, *state, _lib.ptr(st["inv_lp"]), sc.groups,
+                                                       sc.diversity, _lib.ptr(st["key"])), "fira_beam_select_scored")
+        self._family_steps(st, ws, B, beam, lo, hi, select)
 
     @torch.no_grad()
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
              scoring: Optional[BeamScoring] = None, prefix=None):
-        """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``: a ``Constraints``
-        value; one ``fira_constrain_dist`` call per step then zeroes the blocked words' entries of every row between the step
-        and the selection (nothing is renormalised); None or inactive: today's three calls per step and today's graphs.
-
-        ``merge_copies``: search over WORDS instead of entries.  One ``fira_merge_dist`` call per step, between the step and
-        the constraints / the selection, folds every copy entry into the generator entry of the word it resolves to: a word is
-        one candidate however many entries carry it, so the slots of positive probability hold pairwise distinct word
-        sequences.  The returned probability is then the probability of the WORD SEQUENCE: the sum over every entry path that
-        spells it -- exact, because the next step depends on the resolved ids only -- and no longer the product of the entries
-        taken.  The state is keyed ("beam", B, beam, "merge"[, constraints]); False: today's calls, keys, buffers and graphs.
+        """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``
+        and ``prefix`` are the class's options, one library call per step each, between the step and the selection (``_edit``);
+        the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, constraints][, scoring]) (``_key``).
 
         ``scoring``: a ``BeamScoring`` value.  ``fira_beam_select_scored`` then takes the place of ``fira_beam_select`` (after
-        merge and constraints): hypotheses are ranked by the length-normalised key ln(prob) / ((5 + m) / 6)^alpha instead of
+        the edit chain): hypotheses are ranked by the length-normalised key ln(prob) / ((5 + m) / 6)^alpha instead of
         the raw probability, within ``groups`` beam groups that a ``diversity`` penalty per repeated word keeps apart.  The
         call then returns FOUR tensors, (hypotheses, lengths, probabilities, keys [B,beam]) -- the raw probability and the
         unpenalised key of every slot, -inf where the probability is 0 -- and ``best(gen, length, key)`` picks by key.  The
@@ -974,18 +1016,9 @@ class Searcher:
         buffer, and its reset seeds the first slot of every group.  None or an inactive value: today's key, buffers,
         launches, graphs and three tensors.  A beam of 1 with ``scoring`` given is a ``ValueError``.
 
-        ``prefix``: how every message begins, as for ``greedy``: B sequences of vocabulary ids without <start> (empty: none for
-        that commit).  One ``fira_force_dist`` call per step, after the merge and before the constraints, leaves a row that is
-        still inside its commit's prefix the entries of the prefix word only -- every running row of every group -- so each
-        hypothesis of positive probability starts with the prefix.  The returned probability is the JOINT probability of prefix
-        and continuation (nothing is divided out; the ranking within a commit is unaffected).  Without ``merge_copies`` the
-        beam may spend slots on several entries of the same forced word, exactly as it does on unforced steps: ``merge_copies``
-        is recommended with a prefix.  The key gains a "prefix" marker, not the values; the checks and their ``ValueError`` are
-        those of ``greedy``.  None or all empty: today's calls, keys, buffers and graphs.
-
-        Per step: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library calls, no torch
-        op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam) shape, and
-        the ``done`` latch is read back between chunks (run_model.py:276-279)."""
+        Per step, with every option off: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library
+        calls, no torch op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam)
+        shape, and the ``done`` latch is read back between chunks (run_model.py:276-279)."""
         B, T = db.B, self.cfg.tar_len
         BR = B * beam
         con = self._active(constraints)                      # raises before anything is launched
@@ -997,14 +1030,8 @@ class Searcher:
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
 
         def make(i32, f32):
-            st = dict(gen=[i32(BR, T), i32(BR, T)], length=[i32(BR), i32(BR)], prob=[f32(BR), f32(BR)], tok=i32(BR),
-                      parent=i32(BR), fin=i32(BR), active=i32(9), done=i32(1), dist=f32(BR, self.cfg.out_len), con=con)
-            if merge:
-                st["merge"] = True
-            if con is not None:
-                st["banned"] = self._banned_buffer(con)
-            if rows is not None:
-                st.update(prefix=i32(B, T), prefix_len=i32(B))
+            st = dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
+                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True))
             if scoring is not None:
                 st.update(scoring=scoring, key=f32(BR),
                           inv_lp=torch.tensor(scoring.inv_lp(T), dtype=torch.float64).to(torch.float32).to(self.model.device_))
@@ -1016,44 +1043,25 @@ class Searcher:
             self._fill_prefix(st, rows)
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
-        cur = loop.hi & 1                                    # the ping-pong buffer the last step run wrote
-        res = (st["gen"][cur].view(B, beam, T).long(), st["length"][cur].view(B, beam).long(),
-               st["prob"][cur].view(B, beam).clone())
+        res = self._family_result(loop, B, beam, ("prob",))
         return res if scoring is None else res + (st["key"].view(B, beam).clone(),)
 
     # ------------------------------------------------------------------ stochastic beam search: n samples without replacement
     def _sbs_reset(self, st, B, n):
-        for k in ("gen", "length"):
-            st[k][0].zero_()
-            st[k][1].zero_()
-        st["gen"][0][:, 0] = START
-        st["length"][0].fill_(1)
+        self._family_reset(st, ("phi", "G", "logp"), float("-inf"))
         for k in ("phi", "G", "logp"):
-            st[k][0].fill_(float("-inf"))
-            st[k][1].fill_(float("-inf"))
             st[k][0].view(B, n)[:, 0] = 0.0                   # slot 0 of every commit is the empty message; the others are void
-        st["done"].zero_()
 
     def _sbs_steps(self, st, ws, B, n, lo, hi, temperature):
-        """Steps lo..hi-1 of the beam's loop with fira_beam_select_gumbel as the selection: prepare -> KV-cached decoder step
-        (the members' steps and the mix, for an ensemble) -> merge -> constraints -> select, all on the device."""
-        lib, s, T = _lib.lib(), _lib.cur_stream(), self.cfg.tar_len
-        for step in range(lo, hi):
-            cur, nxt = step & 1, (step + 1) & 1
-            _lib.check(lib.fira_beam_prepare(s, B, n, T, step, _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]),
-                                             _lib.ptr(st["tok"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]),
-                                             _lib.ptr(st["done"])), "fira_beam_prepare")
-            self._step(ws, B, n, step, st["tok"], st["parent"] if step > 0 else None, st["dist"], None, None)
-            if st.get("merge", False):
-                self._merge(st, B * n, n, None, None)
-            if st["con"] is not None:
-                self._constrain(st, B * n, n, st["gen"][cur], st["length"][cur], None, None)
+        """Steps lo..hi-1 of the beam's loop (``_family_steps``) with fira_beam_select_gumbel as the selection."""
+        def select(lib, s, step, cur, nxt):
             _lib.check(lib.fira_beam_select_gumbel(
                 s, C.byref(self.model.dims), B, n, step, float(temperature), _lib.ptr(st["dist"]), _lib.ptr(st["fin"]),
                 _lib.ptr(st["done"]), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["key"]), _lib.ptr(st["seed"]),
                 _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]), _lib.ptr(st["phi"][cur]), _lib.ptr(st["G"][cur]),
                 _lib.ptr(st["logp"][cur]), _lib.ptr(st["gen"][nxt]), _lib.ptr(st["length"][nxt]), _lib.ptr(st["phi"][nxt]),
                 _lib.ptr(st["G"][nxt]), _lib.ptr(st["logp"][nxt]), _lib.ptr(st["parent"])), "fira_beam_select_gumbel")
+        self._family_steps(st, ws, B, n, lo, hi, select)
 
     @torch.no_grad()
     def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
@@ -1075,15 +1083,13 @@ class Searcher:
         ``sample(db, 1, ...)``'s, bit for bit.  ``merge_copies`` (default on): sample WORDS -- the hypotheses of finite key are
         then pairwise distinct word sequences.  Off, they are distinct ENTRY paths, and one message may appear twice (spelled
         once through the generator and once through a copy slot).  ``constraints`` as for ``beam``; an ensemble (``members=``)
-        samples from the mix.  The loop is the beam's (``_Loop``): prepare, step, merge, constraints, selection, captured into
+        samples from the mix.  The loop is the beam's (``_family_steps``): prepare, step, edit chain, selection, captured into
         hipGraphs of ``chunk`` steps; the state is keyed ("sbs", B, n, merge, constraints, temperature) -- the temperature
         is baked into the captured launches; the seed and the keys are device values: one capture serves them all."""
-        B, T = db.B, self.cfg.tar_len
+        B = db.B
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
-        keys = torch.arange(B) if keys is None else torch.as_tensor(keys)
-        if keys.numel() != B:                                 # raises before anything is launched
-            raise ValueError("keys: %d values for a batch of %d commits" % (keys.numel(), B))
+        noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched
         temperature = float(temperature)
         # the kernel's own limits, before the encoder pass or any other launch
         if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 8:
@@ -1091,27 +1097,15 @@ class Searcher:
         if not 0.0 < temperature < float("inf"):              # (also refuses nan)
             raise ValueError("sample_distinct: temperature = %r must be finite and > 0" % (temperature,))
         BR = B * n
-
-        def make(i32, f32):
-            st = dict(gen=[i32(BR, T), i32(BR, T)], length=[i32(BR), i32(BR)], phi=[f32(BR), f32(BR)], G=[f32(BR), f32(BR)],
-                      logp=[f32(BR), f32(BR)], tok=i32(BR), parent=i32(BR), fin=i32(BR), active=i32(9), done=i32(1),
-                      dist=f32(BR, self.cfg.out_len), con=con, key=i32(B),
-                      seed=torch.zeros(1, dtype=torch.int64, device=self.model.device_))
-            if merge:
-                st["merge"] = True
-            if con is not None:
-                st["banned"] = self._banned_buffer(con)
-            return st
-        loop = _Loop(self, db, n, ("sbs", B, n, merge, con, temperature), make, chunk, use_graphs)
+        make = lambda i32, f32: dict(self._beam_rows(i32, f32, BR), phi=[f32(BR), f32(BR)], G=[f32(BR), f32(BR)],
+                                     logp=[f32(BR), f32(BR)], **noise_rows(i32),
+                                     **self._edit_state(i32, f32, BR, B, con, merge, None, dist=True))
+        loop = _Loop(self, db, n, self._sbs_key(B, n, merge, con, temperature), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
-        st["key"].copy_(keys.reshape(B).to(torch.int32))
-        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)     # the uint64 bits in an int64 tensor
+        fill_noise(st)
         loop.start(lambda lo, hi: self._sbs_steps(st, ws, B, n, lo, hi, temperature), lambda: self._sbs_reset(st, B, n),
                    lambda hi: bool(st["done"].item())).run()
-        cur = loop.hi & 1                                    # the ping-pong buffer the last step run wrote
-        return (st["gen"][cur].view(B, n, T).long(), st["length"][cur].view(B, n).long(), st["logp"][cur].view(B, n).clone(),
-                st["phi"][cur].view(B, n).clone(), st["G"][cur].view(B, n).clone())
+        return self._family_result(loop, B, n, ("logp", "phi", "G"))
 
     def best(self, gen, length, prob) -> List[List[int]]:
         """argmax-probability hypothesis per item, first on ties (run_model.py:351-352)."""
