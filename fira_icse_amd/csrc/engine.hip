@@ -14,6 +14,7 @@
 #include "engine.h"
 #include <hip/hip_ext.h>
 #include "epilogue.h"
+#include "decode_row.h"
 #include <stdlib.h>
 #include <map>
 #include <mutex>
@@ -2204,6 +2205,9 @@ int fira_decode_begin_ex(void* stream, const fira_dims* d, const fira_batch* bat
                          size_t workspace_bytes, int n_beam, int flags) {
     const Layout* L = get_layout(d);
     if (!L) return 1;
+    // the step loop's distribution, selection and bookkeeping kernels hold a row in registers (decode_row.h): a geometry they
+    // refuse is refused here, ahead of the encoder pass, not at the first step -- possibly inside a graph capture
+    TRY(require_row_geometry(d, 1, 0, nullptr, nullptr, "fira_decode_begin"));
     TRY(check_batch(batch));
     FIRA_REQUIRE(params && workspace && n_beam >= 1, "bad argument");
     FIRA_REQUIRE((flags & ~FIRA_DECODE_KV_BF16) == 0, "fira_decode_begin_ex: unknown flags %d", flags);

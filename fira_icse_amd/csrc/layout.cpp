@@ -253,11 +253,25 @@ const Layout* get_layout(const fira_dims* d) {
         set_err("kernels are specialised for d_model=256, head width 32 (got d_model=%d n_head=%d)", d->d_model, d->n_head);
         return nullptr;
     }
-    if (d->tar_len < 2 || d->tar_len > 32 || d->sou_len + d->sub_len > 384 || d->sou_len < 1 || d->sub_len < 0 ||
-        d->ast_len < 0 || d->n_layer < 1 || d->n_layer > 16 || d->vocab < 4 || d->d_ff % 64 != 0) {
-        set_err("unsupported geometry (tar_len 2..32, sou_len+sub_len <= 384, d_ff %% 64 == 0)");
-        return nullptr;
-    }
+    // The supported box (INTEGRATION.md "Supported geometry"; tests/test_geometry.py pins every bound, tests/test_geometry_gpu.py
+    // runs the engine at its corners).  One message per bound, naming the value and the limit.
+#define FIRA_GEOMETRY(cond, ...) \
+    do { if (!(cond)) { set_err("unsupported geometry: " __VA_ARGS__); return nullptr; } } while (0)
+    FIRA_GEOMETRY(d->tar_len >= 2 && d->tar_len <= 32, "tar_len = %d outside 2..32 (one query tile)", d->tar_len);
+    FIRA_GEOMETRY(d->sou_len >= 1, "sou_len = %d below 1", d->sou_len);
+    FIRA_GEOMETRY(d->sub_len >= 0, "sub_len = %d below 0", d->sub_len);
+    FIRA_GEOMETRY(d->sou_len + d->sub_len <= 384, "sou_len + sub_len = %d above 384 memory rows (twelve key tiles)",
+                  d->sou_len + d->sub_len);
+    // No kernel is sized by the graph width: the encoder runs on the compact list of computed nodes.  What the width does
+    // bound is per batch, not per geometry -- node ids b * N + local are int32 and the row kernels address a [B * N, 256] fp32
+    // buffer with 32-bit byte offsets, so B * N stays below 2^21 rows (their own "2 GiB" checks refuse beyond).  The gate's
+    // cap is lower and deliberate: 400 AST nodes, N = 784, is the widest graph that is compared with the oracle.
+    FIRA_GEOMETRY(d->ast_len >= 0 && d->ast_len <= 400, "ast_len = %d outside 0..400", d->ast_len);
+    FIRA_GEOMETRY(d->n_layer >= 1 && d->n_layer <= 16, "n_layer = %d outside 1..16", d->n_layer);
+    FIRA_GEOMETRY(d->vocab >= 4, "vocab = %d below 4 (<pad>, <eos>, <start>, <unkm>)", d->vocab);
+    FIRA_GEOMETRY(d->ast_vocab >= 1, "ast_vocab = %d below 1", d->ast_vocab);
+    FIRA_GEOMETRY(d->d_ff >= 64 && d->d_ff % 64 == 0, "d_ff = %d is not a positive multiple of 64", d->d_ff);
+#undef FIRA_GEOMETRY
     static std::mutex mu;
     static std::map<std::string, Layout*> cache;
     std::lock_guard<std::mutex> g(mu);

@@ -545,9 +545,13 @@ class Searcher:
             cfg, dev = self.cfg, self.model.device_
             i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
             f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-            st = self._ws[key] = dict(make(i32, f32), sou=i32(db.B, cfg.sou_len), sub=i32(db.B, cfg.sub_token_len), graphs=None)
+            # (a geometry without sub-token slots: one zero column, so that the kernels never get a null pointer -- no entry of
+            #  the distribution resolves to a sub-token then, and the row stride they use is the geometry's, 0)
+            st = self._ws[key] = dict(make(i32, f32), sou=i32(db.B, cfg.sou_len), sub=i32(db.B, max(cfg.sub_token_len, 1)),
+                                      graphs=None)
         st["sou"].copy_(db.sou)
-        st["sub"].copy_(db.sub_token)
+        if self.cfg.sub_token_len:
+            st["sub"].copy_(db.sub_token)
         return st
 
     def _hypothesis_rows(self, i32, f32, R):

@@ -210,9 +210,10 @@ def beam_decode(P: Params, cfg, sou, mark, ast_change, edge, sub_token, beam: in
                                    dtype=torch.float32)
             allv = torch.cat(blocks + [carried], -1)
             top_p, top_i = torch.sort(allv, descending=True, dim=-1)
+            next_p = top_p[:, beam].clone()                   # the best candidate that was NOT taken
             top_p, top_i = top_p[:, :beam], top_i[:, :beam]
-            if trace is not None:          # raw (pre copy-resolution) choices and their scores, per step
-                trace.append((top_i.clone(), top_p.clone(), list(active)))
+            if trace is not None:          # raw (pre copy-resolution) choices, their scores and the runner-up's, per step
+                trace.append((top_i.clone(), top_p.clone(), list(active), next_p))
             new_hyp = []
             for i in range(B):
                 row = []
