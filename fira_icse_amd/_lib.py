@@ -192,6 +192,7 @@ SIGNATURES = {
     "fira_beam_select": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_beam_select_scored": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P]),
     "fira_beam_select_gumbel": (_I, [_P, _DP, _I, _I, _I, _F] + [_P] * 18),
+    "fira_beam_select_required": (_I, [_P, _DP, _I, _I] + [_P] * 16),
     "fira_greedy_advance": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_decode_step": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _P, _P]),
     "fira_decode_step_sample": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _F, _I, _F, _P, _P, _P, _I]),

@@ -181,6 +181,7 @@ class Scores(dict):
 
 
 MAX_MODELS = 8                                   # fira_mix_dist: 2 <= n_members <= 8
+MAX_REQUIRED = 4                                 # fira_beam_select_required: required[B, 4]
 
 
 def ensemble_weights(weights, n_models: int):
@@ -523,12 +524,63 @@ class Searcher:
         st["prefix_len"].copy_(torch.tensor([len(row) for row in rows], dtype=torch.int32))
 
     @staticmethod
-    def _key(base, merge: bool, con, scoring=None, forced: bool = False):
+    def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
         so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
-        marker only: the prefix values live in device buffers); an active BeamScoring value comes last."""
-        return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + ((con,) if con is not None else ())
-                + ((scoring,) if scoring is not None else ()))
+        marker only: the prefix values live in device buffers), then "require" for a search with required words (a marker
+        too); an active BeamScoring value comes last."""
+        return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + (("require",) if require else ())
+                + ((con,) if con is not None else ()) + ((scoring,) if scoring is not None else ()))
+
+    def _required_rows(self, require, B: int, beam: int, con: Optional[Constraints], scoring):
+        """None for "no required words" (None, or every sequence empty: today's launches, buffers and graphs), else the checked
+        words as B lists of vocabulary ids.  Raises ``ValueError`` naming the commit and the reason; nothing is launched before."""
+        if require is None:
+            return None
+        cfg = self.cfg
+        try:
+            rows = [list(p) for p in require]
+        except TypeError:
+            raise ValueError("require: expected one sequence of vocabulary ids per commit, got %r" % (require,)) from None
+        if len(rows) != B:
+            raise ValueError("require: %d sequences for a batch of %d commits" % (len(rows), B))
+        for b, row in enumerate(rows):
+            for w in row:
+                if isinstance(w, bool) or not isinstance(w, numbers.Integral):
+                    raise ValueError("require: commit %d: id %r is not an integer" % (b, w))
+                if not UNK < w < cfg.vocab_size:
+                    raise ValueError("require: commit %d: id %d outside (%d, %d) (<pad>, <eos>, <start> and <unkm> cannot be "
+                                     "required)" % (b, w, UNK, cfg.vocab_size))
+            rows[b] = row = [int(w) for w in row]
+            if len(set(row)) != len(row):
+                raise ValueError("require: commit %d: id %d is listed twice" % (b, next(w for w in row if row.count(w) > 1)))
+            if len(row) > MAX_REQUIRED:
+                raise ValueError("require: commit %d: %d words, more than %d" % (b, len(row), MAX_REQUIRED))
+        if not any(rows):
+            return None
+        if beam < 2:
+            raise ValueError("require: beam = %d, but required words need a beam of at least 2" % beam)
+        for b, row in enumerate(rows):
+            if beam < len(row) + 1:
+                raise ValueError("require: commit %d: %d words need a beam of at least %d (one bank per count of words met), "
+                                 "beam = %d" % (b, len(row), len(row) + 1, beam))
+            if len(row) > cfg.tar_len - 2:
+                raise ValueError("require: commit %d: %d words, more than tar_len - 2 = %d" % (b, len(row), cfg.tar_len - 2))
+            if con is not None:
+                hit = sorted(set(row) & set(con.banned))
+                if hit:
+                    raise ValueError("require: commit %d: id %d is banned by the constraints" % (b, hit[0]))
+        if scoring is not None:
+            raise ValueError("require: required words do not combine with an active scoring (the banks rank by raw probability)")
+        return rows
+
+    def _fill_required(self, st, rows):
+        """The checked words into the state's device buffers (every call, like the prefix buffers)."""
+        host = torch.zeros((len(rows), MAX_REQUIRED), dtype=torch.int32)
+        for b, row in enumerate(rows):
+            host[b, :len(row)] = torch.tensor(row, dtype=torch.int32)
+        st["required"].copy_(host)
+        st["n_required"].copy_(torch.tensor([len(row) for row in rows], dtype=torch.int32))
 
     @staticmethod
     def _sbs_key(B: int, n: int, merge: bool, con, temperature: float):
@@ -987,16 +1039,20 @@ class Searcher:
         st["prob"][0].view(B, beam)[:, ::beam if sc is None else beam // sc.groups] = 1.0
 
     def _beam_steps(self, st, ws, B, beam, lo, hi):
-        """Steps lo..hi-1 of run_model.py:225-340 (``_family_steps``) with fira_beam_select, or under a BeamScoring
-        fira_beam_select_scored, as the selection."""
-        sc, dims = st.get("scoring"), C.byref(self.model.dims)
+        """Steps lo..hi-1 of run_model.py:225-340 (``_family_steps``) with fira_beam_select, under a BeamScoring
+        fira_beam_select_scored, or with required words fira_beam_select_required, as the selection."""
+        sc, dims, req = st.get("scoring"), C.byref(self.model.dims), "required" in st
 
         def select(lib, s, step, cur, nxt):
             state = (_lib.ptr(st["dist"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]), _lib.ptr(st["done"]),
                      _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]),
                      _lib.ptr(st["prob"][cur]), _lib.ptr(st["gen"][nxt]), _lib.ptr(st["length"][nxt]),
                      _lib.ptr(st["prob"][nxt]), _lib.ptr(st["parent"]))
-            if sc is None:
+            if req:
+                _lib.check(lib.fira_beam_select_required(s, dims, B, beam, *state, _lib.ptr(st["required"]),
+                                                         _lib.ptr(st["n_required"]), _lib.ptr(st["met"])),
+                           "fira_beam_select_required")
+            elif sc is None:
                 _lib.check(lib.fira_beam_select(s, dims, B, beam, *state), "fira_beam_select")
             else:
                 _lib.check(lib.fira_beam_select_scored(s, dims, B, beam, *state, _lib.ptr(st["inv_lp"]), sc.groups,
@@ -1006,10 +1062,10 @@ class Searcher:
     @torch.no_grad()
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
-             scoring: Optional[BeamScoring] = None, prefix=None):
+             scoring: Optional[BeamScoring] = None, prefix=None, require=None):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``
         and ``prefix`` are the class's options, one library call per step each, between the step and the selection (``_edit``);
-        the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, constraints][, scoring]) (``_key``).
+        the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, "require"][, constraints][, scoring]) (``_key``).
 
         ``scoring``: a ``BeamScoring`` value.  ``fira_beam_select_scored`` then takes the place of ``fira_beam_select`` (after
         the edit chain): hypotheses are ranked by the length-normalised key ln(prob) / ((5 + m) / 6)^alpha instead of
@@ -1019,6 +1075,20 @@ class Searcher:
         value joins the state key (the scalars are baked into captured graphs); the state owns the inv_lp table and the key
         buffer, and its reset seeds the first slot of every group.  None or an inactive value: today's key, buffers,
         launches, graphs and three tensors.  A beam of 1 with ``scoring`` given is a ``ValueError``.
+
+        ``require``: the words every message must contain -- B sequences of at most 4 distinct vocabulary ids in (UNK, vocab);
+        an empty one means none for that commit.  ``fira_beam_select_required`` then takes the place of ``fira_beam_select``
+        (DESIGN.md section 6v): lexically constrained decoding with dynamic beam allocation.  The beam is divided into banks by
+        the number of required words a hypothesis holds, every bank keeps slots, and no message ends before it holds all its
+        words.  A word counts through its generator entry or a copy slot that carries it; prefix words count as met;
+        ``merge_copies`` is recommended.  The call then returns FOUR tensors, (hypotheses, lengths, probabilities,
+        met [B,beam]) -- met is the number of required words a slot's hypothesis holds -- and ``best_required`` picks the
+        message.  The state is keyed by a "require" marker, not by the words (device buffers, filled on every call: one capture
+        serves every word list).  A commit without words gets the plain ``beam`` result bit for bit.  None or every sequence
+        empty: today's key, buffers, launches, graphs and three tensors.  A ``ValueError`` before anything is launched on a
+        wrong count, a non-integer id, an id outside (UNK, vocab), a duplicate, more than 4 words, ``beam < 2``,
+        ``beam < len(words) + 1`` (a bank per count), more than tar_len - 2 words, a word the ``constraints`` ban, or an
+        active ``scoring``.
 
         Per step, with every option off: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library
         calls, no torch op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam)
@@ -1032,22 +1102,30 @@ class Searcher:
                 raise ValueError("scoring: expected decode.BeamScoring or None, got %r" % (scoring,))
             scoring = scoring.check(beam) if scoring.active() or beam < 2 else None
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
+        words = self._required_rows(require, B, beam, con, scoring)   # likewise
 
         def make(i32, f32):
             st = dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
                       **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True))
+            if words is not None:
+                st.update(required=i32(B, MAX_REQUIRED), n_required=i32(B), met=i32(BR))
             if scoring is not None:
                 st.update(scoring=scoring, key=f32(BR),
                           inv_lp=torch.tensor(scoring.inv_lp(T), dtype=torch.float64).to(torch.float32).to(self.model.device_))
             return st
         # (a captured graph bakes the constraint scalars, the merge launch and the scoring scalars: they are part of the key)
-        loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring, rows is not None), make, chunk, use_graphs)
+        loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring, rows is not None,
+                                               **({} if words is None else {"require": True})), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
         if rows is not None:
             self._fill_prefix(st, rows)
+        if words is not None:
+            self._fill_required(st, words)
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
         res = self._family_result(loop, B, beam, ("prob",))
+        if words is not None:
+            return res + (st["met"].view(B, beam).long(),)
         return res if scoring is None else res + (st["key"].view(B, beam).clone(),)
 
     # ------------------------------------------------------------------ stochastic beam search: n samples without replacement
@@ -1119,3 +1197,12 @@ class Searcher:
         g = gen[torch.arange(gen.shape[0], device=gen.device), j].tolist()
         n = length[torch.arange(gen.shape[0], device=gen.device), j].tolist()
         return [row[:k] for row, k in zip(g, n)]
+
+    def best_required(self, gen, length, prob, met) -> List[List[int]]:
+        """The message of a search with required words, per commit: positive probability first, then the most words met, then
+        the highest probability, then the lowest slot."""
+        out = []
+        for g, n, p, m in zip(gen.tolist(), length.tolist(), prob.tolist(), met.tolist()):
+            j = min(range(len(p)), key=lambda q: (not p[q] > 0, -m[q], -p[q], q))
+            out.append(g[j][:n[j]])
+        return out

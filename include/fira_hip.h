@@ -910,6 +910,44 @@ int fira_beam_select_gumbel(void* stream, const fira_dims* d, int B, int n_beam,
                             const float* logp_in, int32_t* gen_out, int32_t* len_out, float* phi_out, float* G_out,
                             float* logp_out, int32_t* parent);
 
+/* Lexically constrained beam search: fira_beam_select with dynamic beam allocation (csrc/beam_require.hip; additive, the ABI
+ * version is unchanged; Post and Vilar, NAACL 2018).  The arguments of fira_beam_select, then required, n_required and met_out;
+ * the state is the same, since the number of required words a hypothesis holds is a function of its gen row.  required and
+ * n_required are DEVICE buffers read when the kernel runs: one captured graph serves every word list.
+ * Per commit b: C = n_required[b] (a value outside 0..4 is clamped), R_k = required[b, k] for k < C.
+ *     w(i)     the word of entry i, as fira_constrain_dist defines it: the generator id, or the sou / sub_token id of a copy slot
+ *     met(h)   the set of k such that R_k occurs among gen[1 .. length - 1] (length clamped to 1 .. tar_len)
+ *     bank(h)  |met(h)|
+ * Candidates of a step: fira_beam_select's, in its flattened index order (running slots in slot order, then the carried list):
+ *     running   entry i of running slot j: p = fp32(dist[j, i] * prob[j]), the very product fira_beam_select forms;
+ *               bank = |met(h_j) u { k : R_k == w(i) }|
+ *     carried   a finished hypothesis: p = prob[j], bank = bank(h_j)
+ *     void      fira_beam_select's two -1 cases (the row of a finished hypothesis, the padding of the carried list), plus every
+ *               entry with w(i) == <eos> (1) of a running row with bank(h_j) < C: a message may not end before it holds all its
+ *               words.  A copy slot that carries id 1 is blocked like the generator entry.
+ * Selection, phase 1 (round robin over banks): only candidates with p > 0 take part; within a bank they are ranked by
+ * (p descending, flattened index ascending).  Repeat until n_beam picks are made or no positive candidate is left:
+ *     for c = C down to 0: if bank c has an unpicked positive candidate, pick its best.
+ * Each bank gets an even share, the highest bank first; a bank that runs dry hands its share to the others.
+ * Selection, phase 2 (fill): slots still free take the remaining candidates in fira_beam_select's own order: value descending
+ * with void = -1, index ascending.  A void candidate is never reached: r running rows leave at least
+ * r * (W - copies of <eos> - 1) entries that are not void, and vocab > 8.
+ * Written order of the n_beam picks: p > 0 first, then bank descending, then p descending, then pick order ascending.  gen_out,
+ * len_out, prob_out and parent are formed as fira_beam_select forms them; met_out[r] (optional) is the bank of the hypothesis
+ * written to row r.
+ * Anchor: with C = 0 for a commit, phase 1 followed by phase 2 is (p descending, index ascending) and the sort is stable, so that
+ * commit's four outputs are fira_beam_select's bit for bit.  Once `done` is set the state is copied through (met_out is still
+ * written).  Nothing is renormalised.
+ * 2 <= n_beam <= 8, tar_len <= 64, vocab in 9 .. 25 600, sou_len + sub_len <= 1 024; anything else returns non-zero with the
+ * reason in fira_last_error() and nothing is launched.  One workgroup of 1 024 threads per commit; every running row is streamed
+ * once, the bytes are fira_beam_select's (plus at most 4 re-read entries per row); vector stores only, no global atomics.   */
+int fira_beam_select_required(void* stream, const fira_dims* d, int B, int n_beam, const float* dist, const int32_t* finished,
+                              const int32_t* active, const int32_t* done, const int32_t* sou, const int32_t* sub_token,
+                              const int32_t* gen_in, const int32_t* len_in, const float* prob_in, int32_t* gen_out,
+                              int32_t* len_out, float* prob_out, int32_t* parent,
+                              const int32_t* required /* device, [B, 4] */, const int32_t* n_required /* device, [B] */,
+                              int32_t* met_out /* [B*n_beam] or NULL */);
+
 /* Greedy search bookkeeping (the same loop at beam 1 without the [B, vocab+S] distribution): consumes the arg-max
  * index / probability fira_decode_step wrote, resolves copy indices through sou / sub_token, appends the id at
  * out[b, step+1], multiplies prob, bumps length, clears alive[b] at <eos>, writes the next step's input ids to `tokens`

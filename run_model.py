@@ -140,6 +140,14 @@ def parse_args(argv):
                     "words; --merge-copies is recommended with it")
     ap.add_argument("--prefix-file", default=None, metavar="PATH", help="test: as --prefix, with one line per test commit in "
                     "all_index['test'] order (an empty line: no prefix for that commit)")
+    ap.add_argument("--require-words", default=None, metavar="W[,W...]", help="test, beam above 1: every message of the search "
+                    "contains these words (up to 4; lexically constrained decoding with dynamic beam allocation): the beam is "
+                    "divided into banks by the number of required words a hypothesis holds, and no message ends before it holds "
+                    "them all; a word counts through its generator id or a copy slot that carries it, identifiers go through "
+                    "the commit's variable map, a word the vocabulary lacks is dropped with a warning; needs --beam above the "
+                    "number of words; --merge-copies is recommended with it")
+    ap.add_argument("--require-file", default=None, metavar="PATH", help="test: as --require-words, with one line per test "
+                    "commit in all_index['test'] order, words separated by white space (an empty line: none for that commit)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
@@ -178,6 +186,7 @@ def parse_args(argv):
         check_merge_args(a)
         check_scoring_args(a)
         check_prefix_args(a)
+        check_require_args(a)
         check_ensemble_args(a)
         check_sample_args(a)
     except ValueError as e:
@@ -535,6 +544,100 @@ def prefixes_from_args(a, vocab, var_maps, tar_len):
     return out, n_unk
 
 
+MAX_REQUIRED = 4                                 # decode.MAX_REQUIRED (not imported here: parsing needs no torch)
+
+
+def check_require_args(a):
+    """Validates --require-words / --require-file against the other options and the file system (no GPU, no DataSet needed);
+    raises ValueError on a conflict.  The words are looked up later (required_from_args): how many are left for a commit, and
+    the beam they need, is known only then."""
+    words, path = getattr(a, "require_words", None), getattr(a, "require_file", None)
+    given = [flag for v, flag in ((words, "--require-words"), (path, "--require-file")) if v is not None]
+    if not given:
+        return a
+    if len(given) == 2:
+        raise ValueError("--require-words and --require-file are mutually exclusive")
+    what = given[0]
+    if a.stage != "test":
+        raise ValueError("%s only applies to the test stage" % what)
+    if a.sample is not None:
+        raise ValueError("%s names the words of a beam search's messages: it does not combine with --sample" % what)
+    if a.score is not None:
+        raise ValueError("%s names the words of a beam search's messages: it does not combine with --score" % what)
+    beam = a.beam if a.beam is not None else 3
+    if beam <= 1:
+        raise ValueError("%s divides a beam into banks: it does not combine with --beam %d" % (what, beam))
+    for name, flag in SCORING_OPTIONS:
+        if getattr(a, name, None) is not None:
+            raise ValueError("%s ranks its banks by raw probability: it does not combine with %s" % (what, flag))
+    if words is not None:
+        toks = [w for w in words.split(",") if w.strip()]
+        if not toks:
+            raise ValueError("--require-words: no word given")
+        if any(len(w.split()) != 1 for w in toks):
+            raise ValueError("--require-words: words are separated by commas, and a phrase is not one word")
+    if path is not None and not os.path.isfile(path):
+        raise ValueError("--require-file %s: no such file" % path)
+    return a
+
+
+def read_require_lines(path, n_commits):
+    """The lines of ``--require-file PATH``, one per test commit (an empty line: no word).  Raises ValueError on a wrong line
+    count."""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    if len(lines) != n_commits:
+        raise ValueError("--require-file %s: %d lines for %d test commits" % (path, len(lines), n_commits))
+    return lines
+
+
+def required_from_args(a, vocab, var_maps, tar_len):
+    """The required words of the command line: (None, 0) without the options, else (one list of vocabulary ids per test commit,
+    the number of words dropped because the vocabulary lacks them for that commit).  ``var_maps``: the commits' variable maps
+    in test order; its length is the number of test commits.  A word goes through the commit's variable map (the commit's
+    identifiers to their placeholders) as a prefix word does; duplicates after mapping collapse to the first occurrence.
+    Raises ValueError on a wrong line count, on more than 4 words left for a commit, on more than tar_len - 2, or on a
+    --beam smaller than the longest list plus one, naming the line or the beam that is needed."""
+    words, path = getattr(a, "require_words", None), getattr(a, "require_file", None)
+    if words is None and path is None:
+        return None, 0
+    n = len(var_maps)
+    unk = vocab["<unkm>"]
+    lines = [words.replace(",", " ")] * n if words is not None else read_require_lines(path, n)
+    out, n_dropped = [], 0
+    for k, (line, var_map) in enumerate(zip(lines, var_maps)):
+        ids = []
+        for w in line.split():
+            i = vocab.get(var_map.get(w, w))
+            if i is None or i <= unk:                           # unknown here, or <pad> / <eos> / <start> / <unkm>
+                n_dropped += 1
+            elif i not in ids:
+                ids.append(i)
+        where = "--require-words" if words is not None else "--require-file %s: line %d" % (path, k + 1)
+        if len(ids) > MAX_REQUIRED:
+            raise ValueError("%s: %d words, more than %d" % (where, len(ids), MAX_REQUIRED))
+        if len(ids) > tar_len - 2:
+            raise ValueError("%s: %d words, more than tar_len - 2 = %d" % (where, len(ids), tar_len - 2))
+        out.append(ids)
+    longest = max((len(ids) for ids in out), default=0)
+    beam = getattr(a, "beam", None)
+    beam = 3 if beam is None else beam
+    if longest and beam < longest + 1:
+        k = next(k for k, ids in enumerate(out) if len(ids) == longest)
+        where = "--require-words" if words is not None else "--require-file %s: line %d" % (path, k + 1)
+        raise ValueError("%s: %d words need --beam %d or more (one bank per count of words met), not --beam %d"
+                         % (where, longest, longest + 1, beam))
+    return out, n_dropped
+
+
+def required_summary(messages, required):
+    """(commits with required words, those whose written message -- a list of ids -- contains all of them)."""
+    with_words = [(m, r) for m, r in zip(messages, required) if r]
+    return len(with_words), sum(1 for m, r in with_words if set(r) <= set(m[1:]))
+
+
 def check_ensemble_args(a):
     """Validates --ensemble / --ensemble-weights against the other options and the file system (no GPU, no DataSet needed, no
     model loaded); raises ValueError on a conflict, a missing file, a wrong weight count or a bad weight.  Leaves
@@ -577,15 +680,19 @@ def check_ensemble_args(a):
     return a
 
 
-def nbest_record(messages, probs, keys=None):
+def nbest_record(messages, probs, keys=None, met=None):
     """One line of OUTPUT/output_fira_nbest: the beam's messages of positive probability (the -1 padding and zero-probability
     candidates are left out), ordered by probability descending, then slot ascending.  With ``keys`` (a search under
-    --length-penalty / --beam-groups): ordered by key descending, then slot ascending, and the line carries the keys too."""
+    --length-penalty / --beam-groups): ordered by key descending, then slot ascending, and the line carries the keys too.
+    With ``met`` (a search under --require-words / --require-file): ordered by words met descending first, and the line
+    carries the counts under "met"."""
     rank = probs if keys is None else keys
-    order = sorted((j for j in range(len(probs)) if probs[j] > 0), key=lambda j: (-rank[j], j))
+    order = sorted((j for j in range(len(probs)) if probs[j] > 0), key=lambda j: (0 if met is None else -met[j], -rank[j], j))
     rec = {"messages": [messages[j] for j in order], "prob": [probs[j] for j in order]}
     if keys is not None:
         rec["key"] = [keys[j] for j in order]
+    if met is not None:
+        rec["met"] = [met[j] for j in order]
     return json.dumps(rec)
 
 
@@ -811,6 +918,9 @@ class Run:
         if n_unk and self.rank == 0:                         # (a wrong line count or a line too long: an error before the model loads)
             print("warning: %d prefix words are not in the vocabulary and are forced as <unkm>" % n_unk, file=sys.stderr, flush=True)
         scoring = scoring_from_args(self.a)
+        required, n_dropped = required_from_args(self.a, self.vocab, [self.var_maps[i] for i in test_index], cfg.tar_len)
+        if n_dropped and self.rank == 0:                     # (a wrong line count or too many words: an error before the model loads)
+            print("warning: %d required words are not in the vocabulary and are dropped" % n_dropped, file=sys.stderr, flush=True)
         self.model = TransModel(cfg, device="cuda:%d" % self.local, init=False)
         self.model.load_state_dict(torch.load(os.path.join(self.root, "best_model.pt"), map_location="cpu"))
         self.model.compute_dtype = self.a.dtype
@@ -832,6 +942,7 @@ class Run:
             return self.test_score(search, store, mine, given)
         merge, want_nbest = bool(getattr(self.a, "merge_copies", False)), bool(getattr(self.a, "nbest", False))
         lines, nbest, n_tok, t0 = [], [], 0, time.time()
+        n_with, n_all = 0, 0                                 # --require-*: commits with words; messages that hold all of theirs
         # greedy: groups of `in_flight` batches share the GPU (independent launch chains: decode.Searcher.greedy_many; four lanes
         # on eight hardware queues: 0.14 ms per batch-step against 0.33 one at a time); the output order stays
         # all_index['test'] order (run_model.py:372)
@@ -846,9 +957,18 @@ class Run:
                 outs = [search.best(*r) for r in search.greedy_many(dbs, in_flight=group, constraints=constraints,
                                                                     merge_copies=merge, **forced)]
             else:
-                keys = None
+                keys = met = None
                 forced = {k: v[0] for k, v in forced.items()}
-                if scoring is None:
+                if required is not None:                     # banks by words met: best_required's pick
+                    words = [required[i] for i in idxs[0]]
+                    res = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge, require=words, **forced)
+                    gen, length, prob = res[:3]
+                    met = res[3] if len(res) == 4 else torch.zeros_like(length)    # (a batch without words: three tensors)
+                    outs = [search.best_required(gen, length, prob, met)]
+                    w, h = required_summary(outs[0], words)
+                    n_with, n_all = n_with + w, n_all + h
+                    met = met.tolist()
+                elif scoring is None:
                     gen, length, prob = search.beam(dbs[0], cfg.beam_size, constraints=constraints, merge_copies=merge, **forced)
                     outs = [search.best(gen, length, prob)]
                 else:                                        # ranked by key: the best slot of positive probability, lowest on ties
@@ -861,7 +981,8 @@ class Run:
                     for k, i in enumerate(idxs[0]):
                         msgs = [text.detokenize(g[:n], self.r_vocab, self.var_maps[test_index[i]])
                                 for g, n in zip(gen[k], length[k])]
-                        nbest.append(nbest_record(msgs, prob[k], None if keys is None else keys[k]))
+                        nbest.append(nbest_record(msgs, prob[k], None if keys is None else keys[k],
+                                                  None if met is None else met[k]))
             for idx, hyps in zip(idxs, outs):
                 for h, i in zip(hyps, idx):
                     lines.append(text.detokenize(h, self.r_vocab, self.var_maps[test_index[i]]))
@@ -872,6 +993,11 @@ class Run:
         lines = gather_lines(lines)
         if want_nbest:
             nbest = gather_lines(nbest)
+        if required is not None:
+            counts = [l.split() for l in gather_lines(["%d %d" % (n_all, n_with)])]
+            if self.rank == 0:
+                print("required words: %d of the %d commits with words have a message that contains all of them"
+                      % (sum(int(c[0]) for c in counts), sum(int(c[1]) for c in counts)), flush=True)
         if self.rank == 0:
             with open(self.out("output_fira"), "w") as f:
                 f.write("".join(l + "\n" for l in lines))
