@@ -214,6 +214,78 @@ class _Members:
         self.weights = (C.c_float * len(dist))(*[float(x) for x in weights])
 
 
+def neighbour_coef(sim, lam: float, min_sim: float = 0.0):
+    """The mixing coefficients of ``fira_mix_neighbour`` as a float32 numpy array [B, 2]: with c = lam * sim[b], formed in
+    float64, (a, b) = (float32(1 / (1 + c)), float32(c / (1 + c))); a commit with sim < min_sim gets (1, 0)."""
+    import numpy as np
+    sim = np.asarray(sim, dtype=np.float64).reshape(-1)
+    c = float(lam) * sim
+    out = np.stack([1.0 / (1.0 + c), c / (1.0 + c)], axis=1)
+    out[sim < float(min_sim)] = (1.0, 0.0)
+    return out.astype(np.float32)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class Neighbour:
+    """The retrieved neighbours of a batch: ``db`` is a ``DeviceBatch`` of the same B whose row b is the
+    training commit nearest to commit b, ``sim`` [B] their similarities in [0, 1] (``retrieve.Datastore.query``).  At every
+    step the distribution the model predicts for the neighbour on the same tokens, folded into words, is mixed into the
+    input's with weight c = ``lam`` * sim[b]: p <- (p + c q) / (1 + c), so the row stays normalised.  A commit with
+    sim < ``min_sim`` is searched as if it had no neighbour.  Values are checked here (``ValueError`` with the reason);
+    ``check`` holds the value against a batch."""
+    db: DeviceBatch
+    sim: object
+    lam: float = 1.0
+    min_sim: float = 0.0
+
+    MAX_LAMBDA = 1024.0
+
+    def __post_init__(self):
+        import numpy as np
+        if not hasattr(self.db, "B") or not hasattr(self.db, "struct"):
+            raise ValueError("Neighbour: db = %r is not a DeviceBatch" % (self.db,))
+        for name, hi in (("lam", self.MAX_LAMBDA), ("min_sim", float("inf"))):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError("Neighbour: %s = %r is not a number" % (name, v))
+            if not 0 <= v <= hi:                              # (also refuses nan)
+                raise ValueError("Neighbour: %s = %r outside [0, %g]" % (name, v, hi))
+            object.__setattr__(self, name, float(v))
+        sim = self.sim
+        if torch.is_tensor(sim):
+            sim = sim.detach().cpu().tolist()
+        try:
+            sim = np.array([float(x) for x in sim], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("Neighbour: sim = %r is not a sequence of numbers" % (self.sim,)) from None
+        if sim.shape != (self.db.B,):
+            raise ValueError("Neighbour: %d similarities for a neighbour batch of %d commits" % (sim.size, self.db.B))
+        if not (np.isfinite(sim).all() and (sim >= 0).all() and (sim <= 1).all()):
+            raise ValueError("Neighbour: sim = %s holds a value outside [0, 1]" % (sim.tolist(),))
+        object.__setattr__(self, "sim", sim)
+
+    def check(self, B: int) -> "Neighbour":
+        if self.db.B != B:
+            raise ValueError("Neighbour: a neighbour batch of %d commits for a batch of %d" % (self.db.B, B))
+        return self
+
+    def coef(self):
+        return neighbour_coef(self.sim, self.lam, self.min_sim)
+
+
+class _NeighbourWs:
+    """What ``Searcher._begin`` hands to ``Searcher._step`` for a search with a neighbour in place of the one decode workspace:
+    the input's workspace, the neighbour batch's, the [R, out_len] buffer of the neighbour's distribution, the device
+    coefficients and the neighbour's id rows (static buffers, filled on every call: one capture serves every batch)."""
+
+    def __init__(self, ws, ws_n, R, B, cfg, dev):
+        self.ws, self.ws_n = ws, ws_n
+        self.q = torch.zeros((R, cfg.out_len), dtype=torch.float32, device=dev)
+        self.coef = torch.zeros((B, 2), dtype=torch.float32, device=dev)
+        self.sou = torch.zeros((B, cfg.sou_len), dtype=torch.int32, device=dev)
+        self.sub = torch.zeros((B, max(cfg.sub_token_len, 1)), dtype=torch.int32, device=dev)
+
+
 def rank_values(scores, by: str) -> torch.Tensor:
     """The [B, n] values ``Searcher.rank`` orders candidates by (larger is better)."""
     if by == "mean_logp_word":
@@ -236,13 +308,13 @@ class _Loop:
     the ``chunk`` and the ``bounds`` they were captured with: a graph call with another ``chunk`` is refused, since the captured
     chunks would not match its bounds.  Eager calls take any ``chunk``."""
 
-    def __init__(self, search: "Searcher", db: DeviceBatch, rows: int, key, make, chunk: int, use_graphs: bool):
+    def __init__(self, search: "Searcher", db: DeviceBatch, rows: int, key, make, chunk: int, use_graphs: bool, neighbour=None):
         st = search._ws.get(key)
         if use_graphs and st is not None and st["graphs"] is not None and st["chunk"] != chunk:
             raise ValueError("chunk = %d, but the graphs of %r were captured with chunk = %d (use_graphs=False takes any chunk)"
                              % (chunk, key, st["chunk"]))
         self.T, self.chunk, self.use_graphs = search.cfg.tar_len, chunk, use_graphs
-        self.ws = search._begin(db, rows)
+        self.ws = search._begin(db, rows) if neighbour is None else search._begin(db, rows, neighbour)
         self.st = search._state(key, db, make)
 
     def start(self, steps, reset, stop=None, n_steps: Optional[int] = None):
@@ -388,11 +460,26 @@ class Searcher:
                                                    _lib.ptr(model.flat.data), _lib.ptr(ws), ws.numel(), beam,
                                                    self.flags), "fira_decode_begin")
 
-    def _begin(self, db, beam):
+    def _begin(self, db, beam, neighbour=None):
         ws = self._workspace(db.B, beam)
         self.model.sync_params()
         db.wait_ready()
         self._begin_model(self.model, ws, db, beam)
+        if neighbour is not None:
+            # a neighbour (never with members): a second workspace of the one model for the neighbour batch, its encoder pass on
+            # the current stream, and the per-batch values into the static buffers the captured launches read
+            key = ("neighbours", db.B, beam)
+            if key not in self._ws:
+                self._ws[key] = _NeighbourWs(ws, self._workspace(db.B, beam, key=("neighbour", db.B, beam)), db.B * beam, db.B,
+                                             self.cfg, self.model.device_)
+            nb = self._ws[key]
+            neighbour.db.wait_ready()
+            self._begin_model(self.model, nb.ws_n, neighbour.db, beam)
+            nb.coef.copy_(torch.from_numpy(neighbour.coef()))
+            nb.sou.copy_(neighbour.db.sou)
+            if self.cfg.sub_token_len:
+                nb.sub.copy_(neighbour.db.sub_token)
+            return nb
         if not self.members:
             return ws
         # an ensemble: one workspace (the primary's under today's key) and one distribution buffer per member; the encoder pass
@@ -415,6 +502,17 @@ class Searcher:
                                                   _lib.ptr(best_p), self.flags), "fira_decode_step")
 
     def _step(self, ws, B, beam, step, tokens, parent, dist, best_id, best_p):
+        if isinstance(ws, _NeighbourWs):
+            # a neighbour (``ws`` is the _NeighbourWs of ``_begin``): the input's step into the search's ``dist``, the same
+            # model's step over the neighbour batch with the same tokens and parents into ``ws.q``, the neighbour's row folded
+            # into words with the NEIGHBOUR's ids, then the mix in place over ``dist`` -- which also delivers best_id / best_p
+            lib, s, dims = _lib.lib(), _lib.cur_stream(), C.byref(self.model.dims)
+            self._step_model(self.model, ws.ws, B, beam, step, tokens, parent, dist, None, None)
+            self._step_model(self.model, ws.ws_n, B, beam, step, tokens, parent, ws.q, None, None)
+            _lib.check(lib.fira_merge_dist(s, dims, B * beam, beam, _lib.ptr(ws.sou), _lib.ptr(ws.sub), _lib.ptr(ws.q), None, None),
+                       "fira_merge_dist")
+            return _lib.check(lib.fira_mix_neighbour(s, dims, B * beam, beam, _lib.ptr(ws.coef), _lib.ptr(ws.q), _lib.ptr(dist),
+                                                     _lib.ptr(best_id), _lib.ptr(best_p)), "fira_mix_neighbour")
         if not self.members:
             return self._step_model(self.model, ws, B, beam, step, tokens, parent, dist, best_id, best_p)
         # an ensemble (``ws`` is the _Members of ``_begin``): every member's step with the same tokens and parents into its own
@@ -433,6 +531,21 @@ class Searcher:
         if not isinstance(constraints, Constraints):
             raise ValueError("constraints: expected decode.Constraints or None, got %r" % (constraints,))
         return constraints.check(self.cfg) if constraints.active else None
+
+    def _neighbour(self, neighbour, B: int):
+        """None for "no neighbour" (today's launches, buffers and graphs), else the checked value; raises before any launch."""
+        if neighbour is None:
+            return None
+        if not isinstance(neighbour, Neighbour):
+            raise ValueError("neighbour: expected decode.Neighbour or None, got %r" % (neighbour,))
+        if self.members:
+            raise ValueError("neighbour: does not combine with an ensemble (members)")
+        return neighbour.check(B)
+
+    @staticmethod
+    def _no_neighbour(what: str, neighbour):
+        if neighbour is not None:
+            raise ValueError("%s does not combine with a neighbour (greedy, greedy_many and beam do)" % what)
 
     def _edit(self, st, R, rows_per_commit, gen, length, best):
         """The edit chain: the kernels that edit the step's distribution st["dist"] ([R, out_len], ``rows_per_commit`` rows per
@@ -524,12 +637,14 @@ class Searcher:
         st["prefix_len"].copy_(torch.tensor([len(row) for row in rows], dtype=torch.int32))
 
     @staticmethod
-    def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False):
+    def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False, neighbour: bool = False):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
         so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
         marker only: the prefix values live in device buffers), then "require" for a search with required words (a marker
-        too); an active BeamScoring value comes last."""
+        too), then "neighbour" for a search with a neighbour (a marker: the batch and the coefficients live in device buffers);
+        an active BeamScoring value comes last."""
         return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + (("require",) if require else ())
+                + (("neighbour",) if neighbour else ())
                 + ((con,) if con is not None else ()) + ((scoring,) if scoring is not None else ()))
 
     def _required_rows(self, require, B: int, beam: int, con: Optional[Constraints], scoring):
@@ -649,6 +764,8 @@ class Searcher:
         for step in range(lo, hi):
             if "dist" not in st:
                 self._step(ws, B, 1, step, st["tok"], None, None, st["best_id"], st["best_p"])
+            elif st.get("mix_best", False):                   # a neighbour and an empty edit chain: the mix takes the arg-max
+                self._step(ws, B, 1, step, st["tok"], None, st["dist"], st["best_id"], st["best_p"])
             else:
                 self._step(ws, B, 1, step, st["tok"], None, st["dist"], None, None)
                 self._edit(st, B, 1, st["out"], st["length"], (st["best_id"], st["best_p"]))
@@ -659,7 +776,7 @@ class Searcher:
                        "fira_greedy_advance")
 
     def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
-                     merge_copies: bool = False, prefix=None) -> _Loop:
+                     merge_copies: bool = False, prefix=None, neighbour=None) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  The
         active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, constraints]), and so own their graphs)
         and add what ``_edit_state`` lists to the state -- the [B, out_len] distribution with any of them."""
@@ -667,8 +784,16 @@ class Searcher:
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
-        make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **self._edit_state(i32, f32, B, B, con, merge, rows))
-        loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None), make, chunk, use_graphs)
+        nb = self._neighbour(neighbour, B)                   # likewise
+        if nb is None:
+            make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **self._edit_state(i32, f32, B, B, con, merge, rows))
+            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None), make, chunk, use_graphs)
+        else:                                                # a neighbour: the state always owns the distribution
+            bare = con is None and not merge and rows is None
+            make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **({"mix_best": True} if bare else {}),
+                                         **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True))
+            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=True), make, chunk,
+                         use_graphs, nb)
         st, ws = loop.st, loop.ws
         if rows is not None:
             self._fill_prefix(st, rows)
@@ -686,19 +811,25 @@ class Searcher:
 
     @torch.no_grad()
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
-               merge_copies: bool = False, prefix=None):
+               merge_copies: bool = False, prefix=None, neighbour: Optional[Neighbour] = None):
         """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``, ``merge_copies``
         and ``prefix`` are the class's options: with any of them the step writes its distribution instead of taking its fused
         arg-max, and the last kernel of the edit chain (``_edit``) takes the arg-max of what is left.
 
+        ``neighbour``: a ``Neighbour`` value.  Every step then also runs the model over the neighbour
+        batch on the same tokens (a second workspace), folds that row into words with the neighbour's ids and mixes it into the
+        input's row (``fira_mix_neighbour``) ahead of the edit chain; the returned probability is the product of the mixed
+        entries taken.  It combines with the three options above; the state gains a "neighbour" key component and always owns
+        a distribution.  A ``ValueError`` before anything is launched on a wrong value or an ensemble.
+
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
-        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix).run())
+        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix, neighbour).run())
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
-                    merge_copies: bool = False, prefix=None):
+                    merge_copies: bool = False, prefix=None, neighbour=None):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -712,9 +843,19 @@ class Searcher:
         Same arithmetic, same ids as ``greedy`` batch by batch, ``constraints`` and ``merge_copies`` included (with
         ``merge_copies`` the probability is that of the word sequence, summed over every entry path that spells it).
         ``prefix``: one prefix argument of ``greedy`` per batch (a sequence as long as ``dbs``; an entry may be None); the
-        returned probability is then the joint probability of prefix and continuation."""
+        returned probability is then the joint probability of prefix and continuation.
+        ``neighbour``: one ``Neighbour`` (or None) per batch, a sequence as long as ``dbs``."""
         dbs = list(dbs)
         con = self._active(constraints)                      # raises before a lane starts
+        if neighbour is not None:
+            try:
+                neighbour = list(neighbour)
+            except TypeError:
+                raise ValueError("neighbour: expected one Neighbour per batch, got %r" % (neighbour,)) from None
+            if len(neighbour) != len(dbs):
+                raise ValueError("neighbour: %d values for %d batches" % (len(neighbour), len(dbs)))
+            for db, nb in zip(dbs, neighbour):
+                self._neighbour(nb, db.B)                    # every batch's, before a lane starts
         if prefix is not None:
             try:
                 prefix = list(prefix)
@@ -755,7 +896,8 @@ class Searcher:
                             loop.launch()
                     if active[k] is None and nxt < len(dbs):
                         loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies,
-                                                 None if prefix is None else prefix[nxt])
+                                                 None if prefix is None else prefix[nxt],
+                                                 None if neighbour is None else neighbour[nxt])
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -789,7 +931,7 @@ class Searcher:
 
     @torch.no_grad()
     def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-               keys=None, chunk: int = 5, use_graphs: bool = True):
+               keys=None, chunk: int = 5, use_graphs: bool = True, neighbour=None):
         """``n`` sampled messages per commit.  Returns (tokens [B,n,T] int64 starting with <start>, lengths [B,n],
         probability [B,n], log-probability [B,n]); the probabilities are the model's (untempered, unfiltered) ones of the
         emitted ids.
@@ -801,6 +943,7 @@ class Searcher:
         fixed in the captured launches, so they are part of the state's key; the seed is a device scalar read at run time: one
         capture serves every seed."""
         self._no_ensemble("sample")                           # raises before anything is launched
+        self._no_neighbour("sample", neighbour)
         B, T = db.B, self.cfg.tar_len
         R = B * n
         noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched
@@ -940,7 +1083,8 @@ class Searcher:
         return cand.to(torch.int32), length.to(torch.int32), labels
 
     @torch.no_grad()
-    def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None):
+    def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None,
+              neighbour=None):
         """Teacher-forced probability of given messages.  ``cand`` [B, n, T] (or [B, T]) vocabulary ids, each message starting
         with <start> and ending with <eos> unless truncated, zero-padded; 1 <= n <= 8 candidates per commit share the
         commit's encoder pass and memory (``fira_decode_begin`` with n rows per commit).  ``labels`` (same shape, optional):
@@ -956,6 +1100,7 @@ class Searcher:
         inputs and outputs are plain rows of them.
         ``dist`` (tests): a [tar_len - 1, B * n, out_len] tensor that receives every step's distribution (eager only)."""
         self._no_ensemble("score")                            # raises before anything is launched
+        self._no_neighbour("score", neighbour)
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
         cand, length, labels = self.check_candidates(cand, lengths, labels, B)        # raises before anything is launched
@@ -1062,7 +1207,7 @@ class Searcher:
     @torch.no_grad()
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
-             scoring: Optional[BeamScoring] = None, prefix=None, require=None):
+             scoring: Optional[BeamScoring] = None, prefix=None, require=None, neighbour: Optional[Neighbour] = None):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``
         and ``prefix`` are the class's options, one library call per step each, between the step and the selection (``_edit``);
         the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, "require"][, constraints][, scoring]) (``_key``).
@@ -1090,6 +1235,10 @@ class Searcher:
         ``beam < len(words) + 1`` (a bank per count), more than tar_len - 2 words, a word the ``constraints`` ban, or an
         active ``scoring``.
 
+        ``neighbour``: a ``Neighbour`` value, as for ``greedy``: the neighbour batch's step over the same tokens and parents (its
+        caches follow the beam's reordering), its row folded into words, ``fira_mix_neighbour`` into the beam's distribution, then
+        the edit chain and the selection as ever.  It combines with every option above; "neighbour" joins the state key.
+
         Per step, with every option off: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library
         calls, no torch op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam)
         shape, and the ``done`` latch is read back between chunks (run_model.py:276-279)."""
@@ -1103,6 +1252,7 @@ class Searcher:
             scoring = scoring.check(beam) if scoring.active() or beam < 2 else None
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
         words = self._required_rows(require, B, beam, con, scoring)   # likewise
+        nb = self._neighbour(neighbour, B)                   # likewise
 
         def make(i32, f32):
             st = dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
@@ -1115,7 +1265,9 @@ class Searcher:
             return st
         # (a captured graph bakes the constraint scalars, the merge launch and the scoring scalars: they are part of the key)
         loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring, rows is not None,
-                                               **({} if words is None else {"require": True})), make, chunk, use_graphs)
+                                               **({} if words is None else {"require": True}),
+                                               **({} if nb is None else {"neighbour": True})), make, chunk, use_graphs,
+                     *(() if nb is None else (nb,)))
         st, ws = loop.st, loop.ws
         if rows is not None:
             self._fill_prefix(st, rows)
@@ -1148,7 +1300,7 @@ class Searcher:
     @torch.no_grad()
     def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
                         merge_copies: bool = True, constraints: Optional[Constraints] = None, chunk: int = 4,
-                        use_graphs: bool = True):
+                        use_graphs: bool = True, neighbour=None):
         """``n`` messages per commit sampled WITHOUT replacement: stochastic beam search (Kool, van Hoof and Welling 2019;
         ``fira_beam_select_gumbel``).  A beam search whose ranking key is the Gumbel-perturbed
         log-probability of the hypothesis, a child's key conditioned on its parent's; the n hypotheses it ends with are an exact
@@ -1169,6 +1321,7 @@ class Searcher:
         hipGraphs of ``chunk`` steps; the state is keyed ("sbs", B, n, merge, constraints, temperature) -- the temperature
         is baked into the captured launches; the seed and the keys are device values: one capture serves them all."""
         B = db.B
+        self._no_neighbour("sample_distinct", neighbour)     # raises before anything is launched
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
         noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched

@@ -863,3 +863,50 @@ def mbr_bleu_stats(tokens, length, stats=None):
     check(_lib.lib().fira_mbr_bleu_stats(cur_stream(), B, n, T, ptr(_i32(tokens)), ptr(_i32(length)), ptr(_i32(stats))),
           "fira_mbr_bleu_stats")
     return stats
+
+
+def pool_memory(dims, mem, mem_valid, out=None):
+    """fira_pool_memory: the unit vector of every commit -- the mean of its valid encoder-memory rows, L2-normalised.  mem
+    [B, sou_len + sub_len, 256] fp32 and mem_valid [B, sou_len + sub_len] int32 (a decode workspace's views).  Returns out
+    [B, 256]."""
+    B = mem.shape[0]
+    assert mem.dim() == 3 and tuple(mem_valid.shape) == tuple(mem.shape[:2]) and mem.shape[2] == 256
+    assert mem.shape[1] == dims.sou_len + dims.sub_len
+    if out is None:
+        out = torch.empty((B, 256), dtype=torch.float32, device=mem.device)
+    assert tuple(out.shape) == (B, 256)
+    import ctypes as C
+    check(_lib.lib().fira_pool_memory(cur_stream(), C.byref(dims), B, ptr(_f32(mem)), ptr(_i32(mem_valid)), ptr(_f32(out))),
+          "fira_pool_memory")
+    return out
+
+
+def nn_search(Q, store, exclude=None, scratch=None):
+    """fira_nn_search: per query row of Q [B <= 64, 256] the store row (store [N, 256]) with the largest dot product, not
+    counting row exclude[b] (int32 [B], -1 = none).  Returns (best_idx [B] int32, best_sim [B] fp32 clamped to [0, 1]); ties
+    go to the lowest index, NaN never wins."""
+    B, N = Q.shape[0], store.shape[0]
+    assert Q.dim() == 2 and store.dim() == 2 and Q.shape[1] == 256 and store.shape[1] == 256
+    assert exclude is None or tuple(exclude.shape) == (B,)
+    lib = _lib.lib()
+    need = lib.fira_nn_search_scratch_bytes(B, N)
+    if scratch is None:
+        scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=Q.device)
+    idx = torch.empty(B, dtype=torch.int32, device=Q.device)
+    sim = torch.empty(B, dtype=torch.float32, device=Q.device)
+    check(lib.fira_nn_search(cur_stream(), ptr(_f32(Q)), B, ptr(_f32(store)), N, None if exclude is None else ptr(_i32(exclude)),
+                             ptr(idx), ptr(sim), ptr(scratch), scratch.numel()), "fira_nn_search")
+    return idx, sim
+
+
+def mix_neighbour(dims, rows_per_commit, coef, q, dist, best=False):
+    """fira_mix_neighbour: dist [R, W] <- a * dist (+ c * q below the vocabulary), (a, c) = coef[r // rows_per_commit], in place.
+    ``best``: also return (best_id [R] int32, best_p [R]) of the rows as stored."""
+    R = dist.shape[0]
+    assert tuple(q.shape) == tuple(dist.shape) and coef.numel() == 2 * (R // max(rows_per_commit, 1))
+    import ctypes as C
+    bid = torch.empty(R, dtype=torch.int32, device=dist.device) if best else None
+    bp = torch.empty(R, dtype=torch.float32, device=dist.device) if best else None
+    check(_lib.lib().fira_mix_neighbour(cur_stream(), C.byref(dims), R, rows_per_commit, ptr(_f32(coef)), ptr(q), ptr(dist),
+                                        ptr(bid), ptr(bp)), "fira_mix_neighbour")
+    return (bid, bp) if best else dist

@@ -1061,6 +1061,53 @@ int fira_mix_dist(void* stream, int R, int W, int n_members,
                   float* out /* [R, W]; may be dists[0] */,
                   int32_t* best_id, float* best_p /* both NULL or both [R] */);
 
+/* Retrieval-augmented search (csrc/retrieve.hip; additive, the ABI version is unchanged): the nearest
+ * training commit's step distribution mixed into the input's (CoRec, Wang et al. 2021).
+ *
+ *   fira_pool_memory : the vector of every commit of a decode workspace.  mem [B, sou_len + sub_len, 256] and mem_valid
+ *     [B, sou_len + sub_len] are fira_decode_memory / fira_decode_mem_valid (n_beam = 1 layout: one block of rows per commit).
+ *         v[b, c] = (sum over s with mem_valid[b, s] != 0, ascending s, of mem[b, s, c]) / n_b        n_b = the number of such rows
+ *         ss[b]   = ((v[b,0] v[b,0] + v[b,1] v[b,1]) + ...) in ascending c, every multiply and add rounded to fp32 on its own
+ *         out[b, c] = v[b, c] / sqrtf(ss[b])
+ *     each one IEEE fp32 operation, so a loop of np.float32 operations is the reference, bit for bit.  n_b = 0 or ss = 0 (or a
+ *     norm that is not a number): out[b, :] = 0.  Rows with mem_valid == 0 are never read (the workspace leaves them stale).
+ *     B == 0 is a no-op.
+ *
+ *   fira_nn_search : for each of B <= 64 queries Q[b] the store row with the largest dot product,
+ *         best_idx[b] = argmax over j in [0, N), j != exclude[b], of <Q[b], store[j]>        (ties: the lowest j)
+ *         best_sim[b] = that product clamped to [0, 1]
+ *     in ONE pass over the store (tiles of 16 rows x all queries on the fp32 matrix cores, queries in LDS); no [B, N] scores
+ *     touch memory.  The product of a (query, row) pair is one ordered fp32 fma chain over k = 0 .. 255 in a fixed permutation
+ *     that does not depend on j, so identical store rows tie exactly; |product - exact| <= 256 * 2^-24 * sum |q_k s_k|.  A product
+ *     that is NaN never wins; a query whose every admissible product is NaN gets best_idx = -1, best_sim = 0.  exclude (NULL, or
+ *     DEVICE [B], -1 = nothing) is read when the kernel runs.  scratch: fira_nn_search_scratch_bytes(B, N) bytes (0 for
+ *     arguments fira_nn_search refuses), 8-byte aligned, holding the workgroups' partial winners between the two launches.
+ *     Refused with the reason in fira_last_error() and nothing launched: B <= 0, B > 64, N <= 0, exclude with N < 2 (it may leave
+ *     no row), a null or misaligned pointer (Q and store 16-byte aligned), a scratch that is too small.
+ *
+ *   fira_mix_neighbour : between fira_decode_step (+ fira_merge_dist on q with the NEIGHBOUR's sou / sub_token rows) and the edit
+ *     chain of the input.  W = vocab + sou_len + sub_len; row r belongs to commit b = r / rows_per_commit; (a, c) = coef[b, 0..1]:
+ *         dist[r, i] = a * dist[r, i]                            for vocab <= i < W     (the input's own copy entries)
+ *         dist[r, w] = (a * dist[r, w]) + (c * q[r, w])          for 0 <= w < vocab
+ *     every multiply and add rounded to fp32 on its own (no fused multiply-add).  q's entries from vocab on are not read: the
+ *     neighbour's copy slots refer to the neighbour's diff and reach the mix as words only, through the merge.  coef is a DEVICE
+ *     array read when the kernel runs (one captured launch serves every batch); the host forms a = 1 / (1 + lambda sim),
+ *     c = lambda sim / (1 + lambda sim), so a + c = 1 and the row stays normalised.  With (a, c) = (1, 0) and a finite q every
+ *     element keeps its bits (-0.0 becomes +0.0).  best_id / best_p (both NULL, or both [R]): the arg-max of the row AS STORED and
+ *     its value, in the order of fira_mix_dist; NaN never wins.  q must not overlap dist (refused).  Geometry limits of
+ *     fira_merge_dist; any 4-byte alignment of q and dist; R == 0 is a no-op.  Vector stores only, no atomics.                    */
+int fira_pool_memory(void* stream, const fira_dims* d, int B, const float* mem, const int32_t* mem_valid,
+                     float* out /* [B, 256] */);
+size_t fira_nn_search_scratch_bytes(int B, int N);
+int fira_nn_search(void* stream, const float* Q /* [B, 256] */, int B, const float* store /* [N, 256] */, int N,
+                   const int32_t* exclude /* device [B] or NULL */, int32_t* best_idx /* [B] */, float* best_sim /* [B] */,
+                   void* scratch, size_t scratch_bytes);
+int fira_mix_neighbour(void* stream, const fira_dims* d, int R, int rows_per_commit,
+                       const float* coef /* device, [R / rows_per_commit, 2] */,
+                       const float* q /* [R, vocab + sou_len + sub_len], merged with the neighbour's ids */,
+                       float* dist /* [R, vocab + sou_len + sub_len], in place */,
+                       int32_t* best_id, float* best_p /* both NULL or both [R] */);
+
 /* On-device sampling of candidate messages (temperature, top-k, top-p).  Workspace: fira_decode_begin_ex /
  * fira_decode_workspace_bytes_ex with n_beam = n_sample (1..8) and the same flags (FIRA_DECODE_KV_BF16 allowed).
  *   fira_decode_step_sample : fira_decode_step_ex for the B * n_sample rows (row r = commit r / n_sample, sample

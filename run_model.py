@@ -148,6 +148,19 @@ def parse_args(argv):
                     "number of words; --merge-copies is recommended with it")
     ap.add_argument("--require-file", default=None, metavar="PATH", help="test: as --require-words, with one line per test "
                     "commit in all_index['test'] order, words separated by white space (an empty line: none for that commit)")
+    ap.add_argument("--retrieve", action="store_true", help="test: retrieval-augmented search (any --beam) -- every test commit "
+                    "looks up the train commit with the nearest encoder representation, and at every step the distribution the "
+                    "model predicts for that neighbour is mixed into its own, weighted by the similarity; also writes "
+                    "OUTPUT/output_fira_neighbours (one JSON line per commit: train_index, sim, message).  Not with --sample, "
+                    "--score or --ensemble")
+    ap.add_argument("--retrieve-lambda", type=float, default=None, metavar="L", help="with --retrieve: the neighbour's weight is "
+                    "L x similarity (default 1; 0 = the plain search)")
+    ap.add_argument("--retrieve-min-sim", type=float, default=None, metavar="X", help="with --retrieve: commits whose neighbour "
+                    "is less similar than X are searched without it (default 0)")
+    ap.add_argument("--retrieve-store", default=None, metavar="PATH", help="with --retrieve: the file of the train split's "
+                    "vectors; built and written on first use, loaded afterwards (default OUTPUT/retrieve_store.pt)")
+    ap.add_argument("--retrieve-only", action="store_true", help="with --retrieve: write the neighbour's message to "
+                    "OUTPUT/output_fira without decoding (the retrieval baseline)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C", help="train: clip the gradient to the global "
                     "norm C > 0 on the device (torch.nn.utils.clip_grad_norm_; inf = observe and guard only) and apply a step "
                     "whose gradient holds an inf / nan as a zero-gradient step instead of destroying the weights; every "
@@ -189,6 +202,7 @@ def parse_args(argv):
         check_require_args(a)
         check_ensemble_args(a)
         check_sample_args(a)
+        check_retrieve_args(a)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -680,6 +694,44 @@ def check_ensemble_args(a):
     return a
 
 
+RETRIEVE_SUBOPTIONS = (("retrieve_lambda", "--retrieve-lambda"), ("retrieve_min_sim", "--retrieve-min-sim"),
+                       ("retrieve_store", "--retrieve-store"), ("retrieve_only", "--retrieve-only"))
+
+
+def check_retrieve_args(a):
+    """Validates --retrieve and its sub-options against the other options (no GPU, no DataSet needed); raises ValueError on a
+    conflict."""
+    on = bool(getattr(a, "retrieve", False))
+    for name, flag in RETRIEVE_SUBOPTIONS:
+        v = getattr(a, name, None)
+        if v is not None and v is not False and not on:
+            raise ValueError("%s needs --retrieve" % flag)
+    if not on:
+        return a
+    if a.stage != "test":
+        raise ValueError("--retrieve only applies to the test stage")
+    for name, flag in (("sample", "--sample"), ("score", "--score"), ("ensemble", "--ensemble")):
+        if getattr(a, name, None) is not None:
+            raise ValueError("--retrieve mixes a neighbour into the greedy and beam searches: it does not combine with %s" % flag)
+    lam, ms = getattr(a, "retrieve_lambda", None), getattr(a, "retrieve_min_sim", None)
+    if lam is not None and not 0 <= lam <= 1024:             # (also refuses nan)
+        raise ValueError("--retrieve-lambda %r: must be in [0, 1024]" % lam)
+    if ms is not None and not 0 <= ms < float("inf"):
+        raise ValueError("--retrieve-min-sim %r: must be >= 0" % ms)
+    if getattr(a, "retrieve_only", False):
+        for name, flag in (("retrieve_lambda", "--retrieve-lambda"), ("retrieve_min_sim", "--retrieve-min-sim"), ("nbest", "--nbest")):
+            v = getattr(a, name, None)
+            if v is not None and v is not False:
+                raise ValueError("--retrieve-only writes the neighbours' messages without decoding: it does not combine with %s"
+                                 % flag)
+    return a
+
+
+def neighbour_record(train_index, sim, message):
+    """One line of OUTPUT/output_fira_neighbours."""
+    return json.dumps({"train_index": int(train_index), "sim": float(sim), "message": message}, ensure_ascii=False)
+
+
 def nbest_record(messages, probs, keys=None, met=None):
     """One line of OUTPUT/output_fira_nbest: the beam's messages of positive probability (the -1 padding and zero-probability
     candidates are left out), ordered by probability descending, then slot ascending.  With ``keys`` (a search under
@@ -934,6 +986,9 @@ class Run:
             members.append(m)
         search = Searcher(self.model, members=members, weights=getattr(self.a, "ensemble_weights", None))
         mine = shard_indices(list(range(len(store))), self.rank, self.world)
+        retrieve = bool(getattr(self.a, "retrieve", False))
+        datastore = self.retrieve_store(search) if retrieve else None
+        nb_lines = []
         if self.a.sample is not None and getattr(self.a, "without_replacement", False):
             return self.test_sample_distinct(search, store, mine, constraints)
         if self.a.sample is not None:
@@ -953,6 +1008,11 @@ class Run:
             dbs = [self.device_batch(store, idx) for idx in idxs]
             # (--prefix / --prefix-file: the commits' forced message starts, batch by batch; without them no argument at all)
             forced = {} if prefixes is None else {"prefix": [[prefixes[i] for i in idx] for idx in idxs]}
+            if retrieve:                                     # (--retrieve: the batches' neighbours; without it no argument at all)
+                nbs = [self.neighbours(search, datastore, db, nb_lines) for db in dbs]
+                if getattr(self.a, "retrieve_only", False):
+                    continue
+                forced["neighbour"] = nbs
             if cfg.beam_size == 1:
                 outs = [search.best(*r) for r in search.greedy_many(dbs, in_flight=group, constraints=constraints,
                                                                     merge_copies=merge, **forced)]
@@ -990,7 +1050,14 @@ class Run:
             if self.rank == 0:
                 done = min(len(mine), starts[min(g0 + group, len(starts)) - 1] + cfg.test_batch_size)
                 print("data: %d/%d  (%.1f tokens/s)" % (done, len(mine), n_tok / max(time.time() - t0, 1e-9)), flush=True)
+        if retrieve and getattr(self.a, "retrieve_only", False):
+            lines = [json.loads(l)["message"] for l in nb_lines]
         lines = gather_lines(lines)
+        if retrieve:
+            nb_lines = gather_lines(nb_lines)
+            if self.rank == 0:
+                with open(self.out("output_fira_neighbours"), "w") as f:
+                    f.write("".join(l + "\n" for l in nb_lines))
         if want_nbest:
             nbest = gather_lines(nbest)
         if required is not None:
@@ -1005,6 +1072,40 @@ class Run:
                 with open(self.out("output_fira_nbest"), "w") as f:
                     f.write("".join(l + "\n" for l in nbest))
         return lines
+
+    def retrieve_store(self, search):
+        """--retrieve: the train split's vectors -- loaded from --retrieve-store, or built (one encoder pass per train batch) and
+        written there by rank 0 on first use; the other ranks build their own copy in memory."""
+        from fira_icse_amd.retrieve import Datastore
+        path = getattr(self.a, "retrieve_store", None) or self.out("retrieve_store.pt")
+        if os.path.isfile(path):
+            ds = Datastore.load(path, self.model)
+            if self.rank == 0:
+                print("retrieve: loaded %d vectors from %s" % (len(ds), path), flush=True)
+            return ds
+        train = self.sets["train"].store
+        bs = max(1, min(64, len(train)))
+        batches = ((list(range(lo, min(lo + bs, len(train)))), self.device_batch(train, list(range(lo, min(lo + bs, len(train))))))
+                   for lo in range(0, len(train), bs))
+        ds = Datastore.build(self.model, batches, searcher=search)
+        if self.rank == 0:
+            ds.save(path)
+            print("retrieve: built %d vectors, written to %s" % (len(ds), path), flush=True)
+        return ds
+
+    def neighbours(self, search, datastore, db, nb_lines):
+        """The ``decode.Neighbour`` of one test batch: the nearest train commits, collated from the train store; appends the
+        batch's lines of OUTPUT/output_fira_neighbours to ``nb_lines``."""
+        from fira_icse_amd.decode import Neighbour
+        train = self.sets["train"].store
+        idx, sim = datastore.query(search, db)
+        idx, sim = idx.tolist(), sim.tolist()
+        train_index = self.all_index["train"]
+        for i, s_ in zip(idx, sim):
+            nb_lines.append(neighbour_record(i, s_, text.detokenize(train.tar[i], self.r_vocab, self.var_maps[train_index[i]])))
+        a = self.a
+        return Neighbour(self.device_batch(train, idx), sim, lam=1.0 if a.retrieve_lambda is None else a.retrieve_lambda,
+                         min_sim=0.0 if a.retrieve_min_sim is None else a.retrieve_min_sim)
 
     def test_sample(self, search, store, mine):
         """--sample: N candidates per commit drawn on the device (decode.Searcher.sample); the noise of a commit is keyed by
