@@ -289,10 +289,15 @@ int inv_count(hipStream_t s, const int32_t* n_tok, float* out);
 int accum_stats(hipStream_t s, const float* loss_sum, const int32_t* n_tok, float* stats, int32_t* n_tok_total, int first);
 // sample.hip: the same distribution row as decode_dist (inline gate form, bit-identical dist), then temperature / top-k / top-p
 // and a Gumbel-max draw per (commit, sample) row; best_id / best_p as decode_dist writes them (see fira_decode_step_sample)
+// cut: the truncation cuts of fira_decode_step_sample_cut on top of them; null or every cut off = the plain sampler's kernel
+struct SampleCuts {
+    float min_p = 0.f, epsilon = 0.f, eta = 0.f, typical_p = 1.f;
+    bool on() const { return min_p > 0.f || epsilon > 0.f || eta > 0.f || typical_p < 1.f; }
+};
 int sample_dist(hipStream_t s, int R, int n_sample, int V, int S, const float* logits, int ldl, const float* score,
                 const int32_t* mem_valid, const float* x, const float* wp, const float* bp, int T, int step,
                 const int32_t* key, const uint64_t* seed_dev, float temperature, int top_k, float top_p, float* dist,
-                int32_t* best_id, float* best_p);
+                int32_t* best_id, float* best_p, const SampleCuts* cut = nullptr);
 // score.hip: the same distribution row again (bit-identical dist), then the probability of a given target word per (commit,
 // candidate) row: summed over every entry that resolves to it, its largest single entry, the copy share, an optional labelled
 // entry, the row's arg-max, and running log-probability sums (see fira_decode_step_score)

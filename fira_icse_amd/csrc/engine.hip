@@ -2356,27 +2356,64 @@ int fira_decode_step_ex(void* stream, const fira_dims* d, const float* params, v
                     dp.x, params + L.wp, params + L.bp));
     return 0;
 }
+}  // extern "C"
+namespace fira {
+// fira_decode_step_sample (cut == nullptr) and fira_decode_step_sample_cut: one body under either name
+static int decode_step_sample(const char* who, void* stream, const fira_dims* d, const float* params, void* workspace,
+                              size_t workspace_bytes, int B, int n_sample, int step, const int32_t* tokens, const int32_t* key,
+                              const uint64_t* seed_dev, float temperature, int top_k, float top_p, const SampleCuts* cut,
+                              float* dist, int32_t* best_id, float* best_p, int flags) {
+    FIRA_REQUIRE(d, "%s: bad argument", who);
+    FIRA_REQUIRE(n_sample >= 1 && n_sample <= 8, "%s: n_sample %d outside 1..8", who, n_sample);
+    FIRA_REQUIRE(temperature > 0.f && temperature < INFINITY, "%s: temperature %g must be finite and > 0", who,
+                 (double)temperature);
+    const int W = d->vocab + d->sou_len + d->sub_len;
+    FIRA_REQUIRE(top_k >= 0 && top_k <= W, "%s: top_k %d outside 0..%d", who, top_k, W);
+    FIRA_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p %g outside (0, 1]", who, (double)top_p);
+    if (cut) {                                               // (every comparison also refuses nan)
+        FIRA_REQUIRE(cut->min_p >= 0.f && cut->min_p < 1.f, "%s: min_p %g outside [0, 1)", who, (double)cut->min_p);
+        FIRA_REQUIRE(cut->epsilon >= 0.f && cut->epsilon < 1.f, "%s: epsilon %g outside [0, 1)", who, (double)cut->epsilon);
+        FIRA_REQUIRE(cut->eta >= 0.f && cut->eta < 1.f, "%s: eta %g outside [0, 1)", who, (double)cut->eta);
+        FIRA_REQUIRE(cut->typical_p > 0.f && cut->typical_p <= 1.f, "%s: typical_p %g outside (0, 1]", who,
+                     (double)cut->typical_p);
+        if (cut->typical_p < 1.f) {                          // a band in p, not a lower threshold: temperature and top-k only
+            FIRA_REQUIRE(top_p == 1.f, "%s: typical_p %g does not combine with top_p %g", who, (double)cut->typical_p,
+                         (double)top_p);
+            FIRA_REQUIRE(cut->min_p == 0.f, "%s: typical_p %g does not combine with min_p %g", who, (double)cut->typical_p,
+                         (double)cut->min_p);
+            FIRA_REQUIRE(cut->epsilon == 0.f, "%s: typical_p %g does not combine with epsilon %g", who, (double)cut->typical_p,
+                         (double)cut->epsilon);
+            FIRA_REQUIRE(cut->eta == 0.f, "%s: typical_p %g does not combine with eta %g", who, (double)cut->typical_p,
+                         (double)cut->eta);
+        }
+    }
+    FIRA_REQUIRE(key && seed_dev && best_id && best_p, "%s: key, seed_dev, best_id and best_p are required", who);
+    hipStream_t s = (hipStream_t)stream;
+    DecodePlan dp;
+    TRY(decode_step_body(s, d, params, workspace, workspace_bytes, B, n_sample, step, tokens, nullptr, flags, false, who, dp));
+    const Layout& L = *get_layout(d);
+    const Plan& p = dp.enc;
+    TRY(sample_dist(s, dp.BR, n_sample, p.V, p.L + p.S, dp.logits, p.ldl, dp.score, p.mem_valid, dp.x, params + L.wp,
+                    params + L.bp, p.T, step, key, seed_dev, temperature, top_k, top_p, dist, best_id, best_p, cut));
+    return 0;
+}
+}  // namespace fira
+extern "C" {
 int fira_decode_step_sample(void* stream, const fira_dims* d, const float* params, void* workspace, size_t workspace_bytes,
                             int B, int n_sample, int step, const int32_t* tokens, const int32_t* key, const uint64_t* seed_dev,
                             float temperature, int top_k, float top_p, float* dist, int32_t* best_id, float* best_p,
                             int flags) {
-    FIRA_REQUIRE(d, "fira_decode_step_sample: bad argument");
-    FIRA_REQUIRE(n_sample >= 1 && n_sample <= 8, "fira_decode_step_sample: n_sample %d outside 1..8", n_sample);
-    FIRA_REQUIRE(temperature > 0.f && temperature < INFINITY, "fira_decode_step_sample: temperature %g must be finite and > 0",
-                 (double)temperature);
-    const int W = d->vocab + d->sou_len + d->sub_len;
-    FIRA_REQUIRE(top_k >= 0 && top_k <= W, "fira_decode_step_sample: top_k %d outside 0..%d", top_k, W);
-    FIRA_REQUIRE(top_p > 0.f && top_p <= 1.f, "fira_decode_step_sample: top_p %g outside (0, 1]", (double)top_p);
-    FIRA_REQUIRE(key && seed_dev && best_id && best_p, "fira_decode_step_sample: key, seed_dev, best_id and best_p are required");
-    hipStream_t s = (hipStream_t)stream;
-    DecodePlan dp;
-    TRY(decode_step_body(s, d, params, workspace, workspace_bytes, B, n_sample, step, tokens, nullptr, flags, false,
-                         "fira_decode_step_sample", dp));
-    const Layout& L = *get_layout(d);
-    const Plan& p = dp.enc;
-    TRY(sample_dist(s, dp.BR, n_sample, p.V, p.L + p.S, dp.logits, p.ldl, dp.score, p.mem_valid, dp.x, params + L.wp,
-                    params + L.bp, p.T, step, key, seed_dev, temperature, top_k, top_p, dist, best_id, best_p));
-    return 0;
+    return decode_step_sample("fira_decode_step_sample", stream, d, params, workspace, workspace_bytes, B, n_sample, step, tokens,
+                              key, seed_dev, temperature, top_k, top_p, nullptr, dist, best_id, best_p, flags);
+}
+int fira_decode_step_sample_cut(void* stream, const fira_dims* d, const float* params, void* workspace, size_t workspace_bytes,
+                                int B, int n_sample, int step, const int32_t* tokens, const int32_t* key,
+                                const uint64_t* seed_dev, float temperature, int top_k, float top_p, float min_p, float epsilon,
+                                float eta, float typical_p, float* dist, int32_t* best_id, float* best_p, int flags) {
+    SampleCuts cut;
+    cut.min_p = min_p; cut.epsilon = epsilon; cut.eta = eta; cut.typical_p = typical_p;
+    return decode_step_sample("fira_decode_step_sample_cut", stream, d, params, workspace, workspace_bytes, B, n_sample, step,
+                              tokens, key, seed_dev, temperature, top_k, top_p, &cut, dist, best_id, best_p, flags);
 }
 int fira_decode_step_score(void* stream, const fira_dims* d, const float* params, void* workspace, size_t workspace_bytes,
                            int B, int n_cand, int step, const int32_t* tokens, const int32_t* target, const int32_t* label,

@@ -913,16 +913,45 @@ class Searcher:
         self._greedy_reset(st)
         st["logp"].zero_()
 
-    def _sample_steps(self, st, ws, B, n, lo, hi, temperature, top_k, top_p):
+    CUTS_OFF = (0.0, 0.0, 0.0, 1.0)                           # (min_p, epsilon, eta, typical_p)
+
+    @staticmethod
+    def _check_cuts(top_p, min_p, epsilon, eta, typical_p):
+        """The four truncation cuts of ``sample`` as the floats the library receives; raises ValueError naming the argument
+        on a value outside its range (nan included) or a combination the library refuses."""
+        f32 = lambda v: C.c_float(float(v)).value
+        cuts = tuple(f32(v) for v in (min_p, epsilon, eta, typical_p))
+        for name, v in zip(("min_p", "epsilon", "eta"), cuts):
+            if not 0 <= v < 1:
+                raise ValueError("%s %r: must be in [0, 1) (0 = off)" % (name, v))
+        if not 0 < cuts[3] <= 1:
+            raise ValueError("typical_p %r: must be in (0, 1] (1 = off)" % cuts[3])
+        if cuts[3] < 1:
+            for name, v, off in (("top_p", f32(top_p), 1.0), ("min_p", cuts[0], 0.0), ("epsilon", cuts[1], 0.0),
+                                 ("eta", cuts[2], 0.0)):
+                if v != off:
+                    raise ValueError("typical_p %r keeps a band of the distribution, not its head: it does not combine "
+                                     "with %s %r" % (cuts[3], name, v))
+        return cuts
+
+    def _sample_steps(self, st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts=CUTS_OFF):
         """Steps lo..hi-1: the KV-cached decoder step with the sampling kernel in place of the arg-max, then the bookkeeping
         of greedy search over the B * n rows (plus the log-probability sum); no torch op, no host round trip."""
         lib, s = _lib.lib(), _lib.cur_stream()
         for step in range(lo, hi):
-            _lib.check(lib.fira_decode_step_sample(s, C.byref(self.model.dims), _lib.ptr(self.model.flat.data), _lib.ptr(ws),
-                                                   ws.numel(), B, n, step, _lib.ptr(st["tok"]), _lib.ptr(st["key"]),
-                                                   _lib.ptr(st["seed"]), float(temperature), int(top_k), float(top_p), None,
-                                                   _lib.ptr(st["best_id"]), _lib.ptr(st["best_p"]), self.flags),
-                       "fira_decode_step_sample")
+            if cuts == self.CUTS_OFF:
+                _lib.check(lib.fira_decode_step_sample(s, C.byref(self.model.dims), _lib.ptr(self.model.flat.data), _lib.ptr(ws),
+                                                       ws.numel(), B, n, step, _lib.ptr(st["tok"]), _lib.ptr(st["key"]),
+                                                       _lib.ptr(st["seed"]), float(temperature), int(top_k), float(top_p), None,
+                                                       _lib.ptr(st["best_id"]), _lib.ptr(st["best_p"]), self.flags),
+                           "fira_decode_step_sample")
+            else:
+                _lib.check(lib.fira_decode_step_sample_cut(s, C.byref(self.model.dims), _lib.ptr(self.model.flat.data),
+                                                           _lib.ptr(ws), ws.numel(), B, n, step, _lib.ptr(st["tok"]),
+                                                           _lib.ptr(st["key"]), _lib.ptr(st["seed"]), float(temperature),
+                                                           int(top_k), float(top_p), *cuts, None, _lib.ptr(st["best_id"]),
+                                                           _lib.ptr(st["best_p"]), self.flags),
+                           "fira_decode_step_sample_cut")
             _lib.check(lib.fira_sample_advance(s, C.byref(self.model.dims), B, n, step, _lib.ptr(st["best_id"]),
                                                _lib.ptr(st["best_p"]), _lib.ptr(st["sou"]), _lib.ptr(st["sub"]),
                                                _lib.ptr(st["out"]), _lib.ptr(st["length"]), _lib.ptr(st["prob"]),
@@ -931,10 +960,18 @@ class Searcher:
 
     @torch.no_grad()
     def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-               keys=None, chunk: int = 5, use_graphs: bool = True, neighbour=None):
+               keys=None, chunk: int = 5, use_graphs: bool = True, neighbour=None, min_p: float = 0.0, epsilon: float = 0.0,
+               eta: float = 0.0, typical_p: float = 1.0):
         """``n`` sampled messages per commit.  Returns (tokens [B,n,T] int64 starting with <start>, lengths [B,n],
         probability [B,n], log-probability [B,n]); the probabilities are the model's (untempered, unfiltered) ones of the
         emitted ids.
+
+        Truncation cuts on top of the filters, on q = the tempered distribution renormalised over what top-k and top-p kept
+        (``fira_decode_step_sample_cut``): ``min_p`` keeps q >= min_p * max q, ``epsilon`` keeps q >= epsilon, ``eta`` keeps
+        q >= min(eta, sqrt(eta) * exp(-H)) with H the entropy of q (each in [0, 1), ``0`` = off), ``typical_p`` keeps the
+        entries whose surprise is nearest H until they hold that share of the mass (in (0, 1], ``1`` = off; with temperature
+        and top-k only).  Every cut keeps the row's maximum.  With all four off this is the call and the state of the plain
+        sampler; otherwise the four values join the state's key, since they too are fixed in the captured launches.
 
         Filters in the order of HF ``generate``: temperature, then top-k (``0`` = off), then top-p (``1`` = off); the draw is a
         Gumbel-max over the kept entries with counter-hash noise of (``seed``, ``keys[b]``, sample, step, entry), so a commit's
@@ -944,14 +981,16 @@ class Searcher:
         capture serves every seed."""
         self._no_ensemble("sample")                           # raises before anything is launched
         self._no_neighbour("sample", neighbour)
+        cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)
         B, T = db.B, self.cfg.tar_len
         R = B * n
         noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched
         make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), **noise_rows(i32))
-        loop = _Loop(self, db, n, ("sample", B, n, float(temperature), int(top_k), float(top_p)), make, chunk, use_graphs)
+        key = ("sample", B, n, float(temperature), int(top_k), float(top_p))
+        loop = _Loop(self, db, n, key if cuts == self.CUTS_OFF else key + cuts, make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
         fill_noise(st)
-        loop.start(lambda lo, hi: self._sample_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p),
+        loop.start(lambda lo, hi: self._sample_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts),
                    lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
                 st["logp"].view(B, n).clone())

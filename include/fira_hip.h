@@ -1129,6 +1129,25 @@ int fira_decode_step_sample(void* stream, const fira_dims* d, const float* param
                             size_t workspace_bytes, int B, int n_sample, int step, const int32_t* tokens,
                             const int32_t* key, const uint64_t* seed_dev, float temperature, int top_k, float top_p,
                             float* dist, int32_t* best_id, float* best_p, int flags);
+/* Truncation samplers: fira_decode_step_sample with four more cuts of the row, applied after its filters.  Below, q is the
+ * tempered distribution p^(1/T) renormalised over the entries top-k and then top-p kept, and H = -sum q ln q over them (an
+ * entry with q = 0 contributes 0); sums are fixed-order fp32 block sums without atomics, as the filters' are.
+ *     min_p     in [0, 1), 0 = off: keep q_i >= min_p * max q
+ *     epsilon   in [0, 1), 0 = off: keep q_i >= epsilon                                  (epsilon sampling)
+ *     eta       in [0, 1), 0 = off: keep q_i >= min(eta, sqrt(eta) * exp(-H))            (eta sampling)
+ *     typical_p in (0, 1], 1 = off: with s_i = |-ln q_i - H|, keep s_i <= sigma, sigma the smallest value whose lower set
+ *               {s_i <= sigma} holds at least typical_p of the mass (locally typical sampling; bisected over the bits of s)
+ *   The first three are lower thresholds on q and so on p: together with top-k and top-p the largest one decides, ties at it
+ *   are kept.  typical_p < 1 is a band in p, not a lower threshold: it combines with temperature and top_k only and is an
+ *   error with top_p < 1, min_p, epsilon or eta.  Every cut keeps the row's maximum (with its ties), so no row is left empty;
+ *   an entry with p = 0 is never kept.  The draw, best_id, best_p and dist are fira_decode_step_sample's; with
+ *   (min_p, epsilon, eta, typical_p) = (0, 0, 0, 1) the call IS fira_decode_step_sample, bit for bit.  Values outside
+ *   their range or not finite: error.                                                                                 */
+int fira_decode_step_sample_cut(void* stream, const fira_dims* d, const float* params, void* workspace,
+                                size_t workspace_bytes, int B, int n_sample, int step, const int32_t* tokens,
+                                const int32_t* key, const uint64_t* seed_dev, float temperature, int top_k, float top_p,
+                                float min_p, float epsilon, float eta, float typical_p, float* dist, int32_t* best_id,
+                                float* best_p, int flags);
 int fira_sample_advance(void* stream, const fira_dims* d, int B, int n_sample, int step, const int32_t* best_id,
                         const float* best_p, const int32_t* sou, const int32_t* sub_token, int32_t* out, int32_t* length,
                         float* prob, float* logp, int32_t* alive, int32_t* tokens, int32_t* n_alive);

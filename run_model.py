@@ -90,6 +90,17 @@ def parse_args(argv):
     ap.add_argument("--top-k", type=int, default=None, help="with --sample: keep the k most probable entries (default 0 = off)")
     ap.add_argument("--top-p", type=float, default=None, help="with --sample: nucleus mass in (0, 1] (default 1 = off)")
     ap.add_argument("--sample-seed", type=int, default=None, help="with --sample: seed of the sampling noise (default 0)")
+    ap.add_argument("--min-p", type=float, default=None, metavar="X", help="with --sample: keep the entries at least X times as "
+                    "probable as the most probable one, 0 <= X < 1 (default 0 = off); like the three options below a cut of "
+                    "the tempered distribution that --top-k and --top-p left, renormalised; every cut keeps the maximum")
+    ap.add_argument("--epsilon-cutoff", type=float, default=None, metavar="E", help="with --sample: epsilon sampling -- keep "
+                    "the entries of probability >= E, 0 <= E < 1 (default 0 = off); the candidate generator to pair with "
+                    "--rerank mbr_bleu")
+    ap.add_argument("--eta-cutoff", type=float, default=None, metavar="E", help="with --sample: eta sampling -- keep the "
+                    "entries of probability >= min(E, sqrt(E) * exp(-entropy)), 0 <= E < 1 (default 0 = off)")
+    ap.add_argument("--typical-p", type=float, default=None, metavar="P", help="with --sample: locally typical sampling -- keep "
+                    "the entries whose surprise is nearest the entropy until they hold P of the mass, 0 < P <= 1 (default 1 = "
+                    "off); combines with --temperature and --top-k, not with --top-p, --min-p, --epsilon-cutoff, --eta-cutoff")
     ap.add_argument("--without-replacement", action="store_true", help="with --sample: draw the N candidates WITHOUT "
                     "replacement by stochastic beam search on the device -- N distinct messages for the cost of one beam "
                     "search, the first an ordinary sample; implies --merge-copies; combines with --temperature, --sample-seed, "
@@ -202,6 +213,7 @@ def parse_args(argv):
         check_require_args(a)
         check_ensemble_args(a)
         check_sample_args(a)
+        check_cut_args(a)
         check_retrieve_args(a)
     except ValueError as e:
         ap.error(str(e))
@@ -781,6 +793,40 @@ def check_sample_args(a, vocab_size: int = None):
     return a
 
 
+CUT_OPTIONS = (("min_p", "--min-p"), ("epsilon_cutoff", "--epsilon-cutoff"), ("eta_cutoff", "--eta-cutoff"),
+               ("typical_p", "--typical-p"))
+
+
+def check_cut_args(a):
+    """Validates the truncation cuts of --sample (--min-p, --epsilon-cutoff, --eta-cutoff, --typical-p; no GPU, no DataSet
+    needed) after check_sample_args has passed what --sample itself refuses; raises ValueError naming the option on a conflict
+    or an out-of-range value.  An option not given stays None (off)."""
+    given = [(name, flag) for name, flag in CUT_OPTIONS if getattr(a, name, None) is not None]
+    if not given:
+        return a
+    flags = ", ".join(flag for _, flag in given)
+    if a.stage != "test":
+        raise ValueError("%s only apply to the test stage" % flags)
+    if a.sample is None:
+        raise ValueError("%s only apply with --sample" % flags)
+    if getattr(a, "without_replacement", False):
+        raise ValueError("--without-replacement samples from the whole tempered distribution: it does not combine with %s"
+                         % flags)
+    for name, flag in given:
+        v = getattr(a, name)
+        if name == "typical_p":
+            if not 0 < v <= 1:                               # (also refuses nan)
+                raise ValueError("%s %g: must be in (0, 1] (1 = off)" % (flag, v))
+        elif not 0 <= v < 1:
+            raise ValueError("%s %g: must be in [0, 1) (0 = off)" % (flag, v))
+    if given[-1][0] == "typical_p" and a.typical_p < 1:
+        others = (["--top-p"] if a.top_p != 1.0 else []) + [flag for name, flag in given[:-1] if getattr(a, name) > 0]
+        if others:
+            raise ValueError("--typical-p keeps a band of the distribution, not its head: it does not combine with %s"
+                             % ", ".join(others))
+    return a
+
+
 class Run:
     def __init__(self, a):
         self.a = a
@@ -1113,11 +1159,13 @@ class Run:
         a, cfg = self.a, self.cfg
         test_index = self.all_index["test"]
         lines, samples, n_tok, t0 = [], [], 0, time.time()
+        cuts = {kw: getattr(a, name) for (name, _), kw in zip(CUT_OPTIONS, ("min_p", "epsilon", "eta", "typical_p"))
+                if getattr(a, name, None) is not None}
         for lo in range(0, len(mine), cfg.test_batch_size):
             idx = mine[lo:lo + cfg.test_batch_size]
             db = self.device_batch(store, idx)
             toks, lens, _, logp = search.sample(db, a.sample, temperature=a.temperature,
-                                                top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed, keys=idx)
+                                                top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed, keys=idx, **cuts)
             best = search.best_sample(toks, lens, logp)
             values = None
             if a.rerank == "mbr_bleu":                       # expected BLEU among the candidates themselves: no scoring pass
