@@ -197,6 +197,7 @@ SIGNATURES = {
     "fira_beam_select_scored": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P]),
     "fira_beam_select_gumbel": (_I, [_P, _DP, _I, _I, _I, _F] + [_P] * 18),
     "fira_beam_select_required": (_I, [_P, _DP, _I, _I] + [_P] * 16),
+    "fira_contrastive_select": (_I, [_P, _DP, _I, _I, _I, _F] + [_P] * 19),
     "fira_greedy_advance": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_decode_step": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _P, _P]),
     "fira_decode_step_sample": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _F, _I, _F, _P, _P, _P, _I]),
@@ -207,6 +208,7 @@ SIGNATURES = {
     "fira_decoder_forward": (_I, [_P, _DP, _P, _P, _Z, _I, _P, _P, _P, _P]),
     "fira_decode_memory": (_P, [_DP, _P, _I, _I]),
     "fira_decode_mem_valid": (_P, [_DP, _P, _I, _I]),
+    "fira_decode_hidden": (_I, [_P, _DP, _P, _Z, _I, _I, _I, _P]),
 }
 
 

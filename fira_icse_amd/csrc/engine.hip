@@ -2504,6 +2504,23 @@ int fira_debug_chain(void* stream, int n, int mode, float* scratch) {
     return 0;
 }
 
+// The final decoder rows of the last fira_decode_step* call on this workspace: DecodePlan::x, the input of the generator
+// projection and of LinearTarget, copied into the caller's [B * n_beam, 256] buffer (one rows_move launch: capturable).
+// decode_step_body's last consume() leaves x materialised on both of its paths -- the fused LayerNorm prologue stores it
+// (LnA::x_out = pend_y = dp.x), the fallback's add_layernorm_fwd writes it -- and the generator product after it reads it.
+int fira_decode_hidden(void* stream, const fira_dims* d, void* workspace, size_t workspace_bytes, int B, int n_beam, int flags,
+                       float* out) {
+    if (!get_layout(d)) return 1;
+    FIRA_REQUIRE(workspace && out && B > 0 && n_beam >= 1, "fira_decode_hidden: bad argument");
+    FIRA_REQUIRE((flags & ~FIRA_DECODE_KV_BF16) == 0, "fira_decode_hidden: unknown flags %d", flags);
+    FIRA_REQUIRE((uintptr_t)out % 16 == 0, "fira_decode_hidden: out must be 16-byte aligned");
+    DecodePlan dp;
+    const size_t need = dp.build(workspace, *d, B, n_beam, flags);
+    FIRA_REQUIRE(need <= workspace_bytes, "fira_decode_hidden: workspace too small: need %zu bytes, got %zu (fira_decode_workspace_bytes_ex "
+                 "with the same flags)", need, workspace_bytes);
+    return rows_move((hipStream_t)stream, 0, dp.BR, FIRA_D, out, dp.x, nullptr, nullptr);
+}
+
 const float* fira_decode_memory(const fira_dims* d, void* workspace, int B, int n_beam) {
     if (!get_layout(d) || !workspace) return nullptr;
     DecodePlan dp;

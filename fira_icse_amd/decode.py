@@ -7,8 +7,8 @@ Here the encoder, the cross-attention K/V of all layers and ``LinearSource(memor
 hypothesis bookkeeping (probability products, -1 for finished rows, carried finished beams, descending sort, copy-id
 resolution) stays on the device with the reference's exact semantics.  ``beam = 1`` is the reference's "greedy".
 
-Every search (``greedy`` / ``greedy_many``, ``sample``, ``score``, ``beam``) is the same chunked step loop, driven by ``_Loop``:
-static buffers per ``Searcher._ws`` key, the steps captured once into hipGraphs of ``chunk`` steps, replayed chunk by chunk with
+Every search (``greedy`` / ``greedy_many``, ``sample``, ``score``, ``beam``, ``contrastive``) is the same chunked step loop,
+driven by ``_Loop``: static buffers per ``Searcher._ws`` key, the steps captured once into hipGraphs of ``chunk`` steps, replayed chunk by chunk with
 at most one device value read back between chunks.  A search supplies its state, its reset, its ``steps(lo, hi)`` (the library
 calls of those steps), its stop test and how its results are read out -- nothing else.
 """
@@ -1380,6 +1380,94 @@ class Searcher:
         loop.start(lambda lo, hi: self._sbs_steps(st, ws, B, n, lo, hi, temperature), lambda: self._sbs_reset(st, B, n),
                    lambda hi: bool(st["done"].item())).run()
         return self._family_result(loop, B, n, ("logp", "phi", "G"))
+
+    # ------------------------------------------------------------------ contrastive search: top-k look-ahead, degeneration penalty
+    @staticmethod
+    def _check_contrastive(members, k, alpha) -> float:
+        """The refusals of ``contrastive``, before anything is launched; returns alpha as a float."""
+        if members:
+            raise ValueError("contrastive does not combine with an ensemble (the hidden state it compares is one model's)")
+        if isinstance(k, bool) or not isinstance(k, int) or not 2 <= k <= 8:
+            raise ValueError("contrastive: k = %r outside 2..8" % (k,))
+        if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0.0 <= alpha <= 1.0:     # (also refuses nan)
+            raise ValueError("contrastive: alpha = %r must be a finite number in [0, 1]" % (alpha,))
+        return float(alpha)
+
+    def _contrastive_reset(self, st, B, k):
+        self._family_reset(st, ("p",), -1.0)
+        st["p"][0].view(B, k)[:, 0] = 1.0                     # slot 0 holds <start> with confidence 1; the others are void
+        for q in (0, 1):
+            st["prob"][q].fill_(1.0)
+        st["ended"].zero_()                                   # (hist needs no reset: step t reads the rows below t only)
+
+    def _contrastive_steps(self, st, ws, B, k, lo, hi, alpha):
+        """Steps lo..hi-1 of the beam's loop (``_family_steps``) with fira_decode_hidden + fira_contrastive_select as the
+        selection.  Neither call changes the step's ``dist`` and ``hidden`` nor the ``cur`` buffers, so after an eager step
+        the state still holds everything the selection saw."""
+        dims = C.byref(self.model.dims)
+
+        def select(lib, s, step, cur, nxt):
+            _lib.check(lib.fira_decode_hidden(s, dims, _lib.ptr(ws), ws.numel(), B, k, self.flags, _lib.ptr(st["hidden"])),
+                       "fira_decode_hidden")
+            _lib.check(lib.fira_contrastive_select(
+                s, dims, B, k, step, alpha, _lib.ptr(st["dist"]), _lib.ptr(st["hidden"]), _lib.ptr(st["fin"]), _lib.ptr(st["sou"]),
+                _lib.ptr(st["sub"]), _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]), _lib.ptr(st["p"][cur]),
+                _lib.ptr(st["prob"][cur]), _lib.ptr(st["hist"]), _lib.ptr(st["ended"]), _lib.ptr(st["gen"][nxt]),
+                _lib.ptr(st["length"][nxt]), _lib.ptr(st["p"][nxt]), _lib.ptr(st["prob"][nxt]), _lib.ptr(st["parent"]),
+                _lib.ptr(st["pick"]), _lib.ptr(st["sim"]), _lib.ptr(st["score"])), "fira_contrastive_select")
+        self._family_steps(st, ws, B, k, lo, hi, select)
+
+    def _contrastive_loop(self, db: DeviceBatch, k: int, alpha: float, chunk: int, use_graphs: bool,
+                          constraints: Optional[Constraints] = None, prefix=None) -> _Loop:
+        """Encoder pass + reset of the state for one batch; returns the started loop (``contrastive`` runs it and reads the
+        result with ``_contrastive_result``)."""
+        alpha = self._check_contrastive(self.members, k, alpha)          # raises before anything is launched
+        B, T = db.B, self.cfg.tar_len
+        BR = B * k
+        con = self._active(constraints)                      # raises before anything is launched
+        rows = self._prefix_rows(prefix, B, con)             # likewise
+        make = lambda i32, f32: dict(self._beam_rows(i32, f32, BR), p=[f32(BR), f32(BR)], prob=[f32(B), f32(B)],
+                                     hist=f32(B, T, 256), hidden=f32(BR, 256), ended=i32(B), pick=i32(B), sim=f32(BR),
+                                     score=f32(BR), **self._edit_state(i32, f32, BR, B, con, True, rows, dist=True))
+        loop = _Loop(self, db, k, self._key(("contrastive", B, k, alpha), True, con, None, rows is not None), make, chunk,
+                     use_graphs)
+        st, ws = loop.st, loop.ws
+        if rows is not None:
+            self._fill_prefix(st, rows)
+        return loop.start(lambda lo, hi: self._contrastive_steps(st, ws, B, k, lo, hi, alpha),
+                          lambda: self._contrastive_reset(st, B, k), lambda hi: bool(st["done"].item()))
+
+    def _contrastive_result(self, loop, B, k):
+        st, T, cur = loop.st, self.cfg.tar_len, loop.hi & 1   # the ping-pong buffer the last step run wrote
+        gen, length = st["gen"][cur].view(B, k, T)[:, 0], st["length"][cur].view(B, k)[:, 0]
+        # a commit still running at tar_len takes slot 0, its most probable candidate (the candidates are in value order)
+        last = st["p"][cur].view(B, k)[:, 0]
+        running = (st["ended"] == 0) & (last > 0)
+        return gen.long(), length.long(), torch.where(running, st["prob"][cur] * last, st["prob"][cur])
+
+    @torch.no_grad()
+    def contrastive(self, db: DeviceBatch, k: int, alpha: float = 0.6, chunk: int = 4, use_graphs: bool = True,
+                    constraints: Optional[Constraints] = None, prefix=None):
+        """Contrastive search (Su et al., NeurIPS 2022; ``fira_contrastive_select``): the deterministic
+        search that looks one word ahead.  Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]),
+        the message's raw model probability as ``greedy`` returns it.
+
+        The ``k`` slots of a commit hold the chosen prefix and one of the k most probable next WORDS each; a step runs the
+        decoder on all of them and keeps the candidate with the largest (1 - ``alpha``) * p - ``alpha`` * sim, sim being the
+        largest cosine between the candidate's last decoder state and the states of the positions chosen before: a word
+        that would lead the message back to where it has been is passed over.  ``alpha = 0`` is ``greedy(merge_copies=True)``.
+        A message that reaches tar_len without <eos> takes its most probable last word (nothing is left to look ahead to).
+
+        The loop is the beam's (``_family_steps``): prepare, step, edit chain, then ``fira_decode_hidden`` and the selection,
+        captured into hipGraphs of ``chunk`` steps; the edit chain always merges copy entries into words (else the k
+        candidates could be k entries of one word), and ``constraints`` / ``prefix`` pass through it unchanged.  The state
+        is keyed ("contrastive", B, k, alpha, "merge"[, "prefix"][, constraints]): alpha is baked into the captured launches.
+        It owns the history [B, tar_len, 256], the hidden rows, the per-slot confidences and the per-commit probability and
+        ``ended`` flag; after a call ``pick`` / ``sim`` / ``score`` hold the last step's choice.  A ``ValueError`` before
+        anything is launched on an ensemble, ``k`` outside 2..8 or ``alpha`` outside [0, 1] or not finite."""
+        loop = self._contrastive_loop(db, k, alpha, chunk, use_graphs, constraints, prefix)
+        loop.run()
+        return self._contrastive_result(loop, db.B, k)
 
     def best(self, gen, length, prob) -> List[List[int]]:
         """argmax-probability hypothesis per item, first on ties (run_model.py:351-352)."""

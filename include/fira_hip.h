@@ -948,6 +948,39 @@ int fira_beam_select_required(void* stream, const fira_dims* d, int B, int n_bea
                               const int32_t* required /* device, [B, 4] */, const int32_t* n_required /* device, [B] */,
                               int32_t* met_out /* [B*n_beam] or NULL */);
 
+/* Contrastive search: the selection of one step (csrc/contrastive.hip; additive, the ABI version is unchanged; Su et al.,
+ * NeurIPS 2022).  The state is the beam family's with k slots per commit, 2 <= k <= 8.  Entering step `step`, the k slots of
+ * a running commit hold the same chosen prefix gen[0 .. step - 1]; slot j also holds one candidate next word v_j at position
+ * `step` (len = step + 1) with its model confidence p_in[j], or is VOID (p_in[j] not > 0).  The decoder step has consumed v_j:
+ * hidden[j] is its last hidden state (fira_decode_hidden), dist[j] the distribution after it (as the edit chain left it), and
+ * finished[j] says that v_j is <eos> (fira_beam_prepare).  hist[b, i] (i < step) is the hidden state stored when position i
+ * was chosen.  Per commit b with ended[b] == 0:
+ *   1. sim_j = max_{i < step} cos(hidden[j], hist[b, i]),  cos(a, c) = dot / (sqrt(|a|^2) * sqrt(|c|^2)) in fp32, 0 where a
+ *      squared norm is 0; sim_j = 0 at step 0.
+ *   2. score_j = fp32(fp32((1 - alpha) * p_in[j]) - fp32(alpha * sim_j)), 1 - alpha formed in fp32; void slots take no part.
+ *   3. j* = the slot of the largest score, the lowest slot on ties.  hist[b, step] = hidden[j*];
+ *      prob_out[b] = fp32(prob_in[b] * p_in[j*]).
+ *   4. finished[j*]: the commit ENDS.  Every slot receives hypothesis j* (gen, len, p_in[j*]) and ended[b] = 1.
+ *   5. otherwise the new candidates are the k largest POSITIVE entries of dist[j*], by (value descending, index ascending).
+ *      Slot m receives gen[j*] with the word of candidate m appended (the entry itself below vocab, the sou / sub_token id of
+ *      its copy slot above, as fira_beam_select resolves it), len + 1 and p_out[m] = the entry's value; where fewer than k
+ *      entries are positive the remaining slots are void: gen[j*] unchanged, p_out = -1.
+ *   parent[r] = b * k + j* for every row of the commit.
+ * A commit with ended[b] != 0, or with no live slot (it is marked ended), is copied through: gen, len, p, prob unchanged,
+ * parent = the row itself, hist untouched.  pick_out [B] (j*, or -1 for a commit copied through), sim_out and score_out [B*k]
+ * (0 for void slots and commits copied through) are optional.  alpha = 0 is greedy search over the same rows.
+ * 2 <= k <= 8, 2 <= tar_len <= 64, 0 <= step <= tar_len - 2, vocab in 9 .. 25 600, sou_len + sub_len <= 1 024, alpha finite
+ * in [0, 1]; anything else returns non-zero with the reason in fira_last_error() and nothing is launched.  One workgroup of
+ * 1 024 threads per commit: wave j forms slot j's cosines with DPP reductions, then the ONE picked row of dist is streamed;
+ * vector stores only, no global atomics.                                                                                */
+int fira_contrastive_select(void* stream, const fira_dims* d, int B, int k, int step, float alpha, const float* dist,
+                            const float* hidden /* [B*k, 256] */, const int32_t* finished, const int32_t* sou,
+                            const int32_t* sub_token, const int32_t* gen_in, const int32_t* len_in, const float* p_in /* [B*k] */,
+                            const float* prob_in /* [B] */, float* hist /* [B, tar_len, 256], read and appended */,
+                            int32_t* ended /* [B] */, int32_t* gen_out, int32_t* len_out, float* p_out, float* prob_out,
+                            int32_t* parent, int32_t* pick_out /* [B] or NULL */, float* sim_out /* [B*k] or NULL */,
+                            float* score_out /* [B*k] or NULL */);
+
 /* Greedy search bookkeeping (the same loop at beam 1 without the [B, vocab+S] distribution): consumes the arg-max
  * index / probability fira_decode_step wrote, resolves copy indices through sou / sub_token, appends the id at
  * out[b, step+1], multiplies prob, bumps length, clears alive[b] at <eos>, writes the next step's input ids to `tokens`
@@ -1191,6 +1224,14 @@ int fira_decoder_forward(void* stream, const fira_dims* d, const float* params, 
 /* read-only views into a decode workspace (device pointers), for tests and the Python driver */
 const float*   fira_decode_memory(const fira_dims* d, void* workspace, int B, int n_beam);
 const int32_t* fira_decode_mem_valid(const fira_dims* d, void* workspace, int B, int n_beam);
+
+/* The decoder's last hidden state of every row (additive, the ABI version is unchanged): copies the final LayerNorm output of
+ * the last fira_decode_step* call on `workspace` -- the [B*n_beam, 256] input of the generator projection and of the copy
+ * head -- into out (16-byte aligned).  B, n_beam and flags are those of the step call.  One copy launch of B*n_beam KB on
+ * `stream`, capturable; the workspace is only read.  Non-zero with the reason in fira_last_error() on a bad argument or a
+ * workspace that is too small, before any launch.                                                                       */
+int fira_decode_hidden(void* stream, const fira_dims* d, void* workspace, size_t workspace_bytes, int B, int n_beam, int flags,
+                       float* out /* [B*n_beam, 256] */);
 
 /* ---- host-side helper (CPU only, no device work) -----------------------------------------------------------------
  * The index lists of fira_batch from one collated batch (int64 id arrays as the reference's Dataset.py produces them,
