@@ -9,6 +9,7 @@ from typing import Sequence, Tuple
 import numpy as np
 import torch
 
+from search_kit import dims_of
 from fira_icse_amd.config import EOS, START
 
 
@@ -58,10 +59,6 @@ def argmax_ref(row: np.ndarray) -> Tuple[int, np.float32]:
     """Largest value, lowest index among equals (np.argmax returns the first maximum)."""
     i = int(np.argmax(row))
     return i, row[i]
-
-
-def dims_of(cfg):
-    return cfg.vocab_size, cfg.sou_len, cfg.sub_token_len
 
 
 def _masks(gen, length, sou, sub, dims, constraints, rows_per_commit) -> np.ndarray:

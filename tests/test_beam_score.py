@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 import util
+from search_kit import device_dims as dims
 import beamscore_ref as R
 from fira_icse_amd import _lib
-from fira_icse_amd.config import FiraConfig
 from fira_icse_amd.decode import BeamScoring
 from run_model import check_scoring_args, nbest_record, parse_args, scoring_from_args
 
@@ -172,13 +172,6 @@ def test_header_declares_and_library_exports_the_entry():
     assert "#define FIRA_ABI_VERSION 11" in header
     lib = _lib.lib()
     assert lib.fira_abi_version() == 11 and hasattr(lib, "fira_beam_select_scored") and "fira_beam_select_scored" in _lib.SIGNATURES
-
-
-def dims(**kw):
-    d = _lib.make_dims(FiraConfig())
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
 
 
 def call(d=None, B=2, beam=4, groups=2, diversity=0.5, inv_lp=16, key_out=16, dist=16):

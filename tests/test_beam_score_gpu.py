@@ -8,8 +8,9 @@ import pytest
 import torch
 
 import beamscore_ref as R
+from search_kit import device_dims
 from fira_icse_amd import _lib
-from fira_icse_amd.config import EOS, START, FiraConfig
+from fira_icse_amd.config import EOS, START
 
 pytestmark = pytest.mark.gpu
 
@@ -17,15 +18,8 @@ SMALL = dict(vocab=37, sou_len=6, sub_len=5, tar_len=8)            # W = 48
 MODEL = {}                                                          # the reference geometry (FiraConfig's own dims)
 
 
-def device_dims(geo):
-    d = _lib.make_dims(FiraConfig())
-    for k, v in geo.items():
-        setattr(d, k, v)
-    return d
-
-
 def geometry(geo):
-    d = device_dims(geo)
+    d = device_dims(**geo)
     return d.vocab, d.sou_len, d.sub_len, d.tar_len
 
 
@@ -71,7 +65,7 @@ def launch(st, dist, scored, inv_lp=None, groups=1, lam=0.0, want_key=True):
     g_out = torch.full_like(gen, -7)
     l_out, p_out, parent = torch.full_like(length, -7), torch.full_like(prob, -7.0), torch.full_like(length, -7)
     key = torch.full_like(prob, -7.0) if scored and want_key else None
-    dd = device_dims(st["geo"])
+    dd = device_dims(**st["geo"])
     args = (_lib.cur_stream(), C.byref(dd), B, beam, _lib.ptr(dist_d), _lib.ptr(fin), _lib.ptr(active), _lib.ptr(done), _lib.ptr(sou),
             _lib.ptr(sub), _lib.ptr(gen), _lib.ptr(length), _lib.ptr(prob), _lib.ptr(g_out), _lib.ptr(l_out), _lib.ptr(p_out),
             _lib.ptr(parent))

@@ -3,8 +3,6 @@ an active one is deterministic over graphs / chunks / runs, composes with merge 
 selection under the numpy statement (beamscore_ref.py), and the command line writes what it says."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,7 +10,8 @@ import torch
 
 import util
 import beamscore_ref as R
-from fira_icse_amd import data, synth
+from search_kit import golden_search, run_cli
+from fira_icse_amd import synth
 from fira_icse_amd.config import FiraConfig
 from fira_icse_amd.decode import BeamScoring, Constraints, _Loop
 
@@ -28,16 +27,8 @@ def setup():
     """The golden synthetic commits under the peaked weights of the decode parity tests (util.peaked_state_dict, seed 2).  Under
     unsharpened weights the probability product of a hypothesis that a length penalty keeps running underflows fp32 to 0 within
     a dozen steps, every key is -inf and the search decides nothing."""
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    from fira_icse_amd.decode import Searcher
-    cfg = FiraConfig()
-    store = data.process_raw(cfg, util.load_golden_raw())
-    ids = data.split_index(*util.GOLDEN_SPLIT, seed=0)["test"][:B]
-    torch.manual_seed(0)
-    model = TransModel(cfg, init=False)
-    model.load_state_dict(util.peaked_state_dict(reference_init_state_dict(cfg), seed=2))
-    model.eval()
-    return cfg, model, DeviceBatch(store.batch(ids), cfg), Searcher(model)
+    g = golden_search(weights="peaked", batch=B, seed=2)
+    return g.cfg, g.model, g.db, g.searchers[0]
 
 
 def same(a, b):
@@ -152,14 +143,6 @@ def test_every_step_is_a_valid_selection(setup, sc, beam):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def run(args, cwd):
-    env = dict(os.environ, PYTHONPATH=util.REPO)
-    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 def test_cli_scored_search_and_options_off(tmp_path):
     from fira_icse_amd.model import reference_init_state_dict
     root = str(tmp_path)
@@ -170,13 +153,13 @@ def test_cli_scored_search_and_options_off(tmp_path):
     base = ["test", "--splits", "16,4,4", "--test-batch-size", "3"]
     out_f, nbest_f = os.path.join(root, "OUTPUT", "output_fira"), os.path.join(root, "OUTPUT", "output_fira_nbest")
     # without the options: the output recorded before they existed, byte for byte, and an n-best line without a key
-    run(base + ["--nbest"], root)
+    run_cli(base + ["--nbest"], root)
     gold = json.load(open(os.path.join(util.GOLDEN, "decode_ref.json")))["beam3"]
     assert open(out_f, "rb").read() == "".join(l + "\n" for l in gold).encode()
     for rec in open(nbest_f).read().split("\n")[:-1]:
         assert sorted(json.loads(rec)) == ["messages", "prob"]
     os.remove(nbest_f)
-    run(base + ["--beam", "4", "--beam-groups", "2", "--diversity-penalty", "0.5", "--length-penalty", "1", "--nbest"], root)
+    run_cli(base + ["--beam", "4", "--beam-groups", "2", "--diversity-penalty", "0.5", "--length-penalty", "1", "--nbest"], root)
     lines = open(out_f).read().split("\n")
     recs = open(nbest_f).read().split("\n")
     assert len(lines) == 5 and lines[-1] == "" and len(recs) == 5 and recs[-1] == ""

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import util
+from search_kit import device_dims as dims
 import constrain_ref as R
 from fira_icse_amd import _lib
 from fira_icse_amd.config import EOS, PAD, START, UNK, FiraConfig
@@ -127,14 +128,6 @@ def test_header_declares_and_library_exports_the_entry():
     assert "#define FIRA_ABI_VERSION 11" in header
     lib = _lib.lib()
     assert lib.fira_abi_version() == 11 and hasattr(lib, "fira_constrain_dist") and "fira_constrain_dist" in _lib.SIGNATURES
-
-
-def dims(**kw):
-    cfg = FiraConfig()
-    d = _lib.make_dims(cfg)
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
 
 
 def call(d=None, R_=6, rpc=3, n=2, M=3, n_banned=1, gen=16, length=16, sou=16, sub=16, banned=16, dist=16, best_id=16, best_p=16):

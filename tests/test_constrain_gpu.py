@@ -4,8 +4,6 @@ properties of the messages, the options-off paths, the graph cache key, and the 
 import ctypes as C
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,7 +11,8 @@ import torch
 
 import constrain_ref as R
 import util
-from fira_icse_amd import _lib, data, synth, text
+from search_kit import best_pair, bits, device_dims, golden_search, messages, offset_rows, outside_untouched, run_cli, same_search
+from fira_icse_amd import _lib, synth
 from fira_icse_amd.config import EOS, START, UNK, FiraConfig
 from fira_icse_amd.decode import Constraints
 
@@ -70,36 +69,23 @@ def reference(case, c):
     return mask, dist, out, np.array([b[0] for b in best], dtype=np.int32), np.array([b[1] for b in best], dtype=np.float32)
 
 
-def device_dims(dims, T):
-    d = _lib.make_dims(FiraConfig())
-    d.vocab, d.sou_len, d.sub_len, d.tar_len = dims[0], dims[1], dims[2], T
-    return d
-
-
 def run_kernel(case, c, dist, want_best, offset=1):
     """The entry on a copy of ``dist`` that starts ``offset`` floats into its buffer (rows then begin at every alignment)."""
     dev = "cuda"
     n_rows, W = dist.shape
-    buf = torch.zeros(n_rows * W + offset + 8, dtype=torch.float32, device=dev)
-    d_dev = buf[offset:offset + n_rows * W].view(n_rows, W)
-    d_dev.copy_(torch.from_numpy(dist))
+    buf, d_dev = offset_rows(dist, offset)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     gen, length, sou, sub = t(case["gen"]), t(case["length"]), t(case["sou"]), t(case["sub"])
     banned = torch.tensor(list(c.banned) or [0], dtype=torch.int32, device=dev)
-    best_id = torch.full((n_rows,), -7, dtype=torch.int32, device=dev) if want_best else None
-    best_p = torch.full((n_rows,), -7.0, dtype=torch.float32, device=dev) if want_best else None
-    dd = device_dims(case["dims"], case["T"])
+    best_id, best_p = best_pair(n_rows, want_best)
+    dd = device_dims(*case["dims"], case["T"])
     _lib.check(_lib.lib().fira_constrain_dist(_lib.cur_stream(), C.byref(dd), n_rows, case["rpc"], _lib.ptr(gen), _lib.ptr(length),
                                               _lib.ptr(sou), _lib.ptr(sub), c.no_repeat_ngram, c.min_length, _lib.ptr(banned),
                                               len(c.banned), _lib.ptr(d_dev), _lib.ptr(best_id), _lib.ptr(best_p)),
                "fira_constrain_dist")
     torch.cuda.synchronize()
-    assert float(buf[:offset].abs().sum()) == 0 and float(buf[offset + n_rows * W:].abs().sum()) == 0      # nothing outside the rows
+    outside_untouched(buf, offset, n_rows * W)                                         # nothing outside the rows
     return d_dev.cpu(), None if best_id is None else best_id.cpu(), None if best_p is None else best_p.cpu()
-
-
-def bits(x):
-    return (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).contiguous().view(torch.int32)
 
 
 def test_inputs_are_not_vacuous():
@@ -155,18 +141,8 @@ CASES = [Constraints(2, 3, (UNK,)), Constraints(1, 0, ())]
 
 @pytest.fixture(scope="module")
 def setup():
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    from fira_icse_amd.decode import Searcher
-    cfg = FiraConfig()
-    raw = util.load_golden_raw()
-    store = data.process_raw(cfg, raw)
-    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
-    ids = idx["test"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    model = TransModel(cfg, init=False)
-    model.load_state_dict(util.peaked_state_dict(reference_init_state_dict(cfg), seed=2))
-    model.eval()
-    return cfg, model, DeviceBatch(store.batch(ids), cfg), Searcher(model)
+    g = golden_search(weights="peaked", seed=2)
+    return g.cfg, g.model, g.db, g.searchers[0]
 
 
 @pytest.fixture(scope="module")
@@ -178,21 +154,6 @@ def refs(setup):
         out[c] = dict(beam=tuple(t.cpu() for t in R.beam_constrained(search, db, 3, c)), greedy=R.greedy_constrained(search, db, c))
     out[None] = dict(beam=tuple(t.cpu().clone() for t in search.beam(db, 3)), greedy=tuple(t.cpu().clone() for t in search.greedy(db)))
     return out
-
-
-def same_search(got, want):
-    """The equality test_decode_gpu.py holds ``beam`` to against ``beam_torch``: lengths and probabilities equal, ids equal
-    inside the lengths."""
-    (gen, length, p), (gen_t, len_t, p_t) = [tuple(t.cpu() for t in x) for x in (got, want)]
-    assert torch.equal(length, len_t)
-    assert torch.equal(p, p_t)
-    live = torch.arange(gen.shape[-1])[(None,) * (gen.dim() - 1)] < length[..., None]
-    assert torch.equal(gen * live, gen_t * live)
-
-
-def messages(gen, length):
-    gen, length = gen.cpu().reshape(-1, gen.shape[-1]).tolist(), length.cpu().reshape(-1).tolist()
-    return [row[1:n] for row, n in zip(gen, length)]
 
 
 def check_properties(msgs, c, T):
@@ -281,14 +242,6 @@ def test_kernel_with_everything_off_reports_the_steps_own_best(setup):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def run(args, cwd):
-    env = dict(os.environ, PYTHONPATH=util.REPO)
-    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 def test_cli_constrained_search(tmp_path):
     from fira_icse_amd.model import reference_init_state_dict
     root = str(tmp_path)
@@ -298,10 +251,10 @@ def test_cli_constrained_search(tmp_path):
     torch.save(util.peaked_state_dict(reference_init_state_dict(cfg), seed=2), os.path.join(root, "best_model.pt"))
     base = ["test", "--splits", "16,4,4", "--test-batch-size", "3"]
     out_f = os.path.join(root, "OUTPUT", "output_fira")
-    run(base, root)                                          # without the options: the recorded output of the beam-3 search
+    run_cli(base, root)                                          # without the options: the recorded output of the beam-3 search
     gold = json.load(open(os.path.join(util.GOLDEN, "decode_ref.json")))["beam3"]
     assert open(out_f).read() == "".join(l + "\n" for l in gold)
-    run(base + ["--no-repeat-ngram", "2", "--min-length", "2"], root)
+    run_cli(base + ["--no-repeat-ngram", "2", "--min-length", "2"], root)
     lines = open(out_f).read().split("\n")
     assert len(lines) == 5 and lines[-1] == "" and lines[:-1] != gold
     for line in lines[:-1]:

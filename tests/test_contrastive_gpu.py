@@ -7,9 +7,9 @@ import pytest
 import torch
 
 import contrastive_ref as CR
-import util
-from fira_icse_amd import _lib, data
-from fira_icse_amd.config import EOS, START, UNK, FiraConfig
+from search_kit import device_dims, golden_search
+from fira_icse_amd import _lib
+from fira_icse_amd.config import EOS, START, UNK
 
 pytestmark = pytest.mark.gpu
 
@@ -27,15 +27,8 @@ GAP = 1e-4                                                          # a case who
 TOL = 5e-5
 
 
-def device_dims(geo):
-    d = _lib.make_dims(FiraConfig())
-    for k, v in geo.items():
-        setattr(d, k, v)
-    return d
-
-
 def geometry(geo):
-    d = device_dims(geo)
+    d = device_dims(**geo)
     return d.vocab, d.sou_len, d.sub_len, d.tar_len
 
 
@@ -124,7 +117,7 @@ def launch(st, alpha, optional=True):
         torch.full_like(length, -7)
     prob_out = torch.full_like(prob, -7.0)
     pick, sim, score = (torch.full_like(ended, -7), torch.full_like(p, -7.0), torch.full_like(p, -7.0)) if optional else (None,) * 3
-    dd = device_dims(st["geo"])
+    dd = device_dims(**st["geo"])
     _lib.check(_lib.lib().fira_contrastive_select(
         _lib.cur_stream(), C.byref(dd), B, k, step, float(alpha), _lib.ptr(dist), _lib.ptr(hidden), _lib.ptr(fin), _lib.ptr(sou),
         _lib.ptr(sub), _lib.ptr(gen), _lib.ptr(length), _lib.ptr(p), _lib.ptr(prob), _lib.ptr(hist), _lib.ptr(ended),
@@ -256,12 +249,12 @@ def test_refusals_return_non_zero_with_a_message():
                                       (dict(SMALL, sou_len=1000, sub_len=25), 4, 0, 0.5, "memory slots"), (SMALL, 1, 0, 0.5, "k = 1"),
                                       (SMALL, 9, 0, 0.5, "k = 9"), (SMALL, 3, 7, 0.5, "step"), (SMALL, 3, -1, 0.5, "step"),
                                       (SMALL, 3, 0, 1.5, "alpha"), (SMALL, 3, 0, float("nan"), "alpha"), (SMALL, 3, 0, -0.1, "alpha")):
-        dd = device_dims(geo)
+        dd = device_dims(**geo)
         args = [_lib.cur_stream(), C.byref(dd), B, k, step, alpha] + [C.c_void_p(16)] * 19
         assert _lib.lib().fira_contrastive_select(*args) != 0
         msg = _lib.lib().fira_last_error().decode()
         assert "fira_contrastive_select" in msg and word in msg, msg
-    dd = device_dims(SMALL)
+    dd = device_dims(**SMALL)
     args = [_lib.cur_stream(), C.byref(dd), B, 3, 0, 0.5] + [C.c_void_p(16)] * 16 + [None] * 3
     args[6 + 3] = None                                             # sou
     assert _lib.lib().fira_contrastive_select(*args) != 0 and b"null pointer" in _lib.lib().fira_last_error()
@@ -275,16 +268,8 @@ K = 3
 
 @pytest.fixture(scope="module")
 def setup():
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    from fira_icse_amd.decode import Searcher
-    cfg = FiraConfig(tar_len=MODEL_TAR_LEN)
-    store = data.process_raw(cfg, util.load_golden_raw())
-    ids = data.split_index(*util.GOLDEN_SPLIT, seed=0)["test"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    model = TransModel(cfg, init=False)
-    model.load_state_dict(reference_init_state_dict(cfg))          # untrained: every entry of a row is positive
-    model.eval()
-    return cfg, model, DeviceBatch(store.batch(ids), cfg), Searcher(model)
+    g = golden_search(tar_len=MODEL_TAR_LEN)                       # untrained: every entry of a row is positive
+    return g.cfg, g.model, g.db, g.searchers[0]
 
 
 def test_alpha_zero_is_greedy_search_over_words(setup):

@@ -10,8 +10,6 @@ band edge allows for with rel * (|ln q_i| + H) >= 1e-4 * H."""
 import ctypes as C
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,8 +18,8 @@ import torch
 import cut_ref
 import sample_ref
 import util
-from fira_icse_amd import _lib, data, synth
-from fira_icse_amd.config import FiraConfig
+from search_kit import golden_search, run_cli, seed_tensor, spread_state_dict
+from fira_icse_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -29,28 +27,11 @@ REL = 1e-4
 OFF = dict(min_p=0.0, epsilon=0.0, eta=0.0, typical_p=1.0)
 
 
-def spread_state_dict(cfg, seed=2):
-    """Weights whose step distributions have real spread (the peaked fixture weights put ~all mass on one entry)."""
-    from fira_icse_amd.model import reference_init_state_dict
-    torch.manual_seed(0)
-    sd = util.perturb_state_dict(reference_init_state_dict(cfg), seed=seed)
-    sd["out_fc.weight"] = sd["out_fc.weight"] * 10.0
-    sd["copy_net.LinearRes.weight"] = sd["copy_net.LinearRes.weight"] * 6.0
-    return sd
-
-
 @pytest.fixture(scope="module")
 def setup():
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    cfg = FiraConfig()
-    raw = util.load_golden_raw()
-    store = data.process_raw(cfg, raw)
-    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
-    ids = idx["test"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    peaked = TransModel(cfg, init=False)
-    peaked.load_state_dict(util.peaked_state_dict(reference_init_state_dict(cfg), seed=2))
-    peaked.eval()
+    from fira_icse_amd.model import TransModel
+    g = golden_search(weights="peaked", searchers=0, seed=2)
+    cfg = g.cfg
     spread = TransModel(cfg, init=False)
     spread.load_state_dict(spread_state_dict(cfg))
     spread.eval()
@@ -59,12 +40,7 @@ def setup():
     copyish = TransModel(cfg, init=False)
     copyish.load_state_dict(sd)
     copyish.eval()
-    return cfg, store, ids, peaked, spread, copyish, DeviceBatch(store.batch(ids), cfg)
-
-
-def seed_tensor(seed):
-    seed &= (1 << 64) - 1
-    return torch.tensor([seed - (1 << 64) if seed >= 1 << 63 else seed], dtype=torch.int64, device="cuda")
+    return cfg, g.store, g.ids, g.model, spread, copyish, g.db
 
 
 def step_sample(search, ws, B, n, step, tok, key, seed, T, k, p, dist, best_id, best_p, flags=0):
@@ -356,14 +332,6 @@ def test_argument_errors_name_the_argument(setup):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def run(args, cwd):
-    env = dict(os.environ, PYTHONPATH=util.REPO)
-    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 def test_cli_epsilon_cutoff_with_mbr_end_to_end(setup, tmp_path):
     """run_model.py test --sample 4 --epsilon-cutoff 0.02 --rerank mbr_bleu on the synthetic data set: the files are well
     formed, the candidates are Searcher.sample's (the test split is the fixture's batch, keyed by its position), and every
@@ -384,7 +352,7 @@ def test_cli_epsilon_cutoff_with_mbr_end_to_end(setup, tmp_path):
     B, n, W, V, L = db.B, 4, cfg.out_len, cfg.vocab_size, cfg.sou_len
     written = {}
     for name, flags, kw in (("cut", ["--epsilon-cutoff", "0.02"], dict(epsilon=0.02)), ("plain", [], {})):
-        run(base + flags, root)
+        run_cli(base + flags, root)
         test_index = json.load(open(os.path.join(root, "all_index")))["test"]
         lines, recs = open(out_f).read().split("\n"), [json.loads(l) for l in open(samp_f).read().strip().split("\n")]
         assert len(lines) == B + 1 and lines[-1] == "" and len(recs) == B

@@ -7,9 +7,8 @@ import pytest
 import torch
 
 import util
-from fira_icse_amd import _lib, data
-from fira_icse_amd.config import FiraConfig
-from test_sample_gpu import spread_state_dict
+from search_kit import bits, golden_search, spread_state_dict
+from fira_icse_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -17,33 +16,25 @@ CHUNKS = [1, 4, 29]            # one step per graph; a size that does not divide
 SAMPLE_KW = dict(seed=3, temperature=1.5)
 
 
-def bits(x):
-    return x.contiguous().view(torch.int32) if x.dtype == torch.float32 else x
-
-
 @pytest.fixture(scope="module")
 def setup():
     from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    cfg = FiraConfig()
+    g = golden_search(weights="peaked", searchers=0, seed=2)
+    cfg = g.cfg
     assert cfg.tar_len - 1 == 29
-    store = data.process_raw(cfg, util.load_golden_raw())
-    ids = data.split_index(*util.GOLDEN_SPLIT, seed=0)["test"][:util.GOLDEN_B]
-    hb = store.batch(ids)
 
     def model_of(sd):
         m = TransModel(cfg, init=False)
         m.load_state_dict(sd)
         m.eval()
         return m
-    torch.manual_seed(0)
-    peaked = model_of(util.peaked_state_dict(reference_init_state_dict(cfg), seed=2))
     spread = model_of(spread_state_dict(cfg))
     torch.manual_seed(0)
     sd = util.peaked_state_dict(reference_init_state_dict(cfg), seed=2)
     sd["out_fc.bias"][1] += 30.0                                     # <eos> early: every hypothesis ends well before tar_len
     short = model_of(sd)
-    two = DeviceBatch(store.batch(ids[:2]), cfg)                     # the commits whose beam-3 hypotheses all end early
-    return cfg, hb, dict(peaked=peaked, spread=spread, short=short, two=two), DeviceBatch(hb, cfg)
+    two = DeviceBatch(g.store.batch(g.ids[:2]), cfg)                 # the commits whose beam-3 hypotheses all end early
+    return cfg, g.host_batch, dict(peaked=g.model, spread=spread, short=short, two=two), g.db
 
 
 def run_search(kind, models, db, cand=None, **kw):

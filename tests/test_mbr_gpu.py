@@ -4,8 +4,6 @@ candidates against the string scorer (``==``), and ``run_model.py test --sample 
 import json
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,7 +11,8 @@ import torch
 
 import util
 import mbr_ref as R
-from fira_icse_amd import _lib, data, metrics, ops, synth
+from search_kit import golden_search, run_cli, spread_state_dict
+from fira_icse_amd import _lib, metrics, ops, synth
 from fira_icse_amd.config import FiraConfig
 
 pytestmark = pytest.mark.gpu
@@ -98,28 +97,10 @@ def test_kernel_refuses_what_it_cannot_serve(case_list):
 
 
 # ------------------------------------------------------------------------------------------------ Searcher.mbr
-def spread_state_dict(cfg, seed=2):
-    """Weights whose step distributions have real spread (the sampling tests' model)."""
-    from fira_icse_amd.model import reference_init_state_dict
-    torch.manual_seed(0)
-    sd = util.perturb_state_dict(reference_init_state_dict(cfg), seed=seed)
-    sd["out_fc.weight"] = sd["out_fc.weight"] * 10.0
-    sd["copy_net.LinearRes.weight"] = sd["copy_net.LinearRes.weight"] * 6.0
-    return sd
-
-
 @pytest.fixture(scope="module")
 def sampled():
-    from fira_icse_amd.model import TransModel, DeviceBatch
-    from fira_icse_amd.decode import Searcher
-    cfg = FiraConfig()
-    store = data.process_raw(cfg, util.load_golden_raw())
-    ids = data.split_index(*util.GOLDEN_SPLIT, seed=0)["test"][:util.GOLDEN_B]
-    model = TransModel(cfg, init=False)
-    model.load_state_dict(spread_state_dict(cfg))
-    model.eval()
-    search = Searcher(model)
-    db = DeviceBatch(store.batch(ids), cfg)
+    g = golden_search(weights="spread")
+    search, db = g.searchers[0], g.db
     draws = [search.sample(db, 4, temperature=1.3, top_k=30, seed=seed) for seed in (5, 6)]
     return search, draws
 
@@ -169,14 +150,6 @@ def test_searcher_mbr_refuses_bad_arguments(sampled, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def run(args, cwd):
-    env = dict(os.environ, PYTHONPATH=util.REPO)
-    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 def test_cli_rerank_mbr_bleu(tmp_path):
     """The ``mbr_bleu`` values are compared with the string scorer on the WORDS of the written candidates: no variable map of
     the synthetic root maps a placeholder back to a vocabulary word (asserted below), so ids and words are interchangeable."""
@@ -190,7 +163,7 @@ def test_cli_rerank_mbr_bleu(tmp_path):
     base = ["test", "--splits", "16,4,4", "--test-batch-size", "3"]
     opts = ["--sample", "4", "--temperature", "1.2", "--top-k", "30", "--sample-seed", "5"]
     out_f, samp_f = os.path.join(root, "OUTPUT", "output_fira"), os.path.join(root, "OUTPUT", "output_fira_samples")
-    run(base + opts + ["--rerank", "mbr_bleu"], root)
+    run_cli(base + opts + ["--rerank", "mbr_bleu"], root)
     lines, recs = open(out_f).read().split("\n"), [json.loads(l) for l in open(samp_f).read().strip().split("\n")]
     assert len(lines) == 5 and lines[-1] == "" and len(recs) == 4
     differ = 0
@@ -204,7 +177,7 @@ def test_cli_rerank_mbr_bleu(tmp_path):
         differ += pick != int(np.argmax(rec["logp"]))
     print("commits whose pick differs from the arg-max of logp: %d of 4" % differ)
     # the same command without --rerank, run afterwards: the same candidates, the pick and the fields of before
-    run(base + opts, root)
+    run_cli(base + opts, root)
     lines0, recs0 = open(out_f).read().split("\n"), [json.loads(l) for l in open(samp_f).read().strip().split("\n")]
     assert len(lines0) == 5 and lines0[-1] == "" and len(recs0) == 4
     for line, rec0, rec in zip(lines0, recs0, recs):

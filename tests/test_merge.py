@@ -9,9 +9,9 @@ import numpy as np
 import pytest
 
 import util
+from search_kit import device_dims as dims
 import merge_ref as M
 from fira_icse_amd import _lib
-from fira_icse_amd.config import FiraConfig
 from run_model import check_merge_args, nbest_record, parse_args
 
 f32 = np.float32
@@ -94,13 +94,6 @@ def test_header_declares_and_library_exports_the_entry():
     assert "#define FIRA_ABI_VERSION 11" in header
     lib = _lib.lib()
     assert lib.fira_abi_version() == 11 and hasattr(lib, "fira_merge_dist") and "fira_merge_dist" in _lib.SIGNATURES
-
-
-def dims(**kw):
-    d = _lib.make_dims(FiraConfig())
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
 
 
 def call(d=None, R_=6, rpc=3, sou=16, sub=16, dist=16, best_id=16, best_p=16):

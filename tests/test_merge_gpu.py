@@ -5,8 +5,6 @@ flag-off paths, the state keys, and the command line with ``--merge-copies`` / `
 import ctypes as C
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,7 +12,8 @@ import torch
 
 import util
 import merge_ref as M
-from fira_icse_amd import _lib, data, synth
+from search_kit import best_pair, bits, device_dims, golden_search, offset_rows, outside_untouched, run_cli, same_search
+from fira_icse_amd import _lib, synth
 from fira_icse_amd.config import EOS, PAD, START, UNK, FiraConfig
 from fira_icse_amd.decode import Constraints
 
@@ -86,33 +85,20 @@ def reference(case):
     return out, np.array([b[0] for b in best], dtype=np.int32), np.array([b[1] for b in best], dtype=np.float32)
 
 
-def device_dims(dims):
-    d = _lib.make_dims(FiraConfig())
-    d.vocab, d.sou_len, d.sub_len = dims
-    return d
-
-
 def run_kernel(dims, rpc, sou, sub, dist, want_best, offset=1):
     """The entry on a copy of ``dist`` that starts ``offset`` floats into its buffer (rows then begin at every alignment)."""
     dev = "cuda"
     n_rows, W = dist.shape
-    buf = torch.zeros(n_rows * W + offset + 8, dtype=torch.float32, device=dev)
-    d_dev = buf[offset:offset + n_rows * W].view(n_rows, W)
-    d_dev.copy_(torch.from_numpy(dist))
+    buf, d_dev = offset_rows(dist, offset)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) if a.size else torch.zeros(1, dtype=torch.int32, device=dev)
     sou_d, sub_d = t(sou), t(sub)
-    best_id = torch.full((n_rows,), -7, dtype=torch.int32, device=dev) if want_best else None
-    best_p = torch.full((n_rows,), -7.0, dtype=torch.float32, device=dev) if want_best else None
-    dd = device_dims(dims)
+    best_id, best_p = best_pair(n_rows, want_best)
+    dd = device_dims(*dims)
     _lib.check(_lib.lib().fira_merge_dist(_lib.cur_stream(), C.byref(dd), n_rows, rpc, _lib.ptr(sou_d), _lib.ptr(sub_d),
                                           _lib.ptr(d_dev), _lib.ptr(best_id), _lib.ptr(best_p)), "fira_merge_dist")
     torch.cuda.synchronize()
-    assert float(buf[:offset].abs().sum()) == 0 and float(buf[offset + n_rows * W:].abs().sum()) == 0      # nothing outside the rows
+    outside_untouched(buf, offset, n_rows * W)                                         # nothing outside the rows
     return d_dev.cpu(), None if best_id is None else best_id.cpu(), None if best_p is None else best_p.cpu()
-
-
-def bits(x):
-    return (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).contiguous().view(torch.int32)
 
 
 def test_inputs_are_not_vacuous():
@@ -194,7 +180,7 @@ def test_merge_constrain_and_mix_agree_where_none_of_them_edits():
         at = np.flatnonzero(dist[r] == want_p[r]).tolist()
         assert at == (list(ties[r]) if r in ties else [want_id[r]]), (r, at)
     dev = "cuda"
-    dd = device_dims(SMALL)
+    dd = device_dims(*SMALL)
     gen = torch.zeros((n_rows, dd.tar_len), dtype=torch.int32, device=dev)
     gen[:, 0] = START
     length = torch.ones(n_rows, dtype=torch.int32, device=dev)
@@ -246,18 +232,8 @@ def setup():
     generator entry per step: the word search and the entry search then agree on every commit, and the non-vacuity test below
     would show nothing.  The unsharpened weights spread the mass, a word that occurs at several diff positions outweighs the
     largest single entry, and the merged greedy message differs from the unmerged one for every commit (seeds 1..5 alike)."""
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    from fira_icse_amd.decode import Searcher
-    cfg = FiraConfig()
-    raw = util.load_golden_raw()
-    store = data.process_raw(cfg, raw)
-    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
-    ids = idx["test"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    model = TransModel(cfg, init=False)
-    model.load_state_dict(util.perturb_state_dict(reference_init_state_dict(cfg), seed=1))
-    model.eval()
-    return cfg, model, DeviceBatch(store.batch(ids), cfg), Searcher(model)
+    g = golden_search(weights="perturb", seed=1)
+    return g.cfg, g.model, g.db, g.searchers[0]
 
 
 @pytest.fixture(scope="module")
@@ -271,15 +247,6 @@ def refs(setup):
                                greedy=M.greedy_edited(search, db, M.make_edit(sou, sub, dims, 1, c)))
     out[None] = dict(beam=tuple(t.cpu().clone() for t in search.beam(db, 3)), greedy=tuple(t.cpu().clone() for t in search.greedy(db)))
     return out
-
-
-def same_search(got, want):
-    """The rule of test_constrain_gpu.py: lengths and probabilities equal, ids equal inside the lengths."""
-    (gen, length, p), (gen_t, len_t, p_t) = [tuple(t.cpu() for t in x[:3]) for x in (got, want)]
-    assert torch.equal(length, len_t)
-    assert torch.equal(p, p_t)
-    live = torch.arange(gen.shape[-1])[(None,) * (gen.dim() - 1)] < length[..., None]
-    assert torch.equal(gen * live, gen_t * live)
 
 
 def slot_messages(gen, length, prob):
@@ -376,14 +343,6 @@ def test_flag_off_is_todays_search(setup, refs):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def run(args, cwd):
-    env = dict(os.environ, PYTHONPATH=util.REPO)
-    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 def test_cli_merge_copies_and_nbest(tmp_path):
     from fira_icse_amd.model import reference_init_state_dict
     root = str(tmp_path)
@@ -407,12 +366,12 @@ def test_cli_merge_copies_and_nbest(tmp_path):
                 assert len(set(rec["messages"])) == len(rec["messages"]), rec
 
     # neither option: the output recorded before the options existed (same root, same seed), and no n-best file
-    run(base, root)
+    run_cli(base, root)
     gold = json.load(open(os.path.join(util.GOLDEN, "decode_ref.json")))["beam3"]
     plain = open(out_f, "rb").read()
     assert plain == "".join(l + "\n" for l in gold).encode() and not os.path.exists(nbest_f)
-    run(base + ["--nbest"], root)                            # --nbest alone changes nothing in output_fira
+    run_cli(base + ["--nbest"], root)                            # --nbest alone changes nothing in output_fira
     assert open(out_f, "rb").read() == plain
     check_nbest(distinct=False)
-    run(base + ["--merge-copies", "--nbest"], root)
+    run_cli(base + ["--merge-copies", "--nbest"], root)
     check_nbest(distinct=True)

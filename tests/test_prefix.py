@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import util
+from search_kit import device_dims as dims
 import prefix_ref as P
 from fira_icse_amd import _lib
 from fira_icse_amd.config import EOS, PAD, START, UNK, FiraConfig
@@ -27,13 +28,6 @@ def test_header_declares_and_library_exports_the_entry():
     lib = _lib.lib()
     assert lib.fira_abi_version() == 11 and hasattr(lib, "fira_force_dist") and "fira_force_dist" in _lib.SIGNATURES
     assert len(_lib.SIGNATURES["fira_force_dist"][1]) == 13
-
-
-def dims(**kw):
-    d = _lib.make_dims(FiraConfig())
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
 
 
 def call(d=None, R_=6, rpc=3, gen=16, length=16, sou=16, sub=16, prefix=16, prefix_len=16, dist=16, best_id=16, best_p=16):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import util
+from search_kit import device_dims as dims
 import require_ref as R
 from fira_icse_amd import _lib
 from fira_icse_amd.config import EOS, PAD, START, UNK, FiraConfig
@@ -129,13 +130,6 @@ def test_header_declares_and_library_exports_the_entry():
     lib = _lib.lib()
     assert lib.fira_abi_version() == 11 and hasattr(lib, "fira_beam_select_required")
     assert len(_lib.SIGNATURES["fira_beam_select_required"][1]) == len(_lib.SIGNATURES["fira_beam_select"][1]) + 3
-
-
-def dims(**kw):
-    d = _lib.make_dims(FiraConfig())
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
 
 
 BAD_CALLS = {

@@ -8,9 +8,9 @@ import pytest
 import torch
 
 import require_ref as R
-import util
-from fira_icse_amd import _lib, data
-from fira_icse_amd.config import EOS, START, UNK, FiraConfig
+from search_kit import bits, device_dims, golden_search
+from fira_icse_amd import _lib
+from fira_icse_amd.config import EOS, START, UNK
 
 pytestmark = pytest.mark.gpu
 
@@ -19,15 +19,8 @@ SMALL_ODD = dict(vocab=11, sou_len=5, sub_len=3, tar_len=8)        # W = 19: odd
 MODEL = {}                                                          # the model's geometry (FiraConfig's own dims)
 
 
-def device_dims(geo):
-    d = _lib.make_dims(FiraConfig())
-    for k, v in geo.items():
-        setattr(d, k, v)
-    return d
-
-
 def geometry(geo):
-    d = device_dims(geo)
+    d = device_dims(**geo)
     return d.vocab, d.sou_len, d.sub_len, d.tar_len
 
 
@@ -86,7 +79,7 @@ def launch(st, dist, required=True, want_met=True):
     g_out = torch.full_like(gen, -7)
     l_out, p_out, parent = torch.full_like(length, -7), torch.full_like(prob, -7.0), torch.full_like(length, -7)
     met = torch.full_like(length, -7) if required and want_met else None
-    dd = device_dims(st["geo"])
+    dd = device_dims(**st["geo"])
     args = (_lib.cur_stream(), C.byref(dd), B, beam, _lib.ptr(dist_d), _lib.ptr(fin), _lib.ptr(active), _lib.ptr(done), _lib.ptr(sou),
             _lib.ptr(sub), _lib.ptr(gen), _lib.ptr(length), _lib.ptr(prob), _lib.ptr(g_out), _lib.ptr(l_out), _lib.ptr(p_out),
             _lib.ptr(parent))
@@ -98,10 +91,6 @@ def launch(st, dist, required=True, want_met=True):
         _lib.check(_lib.lib().fira_beam_select(*args), "fira_beam_select")
     torch.cuda.synchronize()
     return g_out.cpu(), l_out.cpu(), p_out.cpu(), parent.cpu(), None if met is None else met.cpu()
-
-
-def bits(x):
-    return x.contiguous().view(torch.int32)
 
 
 def equals_the_reference(st, dist, got=None):
@@ -280,7 +269,7 @@ def test_refusals_return_non_zero_with_a_message():
     rng, st, dist = small_case(9)
     for geo, beam, word in ((dict(SMALL, tar_len=65), 4, "tar_len"), (dict(SMALL, vocab=8), 4, "vocabulary"),
                             (dict(SMALL, sou_len=1000, sub_len=25), 4, "memory slots"), (SMALL, 1, "n_beam"), (SMALL, 9, "n_beam")):
-        dd = device_dims(geo)
+        dd = device_dims(**geo)
         args = [_lib.cur_stream(), C.byref(dd), 3, beam] + [C.c_void_p(16)] * 16
         assert _lib.lib().fira_beam_select_required(*args) != 0
         msg = _lib.lib().fira_last_error().decode()
@@ -301,21 +290,11 @@ MODEL_TAR_LEN = 8
 
 @pytest.fixture(scope="module")
 def setup():
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    from fira_icse_amd.decode import Searcher
-    cfg = FiraConfig(tar_len=MODEL_TAR_LEN)
-    raw = util.load_golden_raw()
-    store = data.process_raw(cfg, raw)
-    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
-    ids = idx["test"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    model = TransModel(cfg, init=False)
-    model.load_state_dict(reference_init_state_dict(cfg))          # untrained: every entry of a row is positive
-    model.eval()
-    db = DeviceBatch(store.batch(ids), cfg)
+    g = golden_search(tar_len=MODEL_TAR_LEN)                       # untrained: every entry of a row is positive
+    cfg, model, db = g.cfg, g.model, g.db
     copied = int(next(w for w in db.sou[3].tolist() if w > UNK))   # a word commit 3's diff carries: copy slots promote too
     words = [[700], [1500, 40], [], [copied, 90, 2300 if copied != 2300 else 2301]]
-    return cfg, model, db, Searcher(model), words
+    return cfg, model, db, g.searchers[0], words
 
 
 BEAM = 5

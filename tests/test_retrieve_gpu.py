@@ -3,10 +3,9 @@ statements of retrieve_ref.py, then ``Searcher.greedy / greedy_many / beam(neigh
 file, the properties that need no loop (lam = 0, min_sim > 1, the commit as its own neighbour), the option-off path, the
 refusals, the pooled vectors against the oracle, and the command line with ``--retrieve``."""
 import ctypes as C
+import functools
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +13,8 @@ import torch
 
 import util
 import retrieve_ref as RR
+import search_kit
+from search_kit import bits, count_calls, device_dims, golden_search, last_error, run_cli, same_search
 from fira_icse_amd import _lib, data, ops, synth
 from fira_icse_amd.config import UNK, FiraConfig
 from fira_icse_amd.decode import Constraints, Neighbour
@@ -22,23 +23,8 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 
 
-def bits(x):
-    return (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).contiguous().view(torch.int32)
-
-
 def dev(x, dtype=None):
     return torch.from_numpy(np.ascontiguousarray(x)).to("cuda", dtype)
-
-
-def device_dims(**geo):
-    d = _lib.make_dims(FiraConfig())
-    for k, v in geo.items():
-        setattr(d, k, v)
-    return d
-
-
-def last_error():
-    return _lib.lib().fira_last_error().decode()
 
 
 # ------------------------------------------------------------------------------------------------ fira_pool_memory
@@ -240,21 +226,11 @@ def test_a_captured_search_replays_the_same_bits():
 # sub-token slots), and the model's own row
 MIX_GEOS = {"V19-5slots": dict(vocab=19, sou_len=3, sub_len=2), "W19": dict(vocab=11, sou_len=5, sub_len=3),
             "min-W45": dict(vocab=40, sou_len=5, sub_len=0), "model": {}}
-PAD_FLOATS = 8
 SENTINEL = -3.0
 
 
-def offset_rows(values, offset):
-    """``values`` [R, W] ``offset`` floats into a buffer of sentinels; returns (buffer, view)."""
-    n = values.size
-    buf = torch.full((n + offset + PAD_FLOATS,), SENTINEL, dtype=torch.float32, device="cuda")
-    view = buf[offset:offset + n].view(values.shape)
-    view.copy_(torch.from_numpy(values))
-    return buf, view
-
-
-def outside_untouched(buf, offset, n):
-    return bool((buf[:offset] == SENTINEL).all()) and bool((buf[offset + n:] == SENTINEL).all())
+offset_rows = functools.partial(search_kit.offset_rows, fill=SENTINEL)             # this file's guard words hold a sentinel, not 0
+outside_untouched = functools.partial(search_kit.outside_untouched, fill=SENTINEL)
 
 
 def make_mix_case(geo, B, rpc, seed):
@@ -348,21 +324,13 @@ CON = Constraints(2, 3, (UNK,))
 
 @pytest.fixture(scope="module")
 def setup():
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    from fira_icse_amd.decode import Searcher
-    cfg = FiraConfig(tar_len=MODEL_TAR_LEN)
-    store = data.process_raw(cfg, util.load_golden_raw())
-    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
-    ids, nb_ids = idx["test"][:util.GOLDEN_B], idx["train"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    sd = reference_init_state_dict(cfg)
-    model = TransModel(cfg, init=False)
-    model.load_state_dict(sd)
-    model.eval()
-    hb = store.batch(ids)
-    db, nb_db = DeviceBatch(hb, cfg), DeviceBatch(store.batch(nb_ids), cfg)
+    from fira_icse_amd.model import DeviceBatch
+    g = golden_search(tar_len=MODEL_TAR_LEN, searchers=3)
+    cfg, db = g.cfg, g.db
+    nb_db = DeviceBatch(g.store.batch(g.idx["train"][:util.GOLDEN_B]), cfg)
     assert db.B == len(SIM)
-    return dict(cfg=cfg, sd=sd, model=model, hb=hb, db=db, nb_db=nb_db, search=Searcher(model), own=Searcher(model), other=Searcher(model),
+    search, own, other = g.searchers
+    return dict(cfg=cfg, sd=g.state_dict, model=g.model, hb=g.host_batch, db=db, nb_db=nb_db, search=search, own=own, other=other,
                 nb=Neighbour(nb_db, SIM, lam=LAM), cf=RR.coef(SIM, LAM), dims=RR.dims_of(cfg),
                 sou=db.sou.cpu().numpy(), sub=db.sub_token.cpu().numpy())
 
@@ -387,15 +355,6 @@ def refs(setup):
                 cache[key] = RR.beam_neighbour(s["own"], s["other"], s["db"], s["nb_db"], s["cf"], kind, edit_of(s, kind, merge, con))
         return cache[key]
     return get
-
-
-def same_search(got, want):
-    """The rule of test_ensemble_gpu.py: lengths and probabilities equal, ids equal inside the lengths."""
-    (gen, length, p), (gen_t, len_t, p_t) = [tuple(t.cpu() for t in x[:3]) for x in (got, want)]
-    assert torch.equal(length, len_t)
-    assert torch.equal(p, p_t)
-    live = torch.arange(gen.shape[-1])[(None,) * (gen.dim() - 1)] < length[..., None]
-    assert torch.equal(gen * live, gen_t * live)
 
 
 def test_pooled_vectors_against_the_oracle(setup):
@@ -492,30 +451,6 @@ def test_a_different_neighbour_with_a_large_lambda_changes_a_message(setup):
     assert changed >= 1
 
 
-class CountingLib:
-    """Stands in for the loaded library: counts the calls of every entry by name."""
-
-    def __init__(self, real):
-        self.real, self.calls = real, {}
-
-    def __getattr__(self, name):
-        fn = getattr(self.real, name)
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
-def count_calls(monkeypatch, run):
-    lib = CountingLib(_lib.lib())
-    with monkeypatch.context() as mp:
-        mp.setattr(_lib, "_lib", lib)
-        run()
-    torch.cuda.synchronize()
-    return lib.calls
-
-
 def test_option_off_is_todays_search_and_on_adds_one_step_one_merge_one_mix(setup, monkeypatch):
     from fira_icse_amd.decode import Searcher
     cfg, db, model, nb = setup["cfg"], setup["db"], setup["model"], setup["nb"]
@@ -582,14 +517,6 @@ def types_batch(db, B):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def run_cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=util.REPO)
-    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 BASE = ["test", "--splits", "16,4,4", "--test-batch-size", "4"]
 
 
@@ -628,7 +555,7 @@ def test_cli_retrieve_writes_what_the_python_api_gives_and_the_second_run_loads_
     out_f, nb_f = os.path.join(root, "OUTPUT", "output_fira"), os.path.join(root, "OUTPUT", "output_fira_neighbours")
     store_f = os.path.join(root, "OUTPUT", "retrieve_store.pt")
     for n_run, beam in enumerate((3, 1)):
-        out = run_cli(BASE + ["--retrieve", "--retrieve-lambda", "4", "--beam", str(beam)], root)
+        out = run_cli(BASE + ["--retrieve", "--retrieve-lambda", "4", "--beam", str(beam)], root).stdout
         assert ("retrieve: built 16 vectors" in out) == (n_run == 0) and ("retrieve: loaded 16 vectors" in out) == (n_run == 1)
         assert os.path.isfile(store_f)
         test_index = json.load(open(os.path.join(root, "all_index")))["test"]

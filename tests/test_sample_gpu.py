@@ -4,8 +4,6 @@ draws follow the filtered distribution; replay, eager launches and seeds behave;
 import ctypes as C
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,7 +11,8 @@ import torch
 
 import sample_ref
 import util
-from fira_icse_amd import _lib, data, synth
+from search_kit import golden_search, run_cli, seed_tensor, spread_state_dict
+from fira_icse_amd import _lib, synth
 from fira_icse_amd.config import FiraConfig
 
 pytestmark = pytest.mark.gpu
@@ -22,38 +21,14 @@ FILTERS = [(1.0, 0, 1.0), (1.7, 0, 1.0), (1.0, 1, 1.0), (1.3, 5, 1.0), (1.0, 50,
            (1.5, 50, 0.9)]
 
 
-def spread_state_dict(cfg, seed=2):
-    """Weights whose step distributions have real spread (the peaked fixture weights put ~all mass on one entry)."""
-    from fira_icse_amd.model import reference_init_state_dict
-    torch.manual_seed(0)
-    sd = util.perturb_state_dict(reference_init_state_dict(cfg), seed=seed)
-    sd["out_fc.weight"] = sd["out_fc.weight"] * 10.0
-    sd["copy_net.LinearRes.weight"] = sd["copy_net.LinearRes.weight"] * 6.0
-    return sd
-
-
 @pytest.fixture(scope="module")
 def setup():
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    from fira_icse_amd.decode import Searcher
-    cfg = FiraConfig()
-    raw = util.load_golden_raw()
-    store = data.process_raw(cfg, raw)
-    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
-    ids = idx["test"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    peaked = TransModel(cfg, init=False)
-    peaked.load_state_dict(util.peaked_state_dict(reference_init_state_dict(cfg), seed=2))
-    peaked.eval()
-    spread = TransModel(cfg, init=False)
-    spread.load_state_dict(spread_state_dict(cfg))
+    from fira_icse_amd.model import TransModel
+    g = golden_search(weights="peaked", searchers=0, seed=2)
+    spread = TransModel(g.cfg, init=False)
+    spread.load_state_dict(spread_state_dict(g.cfg))
     spread.eval()
-    return cfg, store, ids, peaked, spread, DeviceBatch(store.batch(ids), cfg)
-
-
-def seed_tensor(seed):
-    seed &= (1 << 64) - 1
-    return torch.tensor([seed - (1 << 64) if seed >= 1 << 63 else seed], dtype=torch.int64, device="cuda")
+    return g.cfg, g.store, g.ids, g.model, spread, g.db
 
 
 def step_sample(search, ws, B, n, step, tok, key, seed, T, k, p, dist, best_id, best_p, flags=0):
@@ -289,14 +264,6 @@ def test_shape_and_argument_errors(setup):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def run(args, cwd):
-    env = dict(os.environ, PYTHONPATH=util.REPO)
-    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 def test_cli_sample_end_to_end(tmp_path):
     root = str(tmp_path)
     synth.write_dataset(root, util.load_golden_raw())
@@ -304,20 +271,20 @@ def test_cli_sample_end_to_end(tmp_path):
     base = ["test", "--splits", "16,4,4", "--test-batch-size", "3"]
     opts = ["--sample", "3", "--temperature", "1.5", "--top-p", "0.9"]
     out_f, samp_f = os.path.join(root, "OUTPUT", "output_fira"), os.path.join(root, "OUTPUT", "output_fira_samples")
-    run(base + opts + ["--sample-seed", "7"], root)
+    run_cli(base + opts + ["--sample-seed", "7"], root)
     best, samples = open(out_f).read(), open(samp_f).read()
     lines, recs = best.split("\n"), [json.loads(l) for l in samples.strip().split("\n")]
     assert len(lines) == 5 and lines[-1] == "" and len(recs) == 4
     for line, rec in zip(lines, recs):
         assert len(rec["candidates"]) == 3 and len(rec["logp"]) == 3
         assert line == rec["candidates"][int(np.argmax(rec["logp"]))]
-    run(base + opts + ["--sample-seed", "7"], root)
+    run_cli(base + opts + ["--sample-seed", "7"], root)
     assert open(out_f).read() == best and open(samp_f).read() == samples
-    run(base + opts + ["--sample-seed", "8"], root)
+    run_cli(base + opts + ["--sample-seed", "8"], root)
     assert open(samp_f).read() != samples
     os.remove(samp_f)
-    run(base, root)                                          # without --sample: the beam-3 search, as before
+    run_cli(base, root)                                          # without --sample: the beam-3 search, as before
     default = open(out_f).read()
     assert not os.path.exists(samp_f) and len(default.split("\n")) == 5
-    run(base + ["--beam", "3"], root)
+    run_cli(base + ["--beam", "3"], root)
     assert open(out_f).read() == default

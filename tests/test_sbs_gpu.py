@@ -14,9 +14,9 @@ import torch
 import sample_ref
 import sbs_ref
 import util
-from fira_icse_amd import _lib, data, synth
+from search_kit import device_dims, golden_search, run_cli, spread_state_dict
+from fira_icse_amd import _lib, synth
 from fira_icse_amd.config import FiraConfig
-from test_sample_gpu import spread_state_dict
 
 pytestmark = pytest.mark.gpu
 
@@ -25,23 +25,8 @@ KEYS = [7, 11, 13, 17]
 
 @pytest.fixture(scope="module")
 def setup():
-    from fira_icse_amd.model import TransModel, DeviceBatch
-    cfg = FiraConfig()
-    raw = util.load_golden_raw()
-    store = data.process_raw(cfg, raw)
-    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
-    ids = idx["test"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    spread = TransModel(cfg, init=False)
-    spread.load_state_dict(spread_state_dict(cfg))
-    spread.eval()
-    return cfg, store, ids, spread, DeviceBatch(store.batch(ids), cfg)
-
-
-def dims_of(d):
-    dims = _lib.make_dims(FiraConfig())
-    dims.vocab, dims.sou_len, dims.sub_len, dims.tar_len = d["V"], d["L"], d["S"], d["T"]
-    return dims
+    g = golden_search(weights="spread", searchers=0)
+    return g.cfg, g.store, g.ids, g.model, g.db
 
 
 def call_kernel(d, n, temp, a, step=sbs_ref.CASE_STEP, seed=sbs_ref.CASE_SEED, B=sbs_ref.CASE_B):
@@ -57,7 +42,7 @@ def call_kernel(d, n, temp, a, step=sbs_ref.CASE_STEP, seed=sbs_ref.CASE_SEED, B
     out = dict(gen=torch.full((R, T), -7, dtype=torch.int32, device=dev), length=torch.full((R,), -7, dtype=torch.int32, device=dev),
                phi=torch.full((R,), 7.0, device=dev), G=torch.full((R,), 7.0, device=dev), logp=torch.full((R,), 7.0, device=dev),
                parent=torch.full((R,), -7, dtype=torch.int32, device=dev))
-    dims = dims_of(d)
+    dims = device_dims(d["V"], d["L"], d["S"], d["T"])
     rc = _lib.lib().fira_beam_select_gumbel(
         _lib.cur_stream(), C.byref(dims), B, n, step, float(temp), _lib.ptr(t["dist"]), _lib.ptr(t["fin"]), _lib.ptr(t["done"]),
         _lib.ptr(t["sou"]), _lib.ptr(t["sub"]), _lib.ptr(t["key"]), _lib.ptr(t["seed"]), _lib.ptr(t["gen"]),
@@ -255,20 +240,18 @@ def test_bad_arguments_are_refused(setup):
 # ------------------------------------------------------------------------------------------------ command line
 def run(args, cwd, poison=False):
     """run_model.py in a fresh process; `poison`: the new kernel's binding and Searcher.sample_distinct raise when touched."""
+    if not poison:
+        return run_cli(args, cwd).stdout
     env = dict(os.environ, PYTHONPATH=util.REPO)
-    if poison:
-        code = ("import sys; sys.argv = ['run_model.py'] + %r\n"
-                "import run_model\n"
-                "from fira_icse_amd import _lib, decode\n"
-                "def boom(*a, **k): raise AssertionError('the option-off path touched the new code')\n"
-                "decode.Searcher.sample_distinct = boom\n"
-                "decode.Searcher._sbs_steps = boom\n"
-                "_lib.lib().fira_beam_select_gumbel = boom\n"
-                "run_model.main()\n" % (args,))
-        cmd = [sys.executable, "-c", code]
-    else:
-        cmd = [sys.executable, os.path.join(util.REPO, "run_model.py")] + args
-    r = subprocess.run(cmd, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
+    code = ("import sys; sys.argv = ['run_model.py'] + %r\n"
+            "import run_model\n"
+            "from fira_icse_amd import _lib, decode\n"
+            "def boom(*a, **k): raise AssertionError('the option-off path touched the new code')\n"
+            "decode.Searcher.sample_distinct = boom\n"
+            "decode.Searcher._sbs_steps = boom\n"
+            "_lib.lib().fira_beam_select_gumbel = boom\n"
+            "run_model.main()\n" % (args,))
+    r = subprocess.run([sys.executable, "-c", code], cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 

@@ -16,7 +16,8 @@ import torch
 
 import score_ref
 import util
-from fira_icse_amd import _lib, data, synth, text
+from search_kit import bits, golden_search, run_cli, spread_state_dict
+from fira_icse_amd import _lib, synth, text
 from fira_icse_amd.config import EOS, PAD, START, UNK, FiraConfig
 
 pytestmark = pytest.mark.gpu
@@ -24,32 +25,15 @@ pytestmark = pytest.mark.gpu
 U24, U23 = 2.0 ** -24, 2.0 ** -23
 
 
-def spread_state_dict(cfg, seed=2):
-    """Weights whose step distributions have real spread (the peaked fixture weights put ~all mass on one entry)."""
-    from fira_icse_amd.model import reference_init_state_dict
-    torch.manual_seed(0)
-    sd = util.perturb_state_dict(reference_init_state_dict(cfg), seed=seed)
-    sd["out_fc.weight"] = sd["out_fc.weight"] * 10.0
-    sd["copy_net.LinearRes.weight"] = sd["copy_net.LinearRes.weight"] * 6.0
-    return sd
-
-
 @pytest.fixture(scope="module")
 def setup():
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    cfg = FiraConfig()
-    raw = util.load_golden_raw()
-    store = data.process_raw(cfg, raw)
-    idx = data.split_index(*util.GOLDEN_SPLIT, seed=0)
-    ids = idx["test"][:util.GOLDEN_B]
-    torch.manual_seed(0)
-    sds = dict(peaked=util.peaked_state_dict(reference_init_state_dict(cfg), seed=2), spread=spread_state_dict(cfg))
-    models = {}
-    for k, sd in sds.items():
-        models[k] = TransModel(cfg, init=False)
-        models[k].load_state_dict(sd)
-        models[k].eval()
-    return cfg, store, ids, sds, models, DeviceBatch(store.batch(ids), cfg)
+    from fira_icse_amd.model import TransModel
+    g = golden_search(weights="peaked", searchers=0, seed=2)
+    sds = dict(peaked=g.state_dict, spread=spread_state_dict(g.cfg))
+    models = dict(peaked=g.model, spread=TransModel(g.cfg, init=False))
+    models["spread"].load_state_dict(sds["spread"])
+    models["spread"].eval()
+    return g.cfg, g.store, g.ids, sds, models, g.db
 
 
 class StepOut:
@@ -76,10 +60,6 @@ def step_score(search, ws, B, n, step, tok, target, label, sou, sub, o, flags=0)
 
 def i32(a):
     return torch.as_tensor(np.ascontiguousarray(a)).to(torch.int32).cuda().contiguous()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def special_targets(cfg, hb):
@@ -316,14 +296,6 @@ def test_invalid_candidates_raise_before_anything_is_launched(setup):
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def run(args, cwd):
-    env = dict(os.environ, PYTHONPATH=util.REPO)
-    r = subprocess.run([sys.executable, os.path.join(util.REPO, "run_model.py")] + args, cwd=cwd, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return r.stdout
-
-
 def test_cli_score_and_rerank_end_to_end(tmp_path):
     from fira_icse_amd.model import reference_init_state_dict
     root = str(tmp_path)
@@ -334,7 +306,7 @@ def test_cli_score_and_rerank_end_to_end(tmp_path):
     base = ["test", "--splits", "16,4,4", "--test-batch-size", "3"]
     out_f, samp_f, score_f = (os.path.join(root, "OUTPUT", n) for n in ("output_fira", "output_fira_samples", "output_fira_scores"))
     # the test split's own messages
-    stdout = run(base + ["--score", "refs"], root)
+    stdout = run_cli(base + ["--score", "refs"], root).stdout
     recs = [json.loads(l) for l in open(score_f).read().strip().split("\n")]
     assert len(recs) == 4 and not os.path.exists(out_f)
     for r in recs:
@@ -347,12 +319,12 @@ def test_cli_score_and_rerank_end_to_end(tmp_path):
     assert abs(ppl - math.exp(-sum(r["logp_word"] for r in recs) / sum(r["n_tokens"] for r in recs))) <= 1e-3 * ppl
     assert "label entries only" in stdout
     # a greedy run's own output: the greedy path is the arg-max path
-    run(base + ["--beam", "1"], root)
+    run_cli(base + ["--beam", "1"], root)
     lines = open(out_f).read().split("\n")[:-1]
     given = os.path.join(root, "given")
     shutil.copy(out_f, given)
     os.remove(out_f)
-    run(base + ["--score", given], root)
+    run_cli(base + ["--score", given], root)
     recs = [json.loads(l) for l in open(score_f).read().strip().split("\n")]
     assert len(recs) == len(lines) == 4 and not os.path.exists(out_f)
     checked = 0
@@ -370,12 +342,12 @@ def test_cli_score_and_rerank_end_to_end(tmp_path):
     # sampling: unchanged without --rerank; with it, the pick follows the key
     torch.save(spread_state_dict(cfg), os.path.join(root, "best_model.pt"))
     opts = ["--sample", "4", "--temperature", "1.2", "--top-k", "30", "--sample-seed", "5"]
-    run(base + opts, root)
+    run_cli(base + opts, root)
     plain_best, plain = open(out_f).read(), open(samp_f).read()
     for line, l in zip(plain_best.split("\n"), plain.strip().split("\n")):
         rec = json.loads(l)
         assert sorted(rec) == ["candidates", "logp"] and line == rec["candidates"][int(np.argmax(rec["logp"]))]
-    run(base + opts + ["--rerank", "logp_word"], root)
+    run_cli(base + opts + ["--rerank", "logp_word"], root)
     for line, l, l0 in zip(open(out_f).read().split("\n"), open(samp_f).read().strip().split("\n"), plain.strip().split("\n")):
         rec, rec0 = json.loads(l), json.loads(l0)
         assert rec["candidates"] == rec0["candidates"] and rec["logp"] == rec0["logp"] and len(rec["logp_word"]) == 4
@@ -383,8 +355,8 @@ def test_cli_score_and_rerank_end_to_end(tmp_path):
         assert line == rec["candidates"][int(np.argmax(vals))]
         assert all(v is None or v >= lp - 1e-3 * max(1.0, abs(lp)) for v, lp in zip(rec["logp_word"], rec["logp"]))
     # the candidates file of the sampling run can be scored as it is
-    run(base + ["--score", samp_f], root)
+    run_cli(base + ["--score", samp_f], root)
     recs = [json.loads(l) for l in open(score_f).read().strip().split("\n")]
     assert len(recs) == 4 and all(len(r["candidates"]) == 4 for r in recs)
-    run(base + opts, root)
+    run_cli(base + opts, root)
     assert open(out_f).read() == plain_best and open(samp_f).read() == plain

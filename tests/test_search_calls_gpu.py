@@ -6,9 +6,9 @@ import pytest
 import torch
 
 import util
-from test_ensemble_gpu import CountingLib
-from fira_icse_amd import _lib, data
-from fira_icse_amd.config import UNK, FiraConfig
+from search_kit import CountingLib, golden_search
+from fira_icse_amd import _lib
+from fira_icse_amd.config import UNK
 from fira_icse_amd.decode import BeamScoring, Constraints, Searcher
 
 pytestmark = pytest.mark.gpu
@@ -58,19 +58,13 @@ def one_step(monkeypatch, run):
 def setup():
     """The model of test_merge_gpu.py's setup (the perturbed seeded initialisation) and the first three of its commits; a second
     model (seed 2) for the ensemble."""
-    from fira_icse_amd.model import TransModel, DeviceBatch, reference_init_state_dict
-    cfg = FiraConfig()
-    store = data.process_raw(cfg, util.load_golden_raw())
-    ids = data.split_index(*util.GOLDEN_SPLIT, seed=0)["test"][:B]
-    models = []
-    for seed in (1, 2):
-        torch.manual_seed(0)
-        model = TransModel(cfg, init=False)
-        model.load_state_dict(util.perturb_state_dict(reference_init_state_dict(cfg), seed=seed))
-        model.eval()
-        models.append(model)
-    return dict(db=DeviceBatch(store.batch(ids), cfg), single=Searcher(models[0]),
-                ens=Searcher(models[0], members=(models[1],)))
+    from fira_icse_amd.model import TransModel, reference_init_state_dict
+    g = golden_search(weights="perturb", searchers=0, batch=B, seed=1)
+    torch.manual_seed(0)
+    second = TransModel(g.cfg, init=False)
+    second.load_state_dict(util.perturb_state_dict(reference_init_state_dict(g.cfg), seed=2))
+    second.eval()
+    return dict(db=g.db, single=Searcher(g.model), ens=Searcher(g.model, members=(second,)))
 
 
 def options(flags):
