@@ -35,34 +35,112 @@ int weight_shadows(hipStream_t s, const ShadowTable& tab, const float* P, uint16
 int gemm_bf16_wb_ex(hipStream_t s, int M, int N, int K, const float* A, int lda, const uint16_t* Bb, int ldb, float* C,
                     int ldc, const float* bias, int flags, int splitk, const int32_t* c_rows = nullptr,
                     const float* relu_mask = nullptr);
-// max_split (both grouped queues): 0 = the default split of the reduction (sized for ~40 problems sharing the chip);
-// a small group of long reductions (one encoder layer's three weight gradients) asks for more slabs
-int gemm_bf16_group_add_wgrad(hipStream_t s, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
-                              float* C, int ldc, float* colsum, int max_split = 0);
-int gemm_bf16_group_flush(hipStream_t s);
 bool gemm_bf16_takes(int M, int N, int K);     // false: the product is too small for the bf16 tiles (runs in fp32)
-void gemm_bf16_group_reset();
-bool gemm_bf16_group_full();     // the next add would launch the queue by itself: the caller forks + flushes first
-// weight gradients as 256 x 256 panel products on the bf16 matrix cores (gemm_wgrad_panel.hip): C[M,N] += A^T B with A [K, lda],
-// B [K, ldb]; np = 1 (operands rounded to bf16) or 3 (three-term split: fp32-accurate).  A queue like the grouped launches.
+// ---- queued weight gradients -------------------------------------------------------------------------
+// dW_i += dY_i^T X_i (+ db_i) for many problems in ONE launch.  The tables travel in the kernel arguments.
+// Tiled group (gemm_f32.hip / gemm_bf16.hip: 64 x 64 output tiles, K split into slabs); the fp32 kernel ignores tiles_m and chunk
+struct GroupProblem {
+    const float* A;      // dY  [K, M] (transA layout)
+    const float* B;      // X   [K, N]
+    float* C;            // dW  [M, N], accumulated
+    float* colsum;       // db  [M] or nullptr
+    int M, N, K, lda, ldb, ldc, tiles_m, tiles_n, splitk, k_chunk;
+};
+constexpr int GROUP_MAX = 40;
+struct GroupTable {
+    int n = 0, chunk = 0;
+    int wg_start[GROUP_MAX + 1] = {0};
+    GroupProblem p[GROUP_MAX];
+    void cost(double& flop, double& bytes) const {      // of the whole launch (ProfScope)
+        flop = bytes = 0;
+        for (int i = 0; i < n; ++i) {
+            const double M = p[i].M, N = p[i].N, K = p[i].K;
+            flop += 2.0 * M * N * K;
+            bytes += 4.0 * (M * K + N * K + M * N);
+        }
+    }
+};
+// what is specific to each tiled kernel: its split of the reduction and K granule (q.splitk, q.k_chunk from q.M / N / K;
+// max_split 0 = the default split, sized for ~40 problems sharing the chip -- a small group of long reductions, one encoder layer's
+// three weight gradients, asks for more slabs), and its launch (the fp32 one pads its LDS request: gemm_f32.hip, SIDE_LDS_PAD)
+int gemm_group_plan(GroupProblem& q, int max_split);
+int gemm_group_launch(hipStream_t s, const GroupTable& t);
+int gemm_bf16_group_plan(GroupProblem& q, int max_split);
+int gemm_bf16_group_launch(hipStream_t s, GroupTable& t);
+// Panel products on the bf16 matrix cores (gemm_wgrad_panel.hip: 256 x 256 output tiles): C[M,N] += A^T B with A [K, lda], B [K, ldb];
+// np = 1 (operands rounded to bf16) or 3 (three-term split: fp32-accurate)
+struct PanelProblem {
+    const float *A, *B;
+    float *C, *colsum;
+    float* part;                     // slabs > 1: [tiles_m * tiles_n][slabs][256 x 256] partial tiles (scratch)
+    int M, N, K, lda, ldb, ldc;
+    int tiles_m, tiles_n, slabs, k_slab;
+};
+constexpr int PANEL_MAX = 48;
+struct PanelTable {
+    int n = 0;
+    int wg_start[PANEL_MAX + 1] = {0};
+    PanelProblem p[PANEL_MAX];
+};
 bool gemm_wgrad_panel_takes(int M, int N, int K, const float* A, int lda, const float* B, int ldb, int ldc);
-void gemm_wgrad_panel_reset();
-bool gemm_wgrad_panel_full();
-int gemm_wgrad_panel_pending();
-int gemm_wgrad_panel_add(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, float* colsum);
-int gemm_wgrad_panel_flush(hipStream_t s, int np);
-void gemm_wgrad_panel_scratch(float* buf, size_t n_floats);      // scratch for split problems (thread-local; nullptr: no splits)
-int gemm_wgrad_panel(hipStream_t s, int np, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-                     int ldc, float* colsum);
-// grouped weight gradients (one launch for many small dW += dY^T X problems; see gemm_f32.hip)
-int gemm_group_add_wgrad(hipStream_t s, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-                         int ldc, float* colsum, int max_split = 0);
-int gemm_group_flush(hipStream_t s);
-void gemm_group_reset();
-bool gemm_group_full();
+// plans the slabs of every queued problem and launches them; scratch: room for the partial tiles of split problems (256 KB per
+// workgroup of one; nullptr: nothing is split)
+int gemm_wgrad_panel_launch(hipStream_t s, int np, PanelTable& t, float* scratch, size_t scratch_floats);
+// The weight gradients a call has queued for the weight-gradient stream, owned by that call (engine.hip: Call::wq; a local of
+// fira_gemm_wgrad_panel): the two tables, the panel scratch and the arithmetic.  A full queue refuses the next problem -- it is
+// the owner who forks the stream behind the operands' writers and flushes.
+struct WgradQueue {
+    GroupTable tiled;
+    PanelTable panels;
+    float* scratch = nullptr;        // partial tiles of split panel problems
+    size_t scratch_floats = 0;
+    int dtype = 0;                   // 0: fp32 tiled kernel, three-term panels;  1: bf16 tiled kernel, one-term panels
+    void reset(int dtype_, float* scratch_, size_t floats) {
+        tiled.n = 0; panels.n = 0;
+        dtype = dtype_; scratch = scratch_; scratch_floats = scratch_ ? floats : 0;
+    }
+    bool full() const { return tiled.n == GROUP_MAX || panels.n == PANEL_MAX; }
+    int panel_pending() const { return panels.n; }
+    // dW[M,N] += A^T B with A = dY [K,M], B = X [K,N]; db[M] += column sums of dY.  Runs at the next flush.
+    int add_tiled(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, float* colsum,
+                  int max_split = 0) {
+        if (M <= 0 || N <= 0 || K <= 0) return 0;
+        FIRA_REQUIRE(tiled.n < GROUP_MAX, "wgrad queue: tiled group full (fork and flush first)");
+        GroupProblem& q = tiled.p[tiled.n];
+        q.A = A; q.B = B; q.C = C; q.colsum = colsum;
+        q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
+        q.tiles_m = cdiv(M, 64); q.tiles_n = cdiv(N, 64);
+        if (int rc = dtype == 1 ? gemm_bf16_group_plan(q, max_split) : gemm_group_plan(q, max_split)) return rc;
+        tiled.wg_start[tiled.n + 1] = tiled.wg_start[tiled.n] + q.tiles_m * q.tiles_n * q.splitk;
+        ++tiled.n;
+        return 0;
+    }
+    int add_panel(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, float* colsum) {
+        FIRA_REQUIRE(panels.n < PANEL_MAX, "wgrad queue: panel table full (fork and flush first)");
+        PanelProblem& q = panels.p[panels.n++];
+        q.A = A; q.B = B; q.C = C; q.colsum = colsum;
+        q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
+        q.tiles_m = cdiv(M, 256); q.tiles_n = N / 256;
+        q.slabs = 1; q.k_slab = K; q.part = nullptr;
+        return 0;
+    }
+    // the queued launches on stream s, tiled group then panels
+    int flush(hipStream_t s) {
+        int rc = 0;
+        if (tiled.n > 0) rc = dtype == 1 ? gemm_bf16_group_launch(s, tiled) : gemm_group_launch(s, tiled);
+        tiled.n = 0;
+        return rc ? rc : flush_panels(s);
+    }
+    int flush_panels(hipStream_t s) {
+        const int rc = gemm_wgrad_panel_launch(s, dtype == 1 ? 1 : 3, panels, scratch, scratch_floats);   // (no problems: no launch)
+        panels.n = 0;
+        return rc;
+    }
+};
+// internal flag of gemm_f32_ex / gemm_bf16_ex (beside FIRA_GEMM_*; the extern "C" entries mask it off): the product runs on the
+// weight-gradient stream and pads its LDS request (gemm_f32.hip: SIDE_LDS_PAD)
+constexpr int GEMM_SIDE_PAD = 1 << 8;
 // coalesced 32x32 tile kernel (gemm_small.hip): shape test, launch with an optional residual epilogue (epilogue.h: EpiRes),
-// the stream whose gemm_f32 launches pad their LDS request (gemm_f32.hip: side_lds_pad)
-void gemm_set_pad_stream(hipStream_t s);
 // and the product with a LayerNorm prologue on its A operand (K = 256)
 struct EpiRes;
 bool gemm_tile32_takes(int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb);

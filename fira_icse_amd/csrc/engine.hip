@@ -246,8 +246,8 @@ static inline bool graphs_dense(const fira_batch* b) {
 // The mode every launch helper below depends on, owned by the call that runs them: a member of the call's Ctx (a step pending
 // between fira_train_step_begin and _end keeps its own in the copied Ctx), a local of the op-level entries and the decode step.
 // What stays thread-local in this file is per-thread resource or ABI state, not per-call mode: side() (the library's streams and
-// event pool), wait_probe() and g_pending (the step between the two calls of the data-parallel ABI).  Outside it: the queue builders
-// and the panel scratch of gemm_f32.hip / gemm_bf16.hip / gemm_wgrad_panel.hip, the error text and the profiler's decoder tag (layout.cpp).
+// event pool), wait_probe() and g_pending (the step between the two calls of the data-parallel ABI).  Outside it: the error text
+// and the profiler's decoder tag (layout.cpp).  The kernel files keep no state.
 struct Call {
     // Compute dtype (fira_train_opts.dtype / the dtype argument of fira_forward_dev and the op-level entries): 0 = fp32 MFMA
     // (the reference's arithmetic), 1 = bf16 MFMA with fp32 accumulation and fp32 storage (BASELINE configs[2]).  Only the
@@ -266,6 +266,7 @@ struct Call {
     int64_t W21n = 0;
     const uint16_t *W21b = nullptr, *W21bT = nullptr;
     RedCollector red;                 // deferred column reductions of the backward pass
+    WgradQueue wq;                    // weight gradients queued for the next grouped launches (reset by backward_decoder)
     void shadows(const float* P_, int64_t total_, const uint16_t* wb, const uint16_t* wbt, const ShadowTable* t) {
         P = P_; total = total_; Wb = wb; WbT = wbt; tab = t;
     }
@@ -424,7 +425,6 @@ struct SideStream {
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;   // no priorities: plain streams
         hipError_t e = hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, least);
         if (e != hipSuccess) return set_err("hipStreamCreate: %s", hipGetErrorString(e));
-        gemm_set_pad_stream(stream);
         e = hipStreamCreateWithPriority(&aux, hipStreamNonBlocking, greatest);
         if (e != hipSuccess) return set_err("hipStreamCreateWithPriority: %s", hipGetErrorString(e));
         events.resize(512);
@@ -507,6 +507,11 @@ static int side_join(hipStream_t main_s, int line = 0) {
 }
 
 static inline bool side_on() { SideStream& sd = side(); return sd.stream && sd.enabled; }
+// the weight-gradient / auxiliary stream, or the caller's when the side streams are off
+static inline hipStream_t wgrad_stream(hipStream_t s) { return side_on() ? side().stream : s; }
+static inline hipStream_t aux_stream(hipStream_t s) { return side_on() ? side().aux : s; }
+// flag of a product issued on stream ws: the tiled fp32 kernel pads its LDS request on the weight-gradient stream (gemm_f32.hip)
+static inline int side_pad(hipStream_t ws) { return side_on() && ws == side().stream ? GEMM_SIDE_PAD : 0; }
 // the auxiliary stream waits for everything enqueued on `main` so far
 static int aux_fork(hipStream_t main_s) {
     SideStream& sd = side();
@@ -526,90 +531,6 @@ static int side_mark(hipEvent_t* out) {
 static int main_wait(hipStream_t main_s, hipEvent_t e, int line = 0) {
     if (stream_wait_probed(main_s, e, line)) return set_err("stream wait failed");
     return 0;
-}
-
-// dW += dY^T X ; db += colsum(dY)      (reduce over the M rows: split-K over rows keeps the chip busy)
-// dY and X must stay untouched until the next side_join (per-layer slots of Plan::encg / decg, saved activations).
-// (round 6) Weight gradients as panel products on the bf16 matrix cores (gemm_wgrad_panel.hip: 256 x 256 output tiles, every
-// operand row read once, no atomics; fp32 mode = three-term bf16 split, fp32-accurate) where the shape allows: dW [N,K] with
-// K (the layer's input width) a multiple of 256 and N >= 32, by class (1 encoder groups, 2 decoder / head groups, 4 vocabulary,
-// 8 stacked K|V).
-enum { PANEL_ENC = 1, PANEL_DEC = 2, PANEL_VOCAB = 4, PANEL_KV = 8 };
-// (measured, profiles/r6_probes.md: fp32 -- every class wins, mask 15; bf16 -- the decoder / head groups (K = the ~1 000 computed
-//  target rows) lose to the tiled grouped kernel, whose single-rounding MFMAs are already short: mask 13)
-static inline bool panel_takes(const Call& call, int cls, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx) {
-    const int mask = call.dtype == 1 ? 13 : 15;
-    return (mask & cls) && gemm_wgrad_panel_takes(N, K, M, dY, lddy, X, ldx, K);
-}
-static inline int panel_np(const Call& call) { return call.dtype == 1 ? 1 : 3; }
-
-// dW [N,K] += dY^T X on stream ws, which already waits for its operands: panel product where the shape allows (panel_cls 0:
-// never), tiled otherwise
-static inline int wgrad_on(const Call& call, hipStream_t ws, int panel_cls, int M, int N, int K, const float* dY, int lddy,
-                           const float* X, int ldx, float* dW, float* db) {
-    if (gemm_wgrad_panel_pending() == 0 && panel_takes(call, panel_cls, M, N, K, dY, lddy, X, ldx))
-        return gemm_wgrad_panel(ws, panel_np(call), N, K, M, dY, lddy, X, ldx, dW, K, db);
-    return gemm_any(call, ws, 1, 0, N, K, M, dY, lddy, X, ldx, dW, K, nullptr, FIRA_GEMM_ACCUM, 0, db);
-}
-// ... behind a fork of its own from the caller's stream
-static inline int linear_wgrad(const Call& call, hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* X,
-                               int ldx, float* dW, float* db, int panel_cls = 0) {
-    hipStream_t ws = s;
-    if (side_on()) {
-        TRY(side_fork(s));
-        ws = side().stream;
-    }
-    return wgrad_on(call, ws, panel_cls, M, N, K, dY, lddy, X, ldx, dW, db);
-}
-
-static inline int flush_wgrad_queues(const Call& call, hipStream_t ws) {     // the queued launches on the weight-gradient stream: tiled group, then panels
-    TRY(call.dtype == 1 ? gemm_bf16_group_flush(ws) : gemm_group_flush(ws));
-    return gemm_wgrad_panel_flush(ws, panel_np(call));
-}
-static inline int flush_grouped_wgrads(const Call& call, hipStream_t s) {
-    if (!side_on()) return 0;
-    TRY(side_fork(s));
-    return flush_wgrad_queues(call, side().stream);
-}
-// A full queue launches itself at the next add -- on the weight-gradient stream, WITHOUT a fork from the caller's stream, i.e.
-// possibly ahead of the kernels that write its operands (deeper models: > 40 queued problems).  Fork + flush first.
-static inline int group_make_room(const Call& call, hipStream_t s) {
-    if ((call.dtype == 1 ? gemm_bf16_group_full() : gemm_group_full()) || gemm_wgrad_panel_full()) return flush_grouped_wgrads(call, s);
-    return 0;
-}
-// The same product QUEUED: launched with the others of its queue as one grouped kernel at the next flush_grouped_wgrads
-// (one fork for all of them), as a panel product (class queue_cls) where the shape allows, a tiled one otherwise.  Operands
-// must stay untouched until then (they are per-layer slots).  `grouping` off: launched at once behind its own fork, with
-// the panel class direct_cls.
-static inline int wgrad_queued(const Call& call, hipStream_t s, bool grouping, int queue_cls, int direct_cls, int max_split, int M,
-                               int N, int K, const float* dY, int lddy, const float* X, int ldx, float* dW, float* db) {
-    if (!grouping) return linear_wgrad(call, s, M, N, K, dY, lddy, X, ldx, dW, db, direct_cls);
-    TRY(group_make_room(call, s));
-    if (panel_takes(call, queue_cls, M, N, K, dY, lddy, X, ldx)) return gemm_wgrad_panel_add(N, K, M, dY, lddy, X, ldx, dW, K, db);
-    if (call.dtype == 1) {
-        if (!gemm_bf16_takes(N, K, M)) return linear_wgrad(call, s, M, N, K, dY, lddy, X, ldx, dW, db);   // e.g. the 2-column gate
-        return gemm_bf16_group_add_wgrad(side().stream, N, K, M, dY, lddy, X, ldx, dW, K, db, max_split);
-    }
-    return gemm_group_add_wgrad(side().stream, N, K, M, dY, lddy, X, ldx, dW, K, db, max_split);
-}
-// The small reductions over the B*30 target rows (decoder layers, gate / target projections of the head): ONE grouped kernel
-// after the decoder's backward loop (gemm_f32.hip), instead of ~40 launches of ~15 us that are mostly fill and drain.
-static inline int linear_wgrad_grouped(const Call& call, hipStream_t s, int M, int N, int K, const float* dY, int lddy,
-                                       const float* X, int ldx, float* dW, float* db, int max_split = 0) {
-    return wgrad_queued(call, s, side_on(), PANEL_DEC, 0, max_split, M, N, K, dY, lddy, X, ldx, dW, db);
-}
-// One encoder layer's three weight gradients (folded GCN weight, Combination output and q|k projections): queued while
-// the layer's data-gradient chain runs, then issued as ONE grouped launch behind ONE fork -- every fork
-// is an event record on the caller's stream, i.e. a barrier packet in the dependent chain (scripts/event_cost.py: ~4-5 us
-// each), and the layer used to pay four of them.  FIRA_ENC_WGRAD_GROUP=0: one fork + launch per gradient
-// (schedule switch: tests/test_model_gpu.py checks its gradients).
-static inline bool enc_group_on() {
-    static const bool off = [] { const char* e = getenv("FIRA_ENC_WGRAD_GROUP"); return e && e[0] == '0'; }();
-    return !off && side_on();
-}
-static inline int enc_wgrad(const Call& call, hipStream_t s, int M, int N, int K, const float* dY, int lddy, const float* X,
-                            int ldx, float* dW, float* db) {
-    return wgrad_queued(call, s, enc_group_on(), PANEL_ENC, PANEL_ENC, 32, M, N, K, dY, lddy, X, ldx, dW, db);
 }
 
 // LayerNorm backward with its dgamma / dbeta reduction deferred
@@ -839,9 +760,82 @@ static int lanes_join(Ctx& c) {
 static int lanes_fork_to(Ctx& c, hipStream_t target) {
     for (int k = 0; k < c.call.lanes; ++k) {
         hipEvent_t e = side().ev();
-        if (hipEventRecord(e, c.lanes[k].s) != hipSuccess || hipStreamWaitEvent(target, e, 0) != hipSuccess) return set_err("lane -> side stream fork failed");
+        // (lane 0 is the caller's stream, also in a context whose decoder never ran)
+        if (hipEventRecord(e, k ? c.lanes[k].s : c.s) != hipSuccess || hipStreamWaitEvent(target, e, 0) != hipSuccess) return set_err("lane -> side stream fork failed");
     }
     return 0;
+}
+
+// dW += dY^T X ; db += colsum(dY)      (reduce over the M rows: split-K over rows keeps the chip busy)
+// dY and X must stay untouched until the next side_join (per-layer slots of Plan::encg / decg, saved activations).
+// (round 6) Weight gradients as panel products on the bf16 matrix cores (gemm_wgrad_panel.hip: 256 x 256 output tiles, every
+// operand row read once, no atomics; fp32 mode = three-term bf16 split, fp32-accurate) where the shape allows: dW [N,K] with
+// K (the layer's input width) a multiple of 256 and N >= 32, by class (1 encoder groups, 2 decoder / head groups, 4 vocabulary,
+// 8 stacked K|V).
+enum { PANEL_ENC = 1, PANEL_DEC = 2, PANEL_VOCAB = 4, PANEL_KV = 8 };
+// (measured, profiles/r6_probes.md: fp32 -- every class wins, mask 15; bf16 -- the decoder / head groups (K = the ~1 000 computed
+//  target rows) lose to the tiled grouped kernel, whose single-rounding MFMAs are already short: mask 13)
+static inline bool panel_takes(const Call& call, int cls, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx) {
+    const int mask = call.dtype == 1 ? 13 : 15;
+    return (mask & cls) && gemm_wgrad_panel_takes(N, K, M, dY, lddy, X, ldx, K);
+}
+
+// dW [N,K] += dY^T X on stream ws, which already waits for its operands: panel product where the shape allows (panel_cls 0:
+// never; not while panels are queued: their table is the call's one), tiled otherwise
+static inline int wgrad_on(Call& call, hipStream_t ws, int panel_cls, int M, int N, int K, const float* dY, int lddy,
+                           const float* X, int ldx, float* dW, float* db) {
+    if (call.wq.panel_pending() == 0 && panel_takes(call, panel_cls, M, N, K, dY, lddy, X, ldx)) {
+        TRY(call.wq.add_panel(N, K, M, dY, lddy, X, ldx, dW, K, db));
+        return call.wq.flush_panels(ws);
+    }
+    return gemm_any(call, ws, 1, 0, N, K, M, dY, lddy, X, ldx, dW, K, nullptr, FIRA_GEMM_ACCUM | side_pad(ws), 0, db);
+}
+// ... behind a fork of its own from the caller's stream
+static inline int linear_wgrad(Ctx& c, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx, float* dW,
+                               float* db, int panel_cls = 0) {
+    if (side_on()) TRY(side_fork(c.s));
+    return wgrad_on(c.call, wgrad_stream(c.s), panel_cls, M, N, K, dY, lddy, X, ldx, dW, db);
+}
+
+// The queued launches, tiled group then panels, on the weight-gradient stream behind ONE fork from every running lane (one lane:
+// the caller's stream).  Without the side streams nothing is queued.
+static inline int flush_wgrads(Ctx& c) {
+    if (!side_on()) return 0;
+    TRY(lanes_fork_to(c, side().stream));
+    return c.call.wq.flush(side().stream);
+}
+// The same product QUEUED: launched with the others of its queue as one grouped kernel at the next flush_wgrads
+// (one fork for all of them), as a panel product (class queue_cls) where the shape allows, a tiled one otherwise.  Operands
+// must stay untouched until then (they are per-layer slots).  `grouping` off: launched at once behind its own fork, with
+// the panel class direct_cls.
+// A full queue (deeper models: > 40 queued problems) refuses the next problem; launching it from inside the add, on the
+// weight-gradient stream WITHOUT a fork, would run it ahead of the kernels that write its operands: fork + flush first.
+static inline int wgrad_queued(Ctx& c, bool grouping, int queue_cls, int direct_cls, int max_split, int M, int N, int K,
+                               const float* dY, int lddy, const float* X, int ldx, float* dW, float* db) {
+    Call& call = c.call;
+    if (!grouping) return linear_wgrad(c, M, N, K, dY, lddy, X, ldx, dW, db, direct_cls);
+    if (call.wq.full()) TRY(flush_wgrads(c));
+    if (panel_takes(call, queue_cls, M, N, K, dY, lddy, X, ldx)) return call.wq.add_panel(N, K, M, dY, lddy, X, ldx, dW, K, db);
+    if (call.dtype == 1 && !gemm_bf16_takes(N, K, M)) return linear_wgrad(c, M, N, K, dY, lddy, X, ldx, dW, db);   // e.g. the 2-column gate
+    return call.wq.add_tiled(N, K, M, dY, lddy, X, ldx, dW, K, db, max_split);
+}
+// The small reductions over the B*30 target rows (decoder layers, gate / target projections of the head): ONE grouped kernel
+// after the decoder's backward loop (gemm_f32.hip), instead of ~40 launches of ~15 us that are mostly fill and drain.
+static inline int linear_wgrad_grouped(Ctx& c, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx,
+                                       float* dW, float* db, int max_split = 0) {
+    return wgrad_queued(c, side_on(), PANEL_DEC, 0, max_split, M, N, K, dY, lddy, X, ldx, dW, db);
+}
+// One encoder layer's three weight gradients (folded GCN weight, Combination output and q|k projections): queued while
+// the layer's data-gradient chain runs, then issued as ONE grouped launch behind ONE fork -- every fork
+// is an event record on the caller's stream, i.e. a barrier packet in the dependent chain (scripts/event_cost.py: ~4-5 us
+// each), and the layer used to pay four of them.  FIRA_ENC_WGRAD_GROUP=0: one fork + launch per gradient
+// (schedule switch: tests/test_model_gpu.py checks its gradients).
+static inline bool enc_group_on() {
+    static const bool off = [] { const char* e = getenv("FIRA_ENC_WGRAD_GROUP"); return e && e[0] == '0'; }();
+    return !off && side_on();
+}
+static inline int enc_wgrad(Ctx& c, int M, int N, int K, const float* dY, int lddy, const float* X, int ldx, float* dW, float* db) {
+    return wgrad_queued(c, enc_group_on(), PANEL_ENC, PANEL_ENC, 32, M, N, K, dY, lddy, X, ldx, dW, db);
 }
 
 // ------------------------------------------------------------------------------------------ encoder forward
@@ -1259,7 +1253,7 @@ static inline int enc_wgrad_every(int n_rows, int n_layers) {
 static int group_a_final_stream(hipStream_t s, hipStream_t* out) {
     SideStream& sd = side();
     *out = s;
-    if (sd.stream && sd.enabled) {
+    if (side_on()) {
         TRY(aux_fork(s));
         hipEvent_t e2 = sd.ev();
         if (hipEventRecord(e2, sd.stream) != hipSuccess || hipStreamWaitEvent(sd.aux, e2, 0) != hipSuccess)
@@ -1285,16 +1279,13 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
     const float* dec = p.dec[p.nl - 1].x_f;
     float* G = c.G;
 
-    gemm_group_reset();
-    gemm_bf16_group_reset();
-    gemm_wgrad_panel_reset();
-    gemm_wgrad_panel_scratch(p.panel_scratch, p.panel_floats);
+    c.call.wq.reset(c.call.dtype, p.panel_scratch, p.panel_floats);
     c.call.red.reset(p.red_buf, p.red_cap);
     // ---- head: p.logits / p.score / p.gate now hold dlogits / dscore / dgate_logits -------------------------
     // The vocabulary dgrad ([R, V] x [V, 256], the head's largest product) and the copy branch are independent until
     // both land in ddec: the former runs on the side stream under the latter.
     const bool so = side_on();
-    hipStream_t ss = so ? side().aux : s;
+    hipStream_t ss = aux_stream(s);
     hipEvent_t ev_dfc = nullptr;
     // dvtab_all, dW21|dc21, dtgt, ddec_c: accumulated into below, one fill for all of them -- issued on the auxiliary stream
     // at the start of the step (under the encoder's forward pass) when there is one, otherwise here
@@ -1312,11 +1303,11 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
     // (the vocabulary projection's weight gradient, the step's largest product, is forked HERE, under the copy branch: forked
     // behind the join of the head it ran under the decoder layers' small launches instead and the step lost 0.6 %, same box)
     if (R > 0)
-        TRY(linear_wgrad(c.call, s, R, p.V, D, p.logits, p.ldl, (c.rows != nullptr && rows == c.rows) ? p.dec_c : dec, D, G + L.wout,
+        TRY(linear_wgrad(c, R, p.V, D, p.logits, p.ldl, (c.rows != nullptr && rows == c.rows) ? p.dec_c : dec, D, G + L.wout,
                          G + L.bout, PANEL_VOCAB));
     if (c.call.dtype == 0) TRY(rank2_rows(s, c.Td, p.gate, c.P + L.wp, p.ddec));        // ddec = dgate Wp: a rank-2 row kernel
     else TRY(linear_dgrad(c.call, s, c.Td, 2, D, p.gate, 2, c.P + L.wp, p.ddec, D, false));
-    TRY(linear_wgrad_grouped(c.call, s, c.Td, 2, D, p.gate, 2, dec, D, G + L.wp, G + L.bp));
+    TRY(linear_wgrad_grouped(c, c.Td, 2, D, p.gate, 2, dec, D, G + L.wp, G + L.bp));
     {
         const int nb = copy_score_bwd_blocks(p.B, Sm);
         float* part = c.call.red.alloc((size_t)nb * COPY_PART_STRIDE);
@@ -1328,7 +1319,7 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
         }
     }
     TRY(linear_dgrad(c.call, s, c.Td, D, D, p.dtgt, D, c.P + L.wt, p.ddec, D, true));
-    TRY(linear_wgrad_grouped(c.call, s, c.Td, D, D, p.dtgt, D, dec, D, G + L.wt, nullptr));
+    TRY(linear_wgrad_grouped(c, c.Td, D, D, p.dtgt, D, dec, D, G + L.wt, nullptr));
     TRY(rows_move(s, 0, Mc, D, p.dsrc_c, p.dsrc, bt.mem_dst, nullptr));
     // d memory (compact rows) = dsrc Ws + sum_l dKV_l Wkv_l: nothing reads it before the encoder's backward pass, so
     // the whole accumulation lives on the side stream (in order: this product initialises dmem_c, the per-layer
@@ -1337,7 +1328,7 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
     TRY(linear_dgrad(c.call, ss, Mc, D, D, p.dsrc_c, D, c.P + L.ws, p.dmem_c, D, false));
     // (round 5: LinearSource's weight gradient rides in the decoder's grouped launch -- its own fork was an event record on the
     //  caller's stream right behind the auxiliary stream's)
-    TRY(linear_wgrad_grouped(c.call, s, Mc, D, D, p.dsrc_c, D, p.mem_c, D, G + L.ws, nullptr, 8));
+    TRY(linear_wgrad_grouped(c, Mc, D, D, p.dsrc_c, D, p.mem_c, D, G + L.ws, nullptr, 8));
     if (R > 0) {
         if (ev_dfc) TRY(main_wait(s, ev_dfc, __LINE__));
         TRY(rows_scatter_add_idx(s, R, p.ddec_c, p.ddec, rows));
@@ -1371,13 +1362,6 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
     TRY(lanes_fork(c));                        // (lane 1 starts behind the head's backward kernels)
     // the other streams' launches inside the loop read rows of EVERY lane: they fork from all of them
     auto aux_fork_all = [&]() -> int { return c.call.lanes > 1 ? lanes_fork_to(c, side().aux) : aux_fork(s); };
-    auto flush_wgrads_all = [&]() -> int {
-        if (c.call.lanes == 1) return flush_grouped_wgrads(c.call, s);
-        SideStream& sd = side();
-        if (!(sd.stream && sd.enabled)) return 0;
-        TRY(lanes_fork_to(c, sd.stream));
-        return flush_wgrad_queues(c.call, sd.stream);
-    };
     for (int l = p.nl - 1; l >= 0; --l) {
         ProfDecoderTag prof_tag;               // data gradients of the M = B*30 products (the grouped wgrads flush later)
         const DecLayer& w = L.dec[l];
@@ -1423,14 +1407,14 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
             TRY(ln_bwd_dgrad(c.call, ls, nr, p.F, bx + r0 * D, e.s_f + r0 * D, e.st_f + r0 * 2, c.P + w.lnf_g, by + r0 * D, g.dYf + r0 * D,
                              G + w.lnf_g, G + w.lnf_b, c.p_drop, c.seed, site(l, SITE_FFN), c.P + w.w2, p.F, g.dh + r0 * p.F, p.F,
                              e.h + r0 * p.F, idx0));
-            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, D, p.F, g.dYf, D, e.h, p.F, G + w.w2, G + w.b2));
-            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, p.F, D, g.dh, p.F, e.x_c, D, G + w.w1, G + w.b1));
+            if (q) TRY(linear_wgrad_grouped(c, c.Td, D, p.F, g.dYf, D, e.h, p.F, G + w.w2, G + w.b2));
+            if (q) TRY(linear_wgrad_grouped(c, c.Td, p.F, D, g.dh, p.F, e.x_c, D, G + w.w1, G + w.b1));
             TRY(linear_dgrad(c.call, ls, nr, p.F, D, g.dh + r0 * p.F, p.F, c.P + w.w1, by + r0 * D, D, true));               // by = d x_c
             // cross attention: LayerNorm backward + d ao2 = dYc Wo_c
             TRY(ln_bwd_dgrad(c.call, ls, nr, D, by + r0 * D, e.s_c + r0 * D, e.st_c + r0 * 2, c.P + w.lnc_g, bz + r0 * D, g.dYc + r0 * D,
                              G + w.lnc_g, G + w.lnc_b, c.p_drop, c.seed, site(l, SITE_CROSS), c.P + w.wo_c, D, bx + r0 * D, D, nullptr,
                              idx0));                                                                              // bx = d ao2
-            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, D, D, g.dYc, D, e.ao2, D, G + w.wo_c, G + w.bo_c));
+            if (q) TRY(linear_wgrad_grouped(c, c.Td, D, D, g.dYc, D, e.ao2, D, G + w.wo_c, G + w.bo_c));
             // (ragged key rows: dkv_all holds the computed memory rows only, every one of them written by this launch)
             TRY(attention_bwd(ls, ln.nb, H, p.T, Sm, e.qc, D, p.kv_all + l * 2 * D, p.kvp, p.kv_all + l * 2 * D + D, p.kvp,
                               p.mem_valid_c, 0, 0, e.ao2, D, bx, D, g.dq, D, p.dkv_all + l * 2 * D, p.kvp,
@@ -1440,26 +1424,26 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
                 ev_kv_done[k] = side().ev();
                 if (hipEventRecord(ev_kv_done[k], ls) != hipSuccess) return set_err("lane event record failed");
             }
-            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, D, D, g.dq, D, e.x_a, D, G + w.wq_c, G + w.bq_c));
+            if (q) TRY(linear_wgrad_grouped(c, c.Td, D, D, g.dq, D, e.x_a, D, G + w.wq_c, G + w.bq_c));
             TRY(linear_dgrad(c.call, ls, nr, D, D, g.dq + r0 * D, D, c.P + w.wq_c, bz + r0 * D, D, true));                 // bz = d x_a
             // self attention: LayerNorm backward + d ao = dYs Wo_s
             TRY(ln_bwd_dgrad(c.call, ls, nr, D, bz + r0 * D, e.s_a + r0 * D, e.st_a + r0 * 2, c.P + w.lns_g, by + r0 * D, g.dYs + r0 * D,
                              G + w.lns_g, G + w.lns_b, c.p_drop, c.seed, site(l, SITE_SELF), c.P + w.wo_s, D, bx + r0 * D, D, nullptr,
                              idx0));                                                                              // bx = d ao
-            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, D, D, g.dYs, D, e.ao, D, G + w.wo_s, G + w.bo_s));
+            if (q) TRY(linear_wgrad_grouped(c, c.Td, D, D, g.dYs, D, e.ao, D, G + w.wo_s, G + w.bo_s));
             TRY(attention_bwd(ls, ln.nb, H, p.T, p.T, e.qkv, 3 * D, e.qkv + D, 3 * D, e.qkv + 2 * D, 3 * D,
                               p.tar_valid + (size_t)ln.b0 * p.T, 1, 0, e.ao, D, bx, D, g.dqkv, 3 * D, g.dqkv + D, 3 * D, g.dqkv + 2 * D,
                               3 * D, q_off, 1, attn_bf16(c.call)));
-            if (q) TRY(linear_wgrad_grouped(c.call, s, c.Td, 3 * D, D, g.dqkv, 3 * D, x_in, D, G + w.wqkv, G + w.bqkv));
+            if (q) TRY(linear_wgrad_grouped(c, c.Td, 3 * D, D, g.dqkv, 3 * D, x_in, D, G + w.wqkv, G + w.bqkv));
             TRY(linear_dgrad(c.call, ls, nr, 3 * D, D, g.dqkv + r0 * 3 * D, 3 * D, c.P + w.wqkv, by + r0 * D, D, true));   // by = d x_in
         }
         if (c.call.lanes > 1) TRY(dmem_pair());   // (behind the layer of every lane: dkv_all's column block is complete)
-        if (dec_every > 0 && l % dec_every == 0 && side().stream && side().enabled) {
+        if (dec_every > 0 && l % dec_every == 0 && so) {
             // the weight gradients of the last dec_every layers: one grouped launch + their row block of the stacked K|V weight
             const int nlay = std::min(dec_every, p.nl - l);
             const size_t o = (size_t)l * 2 * D;
             prof_decoder_tag(-1);               // weight gradients: not among the decoder's forward / data-gradient products
-            int rc_w = flush_wgrads_all();
+            int rc_w = flush_wgrads(c);
             if (!rc_w)
                 rc_w = wgrad_on(c.call, side().stream, PANEL_KV, Mc, nlay * 2 * D, D, p.dkv_all + o, p.kvp, p.mem_c, D, G + L.wkv_all + o * D,
                                 G + L.bkv_all + o);
@@ -1469,16 +1453,17 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
         float* t = bx; bx = by; by = t;         // the next layer's output gradient is in (the old) by; bz stays free
     }
     TRY(lanes_join(c));
+    c.call.lanes = 1;                          // one chain again: what follows forks from the caller's stream alone
     }
     const float* dy = bx;
-    TRY(flush_grouped_wgrads(c.call, s));                                  // the decoder's and the head's small weight gradients
+    TRY(flush_wgrads(c));                                                   // the decoder's and the head's small weight gradients
     // decoder embedding.  The table has no padding_idx (gnn_transformer.py:92-93), but rows of padded target positions
     // carry an exactly-zero gradient (never attended as keys, zero loss weight): skipping id 0 only drops the
     // hundreds of serialised atomic additions of 0.0 onto table row 0.
     // (nothing on the chain reads it: behind the fork of the grouped launch above, on the weight-gradient stream; dy is a
     // decoder-only buffer, untouched until the next step)
     {
-        hipStream_t es = (side().stream && side().enabled) ? side().stream : s;
+        hipStream_t es = wgrad_stream(s);
         if (c.row_bt) TRY(embed_rows_bwd(es, c.Td, c.row_bt, c.bt->tar, G + L.dec_emb, dy, 0));
         else TRY(embed_gather_bwd(es, p.B, p.T, c.bt->tar, G + L.dec_emb, dy, p.T, 0, 0));
     }
@@ -1491,18 +1476,18 @@ static int backward_decoder(Ctx& c, int R, const int32_t* rows, BwdMid& mid) {
     }
     // (round 5: no fork of its own -- the weight-gradient stream waited for the caller's stream at the grouped launch above, and
     //  dkv_all was complete by then; with dec_every > 0 it went out in row blocks inside the loop)
-    if (!(side().stream && side().enabled))
-        TRY(linear_wgrad(c.call, s, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all, PANEL_KV));
+    if (!so)
+        TRY(linear_wgrad(c, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all, PANEL_KV));
     else if (dec_every == 0)
         TRY(wgrad_on(c.call, side().stream, PANEL_KV, Mc, KV, D, p.dkv_all, p.kvp, p.mem_c, D, G + L.wkv_all, G + L.bkv_all));
     // decoder LayerNorms, copy head: their partial rows were written before the fork of the weight gradient above, and only
     // the end of the step (or the mid-event below, which waits for this stream) reads the sums: off the dependent chain
-    TRY(deferred_reduce(side().stream && side().enabled ? side().stream : s, c.call.red.tab));
+    TRY(deferred_reduce(wgrad_stream(s), c.call.red.tab));
     // every gradient of [0, split) is final once the weight-gradient stream has passed this point (its launches above: the
     // vocabulary / copy / decoder weight gradients, the decoder embedding, the stacked K|V weight, the deferred column sums;
     // the auxiliary stream writes data gradients only)
     hipEvent_t& ev_groupA = mid.ev_groupA;
-    if ((st.kind == Step::Own || st.kind == Step::DpEarly) && side().stream && side().enabled) {
+    if ((st.kind == Step::Own || st.kind == Step::DpEarly) && so) {
         ev_groupA = side().ev();
         if (hipEventRecord(ev_groupA, side().stream) != hipSuccess) return set_err("group-A mark failed");
     }
@@ -1655,21 +1640,18 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
         // back to the reference's parameters (reads dW21: after its weight gradient on the same stream)
         bool flushed = false;                    // this layer's grouped launch went out (behind a fork from the caller's stream)
         auto unfold = [&]() -> int {
-            hipStream_t ws = s;
-            if (side().stream && side().enabled) {
-                // (dY2 / dW21's operands are written on the caller's stream: whatever reads them over there needs a fork behind
-                //  them -- the grouped flush of this layer was one)
-                if (!grouped || (!flushed && (!sums || !unfold_late))) TRY(side_fork(s));
-                ws = side().stream;
-            }
+            hipStream_t ws = wgrad_stream(s);
+            // (dY2 / dW21's operands are written on the caller's stream: whatever reads them over there needs a fork behind
+            //  them -- the grouped flush of this layer was one)
+            if (ws != s && (!grouped || (!flushed && (!sums || !unfold_late)))) TRY(side_fork(s));
             if (!sums) TRY(colsum(ws, Nc, D, g.dY2, D, dc21, p.rsum));
             if (unfold_late) {                       // the two products of every layer: ONE launch behind the last layer's group
                 uf_dW21[uf_n] = dW21; uf_W1[uf_n] = c.P + w.fc1w; uf_W2[uf_n] = c.P + w.fc2w;
                 uf_dW1[uf_n] = G + w.fc1w; uf_dW2[uf_n] = G + w.fc2w;
                 ++uf_n;
             } else {
-            TRY(gemm_f32_ex(ws, 0, 1, D, D, D, dW21, D, c.P + w.fc1w, D, G + w.fc2w, D, nullptr, FIRA_GEMM_ACCUM, 0, nullptr));
-            TRY(gemm_f32_ex(ws, 1, 0, D, D, D, c.P + w.fc2w, D, dW21, D, G + w.fc1w, D, nullptr, FIRA_GEMM_ACCUM, 0, nullptr));
+            TRY(gemm_f32_ex(ws, 0, 1, D, D, D, dW21, D, c.P + w.fc1w, D, G + w.fc2w, D, nullptr, FIRA_GEMM_ACCUM | side_pad(ws), 0, nullptr));
+            TRY(gemm_f32_ex(ws, 1, 0, D, D, D, c.P + w.fc2w, D, dW21, D, G + w.fc1w, D, nullptr, FIRA_GEMM_ACCUM | side_pad(ws), 0, nullptr));
             }
             if (!sums) TRY(gcn_bias_unfold(ws, c.P + w.fc2w, c.P + w.fc1b, dc21, G + w.fc2w, G + w.fc1b));
             return 0;
@@ -1679,11 +1661,11 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
             // The weight gradient follows from the same V: dW21 = dY^T (A_hat X) = (A_hat dY)^T X = V^T X
             TRY(gcn_fused_bwd(s, Nc, bt.rowptr, bt.col, bt.val, g.dY2, p.W21 + (size_t)l * D * D, e.Z, other, c.call.dtype == 1,
                               gcn_x3_on(c.call, p.nl) ? p.W21tx + (size_t)l * 3 * D * D : nullptr));
-            TRY(enc_wgrad(c.call, s, Nc, D, D, e.Z, D, p.X[l], D, dW21, nullptr));
+            TRY(enc_wgrad(c, Nc, D, D, e.Z, D, p.X[l], D, dW21, nullptr));
             if (!sums) TRY(colsum(s, Nc, D, g.dY2, D, G + w.fc2b));     // (db2 = column sums of dY, not of V)
             if (!grouped) TRY(unfold());
         } else {
-        TRY(enc_wgrad(c.call, s, Nc, D, D, g.dY2, D, e.Z, D, dW21, sums ? nullptr : G + w.fc2b));
+        TRY(enc_wgrad(c, Nc, D, D, g.dY2, D, e.Z, D, dW21, sums ? nullptr : G + w.fc2b));
         if (!grouped) TRY(unfold());
         TRY(linear_dgrad(c.call, s, Nc, D, D, g.dY2, D, p.W21 + (size_t)l * D * D, p.dNB2, D, false));  // dU
         TRY(csr_spmm_ex(s, Nc, bt.rowptr, bt.col, bt.val, p.dNB2, D, other, D, 0, 1, 1, nullptr));   // other = ds + A_hat dU
@@ -1706,11 +1688,11 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
             c.call.red.add(G + w.ln1b, part_ln + D, D, nb_comb, 2 * D);
             for (int k = 0; k < 4; ++k)
                 c.call.red.add(p.dvtab_all + (size_t)k * p.nl * D + l * D, part_v + k * D, D, nb_comb, 4 * D);
-            TRY(enc_wgrad(c.call, s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
+            TRY(enc_wgrad(c, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
         } else {
         TRY(ln_bwd(c.call, s, Cc, other, e.s1, e.st1, c.P + w.ln1g, other, g.dYc, G + w.ln1g, G + w.ln1b, c.p_drop,
                               c.seed, site(l, SITE_COMB_OUT), bt.code_rows));
-        TRY(enc_wgrad(c.call, s, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
+        TRY(enc_wgrad(c, Cc, D, D, g.dYc, D, e.c, D, G + w.wo, G + w.bo));
         TRY(linear_dgrad(c.call, s, Cc, D, D, g.dYc, D, c.P + w.wo, p.dCB_a, D, false));               // d c
         {
             const int nb = combination_bwd_blocks(Cc);
@@ -1722,10 +1704,10 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
                     c.call.red.add(p.dvtab_all + (size_t)k * p.nl * D + l * D, part + k * D, D, nb, 4 * D);
         }
         }
-        TRY(enc_wgrad(c.call, s, Cc, 2 * D, D, g.dqk, 2 * D, e.Xc, D, G + w.wqk, G + w.bqk));
+        TRY(enc_wgrad(c, Cc, 2 * D, D, g.dqk, 2 * D, e.Xc, D, G + w.wqk, G + w.bqk));
         if (grouped) {                           // the layer's three weight gradients: one fork, one launch, then the unfold
             // (one launch for every n layers' gradients: enc_wgrad_every)
-            if ((p.nl - l) % wgrad_every == 0 || l == 0) { TRY(flush_grouped_wgrads(c.call, s)); flushed = true; }
+            if ((p.nl - l) % wgrad_every == 0 || l == 0) { TRY(flush_wgrads(c)); flushed = true; }
             TRY(unfold());
         }
         if (!comb_done)
@@ -1740,7 +1722,7 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
     int64_t adam_b0 = L.split;               // fira_train_step: first parameter the closing Adam launch still has to update
     {
         const bool ax = side_on();
-        hipStream_t rs = ax ? side().aux : s;
+        hipStream_t rs = aux_stream(s);
         if (ax) TRY(aux_fork(s));
         TRY(deferred_reduce(rs, c.call.red.tab));
         // value projection of the mark table: vtab_all = mark_emb W2_all^T + b2_all
@@ -1770,7 +1752,7 @@ static int backward_encoder(Ctx& c, BwdMid& mid) {
     }
     TRY(update_early(c, ev_groupA, &adam_b0));
     if (ev_tail) TRY(main_wait(s, ev_tail, __LINE__));
-    if (side().stream && side().enabled) TRY(side_join(s, __LINE__));        // every weight gradient is complete past this point
+    if (side_on()) TRY(side_join(s, __LINE__));        // every weight gradient is complete past this point
     // dc of every GCN layer is final (deferred reduction above) and so are the side stream's additions to dW2: back to the
     // reference's fc2.weight / fc1.bias gradients, one launch for all layers
     TRY(gcn_bias_unfold_all(s, unfold_tab));
@@ -1843,8 +1825,9 @@ size_t fira_decode_workspace_bytes_ex(const fira_dims* d, int B, int n_beam, int
 
 // fira_train_step_begin leaves its step here (per thread) for fira_train_step_end: the plan of the workspace, the call's
 // context (a copy of the batch descriptor: its arrays must stay valid until the second call) and what the two halves of the
-// backward pass share.  The step owns its state (Ctx::call travels with the copy): other library calls may run on the thread
-// between the two halves.
+// backward pass share.  The step owns its state (Ctx::call travels with the copy -- the mode, the deferred reductions and the
+// weight-gradient queue, empty at this point and pointing at this workspace's panel scratch): other library calls may run on
+// the thread between the two halves.
 struct PendingStep {
     bool active = false;
     Plan plan;

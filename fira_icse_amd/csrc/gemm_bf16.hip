@@ -394,27 +394,14 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(int M, int N, int K, con
 
 // Grouped weight gradients: dW_i += dY_i^T X_i (+ db_i) for up to GROUP_MAX independent problems in ONE launch -- the
 // decoder's and the head's small reductions over the B*30 target rows, which launched one by one are a fill and a
-// drain each.  The table travels in the kernel arguments; workgroups are ordered problem-major with the same
+// drain each.  The table (engine.h: GroupTable) travels in the kernel arguments; workgroups are ordered problem-major with the same
 // contiguous-range-per-XCD rule, so one XCD works on a few whole problems.
-struct GroupProblem16 {
-    const float* A;      // dY  [K, M] (transA layout)
-    const float* B;      // X   [K, N]
-    float* C;            // dW  [M, N], accumulated
-    float* colsum;       // db  [M] or nullptr
-    int M, N, K, lda, ldb, ldc, tiles_m, tiles_n, splitk, k_chunk;
-};
-constexpr int GROUP16_MAX = 40;
-struct GroupTable16 {
-    int n, chunk;
-    int wg_start[GROUP16_MAX + 1];
-    GroupProblem16 p[GROUP16_MAX];
-};
-__global__ __launch_bounds__(256) void gemm_bf16_grouped_wgrad_kernel(GroupTable16 g) {
+__global__ __launch_bounds__(256) void gemm_bf16_grouped_wgrad_kernel(GroupTable g) {
     const int w = (blockIdx.x & 7) * g.chunk + (blockIdx.x >> 3);
     if (w >= g.wg_start[g.n]) return;
     int i = 0;
     while (i + 1 < g.n && w >= g.wg_start[i + 1]) ++i;               // uniform scan of <= 40 entries
-    const GroupProblem16& q = g.p[i];
+    const GroupProblem& q = g.p[i];
     const int r = w - g.wg_start[i];
     const int per = q.tiles_m * q.tiles_n;
     const int z = r / per, tile = r - z * per;
@@ -737,51 +724,22 @@ int gemm_bf16_ex(hipStream_t s, int tA, int tB, int M, int N, int K, const float
     return launch_bf16<64, 64>(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk, colsum, c_rows, relu_mask);
 }
 
-// ---- grouped weight gradients (host side): problems are collected, then launched together
-struct GroupBuilder16 {
-    GroupTable16 t;
-    GroupBuilder16() { t.n = 0; t.wg_start[0] = 0; }
-};
-static GroupBuilder16& group16() { static thread_local GroupBuilder16 g; return g; }
-
-void gemm_bf16_group_reset() { group16().t.n = 0; }
-bool gemm_bf16_group_full() { return group16().t.n == GROUP16_MAX; }
-int gemm_bf16_group_flush(hipStream_t s) {
-    GroupTable16& t = group16().t;
-    if (t.n == 0) return 0;
-    double flop = 0, bytes = 0;
-    for (int i = 0; i < t.n; ++i) {
-        const double M = t.p[i].M, N = t.p[i].N, K = t.p[i].K;
-        flop += 2.0 * M * N * K;
-        bytes += 4.0 * (M * K + N * K + M * N);
-    }
+// ---- grouped weight gradients (host side; the problems are collected by WgradQueue, engine.h)
+// the group shares the chip (a few thousand workgroups in all): short K chains (<= 8 tiles) matter more than the extra atomics
+// of a split
+int gemm_bf16_group_plan(GroupProblem& q, int max_split) {
+    FIRA_REQUIRE(bf16_shape_ok(1, 0, q.M, q.N, q.K, q.A, q.lda, q.B, q.ldb), "gemm_bf16_group_plan: unsupported shape %dx%dx%d", q.M, q.N, q.K);
+    q.splitk = std::max(1, std::min(max_split > 0 ? max_split : 8, q.K / 512));
+    q.k_chunk = cdiv(cdiv(q.K, q.splitk), HK) * HK;
+    return 0;
+}
+int gemm_bf16_group_launch(hipStream_t s, GroupTable& t) {
+    double flop, bytes;
+    t.cost(flop, bytes);
     ProfScope prof(s, PROF_GEMM, flop, bytes);
     t.chunk = cdiv(t.wg_start[t.n], 8);
     hipLaunchKernelGGL(gemm_bf16_grouped_wgrad_kernel, dim3(8 * t.chunk), dim3(256), 0, s, t);
-    t.n = 0;
     FIRA_CHECK_LAUNCH("gemm_bf16_grouped_wgrad");
-    return 0;
-}
-// dW[M,N] += A^T B with A = dY [K,M], B = X [K,N]; db[M] += column sums of dY.  Queued; runs at the next flush on `s`.
-int gemm_bf16_group_add_wgrad(hipStream_t s, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
-                              float* C, int ldc, float* colsum, int max_split) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    FIRA_REQUIRE(bf16_shape_ok(1, 0, M, N, K, A, lda, B, ldb), "gemm_bf16_group_add_wgrad: unsupported shape %dx%dx%d", M, N, K);
-    GroupTable16& t = group16().t;
-    if (t.n == GROUP16_MAX) {
-        int rc = gemm_bf16_group_flush(s);
-        if (rc) return rc;
-    }
-    GroupProblem16& q = t.p[t.n];
-    q.A = A; q.B = B; q.C = C; q.colsum = colsum;
-    q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
-    q.tiles_m = cdiv(M, 64); q.tiles_n = cdiv(N, 64);
-    // the group shares the chip (a few thousand workgroups in all): short K chains (<= 8 tiles) matter more than the
-    // extra atomics of a split
-    q.splitk = std::max(1, std::min(max_split > 0 ? max_split : 8, K / 512));
-    q.k_chunk = cdiv(cdiv(K, q.splitk), HK) * HK;
-    t.wg_start[t.n + 1] = t.wg_start[t.n] + q.tiles_m * q.tiles_n * q.splitk;
-    ++t.n;
     return 0;
 }
 
@@ -903,6 +861,6 @@ extern "C" int fira_gemm_bf16_wb(void* stream, int M, int N, int K, const float*
 extern "C" int fira_gemm_bf16(void* stream, int transA, int transB, int M, int N, int K, const float* A, int lda,
                               const float* B, int ldb, float* C, int ldc, const float* bias, int flags, int splitk) {
     FIRA_REQUIRE(splitk >= 0, "fira_gemm_bf16: splitk must be >= 0 (0 = automatic)");
-    return fira::gemm_bf16_ex((hipStream_t)stream, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk,
-                              nullptr, nullptr, nullptr);
+    return fira::gemm_bf16_ex((hipStream_t)stream, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags & ~fira::GEMM_SIDE_PAD,
+                              splitk, nullptr, nullptr, nullptr);
 }

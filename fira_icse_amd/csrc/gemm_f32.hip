@@ -324,20 +324,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(int M, int N, int K, cons
 // Grouped weight gradients: dW_i (+)= dY_i^T X_i for up to GROUP_MAX independent problems in ONE launch.  The decoder's
 // 36 weight gradients reduce over only B*30 target rows each (0.1-0.5 GFLOP): launched one by one they cost ~15 us
 // apiece, mostly fill and drain; as one grid of ~2000 workgroups they run at the throughput of a single large GEMM.
-// The problem table travels in the kernel arguments.
-struct GroupProblem {
-    const float* A;      // dY  [K, M] (transA layout)
-    const float* B;      // X   [K, N]
-    float* C;            // dW  [M, N], accumulated
-    float* colsum;       // db  [M] or nullptr
-    int M, N, K, lda, ldb, ldc, tiles_n, splitk, k_chunk;
-};
-constexpr int GROUP_MAX = 40;
-struct GroupTable {
-    int n;
-    int wg_start[GROUP_MAX + 1];
-    GroupProblem p[GROUP_MAX];
-};
+// The problem table (engine.h: GroupTable) travels in the kernel arguments.
 __global__ __launch_bounds__(256) void gemm_grouped_wgrad_kernel(GroupTable g) {
     const int total = g.wg_start[g.n];
     for (int b = blockIdx.x; b < total; b += gridDim.x) {                          // (one item per workgroup unless the grid is capped)
@@ -360,15 +347,14 @@ __global__ __launch_bounds__(256) void gemm_grouped_wgrad_kernel(GroupTable g) {
 // (33 KB for the 32x32 tile kernel) then waits for one of them to END before it can be placed -- stream priority orders
 // the dispatch of new workgroups, it frees nothing.  With the pad (7 KB) only three fit and the chain always finds
 // room: +0.3 % step on one box (11 409 -> 11 446 commits/s over three pairs); 20 KB (two per CU) costs 0.8 %.
+// The launcher is told (GEMM_SIDE_PAD in the flags of gemm_f32_ex): the stream's owner knows.  The grouped launch always pads:
+// a queue of weight gradients has no other stream to run on.
 static constexpr unsigned SIDE_LDS_PAD = 7168;
-static hipStream_t g_pad_stream = nullptr;
-void gemm_set_pad_stream(hipStream_t s) { g_pad_stream = s; }
-static unsigned side_lds_pad(hipStream_t s) { return (s && s == g_pad_stream) ? SIDE_LDS_PAD : 0u; }
 
 template <int BM, int BN>
 static int launch(hipStream_t s, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                   float* C, int ldc, const float* bias, int flags, int splitk, float* colsum, const int32_t* c_rows,
-                  const float* relu_mask) {
+                  const float* relu_mask, unsigned lds_pad) {
     const int tiles_m = cdiv(M, BM), tiles_n = cdiv(N, BN);
     const int spread_n = (long)N > (long)M ? 1 : 0;
     const int chunk = cdiv(tiles_m * tiles_n * splitk, 8);
@@ -377,7 +363,7 @@ static int launch(hipStream_t s, int tA, int tB, int M, int N, int K, const floa
     const int vecA = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0);
     const int vecB = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0);
 #define FIRA_GEMM_GO(TA, TB)                                                                                     \
-    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, TA, TB>), grid, dim3(256), side_lds_pad(s), s, M, N, K, A, lda, B, ldb, C, ldc, \
+    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, TA, TB>), grid, dim3(256), lds_pad, s, M, N, K, A, lda, B, ldb, C, ldc,         \
                        bias, flags, k_chunk, vecA, vecB, colsum, c_rows, relu_mask, tiles_m, tiles_n, splitk, spread_n, \
                        chunk)
     if (!tA && tB) FIRA_GEMM_GO(false, true);
@@ -438,55 +424,27 @@ int gemm_f32_ex(hipStream_t s, int tA, int tB, int M, int N, int K, const float*
         if (splitk == 0) splitk = c.splitk;
     }
     FIRA_REQUIRE(!(splitk > 1 && !can_split), "gemm_f32: split-K needs accumulate semantics and no relu");
+    const unsigned pad = (flags & GEMM_SIDE_PAD) ? SIDE_LDS_PAD : 0u;
     flags &= 3;
-    if (tile == 0) return launch<128, 128>(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk, colsum, c_rows, relu_mask);
-    if (tile == 1) return launch<64, 128>(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk, colsum, c_rows, relu_mask);
-    return launch<64, 64>(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk, colsum, c_rows, relu_mask);
+    if (tile == 0) return launch<128, 128>(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk, colsum, c_rows, relu_mask, pad);
+    if (tile == 1) return launch<64, 128>(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk, colsum, c_rows, relu_mask, pad);
+    return launch<64, 64>(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk, colsum, c_rows, relu_mask, pad);
 }
 
-// ---- grouped weight gradients (host side): problems are collected, then launched together
-struct GroupBuilder {
-    GroupTable t;
-    GroupBuilder() { t.n = 0; t.wg_start[0] = 0; }
-};
-static GroupBuilder& group() { static thread_local GroupBuilder g; return g; }
-
-void gemm_group_reset() { group().t.n = 0; }
-bool gemm_group_full() { return group().t.n == GROUP_MAX; }
-int gemm_group_flush(hipStream_t s) {
-    GroupTable& t = group().t;
-    if (t.n == 0) return 0;
-    double flop = 0, bytes = 0;
-    for (int i = 0; i < t.n; ++i) {
-        const double M = t.p[i].M, N = t.p[i].N, K = t.p[i].K;
-        flop += 2.0 * M * N * K;
-        bytes += 4.0 * (M * K + N * K + M * N);
-    }
-    ProfScope prof(s, PROF_GEMM, flop, bytes);
-    hipLaunchKernelGGL(gemm_grouped_wgrad_kernel, dim3(t.wg_start[t.n]), dim3(256), side_lds_pad(s), s, t);
-    t.n = 0;
-    FIRA_CHECK_LAUNCH("gemm_grouped_wgrad");
+// ---- grouped weight gradients (host side; the problems are collected by WgradQueue, engine.h)
+// the whole group shares the chip: two K splits per tile keep the tail short without drowning the result in atomics
+int gemm_group_plan(GroupProblem& q, int max_split) {
+    q.splitk = q.K >= 512 ? 2 : 1;
+    if (max_split > 0) q.splitk = std::max(1, std::min(max_split, q.K / 512));
+    q.k_chunk = cdiv(cdiv(q.K, q.splitk), BK) * BK;
     return 0;
 }
-// dW[M,N] += A^T B with A = dY [K,M], B = X [K,N]; db[M] += column sums of dY.  Queued; runs at the next flush on `s`.
-int gemm_group_add_wgrad(hipStream_t s, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-                         int ldc, float* colsum, int max_split) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    GroupTable& t = group().t;
-    if (t.n == GROUP_MAX) {
-        int rc = gemm_group_flush(s);
-        if (rc) return rc;
-    }
-    GroupProblem& q = t.p[t.n];
-    q.A = A; q.B = B; q.C = C; q.colsum = colsum;
-    q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
-    q.tiles_n = cdiv(N, 64);
-    // the whole group shares the chip: two K splits per tile keep the tail short without drowning the result in atomics
-    q.splitk = K >= 512 ? 2 : 1;
-    if (max_split > 0) q.splitk = std::max(1, std::min(max_split, K / 512));
-    q.k_chunk = cdiv(cdiv(K, q.splitk), BK) * BK;
-    t.wg_start[t.n + 1] = t.wg_start[t.n] + cdiv(M, 64) * q.tiles_n * q.splitk;
-    ++t.n;
+int gemm_group_launch(hipStream_t s, const GroupTable& t) {
+    double flop, bytes;
+    t.cost(flop, bytes);
+    ProfScope prof(s, PROF_GEMM, flop, bytes);
+    hipLaunchKernelGGL(gemm_grouped_wgrad_kernel, dim3(t.wg_start[t.n]), dim3(256), SIDE_LDS_PAD, s, t);
+    FIRA_CHECK_LAUNCH("gemm_grouped_wgrad");
     return 0;
 }
 
@@ -500,5 +458,5 @@ int gemm_f32(hipStream_t s, int tA, int tB, int M, int N, int K, const float* A,
 extern "C" int fira_gemm_f32(void* stream, int transA, int transB, int M, int N, int K, const float* A, int lda,
                              const float* B, int ldb, float* C, int ldc, const float* bias, int flags, int splitk) {
     FIRA_REQUIRE(splitk >= 0, "fira_gemm_f32: splitk must be >= 0 (0 = automatic)");
-    return fira::gemm_f32((hipStream_t)stream, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, splitk);
+    return fira::gemm_f32((hipStream_t)stream, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags & ~fira::GEMM_SIDE_PAD, splitk);
 }

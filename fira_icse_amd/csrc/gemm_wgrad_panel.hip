@@ -41,20 +41,6 @@ typedef float pf32x16 __attribute__((ext_vector_type(16)));
 constexpr int PN_T = 256;            // output tile (rows of C = columns of A) x (columns of C = columns of B)
 constexpr int PN_KB = 16;            // reduction rows per step = the k depth of one MFMA
 constexpr int PN_PART = PN_T * 32;   // bytes of one operand part in LDS: 256 rows x 16 bf16
-constexpr int PANEL_MAX = 48;
-
-struct PanelProblem {
-    const float *A, *B;
-    float *C, *colsum;
-    float* part;                     // slabs > 1: [tiles_m * tiles_n][slabs][256 x 256] partial tiles (scratch)
-    int M, N, K, lda, ldb, ldc;
-    int tiles_m, tiles_n, slabs, k_slab;
-};
-struct PanelTable {
-    int n;
-    int wg_start[PANEL_MAX + 1];
-    PanelProblem p[PANEL_MAX];
-};
 
 // 16-byte unit of (row, k half) inside an operand part: TWO PLANES of 256 units, one per k half (8 bf16 of a row each).
 //   fetch  ds_read_b128, lanes of one 16-lane group ({0-3,12-15,20-27} / {4-11,16-19,28-31} of a half-wave) share the k half and
@@ -298,13 +284,7 @@ __global__ __launch_bounds__(256) void wgrad_panel_reduce_kernel(const PanelTabl
     }
 }
 
-// ---- host side: a queue of problems, one launch -----------------------------------------------------------------------
-struct PanelBuilder {
-    PanelTable t;
-    PanelBuilder() { t.n = 0; t.wg_start[0] = 0; }
-};
-static PanelBuilder& panel() { static thread_local PanelBuilder b; return b; }
-
+// ---- host side: the problems are collected by WgradQueue (engine.h), one launch for all of them ------------------------
 // shapes the kernel takes: at least one full 32-row MFMA tile of output rows, whole 256-column tiles of B, 8-byte aligned
 // column pairs, a result the 31-bit byte offsets of the epilogue reach
 bool gemm_wgrad_panel_takes(int M, int N, int K, const float* A, int lda, const float* B, int ldb, int ldc) {
@@ -312,27 +292,7 @@ bool gemm_wgrad_panel_takes(int M, int N, int K, const float* A, int lda, const 
            ((uintptr_t)A % 8) == 0 && ((uintptr_t)B % 8) == 0 && (long)K * lda * 4 < 0x7fffffffL && (long)K * ldb * 4 < 0x7fffffffL &&
            epilogue_fits(M, ldc);
 }
-void gemm_wgrad_panel_reset() { panel().t.n = 0; }
-bool gemm_wgrad_panel_full() { return panel().t.n == PANEL_MAX; }
-int gemm_wgrad_panel_pending() { return panel().t.n; }
-
-int gemm_wgrad_panel_add(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, float* colsum) {
-    PanelTable& t = panel().t;
-    FIRA_REQUIRE(t.n < PANEL_MAX, "gemm_wgrad_panel_add: queue full (flush first)");
-    PanelProblem& q = t.p[t.n++];
-    q.A = A; q.B = B; q.C = C; q.colsum = colsum;
-    q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
-    q.tiles_m = cdiv(M, PN_T); q.tiles_n = N / PN_T;
-    q.slabs = 1; q.k_slab = K; q.part = nullptr;
-    return 0;
-}
-// scratch for the partial tiles of split problems (256 KB per workgroup of a split problem); without one nothing is split
-static thread_local float* g_panel_scratch = nullptr;
-static thread_local size_t g_panel_scratch_floats = 0;
-void gemm_wgrad_panel_scratch(float* buf, size_t n_floats) { g_panel_scratch = buf; g_panel_scratch_floats = n_floats; }
-// np: 1 = operands rounded to bf16 once (bf16 mode), 3 = three-term split (fp32-accurate)
-int gemm_wgrad_panel_flush(hipStream_t s, int np) {
-    PanelTable& t = panel().t;
+int gemm_wgrad_panel_launch(hipStream_t s, int np, PanelTable& t, float* scratch, size_t scratch_floats) {
     if (t.n == 0) return 0;
     // Slab length: the launch's reduction rows spread over about one workgroup per CU (a slab is a multiple of 16 rows and at
     // least 256 of them: every slab of a split problem costs a 256 KB partial tile written and read once more); a launch
@@ -354,15 +314,15 @@ int gemm_wgrad_panel_flush(hipStream_t s, int np) {
         need = 0;
         for (int i = 0; i < t.n; ++i) {
             PanelProblem& q = t.p[i];
-            q.slabs = g_panel_scratch ? std::max(1, cdiv(q.K, per)) : 1;
+            q.slabs = scratch ? std::max(1, cdiv(q.K, per)) : 1;
             q.k_slab = cdiv(cdiv(q.K, q.slabs), PN_KB) * PN_KB;
             q.slabs = cdiv(q.K, q.k_slab);
             if (q.slabs > 1) need += (size_t)q.tiles_m * q.tiles_n * q.slabs * (PN_T * PN_T);
         }
-        if (need <= g_panel_scratch_floats) break;
+        if (need <= scratch_floats) break;
         per *= 2;
     }
-    if (need > g_panel_scratch_floats) {                 // (cannot happen with per doubling up to 256x: unsplit needs nothing)
+    if (need > scratch_floats) {                 // (cannot happen with per doubling up to 256x: unsplit needs nothing)
         for (int i = 0; i < t.n; ++i) { t.p[i].slabs = 1; t.p[i].k_slab = cdiv(t.p[i].K, PN_KB) * PN_KB; }
         need = 0;
     }
@@ -372,7 +332,7 @@ int gemm_wgrad_panel_flush(hipStream_t s, int np) {
         PanelProblem& q = t.p[i];
         q.part = nullptr;
         if (q.slabs > 1) {
-            q.part = g_panel_scratch + off;
+            q.part = scratch + off;
             off += (size_t)q.tiles_m * q.tiles_n * q.slabs * (PN_T * PN_T);
             bands += q.tiles_m * q.tiles_n * 64;
         }
@@ -388,18 +348,9 @@ int gemm_wgrad_panel_flush(hipStream_t s, int np) {
         hipLaunchKernelGGL(wgrad_panel_kernel<1>, dim3(t.wg_start[t.n]), dim3(512), lds, s, t);
     }
     if (bands > 0) hipLaunchKernelGGL(wgrad_panel_reduce_kernel, dim3(bands), dim3(256), 0, s, t);
-    t.n = 0;
     FIRA_CHECK_LAUNCH("wgrad_panel");
     return 0;
 }
-// one product, launched at once
-int gemm_wgrad_panel(hipStream_t s, int np, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
-                     int ldc, float* colsum) {
-    FIRA_REQUIRE(panel().t.n == 0, "gemm_wgrad_panel: problems are queued (flush first)");
-    if (int rc = gemm_wgrad_panel_add(M, N, K, A, lda, B, ldb, C, ldc, colsum)) return rc;
-    return gemm_wgrad_panel_flush(s, np);
-}
-
 }  // namespace fira
 
 extern "C" int fira_gemm_wgrad_panel(void* stream, int dtype, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
@@ -407,8 +358,8 @@ extern "C" int fira_gemm_wgrad_panel(void* stream, int dtype, int M, int N, int 
     FIRA_REQUIRE(A && B && C && (dtype == 0 || dtype == 1), "fira_gemm_wgrad_panel: bad argument");
     FIRA_REQUIRE(fira::gemm_wgrad_panel_takes(M, N, K, A, lda, B, ldb, ldc),
                  "fira_gemm_wgrad_panel: shape %d x %d x %d / alignment not taken (M >= 32, N %% 256 == 0, even pitches)", M, N, K);
-    fira::gemm_wgrad_panel_scratch(scratch, scratch ? scratch_floats : 0);
-    const int rc = fira::gemm_wgrad_panel((hipStream_t)stream, dtype == 1 ? 1 : 3, M, N, K, A, lda, B, ldb, C, ldc, colsum);
-    fira::gemm_wgrad_panel_scratch(nullptr, 0);
-    return rc;
+    fira::WgradQueue q;                      // the call's own: nothing a pending step or another thread holds is touched
+    q.reset(dtype, scratch, scratch_floats);
+    if (int rc = q.add_panel(M, N, K, A, lda, B, ldb, C, ldc, colsum)) return rc;
+    return q.flush((hipStream_t)stream);
 }

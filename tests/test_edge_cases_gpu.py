@@ -135,7 +135,10 @@ def test_a_pending_step_owns_its_state(model_sd, dtype):
     calls on the thread in between must not change its second half.  The step is begun on a sparse batch (fused GCN kernels);
     a dense batch evaluated in between (another model, its own workspaces) once switched the pending encoder backward to the
     unfused branch, which reads an aggregation the fused forward never wrote -- wrong gcn_list fc1 / fc2 gradients, no error;
-    fira_ffn_bwd in between once reset the pending step's deferred column reductions.
+    fira_ffn_bwd in between once reset the pending step's deferred column reductions.  The weight-gradient queue and its panel
+    scratch travel with the step too (engine.h: WgradQueue): fira_gemm_wgrad_panel in between once left the pending encoder
+    backward without scratch (its panel products silently unsplit), a training call on another workspace once pointed its
+    partial tiles at that workspace.
     Bounds: those of test_encoder_wgrad_schedules_give_the_same_gradient (f32) and test_two_commit_lanes_equal_one (bf16)."""
     from fira_icse_amd import ops
     from fira_icse_amd.model import TransModel, DeviceBatch
@@ -172,8 +175,17 @@ def test_a_pending_step_owns_its_state(model_sd, dtype):
         model.train_step_end(None, None, 0.0, 1, update=False)
         return model.gbuf[:model.layout.live].cpu().double()
 
+    def wgrad_panel_call():                  # a taken shape (M = 32, N = 256, K = 512), with and without the split scratch
+        g = torch.Generator().manual_seed(11)
+        r = lambda *s: (0.1 * torch.randn(*s, generator=g)).cuda()
+        A, B = r(512, 32), r(512, 256)
+        for split in (True, False):
+            ops.gemm_wgrad_panel(A, B, torch.zeros(32, 256, device="cuda"), dtype=int(dtype == "bf16"), split=split)
+
     want = step(None)
-    cases = {"dense forward_dev": lambda: other.forward_dev(db_dense)}
+    cases = {"dense forward_dev": lambda: other.forward_dev(db_dense),
+             "gemm_wgrad_panel": wgrad_panel_call,
+             "train_fwd_bwd on another workspace": lambda: other.train_fwd_bwd(db_sparse)}
     if dtype == "f32":
         cases["ffn_bwd"] = ffn_bwd_call
     tol, tol_gcn = (1e-5, 2e-5) if dtype == "f32" else (3e-3, 3e-3)
