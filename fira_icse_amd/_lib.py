@@ -203,6 +203,7 @@ SIGNATURES = {
     "fira_decode_step_sample": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _F, _I, _F, _P, _P, _P, _I]),
     "fira_decode_step_sample_cut": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _F, _I, _F, _F, _F, _F, _F, _P, _P, _P,
                                         _I]),
+    "fira_sample_dist": (_I, [_P, _DP, _I, _I, _I, _P, _P, _P, _F, _I, _F, _F, _F, _F, _F, _P, _P]),
     "fira_decode_step_score": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I] + [_P] * 15 + [_I]),
     "fira_sample_advance": (_I, [_P, _DP, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_decoder_forward": (_I, [_P, _DP, _P, _P, _Z, _I, _P, _P, _P, _P]),

@@ -995,6 +995,82 @@ class Searcher:
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
                 st["logp"].view(B, n).clone())
 
+    def _sample_search_steps(self, st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts):
+        """Steps lo..hi-1 of ``sample_search``: the step (every member's and the mix, or the neighbour's and the mix) into the
+        state's distribution, the edit chain without an arg-max, the draw from the rows as they then stand, the bookkeeping of
+        ``sample``; no torch op, no host round trip."""
+        lib, s, dims = _lib.lib(), _lib.cur_stream(), C.byref(self.model.dims)
+        R = B * n
+        for step in range(lo, hi):
+            self._step(ws, B, n, step, st["tok"], None, st["dist"], None, None)
+            self._edit(st, R, n, st["out"], st["length"], None)
+            _lib.check(lib.fira_sample_dist(s, dims, R, n, step, _lib.ptr(st["dist"]), _lib.ptr(st["key"]), _lib.ptr(st["seed"]),
+                                            float(temperature), int(top_k), float(top_p), *cuts, _lib.ptr(st["best_id"]),
+                                            _lib.ptr(st["best_p"])), "fira_sample_dist")
+            _lib.check(lib.fira_sample_advance(s, dims, B, n, step, _lib.ptr(st["best_id"]), _lib.ptr(st["best_p"]),
+                                               _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["out"]),
+                                               _lib.ptr(st["length"]), _lib.ptr(st["prob"]), _lib.ptr(st["logp"]),
+                                               _lib.ptr(st["alive"]), _lib.ptr(st["tok"]), _lib.ptr(st["n_alive"])),
+                       "fira_sample_advance")
+
+    @torch.no_grad()
+    def sample_search(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                      min_p: float = 0.0, epsilon: float = 0.0, eta: float = 0.0, typical_p: float = 1.0, seed: int = 0, keys=None,
+                      constraints: Optional[Constraints] = None, merge_copies: bool = False, prefix=None,
+                      neighbour: Optional[Neighbour] = None, chunk: int = 5, use_graphs: bool = True):
+        """``n`` sampled messages per commit, drawn from the search's EDITED distribution: what ``sample`` returns (tokens
+        [B,n,T], lengths [B,n], probability [B,n], log-probability [B,n]), with every option of the searches -- ``constraints``,
+        ``merge_copies``, ``prefix`` (the class's options), an ensemble (``members=``) and a ``neighbour`` -- and every filter and
+        cut of ``sample``.  Per step: the decoder step writes its distribution (every member's and ``fira_mix_dist``, or the
+        neighbour's and ``fira_mix_neighbour``), the edit chain (``_edit``) edits it, ``fira_sample_dist`` applies the filters, the
+        cuts and the Gumbel-max draw to the rows as they then stand, ``fira_sample_advance`` appends.  The rows are not
+        renormalised; the filters work relative to each row's own sums, an entry with probability 0 is never drawn, and the
+        returned probabilities are the edited (untempered, unfiltered) values of the entries taken: a word's probability after
+        a merge, the mixed probability after a mix, the joint probability of prefix and continuation with a prefix.  A row the
+        edits left without a positive entry takes entry 0 with probability 0 (log-probability -inf).
+
+        What holds exactly:
+          * no option and no members: ``sample``'s result, bit for bit, for the same filters, cuts, seed and keys;
+          * ``top_k=1``: ``greedy(...)`` with the same options, wherever every step's maximum is unique;
+          * members with weights (1, 0, ...): the single model's result;
+          * a neighbour with ``lam = 0``: the plain result.
+
+        The filters and cuts are fixed in the captured launches and join the state's key with the options (``_key``); the
+        prefix, the seed, the keys and the neighbour's coefficients are device values, so one capture serves all of them.
+        There is no ``require=``: banks need a beam.  A ``ValueError`` before anything is launched on a value outside its
+        range, ``n`` outside 1..8, or whatever the options' own checks refuse (a neighbour with members among them)."""
+        cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)     # every refusal: before anything is launched
+        if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 1 <= n <= 8:
+            raise ValueError("n = %r: samples per commit outside 1..8" % (n,))
+        temperature, top_p = C.c_float(float(temperature)).value, C.c_float(float(top_p)).value
+        if not 0 < temperature < float("inf"):
+            raise ValueError("temperature %r: must be finite and > 0" % temperature)
+        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or not 0 <= top_k <= self.cfg.out_len:
+            raise ValueError("top_k %r: must be an integer in 0..%d (0 = off)" % (top_k, self.cfg.out_len))
+        if not 0 < top_p <= 1:
+            raise ValueError("top_p %r: must be in (0, 1] (1 = off)" % top_p)
+        n, top_k = int(n), int(top_k)
+        B, T = db.B, self.cfg.tar_len
+        R = B * n
+        con = self._active(constraints)
+        merge = bool(merge_copies)
+        rows = self._prefix_rows(prefix, B, con)
+        nb = self._neighbour(neighbour, B)
+        noise_rows, fill_noise = self._noise(keys, seed, B)
+        make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), **noise_rows(i32),
+                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True))
+        key = self._key(("sample_search", B, n, temperature, top_k, top_p) + cuts, merge, con, forced=rows is not None,
+                        neighbour=nb is not None)
+        loop = _Loop(self, db, n, key, make, chunk, use_graphs, nb)
+        st, ws = loop.st, loop.ws
+        fill_noise(st)
+        if rows is not None:
+            self._fill_prefix(st, rows)
+        loop.start(lambda lo, hi: self._sample_search_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts),
+                   lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
+        return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
+                st["logp"].view(B, n).clone())
+
     def best_sample(self, tokens, lengths, logp) -> List[List[int]]:
         """The highest-log-probability sample per commit, first on ties."""
         return self.best(tokens, lengths, logp)

@@ -1185,6 +1185,33 @@ int fira_sample_advance(void* stream, const fira_dims* d, int B, int n_sample, i
                         const float* best_p, const int32_t* sou, const int32_t* sub_token, int32_t* out, int32_t* length,
                         float* prob, float* logp, int32_t* alive, int32_t* tokens, int32_t* n_alive);
 
+/* Sampling from the search's edited distribution (csrc/sample_row.hip; additive, the ABI version is
+ * unchanged): the filters, cuts and Gumbel-max draw of fira_decode_step_sample_cut applied to rows that already exist in memory,
+ * after fira_decode_step_ex (fira_mix_dist / fira_mix_neighbour) and the edit chain (fira_merge_dist, fira_force_dist,
+ * fira_constrain_dist) and before fira_sample_advance.  W = vocab + sou_len + sub_len; row r belongs to commit
+ * b = r / rows_per_commit and is its sample j = r % rows_per_commit; the noise is fira_decode_step_sample's, of (seed, key[b], j,
+ * tar_len, step, entry).  dist is only read, at any 4-byte alignment.
+ *   Definitions on an UNNORMALISED row (the edits renormalise nothing): those of fira_decode_step_sample_cut with every quantity
+ *   taken relative to the row's own sums -- top-p keeps at least top_p of the mass top-k kept, q = w / Z over the kept entries, w
+ *   relative to the row's largest entry as it stands (the block maximum, not the step's own maximum: an edit may have zeroed it).
+ *   An entry with p = 0 is never kept and never drawn; with fewer than top_k positive entries top-k cuts nothing.  Scaling a row
+ *   by a power of two changes neither the kept set nor the draw.
+ *   best_id[r] the drawn entry, best_p[r] = dist[r, best_id[r]] bit for bit (edited, untempered, unfiltered: a word's probability
+ *   after a merge, the mixed probability after a mix).  On the rows fira_decode_step_sample_cut stores (its dist argument) the
+ *   pair equals that call's own, bit for bit.  Every row is written: a row without a positive entry gets what the edit chain's
+ *   arg-max reports for it, best_id = 0 and best_p = 0.0f (fira_sample_advance then carries probability 0, log-probability -inf).
+ *   Contract: entries finite and non-negative; on anything else the result is unspecified, but best_id stays inside [0, W) and
+ *   nothing but best_id / best_p is written.
+ * Refused with the reason in fira_last_error() and nothing launched or written: a null best_id or best_p, rows_per_commit outside
+ * 1..8 or not dividing R, a negative step, vocab outside 4 .. 25 600 or sou_len + sub_len > 1 024, top_k outside 0..W, and the
+ * argument ranges and combinations fira_decode_step_sample_cut refuses; with R > 0 a null dist, key or seed_dev.  R == 0 is a
+ * no-op.  Vector stores only, no atomics on global memory.                                                                      */
+int fira_sample_dist(void* stream, const fira_dims* d, int R, int rows_per_commit, int step,
+                     const float* dist /* [R, vocab + sou_len + sub_len], read only */,
+                     const int32_t* key /* [R / rows_per_commit] */, const uint64_t* seed_dev,
+                     float temperature, int top_k, float top_p, float min_p, float epsilon, float eta, float typical_p,
+                     int32_t* best_id /* [R] */, float* best_p /* [R] */);
+
 /* Teacher-forced scoring of given candidate messages: how probable is this message for this commit?  Workspace:
  * fira_decode_begin_ex / fira_decode_workspace_bytes_ex with n_beam = n_cand (1..8) and the same flags
  * (FIRA_DECODE_KV_BF16 allowed), so the encoder, the cross-attention K|V and LinearSource(memory) are computed once per
