@@ -1,7 +1,8 @@
 // The decode-row toolkit: what the 1024-thread kernels that work on one row of the decode step's output distribution
 // dist[r, 0 .. V + L + S) have in common.  A kernel that includes this header states only what it adds.
 //   geometry    ROW_MAX_V / ROW_MAX_SLOTS / ROW_MAX_T, BEAM_MAX, require_row_geometry (host)
-//   reductions  block16_sum, block16_argmax: the 16 wave partials combined in one fixed order, every thread gets the result
+//   reductions  block16_sum, block16_min, block16_max, block16_argmax: the 16 wave partials combined in one fixed order, every
+//               thread gets the result
 //   the order   better(): value descending, index ascending; NaN is never better than anything.  ArgMax carries it.
 //   the row     WideRow: the distribution itself (decode_dist_wide_kernel, sample_dist_kernel, score_dist_kernel) -- one
 //               body, so the three kernels' rows are bit-identical by construction
@@ -54,6 +55,28 @@ __device__ __forceinline__ float block16_sum(float v, float* sm) {
     float t = 0.f;
 #pragma unroll
     for (int k = 0; k < DDW_NT / 64; ++k) t += sm[k];
+    return t;
+}
+__device__ __forceinline__ int block16_min(int v, int* sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int t = sm[0];
+#pragma unroll
+    for (int k = 1; k < DDW_NT / 64; ++k) t = min(t, sm[k]);
+    return t;
+}
+__device__ __forceinline__ float block16_max(float v, float* sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = sm[0];
+#pragma unroll
+    for (int k = 1; k < DDW_NT / 64; ++k) t = fmaxf(t, sm[k]);
     return t;
 }
 __device__ __forceinline__ void block16_argmax(float& v, int& idx, float* smv, int* smi) {

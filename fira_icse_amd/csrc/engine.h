@@ -372,6 +372,9 @@ struct SampleCuts {
     float min_p = 0.f, epsilon = 0.f, eta = 0.f, typical_p = 1.f;
     bool on() const { return min_p > 0.f || epsilon > 0.f || eta > 0.f || typical_p < 1.f; }
 };
+// the range and combination checks of a sampler call over rows of W entries, in the order temperature, top_k, top_p, cuts
+// (cut may be null: no cuts); 0, or the error set under `who`'s name
+int require_sampler_args(const char* who, int W, float temperature, int top_k, float top_p, const SampleCuts* cut);
 int sample_dist(hipStream_t s, int R, int n_sample, int V, int S, const float* logits, int ldl, const float* score,
                 const int32_t* mem_valid, const float* x, const float* wp, const float* bp, int T, int step,
                 const int32_t* key, const uint64_t* seed_dev, float temperature, int top_k, float top_p, float* dist,

@@ -2348,28 +2348,7 @@ static int decode_step_sample(const char* who, void* stream, const fira_dims* d,
                               float* dist, int32_t* best_id, float* best_p, int flags) {
     FIRA_REQUIRE(d, "%s: bad argument", who);
     FIRA_REQUIRE(n_sample >= 1 && n_sample <= 8, "%s: n_sample %d outside 1..8", who, n_sample);
-    FIRA_REQUIRE(temperature > 0.f && temperature < INFINITY, "%s: temperature %g must be finite and > 0", who,
-                 (double)temperature);
-    const int W = d->vocab + d->sou_len + d->sub_len;
-    FIRA_REQUIRE(top_k >= 0 && top_k <= W, "%s: top_k %d outside 0..%d", who, top_k, W);
-    FIRA_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p %g outside (0, 1]", who, (double)top_p);
-    if (cut) {                                               // (every comparison also refuses nan)
-        FIRA_REQUIRE(cut->min_p >= 0.f && cut->min_p < 1.f, "%s: min_p %g outside [0, 1)", who, (double)cut->min_p);
-        FIRA_REQUIRE(cut->epsilon >= 0.f && cut->epsilon < 1.f, "%s: epsilon %g outside [0, 1)", who, (double)cut->epsilon);
-        FIRA_REQUIRE(cut->eta >= 0.f && cut->eta < 1.f, "%s: eta %g outside [0, 1)", who, (double)cut->eta);
-        FIRA_REQUIRE(cut->typical_p > 0.f && cut->typical_p <= 1.f, "%s: typical_p %g outside (0, 1]", who,
-                     (double)cut->typical_p);
-        if (cut->typical_p < 1.f) {                          // a band in p, not a lower threshold: temperature and top-k only
-            FIRA_REQUIRE(top_p == 1.f, "%s: typical_p %g does not combine with top_p %g", who, (double)cut->typical_p,
-                         (double)top_p);
-            FIRA_REQUIRE(cut->min_p == 0.f, "%s: typical_p %g does not combine with min_p %g", who, (double)cut->typical_p,
-                         (double)cut->min_p);
-            FIRA_REQUIRE(cut->epsilon == 0.f, "%s: typical_p %g does not combine with epsilon %g", who, (double)cut->typical_p,
-                         (double)cut->epsilon);
-            FIRA_REQUIRE(cut->eta == 0.f, "%s: typical_p %g does not combine with eta %g", who, (double)cut->typical_p,
-                         (double)cut->eta);
-        }
-    }
+    TRY(require_sampler_args(who, d->vocab + d->sou_len + d->sub_len, temperature, top_k, top_p, cut));
     FIRA_REQUIRE(key && seed_dev && best_id && best_p, "%s: key, seed_dev, best_id and best_p are required", who);
     hipStream_t s = (hipStream_t)stream;
     DecodePlan dp;

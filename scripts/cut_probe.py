@@ -1,11 +1,11 @@
-"""ms per step of the replayed sampling loop (Searcher.sample) with each truncation cut against the cuts-off call, and the
-cuts-off call of this tree's library against another build of it (the parent commit's).
+"""ms per step of the replayed sampling loop (Searcher.sample) with each truncation cut against the cuts-off call, and every
+row of this tree's library against another build of it (the parent commit's).
 
     python scripts/cut_probe.py [--reps 5] [--rounds 2] [--parent-lib PATH/libfira_hip.so] [--md profiles/cut_probe.md]
 
 Every library is timed in a process of its own (FIRA_HIP_LIB), the two alternating over the rounds.  The loop runs all
 tar_len - 1 steps (the captured graphs are timed directly, so the early stop does not shorten it): the time per step is
-the chain's, whatever the samples emit.  The parent's library has no cut entry: only the cuts-off rows are timed there."""
+the chain's, whatever the samples emit.  Both libraries are timed on every row."""
 import argparse
 import json
 import os
@@ -27,12 +27,10 @@ CASES = [("off", {}), ("off_k50_p95", dict(top_k=50, top_p=0.95)), ("min_p_0.05"
 CUT_NAMES = ("min_p", "epsilon", "eta", "typical_p")
 
 
-def worker(reps, with_cuts):
+def worker(reps):
     import torch
-    from fira_icse_amd import _lib, data, synth
+    from fira_icse_amd import data, synth
     from fira_icse_amd.config import FiraConfig
-    if not with_cuts:                                        # a build from before the cut entry: bind what it exports
-        _lib.SIGNATURES.pop("fira_decode_step_sample_cut")
     from fira_icse_amd.decode import Searcher
     from fira_icse_amd.model import DeviceBatch, TransModel
     cfg = FiraConfig()
@@ -45,8 +43,6 @@ def worker(reps, with_cuts):
     steps = cfg.tar_len - 1
     res = {"device": torch.cuda.get_device_name(0)}
     for name, kw in CASES:
-        if any(k in kw for k in CUT_NAMES) and not with_cuts:
-            continue
         kw = dict(BASE, **kw)
         search.sample(db, N, seed=1, **kw)
         key = ("sample", B, N, float(kw["temperature"]), int(kw["top_k"]), float(kw["top_p"]))
@@ -68,12 +64,12 @@ def worker(reps, with_cuts):
     print("RESULT " + json.dumps(res))
 
 
-def run_worker(lib, reps, with_cuts):
+def run_worker(lib, reps):
     env = dict(os.environ)
     if lib:
         env["FIRA_HIP_LIB"] = lib
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", "--reps", str(reps)] + ([] if with_cuts else ["--no-cuts"]),
-                       env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", "--reps", str(reps)], env=env, capture_output=True,
+                       text=True, timeout=600)
     if r.returncode != 0:
         raise RuntimeError("worker failed (%d):\n%s" % (r.returncode, (r.stdout + r.stderr)[-3000:]))
     return json.loads([l for l in r.stdout.split("\n") if l.startswith("RESULT ")][-1][7:])
@@ -86,15 +82,14 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--md", default=None)
     ap.add_argument("--worker", action="store_true")
-    ap.add_argument("--no-cuts", action="store_true")
     a = ap.parse_args()
     if a.worker:
-        return worker(a.reps, not a.no_cuts)
+        return worker(a.reps)
     runs = {"this tree": [], "parent commit": []}
     for _ in range(a.rounds):
-        runs["this tree"].append(run_worker(None, a.reps, True))
+        runs["this tree"].append(run_worker(None, a.reps))
         if a.parent_lib:
-            runs["parent commit"].append(run_worker(os.path.abspath(a.parent_lib), a.reps, False))
+            runs["parent commit"].append(run_worker(os.path.abspath(a.parent_lib), a.reps))
     device = runs["this tree"][0]["device"]
     rows = []
     for tree, rs in runs.items():
@@ -108,7 +103,7 @@ def main():
            "| library | filters and cuts | median ms / step | min | max | against off (this tree) |", "|---|---|---|---|---|---|"]
     for t, n, m, lo, hi in rows:
         out.append("| %s | %s | %.4f | %.4f | %.4f | %+.4f |" % (t, n, m, lo, hi, m - med[("this tree", "off")]))
-    for n in ("off", "off_k50_p95"):
+    for n, _ in CASES:
         if ("parent commit", n) in med:
             d = med[("this tree", n)] - med[("parent commit", n)]
             out.append("")

@@ -1,10 +1,13 @@
 """Sampling from the search's edited distribution on the device (fira_sample_dist / Searcher.sample_search): on the fused
 sampler's own rows the kernel draws what the fused sampler draws, bit for bit; on synthetic edited rows (unnormalised, with
-zeros, at every alignment) it follows the numpy statement (sample_search_ref.py); the draws follow the filtered law of an edited
+zeros, at every alignment) it follows the numpy statement (sample_search_ref.py) and reproduces the recorded draws of
+tests/golden/sampler_draws.npz bit for bit; the draws follow the filtered law of an edited
 row; top_k = 1 is the edit chain's arg-max; sample_search without options is sample, with options it honours them, and its
 exact reductions (greedy, a (1, 0) ensemble, a neighbour with lam = 0) hold; the calls per step; the library's argument errors."""
 import ctypes as C
 import functools
+import importlib.util
+import os
 import re
 
 import numpy as np
@@ -162,6 +165,35 @@ def test_synthetic_edited_rows_at_every_alignment_follow_the_statement(V, L, S):
             # dist and the guard words: bitwise untouched
             assert torch.equal(bits(view.cpu()), want_bits) and outside_untouched(buf, offset, R * W, fill=GUARD)
     assert compared >= 0.8 * total
+
+
+def test_recorded_draws_are_reproduced_bit_for_bit():
+    """tests/golden/sampler_draws.npz (scripts/record_sampler_draws.py: recorded from the library before the sampler body was
+    shared between sample.hip and sample_row.hip) replayed: every best_id equal, every best_p equal as bits -- 3 geometries x
+    4 offsets x 9 settings x 32 rows (4 kinds under 8 noise streams) = 3 456 draws, no tolerance.  The small geometries' rows come from the fixture, the large
+    one from the script's integer formula."""
+    spec = importlib.util.spec_from_file_location("record_sampler_draws", os.path.join(util.REPO, "scripts", "record_sampler_draws.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    fx = np.load(os.path.join(util.REPO, "tests", "golden", "sampler_draws.npz"))
+    assert [tuple(g) for g in fx["geometries"].tolist()] == GEOMETRIES and tuple(fx["fields"]) == rec.FIELDS
+    compared = 0
+    for g in GEOMETRIES:
+        name = rec.name(g)
+        stored = "rows_" + name in fx.files
+        rows = fx["rows_" + name] if stored else rec.pinned_rows(sum(g))
+        assert stored == (g in rec.STORED) and [int((r > 0).sum()) for r in rows[2:]] == [1, 0]
+        assert (rows[0] > 0).all() and (rows[1] == 0).sum() > 0.4 * rows.shape[1] and rows[1, rows[0].argmax()] == 0
+        table = fx["settings_" + name]
+        for k, f in enumerate(rec.FIELDS):                                   # every filter and cut is on somewhere, off somewhere
+            on = table[:, k] != rec.DEFAULTS[f]
+            assert on.any() and not on.all(), f
+        ids, p_bits = rec.replay(g, rows, table, int(fx["rpc"]), int(fx["step"]), int(fx["seed"]), fx["keys"].tolist())
+        assert np.array_equal(ids, fx["best_id_" + name]), np.argwhere(ids != fx["best_id_" + name])[:5]
+        assert np.array_equal(p_bits, fx["best_p_bits_" + name]), np.argwhere(p_bits != fx["best_p_bits_" + name])[:5]
+        assert (ids[:, :, 3::4] == 0).all() and (p_bits[:, :, 3::4] == 0).all()   # the empty rows' documented pair
+        compared += ids.size
+    assert compared == 3456
 
 
 # ------------------------------------------------------------------------------------------------ 3. the law of the draws
