@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import functools
 import gc
 import numbers
 from typing import List, Optional, Tuple
@@ -170,6 +171,122 @@ class BeamScoring:
         return [1.0 / ((5.0 + m) / 6.0) ** self.length_alpha for m in range(tar_len + 1)]
 
 
+@dataclasses.dataclass(frozen=True)
+class Penalties:
+    """Soft word penalties and biases of a search (``fira_penalise_dist``).  Where ``Constraints`` forbids a
+    word, this makes it less or more likely: the entries of the WORD -- its generator id and every copy slot of the commit that
+    carries it -- are multiplied by a factor; nothing is renormalised.
+
+    ``presence`` a and ``frequency`` f, each in [0, 10] (the OpenAI / vLLM meaning): a word the message holds c >= 1 times is
+    multiplied by exp(-(a + f c)) -- the table ``table(tar_len)``: t[c] = float32(exp(-(float64(a) + float64(f) * c))), t[0] = 1.
+    A factor that underflows to 0 bans the repeated word.
+    ``bias``: None, one mapping {vocabulary id: b} used for every commit, or a sequence of one mapping (or None) per commit
+    (the OpenAI ``logit_bias``).  b in [-30, 30]; the word is multiplied by float32(exp(float64(b))) at every step.  At most 16 ids
+    per commit, each <eos> (1) or in [UNK, vocab) = [3, vocab): <pad> and <start> are refused.  Stored as sorted (id, b) pairs.
+
+    Values are checked here (``ValueError`` with the reason); what depends on the model and the batch is checked by ``check``
+    when a ``Searcher`` takes the value.  The value a search returns under an active ``Penalties`` is the product of the EDITED
+    entries taken: a score, not a probability (``Searcher.score`` gives the model's probability of a message)."""
+    presence: float = 0.0
+    frequency: float = 0.0
+    bias: object = None
+
+    MAX_PENALTY, MAX_BIAS, MAX_BIASED = 10.0, 30.0, 16
+    MAX_LOG_SCORE = 87.0                             # ln FLT_MAX = 88.72...
+
+    def __post_init__(self):
+        for name in ("presence", "frequency"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, numbers.Real):
+                raise ValueError("Penalties: %s = %r is not a number" % (name, v))
+            if not 0 <= v <= self.MAX_PENALTY:                # (also refuses nan)
+                raise ValueError("Penalties: %s = %r outside [0, %g]" % (name, v, self.MAX_PENALTY))
+            object.__setattr__(self, name, float(v))
+        bias = self.bias
+        shared = bias is None or hasattr(bias, "items")
+        if shared:
+            rows = [bias]
+        else:
+            try:
+                rows = list(bias)
+            except TypeError:
+                raise ValueError("Penalties: bias = %r is neither a mapping {id: b} nor a sequence of them" % (bias,)) from None
+        out = []
+        for k, row in enumerate(rows):
+            where = "bias" if shared else "bias of commit %d" % k
+            if row is None:
+                out.append(())
+                continue
+            if not hasattr(row, "items"):
+                raise ValueError("Penalties: %s = %r is not a mapping {id: b}" % (where, row))
+            pairs = list(row.items())
+            for w, b in pairs:
+                if isinstance(w, bool) or not isinstance(w, numbers.Integral):
+                    raise ValueError("Penalties: %s: id %r is not an integer" % (where, w))
+                if w != EOS and w < UNK:
+                    raise ValueError("Penalties: %s: id %d is neither <eos> (%d) nor at least %d (<pad> and <start> cannot be "
+                                     "biased)" % (where, w, EOS, UNK))
+                if isinstance(b, bool) or not isinstance(b, numbers.Real):
+                    raise ValueError("Penalties: %s: the bias %r of id %d is not a number" % (where, b, w))
+                if not -self.MAX_BIAS <= b <= self.MAX_BIAS:  # (also refuses nan)
+                    raise ValueError("Penalties: %s: the bias %r of id %d is outside [-%g, %g]" % (where, b, w, self.MAX_BIAS,
+                                                                                                  self.MAX_BIAS))
+            if len(pairs) > self.MAX_BIASED:                  # (a mapping's keys are distinct: so are the ids)
+                raise ValueError("Penalties: %s: %d ids, more than %d" % (where, len(pairs), self.MAX_BIASED))
+            out.append(tuple(sorted((int(w), float(b)) for w, b in pairs)))
+        object.__setattr__(self, "bias", None if bias is None else out[0] if shared else tuple(out))
+        object.__setattr__(self, "_shared", shared)
+
+    @property
+    def active(self) -> bool:
+        return bool(self.presence or self.frequency or any(b for row in self._rows(1) for _, b in row))
+
+    def _rows(self, B: int):
+        """The (id, b) pairs of each of B commits (a per-commit value: of the commits it was given for)."""
+        if self.bias is None:
+            return [()] * B
+        return [self.bias] * B if self._shared else list(self.bias)
+
+    def check(self, cfg, B: int) -> "Penalties":
+        """Against a model's geometry and a batch of B commits: the number of mappings, the ids against the vocabulary, and the
+        overflow bound max(b, 0) * (tar_len - 1) <= 87 -- a message's score is a product of at most tar_len - 1 edited values,
+        each at most exp(max b), and ln FLT_MAX = 88.7."""
+        if not self._shared and len(self.bias) != B:
+            raise ValueError("Penalties: %d bias mappings for a batch of %d commits" % (len(self.bias), B))
+        for k, row in enumerate(self._rows(B)):
+            for w, b in row:
+                if w >= cfg.vocab_size:
+                    raise ValueError("Penalties: commit %d: id %d outside the vocabulary [%d, %d)" % (k, w, UNK, cfg.vocab_size))
+                if max(b, 0.0) * (cfg.tar_len - 1) > self.MAX_LOG_SCORE:
+                    raise ValueError("Penalties: commit %d: the bias %g of id %d times tar_len - 1 = %d exceeds %g (a message's "
+                                     "score could overflow fp32): at most %g" % (k, b, w, cfg.tar_len - 1, self.MAX_LOG_SCORE,
+                                                                                 self.MAX_LOG_SCORE / (cfg.tar_len - 1)))
+        return self
+
+    def table(self, tar_len: int):
+        """count_factor [tar_len] float32: the exponent formed in float64, the factor cast once -- the kernel's work is then one
+        fp32 multiplication, which numpy repeats bit for bit."""
+        import numpy as np
+        c = np.arange(tar_len, dtype=np.float64)
+        t = np.exp(-(np.float64(self.presence) + np.float64(self.frequency) * c)).astype(np.float32)
+        t[0] = np.float32(1.0)
+        return t
+
+    def bias_arrays(self, B: int):
+        """(bias_id [B, 16] int32, bias_factor [B, 16] float32 = float32(exp(float64(b))), n_bias [B] int32) of B commits;
+        unused pairs hold id 0 and factor 1."""
+        import numpy as np
+        ids = np.zeros((B, self.MAX_BIASED), dtype=np.int32)
+        fac = np.ones((B, self.MAX_BIASED), dtype=np.float32)
+        n = np.zeros(B, dtype=np.int32)
+        for k, row in enumerate(self._rows(B)):
+            n[k] = len(row)
+            for q, (w, b) in enumerate(row):
+                ids[k, q] = w
+                fac[k, q] = np.float32(np.exp(np.float64(b)))
+        return ids, fac, n
+
+
 class Scores(dict):
     """Result of ``Searcher.score``: a dict whose keys also read as attributes."""
 
@@ -293,6 +410,18 @@ def rank_values(scores, by: str) -> torch.Tensor:
     return scores[by]
 
 
+def _refuses_penalties(why: str):
+    """For a search whose published signature stays as it is: ``penalties=`` is taken for one purpose only, to refuse an active
+    value with the reason (``Searcher._no_penalties``) before the search itself is entered; it is not handed on."""
+    def wrap(search):
+        @functools.wraps(search)
+        def refusing(self, *args, penalties=None, **kwargs):
+            Searcher._no_penalties(search.__name__, why, penalties)
+            return search(self, *args, **kwargs)
+        return refusing
+    return wrap
+
+
 class _Loop:
     """The chunked step loop of one search over one batch, on the current stream.
 
@@ -378,10 +507,10 @@ class _Loop:
 
 
 class Searcher:
-    """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many`` and ``beam`` take three options that edit the
-    step's distribution before a word is chosen (``sample_distinct`` takes the first two); ``_edit`` is the one place that
-    issues their kernels, in the order merge, prefix, constraints.  Each is off by default, and off -- None, False, an inactive
-    value, an all-empty prefix -- means the calls, keys, buffers and graphs of a search without it.
+    """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many``, ``beam`` and ``sample_search`` take four options
+    that edit the step's distribution before a word is chosen (``sample_distinct`` takes the first two); ``_edit`` is the one place
+    that issues their kernels, in the order merge, prefix, constraints, penalties.  Each is off by default, and off -- None, False,
+    an inactive value, an all-empty prefix -- means the calls, keys, buffers and graphs of a search without it.
 
     ``constraints``: a ``Constraints`` value.  ``fira_constrain_dist`` zeroes the blocked words' entries of every row between
     the step and the selection; nothing is renormalised (greedy: probability = the product of the UNnormalised entries taken).
@@ -404,7 +533,15 @@ class Searcher:
     and the beam may spend slots on several of them, exactly as it does on unforced steps.  The state is keyed by a "prefix"
     marker, not by the values (device buffers read when the kernels run: one capture serves every prefix).  A ``ValueError``
     before anything is launched on a wrong count, a non-integer id, an id outside [UNK, vocab), a prefix that is too long, or --
-    with ``constraints`` -- one that holds a banned id or itself repeats an n-gram."""
+    with ``constraints`` -- one that holds a banned id or itself repeats an n-gram.
+
+    ``penalties``: a ``Penalties`` value -- presence and frequency penalties on the words a hypothesis already holds (prefix words
+    count as emitted) and a per-word bias.  ``fira_penalise_dist`` multiplies the words' entries by their factors, last in the
+    chain: a finite non-negative factor commutes bit for bit with the zeroing links, and after a merge a word's mass sits on its
+    generator entry.  The value a search then returns is the product of the EDITED entries taken: a score, not a probability
+    (``score`` gives the model's probability of a message).  The state is keyed by a "penalties" marker, not by the values (the
+    table and the bias lists are device buffers, filled on every call: one capture serves every value).  ``sample``, ``score``,
+    ``sample_distinct`` and ``contrastive`` refuse an active value with a ``ValueError`` before anything is launched."""
 
     def __init__(self, model: TransModel, kv_bf16: bool = False, members=(), weights=None):
         """``kv_bf16``: stream a bf16 copy of the cross-attention K|V in the step loop (FIRA_DECODE_KV_BF16: half of the
@@ -532,6 +669,28 @@ class Searcher:
             raise ValueError("constraints: expected decode.Constraints or None, got %r" % (constraints,))
         return constraints.check(self.cfg) if constraints.active else None
 
+    def _penalties(self, penalties, B: int) -> Optional[Penalties]:
+        """None for "no penalties" (None or an inactive value: today's launches, buffers and graphs), else the value checked
+        against the model and the batch; raises before any launch."""
+        if penalties is None:
+            return None
+        if not isinstance(penalties, Penalties):
+            raise ValueError("penalties: expected decode.Penalties or None, got %r" % (penalties,))
+        return penalties.check(self.cfg, B) if penalties.active else None
+
+    @staticmethod
+    def _no_penalties(what: str, why: str, penalties):
+        if penalties is not None and (not isinstance(penalties, Penalties) or penalties.active):
+            raise ValueError("%s does not take penalties (%s); greedy, greedy_many, beam and sample_search do" % (what, why))
+
+    def _fill_penalties(self, st, pen: Penalties, B: int):
+        """The checked value into the state's device buffers (every call, like the prefix buffers)."""
+        ids, fac, n = pen.bias_arrays(B)
+        st["count_factor"].copy_(torch.from_numpy(pen.table(self.cfg.tar_len)))
+        st["bias_id"].copy_(torch.from_numpy(ids))
+        st["bias_factor"].copy_(torch.from_numpy(fac))
+        st["n_bias"].copy_(torch.from_numpy(n))
+
     def _neighbour(self, neighbour, B: int):
         """None for "no neighbour" (today's launches, buffers and graphs), else the checked value; raises before any launch."""
         if neighbour is None:
@@ -558,6 +717,10 @@ class Searcher:
         when the kernel runs.
         constrain (st["con"]): ``fira_constrain_dist`` zeroes the blocked words' entries (section 6k); nothing is renormalised.
         Its scalars are baked into a captured graph.
+        penalise ("penalties" in st): ``fira_penalise_dist`` multiplies the entries of the words a row already holds, and of the
+        commit's biased words, by their factors (section 6za).  Last: a finite non-negative factor commutes bit for bit with the
+        zeroing links, and after a merge a word's mass sits on its generator entry.  The table and the bias lists are read from
+        st["count_factor"] / st["bias_id"] / st["bias_factor"] / st["n_bias"] when the kernel runs.
 
         ``best``: (best_id, best_p) or None.  The last kernel that edits the distribution takes the arg-max of what is left: a
         pair goes to the last call the chain makes, every other call gets NULL for both (greedy); None: NULL for all (the beam
@@ -575,18 +738,26 @@ class Searcher:
             chain.append(("fira_constrain_dist", lambda *b: lib.fira_constrain_dist(
                 s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, c.no_repeat_ngram, c.min_length,
                 _lib.ptr(st["banned"]), len(c.banned), dist, *b)))
+        if "penalties" in st:
+            chain.append(("fira_penalise_dist", lambda *b: lib.fira_penalise_dist(
+                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["count_factor"]),
+                _lib.ptr(st["bias_id"]), _lib.ptr(st["bias_factor"]), _lib.ptr(st["n_bias"]), dist, *b)))
         for k, (name, call) in enumerate(chain):
             last = best is not None and k == len(chain) - 1
             _lib.check(call(*((_lib.ptr(best[0]), _lib.ptr(best[1])) if last else (None, None))), name)
 
-    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False):
+    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None):
         """What the edit chain (``_edit``) owns in a state of R rows over B commits: ``con`` always (None: no constraint);
         ``merge`` only when merging; the [R, out_len] distribution when an edit is active (``dist=True``: in any case, for the
-        beam family, whose selection reads it); the banned ids with constraints; the two prefix buffers with a prefix ``rows``."""
+        beam family, whose selection reads it); the banned ids with constraints; the two prefix buffers with a prefix ``rows``;
+        with penalties ``pen`` the "penalties" marker, the count table [tar_len] and the bias lists [B, 16] / [B, 16] / [B]."""
         st = dict(con=con)
         if merge:
             st["merge"] = True
-        if dist or con is not None or merge or rows is not None:
+        if pen is not None:
+            st.update(penalties=True, count_factor=f32(self.cfg.tar_len), bias_id=i32(B, Penalties.MAX_BIASED),
+                      bias_factor=f32(B, Penalties.MAX_BIASED), n_bias=i32(B))
+        if dist or con is not None or merge or rows is not None or pen is not None:
             st["dist"] = f32(R, self.cfg.out_len)
         if con is not None:
             st["banned"] = torch.tensor(list(con.banned) or [0], dtype=torch.int32, device=self.model.device_)
@@ -637,14 +808,16 @@ class Searcher:
         st["prefix_len"].copy_(torch.tensor([len(row) for row in rows], dtype=torch.int32))
 
     @staticmethod
-    def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False, neighbour: bool = False):
+    def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False, neighbour: bool = False,
+             penalties: bool = False):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
         so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
         marker only: the prefix values live in device buffers), then "require" for a search with required words (a marker
-        too), then "neighbour" for a search with a neighbour (a marker: the batch and the coefficients live in device buffers);
+        too), then "neighbour" for a search with a neighbour (a marker: the batch and the coefficients live in device buffers),
+        then "penalties" for a search with active penalties (a marker: the table and the bias lists live in device buffers);
         an active BeamScoring value comes last."""
         return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + (("require",) if require else ())
-                + (("neighbour",) if neighbour else ())
+                + (("neighbour",) if neighbour else ()) + (("penalties",) if penalties else ())
                 + ((con,) if con is not None else ()) + ((scoring,) if scoring is not None else ()))
 
     def _required_rows(self, require, B: int, beam: int, con: Optional[Constraints], scoring):
@@ -776,27 +949,32 @@ class Searcher:
                        "fira_greedy_advance")
 
     def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
-                     merge_copies: bool = False, prefix=None, neighbour=None) -> _Loop:
+                     merge_copies: bool = False, prefix=None, neighbour=None, penalties=None) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  The
-        active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, constraints]), and so own their graphs)
+        active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, "penalties"][, constraints]), and so own their graphs)
         and add what ``_edit_state`` lists to the state -- the [B, out_len] distribution with any of them."""
         B = db.B
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
         nb = self._neighbour(neighbour, B)                   # likewise
+        pen = self._penalties(penalties, B)                  # likewise
         if nb is None:
-            make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **self._edit_state(i32, f32, B, B, con, merge, rows))
-            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None), make, chunk, use_graphs)
+            make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B),
+                                         **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen))
+            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, penalties=pen is not None),
+                         make, chunk, use_graphs)
         else:                                                # a neighbour: the state always owns the distribution
-            bare = con is None and not merge and rows is None
+            bare = con is None and not merge and rows is None and pen is None
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **({"mix_best": True} if bare else {}),
-                                         **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True))
-            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=True), make, chunk,
-                         use_graphs, nb)
+                                         **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True, pen=pen))
+            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=True,
+                                                penalties=pen is not None), make, chunk, use_graphs, nb)
         st, ws = loop.st, loop.ws
         if rows is not None:
             self._fill_prefix(st, rows)
+        if pen is not None:
+            self._fill_penalties(st, pen, B)
         return loop.start(lambda lo, hi: self._greedy_steps(st, ws, B, lo, hi), lambda: self._greedy_reset(st),
                           lambda hi: self._none_alive(st, hi))
 
@@ -811,10 +989,13 @@ class Searcher:
 
     @torch.no_grad()
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
-               merge_copies: bool = False, prefix=None, neighbour: Optional[Neighbour] = None):
-        """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``, ``merge_copies``
-        and ``prefix`` are the class's options: with any of them the step writes its distribution instead of taking its fused
-        arg-max, and the last kernel of the edit chain (``_edit``) takes the arg-max of what is left.
+               merge_copies: bool = False, prefix=None, neighbour: Optional[Neighbour] = None,
+               penalties: Optional[Penalties] = None):
+        """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``, ``merge_copies``,
+        ``prefix`` and ``penalties`` are the class's options: with any of them the step writes its distribution instead of taking
+        its fused arg-max, and the last kernel of the edit chain (``_edit``) takes the arg-max of what is left.  With active
+        ``penalties`` the third tensor is the product of the edited entries taken -- a score, not a probability (``score`` gives
+        the model's probability of a message).
 
         ``neighbour``: a ``Neighbour`` value.  Every step then also runs the model over the neighbour
         batch on the same tokens (a second workspace), folds that row into words with the neighbour's ids and mixes it into the
@@ -825,11 +1006,12 @@ class Searcher:
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
-        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix, neighbour).run())
+        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix, neighbour,
+                                                     penalties).run())
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
-                    merge_copies: bool = False, prefix=None, neighbour=None):
+                    merge_copies: bool = False, prefix=None, neighbour=None, penalties: Optional[Penalties] = None):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -844,9 +1026,13 @@ class Searcher:
         ``merge_copies`` the probability is that of the word sequence, summed over every entry path that spells it).
         ``prefix``: one prefix argument of ``greedy`` per batch (a sequence as long as ``dbs``; an entry may be None); the
         returned probability is then the joint probability of prefix and continuation.
-        ``neighbour``: one ``Neighbour`` (or None) per batch, a sequence as long as ``dbs``."""
+        ``neighbour``: one ``Neighbour`` (or None) per batch, a sequence as long as ``dbs``.
+        ``penalties``: one ``Penalties`` value for every batch (a per-commit bias list then needs batches of one size); the
+        returned value is then a score, as for ``greedy``."""
         dbs = list(dbs)
         con = self._active(constraints)                      # raises before a lane starts
+        for db in dbs:
+            self._penalties(penalties, db.B)                 # every batch's, before a lane starts
         if neighbour is not None:
             try:
                 neighbour = list(neighbour)
@@ -897,7 +1083,7 @@ class Searcher:
                     if active[k] is None and nxt < len(dbs):
                         loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies,
                                                  None if prefix is None else prefix[nxt],
-                                                 None if neighbour is None else neighbour[nxt])
+                                                 None if neighbour is None else neighbour[nxt], penalties)
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -961,7 +1147,7 @@ class Searcher:
     @torch.no_grad()
     def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                keys=None, chunk: int = 5, use_graphs: bool = True, neighbour=None, min_p: float = 0.0, epsilon: float = 0.0,
-               eta: float = 0.0, typical_p: float = 1.0):
+               eta: float = 0.0, typical_p: float = 1.0, penalties=None):
         """``n`` sampled messages per commit.  Returns (tokens [B,n,T] int64 starting with <start>, lengths [B,n],
         probability [B,n], log-probability [B,n]); the probabilities are the model's (untempered, unfiltered) ones of the
         emitted ids.
@@ -981,6 +1167,7 @@ class Searcher:
         capture serves every seed."""
         self._no_ensemble("sample")                           # raises before anything is launched
         self._no_neighbour("sample", neighbour)
+        self._no_penalties("sample", "its fused step hands no distribution over; sample_search does", penalties)
         cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)
         B, T = db.B, self.cfg.tar_len
         R = B * n
@@ -1017,11 +1204,13 @@ class Searcher:
     def sample_search(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                       min_p: float = 0.0, epsilon: float = 0.0, eta: float = 0.0, typical_p: float = 1.0, seed: int = 0, keys=None,
                       constraints: Optional[Constraints] = None, merge_copies: bool = False, prefix=None,
-                      neighbour: Optional[Neighbour] = None, chunk: int = 5, use_graphs: bool = True):
+                      neighbour: Optional[Neighbour] = None, chunk: int = 5, use_graphs: bool = True,
+                      penalties: Optional[Penalties] = None):
         """``n`` sampled messages per commit, drawn from the search's EDITED distribution: what ``sample`` returns (tokens
         [B,n,T], lengths [B,n], probability [B,n], log-probability [B,n]), with every option of the searches -- ``constraints``,
-        ``merge_copies``, ``prefix`` (the class's options), an ensemble (``members=``) and a ``neighbour`` -- and every filter and
-        cut of ``sample``.  Per step: the decoder step writes its distribution (every member's and ``fira_mix_dist``, or the
+        ``merge_copies``, ``prefix``, ``penalties`` (the class's options), an ensemble (``members=``) and a ``neighbour`` -- and
+        every filter and cut of ``sample``.  With active ``penalties`` the returned values are scores (products and log-sums of
+        the penalised entries), not probabilities.  Per step: the decoder step writes its distribution (every member's and ``fira_mix_dist``, or the
         neighbour's and ``fira_mix_neighbour``), the edit chain (``_edit``) edits it, ``fira_sample_dist`` applies the filters, the
         cuts and the Gumbel-max draw to the rows as they then stand, ``fira_sample_advance`` appends.  The rows are not
         renormalised; the filters work relative to each row's own sums, an entry with probability 0 is never drawn, and the
@@ -1056,16 +1245,19 @@ class Searcher:
         merge = bool(merge_copies)
         rows = self._prefix_rows(prefix, B, con)
         nb = self._neighbour(neighbour, B)
+        pen = self._penalties(penalties, B)
         noise_rows, fill_noise = self._noise(keys, seed, B)
         make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), **noise_rows(i32),
-                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True))
+                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True, pen=pen))
         key = self._key(("sample_search", B, n, temperature, top_k, top_p) + cuts, merge, con, forced=rows is not None,
-                        neighbour=nb is not None)
+                        neighbour=nb is not None, penalties=pen is not None)
         loop = _Loop(self, db, n, key, make, chunk, use_graphs, nb)
         st, ws = loop.st, loop.ws
         fill_noise(st)
         if rows is not None:
             self._fill_prefix(st, rows)
+        if pen is not None:
+            self._fill_penalties(st, pen, B)
         loop.start(lambda lo, hi: self._sample_search_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts),
                    lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
@@ -1199,7 +1391,7 @@ class Searcher:
 
     @torch.no_grad()
     def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None,
-              neighbour=None):
+              neighbour=None, penalties=None):
         """Teacher-forced probability of given messages.  ``cand`` [B, n, T] (or [B, T]) vocabulary ids, each message starting
         with <start> and ending with <eos> unless truncated, zero-padded; 1 <= n <= 8 candidates per commit share the
         commit's encoder pass and memory (``fira_decode_begin`` with n rows per commit).  ``labels`` (same shape, optional):
@@ -1216,6 +1408,7 @@ class Searcher:
         ``dist`` (tests): a [tar_len - 1, B * n, out_len] tensor that receives every step's distribution (eager only)."""
         self._no_ensemble("score")                            # raises before anything is launched
         self._no_neighbour("score", neighbour)
+        self._no_penalties("score", "its fused step hands no distribution over, and it reports the model's probability", penalties)
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
         cand, length, labels = self.check_candidates(cand, lengths, labels, B)        # raises before anything is launched
@@ -1322,10 +1515,13 @@ class Searcher:
     @torch.no_grad()
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
-             scoring: Optional[BeamScoring] = None, prefix=None, require=None, neighbour: Optional[Neighbour] = None):
-        """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``
-        and ``prefix`` are the class's options, one library call per step each, between the step and the selection (``_edit``);
-        the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, "require"][, constraints][, scoring]) (``_key``).
+             scoring: Optional[BeamScoring] = None, prefix=None, require=None, neighbour: Optional[Neighbour] = None,
+             penalties: Optional[Penalties] = None):
+        """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``,
+        ``prefix`` and ``penalties`` are the class's options, one library call per step each, between the step and the selection
+        (``_edit``); the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, "require"][, "neighbour"][, "penalties"]
+        [, constraints][, scoring]) (``_key``).  ``penalties`` combines with everything below (the selections read the edited row);
+        the third tensor is then the product of the edited entries taken -- a score, not a probability.
 
         ``scoring``: a ``BeamScoring`` value.  ``fira_beam_select_scored`` then takes the place of ``fira_beam_select`` (after
         the edit chain): hypotheses are ranked by the length-normalised key ln(prob) / ((5 + m) / 6)^alpha instead of
@@ -1368,10 +1564,11 @@ class Searcher:
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
         words = self._required_rows(require, B, beam, con, scoring)   # likewise
         nb = self._neighbour(neighbour, B)                   # likewise
+        pen = self._penalties(penalties, B)                  # likewise
 
         def make(i32, f32):
             st = dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
-                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True))
+                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True, pen=pen))
             if words is not None:
                 st.update(required=i32(B, MAX_REQUIRED), n_required=i32(B), met=i32(BR))
             if scoring is not None:
@@ -1381,13 +1578,16 @@ class Searcher:
         # (a captured graph bakes the constraint scalars, the merge launch and the scoring scalars: they are part of the key)
         loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring, rows is not None,
                                                **({} if words is None else {"require": True}),
-                                               **({} if nb is None else {"neighbour": True})), make, chunk, use_graphs,
+                                               **({} if nb is None else {"neighbour": True}),
+                                               **({} if pen is None else {"penalties": True})), make, chunk, use_graphs,
                      *(() if nb is None else (nb,)))
         st, ws = loop.st, loop.ws
         if rows is not None:
             self._fill_prefix(st, rows)
         if words is not None:
             self._fill_required(st, words)
+        if pen is not None:
+            self._fill_penalties(st, pen, B)
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
         res = self._family_result(loop, B, beam, ("prob",))
@@ -1415,7 +1615,7 @@ class Searcher:
     @torch.no_grad()
     def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
                         merge_copies: bool = True, constraints: Optional[Constraints] = None, chunk: int = 4,
-                        use_graphs: bool = True, neighbour=None):
+                        use_graphs: bool = True, neighbour=None, penalties=None):
         """``n`` messages per commit sampled WITHOUT replacement: stochastic beam search (Kool, van Hoof and Welling 2019;
         ``fira_beam_select_gumbel``).  A beam search whose ranking key is the Gumbel-perturbed
         log-probability of the hypothesis, a child's key conditioned on its parent's; the n hypotheses it ends with are an exact
@@ -1437,6 +1637,7 @@ class Searcher:
         is baked into the captured launches; the seed and the keys are device values: one capture serves them all."""
         B = db.B
         self._no_neighbour("sample_distinct", neighbour)     # raises before anything is launched
+        self._no_penalties("sample_distinct", "its hypotheses are an exact sample from the model's distribution", penalties)
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
         noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched
@@ -1521,6 +1722,7 @@ class Searcher:
         running = (st["ended"] == 0) & (last > 0)
         return gen.long(), length.long(), torch.where(running, st["prob"][cur] * last, st["prob"][cur])
 
+    @_refuses_penalties("it already penalises degeneration")
     @torch.no_grad()
     def contrastive(self, db: DeviceBatch, k: int, alpha: float = 0.6, chunk: int = 4, use_graphs: bool = True,
                     constraints: Optional[Constraints] = None, prefix=None):

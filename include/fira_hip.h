@@ -1074,6 +1074,41 @@ int fira_force_dist(void* stream, const fira_dims* d, int R, int rows_per_commit
                     float* dist /* [R, vocab + sou_len + sub_len], in place */,
                     int32_t* best_id, float* best_p /* both NULL or both [R] */);
 
+/* Soft word penalties and biases (csrc/penalise.hip; additive, the ABI version is unchanged): multiplies the entries of words the
+ * hypothesis already holds, and of a commit's biased words, by given factors, in place, LAST in the edit chain -- after
+ * fira_merge_dist, fira_force_dist and fira_constrain_dist, if any, and before the selection.  The soft sibling of
+ * fira_constrain_dist, with its definitions: W = vocab + sou_len + sub_len, entry i resolves to the word w(i), row r belongs to
+ * commit b = r / rows_per_commit, len = length[r] clamped to 1 .. tar_len, m = len - 1 words emitted, and a row with
+ * gen[r, len - 1] == <eos> (1) is finished: it is not touched.  For every other row, with c(w) = the number of positions p in
+ * 1 .. m with gen[r, p] == w:
+ *   count   every entry i with c(w(i)) > 0:  dist[r, i] <- fl32(dist[r, i] * count_factor[c(w(i))])   (c <= tar_len - 1, so the
+ *           index is inside the table; count_factor[0] is never read)
+ *   bias    then every entry i whose word equals bias_id[b, q] for some q < min(max(n_bias[b], 0), 16):
+ *           dist[r, i] <- fl32(dist[r, i] * bias_factor[b, q]), for the first such q, once
+ * The two fp32 multiplications round separately, in that order.  A word is reached through its generator entry and through every
+ * diff and sub-token slot of the commit that carries it (fira_decode_step_score's p_word notion); <eos> is no exception.  Every
+ * other element keeps its bits; nothing is renormalised.
+ * The entry cannot see the contents of the device buffers.  The HOST guarantees: every factor finite and >= 0 (a 0 bans the word
+ * as fira_constrain_dist would), the ids of a commit pairwise distinct and inside [0, vocab), n_bias in 0 .. 16.  Otherwise the
+ * kernel clamps n_bias to 0 .. 16, ignores a bias id outside [0, vocab), and uses the first of two equal ids; factors are
+ * multiplied in as they are.
+ * best_id / best_p (both NULL, or both [R]): the arg-max of the row as it then stands and its value, under (value descending,
+ * index ascending) -- the order of fira_constrain_dist; NaN never wins.  A finished row reports the arg-max of its untouched row.
+ * Without best_id the row is read at its copy slots and at the touched generator entries only.
+ * count_factor, bias_id, bias_factor and n_bias are DEVICE arrays read when the kernel runs, so one captured launch serves every
+ * penalty value and every bias list.  tar_len in 2 .. 64, vocab in 4 .. 25 600, sou_len + sub_len <= 1 024, rows_per_commit >= 1
+ * divides R; R == 0 is a no-op.  Any row width and any 4-byte alignment of dist; vector stores only, no atomics on global memory,
+ * no two threads write one address.                                                                                          */
+int fira_penalise_dist(void* stream, const fira_dims* d, int R, int rows_per_commit, const int32_t* gen /* [R, tar_len] */,
+                       const int32_t* length /* [R] */, const int32_t* sou /* [R / rows_per_commit, sou_len] */,
+                       const int32_t* sub_token /* [R / rows_per_commit, sub_len] */,
+                       const float* count_factor /* device, [tar_len] */,
+                       const int32_t* bias_id /* device, [R / rows_per_commit, 16] */,
+                       const float* bias_factor /* device, [R / rows_per_commit, 16] */,
+                       const int32_t* n_bias /* device, [R / rows_per_commit] */,
+                       float* dist /* [R, vocab + sou_len + sub_len], in place */,
+                       int32_t* best_id, float* best_p /* both NULL or both [R] */);
+
 /* Ensemble decoding (csrc/mix.hip; additive, the ABI version is unchanged): mixes the step distributions of n_members models into
  * one, between the members' fira_decode_step calls and whatever takes a distribution next (fira_merge_dist, fira_constrain_dist,
  * fira_beam_select / fira_beam_select_scored / fira_greedy_advance).  For every element i of the [R, W] rows, in member order,
