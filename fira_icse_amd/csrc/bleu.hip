@@ -23,14 +23,13 @@
 //      (a shifted mask has no bit j with j + n - 1 past the length, which is exactly "position j starts an n-gram").  The masks
 //      of the neighbouring lanes come through LDS.  Lane i contributes min(popc(Mh_n), popc(Mr_n)) if it starts an n-gram and
 //      no lower position holds the same one (Mh_n has no bit below i); the wave sum is the integer form of common.h's DPP tree.
-#include "common.h"
+//
+// What the hypothesis, the reference and a candidate's message ARE (steps 1 below) is message.h's, shared with rouge.hip.
+#include "message.h"
 
 namespace fira {
 
 constexpr int BLEU_CPW = 4;            // commits (= waves) per workgroup
-constexpr int BLEU_T = 64;             // positions a wave covers
-constexpr int BLEU_PAD = 0, BLEU_EOS = 1, BLEU_UNK = 3;      // config.PAD / EOS / UNK
-constexpr int BLEU_UNK_CMP = -2;       // what a hypothesis <unkm> is compared as: no vocabulary id, not the -1 fill of hyp
 
 __device__ __forceinline__ int wave_sum_i32(int v) {
     v += __builtin_amdgcn_update_dpp(v, v, DPP_XOR1, 0xf, 0xf, false);
@@ -41,9 +40,6 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, DPP_BCAST31, 0xc, 0xf, false);      // rows 2, 3 += lane 31
     return __builtin_amdgcn_readlane(v, 63);
 }
-
-__device__ __forceinline__ uint64_t low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }      // n in [0, 64]
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 __global__ __launch_bounds__(BLEU_CPW * 64) void dev_bleu_stats_kernel(int B, int T, int V, int L, int S,
                                                                        const int32_t* __restrict__ ids,
@@ -61,30 +57,12 @@ __global__ __launch_bounds__(BLEU_CPW * 64) void dev_bleu_stats_kernel(int B, in
     const bool live = b_raw < B;                           // wave-uniform; a wave past B recomputes commit B - 1, stores nothing
     const size_t b = (size_t)(live ? b_raw : B - 1);
     const bool in_t = lane < T;
-    const int tc = in_t ? lane : T - 1;
 
-    // ---- 1. requests (all unconditional, indices clamped), then the selects
-    const int raw = ids[b * T + tc];
-    const int tv = tar[b * T + tc];
-    const int rc = clampi(raw, 0, V + L + S - 1);
-    int from_sou = sou[b * L + clampi(rc - V, 0, L - 1)];
-    int from_sub = sub[b * S + clampi(rc - V - L, 0, S - 1)];
-    // (the compiler otherwise sinks each of the two loads under the test of its select: a divergent branch with a full vmcnt
-    //  wait inside; both requests are in flight together this way)
-    asm volatile("" : "+v"(from_sou), "+v"(from_sub));
-    const int tok = raw >= V + L ? from_sub : (raw >= V ? from_sou : raw);
-
+    // ---- 1. requests (all unconditional, indices clamped), then the selects: message.h
+    const DevMessage m = dev_message(b, lane, T, V, L, S, ids, sou, sub, tar);
+    const int tok = m.tok, tv = m.tv, hyp_len = m.hyp_len, pos = m.pos, e_ref = m.e_ref, ref_len = m.ref_len;
+    const bool keep = m.keep;
     const uint64_t below = low_bits(lane);
-    const uint64_t eos_h = __ballot(in_t && raw == BLEU_EOS);
-    const int n_raw = eos_h ? __builtin_ctzll(eos_h) : T;              // raw positions ahead of the first raw <eos>
-    const bool keep = lane < n_raw && tok != BLEU_PAD;
-    const uint64_t keep_m = __ballot(keep);
-    const int hyp_len = __builtin_popcountll(keep_m);
-    const int pos = __builtin_popcountll(keep_m & below);
-
-    const uint64_t eos_r = __ballot(in_t && tv == BLEU_EOS);
-    const int e_ref = eos_r ? __builtin_ctzll(eos_r) : T;
-    const int ref_len = e_ref > 0 ? e_ref - 1 : 0;
 
     // ---- 2. compacted hypothesis and reference into LDS
     if (keep) {
@@ -152,8 +130,6 @@ __global__ __launch_bounds__(BLEU_CPW * 64) void dev_bleu_stats_kernel(int B, in
 //      only Er (64 LDS reads at a wave-uniform address) and Mr_n, four wave sums, and one 12-lane store.
 // A reference is read from LDS, not from HBM n times.  Lengths, not sentinels, bound every mask, so any int32 is a word.
 constexpr int MBR_WAVES = 4;
-constexpr int MBR_N = 32;              // candidates per commit the LDS stage holds
-constexpr int BLEU_START = 2;          // config.START
 
 __device__ __forceinline__ uint64_t shfl_up_mask(uint64_t m, int lane, int k) {      // m of lane + k, >> k; 0 past the wave
     const int lo = __shfl((int)(uint32_t)m, lane + k), hi = __shfl((int)(uint32_t)(m >> 32), lane + k);
@@ -178,17 +154,13 @@ __global__ __launch_bounds__(MBR_WAVES * 64) void mbr_bleu_stats_kernel(int n, i
     __shared__ int32_t s_len[MBR_N];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const size_t row0 = (size_t)blockIdx.x * n;                                // first candidate row of this commit
-    const int tc = lane < T ? lane : T - 1;
     const uint64_t below = low_bits(lane);
 
-    // ---- 1. compact the commit's candidates into LDS
+    // ---- 1. compact the commit's candidates into LDS (message.h)
     for (int c = w; c < n; c += MBR_WAVES) {                                   // (wave-uniform trip count)
-        const int tok = tokens[(row0 + c) * T + tc];
-        const int len = clampi(length[row0 + c], 0, T);
-        const bool keep = lane >= 1 && lane < len && tok != BLEU_PAD && tok != BLEU_EOS && tok != BLEU_START;
-        const uint64_t keep_m = __ballot(keep);
-        if (keep) s_tok[c][__builtin_popcountll(keep_m & below)] = tok;
-        if (lane == 0) s_len[c] = __builtin_popcountll(keep_m);
+        const CandMessage m = cand_message(row0 + c, lane, T, tokens, length);
+        if (m.keep) s_tok[c][m.pos] = m.tok;
+        if (lane == 0) s_len[c] = m.len;
     }
     __syncthreads();
 

@@ -1270,7 +1270,7 @@ class Searcher:
     # ------------------------------------------------------------------ minimum-Bayes-risk pick by expected sentence BLEU
     MBR_MAX_N, MBR_MAX_T = 32, 64
 
-    def mbr(self, tokens, lengths, logp=None):
+    def mbr(self, tokens, lengths, logp=None, utility="bleu"):
         """Minimum-Bayes-risk selection among candidate messages: the candidates of a commit are taken as draws from the model
         and the one with the highest mean sentence BLEU (method 2) against the others wins.  ``tokens`` [B, n, T] vocabulary
         ids and ``lengths`` [B, n] as ``sample`` returns them (or several ``sample`` calls concatenated along n), 1 <= n <= 32,
@@ -1280,8 +1280,14 @@ class Searcher:
         Returns (pick: the winner's index per commit, utilities [B, n] float64 CPU tensor).  One launch
         (``fira_mbr_bleu_stats``: all n x n pairs, exact integers), one copy back, the scores formed on the host by
         ``metrics.mbr_utilities`` / ``mbr_pick`` -- ``==`` the string scorer on the same words.  Raises ValueError before
-        anything is launched on a wrong shape, an id outside int32 or n / T outside the limits."""
+        anything is launched on a wrong shape, an id outside int32 or n / T outside the limits.
+
+        ``utility="rouge_l"`` takes sentence-level ROUGE-L (``metrics.rouge_l``: in-order overlap at any distance) in place of
+        BLEU: the same messages, the same checks, ``fira_mbr_rouge_l_stats`` as the one launch (4 integers per pair), the
+        utilities ``==`` the mean of ``metrics.rouge_l`` on the words.  Any other ``utility`` is a ValueError."""
         from . import metrics, ops
+        if utility not in metrics.MBR_UTILITIES:
+            raise ValueError("utility: %r is not one of %s" % (utility, ", ".join(metrics.MBR_UTILITIES)))
         if not (torch.is_tensor(tokens) and torch.is_tensor(lengths)):
             tokens, lengths = torch.as_tensor(tokens), torch.as_tensor(lengths)
         if tokens.dim() != 3:
@@ -1309,8 +1315,9 @@ class Searcher:
             if int(lo) < -(1 << 31) or int(hi) >= 1 << 31:
                 raise ValueError("tokens: id outside the int32 range")
         lengths = lengths.clamp(min=0, max=T)                 # (the message ends at min(length, T) anyway)
-        stats = ops.mbr_bleu_stats(tokens.to(torch.int32).contiguous(), lengths.to(torch.int32).contiguous())
-        util = metrics.mbr_utilities(stats.cpu())
+        launch = ops.mbr_bleu_stats if utility == "bleu" else ops.mbr_rouge_l_stats
+        stats = launch(tokens.to(torch.int32).contiguous(), lengths.to(torch.int32).contiguous())
+        util = metrics.mbr_utilities(stats.cpu(), utility)
         pick = metrics.mbr_pick(util, None if logp is None else logp.detach().cpu())
         return pick, torch.tensor(util, dtype=torch.float64).reshape(B, n)
 

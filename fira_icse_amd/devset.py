@@ -18,6 +18,7 @@ from .config import EOS, PAD, UNK, FiraConfig
 from .parallel import shard_indices
 
 _STAT_COLS = 12
+_ROUGE_COLS = 4
 
 
 def check_vocabulary(r_vocab: Dict[int, str], vocab_size: int) -> None:
@@ -59,11 +60,16 @@ class DevEvaluator:
     per arena), i.e. about 148 MB for the reference's 8 000 valid commits on one rank -- 0.05 % of 288 GB -- plus
     4 * (12 + tar_len) = 168 bytes per commit (1.3 MB) for the two pass-wide result buffers.  ``resident_bytes`` has the
     actual figure of a built set.
+
+    ``rouge_l=True``: both passes also score every commit by sentence-level ROUGE-L (``metrics.rouge_l`` on the same words;
+    on the device ``fira_dev_rouge_l_stats`` on the same ids, 16 more bytes per commit in the pass-wide buffer and the same one
+    copy back) and leave the values in ``last_rouge_l``, per commit in shard order.  A second reported figure only: model
+    selection, the ``dev_output`` lines and the return values are the BLEU ones either way.
     """
 
     def __init__(self, model, store, cfg: FiraConfig, r_vocab: Dict[int, str], var_maps: Sequence[Dict[str, str]],
                  valid_index: Sequence[int], rank: int = 0, world: int = 1,
-                 ids_fn: Optional[Callable] = None, device=None):
+                 ids_fn: Optional[Callable] = None, device=None, rouge_l: bool = False):
         self.model, self.store, self.cfg = model, store, cfg
         self.r_vocab, self.var_maps, self.valid_index = r_vocab, var_maps, valid_index
         self.rank, self.world = rank, world
@@ -76,8 +82,10 @@ class DevEvaluator:
         self.mine: List[int] = shard_indices(list(range(len(store))), rank, world)
         self.bs = max(1, cfg.batch_size // world)
         self.last_scores: List[float] = []       # per-commit scores of the latest pass, in shard order
+        self.rouge_l = bool(rouge_l)
+        self.last_rouge_l: List[float] = []      # per-commit ROUGE-L of the latest pass (rouge_l=True), in shard order
         self._batches = None                     # resident DeviceBatches (device_pass)
-        self._out = None                         # [n_mine, 12 + T] int32: stats | hyp of one pass
+        self._out = None                         # [n_mine, 12 + T (+ 4)] int32: stats | hyp (| ROUGE-L stats) of one pass
 
     def _batch(self, idx):
         from .model import DeviceBatch
@@ -93,7 +101,7 @@ class DevEvaluator:
     @torch.no_grad()
     def host_pass(self):
         cfg, store = self.cfg, self.store
-        lines, total, scores = [], 0.0, []
+        lines, total, scores, rouge = [], 0.0, [], []
         for lo in range(0, len(self.mine), self.bs):
             idx = self.mine[lo:lo + self.bs]
             ids = self.ids_fn(self._batch(idx)).cpu().tolist()
@@ -106,8 +114,11 @@ class DevEvaluator:
                 b = metrics.sentence_bleu_method2([ref], hyp)
                 total += b
                 scores.append(b)
+                if self.rouge_l:
+                    rouge.append(metrics.rouge_l(ref, hyp))
                 lines.append(self._line(i, hyp, b))
         self.last_scores = scores
+        self.last_rouge_l = rouge
         return total, lambda: lines
 
     # ------------------------------------------------------------------------------ the device pass
@@ -118,7 +129,8 @@ class DevEvaluator:
         if no_eos.size:                          # (the host pass raises ValueError from list.index on such a commit)
             raise ValueError("device dev pass: valid commit %d has no <eos> in its target" % self.mine[int(no_eos[0])])
         self._batches = [self._batch(self.mine[lo:lo + self.bs]) for lo in range(0, len(self.mine), self.bs)]
-        self._out = torch.empty((len(self.mine) * (_STAT_COLS + self.cfg.tar_len),), dtype=torch.int32, device=self.device)
+        cols = _STAT_COLS + self.cfg.tar_len + (_ROUGE_COLS if self.rouge_l else 0)
+        self._out = torch.empty((len(self.mine) * cols,), dtype=torch.int32, device=self.device)
 
     @property
     def resident_bytes(self) -> int:
@@ -134,13 +146,16 @@ class DevEvaluator:
         if self._batches is None:
             self._build_resident()
         stats = self._out[:n * _STAT_COLS].view(n, _STAT_COLS)
-        hyp = self._out[n * _STAT_COLS:].view(n, T)
+        hyp = self._out[n * _STAT_COLS:n * (_STAT_COLS + T)].view(n, T)
+        rouge = self._out[n * (_STAT_COLS + T):].view(n, _ROUGE_COLS) if self.rouge_l else None
         off = 0
         for db in self._batches:
             ids = self.ids_fn(db)
             db.wait_ready()
             ops.dev_bleu_stats(ids, db.sou, db.sub_token, db.tar, cfg.vocab_size, hyp=hyp[off:off + db.B],
                                stats=stats[off:off + db.B])
+            if self.rouge_l:
+                ops.dev_rouge_l_stats(ids, db.sou, db.sub_token, db.tar, cfg.vocab_size, stats=rouge[off:off + db.B])
             off += db.B
         host = self._out.cpu()                   # the pass's one copy back and its one synchronisation
         st = host[:n * _STAT_COLS].view(n, _STAT_COLS).tolist()
@@ -150,7 +165,9 @@ class DevEvaluator:
             total += b
             scores.append(b)
         self.last_scores = scores
-        hyp_host = host[n * _STAT_COLS:].view(n, T)
+        self.last_rouge_l = ([metrics.rouge_l_from_stats(r[0], r[1], r[2])
+                              for r in host[n * (_STAT_COLS + T):].view(n, _ROUGE_COLS).tolist()] if self.rouge_l else [])
+        hyp_host = host[n * _STAT_COLS:n * (_STAT_COLS + T)].view(n, T)
 
         def lines():
             out = []

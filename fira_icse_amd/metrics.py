@@ -7,6 +7,10 @@
   17.666 / 0.13299 (checked in tests/test_metrics.py when the reference tree is present).
 * ``sentence_bleu_method2``: what ``dev()`` uses for checkpoint selection (reference run_model.py:22,171):
   NLTK ``sentence_bleu`` with ``SmoothingFunction().method2``.
+* ``rouge_l`` / ``rouge_l_corpus``: sentence-level ROUGE-L as Lin (2004) defines it -- the F-measure (beta = 1) of the longest
+  common subsequence of two word lists.  The reference computes its ROUGE column by calling the ``sumeval`` command-line tool
+  (Metrics/Rouge.py); that tool is not available here, so identity with ``sumeval r-nl`` has NOT been checked (its tokenisation
+  and stop-word handling may differ) and no claim against the paper's 21.58 is made.
 """
 from __future__ import annotations
 
@@ -134,19 +138,68 @@ def bleu_method2_from_stats(num: Sequence[int], cnt: Sequence[int], hyp_len: int
     return bp * math.exp(math.fsum(0.25 * x for x in logs))
 
 
-def mbr_utilities(stats) -> List[List[float]]:
-    """Expected-BLEU utilities from the all-pairs statistics of ``fira_mbr_bleu_stats``: ``stats`` is [B][n][n][12] integers
+def lcs_length(a: Sequence, b: Sequence) -> int:
+    """Length of the longest common subsequence of two sequences: the plain O(mn) DP, one row kept."""
+    row = [0] * (len(b) + 1)
+    for x in a:
+        diag = 0
+        for j, y in enumerate(b):
+            diag, row[j + 1] = row[j + 1], (diag + 1 if x == y else max(row[j + 1], row[j]))
+    return row[len(b)]
+
+
+def rouge_l_from_stats(lcs: int, hyp_len: int, ref_len: int) -> float:
+    """Sentence-level ROUGE-L (Lin 2004, F-measure with beta = 1) from its three integers: ``2PR / (P + R)`` with
+    ``P = lcs / hyp_len`` and ``R = lcs / ref_len``, reduced to ``2 lcs / (hyp_len + ref_len)`` so that the value has one
+    rounding.  0.0 when ``lcs == 0`` (which covers either side empty).  These are the numbers ``fira_dev_rouge_l_stats`` /
+    ``fira_mbr_rouge_l_stats`` write.  The standard definition; identity with the reference's ``sumeval r-nl`` has NOT been
+    checked (the tool is absent)."""
+    if lcs == 0:
+        return 0.0
+    return 2.0 * lcs / (hyp_len + ref_len)
+
+
+def rouge_l(reference: Sequence[str], hypothesis: Sequence[str]) -> float:
+    """``rouge_l_from_stats`` of two word lists."""
+    return rouge_l_from_stats(lcs_length(hypothesis, reference), len(hypothesis), len(reference))
+
+
+def rouge_l_corpus(references: Iterable[str], predictions: Iterable[str]) -> float:
+    """100 x the mean sentence-level ROUGE-L of the lines, both sides tokenised by ``str.split()``.  Raises ValueError when the
+    two sides differ in length (or are empty).  Not checked against ``sumeval`` -- see the module docstring."""
+    refs, preds = list(references), list(predictions)
+    if len(refs) != len(preds):
+        raise ValueError("rouge_l_corpus: %d references and %d predictions" % (len(refs), len(preds)))
+    if not refs:
+        raise ValueError("rouge_l_corpus: no lines")
+    return 100.0 * math.fsum(rouge_l(r.split(), p.split()) for r, p in zip(refs, preds)) / len(refs)
+
+
+MBR_UTILITIES = ("bleu", "rouge_l")
+
+
+def mbr_utilities(stats, utility: str = "bleu") -> List[List[float]]:
+    """Expected-utility values from the all-pairs statistics of one commit's candidates: ``stats`` is [B][n][n][k] integers
     (nested lists, a numpy array or a CPU tensor), row [b][i][j] the statistics of candidate i scored against candidate j.
-    ``u[b][i]`` is the mean over j != i of ``bleu_method2_from_stats`` of pair (i, j) -- Python ints in, ``math.fsum`` for the
-    mean -- so it is ``==`` the same mean of ``sentence_bleu_method2`` on the candidates' word lists.  0.0 for n == 1."""
+
+    ``"bleu"``: the twelve integers of ``fira_mbr_bleu_stats``; ``u[b][i]`` is the mean over j != i of
+    ``bleu_method2_from_stats`` of pair (i, j) -- Python ints in, ``math.fsum`` for the mean -- so it is ``==`` the same mean of
+    ``sentence_bleu_method2`` on the candidates' word lists.  ``"rouge_l"``: the four integers (lcs, hyp_len, ref_len, 0) of
+    ``fira_mbr_rouge_l_stats`` and ``rouge_l_from_stats`` in the same mean, ``==`` that of ``rouge_l``.  0.0 for n == 1."""
+    if utility not in MBR_UTILITIES:
+        raise ValueError("mbr_utilities: utility %r is not one of %s" % (utility, ", ".join(MBR_UTILITIES)))
     if hasattr(stats, "tolist"):
         stats = stats.tolist()
+    if utility == "bleu":
+        score = lambda st: bleu_method2_from_stats(st[0:4], st[4:8], st[8], st[9])
+    else:
+        score = lambda st: rouge_l_from_stats(st[0], st[1], st[2])
     out = []
     for commit in stats:
         n = len(commit)
         row = []
         for i in range(n):
-            scores = [bleu_method2_from_stats(st[0:4], st[4:8], st[8], st[9]) for j, st in enumerate(commit[i]) if j != i]
+            scores = [score(st) for j, st in enumerate(commit[i]) if j != i]
             row.append(math.fsum(scores) / (n - 1) if n > 1 else 0.0)
         out.append(row)
     return out

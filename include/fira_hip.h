@@ -801,6 +801,21 @@ int fira_mbr_bleu_stats(void* stream, int B, int n, int T,
                         const int32_t* tokens, /* [B,n,T] vocabulary ids */  const int32_t* length, /* [B,n] */
                         int32_t* stats);       /* [B,n,n,12]: num[4], cnt[4], hyp_len, ref_len, 0, 0 */
 
+/* ROUGE-L statistics on token ids (csrc/rouge.hip; additive, the ABI version is unchanged): lcs = the length of the longest
+ * common subsequence of hypothesis and reference, and the two lengths; sentence-level ROUGE-L (F-measure, beta = 1) is
+ * 2 lcs / (hyp_len + ref_len), 0 for lcs == 0.  The candidates' messages are exactly fira_mbr_bleu_stats's, the hypothesis and
+ * reference of a commit exactly fira_dev_bleu_stats's (a hypothesis <unkm> matches nothing; copy indices clamped), and so are
+ * the limits: 1 <= n <= 32, 1 <= T <= 64, V >= 4, L, S >= 1; B == 0 is a no-op.  int32 and exact.  lcs[b][i][j] == lcs[b][j][i],
+ * and on the diagonal lcs == hyp_len == ref_len.                                                                               */
+int fira_mbr_rouge_l_stats(void* stream, int B, int n, int T,
+                           const int32_t* tokens, /* [B,n,T] vocabulary ids */  const int32_t* length, /* [B,n] */
+                           int32_t* stats);       /* [B,n,n,4]: lcs, hyp_len, ref_len, 0 (candidate i hypothesis, j reference) */
+int fira_dev_rouge_l_stats(void* stream, int B, int T, int V, int L, int S,
+                           const int32_t* ids,  /* [B,T] output indices of fira_forward_dev, in [0, V+L+S) */
+                           const int32_t* sou,  /* [B,L] */  const int32_t* sub_token, /* [B,S] */
+                           const int32_t* tar,  /* [B,T] */
+                           int32_t* stats);     /* [B,4]: lcs, hyp_len, ref_len, 0 */
+
 /* Encoder once per batch (run_model.py:202-207) + everything of the decode loop that does not depend
  * on the generated prefix: memory [B,S,256], mem_valid [B,S], cross-attention K/V of all layers,
  * LinearSource(memory).  State lives in the caller's workspace.                                     */
