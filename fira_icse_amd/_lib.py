@@ -187,6 +187,7 @@ SIGNATURES = {
     "fira_merge_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P]),
     "fira_force_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_penalise_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fira_ban_phrases_dist": (_I, [_P, _DP, _I, _I] + [_P] * 10),
     "fira_mix_dist": (_I, [_P, _I, _I, _I, C.POINTER(_P), C.POINTER(_F), _P, _P, _P]),
     "fira_pool_memory": (_I, [_P, _DP, _I, _P, _P, _P]),
     "fira_nn_search_scratch_bytes": (_Z, [_I, _I]),
@@ -200,6 +201,7 @@ SIGNATURES = {
     "fira_beam_select_scored": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P]),
     "fira_beam_select_gumbel": (_I, [_P, _DP, _I, _I, _I, _F] + [_P] * 18),
     "fira_beam_select_required": (_I, [_P, _DP, _I, _I] + [_P] * 16),
+    "fira_beam_select_phrases": (_I, [_P, _DP, _I, _I] + [_P] * 17),
     "fira_contrastive_select": (_I, [_P, _DP, _I, _I, _I, _F] + [_P] * 19),
     "fira_greedy_advance": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_decode_step": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -287,6 +287,168 @@ class Penalties:
         return ids, fac, n
 
 
+@dataclasses.dataclass(frozen=True)
+class Phrases:
+    """Word SEQUENCES in the hard search controls: what a message must not contain and what it must
+    contain, where ``Constraints.banned`` and ``beam(require=)`` speak of single words.
+
+    ``banned``: phrases of 2..4 vocabulary ids in [UNK, vocab) -- one list of phrases used for every commit, or a sequence of one
+    list per commit; at most 8 per commit.  ``fira_ban_phrases_dist`` blocks the word that would complete a listed phrase: its
+    generator id and every copy slot of the commit that carries it, as ``no_repeat_ngram`` blocks the word that would complete
+    an n-gram the hypothesis already holds.  Taken by ``greedy``, ``greedy_many``, ``beam`` and ``sample_search``.
+    ``required``: one list of ITEMS per commit, an item being 1..4 ids in (UNK, vocab) that the message must hold contiguously;
+    at most 4 items per commit whose lengths sum to at most 4 (the selection keeps five banks); an empty list means no
+    requirement for that commit.  ``fira_beam_select_phrases`` divides the beam into banks by ``progress`` (the words of the
+    completed items plus the longest phrase start the hypothesis ends in).  Taken by ``beam`` only.
+
+    Values are checked here (``ValueError`` with the reason); what depends on the model, the batch and the other options is
+    checked when a ``Searcher`` takes the value.  Stored as tuples, so equal values compare and hash equal."""
+    banned: object = ()
+    required: object = ()
+
+    MAX_BANNED, MAX_WORDS, MAX_ITEMS, MAX_REQUIRED_WORDS = 8, 4, 4, 4
+
+    @staticmethod
+    def _ids(seq, what, lowest):
+        out = []
+        for w in seq:
+            if isinstance(w, bool) or not isinstance(w, numbers.Integral):
+                raise ValueError("Phrases: %s: id %r is not an integer" % (what, w))
+            if w < lowest:
+                raise ValueError("Phrases: %s: id %d is below %d" % (what, w, lowest))
+            out.append(int(w))
+        return tuple(out)
+
+    @staticmethod
+    def _seq(x):
+        return not isinstance(x, (str, bytes)) and hasattr(x, "__iter__")
+
+    def __post_init__(self):
+        seq = self._seq
+        banned = self.banned
+        if banned is None:
+            banned = ()
+        if not seq(banned):
+            raise ValueError("Phrases: banned = %r is not a sequence of phrases" % (banned,))
+        banned = [list(p) if seq(p) else p for p in banned]
+        if any(not seq(p) for p in banned):
+            raise ValueError("Phrases: banned = %r is neither a list of phrases nor one list of phrases per commit" % (self.banned,))
+        # one list for every commit: every element is a non-empty sequence of ids; else one list (possibly empty) per commit
+        shared = all(len(p) > 0 and not any(seq(w) for w in p) for p in banned)
+        rows = [banned] if shared else banned
+        out = []
+        for k, row in enumerate(rows):
+            where = "banned" if shared else "banned phrases of commit %d" % k
+            phrases = []
+            for ph in row:
+                if not seq(ph):
+                    raise ValueError("Phrases: %s: %r is not a phrase (a sequence of ids)" % (where, ph))
+                ph = self._ids(ph, where, UNK)
+                if len(ph) == 1:
+                    raise ValueError("Phrases: %s: (%d,) is one word; a single word is banned with Constraints.banned" % (where, ph[0]))
+                if not 2 <= len(ph) <= self.MAX_WORDS:
+                    raise ValueError("Phrases: %s: a phrase of %d words, outside 2..%d" % (where, len(ph), self.MAX_WORDS))
+                if ph in phrases:
+                    raise ValueError("Phrases: %s: the phrase %r is listed twice" % (where, ph))
+                phrases.append(ph)
+            if len(phrases) > self.MAX_BANNED:
+                raise ValueError("Phrases: %s: %d phrases, more than %d" % (where, len(phrases), self.MAX_BANNED))
+            out.append(tuple(phrases))
+        required = self.required
+        if required is None:
+            required = ()
+        if not seq(required) or any(not seq(row) for row in required):
+            raise ValueError("Phrases: required = %r is not one list of items per commit" % (required,))
+        req = []
+        for k, row in enumerate(required):
+            where = "required items of commit %d" % k
+            items = []
+            for item in row:
+                if not seq(item):
+                    raise ValueError("Phrases: %s: %r is not an item (a sequence of 1..%d ids)" % (where, item, self.MAX_WORDS))
+                item = self._ids(item, where, UNK + 1)
+                if not 1 <= len(item) <= self.MAX_WORDS:
+                    raise ValueError("Phrases: %s: an item of %d words, outside 1..%d" % (where, len(item), self.MAX_WORDS))
+                items.append(item)
+            if len(items) > self.MAX_ITEMS:
+                raise ValueError("Phrases: %s: %d items, more than %d" % (where, len(items), self.MAX_ITEMS))
+            if sum(len(i) for i in items) > self.MAX_REQUIRED_WORDS:
+                raise ValueError("Phrases: %s: %d words in all, more than %d (one bank per word)"
+                                 % (where, sum(len(i) for i in items), self.MAX_REQUIRED_WORDS))
+            for a, x in enumerate(items):
+                for c, y in enumerate(items):
+                    if a != c and len(x) <= len(y) and any(y[o:o + len(x)] == x for o in range(len(y) - len(x) + 1)) \
+                            and (len(x) < len(y) or a > c):
+                        raise ValueError("Phrases: %s: the item %r %s %r" % (where, x, "duplicates" if x == y else "is part of", y))
+            req.append(tuple(items))
+        object.__setattr__(self, "banned", out[0] if shared else tuple(out))
+        object.__setattr__(self, "required", tuple(req))
+        object.__setattr__(self, "_shared", shared)
+
+    @property
+    def ban_active(self) -> bool:
+        return any(self.banned_rows(1)) if self._shared else any(self.banned)
+
+    @property
+    def require_active(self) -> bool:
+        return any(self.required)
+
+    @property
+    def active(self) -> bool:
+        return self.ban_active or self.require_active
+
+    def banned_rows(self, B: int):
+        """The banned phrases of each of B commits (a per-commit value: of the commits it was given for)."""
+        return [self.banned] * B if self._shared else list(self.banned)
+
+    def check(self, cfg, B: int) -> "Phrases":
+        """Against a model's geometry and a batch of B commits: the counts of lists and the ids against the vocabulary."""
+        if not self._shared and self.banned and len(self.banned) != B:
+            raise ValueError("Phrases: %d lists of banned phrases for a batch of %d commits" % (len(self.banned), B))
+        if self.required and len(self.required) != B:
+            raise ValueError("Phrases: %d lists of required items for a batch of %d commits" % (len(self.required), B))
+        for what, rows in (("banned", self.banned_rows(B)), ("required", self.required)):
+            for k, row in enumerate(rows):
+                for ph in row:
+                    for w in ph:
+                        if w >= cfg.vocab_size:
+                            raise ValueError("Phrases: commit %d: %s id %d outside the vocabulary (below %d)"
+                                             % (k, what, w, cfg.vocab_size))
+        return self
+
+    def banned_arrays(self, B: int):
+        """(phrase [B, 8, 4] int32, phrase_len [B, 8] int32, n_phrases [B] int32) of B commits; unused places hold 0."""
+        import numpy as np
+        words = np.zeros((B, self.MAX_BANNED, self.MAX_WORDS), dtype=np.int32)
+        lens = np.zeros((B, self.MAX_BANNED), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        for k, row in enumerate(self.banned_rows(B)):
+            n[k] = len(row)
+            for q, ph in enumerate(row):
+                words[k, q, :len(ph)] = ph
+                lens[k, q] = len(ph)
+        return words, lens, n
+
+    def required_arrays(self, B: int):
+        """(words [B, 4] int32: the items' words concatenated, item_len [B, 4] int32, n_items [B] int32) of B commits."""
+        import numpy as np
+        words = np.zeros((B, self.MAX_REQUIRED_WORDS), dtype=np.int32)
+        lens = np.zeros((B, self.MAX_ITEMS), dtype=np.int32)
+        n = np.zeros(B, dtype=np.int32)
+        for k, row in enumerate(self.required or [()] * B):
+            flat = [w for item in row for w in item]
+            words[k, :len(flat)] = flat
+            lens[k, :len(row)] = [len(item) for item in row]
+            n[k] = len(row)
+        return words, lens, n
+
+
+def contains_phrase(words, phrase) -> bool:
+    """``phrase`` occurs contiguously in ``words``."""
+    words, phrase = list(words), list(phrase)
+    return any(words[o:o + len(phrase)] == phrase for o in range(len(words) - len(phrase) + 1))
+
+
 class Scores(dict):
     """Result of ``Searcher.score``: a dict whose keys also read as attributes."""
 
@@ -422,6 +584,16 @@ def _refuses_penalties(why: str):
     return wrap
 
 
+def _refuses_phrases(search):
+    """``_refuses_penalties`` for ``phrases=``: taken for one purpose only, to refuse an active value (``Searcher._no_phrases``;
+    None and a value with nothing in it pass, as an inactive ``Penalties`` does); it is not handed on."""
+    @functools.wraps(search)
+    def refusing(self, *args, phrases=None, **kwargs):
+        Searcher._no_phrases(search.__name__, phrases)
+        return search(self, *args, **kwargs)
+    return refusing
+
+
 class _Loop:
     """The chunked step loop of one search over one batch, on the current stream.
 
@@ -507,9 +679,9 @@ class _Loop:
 
 
 class Searcher:
-    """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many``, ``beam`` and ``sample_search`` take four options
+    """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many``, ``beam`` and ``sample_search`` take five options
     that edit the step's distribution before a word is chosen (``sample_distinct`` takes the first two); ``_edit`` is the one place
-    that issues their kernels, in the order merge, prefix, constraints, penalties.  Each is off by default, and off -- None, False,
+    that issues their kernels, in the order merge, prefix, constraints, banned phrases, penalties.  Each is off by default, and off -- None, False,
     an inactive value, an all-empty prefix -- means the calls, keys, buffers and graphs of a search without it.
 
     ``constraints``: a ``Constraints`` value.  ``fira_constrain_dist`` zeroes the blocked words' entries of every row between
@@ -541,7 +713,12 @@ class Searcher:
     generator entry.  The value a search then returns is the product of the EDITED entries taken: a score, not a probability
     (``score`` gives the model's probability of a message).  The state is keyed by a "penalties" marker, not by the values (the
     table and the bias lists are device buffers, filled on every call: one capture serves every value).  ``sample``, ``score``,
-    ``sample_distinct`` and ``contrastive`` refuse an active value with a ``ValueError`` before anything is launched."""
+    ``sample_distinct`` and ``contrastive`` refuse an active value with a ``ValueError`` before anything is launched.
+
+    ``phrases``: a ``Phrases`` value.  Its banned phrases are the chain's fourth link: ``fira_ban_phrases_dist`` zeroes the entries of
+    the word that would complete a listed phrase.  Its required items are no edit but a selection (``fira_beam_select_phrases``), and
+    ``beam`` alone takes them.  The state is keyed by the markers "ban-phrases" / "require-phrases" (the lists are device buffers,
+    filled on every call).  ``sample``, ``score``, ``sample_distinct`` and ``contrastive`` refuse an active value."""
 
     def __init__(self, model: TransModel, kv_bf16: bool = False, members=(), weights=None):
         """``kv_bf16``: stream a bf16 copy of the cross-attention K|V in the step loop (FIRA_DECODE_KV_BF16: half of the
@@ -683,6 +860,79 @@ class Searcher:
         if penalties is not None and (not isinstance(penalties, Penalties) or penalties.active):
             raise ValueError("%s does not take penalties (%s); greedy, greedy_many, beam and sample_search do" % (what, why))
 
+    @staticmethod
+    def _no_phrases(what: str, phrases):
+        if phrases is not None and (not isinstance(phrases, Phrases) or phrases.active):
+            raise ValueError("%s does not take phrases (greedy, greedy_many, beam and sample_search take banned phrases, beam "
+                             "required ones)" % what)
+
+    def _phrases(self, phrases, B: int, con: Optional[Constraints], what: str, prefix_rows=None, beam: Optional[int] = None,
+                 require=None, scoring=None):
+        """(ban, req) of a search: each None for "none" (no value, or nothing in it: today's launches, buffers and graphs), else the
+        ``Phrases`` value checked against the model, the batch and the search's other options.  ``beam`` None: a search that has
+        no banks and refuses required items.  Raises ``ValueError`` naming the reason; nothing is launched before."""
+        if phrases is None:
+            return None, None
+        if not isinstance(phrases, Phrases):
+            raise ValueError("phrases: expected decode.Phrases or None, got %r" % (phrases,))
+        if not phrases.active:
+            return None, None
+        phrases.check(self.cfg, B)
+        cfg = self.cfg
+        ban = phrases if phrases.ban_active else None
+        req = phrases if phrases.require_active else None
+        banned = phrases.banned_rows(B)
+        if ban is not None and prefix_rows is not None:
+            for b, row in enumerate(prefix_rows):
+                for ph in banned[b]:
+                    if contains_phrase(row, ph):
+                        raise ValueError("phrases: commit %d: the prefix contains the banned phrase %r" % (b, ph))
+        if req is None:
+            return ban, None
+        if beam is None:
+            raise ValueError("phrases: %s does not take required items (banks need a beam; beam does)" % what)
+        if require is not None:
+            raise ValueError("phrases: required items do not combine with require= (a one-word item is a required word)")
+        if scoring is not None:
+            raise ValueError("phrases: required items do not combine with an active scoring (the banks rank by raw probability)")
+        if beam < 2:
+            raise ValueError("phrases: beam = %d, but required items need a beam of at least 2" % beam)
+        for b, row in enumerate(phrases.required):
+            total = sum(len(item) for item in row)
+            if beam < total + 1:
+                raise ValueError("phrases: commit %d: %d required words need a beam of at least %d (one bank per word of "
+                                 "progress), beam = %d" % (b, total, total + 1, beam))
+            if total > cfg.tar_len - 2:
+                raise ValueError("phrases: commit %d: %d required words, more than tar_len - 2 = %d" % (b, total, cfg.tar_len - 2))
+            for item in row:
+                if con is not None:
+                    hit = sorted(set(item) & set(con.banned))
+                    if hit:
+                        raise ValueError("phrases: commit %d: the required item %r holds id %d, which the constraints ban"
+                                         % (b, item, hit[0]))
+                    n = con.no_repeat_ngram
+                    grams = [item[i:i + n] for i in range(len(item) - n + 1)] if n >= 1 else []
+                    if len(set(grams)) != len(grams):
+                        raise ValueError("phrases: commit %d: the required item %r itself repeats a %d-gram, which "
+                                         "no_repeat_ngram = %d forbids" % (b, item, n, n))
+                for ph in banned[b]:
+                    if contains_phrase(item, ph):
+                        raise ValueError("phrases: commit %d: the required item %r contains the banned phrase %r" % (b, item, ph))
+        return ban, req
+
+    def _fill_ban_phrases(self, st, ban: Phrases, B: int):
+        """The checked lists into the state's device buffers (every call, like the prefix buffers)."""
+        words, lens, n = ban.banned_arrays(B)
+        st["ban_phrase"].copy_(torch.from_numpy(words))
+        st["ban_phrase_len"].copy_(torch.from_numpy(lens))
+        st["n_ban_phrases"].copy_(torch.from_numpy(n))
+
+    def _fill_required_phrases(self, st, req: Phrases, B: int):
+        words, lens, n = req.required_arrays(B)
+        st["item_words"].copy_(torch.from_numpy(words))
+        st["item_len"].copy_(torch.from_numpy(lens))
+        st["n_items"].copy_(torch.from_numpy(n))
+
     def _fill_penalties(self, st, pen: Penalties, B: int):
         """The checked value into the state's device buffers (every call, like the prefix buffers)."""
         ids, fac, n = pen.bias_arrays(B)
@@ -717,6 +967,9 @@ class Searcher:
         when the kernel runs.
         constrain (st["con"]): ``fira_constrain_dist`` zeroes the blocked words' entries (section 6k); nothing is renormalised.
         Its scalars are baked into a captured graph.
+        ban phrases ("ban-phrases" in st): ``fira_ban_phrases_dist`` zeroes the entries of the word that would complete a banned
+        phrase (section 6zb).  The lists are read from st["ban_phrase"] / st["ban_phrase_len"] / st["n_ban_phrases"] when the
+        kernel runs.
         penalise ("penalties" in st): ``fira_penalise_dist`` multiplies the entries of the words a row already holds, and of the
         commit's biased words, by their factors (section 6za).  Last: a finite non-negative factor commutes bit for bit with the
         zeroing links, and after a merge a word's mass sits on its generator entry.  The table and the bias lists are read from
@@ -738,6 +991,10 @@ class Searcher:
             chain.append(("fira_constrain_dist", lambda *b: lib.fira_constrain_dist(
                 s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, c.no_repeat_ngram, c.min_length,
                 _lib.ptr(st["banned"]), len(c.banned), dist, *b)))
+        if "ban-phrases" in st:
+            chain.append(("fira_ban_phrases_dist", lambda *b: lib.fira_ban_phrases_dist(
+                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["ban_phrase"]),
+                _lib.ptr(st["ban_phrase_len"]), _lib.ptr(st["n_ban_phrases"]), dist, *b)))
         if "penalties" in st:
             chain.append(("fira_penalise_dist", lambda *b: lib.fira_penalise_dist(
                 s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["count_factor"]),
@@ -746,18 +1003,22 @@ class Searcher:
             last = best is not None and k == len(chain) - 1
             _lib.check(call(*((_lib.ptr(best[0]), _lib.ptr(best[1])) if last else (None, None))), name)
 
-    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None):
+    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None, ban=None):
         """What the edit chain (``_edit``) owns in a state of R rows over B commits: ``con`` always (None: no constraint);
         ``merge`` only when merging; the [R, out_len] distribution when an edit is active (``dist=True``: in any case, for the
         beam family, whose selection reads it); the banned ids with constraints; the two prefix buffers with a prefix ``rows``;
-        with penalties ``pen`` the "penalties" marker, the count table [tar_len] and the bias lists [B, 16] / [B, 16] / [B]."""
+        with penalties ``pen`` the "penalties" marker, the count table [tar_len] and the bias lists [B, 16] / [B, 16] / [B]; with
+        banned phrases ``ban`` the "ban-phrases" marker and the lists [B, 8, 4] / [B, 8] / [B]."""
         st = dict(con=con)
+        if ban is not None:
+            st.update({"ban-phrases": True}, ban_phrase=i32(B, Phrases.MAX_BANNED, Phrases.MAX_WORDS),
+                      ban_phrase_len=i32(B, Phrases.MAX_BANNED), n_ban_phrases=i32(B))
         if merge:
             st["merge"] = True
         if pen is not None:
             st.update(penalties=True, count_factor=f32(self.cfg.tar_len), bias_id=i32(B, Penalties.MAX_BIASED),
                       bias_factor=f32(B, Penalties.MAX_BIASED), n_bias=i32(B))
-        if dist or con is not None or merge or rows is not None or pen is not None:
+        if dist or con is not None or merge or rows is not None or pen is not None or ban is not None:
             st["dist"] = f32(R, self.cfg.out_len)
         if con is not None:
             st["banned"] = torch.tensor(list(con.banned) or [0], dtype=torch.int32, device=self.model.device_)
@@ -809,15 +1070,17 @@ class Searcher:
 
     @staticmethod
     def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False, neighbour: bool = False,
-             penalties: bool = False):
+             penalties: bool = False, ban_phrases: bool = False, require_phrases: bool = False):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
         so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
         marker only: the prefix values live in device buffers), then "require" for a search with required words (a marker
         too), then "neighbour" for a search with a neighbour (a marker: the batch and the coefficients live in device buffers),
-        then "penalties" for a search with active penalties (a marker: the table and the bias lists live in device buffers);
-        an active BeamScoring value comes last."""
+        then "penalties" for a search with active penalties (a marker: the table and the bias lists live in device buffers),
+        then "ban-phrases" / "require-phrases" for a search with an active ``Phrases`` value (markers: the lists live in device
+        buffers); an active BeamScoring value comes last."""
         return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + (("require",) if require else ())
                 + (("neighbour",) if neighbour else ()) + (("penalties",) if penalties else ())
+                + (("ban-phrases",) if ban_phrases else ()) + (("require-phrases",) if require_phrases else ())
                 + ((con,) if con is not None else ()) + ((scoring,) if scoring is not None else ()))
 
     def _required_rows(self, require, B: int, beam: int, con: Optional[Constraints], scoring):
@@ -949,7 +1212,7 @@ class Searcher:
                        "fira_greedy_advance")
 
     def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
-                     merge_copies: bool = False, prefix=None, neighbour=None, penalties=None) -> _Loop:
+                     merge_copies: bool = False, prefix=None, neighbour=None, penalties=None, phrases=None) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  The
         active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, "penalties"][, constraints]), and so own their graphs)
         and add what ``_edit_state`` lists to the state -- the [B, out_len] distribution with any of them."""
@@ -959,22 +1222,26 @@ class Searcher:
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
         nb = self._neighbour(neighbour, B)                   # likewise
         pen = self._penalties(penalties, B)                  # likewise
+        ban, _ = self._phrases(phrases, B, con, "greedy", rows)      # likewise
         if nb is None:
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B),
-                                         **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen))
-            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, penalties=pen is not None),
-                         make, chunk, use_graphs)
+                                         **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen, ban=ban))
+            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, penalties=pen is not None,
+                                                ban_phrases=ban is not None), make, chunk, use_graphs)
         else:                                                # a neighbour: the state always owns the distribution
-            bare = con is None and not merge and rows is None and pen is None
+            bare = con is None and not merge and rows is None and pen is None and ban is None
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **({"mix_best": True} if bare else {}),
-                                         **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True, pen=pen))
+                                         **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True, pen=pen, ban=ban))
             loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=True,
-                                                penalties=pen is not None), make, chunk, use_graphs, nb)
+                                                penalties=pen is not None, ban_phrases=ban is not None), make, chunk,
+                         use_graphs, nb)
         st, ws = loop.st, loop.ws
         if rows is not None:
             self._fill_prefix(st, rows)
         if pen is not None:
             self._fill_penalties(st, pen, B)
+        if ban is not None:
+            self._fill_ban_phrases(st, ban, B)
         return loop.start(lambda lo, hi: self._greedy_steps(st, ws, B, lo, hi), lambda: self._greedy_reset(st),
                           lambda hi: self._none_alive(st, hi))
 
@@ -990,12 +1257,13 @@ class Searcher:
     @torch.no_grad()
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
                merge_copies: bool = False, prefix=None, neighbour: Optional[Neighbour] = None,
-               penalties: Optional[Penalties] = None):
+               penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None):
         """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``, ``merge_copies``,
         ``prefix`` and ``penalties`` are the class's options: with any of them the step writes its distribution instead of taking
         its fused arg-max, and the last kernel of the edit chain (``_edit``) takes the arg-max of what is left.  With active
         ``penalties`` the third tensor is the product of the edited entries taken -- a score, not a probability (``score`` gives
-        the model's probability of a message).
+        the model's probability of a message).  ``phrases``: a ``Phrases`` value with banned phrases (a link of the edit chain
+        after the constraints; "ban-phrases" joins the state key); required items are refused, they need a beam's banks.
 
         ``neighbour``: a ``Neighbour`` value.  Every step then also runs the model over the neighbour
         batch on the same tokens (a second workspace), folds that row into words with the neighbour's ids and mixes it into the
@@ -1007,11 +1275,12 @@ class Searcher:
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
         return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix, neighbour,
-                                                     penalties).run())
+                                                     penalties, phrases).run())
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
-                    merge_copies: bool = False, prefix=None, neighbour=None, penalties: Optional[Penalties] = None):
+                    merge_copies: bool = False, prefix=None, neighbour=None, penalties: Optional[Penalties] = None,
+                    phrases: Optional[Phrases] = None):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -1028,11 +1297,15 @@ class Searcher:
         returned probability is then the joint probability of prefix and continuation.
         ``neighbour``: one ``Neighbour`` (or None) per batch, a sequence as long as ``dbs``.
         ``penalties``: one ``Penalties`` value for every batch (a per-commit bias list then needs batches of one size); the
-        returned value is then a score, as for ``greedy``."""
+        returned value is then a score, as for ``greedy``.
+        ``phrases``: one ``Phrases`` value with banned phrases for every batch (per-commit lists then need batches of one
+        size), as for ``greedy``."""
         dbs = list(dbs)
         con = self._active(constraints)                      # raises before a lane starts
         for db in dbs:
             self._penalties(penalties, db.B)                 # every batch's, before a lane starts
+            if prefix is None:                               # (with prefixes: checked with each batch's, below)
+                self._phrases(phrases, db.B, con, "greedy_many")
         if neighbour is not None:
             try:
                 neighbour = list(neighbour)
@@ -1049,8 +1322,8 @@ class Searcher:
                 raise ValueError("prefix: expected one prefix argument per batch, got %r" % (prefix,)) from None
             if len(prefix) != len(dbs):
                 raise ValueError("prefix: %d prefix arguments for %d batches" % (len(prefix), len(dbs)))
-            for db, p in zip(dbs, prefix):
-                self._prefix_rows(p, db.B, con)              # every batch's, before a lane starts
+            for db, p in zip(dbs, prefix):                   # every batch's, before a lane starts
+                self._phrases(phrases, db.B, con, "greedy_many", self._prefix_rows(p, db.B, con))
         n_lane = max(1, min(in_flight, len(dbs)))
         if not hasattr(self, "_lanes") or len(self._lanes) < n_lane:
             streams = concurrent_streams(n_lane, self.model.device_)
@@ -1083,7 +1356,7 @@ class Searcher:
                     if active[k] is None and nxt < len(dbs):
                         loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies,
                                                  None if prefix is None else prefix[nxt],
-                                                 None if neighbour is None else neighbour[nxt], penalties)
+                                                 None if neighbour is None else neighbour[nxt], penalties, phrases)
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -1147,7 +1420,7 @@ class Searcher:
     @torch.no_grad()
     def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                keys=None, chunk: int = 5, use_graphs: bool = True, neighbour=None, min_p: float = 0.0, epsilon: float = 0.0,
-               eta: float = 0.0, typical_p: float = 1.0, penalties=None):
+               eta: float = 0.0, typical_p: float = 1.0, penalties=None, phrases=None):
         """``n`` sampled messages per commit.  Returns (tokens [B,n,T] int64 starting with <start>, lengths [B,n],
         probability [B,n], log-probability [B,n]); the probabilities are the model's (untempered, unfiltered) ones of the
         emitted ids.
@@ -1168,6 +1441,7 @@ class Searcher:
         self._no_ensemble("sample")                           # raises before anything is launched
         self._no_neighbour("sample", neighbour)
         self._no_penalties("sample", "its fused step hands no distribution over; sample_search does", penalties)
+        self._no_phrases("sample", phrases)
         cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)
         B, T = db.B, self.cfg.tar_len
         R = B * n
@@ -1205,7 +1479,7 @@ class Searcher:
                       min_p: float = 0.0, epsilon: float = 0.0, eta: float = 0.0, typical_p: float = 1.0, seed: int = 0, keys=None,
                       constraints: Optional[Constraints] = None, merge_copies: bool = False, prefix=None,
                       neighbour: Optional[Neighbour] = None, chunk: int = 5, use_graphs: bool = True,
-                      penalties: Optional[Penalties] = None):
+                      penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None):
         """``n`` sampled messages per commit, drawn from the search's EDITED distribution: what ``sample`` returns (tokens
         [B,n,T], lengths [B,n], probability [B,n], log-probability [B,n]), with every option of the searches -- ``constraints``,
         ``merge_copies``, ``prefix``, ``penalties`` (the class's options), an ensemble (``members=``) and a ``neighbour`` -- and
@@ -1226,7 +1500,7 @@ class Searcher:
 
         The filters and cuts are fixed in the captured launches and join the state's key with the options (``_key``); the
         prefix, the seed, the keys and the neighbour's coefficients are device values, so one capture serves all of them.
-        There is no ``require=``: banks need a beam.  A ``ValueError`` before anything is launched on a value outside its
+        ``phrases``: banned phrases, as for ``greedy``.  There is no ``require=`` and no required item: banks need a beam.  A ``ValueError`` before anything is launched on a value outside its
         range, ``n`` outside 1..8, or whatever the options' own checks refuse (a neighbour with members among them)."""
         cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)     # every refusal: before anything is launched
         if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 1 <= n <= 8:
@@ -1246,11 +1520,12 @@ class Searcher:
         rows = self._prefix_rows(prefix, B, con)
         nb = self._neighbour(neighbour, B)
         pen = self._penalties(penalties, B)
+        ban, _ = self._phrases(phrases, B, con, "sample_search", rows)
         noise_rows, fill_noise = self._noise(keys, seed, B)
         make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), **noise_rows(i32),
-                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True, pen=pen))
+                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True, pen=pen, ban=ban))
         key = self._key(("sample_search", B, n, temperature, top_k, top_p) + cuts, merge, con, forced=rows is not None,
-                        neighbour=nb is not None, penalties=pen is not None)
+                        neighbour=nb is not None, penalties=pen is not None, ban_phrases=ban is not None)
         loop = _Loop(self, db, n, key, make, chunk, use_graphs, nb)
         st, ws = loop.st, loop.ws
         fill_noise(st)
@@ -1258,6 +1533,8 @@ class Searcher:
             self._fill_prefix(st, rows)
         if pen is not None:
             self._fill_penalties(st, pen, B)
+        if ban is not None:
+            self._fill_ban_phrases(st, ban, B)
         loop.start(lambda lo, hi: self._sample_search_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts),
                    lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
@@ -1398,7 +1675,7 @@ class Searcher:
 
     @torch.no_grad()
     def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None,
-              neighbour=None, penalties=None):
+              neighbour=None, penalties=None, phrases=None):
         """Teacher-forced probability of given messages.  ``cand`` [B, n, T] (or [B, T]) vocabulary ids, each message starting
         with <start> and ending with <eos> unless truncated, zero-padded; 1 <= n <= 8 candidates per commit share the
         commit's encoder pass and memory (``fira_decode_begin`` with n rows per commit).  ``labels`` (same shape, optional):
@@ -1416,6 +1693,7 @@ class Searcher:
         self._no_ensemble("score")                            # raises before anything is launched
         self._no_neighbour("score", neighbour)
         self._no_penalties("score", "its fused step hands no distribution over, and it reports the model's probability", penalties)
+        self._no_phrases("score", phrases)
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
         cand, length, labels = self.check_candidates(cand, lengths, labels, B)        # raises before anything is launched
@@ -1500,15 +1778,20 @@ class Searcher:
 
     def _beam_steps(self, st, ws, B, beam, lo, hi):
         """Steps lo..hi-1 of run_model.py:225-340 (``_family_steps``) with fira_beam_select, under a BeamScoring
-        fira_beam_select_scored, or with required words fira_beam_select_required, as the selection."""
-        sc, dims, req = st.get("scoring"), C.byref(self.model.dims), "required" in st
+        fira_beam_select_scored, with required words fira_beam_select_required, or with required items
+        fira_beam_select_phrases, as the selection."""
+        sc, dims, req, items = st.get("scoring"), C.byref(self.model.dims), "required" in st, "require-phrases" in st
 
         def select(lib, s, step, cur, nxt):
             state = (_lib.ptr(st["dist"]), _lib.ptr(st["fin"]), _lib.ptr(st["active"]), _lib.ptr(st["done"]),
                      _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["gen"][cur]), _lib.ptr(st["length"][cur]),
                      _lib.ptr(st["prob"][cur]), _lib.ptr(st["gen"][nxt]), _lib.ptr(st["length"][nxt]),
                      _lib.ptr(st["prob"][nxt]), _lib.ptr(st["parent"]))
-            if req:
+            if items:
+                _lib.check(lib.fira_beam_select_phrases(s, dims, B, beam, *state, _lib.ptr(st["item_words"]),
+                                                        _lib.ptr(st["item_len"]), _lib.ptr(st["n_items"]), _lib.ptr(st["met"])),
+                           "fira_beam_select_phrases")
+            elif req:
                 _lib.check(lib.fira_beam_select_required(s, dims, B, beam, *state, _lib.ptr(st["required"]),
                                                          _lib.ptr(st["n_required"]), _lib.ptr(st["met"])),
                            "fira_beam_select_required")
@@ -1523,7 +1806,7 @@ class Searcher:
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
              scoring: Optional[BeamScoring] = None, prefix=None, require=None, neighbour: Optional[Neighbour] = None,
-             penalties: Optional[Penalties] = None):
+             penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``,
         ``prefix`` and ``penalties`` are the class's options, one library call per step each, between the step and the selection
         (``_edit``); the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, "require"][, "neighbour"][, "penalties"]
@@ -1553,6 +1836,16 @@ class Searcher:
         ``beam < len(words) + 1`` (a bank per count), more than tar_len - 2 words, a word the ``constraints`` ban, or an
         active ``scoring``.
 
+        ``phrases``: a ``Phrases`` value.  Its banned phrases are a link of the edit chain, after the
+        constraints ("ban-phrases" joins the state key).  Its required items take ``require=``'s place with word sequences:
+        ``fira_beam_select_phrases`` is the selection, the banks count ``progress`` -- the words of the items a hypothesis holds
+        contiguously plus the longest item start it ends in, a credit it loses when it breaks the phrase off -- no message ends
+        before every item is complete, and the call returns (hypotheses, lengths, probabilities, met [B,beam]) with met = the
+        progress of every slot; ``best_required`` picks the message ("require-phrases" joins the state key; device buffers, one
+        capture for every list).  A ``ValueError`` before anything is launched on what ``Phrases`` and ``_phrases`` refuse:
+        required items together with ``require=`` or an active ``scoring``, ``beam < 2``, ``beam`` below the number of required
+        words + 1, an item that holds a banned word or phrase or repeats an n-gram, a prefix that contains a banned phrase.
+
         ``neighbour``: a ``Neighbour`` value, as for ``greedy``: the neighbour batch's step over the same tokens and parents (its
         caches follow the beam's reordering), its row folded into words, ``fira_mix_neighbour`` into the beam's distribution, then
         the edit chain and the selection as ever.  It combines with every option above; "neighbour" joins the state key.
@@ -1572,10 +1865,14 @@ class Searcher:
         words = self._required_rows(require, B, beam, con, scoring)   # likewise
         nb = self._neighbour(neighbour, B)                   # likewise
         pen = self._penalties(penalties, B)                  # likewise
+        ban, items = self._phrases(phrases, B, con, "beam", rows, beam, words, scoring)     # likewise
 
         def make(i32, f32):
             st = dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
-                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True, pen=pen))
+                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True, pen=pen, ban=ban))
+            if items is not None:
+                st.update({"require-phrases": True}, item_words=i32(B, Phrases.MAX_REQUIRED_WORDS),
+                          item_len=i32(B, Phrases.MAX_ITEMS), n_items=i32(B), met=i32(BR))
             if words is not None:
                 st.update(required=i32(B, MAX_REQUIRED), n_required=i32(B), met=i32(BR))
             if scoring is not None:
@@ -1586,7 +1883,9 @@ class Searcher:
         loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring, rows is not None,
                                                **({} if words is None else {"require": True}),
                                                **({} if nb is None else {"neighbour": True}),
-                                               **({} if pen is None else {"penalties": True})), make, chunk, use_graphs,
+                                               **({} if pen is None else {"penalties": True}),
+                                               **({} if ban is None else {"ban_phrases": True}),
+                                               **({} if items is None else {"require_phrases": True})), make, chunk, use_graphs,
                      *(() if nb is None else (nb,)))
         st, ws = loop.st, loop.ws
         if rows is not None:
@@ -1595,10 +1894,14 @@ class Searcher:
             self._fill_required(st, words)
         if pen is not None:
             self._fill_penalties(st, pen, B)
+        if ban is not None:
+            self._fill_ban_phrases(st, ban, B)
+        if items is not None:
+            self._fill_required_phrases(st, items, B)
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
         res = self._family_result(loop, B, beam, ("prob",))
-        if words is not None:
+        if words is not None or items is not None:
             return res + (st["met"].view(B, beam).long(),)
         return res if scoring is None else res + (st["key"].view(B, beam).clone(),)
 
@@ -1622,7 +1925,7 @@ class Searcher:
     @torch.no_grad()
     def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
                         merge_copies: bool = True, constraints: Optional[Constraints] = None, chunk: int = 4,
-                        use_graphs: bool = True, neighbour=None, penalties=None):
+                        use_graphs: bool = True, neighbour=None, penalties=None, phrases=None):
         """``n`` messages per commit sampled WITHOUT replacement: stochastic beam search (Kool, van Hoof and Welling 2019;
         ``fira_beam_select_gumbel``).  A beam search whose ranking key is the Gumbel-perturbed
         log-probability of the hypothesis, a child's key conditioned on its parent's; the n hypotheses it ends with are an exact
@@ -1645,6 +1948,7 @@ class Searcher:
         B = db.B
         self._no_neighbour("sample_distinct", neighbour)     # raises before anything is launched
         self._no_penalties("sample_distinct", "its hypotheses are an exact sample from the model's distribution", penalties)
+        self._no_phrases("sample_distinct", phrases)
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
         noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched
@@ -1729,6 +2033,7 @@ class Searcher:
         running = (st["ended"] == 0) & (last > 0)
         return gen.long(), length.long(), torch.where(running, st["prob"][cur] * last, st["prob"][cur])
 
+    @_refuses_phrases
     @_refuses_penalties("it already penalises degeneration")
     @torch.no_grad()
     def contrastive(self, db: DeviceBatch, k: int, alpha: float = 0.6, chunk: int = 4, use_graphs: bool = True,

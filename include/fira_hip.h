@@ -963,6 +963,37 @@ int fira_beam_select_required(void* stream, const fira_dims* d, int B, int n_bea
                               const int32_t* required /* device, [B, 4] */, const int32_t* n_required /* device, [B] */,
                               int32_t* met_out /* [B*n_beam] or NULL */);
 
+/* Required PHRASES: fira_beam_select_required with items that are word sequences (csrc/beam_phrase.hip; additive, the ABI version
+ * is unchanged; Post and Vilar define dynamic beam allocation for phrases).  The arguments of fira_beam_select, then words,
+ * item_len, n_items and met_out -- DEVICE buffers read when the kernel runs: one captured graph serves every list.
+ * Per commit b: n = n_items[b] (clamped to 0..4) items, given flattened: item k has l_k = item_len[b, k] words (clamped to
+ * 0 .. 4 - (l_0 + .. + l_{k-1}), so the lengths sum to at most 4), the words words[b, o_k .. o_k + l_k), o_k = l_0 + .. + l_{k-1};
+ * total = the sum of the l_k.  For a hypothesis h = gen[1 .. length - 1] (length clamped to 1 .. tar_len):
+ *     done(h)      the set of items that occur contiguously in h
+ *     partial(h)   the largest q >= 1 for which some item k outside done(h) has q < l_k and its first q words are the last q
+ *                  words of h; 0 if there is none
+ *     progress(h)  (the sum of l_k over done(h)) + partial(h), in 0 .. total;  bank(h) = progress(h)
+ * Candidates: fira_beam_select_required's, with
+ *     running   entry i of running slot j: p = fp32(dist[j, i] * prob[j]), bank = progress(h_j . w(i))
+ *     carried   a finished hypothesis: p = prob[j], bank = progress(h_j)
+ *     void      fira_beam_select's two -1 cases, plus every entry with w(i) == <eos> (1) -- the generator entry and every copy slot
+ *               that carries id 1 -- of a running row with progress(h_j) < total
+ * A hypothesis that breaks a phrase off loses that phrase's partial credit: appending an unrelated word gives the sum over
+ * done(h_j) alone.  The two phases, the written order, the four state outputs, the `done` pass-through and the limits are
+ * fira_beam_select_required's with C = total; met_out[r] (optional) is the progress of the hypothesis written to row r.
+ * Anchors: with every item one word long the five outputs are fira_beam_select_required's bit for bit (words = its required,
+ * n_items = its n_required, item_len all 1); with n_items = 0 the four state outputs are fira_beam_select's.
+ * 2 <= n_beam <= 8, tar_len <= 64, vocab in 9 .. 25 600, sou_len + sub_len <= 1 024; anything else returns non-zero with the
+ * reason in fira_last_error() and nothing is launched.  One workgroup of 1 024 threads per commit; every running row is streamed
+ * once (plus at most 4 re-read entries per row); vector stores only, no global atomics.                                        */
+int fira_beam_select_phrases(void* stream, const fira_dims* d, int B, int n_beam, const float* dist, const int32_t* finished,
+                             const int32_t* active, const int32_t* done, const int32_t* sou, const int32_t* sub_token,
+                             const int32_t* gen_in, const int32_t* len_in, const float* prob_in, int32_t* gen_out,
+                             int32_t* len_out, float* prob_out, int32_t* parent,
+                             const int32_t* words /* device, [B, 4]: the items' words, concatenated */,
+                             const int32_t* item_len /* device, [B, 4] */, const int32_t* n_items /* device, [B] */,
+                             int32_t* met_out /* [B*n_beam] or NULL */);
+
 /* Contrastive search: the selection of one step (csrc/contrastive.hip; additive, the ABI version is unchanged; Su et al.,
  * NeurIPS 2022).  The state is the beam family's with k slots per commit, 2 <= k <= 8.  Entering step `step`, the k slots of
  * a running commit hold the same chosen prefix gen[0 .. step - 1]; slot j also holds one candidate next word v_j at position
@@ -1123,6 +1154,30 @@ int fira_penalise_dist(void* stream, const fira_dims* d, int R, int rows_per_com
                        const int32_t* n_bias /* device, [R / rows_per_commit] */,
                        float* dist /* [R, vocab + sou_len + sub_len], in place */,
                        int32_t* best_id, float* best_p /* both NULL or both [R] */);
+
+/* Banned phrases (csrc/phrase.hip; additive, the ABI version is unchanged): blocks the word that would complete a listed n-gram, in
+ * place, in the edit chain after fira_constrain_dist and before fira_penalise_dist.  fira_constrain_dist's definitions: W = vocab +
+ * sou_len + sub_len, entry i resolves to the word w(i), row r belongs to commit b = r / rows_per_commit, len = length[r] clamped to
+ * 1 .. tar_len, m = len - 1 words h_1 .. h_m emitted (prefix words included), and a row with gen[r, len - 1] == <eos> (1) is
+ * finished: it is not touched.  Commit b lists n = n_phrases[b] (clamped to 0 .. 8) phrases; phrase q is the l = phrase_len[b, q]
+ * words phrase[b, q, 0 .. l); a phrase with l outside 2 .. 4 is ignored.  For every other row and every phrase (w_1 .. w_l):
+ *     if m >= l - 1 and (h_{m-l+2} .. h_m) == (w_1 .. w_{l-1}), the word w_l is blocked
+ * and every entry i with w(i) blocked -- the generator id and every diff and sub-token slot that carries the word -- is set to
+ * exactly 0.0f.  Every other element keeps its bits; nothing is renormalised.  A blocked word outside [0, vocab) is never used as an
+ * index: it matches slots only.
+ * best_id / best_p (both NULL, or both [R]): the arg-max of the row as it then stands and its value, under (value descending,
+ * index ascending) -- the order of fira_constrain_dist; NaN never wins.  Without best_id the row is not read.
+ * phrase, phrase_len and n_phrases are DEVICE arrays read when the kernel runs, so one captured launch serves every list.
+ * tar_len in 2 .. 64, vocab in 4 .. 25 600, sou_len + sub_len <= 1 024, rows_per_commit >= 1 divides R; R == 0 is a no-op.  Any row
+ * width and any 4-byte alignment of dist; vector stores only, no atomics on global memory.                                     */
+int fira_ban_phrases_dist(void* stream, const fira_dims* d, int R, int rows_per_commit, const int32_t* gen /* [R, tar_len] */,
+                          const int32_t* length /* [R] */, const int32_t* sou /* [R / rows_per_commit, sou_len] */,
+                          const int32_t* sub_token /* [R / rows_per_commit, sub_len] */,
+                          const int32_t* phrase /* device, [R / rows_per_commit, 8, 4] */,
+                          const int32_t* phrase_len /* device, [R / rows_per_commit, 8] */,
+                          const int32_t* n_phrases /* device, [R / rows_per_commit] */,
+                          float* dist /* [R, vocab + sou_len + sub_len], in place */,
+                          int32_t* best_id, float* best_p /* both NULL or both [R] */);
 
 /* Ensemble decoding (csrc/mix.hip; additive, the ABI version is unchanged): mixes the step distributions of n_members models into
  * one, between the members' fira_decode_step calls and whatever takes a distribution next (fira_merge_dist, fira_constrain_dist,
