@@ -449,6 +449,284 @@ def contains_phrase(words, phrase) -> bool:
     return any(words[o:o + len(phrase)] == phrase for o in range(len(words) - len(phrase) + 1))
 
 
+@dataclasses.dataclass(frozen=True)
+class Template:
+    """A TEMPLATE in the hard search controls: a deterministic automaton over word classes that every
+    message must be accepted by -- the general form of ``Constraints.banned``, ``prefix=`` and ``Phrases(banned=)``, each of which
+    is a regular language over words.  ``fira_template_dist`` blocks, at every step, the words after which no accepted message
+    fits into the buffer any more, and <eos> wherever the automaton does not accept.  ``Template.sequence`` builds one from a
+    list of (word set, at least, at most) items.
+
+    ``word_class``: the class 0 .. C-1 of the vocabulary ids -- a ``{id: class}`` mapping (every id not named has class 0) or a
+    full sequence of ``vocab_size`` classes.  <pad>, <start> and <unkm> are ordinary ids; <eos> is no word: a mapping must not
+    name it, and its place in a full sequence is never used.
+    ``next``: S rows of C targets: the state after a word of that class, or -1 for "no such word here"; S, C <= 32.
+    ``accept``: the states in which a message may end.
+    ``start``: the start state -- one for every commit, or a sequence of one per commit, so that one union automaton serves a
+    batch whose commits follow different rules.
+
+    The default value has no state: it is inactive, and a search that is given it is the plain search.  Values are checked here
+    (``ValueError`` with the reason); what depends on the model and the batch is checked by ``check`` when a ``Searcher`` takes
+    the value.  Stored as tuples, so equal values compare and hash equal."""
+    word_class: object = ()
+    next: object = ()
+    accept: object = ()
+    start: object = 0
+
+    MAX_STATES, MAX_CLASSES, NEVER = 32, 32, 1 << 20
+
+    @staticmethod
+    def _int(v, what):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("Template: %s %r is not an integer" % (what, v))
+        return int(v)
+
+    def __post_init__(self):
+        seq = Phrases._seq
+        if not seq(self.next) or any(not seq(row) for row in self.next):
+            raise ValueError("Template: next = %r is not a sequence of rows of target states" % (self.next,))
+        nxt = tuple(tuple(self._int(t, "next: target") for t in row) for row in self.next)
+        S = len(nxt)
+        if S > self.MAX_STATES:
+            raise ValueError("Template: %d states, more than %d states" % (S, self.MAX_STATES))
+        C_ = len(nxt[0]) if S else 0
+        if any(len(row) != C_ for row in nxt):
+            raise ValueError("Template: next: the rows have different numbers of classes")
+        if C_ > self.MAX_CLASSES:
+            raise ValueError("Template: %d classes, more than %d classes" % (C_, self.MAX_CLASSES))
+        if S and C_ == 0:
+            raise ValueError("Template: next: no class (class 0, every word not named, always exists)")
+        for s, row in enumerate(nxt):
+            for c, t in enumerate(row):
+                if not -1 <= t < S:
+                    raise ValueError("Template: next[%d][%d] = %d is a target outside -1..%d" % (s, c, t, S - 1))
+        if not seq(self.accept):
+            raise ValueError("Template: accept = %r is not a sequence of states" % (self.accept,))
+        accept = tuple(sorted(set(self._int(s, "accept: state") for s in self.accept)))
+        for s in accept:
+            if not 0 <= s < S:
+                raise ValueError("Template: accept: state %d outside 0..%d" % (s, S - 1))
+        shared = not seq(self.start)
+        start = (self._int(self.start, "start: state"),) if shared else tuple(self._int(s, "start: state") for s in self.start)
+        for s in start:
+            if S and not 0 <= s < S:
+                raise ValueError("Template: start: state %d outside 0..%d (wrong range)" % (s, S - 1))
+        wc = self.word_class
+        full = not isinstance(wc, dict)
+        if full and not seq(wc):
+            raise ValueError("Template: word_class = %r is neither an {id: class} mapping nor a sequence of classes" % (wc,))
+        pairs = list(enumerate(wc)) if full else sorted((self._int(w, "word_class: id"), c) for w, c in wc.items())
+        classes = []
+        for w, c in pairs:
+            c = self._int(c, "word_class: class of id %d:" % w)
+            if w < 0:
+                raise ValueError("Template: word_class: id %d is negative" % w)
+            if not 0 <= c < max(C_, 1):
+                raise ValueError("Template: word_class: id %d has class %d outside 0..%d" % (w, c, max(C_, 1) - 1))
+            classes.append(c)
+        # need[s]: the fewest words from s to an accepting state (breadth first, backwards from the accepting states)
+        need = [0 if s in accept else self.NEVER for s in range(S)]
+        frontier = list(accept)
+        while frontier:
+            reached = []
+            for s in range(S):
+                if need[s] == self.NEVER and any(t in frontier for t in nxt[s]):
+                    need[s] = need[frontier[0]] + 1
+                    reached.append(s)
+            frontier = reached
+        object.__setattr__(self, "next", nxt)
+        object.__setattr__(self, "accept", accept)
+        object.__setattr__(self, "start", start[0] if shared else start)
+        object.__setattr__(self, "word_class", tuple(classes) if full else tuple((w, c) for (w, _), c in zip(pairs, classes)))
+        object.__setattr__(self, "_full", full)
+        object.__setattr__(self, "_class_of", None if full else dict(self.word_class))
+        object.__setattr__(self, "need", tuple(need))
+
+    @property
+    def n_states(self) -> int:
+        return len(self.next)
+
+    @property
+    def n_classes(self) -> int:
+        return len(self.next[0]) if self.next else 0
+
+    @property
+    def active(self) -> bool:
+        return self.n_states > 0
+
+    def class_of(self, w: int) -> int:
+        """The class of the word ``w``; an id that is not named, or outside the vocabulary, has class 0."""
+        if self._full:
+            return self.word_class[w] if 0 <= w < len(self.word_class) else 0
+        return self._class_of.get(w, 0)
+
+    def start_rows(self, B: int):
+        """The start state of each of B commits."""
+        return [self.start] * B if isinstance(self.start, int) else list(self.start)
+
+    def walk(self, words, state: int) -> int:
+        """The state after ``words`` from ``state``; -1 once there is no transition."""
+        for w in words:
+            if state < 0:
+                break
+            state = self.next[state][self.class_of(int(w))]
+        return state
+
+    def accepts(self, ids, commit: int = 0) -> bool:
+        """The automaton of commit ``commit`` accepts the message ``ids``: the words after <start>, with or without the <eos>
+        that ends them (a message that filled the buffer has none).  The inactive value accepts everything."""
+        words = [int(w) for w in ids]
+        if words and words[-1] == EOS:
+            words.pop()
+        if not self.active:
+            return True
+        if EOS in words:
+            return False
+        return self.walk(words, self.start_rows(commit + 1)[commit]) in self.accept
+
+    def longest_fits(self, state: int, least: int, most: int) -> bool:
+        """From ``state`` some accepted message has between ``least`` and ``most`` words (a dynamic program over (state, words))."""
+        reach = {state} if state >= 0 else set()
+        for n in range(most + 1):
+            if n >= least and reach & set(self.accept):
+                return True
+            reach = {t for s in reach for t in self.next[s] if t >= 0}
+        return False
+
+    def check(self, cfg, B: int) -> "Template":
+        """Against a model's geometry and a batch of B commits."""
+        V, T = cfg.vocab_size, cfg.tar_len
+        if self._full:
+            if len(self.word_class) != V:
+                raise ValueError("Template: word_class: %d classes for a vocabulary of %d ids" % (len(self.word_class), V))
+        else:
+            for w, _ in self.word_class:
+                if w >= V:
+                    raise ValueError("Template: word_class: id %d outside the vocabulary [0, %d)" % (w, V))
+                if w == EOS:
+                    raise ValueError("Template: word_class: <eos> (id %d) is named; it is no word, accept says where a message "
+                                     "may end" % EOS)
+        if not isinstance(self.start, int) and len(self.start) != B:
+            raise ValueError("Template: start: %d states for a batch of %d commits (wrong length)" % (len(self.start), B))
+        for b, s in enumerate(self.start_rows(B)):
+            if self.need[s] > T - 1:
+                raise ValueError("Template: commit %d: no accepted message within tar_len - 1 = %d words from state %d"
+                                 % (b, T - 1, s))
+        return self
+
+    def arrays(self, B: int, vocab_size: Optional[int] = None):
+        """The device tables of B commits as numpy arrays: (word_class [V] uint8, next [32 * 32] int8 with pitch 32, need [32]
+        int32, start [B] int32).  Rows of states that do not exist hold -1 (need: ``NEVER``); the columns of classes that do
+        not exist repeat class 0's, so a state that takes every word allows all 32 classes and the kernel returns early."""
+        import numpy as np
+        V = len(self.word_class) if self._full else vocab_size
+        if V is None:
+            raise ValueError("Template: arrays needs vocab_size for an {id: class} mapping")
+        wc = np.zeros(V, dtype=np.uint8)
+        if self._full:
+            wc[:] = self.word_class
+        else:
+            for w, c in self.word_class:
+                wc[w] = c
+        S, C_ = self.n_states, self.n_classes
+        nxt = np.full((self.MAX_STATES, self.MAX_CLASSES), -1, dtype=np.int8)
+        need = np.full(self.MAX_STATES, self.NEVER, dtype=np.int32)
+        if S:
+            nxt[:S, :C_] = self.next
+            nxt[:S, C_:] = nxt[:S, :1]
+            need[:S] = self.need
+        return wc, nxt.reshape(-1), need, np.array(self.start_rows(B), dtype=np.int32)
+
+    @classmethod
+    def sequence(cls, items, vocab_size: int, start=0) -> "Template":
+        """The template "``items`` in this order": every item is (ids or None, lo, hi) -- a word from this set of vocabulary ids,
+        or any word for None, between ``lo`` and ``hi`` times, ``hi=None`` meaning unbounded.  The classes are the distinct
+        membership signatures of the ids in the sets (class 0: in no set), the states come from the subset construction, so
+        adjacent sets may overlap ("any word, 0 to 3 times" followed by ":").  More than 32 of either is a ``ValueError``."""
+        V = cls._int(vocab_size, "sequence: vocab_size")
+        sets, units = [], []                               # units: (set index or None, optional); loops: node -> set index
+        loops = {}
+        for k, item in enumerate(items):
+            try:
+                ids, lo, hi = item
+            except (TypeError, ValueError):
+                raise ValueError("Template.sequence: item %d: %r is not (ids or None, lo, hi)" % (k, item)) from None
+            lo = cls._int(lo, "sequence: item %d: lo" % k)
+            hi = None if hi is None else cls._int(hi, "sequence: item %d: hi" % k)
+            if lo < 0 or (hi is not None and hi < lo):
+                raise ValueError("Template.sequence: item %d: counts %d..%r are not 0 <= lo <= hi" % (k, lo, hi))
+            if ids is not None:
+                if not Phrases._seq(ids):
+                    raise ValueError("Template.sequence: item %d: %r is neither a set of ids nor None" % (k, ids))
+                ids = frozenset(cls._int(w, "sequence: item %d: id" % k) for w in ids)
+                for w in sorted(ids):
+                    if not 0 <= w < V:
+                        raise ValueError("Template.sequence: item %d: id %d outside the vocabulary [0, %d)" % (k, w, V))
+                    if w == EOS:
+                        raise ValueError("Template.sequence: item %d: <eos> (id %d) is named; it is no word" % (k, EOS))
+                if not ids:
+                    raise ValueError("Template.sequence: item %d: an empty set of ids" % k)
+            if lo > cls.MAX_STATES or (hi is not None and hi - lo > cls.MAX_STATES):
+                raise ValueError("Template.sequence: item %d: counting %d..%r words takes more than %d states"
+                                 % (k, lo, hi, cls.MAX_STATES))
+            if ids is not None and ids not in sets:
+                sets.append(ids)
+            j = None if ids is None else sets.index(ids)
+            units += [(j, False)] * lo + [(j, True)] * (0 if hi is None else hi - lo)
+            if hi is None:
+                loops.setdefault(len(units), []).append(j)
+        # classes: the membership signature of every id; class 0 is "in no set"
+        sig_class = {(False,) * len(sets): 0}
+        word_class = {}
+        for w in sorted(set().union(*sets) if sets else ()):
+            c = sig_class.setdefault(tuple(w in s for s in sets), len(sig_class))
+            word_class[w] = c
+        if len(sig_class) > cls.MAX_CLASSES:
+            too_many_classes = len(sig_class)
+        else:
+            too_many_classes = 0
+        takes = lambda j, sig: j is None or sig[j]         # a unit or a loop over set j (None: any word) takes a word of sig
+        final = len(units)
+
+        def closure(nodes):
+            out = set()
+            for n in nodes:
+                out.add(n)
+                while n < final and units[n][1]:           # an optional unit may be skipped
+                    n += 1
+                    out.add(n)
+            return frozenset(out)
+
+        sigs = sorted(sig_class, key=sig_class.get)
+        states = {closure({0}): 0}
+        order = [closure({0})]
+        nxt = []
+        for sub in order:                                  # (grows while it is walked)
+            row = []
+            for sig in sigs:
+                to = set()
+                for n in sub:
+                    if n < final and takes(units[n][0], sig):
+                        to.add(n + 1)
+                    if any(takes(j, sig) for j in loops.get(n, ())):
+                        to.add(n)
+                if not to:
+                    row.append(-1)
+                    continue
+                to = closure(to)
+                if to not in states:
+                    states[to] = len(order)
+                    order.append(to)
+                    if len(order) > cls.MAX_STATES:
+                        raise ValueError("Template.sequence: the items take more than %d states" % cls.MAX_STATES)
+                row.append(states[to])
+            nxt.append(row)
+        if too_many_classes:
+            raise ValueError("Template.sequence: the sets divide the vocabulary into %d classes, more than %d classes"
+                             % (too_many_classes, cls.MAX_CLASSES))
+        return cls(word_class, nxt, [k for k, sub in enumerate(order) if final in sub], start)
+
+
 class Scores(dict):
     """Result of ``Searcher.score``: a dict whose keys also read as attributes."""
 
@@ -594,6 +872,15 @@ def _refuses_phrases(search):
     return refusing
 
 
+def _refuses_template(search):
+    """``_refuses_phrases`` for ``template=`` (``Searcher._no_template``); it is not handed on."""
+    @functools.wraps(search)
+    def refusing(self, *args, template=None, **kwargs):
+        Searcher._no_template(search.__name__, template)
+        return search(self, *args, **kwargs)
+    return refusing
+
+
 class _Loop:
     """The chunked step loop of one search over one batch, on the current stream.
 
@@ -681,7 +968,7 @@ class _Loop:
 class Searcher:
     """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many``, ``beam`` and ``sample_search`` take five options
     that edit the step's distribution before a word is chosen (``sample_distinct`` takes the first two); ``_edit`` is the one place
-    that issues their kernels, in the order merge, prefix, constraints, banned phrases, penalties.  Each is off by default, and off -- None, False,
+    that issues their kernels, in the order merge, prefix, constraints, banned phrases, template, penalties.  Each is off by default, and off -- None, False,
     an inactive value, an all-empty prefix -- means the calls, keys, buffers and graphs of a search without it.
 
     ``constraints``: a ``Constraints`` value.  ``fira_constrain_dist`` zeroes the blocked words' entries of every row between
@@ -718,7 +1005,13 @@ class Searcher:
     ``phrases``: a ``Phrases`` value.  Its banned phrases are the chain's fourth link: ``fira_ban_phrases_dist`` zeroes the entries of
     the word that would complete a listed phrase.  Its required items are no edit but a selection (``fira_beam_select_phrases``), and
     ``beam`` alone takes them.  The state is keyed by the markers "ban-phrases" / "require-phrases" (the lists are device buffers,
-    filled on every call).  ``sample``, ``score``, ``sample_distinct`` and ``contrastive`` refuse an active value."""
+    filled on every call).  ``sample``, ``score``, ``sample_distinct`` and ``contrastive`` refuse an active value.
+
+    ``template``: a ``Template`` value, the chain's fifth link: ``fira_template_dist`` zeroes the entries of every word after which
+    the automaton accepts no message that still fits, and <eos> where it does not accept, so a message of positive probability
+    is one the automaton accepts.  The state is keyed by a "template" marker (the four tables are device buffers, filled on every
+    call).  It does not combine with required words or items; ``sample``, ``score``, ``sample_distinct`` and ``contrastive``
+    refuse an active value."""
 
     def __init__(self, model: TransModel, kv_bf16: bool = False, members=(), weights=None):
         """``kv_bf16``: stream a bf16 copy of the cross-attention K|V in the step loop (FIRA_DECODE_KV_BF16: half of the
@@ -920,6 +1213,48 @@ class Searcher:
                         raise ValueError("phrases: commit %d: the required item %r contains the banned phrase %r" % (b, item, ph))
         return ban, req
 
+    @staticmethod
+    def _no_template(what: str, template):
+        if template is not None and (not isinstance(template, Template) or template.active):
+            raise ValueError("%s does not take a template (greedy, greedy_many, beam and sample_search do)" % what)
+
+    def _template(self, template, B: int, con: Optional[Constraints], prefix_rows=None, require=None, items=None):
+        """None for "no template" (None or the inactive value: today's launches, buffers and graphs), else the ``Template`` value
+        checked against the model, the batch and the search's other options: ``prefix_rows`` (the checked prefix), ``con``,
+        ``require`` (the checked required words) and ``items`` (a ``Phrases`` value with required items).  Raises ``ValueError``
+        naming the reason; nothing is launched before.  What cannot be seen in advance -- a state that admits only words another
+        control blocks at that step -- gives the hypothesis probability 0: a zero simply loses."""
+        if template is None:
+            return None
+        if not isinstance(template, Template):
+            raise ValueError("template: expected decode.Template or None, got %r" % (template,))
+        if not template.active:
+            return None
+        template.check(self.cfg, B)
+        T = self.cfg.tar_len
+        if require is not None or items is not None:
+            raise ValueError("template: does not combine with require= or Phrases(required=) (their <eos> rule and the "
+                             "template's can leave a row with nothing, and the banks would need the automaton)")
+        starts = template.start_rows(B)
+        for b, row in enumerate(prefix_rows or ()):
+            s = template.walk(row, starts[b])
+            if s < 0:
+                raise ValueError("template: commit %d: the prefix is not a path of the automaton from state %d" % (b, starts[b]))
+            if template.need[s] > T - 1 - len(row):
+                raise ValueError("template: commit %d: after the prefix of %d words no accepted message fits into the "
+                                 "remaining %d words" % (b, len(row), T - 1 - len(row)))
+        if con is not None and con.min_length:
+            for b, s in enumerate(starts):
+                if not template.longest_fits(s, con.min_length, T - 1):
+                    raise ValueError("template: commit %d: no accepted message has at least min_length = %d words within "
+                                     "tar_len - 1 = %d" % (b, con.min_length, T - 1))
+        return template
+
+    def _fill_template(self, st, tpl: Template, B: int):
+        """The checked tables into the state's device buffers (every call, like the prefix buffers)."""
+        for name, a in zip(("tpl_word_class", "tpl_next", "tpl_need", "tpl_start"), tpl.arrays(B, self.cfg.vocab_size)):
+            st[name].copy_(torch.from_numpy(a))
+
     def _fill_ban_phrases(self, st, ban: Phrases, B: int):
         """The checked lists into the state's device buffers (every call, like the prefix buffers)."""
         words, lens, n = ban.banned_arrays(B)
@@ -970,6 +1305,9 @@ class Searcher:
         ban phrases ("ban-phrases" in st): ``fira_ban_phrases_dist`` zeroes the entries of the word that would complete a banned
         phrase (section 6zb).  The lists are read from st["ban_phrase"] / st["ban_phrase_len"] / st["n_ban_phrases"] when the
         kernel runs.
+        template ("template" in st): ``fira_template_dist`` zeroes the entries of the words the automaton does not admit after
+        the row's hypothesis, and <eos> where it does not accept (section 6zc).  The four tables are read from st["tpl_word_class"]
+        / st["tpl_next"] / st["tpl_need"] / st["tpl_start"] when the kernel runs.
         penalise ("penalties" in st): ``fira_penalise_dist`` multiplies the entries of the words a row already holds, and of the
         commit's biased words, by their factors (section 6za).  Last: a finite non-negative factor commutes bit for bit with the
         zeroing links, and after a merge a word's mass sits on its generator entry.  The table and the bias lists are read from
@@ -995,6 +1333,10 @@ class Searcher:
             chain.append(("fira_ban_phrases_dist", lambda *b: lib.fira_ban_phrases_dist(
                 s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["ban_phrase"]),
                 _lib.ptr(st["ban_phrase_len"]), _lib.ptr(st["n_ban_phrases"]), dist, *b)))
+        if "template" in st:
+            chain.append(("fira_template_dist", lambda *b: lib.fira_template_dist(
+                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["tpl_word_class"]),
+                _lib.ptr(st["tpl_next"]), _lib.ptr(st["tpl_need"]), _lib.ptr(st["tpl_start"]), dist, *b)))
         if "penalties" in st:
             chain.append(("fira_penalise_dist", lambda *b: lib.fira_penalise_dist(
                 s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["count_factor"]),
@@ -1003,13 +1345,19 @@ class Searcher:
             last = best is not None and k == len(chain) - 1
             _lib.check(call(*((_lib.ptr(best[0]), _lib.ptr(best[1])) if last else (None, None))), name)
 
-    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None, ban=None):
+    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None, ban=None, tpl=None):
         """What the edit chain (``_edit``) owns in a state of R rows over B commits: ``con`` always (None: no constraint);
         ``merge`` only when merging; the [R, out_len] distribution when an edit is active (``dist=True``: in any case, for the
         beam family, whose selection reads it); the banned ids with constraints; the two prefix buffers with a prefix ``rows``;
         with penalties ``pen`` the "penalties" marker, the count table [tar_len] and the bias lists [B, 16] / [B, 16] / [B]; with
-        banned phrases ``ban`` the "ban-phrases" marker and the lists [B, 8, 4] / [B, 8] / [B]."""
+        banned phrases ``ban`` the "ban-phrases" marker and the lists [B, 8, 4] / [B, 8] / [B]; with a template ``tpl`` the
+        "template" marker and the tables [vocab] uint8 / [32 * 32] int8 / [32] / [B]."""
         st = dict(con=con)
+        if tpl is not None:
+            dev = self.model.device_
+            st.update(template=True, tpl_word_class=torch.zeros(self.cfg.vocab_size, dtype=torch.uint8, device=dev),
+                      tpl_next=torch.zeros(Template.MAX_STATES * Template.MAX_CLASSES, dtype=torch.int8, device=dev),
+                      tpl_need=i32(Template.MAX_STATES), tpl_start=i32(B))
         if ban is not None:
             st.update({"ban-phrases": True}, ban_phrase=i32(B, Phrases.MAX_BANNED, Phrases.MAX_WORDS),
                       ban_phrase_len=i32(B, Phrases.MAX_BANNED), n_ban_phrases=i32(B))
@@ -1018,7 +1366,7 @@ class Searcher:
         if pen is not None:
             st.update(penalties=True, count_factor=f32(self.cfg.tar_len), bias_id=i32(B, Penalties.MAX_BIASED),
                       bias_factor=f32(B, Penalties.MAX_BIASED), n_bias=i32(B))
-        if dist or con is not None or merge or rows is not None or pen is not None or ban is not None:
+        if dist or con is not None or merge or rows is not None or pen is not None or ban is not None or tpl is not None:
             st["dist"] = f32(R, self.cfg.out_len)
         if con is not None:
             st["banned"] = torch.tensor(list(con.banned) or [0], dtype=torch.int32, device=self.model.device_)
@@ -1070,17 +1418,19 @@ class Searcher:
 
     @staticmethod
     def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False, neighbour: bool = False,
-             penalties: bool = False, ban_phrases: bool = False, require_phrases: bool = False):
+             penalties: bool = False, ban_phrases: bool = False, require_phrases: bool = False, template: bool = False):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
         so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
         marker only: the prefix values live in device buffers), then "require" for a search with required words (a marker
         too), then "neighbour" for a search with a neighbour (a marker: the batch and the coefficients live in device buffers),
         then "penalties" for a search with active penalties (a marker: the table and the bias lists live in device buffers),
         then "ban-phrases" / "require-phrases" for a search with an active ``Phrases`` value (markers: the lists live in device
-        buffers); an active BeamScoring value comes last."""
+        buffers), then "template" for a search with an active ``Template`` (a marker: the tables live in device buffers); an
+        active BeamScoring value comes last."""
         return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + (("require",) if require else ())
                 + (("neighbour",) if neighbour else ()) + (("penalties",) if penalties else ())
                 + (("ban-phrases",) if ban_phrases else ()) + (("require-phrases",) if require_phrases else ())
+                + (("template",) if template else ())
                 + ((con,) if con is not None else ()) + ((scoring,) if scoring is not None else ()))
 
     def _required_rows(self, require, B: int, beam: int, con: Optional[Constraints], scoring):
@@ -1212,7 +1562,7 @@ class Searcher:
                        "fira_greedy_advance")
 
     def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
-                     merge_copies: bool = False, prefix=None, neighbour=None, penalties=None, phrases=None) -> _Loop:
+                     merge_copies: bool = False, prefix=None, neighbour=None, penalties=None, phrases=None, template=None) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  The
         active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, "penalties"][, constraints]), and so own their graphs)
         and add what ``_edit_state`` lists to the state -- the [B, out_len] distribution with any of them."""
@@ -1223,17 +1573,20 @@ class Searcher:
         nb = self._neighbour(neighbour, B)                   # likewise
         pen = self._penalties(penalties, B)                  # likewise
         ban, _ = self._phrases(phrases, B, con, "greedy", rows)      # likewise
+        tpl = self._template(template, B, con, rows)         # likewise
+        marks = {} if tpl is None else {"template": True}    # (off: today's key, argument for argument)
         if nb is None:
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B),
-                                         **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen, ban=ban))
+                                         **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen, ban=ban, tpl=tpl))
             loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, penalties=pen is not None,
-                                                ban_phrases=ban is not None), make, chunk, use_graphs)
+                                                ban_phrases=ban is not None, **marks), make, chunk, use_graphs)
         else:                                                # a neighbour: the state always owns the distribution
-            bare = con is None and not merge and rows is None and pen is None and ban is None
+            bare = con is None and not merge and rows is None and pen is None and ban is None and tpl is None
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **({"mix_best": True} if bare else {}),
-                                         **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True, pen=pen, ban=ban))
+                                         **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True, pen=pen, ban=ban,
+                                                            tpl=tpl))
             loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=True,
-                                                penalties=pen is not None, ban_phrases=ban is not None), make, chunk,
+                                                penalties=pen is not None, ban_phrases=ban is not None, **marks), make, chunk,
                          use_graphs, nb)
         st, ws = loop.st, loop.ws
         if rows is not None:
@@ -1242,6 +1595,8 @@ class Searcher:
             self._fill_penalties(st, pen, B)
         if ban is not None:
             self._fill_ban_phrases(st, ban, B)
+        if tpl is not None:
+            self._fill_template(st, tpl, B)
         return loop.start(lambda lo, hi: self._greedy_steps(st, ws, B, lo, hi), lambda: self._greedy_reset(st),
                           lambda hi: self._none_alive(st, hi))
 
@@ -1257,13 +1612,19 @@ class Searcher:
     @torch.no_grad()
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
                merge_copies: bool = False, prefix=None, neighbour: Optional[Neighbour] = None,
-               penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None):
+               penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
+               template: Optional[Template] = None):
         """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``, ``merge_copies``,
         ``prefix`` and ``penalties`` are the class's options: with any of them the step writes its distribution instead of taking
         its fused arg-max, and the last kernel of the edit chain (``_edit``) takes the arg-max of what is left.  With active
         ``penalties`` the third tensor is the product of the edited entries taken -- a score, not a probability (``score`` gives
         the model's probability of a message).  ``phrases``: a ``Phrases`` value with banned phrases (a link of the edit chain
         after the constraints; "ban-phrases" joins the state key); required items are refused, they need a beam's banks.
+        ``template``: a ``Template`` value, a link of the edit chain after the banned phrases ("template"
+        joins the state key; the tables are device buffers, one capture for every template).  A message of positive probability
+        is then accepted by the automaton.  A ``ValueError`` before anything is launched on what ``Template.check`` and
+        ``_template`` refuse: a prefix that is no path of the automaton or leaves no room, a ``min_length`` no accepted message
+        reaches.  A state that admits only words another control blocks leaves the hypothesis probability 0.
 
         ``neighbour``: a ``Neighbour`` value.  Every step then also runs the model over the neighbour
         batch on the same tokens (a second workspace), folds that row into words with the neighbour's ids and mixes it into the
@@ -1275,12 +1636,12 @@ class Searcher:
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
         return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix, neighbour,
-                                                     penalties, phrases).run())
+                                                     penalties, phrases, template).run())
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
                     merge_copies: bool = False, prefix=None, neighbour=None, penalties: Optional[Penalties] = None,
-                    phrases: Optional[Phrases] = None):
+                    phrases: Optional[Phrases] = None, template: Optional[Template] = None):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -1299,13 +1660,16 @@ class Searcher:
         ``penalties``: one ``Penalties`` value for every batch (a per-commit bias list then needs batches of one size); the
         returned value is then a score, as for ``greedy``.
         ``phrases``: one ``Phrases`` value with banned phrases for every batch (per-commit lists then need batches of one
-        size), as for ``greedy``."""
+        size), as for ``greedy``.
+        ``template``: one ``Template`` value for every batch (per-commit start states then need batches of one size), as for
+        ``greedy``."""
         dbs = list(dbs)
         con = self._active(constraints)                      # raises before a lane starts
         for db in dbs:
             self._penalties(penalties, db.B)                 # every batch's, before a lane starts
             if prefix is None:                               # (with prefixes: checked with each batch's, below)
                 self._phrases(phrases, db.B, con, "greedy_many")
+                self._template(template, db.B, con)
         if neighbour is not None:
             try:
                 neighbour = list(neighbour)
@@ -1324,6 +1688,7 @@ class Searcher:
                 raise ValueError("prefix: %d prefix arguments for %d batches" % (len(prefix), len(dbs)))
             for db, p in zip(dbs, prefix):                   # every batch's, before a lane starts
                 self._phrases(phrases, db.B, con, "greedy_many", self._prefix_rows(p, db.B, con))
+                self._template(template, db.B, con, self._prefix_rows(p, db.B, con))
         n_lane = max(1, min(in_flight, len(dbs)))
         if not hasattr(self, "_lanes") or len(self._lanes) < n_lane:
             streams = concurrent_streams(n_lane, self.model.device_)
@@ -1356,7 +1721,8 @@ class Searcher:
                     if active[k] is None and nxt < len(dbs):
                         loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies,
                                                  None if prefix is None else prefix[nxt],
-                                                 None if neighbour is None else neighbour[nxt], penalties, phrases)
+                                                 None if neighbour is None else neighbour[nxt], penalties, phrases,
+                                                 template)
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -1420,7 +1786,7 @@ class Searcher:
     @torch.no_grad()
     def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                keys=None, chunk: int = 5, use_graphs: bool = True, neighbour=None, min_p: float = 0.0, epsilon: float = 0.0,
-               eta: float = 0.0, typical_p: float = 1.0, penalties=None, phrases=None):
+               eta: float = 0.0, typical_p: float = 1.0, penalties=None, phrases=None, template=None):
         """``n`` sampled messages per commit.  Returns (tokens [B,n,T] int64 starting with <start>, lengths [B,n],
         probability [B,n], log-probability [B,n]); the probabilities are the model's (untempered, unfiltered) ones of the
         emitted ids.
@@ -1442,6 +1808,7 @@ class Searcher:
         self._no_neighbour("sample", neighbour)
         self._no_penalties("sample", "its fused step hands no distribution over; sample_search does", penalties)
         self._no_phrases("sample", phrases)
+        self._no_template("sample", template)
         cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)
         B, T = db.B, self.cfg.tar_len
         R = B * n
@@ -1479,7 +1846,8 @@ class Searcher:
                       min_p: float = 0.0, epsilon: float = 0.0, eta: float = 0.0, typical_p: float = 1.0, seed: int = 0, keys=None,
                       constraints: Optional[Constraints] = None, merge_copies: bool = False, prefix=None,
                       neighbour: Optional[Neighbour] = None, chunk: int = 5, use_graphs: bool = True,
-                      penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None):
+                      penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
+                      template: Optional[Template] = None):
         """``n`` sampled messages per commit, drawn from the search's EDITED distribution: what ``sample`` returns (tokens
         [B,n,T], lengths [B,n], probability [B,n], log-probability [B,n]), with every option of the searches -- ``constraints``,
         ``merge_copies``, ``prefix``, ``penalties`` (the class's options), an ensemble (``members=``) and a ``neighbour`` -- and
@@ -1500,6 +1868,7 @@ class Searcher:
 
         The filters and cuts are fixed in the captured launches and join the state's key with the options (``_key``); the
         prefix, the seed, the keys and the neighbour's coefficients are device values, so one capture serves all of them.
+        ``template``: a ``Template`` value, as for ``greedy``.
         ``phrases``: banned phrases, as for ``greedy``.  There is no ``require=`` and no required item: banks need a beam.  A ``ValueError`` before anything is launched on a value outside its
         range, ``n`` outside 1..8, or whatever the options' own checks refuse (a neighbour with members among them)."""
         cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)     # every refusal: before anything is launched
@@ -1521,11 +1890,13 @@ class Searcher:
         nb = self._neighbour(neighbour, B)
         pen = self._penalties(penalties, B)
         ban, _ = self._phrases(phrases, B, con, "sample_search", rows)
+        tpl = self._template(template, B, con, rows)
         noise_rows, fill_noise = self._noise(keys, seed, B)
         make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), **noise_rows(i32),
-                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True, pen=pen, ban=ban))
+                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True, pen=pen, ban=ban, tpl=tpl))
         key = self._key(("sample_search", B, n, temperature, top_k, top_p) + cuts, merge, con, forced=rows is not None,
-                        neighbour=nb is not None, penalties=pen is not None, ban_phrases=ban is not None)
+                        neighbour=nb is not None, penalties=pen is not None, ban_phrases=ban is not None,
+                        **({} if tpl is None else {"template": True}))
         loop = _Loop(self, db, n, key, make, chunk, use_graphs, nb)
         st, ws = loop.st, loop.ws
         fill_noise(st)
@@ -1535,6 +1906,8 @@ class Searcher:
             self._fill_penalties(st, pen, B)
         if ban is not None:
             self._fill_ban_phrases(st, ban, B)
+        if tpl is not None:
+            self._fill_template(st, tpl, B)
         loop.start(lambda lo, hi: self._sample_search_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts),
                    lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
@@ -1675,7 +2048,7 @@ class Searcher:
 
     @torch.no_grad()
     def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None,
-              neighbour=None, penalties=None, phrases=None):
+              neighbour=None, penalties=None, phrases=None, template=None):
         """Teacher-forced probability of given messages.  ``cand`` [B, n, T] (or [B, T]) vocabulary ids, each message starting
         with <start> and ending with <eos> unless truncated, zero-padded; 1 <= n <= 8 candidates per commit share the
         commit's encoder pass and memory (``fira_decode_begin`` with n rows per commit).  ``labels`` (same shape, optional):
@@ -1694,6 +2067,7 @@ class Searcher:
         self._no_neighbour("score", neighbour)
         self._no_penalties("score", "its fused step hands no distribution over, and it reports the model's probability", penalties)
         self._no_phrases("score", phrases)
+        self._no_template("score", template)
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
         cand, length, labels = self.check_candidates(cand, lengths, labels, B)        # raises before anything is launched
@@ -1806,7 +2180,8 @@ class Searcher:
     def beam(self, db: DeviceBatch, beam: int, chunk: int = 4, use_graphs: bool = True,
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
              scoring: Optional[BeamScoring] = None, prefix=None, require=None, neighbour: Optional[Neighbour] = None,
-             penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None):
+             penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
+             template: Optional[Template] = None):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``,
         ``prefix`` and ``penalties`` are the class's options, one library call per step each, between the step and the selection
         (``_edit``); the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, "require"][, "neighbour"][, "penalties"]
@@ -1846,6 +2221,11 @@ class Searcher:
         required items together with ``require=`` or an active ``scoring``, ``beam < 2``, ``beam`` below the number of required
         words + 1, an item that holds a banned word or phrase or repeats an n-gram, a prefix that contains a banned phrase.
 
+        ``template``: a ``Template`` value, a link of the edit chain after the banned phrases ("template"
+        joins the state key; device buffers, one capture for every template): every hypothesis of positive probability is then
+        accepted by the automaton.  It does not combine with ``require=`` or required items (a ``ValueError``, like a prefix
+        that is no path of the automaton and a ``min_length`` no accepted message reaches).
+
         ``neighbour``: a ``Neighbour`` value, as for ``greedy``: the neighbour batch's step over the same tokens and parents (its
         caches follow the beam's reordering), its row folded into words, ``fira_mix_neighbour`` into the beam's distribution, then
         the edit chain and the selection as ever.  It combines with every option above; "neighbour" joins the state key.
@@ -1866,10 +2246,11 @@ class Searcher:
         nb = self._neighbour(neighbour, B)                   # likewise
         pen = self._penalties(penalties, B)                  # likewise
         ban, items = self._phrases(phrases, B, con, "beam", rows, beam, words, scoring)     # likewise
+        tpl = self._template(template, B, con, rows, words, items)                          # likewise
 
         def make(i32, f32):
             st = dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
-                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True, pen=pen, ban=ban))
+                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True, pen=pen, ban=ban, tpl=tpl))
             if items is not None:
                 st.update({"require-phrases": True}, item_words=i32(B, Phrases.MAX_REQUIRED_WORDS),
                           item_len=i32(B, Phrases.MAX_ITEMS), n_items=i32(B), met=i32(BR))
@@ -1885,7 +2266,8 @@ class Searcher:
                                                **({} if nb is None else {"neighbour": True}),
                                                **({} if pen is None else {"penalties": True}),
                                                **({} if ban is None else {"ban_phrases": True}),
-                                               **({} if items is None else {"require_phrases": True})), make, chunk, use_graphs,
+                                               **({} if items is None else {"require_phrases": True}),
+                                               **({} if tpl is None else {"template": True})), make, chunk, use_graphs,
                      *(() if nb is None else (nb,)))
         st, ws = loop.st, loop.ws
         if rows is not None:
@@ -1898,6 +2280,8 @@ class Searcher:
             self._fill_ban_phrases(st, ban, B)
         if items is not None:
             self._fill_required_phrases(st, items, B)
+        if tpl is not None:
+            self._fill_template(st, tpl, B)
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
         res = self._family_result(loop, B, beam, ("prob",))
@@ -1925,7 +2309,7 @@ class Searcher:
     @torch.no_grad()
     def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
                         merge_copies: bool = True, constraints: Optional[Constraints] = None, chunk: int = 4,
-                        use_graphs: bool = True, neighbour=None, penalties=None, phrases=None):
+                        use_graphs: bool = True, neighbour=None, penalties=None, phrases=None, template=None):
         """``n`` messages per commit sampled WITHOUT replacement: stochastic beam search (Kool, van Hoof and Welling 2019;
         ``fira_beam_select_gumbel``).  A beam search whose ranking key is the Gumbel-perturbed
         log-probability of the hypothesis, a child's key conditioned on its parent's; the n hypotheses it ends with are an exact
@@ -1949,6 +2333,7 @@ class Searcher:
         self._no_neighbour("sample_distinct", neighbour)     # raises before anything is launched
         self._no_penalties("sample_distinct", "its hypotheses are an exact sample from the model's distribution", penalties)
         self._no_phrases("sample_distinct", phrases)
+        self._no_template("sample_distinct", template)
         con = self._active(constraints)                      # raises before anything is launched
         merge = bool(merge_copies)
         noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched
@@ -2033,6 +2418,7 @@ class Searcher:
         running = (st["ended"] == 0) & (last > 0)
         return gen.long(), length.long(), torch.where(running, st["prob"][cur] * last, st["prob"][cur])
 
+    @_refuses_template
     @_refuses_phrases
     @_refuses_penalties("it already penalises degeneration")
     @torch.no_grad()

@@ -1179,6 +1179,38 @@ int fira_ban_phrases_dist(void* stream, const fira_dims* d, int R, int rows_per_
                           float* dist /* [R, vocab + sou_len + sub_len], in place */,
                           int32_t* best_id, float* best_p /* both NULL or both [R] */);
 
+/* Template-constrained search (csrc/template.hip; additive, the ABI version is unchanged): a deterministic
+ * automaton over word classes says which words may come next, in place, in the edit chain after fira_ban_phrases_dist and before
+ * fira_penalise_dist.  fira_constrain_dist's definitions: W, w(i), b = r / rows_per_commit, len = length[r] clamped to
+ * 1 .. tar_len, m = len - 1 words h_1 .. h_m emitted, and a row with gen[r, len - 1] == <eos> (1) is finished: it is not touched.
+ * The tables, at most 32 states and 32 classes:
+ *     word_class[vocab]  the class of every vocabulary id (the low five bits of the byte); an id outside [0, vocab), in the
+ *                        hypothesis or in a copy slot, has class 0
+ *     next[32 * 32]      next[s * 32 + c]: the state after a word of class c in state s, -1 for none (a value of 32 or more: -1)
+ *     need[32]           the fewest words from state s to an accepting state; 0 says that s accepts
+ *     start[R / rows_per_commit]   the start state of every commit (a value outside 0 .. 31: -1)
+ * For every other row: s = start[b], then s = next[s][class(h_p)] for p = 1 .. m, and -1 stays -1; left = tar_len - 1 - len, the
+ * positions that stay free after this step's word.  The word w is blocked iff
+ *     s == -1,   or   w == <eos> and need[s] != 0,   or   w != <eos> and (s' = next[s][class(w)]) == -1 or need[s'] > left
+ * and every entry i with w(i) blocked -- the generator id and every diff and sub-token slot that carries the word -- is set to
+ * exactly 0.0f.  Every other element keeps its bits; nothing is renormalised.  A row in which every one of the 32 classes is allowed
+ * and <eos> is free is not edited; without best_id it is not read either (so the host fills the columns of unused classes with
+ * class 0's column: the accept-everything template then costs the launch and the walk).
+ * best_id / best_p (both NULL, or both [R]): the arg-max of the row as it then stands and its value, under (value descending,
+ * index ascending) -- the order of fira_constrain_dist; NaN never wins; an all-zero row reports entry 0 with 0.  Without best_id
+ * the row is not read.
+ * The four tables are DEVICE arrays read when the kernel runs, so one captured launch serves every template; word_class and next
+ * may have any alignment (aligned dwords that overlap the table are read, no other).
+ * tar_len in 2 .. 64, vocab in 4 .. 25 600, sou_len + sub_len <= 1 024, rows_per_commit >= 1 divides R; R == 0 is a no-op.  Any row
+ * width and any 4-byte alignment of dist; vector stores only, no atomics on global memory.                                     */
+int fira_template_dist(void* stream, const fira_dims* d, int R, int rows_per_commit, const int32_t* gen /* [R, tar_len] */,
+                       const int32_t* length /* [R] */, const int32_t* sou /* [R / rows_per_commit, sou_len] */,
+                       const int32_t* sub_token /* [R / rows_per_commit, sub_len] */,
+                       const uint8_t* word_class /* device, [vocab] */, const int8_t* next /* device, [32 * 32] */,
+                       const int32_t* need /* device, [32] */, const int32_t* start /* device, [R / rows_per_commit] */,
+                       float* dist /* [R, vocab + sou_len + sub_len], in place */,
+                       int32_t* best_id, float* best_p /* both NULL or both [R] */);
+
 /* Ensemble decoding (csrc/mix.hip; additive, the ABI version is unchanged): mixes the step distributions of n_members models into
  * one, between the members' fira_decode_step calls and whatever takes a distribution next (fira_merge_dist, fira_constrain_dist,
  * fira_beam_select / fira_beam_select_scored / fira_greedy_advance).  For every element i of the [R, W] rows, in member order,
