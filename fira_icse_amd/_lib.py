@@ -189,6 +189,7 @@ SIGNATURES = {
     "fira_penalise_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fira_ban_phrases_dist": (_I, [_P, _DP, _I, _I] + [_P] * 10),
     "fira_template_dist": (_I, [_P, _DP, _I, _I] + [_P] * 11),
+    "fira_wordset_dist": (_I, [_P, _DP, _I, _I] + [_P] * 13),
     "fira_mix_dist": (_I, [_P, _I, _I, _I, C.POINTER(_P), C.POINTER(_F), _P, _P, _P]),
     "fira_pool_memory": (_I, [_P, _DP, _I, _P, _P, _P]),
     "fira_nn_search_scratch_bytes": (_Z, [_I, _I]),

@@ -727,6 +727,182 @@ class Template:
         return cls(word_class, nxt, [k for k, sub in enumerate(order) if final in sub], start)
 
 
+def looks_like_an_identifier(word: str) -> bool:
+    """The default predicate of ``WordSets.grounded``: the word contains a digit, ``_``, ``.``, ``/`` or an inner capital (a
+    capital letter after the first character) -- the shape of identifiers, file names and ticket-like tokens."""
+    return any(ch.isdigit() or ch in "_./" for ch in word) or any(ch.isupper() for ch in word[1:])
+
+
+@dataclasses.dataclass(frozen=True)
+class WordSets:
+    """Per-commit WORD SETS in the search controls (``fira_wordset_dist``): the hard and the soft word
+    controls at the scale of the vocabulary, where ``Constraints.banned`` takes 32 ids and ``Penalties.bias`` 16.  A set speaks of
+    WORDS: the generator id and every copy slot of the commit that carries it.
+
+    ``allow``: only these ids (and <eos>, always) may be written.  ``deny``: these ids may not.  ``boost``: these ids are
+    multiplied by float32(exp(float64(``boost_bias``))) at every step.  Each is None, one iterable of vocabulary ids used for
+    every commit, or a list of one iterable per commit.  ``boost_bias`` b in [-30, 30]: one number, or a list of one per commit.
+    ``ground``: one iterable of ids for every commit (a property of the vocabulary): such an id may be written only if a valid
+    copy slot of the commit carries it -- "identifier-like words only if the diff has them" (``WordSets.grounded``).
+
+    The default value holds nothing: it is inactive, and a search that is given it is the plain search.  A given ``allow`` is
+    active whatever it holds; ``deny`` and ``ground`` are active if they hold an id; ``boost`` if it holds an id and some bias is
+    not 0.  Values are checked here (``ValueError`` with the reason); what depends on the model and the batch is checked by
+    ``check`` when a ``Searcher`` takes the value.  Stored as sorted tuples, so equal values compare and hash equal.  Under an
+    active ``boost`` the value a search returns is the product of the EDITED entries taken: a score, not a probability
+    (``Searcher.score`` gives the model's probability of a message)."""
+    allow: object = None
+    deny: object = None
+    boost: object = None
+    boost_bias: object = 0.0
+    ground: object = None
+
+    MAX_BIAS, MAX_LOG_SCORE = Penalties.MAX_BIAS, Penalties.MAX_LOG_SCORE
+
+    @staticmethod
+    def _ids(ids, where):
+        out = []
+        for w in ids:
+            if isinstance(w, bool) or not isinstance(w, numbers.Integral):
+                raise ValueError("WordSets: %s: id %r is not an integer" % (where, w))
+            out.append(int(w))
+        return tuple(sorted(set(out)))
+
+    def __post_init__(self):
+        seq = Phrases._seq
+        shared = {}
+        for name in ("allow", "deny", "boost"):
+            v = getattr(self, name)
+            if v is None:
+                shared[name] = True
+                continue
+            if not seq(v):
+                raise ValueError("WordSets: %s = %r is neither an iterable of vocabulary ids nor a list of one per commit" % (name, v))
+            v = list(v)
+            per_commit = bool(v) and all(x is None or seq(x) for x in v)
+            if per_commit:
+                value = tuple(self._ids(() if x is None else x, "%s of commit %d" % (name, k)) for k, x in enumerate(v))
+            else:
+                value = self._ids(v, name)
+            shared[name] = not per_commit
+            object.__setattr__(self, name, value)
+        if self.ground is not None:
+            if not seq(self.ground):
+                raise ValueError("WordSets: ground = %r is not an iterable of vocabulary ids" % (self.ground,))
+            g = list(self.ground)
+            if any(seq(x) for x in g):
+                raise ValueError("WordSets: ground is one set for every commit (a property of the vocabulary), not one per commit")
+            object.__setattr__(self, "ground", self._ids(g, "ground"))
+        bias = self.boost_bias
+        bias_shared = not seq(bias)
+        values = []
+        for k, b in enumerate([bias] if bias_shared else list(bias)):
+            where = "boost_bias" if bias_shared else "boost_bias of commit %d" % k
+            if isinstance(b, bool) or not isinstance(b, numbers.Real):
+                raise ValueError("WordSets: %s = %r is not a number" % (where, b))
+            if not -self.MAX_BIAS <= b <= self.MAX_BIAS:      # (also refuses nan)
+                raise ValueError("WordSets: %s = %r is outside [-%g, %g]" % (where, b, self.MAX_BIAS, self.MAX_BIAS))
+            values.append(float(b))
+        object.__setattr__(self, "boost_bias", values[0] if bias_shared else tuple(values))
+        object.__setattr__(self, "_shared", dict(shared, boost_bias=bias_shared))
+
+    def _rows(self, name: str, B: int):
+        """The ids of set ``name`` for each of B commits, or None for a set that is not given."""
+        v = getattr(self, name)
+        if v is None:
+            return None
+        return [v] * B if name == "ground" or self._shared[name] else list(v)
+
+    def bias_rows(self, B: int):
+        return [self.boost_bias] * B if self._shared["boost_bias"] else list(self.boost_bias)
+
+    @property
+    def given(self):
+        """Which sets a launch gets, as the tuple of their names in the order allow, deny, boost, ground."""
+        out = []
+        if self.allow is not None:
+            out.append("allow")
+        if any(self._rows("deny", 1) or ()):
+            out.append("deny")
+        if any(self._rows("boost", 1) or ()) and any(self.bias_rows(1)):
+            out.append("boost")
+        if self.ground:
+            out.append("ground")
+        return tuple(out)
+
+    @property
+    def active(self) -> bool:
+        return bool(self.given)
+
+    def check(self, cfg, B: int) -> "WordSets":
+        """Against a model's geometry and a batch of B commits: the list lengths, every id against the vocabulary and the special
+        ids, an ``allow`` that holds nothing, and the overflow bound max(b, 0) * (tar_len - 1) <= 87 of ``Penalties``."""
+        V, T = cfg.vocab_size, cfg.tar_len
+        for name in ("allow", "deny", "boost", "boost_bias"):
+            if not self._shared[name] and len(getattr(self, name)) != B:
+                raise ValueError("WordSets: %s: %d lists for a batch of %d commits" % (name, len(getattr(self, name)), B)
+                                 if name != "boost_bias" else
+                                 "WordSets: boost_bias: %d values for a batch of %d commits" % (len(self.boost_bias), B))
+        for name in ("allow", "deny", "boost", "ground"):
+            for k, row in enumerate(self._rows(name, B) or ()):
+                where = name if name == "ground" or self._shared[name] else "%s of commit %d" % (name, k)
+                for w in row:
+                    if not 0 <= w < V:
+                        raise ValueError("WordSets: %s: id %d outside the vocabulary [0, %d)" % (where, w, V))
+                    if w in (PAD, START):
+                        raise ValueError("WordSets: %s: id %d is <pad> or <start>, which no set may hold" % (where, w))
+                    if w == EOS and name in ("deny", "ground"):
+                        raise ValueError("WordSets: %s: <eos> (id %d) cannot be in %s (Constraints.min_length holds a message "
+                                         "open)" % (where, EOS, name))
+                if name == "allow" and not row:
+                    raise ValueError("WordSets: %s: commit %d is allowed no word at all" % (where, k))
+                if name == "ground" or self._shared[name]:
+                    break                                      # (one set for every commit: checked once)
+        for k, b in enumerate(self.bias_rows(B)):
+            if max(b, 0.0) * (T - 1) > self.MAX_LOG_SCORE:
+                raise ValueError("WordSets: commit %d: boost_bias = %g times tar_len - 1 = %d exceeds %g (a message's score could "
+                                 "overflow fp32): at most %g" % (k, b, T - 1, self.MAX_LOG_SCORE, self.MAX_LOG_SCORE / (T - 1)))
+        return self
+
+    def blocks(self, w: int, commit: int, B: int) -> bool:
+        """``allow`` or ``deny`` blocks the word ``w`` for commit ``commit`` of B (``ground`` depends on the batch: not here)."""
+        allow, deny = self._rows("allow", B), self._rows("deny", B)
+        return (allow is not None and w != EOS and w not in allow[commit]) or (deny is not None and w in deny[commit])
+
+    @staticmethod
+    def pack(rows, vocab_size: int):
+        """[len(rows), ceil(vocab_size / 32)] uint32: bit w % 32 of word w / 32 set for every id w of the row."""
+        import numpy as np
+        out = np.zeros((len(rows), (vocab_size + 31) // 32), dtype=np.uint32)
+        cache = {}
+        for k, row in enumerate(rows):
+            if id(row) not in cache:
+                ids = np.asarray(row, dtype=np.int64).reshape(-1)
+                words = np.zeros(out.shape[1], dtype=np.uint32)
+                np.bitwise_or.at(words, ids >> 5, np.uint32(1) << (ids & 31).astype(np.uint32))
+                cache[id(row)] = words
+            out[k] = cache[id(row)]
+        return out
+
+    def arrays(self, B: int, vocab_size: int):
+        """The device buffers of B commits as numpy arrays: a dict with "allow" / "deny" / "boost" / "ground", each
+        [B, ceil(vocab_size / 32)] uint32 for a set in ``given`` and None otherwise, and "boost_factor" [B] float32 =
+        float32(exp(float64(b))).  No bit at or past ``vocab_size`` is set."""
+        import numpy as np
+        given = self.given
+        out = {name: self.pack(self._rows(name, B), vocab_size) if name in given else None
+               for name in ("allow", "deny", "boost", "ground")}
+        out["boost_factor"] = np.exp(np.asarray(self.bias_rows(B), dtype=np.float64)).astype(np.float32)
+        return out
+
+    @classmethod
+    def grounded(cls, words, is_identifier=looks_like_an_identifier, **sets) -> "WordSets":
+        """The value whose ``ground`` holds every id of the vocabulary list ``words`` (id = position) from UNK + 1 on whose word
+        ``is_identifier`` accepts: such a word can then be written only where the commit's diff carries it.  ``sets``: the other
+        fields."""
+        return cls(ground=[w for w, word in enumerate(words) if w > UNK and is_identifier(word)], **sets)
+
+
 class Scores(dict):
     """Result of ``Searcher.score``: a dict whose keys also read as attributes."""
 
@@ -881,6 +1057,15 @@ def _refuses_template(search):
     return refusing
 
 
+def _refuses_wordsets(search):
+    """``_refuses_phrases`` for ``wordsets=`` (``Searcher._no_wordsets``); it is not handed on."""
+    @functools.wraps(search)
+    def refusing(self, *args, wordsets=None, **kwargs):
+        Searcher._no_wordsets(search.__name__, wordsets)
+        return search(self, *args, **kwargs)
+    return refusing
+
+
 class _Loop:
     """The chunked step loop of one search over one batch, on the current stream.
 
@@ -968,7 +1153,7 @@ class _Loop:
 class Searcher:
     """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many``, ``beam`` and ``sample_search`` take five options
     that edit the step's distribution before a word is chosen (``sample_distinct`` takes the first two); ``_edit`` is the one place
-    that issues their kernels, in the order merge, prefix, constraints, banned phrases, template, penalties.  Each is off by default, and off -- None, False,
+    that issues their kernels, in the order merge, prefix, constraints, banned phrases, template, word sets, penalties.  Each is off by default, and off -- None, False,
     an inactive value, an all-empty prefix -- means the calls, keys, buffers and graphs of a search without it.
 
     ``constraints``: a ``Constraints`` value.  ``fira_constrain_dist`` zeroes the blocked words' entries of every row between
@@ -1011,7 +1196,13 @@ class Searcher:
     the automaton accepts no message that still fits, and <eos> where it does not accept, so a message of positive probability
     is one the automaton accepts.  The state is keyed by a "template" marker (the four tables are device buffers, filled on every
     call).  It does not combine with required words or items; ``sample``, ``score``, ``sample_distinct`` and ``contrastive``
-    refuse an active value."""
+    refuse an active value.
+
+    ``wordsets``: a ``WordSets`` value, the chain's sixth link: ``fira_wordset_dist`` zeroes the entries of every word its
+    ``allow``, ``deny`` and ``ground`` sets block for the row's commit and multiplies the entries of the ``boost`` words.  The state
+    is keyed by a ("wordsets", names of the given sets) marker (the sets are device buffers, filled on every call; which of them
+    a launch gets is part of a captured graph).  ``sample``, ``score``, ``sample_distinct`` and ``contrastive`` refuse an active
+    value."""
 
     def __init__(self, model: TransModel, kv_bf16: bool = False, members=(), weights=None):
         """``kv_bf16``: stream a bf16 copy of the cross-attention K|V in the step loop (FIRA_DECODE_KV_BF16: half of the
@@ -1250,6 +1441,48 @@ class Searcher:
                                      "tar_len - 1 = %d" % (b, con.min_length, T - 1))
         return template
 
+    @staticmethod
+    def _no_wordsets(what: str, wordsets):
+        if wordsets is not None and (not isinstance(wordsets, WordSets) or wordsets.active):
+            raise ValueError("%s does not take word sets (greedy, greedy_many, beam and sample_search do)" % what)
+
+    def _wordsets(self, wordsets, B: int, prefix_rows=None, require=None, items=None):
+        """None for "no word sets" (None or an inactive value: today's launches, buffers and graphs), else the ``WordSets`` value
+        checked against the model, the batch and the search's other options: no word of ``prefix_rows`` (the checked prefix),
+        of ``require`` (the checked required words) or of ``items`` (a ``Phrases`` value with required items) may be one that
+        ``allow`` or ``deny`` blocks.  Raises ``ValueError`` naming the reason; nothing is launched before.  What the host cannot
+        see -- a forced or required word that ``ground`` blocks because the commit does not carry it, a ``Template`` state
+        reachable only through blocked words -- leaves the hypothesis probability 0."""
+        if wordsets is None:
+            return None
+        if not isinstance(wordsets, WordSets):
+            raise ValueError("wordsets: expected decode.WordSets or None, got %r" % (wordsets,))
+        if not wordsets.active:
+            return None
+        wordsets.check(self.cfg, B)
+        item_rows = None if items is None else [[w for item in row for w in item] for row in items.required]
+        for what, rows in (("prefix", prefix_rows), ("required", require), ("required phrase", item_rows)):
+            for b, row in enumerate(rows or ()):
+                for w in row:
+                    if wordsets.blocks(w, b, B):
+                        raise ValueError("wordsets: commit %d: the %s word %d is blocked by allow or deny" % (b, what, w))
+        return wordsets
+
+    def _fill_wordsets(self, st, wst: WordSets, db: DeviceBatch):
+        """The checked sets into the state's device buffers (every call, like the prefix buffers), and the valid copy slots of
+        the batch: slot j is valid iff its source id is not <pad> (0) -- the rule by which ``fira_decode_begin`` forms the copy
+        head's mask (mem_valid), so a slot is valid here exactly where the step can give it mass."""
+        for name, a in wst.arrays(db.B, self.cfg.vocab_size).items():
+            if a is not None and "wst_" + name in st:
+                st["wst_" + name].copy_(torch.from_numpy(a.view("int32") if a.dtype.kind == "u" else a))
+        if "wst_slot_valid" in st:
+            ids = torch.cat([db.sou, db.sub_token], 1) if self.cfg.sub_token_len else db.sou
+            n = st["wst_slot_valid"].shape[1] * 32
+            valid = torch.zeros((db.B, n), dtype=torch.int64, device=ids.device)
+            valid[:, :ids.shape[1]] = ids != PAD
+            words = (valid.view(db.B, n // 32, 32) << torch.arange(32, device=ids.device)).sum(-1)
+            st["wst_slot_valid"].copy_(torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32))
+
     def _fill_template(self, st, tpl: Template, B: int):
         """The checked tables into the state's device buffers (every call, like the prefix buffers)."""
         for name, a in zip(("tpl_word_class", "tpl_next", "tpl_need", "tpl_start"), tpl.arrays(B, self.cfg.vocab_size)):
@@ -1308,6 +1541,11 @@ class Searcher:
         template ("template" in st): ``fira_template_dist`` zeroes the entries of the words the automaton does not admit after
         the row's hypothesis, and <eos> where it does not accept (section 6zc).  The four tables are read from st["tpl_word_class"]
         / st["tpl_next"] / st["tpl_need"] / st["tpl_start"] when the kernel runs.
+        word sets ("wordsets" in st): ``fira_wordset_dist`` zeroes the entries of the words the commit's allow / deny / ground sets
+        block and multiplies the entries of its boost set (section 6zd).  After the other hard edits, before the soft one: its one
+        multiplication is the last of its own edits.  The sets st["wst_allow"] / st["wst_deny"] / st["wst_boost"] /
+        st["wst_ground"] (those the state owns; NULL for the rest), st["wst_slot_valid"] and st["wst_boost_factor"] are read when
+        the kernel runs.
         penalise ("penalties" in st): ``fira_penalise_dist`` multiplies the entries of the words a row already holds, and of the
         commit's biased words, by their factors (section 6za).  Last: a finite non-negative factor commutes bit for bit with the
         zeroing links, and after a merge a word's mass sits on its generator entry.  The table and the bias lists are read from
@@ -1337,6 +1575,11 @@ class Searcher:
             chain.append(("fira_template_dist", lambda *b: lib.fira_template_dist(
                 s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["tpl_word_class"]),
                 _lib.ptr(st["tpl_next"]), _lib.ptr(st["tpl_need"]), _lib.ptr(st["tpl_start"]), dist, *b)))
+        if "wordsets" in st:
+            sets = [_lib.ptr(st[k]) if k in st else None for k in ("wst_allow", "wst_deny", "wst_boost", "wst_ground",
+                                                                    "wst_slot_valid", "wst_boost_factor")]
+            chain.append(("fira_wordset_dist", lambda *b: lib.fira_wordset_dist(
+                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, *sets, dist, *b)))
         if "penalties" in st:
             chain.append(("fira_penalise_dist", lambda *b: lib.fira_penalise_dist(
                 s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["count_factor"]),
@@ -1345,14 +1588,23 @@ class Searcher:
             last = best is not None and k == len(chain) - 1
             _lib.check(call(*((_lib.ptr(best[0]), _lib.ptr(best[1])) if last else (None, None))), name)
 
-    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None, ban=None, tpl=None):
+    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None, ban=None, tpl=None, wst=None):
         """What the edit chain (``_edit``) owns in a state of R rows over B commits: ``con`` always (None: no constraint);
         ``merge`` only when merging; the [R, out_len] distribution when an edit is active (``dist=True``: in any case, for the
         beam family, whose selection reads it); the banned ids with constraints; the two prefix buffers with a prefix ``rows``;
         with penalties ``pen`` the "penalties" marker, the count table [tar_len] and the bias lists [B, 16] / [B, 16] / [B]; with
         banned phrases ``ban`` the "ban-phrases" marker and the lists [B, 8, 4] / [B, 8] / [B]; with a template ``tpl`` the
-        "template" marker and the tables [vocab] uint8 / [32 * 32] int8 / [32] / [B]."""
+        "template" marker and the tables [vocab] uint8 / [32 * 32] int8 / [32] / [B]; with word sets ``wst`` the "wordsets" marker,
+        one [B, ceil(vocab / 32)] bit set for each set the value gives, the valid slots [B, ceil(slots / 32)] with ``ground`` and
+        the factors [B] with ``boost``."""
         st = dict(con=con)
+        if wst is not None:
+            cfg = self.cfg
+            st.update(wordsets=wst.given, **{"wst_" + name: i32(B, (cfg.vocab_size + 31) // 32) for name in wst.given})
+            if "ground" in wst.given:
+                st["wst_slot_valid"] = i32(B, max((cfg.sou_len + cfg.sub_token_len + 31) // 32, 1))
+            if "boost" in wst.given:
+                st["wst_boost_factor"] = f32(B)
         if tpl is not None:
             dev = self.model.device_
             st.update(template=True, tpl_word_class=torch.zeros(self.cfg.vocab_size, dtype=torch.uint8, device=dev),
@@ -1366,7 +1618,8 @@ class Searcher:
         if pen is not None:
             st.update(penalties=True, count_factor=f32(self.cfg.tar_len), bias_id=i32(B, Penalties.MAX_BIASED),
                       bias_factor=f32(B, Penalties.MAX_BIASED), n_bias=i32(B))
-        if dist or con is not None or merge or rows is not None or pen is not None or ban is not None or tpl is not None:
+        if dist or con is not None or merge or rows is not None or pen is not None or ban is not None or tpl is not None \
+                or wst is not None:
             st["dist"] = f32(R, self.cfg.out_len)
         if con is not None:
             st["banned"] = torch.tensor(list(con.banned) or [0], dtype=torch.int32, device=self.model.device_)
@@ -1418,19 +1671,22 @@ class Searcher:
 
     @staticmethod
     def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False, neighbour: bool = False,
-             penalties: bool = False, ban_phrases: bool = False, require_phrases: bool = False, template: bool = False):
+             penalties: bool = False, ban_phrases: bool = False, require_phrases: bool = False, template: bool = False,
+             wordsets=()):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
         so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
         marker only: the prefix values live in device buffers), then "require" for a search with required words (a marker
         too), then "neighbour" for a search with a neighbour (a marker: the batch and the coefficients live in device buffers),
         then "penalties" for a search with active penalties (a marker: the table and the bias lists live in device buffers),
         then "ban-phrases" / "require-phrases" for a search with an active ``Phrases`` value (markers: the lists live in device
-        buffers), then "template" for a search with an active ``Template`` (a marker: the tables live in device buffers); an
-        active BeamScoring value comes last."""
+        buffers), then "template" for a search with an active ``Template`` (a marker: the tables live in device buffers), then
+        ("wordsets", names) for a search with an active ``WordSets`` (the names of the sets it gives: which pointers a launch
+        gets is baked into a captured graph, the sets themselves live in device buffers); an active BeamScoring value comes
+        last."""
         return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + (("require",) if require else ())
                 + (("neighbour",) if neighbour else ()) + (("penalties",) if penalties else ())
                 + (("ban-phrases",) if ban_phrases else ()) + (("require-phrases",) if require_phrases else ())
-                + (("template",) if template else ())
+                + (("template",) if template else ()) + ((("wordsets", tuple(wordsets)),) if wordsets else ())
                 + ((con,) if con is not None else ()) + ((scoring,) if scoring is not None else ()))
 
     def _required_rows(self, require, B: int, beam: int, con: Optional[Constraints], scoring):
@@ -1562,7 +1818,8 @@ class Searcher:
                        "fira_greedy_advance")
 
     def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
-                     merge_copies: bool = False, prefix=None, neighbour=None, penalties=None, phrases=None, template=None) -> _Loop:
+                     merge_copies: bool = False, prefix=None, neighbour=None, penalties=None, phrases=None, template=None,
+                     wordsets=None) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  The
         active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, "penalties"][, constraints]), and so own their graphs)
         and add what ``_edit_state`` lists to the state -- the [B, out_len] distribution with any of them."""
@@ -1574,17 +1831,21 @@ class Searcher:
         pen = self._penalties(penalties, B)                  # likewise
         ban, _ = self._phrases(phrases, B, con, "greedy", rows)      # likewise
         tpl = self._template(template, B, con, rows)         # likewise
+        wst = self._wordsets(wordsets, B, rows)              # likewise
         marks = {} if tpl is None else {"template": True}    # (off: today's key, argument for argument)
+        if wst is not None:
+            marks["wordsets"] = wst.given
         if nb is None:
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B),
-                                         **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen, ban=ban, tpl=tpl))
+                                         **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen, ban=ban, tpl=tpl,
+                                                            **({} if wst is None else {"wst": wst})))
             loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, penalties=pen is not None,
                                                 ban_phrases=ban is not None, **marks), make, chunk, use_graphs)
         else:                                                # a neighbour: the state always owns the distribution
-            bare = con is None and not merge and rows is None and pen is None and ban is None and tpl is None
+            bare = con is None and not merge and rows is None and pen is None and ban is None and tpl is None and wst is None
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **({"mix_best": True} if bare else {}),
                                          **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True, pen=pen, ban=ban,
-                                                            tpl=tpl))
+                                                            tpl=tpl, **({} if wst is None else {"wst": wst})))
             loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=True,
                                                 penalties=pen is not None, ban_phrases=ban is not None, **marks), make, chunk,
                          use_graphs, nb)
@@ -1597,6 +1858,8 @@ class Searcher:
             self._fill_ban_phrases(st, ban, B)
         if tpl is not None:
             self._fill_template(st, tpl, B)
+        if wst is not None:
+            self._fill_wordsets(st, wst, db)
         return loop.start(lambda lo, hi: self._greedy_steps(st, ws, B, lo, hi), lambda: self._greedy_reset(st),
                           lambda hi: self._none_alive(st, hi))
 
@@ -1613,7 +1876,7 @@ class Searcher:
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
                merge_copies: bool = False, prefix=None, neighbour: Optional[Neighbour] = None,
                penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
-               template: Optional[Template] = None):
+               template: Optional[Template] = None, wordsets: Optional[WordSets] = None):
         """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``, ``merge_copies``,
         ``prefix`` and ``penalties`` are the class's options: with any of them the step writes its distribution instead of taking
         its fused arg-max, and the last kernel of the edit chain (``_edit``) takes the arg-max of what is left.  With active
@@ -1625,6 +1888,12 @@ class Searcher:
         is then accepted by the automaton.  A ``ValueError`` before anything is launched on what ``Template.check`` and
         ``_template`` refuse: a prefix that is no path of the automaton or leaves no room, a ``min_length`` no accepted message
         reaches.  A state that admits only words another control blocks leaves the hypothesis probability 0.
+        ``wordsets``: a ``WordSets`` value, a link of the edit chain after the template (("wordsets",
+        names of the given sets) joins the state key; the sets are device buffers, one capture for every value that gives the
+        same sets).  No word its ``allow``, ``deny`` or ``ground`` blocks is then written by a message of positive probability.
+        With an active ``boost`` the third tensor is a score, as under ``penalties``.  A ``ValueError`` before anything is launched
+        on what ``WordSets.check`` and ``_wordsets`` refuse, a prefix word that ``allow`` or ``deny`` blocks among them; a word
+        ``ground`` blocks because the commit does not carry it leaves probability 0.
 
         ``neighbour``: a ``Neighbour`` value.  Every step then also runs the model over the neighbour
         batch on the same tokens (a second workspace), folds that row into words with the neighbour's ids and mixes it into the
@@ -1636,12 +1905,12 @@ class Searcher:
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
         return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix, neighbour,
-                                                     penalties, phrases, template).run())
+                                                     penalties, phrases, template, wordsets).run())
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
                     merge_copies: bool = False, prefix=None, neighbour=None, penalties: Optional[Penalties] = None,
-                    phrases: Optional[Phrases] = None, template: Optional[Template] = None):
+                    phrases: Optional[Phrases] = None, template: Optional[Template] = None, wordsets=None):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -1662,14 +1931,25 @@ class Searcher:
         ``phrases``: one ``Phrases`` value with banned phrases for every batch (per-commit lists then need batches of one
         size), as for ``greedy``.
         ``template``: one ``Template`` value for every batch (per-commit start states then need batches of one size), as for
-        ``greedy``."""
+        ``greedy``.
+        ``wordsets``: one ``WordSets`` value for every batch, or a sequence of one value (or None) per batch, as for ``greedy``."""
         dbs = list(dbs)
         con = self._active(constraints)                      # raises before a lane starts
-        for db in dbs:
+        if wordsets is None or isinstance(wordsets, WordSets):
+            wordsets = [wordsets] * len(dbs)
+        else:
+            try:
+                wordsets = list(wordsets)
+            except TypeError:
+                raise ValueError("wordsets: expected decode.WordSets, None or one of them per batch, got %r" % (wordsets,)) from None
+            if len(wordsets) != len(dbs):
+                raise ValueError("wordsets: %d values for %d batches" % (len(wordsets), len(dbs)))
+        for db, w in zip(dbs, wordsets):
             self._penalties(penalties, db.B)                 # every batch's, before a lane starts
             if prefix is None:                               # (with prefixes: checked with each batch's, below)
                 self._phrases(phrases, db.B, con, "greedy_many")
                 self._template(template, db.B, con)
+                self._wordsets(w, db.B)
         if neighbour is not None:
             try:
                 neighbour = list(neighbour)
@@ -1689,6 +1969,8 @@ class Searcher:
             for db, p in zip(dbs, prefix):                   # every batch's, before a lane starts
                 self._phrases(phrases, db.B, con, "greedy_many", self._prefix_rows(p, db.B, con))
                 self._template(template, db.B, con, self._prefix_rows(p, db.B, con))
+            for db, p, w in zip(dbs, prefix, wordsets):
+                self._wordsets(w, db.B, self._prefix_rows(p, db.B, con))
         n_lane = max(1, min(in_flight, len(dbs)))
         if not hasattr(self, "_lanes") or len(self._lanes) < n_lane:
             streams = concurrent_streams(n_lane, self.model.device_)
@@ -1722,7 +2004,7 @@ class Searcher:
                         loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies,
                                                  None if prefix is None else prefix[nxt],
                                                  None if neighbour is None else neighbour[nxt], penalties, phrases,
-                                                 template)
+                                                 template, wordsets[nxt])
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -1783,6 +2065,7 @@ class Searcher:
                                                _lib.ptr(st["logp"]), _lib.ptr(st["alive"]), _lib.ptr(st["tok"]),
                                                _lib.ptr(st["n_alive"])), "fira_sample_advance")
 
+    @_refuses_wordsets
     @torch.no_grad()
     def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                keys=None, chunk: int = 5, use_graphs: bool = True, neighbour=None, min_p: float = 0.0, epsilon: float = 0.0,
@@ -1847,7 +2130,7 @@ class Searcher:
                       constraints: Optional[Constraints] = None, merge_copies: bool = False, prefix=None,
                       neighbour: Optional[Neighbour] = None, chunk: int = 5, use_graphs: bool = True,
                       penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
-                      template: Optional[Template] = None):
+                      template: Optional[Template] = None, wordsets: Optional[WordSets] = None):
         """``n`` sampled messages per commit, drawn from the search's EDITED distribution: what ``sample`` returns (tokens
         [B,n,T], lengths [B,n], probability [B,n], log-probability [B,n]), with every option of the searches -- ``constraints``,
         ``merge_copies``, ``prefix``, ``penalties`` (the class's options), an ensemble (``members=``) and a ``neighbour`` -- and
@@ -1869,6 +2152,7 @@ class Searcher:
         The filters and cuts are fixed in the captured launches and join the state's key with the options (``_key``); the
         prefix, the seed, the keys and the neighbour's coefficients are device values, so one capture serves all of them.
         ``template``: a ``Template`` value, as for ``greedy``.
+        ``wordsets``: a ``WordSets`` value, as for ``greedy``; with an active ``boost`` the returned values are scores.
         ``phrases``: banned phrases, as for ``greedy``.  There is no ``require=`` and no required item: banks need a beam.  A ``ValueError`` before anything is launched on a value outside its
         range, ``n`` outside 1..8, or whatever the options' own checks refuse (a neighbour with members among them)."""
         cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)     # every refusal: before anything is launched
@@ -1891,12 +2175,15 @@ class Searcher:
         pen = self._penalties(penalties, B)
         ban, _ = self._phrases(phrases, B, con, "sample_search", rows)
         tpl = self._template(template, B, con, rows)
+        wst = self._wordsets(wordsets, B, rows)
         noise_rows, fill_noise = self._noise(keys, seed, B)
         make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), **noise_rows(i32),
-                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True, pen=pen, ban=ban, tpl=tpl))
+                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True, pen=pen, ban=ban, tpl=tpl,
+                                                        **({} if wst is None else {"wst": wst})))
         key = self._key(("sample_search", B, n, temperature, top_k, top_p) + cuts, merge, con, forced=rows is not None,
                         neighbour=nb is not None, penalties=pen is not None, ban_phrases=ban is not None,
-                        **({} if tpl is None else {"template": True}))
+                        **({} if tpl is None else {"template": True}),
+                        **({} if wst is None else {"wordsets": wst.given}))
         loop = _Loop(self, db, n, key, make, chunk, use_graphs, nb)
         st, ws = loop.st, loop.ws
         fill_noise(st)
@@ -1908,6 +2195,8 @@ class Searcher:
             self._fill_ban_phrases(st, ban, B)
         if tpl is not None:
             self._fill_template(st, tpl, B)
+        if wst is not None:
+            self._fill_wordsets(st, wst, db)
         loop.start(lambda lo, hi: self._sample_search_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts),
                    lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
@@ -2046,6 +2335,7 @@ class Searcher:
             labels = torch.where(inside & (labels >= 0), labels, torch.full_like(labels, -1)).to(torch.int32)
         return cand.to(torch.int32), length.to(torch.int32), labels
 
+    @_refuses_wordsets
     @torch.no_grad()
     def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None,
               neighbour=None, penalties=None, phrases=None, template=None):
@@ -2181,7 +2471,7 @@ class Searcher:
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
              scoring: Optional[BeamScoring] = None, prefix=None, require=None, neighbour: Optional[Neighbour] = None,
              penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
-             template: Optional[Template] = None):
+             template: Optional[Template] = None, wordsets: Optional[WordSets] = None):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``,
         ``prefix`` and ``penalties`` are the class's options, one library call per step each, between the step and the selection
         (``_edit``); the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, "require"][, "neighbour"][, "penalties"]
@@ -2226,6 +2516,12 @@ class Searcher:
         accepted by the automaton.  It does not combine with ``require=`` or required items (a ``ValueError``, like a prefix
         that is no path of the automaton and a ``min_length`` no accepted message reaches).
 
+        ``wordsets``: a ``WordSets`` value, a link of the edit chain after the template (("wordsets",
+        names of the given sets) joins the state key; device buffers, one capture for every value that gives the same sets): no
+        hypothesis of positive probability then holds a word that ``allow``, ``deny`` or ``ground`` blocks for its commit.  With an
+        active ``boost`` the returned values are scores, as under ``penalties``.  A prefix word, a ``require=`` word or a word of
+        a required item that ``allow`` or ``deny`` blocks is a ``ValueError``; one that ``ground`` blocks leaves probability 0.
+
         ``neighbour``: a ``Neighbour`` value, as for ``greedy``: the neighbour batch's step over the same tokens and parents (its
         caches follow the beam's reordering), its row folded into words, ``fira_mix_neighbour`` into the beam's distribution, then
         the edit chain and the selection as ever.  It combines with every option above; "neighbour" joins the state key.
@@ -2247,10 +2543,12 @@ class Searcher:
         pen = self._penalties(penalties, B)                  # likewise
         ban, items = self._phrases(phrases, B, con, "beam", rows, beam, words, scoring)     # likewise
         tpl = self._template(template, B, con, rows, words, items)                          # likewise
+        wst = self._wordsets(wordsets, B, rows, words, items)                                # likewise
 
         def make(i32, f32):
             st = dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
-                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True, pen=pen, ban=ban, tpl=tpl))
+                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True, pen=pen, ban=ban, tpl=tpl,
+                                         **({} if wst is None else {"wst": wst})))
             if items is not None:
                 st.update({"require-phrases": True}, item_words=i32(B, Phrases.MAX_REQUIRED_WORDS),
                           item_len=i32(B, Phrases.MAX_ITEMS), n_items=i32(B), met=i32(BR))
@@ -2267,7 +2565,8 @@ class Searcher:
                                                **({} if pen is None else {"penalties": True}),
                                                **({} if ban is None else {"ban_phrases": True}),
                                                **({} if items is None else {"require_phrases": True}),
-                                               **({} if tpl is None else {"template": True})), make, chunk, use_graphs,
+                                               **({} if tpl is None else {"template": True}),
+                                               **({} if wst is None else {"wordsets": wst.given})), make, chunk, use_graphs,
                      *(() if nb is None else (nb,)))
         st, ws = loop.st, loop.ws
         if rows is not None:
@@ -2282,6 +2581,8 @@ class Searcher:
             self._fill_required_phrases(st, items, B)
         if tpl is not None:
             self._fill_template(st, tpl, B)
+        if wst is not None:
+            self._fill_wordsets(st, wst, db)
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
         res = self._family_result(loop, B, beam, ("prob",))
@@ -2306,6 +2607,7 @@ class Searcher:
                 _lib.ptr(st["G"][nxt]), _lib.ptr(st["logp"][nxt]), _lib.ptr(st["parent"])), "fira_beam_select_gumbel")
         self._family_steps(st, ws, B, n, lo, hi, select)
 
+    @_refuses_wordsets
     @torch.no_grad()
     def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
                         merge_copies: bool = True, constraints: Optional[Constraints] = None, chunk: int = 4,
@@ -2418,6 +2720,7 @@ class Searcher:
         running = (st["ended"] == 0) & (last > 0)
         return gen.long(), length.long(), torch.where(running, st["prob"][cur] * last, st["prob"][cur])
 
+    @_refuses_wordsets
     @_refuses_template
     @_refuses_phrases
     @_refuses_penalties("it already penalises degeneration")

@@ -1211,6 +1211,40 @@ int fira_template_dist(void* stream, const fira_dims* d, int R, int rows_per_com
                        float* dist /* [R, vocab + sou_len + sub_len], in place */,
                        int32_t* best_id, float* best_p /* both NULL or both [R] */);
 
+/* Per-commit word sets (csrc/wordset.hip; additive, the ABI version is unchanged): allow, deny, boost and
+ * ground, each a vocabulary-sized bit set per commit, in place, in the edit chain after fira_template_dist and before
+ * fira_penalise_dist.  fira_constrain_dist's definitions: W, w(i), b = r / rows_per_commit, len = length[r] clamped to
+ * 1 .. tar_len, and a row with gen[r, len - 1] == <eos> (1) is finished: it is not touched.
+ * allow, deny, boost, ground: each NULL (not given) or [R / rows_per_commit, ceil(vocab / 32)] uint32; bit w % 32 of word w / 32
+ * says that id w is in the set; the bits at or past vocab in the last word are ignored.
+ * slot_valid [R / rows_per_commit, ceil((sou_len + sub_len) / 32)] uint32: bit j says that copy slot j (diff positions, then
+ * sub-token positions) can be given mass by the copy head; required with ground.  boost_factor [R / rows_per_commit], finite and
+ * >= 0 (the host's promise); required with boost.
+ *     in(S, w)       S is given, 0 <= w < vocab and the bit is set
+ *     carried(b, w)  some VALID slot of commit b has the source id w
+ * For every other row the word w is blocked iff
+ *     allow is given and w != <eos> and !in(allow, w),   or   in(deny, w),   or   in(ground, w) and !carried(b, w)
+ * An id outside [0, vocab) is in no set: blocked under allow, untouched by deny and ground, never used as an index.  Every entry i
+ * with w(i) blocked -- the generator id and every diff and sub-token slot that carries the word -- is set to exactly +0.0f.  Every
+ * entry that is not blocked and has in(boost, w(i)) becomes fl32(dist[i] * boost_factor[b]): one multiplication, applied once, the
+ * last of this link's edits.  Every other element keeps its bits; nothing is renormalised.
+ * best_id / best_p (both NULL, or both [R]): the arg-max of the row as it then stands and its value, under (value descending,
+ * index ascending) -- the order of fira_constrain_dist; NaN never wins; an all-zero row reports entry 0 with 0.  Without best_id
+ * an allowed and unboosted entry is neither read nor written.
+ * Every input is a DEVICE array read when the kernel runs, so one captured launch serves every set; which sets are given (NULL or
+ * not) is part of the launch.
+ * tar_len in 2 .. 64, vocab in 4 .. 25 600, sou_len + sub_len <= 1 024, rows_per_commit >= 1 divides R; R == 0 is a no-op.  Any row
+ * width and any 4-byte alignment of dist; vector stores only, no atomics on global memory, no two threads write one address. */
+int fira_wordset_dist(void* stream, const fira_dims* d, int R, int rows_per_commit, const int32_t* gen /* [R, tar_len] */,
+                      const int32_t* length /* [R] */, const int32_t* sou /* [R / rows_per_commit, sou_len] */,
+                      const int32_t* sub_token /* [R / rows_per_commit, sub_len] */,
+                      const uint32_t* allow, const uint32_t* deny, const uint32_t* boost,
+                      const uint32_t* ground /* device, each NULL or [R / rows_per_commit, ceil(vocab / 32)] */,
+                      const uint32_t* slot_valid /* device, [R / rows_per_commit, ceil((sou_len + sub_len) / 32)] */,
+                      const float* boost_factor /* device, [R / rows_per_commit] */,
+                      float* dist /* [R, vocab + sou_len + sub_len], in place */,
+                      int32_t* best_id, float* best_p /* both NULL or both [R] */);
+
 /* Ensemble decoding (csrc/mix.hip; additive, the ABI version is unchanged): mixes the step distributions of n_members models into
  * one, between the members' fira_decode_step calls and whatever takes a distribution next (fira_merge_dist, fira_constrain_dist,
  * fira_beam_select / fira_beam_select_scored / fira_greedy_advance).  For every element i of the [R, W] rows, in member order,
