@@ -195,6 +195,9 @@ SIGNATURES = {
     "fira_nn_search_scratch_bytes": (_Z, [_I, _I]),
     "fira_nn_search": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _Z]),
     "fira_mix_neighbour": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P]),
+    "fira_knn_search_scratch_bytes": (_Z, [_I, _I, _I]),
+    "fira_knn_search": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _Z]),
+    "fira_mix_knn": (_I, [_P, _DP, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "fira_decode_begin": (_I, [_P, _DP, _BP, _P, _P, _Z, _I]),
     "fira_decode_begin_ex": (_I, [_P, _DP, _BP, _P, _P, _Z, _I, _I]),
     "fira_decode_step_ex": (_I, [_P, _DP, _P, _P, _Z, _I, _I, _I, _P, _P, _P, _P, _P, _I]),

@@ -1019,6 +1019,93 @@ class _NeighbourWs:
         self.sub = torch.zeros((B, max(cfg.sub_token_len, 1)), dtype=torch.int32, device=dev)
 
 
+@dataclasses.dataclass(frozen=True, eq=False)
+class KnnMT:
+    """Token-level retrieval (kNN-MT): ``store`` is a ``retrieve.TokenStore``.  At every step the row's
+    last hidden state (``fira_decode_hidden``) is looked up among the stored keys (``fira_knn_search``: the ``k`` nearest by
+    squared distance, ties to the lower row), and the words that followed there are mixed into the row's distribution
+    (``fira_mix_knn``): p <- (1 - ``lam``) p, then p[value_k] += ``lam`` w_k with w = softmax(-d2 / ``temperature``) over the
+    slots found.  ``exclude``: per commit of the batch an owner (commit index of the store) whose rows are left out, e.g. the
+    commit itself when it is in the store; None or -1: nothing.  ``check`` refuses a wrong value before anything is launched;
+    ``lam == 0`` is the search without the option."""
+    store: object
+    k: int = 8
+    lam: float = 0.3
+    temperature: float = 10.0
+    exclude: object = None
+
+    MAX_K = 16                                   # fira_knn_search: 1 <= K <= 16
+    WIDTH = 256
+
+    @property
+    def active(self) -> bool:
+        return self.lam != 0
+
+    def check(self, B: Optional[int] = None) -> "KnnMT":
+        if isinstance(self.k, bool) or not isinstance(self.k, numbers.Integral) or not 1 <= self.k <= self.MAX_K:
+            raise ValueError("KnnMT: k = %r outside 1..%d" % (self.k, self.MAX_K))
+        for name in ("lam", "temperature"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError("KnnMT: %s = %r is not a number" % (name, v))
+        if not 0 <= self.lam <= 1:                            # (also refuses nan)
+            raise ValueError("KnnMT: lam = %r outside [0, 1]" % (self.lam,))
+        if not 0 < self.temperature < float("inf"):
+            raise ValueError("KnnMT: temperature = %r must be finite and > 0" % (self.temperature,))
+        keys = getattr(self.store, "keys", None)
+        if keys is None or not all(hasattr(self.store, f) for f in ("key_sq", "values", "owner", "N")):
+            raise ValueError("KnnMT: store = %r is not a retrieve.TokenStore" % (self.store,))
+        if self.store.N < 1 or keys.shape[0] < 1:
+            raise ValueError("KnnMT: the store is empty")
+        if keys.dim() != 2 or keys.shape[1] != self.WIDTH:
+            raise ValueError("KnnMT: the store's keys are %s, expected [N, %d]" % (tuple(keys.shape), self.WIDTH))
+        if self.exclude is not None:
+            ex = self.exclude_rows()
+            if B is not None and len(ex) != B:
+                raise ValueError("KnnMT: %d exclude values for a batch of %d commits" % (len(ex), B))
+        return self
+
+    def exclude_rows(self) -> List[int]:
+        try:
+            ex = self.exclude.tolist() if hasattr(self.exclude, "tolist") else list(self.exclude)
+            return [-1 if e is None else int(e) for e in ex]
+        except (TypeError, ValueError):
+            raise ValueError("KnnMT: exclude = %r is not a sequence of commit indices" % (self.exclude,)) from None
+
+    def coef(self):
+        """(lam, 1 / temperature) as the float32 pair ``fira_mix_knn`` reads from the device."""
+        import numpy as np
+        return np.array([self.lam, 1.0 / float(self.temperature)], dtype=np.float64).astype(np.float32)
+
+
+class _KnnWs:
+    """What ``Searcher._begin`` hands to ``Searcher._step`` for a search with ``knn=`` in place of the one decode workspace:
+    the workspace, the store, and the static buffers of the three extra launches -- the hidden rows [R, 256], the slots found
+    idx / d2 [R, K], the search's scratch, and the device values filled on every call (coef [2], exclude [R]: one capture serves
+    every lam, temperature and exclude list)."""
+
+    def __init__(self, ws, store, R, K, dev):
+        self.ws, self.store, self.K = ws, store, K
+        self.hidden = torch.zeros((R, KnnMT.WIDTH), dtype=torch.float32, device=dev)
+        self.idx = torch.full((R, K), -1, dtype=torch.int32, device=dev)
+        self.d2 = torch.full((R, K), float("inf"), dtype=torch.float32, device=dev)
+        self.coef = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.exclude = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        need = _lib.lib().fira_knn_search_scratch_bytes(R, store.N, K)
+        if need == 0:
+            raise ValueError("knn: fira_knn_search takes no store of %d rows with K = %d" % (store.N, K))
+        self.scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+
+
+def _refuses_knn(search):
+    """``_refuses_phrases`` for ``knn=`` (``Searcher._no_knn``): None and a value with ``lam == 0`` pass; it is not handed on."""
+    @functools.wraps(search)
+    def refusing(self, *args, knn=None, **kwargs):
+        Searcher._no_knn(search.__name__, knn)
+        return search(self, *args, **kwargs)
+    return refusing
+
+
 def rank_values(scores, by: str) -> torch.Tensor:
     """The [B, n] values ``Searcher.rank`` orders candidates by (larger is better)."""
     if by == "mean_logp_word":
@@ -1263,6 +1350,18 @@ class Searcher:
         self.model.sync_params()
         db.wait_ready()
         self._begin_model(self.model, ws, db, beam)
+        if isinstance(neighbour, KnnMT):
+            # knn= (never with members or a neighbour): the static buffers of the three extra launches, keyed by the store
+            # and K, and the per-call values into the device buffers the captured launches read
+            kn, R = neighbour, db.B * beam
+            key = ("knn", db.B, beam, kn.k, id(kn.store))
+            if key not in self._ws:
+                self._ws[key] = _KnnWs(ws, kn.store, R, kn.k, self.model.device_)
+            kw = self._ws[key]
+            kw.coef.copy_(torch.from_numpy(kn.coef()))
+            ex = [-1] * db.B if kn.exclude is None else kn.exclude_rows()
+            kw.exclude.copy_(torch.tensor(ex, dtype=torch.int32).repeat_interleave(beam))
+            return kw
         if neighbour is not None:
             # a neighbour (never with members): a second workspace of the one model for the neighbour batch, its encoder pass on
             # the current stream, and the per-batch values into the static buffers the captured launches read
@@ -1300,6 +1399,19 @@ class Searcher:
                                                   _lib.ptr(best_p), self.flags), "fira_decode_step")
 
     def _step(self, ws, B, beam, step, tokens, parent, dist, best_id, best_p):
+        if isinstance(ws, _KnnWs):
+            # knn= (``ws`` is the _KnnWs of ``_begin``): the model's step into the search's ``dist``, the rows' hidden states,
+            # their K nearest stored rows, then the mix in place over ``dist`` -- which also delivers best_id / best_p
+            lib, s, dims, st, R = _lib.lib(), _lib.cur_stream(), C.byref(self.model.dims), ws.store, B * beam
+            self._step_model(self.model, ws.ws, B, beam, step, tokens, parent, dist, None, None)
+            _lib.check(lib.fira_decode_hidden(s, dims, _lib.ptr(ws.ws), ws.ws.numel(), B, beam, self.flags, _lib.ptr(ws.hidden)),
+                       "fira_decode_hidden")
+            _lib.check(lib.fira_knn_search(s, _lib.ptr(ws.hidden), R, _lib.ptr(st.keys), _lib.ptr(st.key_sq), _lib.ptr(st.owner),
+                                           _lib.ptr(ws.exclude), st.N, ws.K, _lib.ptr(ws.idx), _lib.ptr(ws.d2),
+                                           _lib.ptr(ws.scratch), ws.scratch.numel()), "fira_knn_search")
+            return _lib.check(lib.fira_mix_knn(s, dims, R, _lib.ptr(ws.idx), _lib.ptr(ws.d2), _lib.ptr(st.values), st.N, ws.K,
+                                               _lib.ptr(ws.coef), _lib.ptr(dist), _lib.ptr(best_id), _lib.ptr(best_p)),
+                              "fira_mix_knn")
         if isinstance(ws, _NeighbourWs):
             # a neighbour (``ws`` is the _NeighbourWs of ``_begin``): the input's step into the search's ``dist``, the same
             # model's step over the neighbour batch with the same tokens and parents into ``ws.q``, the neighbour's row folded
@@ -1524,6 +1636,32 @@ class Searcher:
         if neighbour is not None:
             raise ValueError("%s does not combine with a neighbour (greedy, greedy_many and beam do)" % what)
 
+    def _knn(self, knn, B: int, neighbour=None):
+        """None for "no retrieval" (None, or ``lam == 0``: today's launches, buffers and graphs), else the checked value; raises
+        before any launch."""
+        if knn is None:
+            return None
+        if not isinstance(knn, KnnMT):
+            raise ValueError("knn: expected decode.KnnMT or None, got %r" % (knn,))
+        knn.check(B)
+        if not knn.active:
+            return None
+        if self.members:
+            raise ValueError("knn: does not combine with an ensemble (members)")
+        if neighbour is not None:
+            raise ValueError("knn: does not combine with a neighbour")
+        have, want = knn.store.keys.device, torch.device(self.model.device_)
+        if have.type != want.type or (have.index is not None and want.index is not None and have.index != want.index):
+            raise ValueError("knn: the store is on %s, the model on %s" % (knn.store.keys.device, self.model.device_))
+        return knn
+
+    @staticmethod
+    def _no_knn(what: str, knn):
+        if knn is not None and not isinstance(knn, KnnMT):
+            raise ValueError("knn: expected decode.KnnMT or None, got %r" % (knn,))
+        if knn is not None and knn.check().active:
+            raise ValueError("%s does not combine with knn= (greedy, greedy_many, beam and sample_search do)" % what)
+
     def _edit(self, st, R, rows_per_commit, gen, length, best):
         """The edit chain: the kernels that edit the step's distribution st["dist"] ([R, out_len], ``rows_per_commit`` rows per
         commit) between the decoder step and the selection, for whatever the state ``st`` carries, in this order:
@@ -1672,7 +1810,7 @@ class Searcher:
     @staticmethod
     def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False, neighbour: bool = False,
              penalties: bool = False, ban_phrases: bool = False, require_phrases: bool = False, template: bool = False,
-             wordsets=()):
+             wordsets=(), knn=None):
         """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
         so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
         marker only: the prefix values live in device buffers), then "require" for a search with required words (a marker
@@ -1682,9 +1820,11 @@ class Searcher:
         buffers), then "template" for a search with an active ``Template`` (a marker: the tables live in device buffers), then
         ("wordsets", names) for a search with an active ``WordSets`` (the names of the sets it gives: which pointers a launch
         gets is baked into a captured graph, the sets themselves live in device buffers); an active BeamScoring value comes
-        last."""
+        last.  ("knn", K, the store) follows "neighbour" for a search with ``knn=`` (K, N and the store's pointers are baked into a
+        captured graph; lam, the temperature and the exclude list live in device buffers)."""
         return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + (("require",) if require else ())
-                + (("neighbour",) if neighbour else ()) + (("penalties",) if penalties else ())
+                + (("neighbour",) if neighbour else ()) + ((("knn", knn.k, id(knn.store)),) if knn is not None else ())
+                + (("penalties",) if penalties else ())
                 + (("ban-phrases",) if ban_phrases else ()) + (("require-phrases",) if require_phrases else ())
                 + (("template",) if template else ()) + ((("wordsets", tuple(wordsets)),) if wordsets else ())
                 + ((con,) if con is not None else ()) + ((scoring,) if scoring is not None else ()))
@@ -1819,7 +1959,7 @@ class Searcher:
 
     def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
                      merge_copies: bool = False, prefix=None, neighbour=None, penalties=None, phrases=None, template=None,
-                     wordsets=None) -> _Loop:
+                     wordsets=None, knn=None) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  The
         active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, "penalties"][, constraints]), and so own their graphs)
         and add what ``_edit_state`` lists to the state -- the [B, out_len] distribution with any of them."""
@@ -1828,6 +1968,7 @@ class Searcher:
         merge = bool(merge_copies)
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
         nb = self._neighbour(neighbour, B)                   # likewise
+        kn = self._knn(knn, B, nb)                           # likewise
         pen = self._penalties(penalties, B)                  # likewise
         ban, _ = self._phrases(phrases, B, con, "greedy", rows)      # likewise
         tpl = self._template(template, B, con, rows)         # likewise
@@ -1835,20 +1976,22 @@ class Searcher:
         marks = {} if tpl is None else {"template": True}    # (off: today's key, argument for argument)
         if wst is not None:
             marks["wordsets"] = wst.given
-        if nb is None:
+        if kn is not None:                                   # a second distribution is mixed in, as with a neighbour
+            marks["knn"] = kn
+        if nb is None and kn is None:
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B),
                                          **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen, ban=ban, tpl=tpl,
                                                             **({} if wst is None else {"wst": wst})))
             loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, penalties=pen is not None,
                                                 ban_phrases=ban is not None, **marks), make, chunk, use_graphs)
-        else:                                                # a neighbour: the state always owns the distribution
+        else:                                                # a neighbour or knn=: the state always owns the distribution
             bare = con is None and not merge and rows is None and pen is None and ban is None and tpl is None and wst is None
             make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **({"mix_best": True} if bare else {}),
                                          **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True, pen=pen, ban=ban,
                                                             tpl=tpl, **({} if wst is None else {"wst": wst})))
-            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=True,
+            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=nb is not None,
                                                 penalties=pen is not None, ban_phrases=ban is not None, **marks), make, chunk,
-                         use_graphs, nb)
+                         use_graphs, nb if kn is None else kn)
         st, ws = loop.st, loop.ws
         if rows is not None:
             self._fill_prefix(st, rows)
@@ -1876,7 +2019,7 @@ class Searcher:
     def greedy(self, db: DeviceBatch, chunk: int = 5, use_graphs: bool = True, constraints: Optional[Constraints] = None,
                merge_copies: bool = False, prefix=None, neighbour: Optional[Neighbour] = None,
                penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
-               template: Optional[Template] = None, wordsets: Optional[WordSets] = None):
+               template: Optional[Template] = None, wordsets: Optional[WordSets] = None, knn: Optional[KnnMT] = None):
         """Returns (tokens [B,T] int64 starting with <start>, lengths [B], probability [B]).  ``constraints``, ``merge_copies``,
         ``prefix`` and ``penalties`` are the class's options: with any of them the step writes its distribution instead of taking
         its fused arg-max, and the last kernel of the edit chain (``_edit``) takes the arg-max of what is left.  With active
@@ -1901,16 +2044,23 @@ class Searcher:
         entries taken.  It combines with the three options above; the state gains a "neighbour" key component and always owns
         a distribution.  A ``ValueError`` before anything is launched on a wrong value or an ensemble.
 
+        ``knn``: a ``KnnMT`` value.  Every step then also takes the rows' last hidden states
+        (``fira_decode_hidden``), finds their K nearest rows in the token store (``fira_knn_search``) and mixes the words that
+        followed there into the step's distribution (``fira_mix_knn``) ahead of the edit chain; the returned probability is the
+        product of the mixed entries taken.  ("knn", K, the store) joins the state key; lam, the temperature and the exclude
+        list are device values.  None or ``lam == 0``: the search without it.  A ``ValueError`` before anything is launched on
+        what ``KnnMT.check`` refuses, an ensemble or a neighbour.
+
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
         return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix, neighbour,
-                                                     penalties, phrases, template, wordsets).run())
+                                                     penalties, phrases, template, wordsets, knn).run())
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
                     merge_copies: bool = False, prefix=None, neighbour=None, penalties: Optional[Penalties] = None,
-                    phrases: Optional[Phrases] = None, template: Optional[Template] = None, wordsets=None):
+                    phrases: Optional[Phrases] = None, template: Optional[Template] = None, wordsets=None, knn=None):
         """Greedy search over a sequence of batches with ``in_flight`` of them on the GPU at once, each on its own stream
         (its own workspace, hypothesis state and captured graphs); results are returned in the order of ``dbs``.
 
@@ -1932,9 +2082,22 @@ class Searcher:
         size), as for ``greedy``.
         ``template``: one ``Template`` value for every batch (per-commit start states then need batches of one size), as for
         ``greedy``.
-        ``wordsets``: one ``WordSets`` value for every batch, or a sequence of one value (or None) per batch, as for ``greedy``."""
+        ``wordsets``: one ``WordSets`` value for every batch, or a sequence of one value (or None) per batch, as for ``greedy``.
+        ``knn``: one ``KnnMT`` value for every batch (an exclude list then needs batches of one size), or a sequence of one value
+        (or None) per batch, as for ``greedy``."""
         dbs = list(dbs)
         con = self._active(constraints)                      # raises before a lane starts
+        if knn is None or isinstance(knn, KnnMT):
+            knn = [knn] * len(dbs)
+        else:
+            try:
+                knn = list(knn)
+            except TypeError:
+                raise ValueError("knn: expected decode.KnnMT, None or one of them per batch, got %r" % (knn,)) from None
+            if len(knn) != len(dbs):
+                raise ValueError("knn: %d values for %d batches" % (len(knn), len(dbs)))
+        for db, kn in zip(dbs, knn):
+            self._knn(kn, db.B)                              # every batch's, before a lane starts
         if wordsets is None or isinstance(wordsets, WordSets):
             wordsets = [wordsets] * len(dbs)
         else:
@@ -1957,8 +2120,8 @@ class Searcher:
                 raise ValueError("neighbour: expected one Neighbour per batch, got %r" % (neighbour,)) from None
             if len(neighbour) != len(dbs):
                 raise ValueError("neighbour: %d values for %d batches" % (len(neighbour), len(dbs)))
-            for db, nb in zip(dbs, neighbour):
-                self._neighbour(nb, db.B)                    # every batch's, before a lane starts
+            for db, nb, kn in zip(dbs, neighbour, knn):
+                self._knn(kn, db.B, self._neighbour(nb, db.B))       # every batch's, before a lane starts
         if prefix is not None:
             try:
                 prefix = list(prefix)
@@ -2004,7 +2167,7 @@ class Searcher:
                         loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies,
                                                  None if prefix is None else prefix[nxt],
                                                  None if neighbour is None else neighbour[nxt], penalties, phrases,
-                                                 template, wordsets[nxt])
+                                                 template, wordsets[nxt], knn[nxt])
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -2065,6 +2228,7 @@ class Searcher:
                                                _lib.ptr(st["logp"]), _lib.ptr(st["alive"]), _lib.ptr(st["tok"]),
                                                _lib.ptr(st["n_alive"])), "fira_sample_advance")
 
+    @_refuses_knn
     @_refuses_wordsets
     @torch.no_grad()
     def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
@@ -2130,7 +2294,7 @@ class Searcher:
                       constraints: Optional[Constraints] = None, merge_copies: bool = False, prefix=None,
                       neighbour: Optional[Neighbour] = None, chunk: int = 5, use_graphs: bool = True,
                       penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
-                      template: Optional[Template] = None, wordsets: Optional[WordSets] = None):
+                      template: Optional[Template] = None, wordsets: Optional[WordSets] = None, knn: Optional[KnnMT] = None):
         """``n`` sampled messages per commit, drawn from the search's EDITED distribution: what ``sample`` returns (tokens
         [B,n,T], lengths [B,n], probability [B,n], log-probability [B,n]), with every option of the searches -- ``constraints``,
         ``merge_copies``, ``prefix``, ``penalties`` (the class's options), an ensemble (``members=``) and a ``neighbour`` -- and
@@ -2153,6 +2317,7 @@ class Searcher:
         prefix, the seed, the keys and the neighbour's coefficients are device values, so one capture serves all of them.
         ``template``: a ``Template`` value, as for ``greedy``.
         ``wordsets``: a ``WordSets`` value, as for ``greedy``; with an active ``boost`` the returned values are scores.
+        ``knn``: a ``KnnMT`` value, as for ``greedy``: the returned probabilities are the mixed values of the entries taken.
         ``phrases``: banned phrases, as for ``greedy``.  There is no ``require=`` and no required item: banks need a beam.  A ``ValueError`` before anything is launched on a value outside its
         range, ``n`` outside 1..8, or whatever the options' own checks refuse (a neighbour with members among them)."""
         cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)     # every refusal: before anything is launched
@@ -2172,6 +2337,7 @@ class Searcher:
         merge = bool(merge_copies)
         rows = self._prefix_rows(prefix, B, con)
         nb = self._neighbour(neighbour, B)
+        kn = self._knn(knn, B, nb)
         pen = self._penalties(penalties, B)
         ban, _ = self._phrases(phrases, B, con, "sample_search", rows)
         tpl = self._template(template, B, con, rows)
@@ -2183,8 +2349,8 @@ class Searcher:
         key = self._key(("sample_search", B, n, temperature, top_k, top_p) + cuts, merge, con, forced=rows is not None,
                         neighbour=nb is not None, penalties=pen is not None, ban_phrases=ban is not None,
                         **({} if tpl is None else {"template": True}),
-                        **({} if wst is None else {"wordsets": wst.given}))
-        loop = _Loop(self, db, n, key, make, chunk, use_graphs, nb)
+                        **({} if wst is None else {"wordsets": wst.given}), **({} if kn is None else {"knn": kn}))
+        loop = _Loop(self, db, n, key, make, chunk, use_graphs, nb if kn is None else kn)
         st, ws = loop.st, loop.ws
         fill_noise(st)
         if rows is not None:
@@ -2335,6 +2501,7 @@ class Searcher:
             labels = torch.where(inside & (labels >= 0), labels, torch.full_like(labels, -1)).to(torch.int32)
         return cand.to(torch.int32), length.to(torch.int32), labels
 
+    @_refuses_knn
     @_refuses_wordsets
     @torch.no_grad()
     def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None,
@@ -2471,7 +2638,7 @@ class Searcher:
              constraints: Optional[Constraints] = None, merge_copies: bool = False,
              scoring: Optional[BeamScoring] = None, prefix=None, require=None, neighbour: Optional[Neighbour] = None,
              penalties: Optional[Penalties] = None, phrases: Optional[Phrases] = None,
-             template: Optional[Template] = None, wordsets: Optional[WordSets] = None):
+             template: Optional[Template] = None, wordsets: Optional[WordSets] = None, knn: Optional[KnnMT] = None):
         """Returns (hypotheses [B,beam,T] int64, lengths [B,beam], probabilities [B,beam]).  ``constraints``, ``merge_copies``,
         ``prefix`` and ``penalties`` are the class's options, one library call per step each, between the step and the selection
         (``_edit``); the state is keyed ("beam", B, beam[, "merge"][, "prefix"][, "require"][, "neighbour"][, "penalties"]
@@ -2526,6 +2693,10 @@ class Searcher:
         caches follow the beam's reordering), its row folded into words, ``fira_mix_neighbour`` into the beam's distribution, then
         the edit chain and the selection as ever.  It combines with every option above; "neighbour" joins the state key.
 
+        ``knn``: a ``KnnMT`` value, as for ``greedy``: every (commit, slot) row's hidden state is looked up (a commit's exclude
+        value holds for all its rows), ``fira_mix_knn`` over the beam's distribution, then the edit chain and the selection as
+        ever.  It combines with every option above but a neighbour; ("knn", K, the store) joins the state key.
+
         Per step, with every option off: fira_beam_prepare, fira_decode_step, fira_beam_select (csrc/beam.hip) -- three library
         calls, no torch op and no host round trip; the loop is captured into hipGraphs of ``chunk`` steps per (batch, beam)
         shape, and the ``done`` latch is read back between chunks (run_model.py:276-279)."""
@@ -2540,6 +2711,7 @@ class Searcher:
         rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
         words = self._required_rows(require, B, beam, con, scoring)   # likewise
         nb = self._neighbour(neighbour, B)                   # likewise
+        kn = self._knn(knn, B, nb)                           # likewise
         pen = self._penalties(penalties, B)                  # likewise
         ban, items = self._phrases(phrases, B, con, "beam", rows, beam, words, scoring)     # likewise
         tpl = self._template(template, B, con, rows, words, items)                          # likewise
@@ -2566,8 +2738,9 @@ class Searcher:
                                                **({} if ban is None else {"ban_phrases": True}),
                                                **({} if items is None else {"require_phrases": True}),
                                                **({} if tpl is None else {"template": True}),
-                                               **({} if wst is None else {"wordsets": wst.given})), make, chunk, use_graphs,
-                     *(() if nb is None else (nb,)))
+                                               **({} if wst is None else {"wordsets": wst.given}),
+                                               **({} if kn is None else {"knn": kn})), make, chunk, use_graphs,
+                     *(() if nb is None and kn is None else (nb if kn is None else kn,)))
         st, ws = loop.st, loop.ws
         if rows is not None:
             self._fill_prefix(st, rows)
@@ -2607,6 +2780,7 @@ class Searcher:
                 _lib.ptr(st["G"][nxt]), _lib.ptr(st["logp"][nxt]), _lib.ptr(st["parent"])), "fira_beam_select_gumbel")
         self._family_steps(st, ws, B, n, lo, hi, select)
 
+    @_refuses_knn
     @_refuses_wordsets
     @torch.no_grad()
     def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
@@ -2720,6 +2894,7 @@ class Searcher:
         running = (st["ended"] == 0) & (last > 0)
         return gen.long(), length.long(), torch.where(running, st["prob"][cur] * last, st["prob"][cur])
 
+    @_refuses_knn
     @_refuses_wordsets
     @_refuses_template
     @_refuses_phrases

@@ -1312,6 +1312,45 @@ int fira_mix_neighbour(void* stream, const fira_dims* d, int R, int rows_per_com
                        float* dist /* [R, vocab + sou_len + sub_len], in place */,
                        int32_t* best_id, float* best_p /* both NULL or both [R] */);
 
+/* Token-level retrieval for the search: kNN-MT (Khandelwal et al., ICLR 2021; the numpy statement:
+ * tests/knn_ref.py).  Additive, the ABI version is unchanged.  The store holds one row per training token: keys [N, 256] (the
+ * decoder's last hidden state, fira_decode_hidden, before that token was written), key_sq [N] (the row's sum of squares in
+ * ascending column order, every operation rounded to fp32), values [N] (the vocabulary id written there) and owner [N] (the
+ * commit the row comes from).
+ *
+ *   fira_knn_search : for each of R >= 0 queries Q[r] the K (1..16) stored rows with the smallest
+ *         s_j = key_sq[j] - 2 <Q[r], keys[j]>                                  (ties: the lowest j; NaN never wins)
+ *     over the rows with owner[j] != exclude[r] (owner NULL, exclude NULL or exclude[r] = -1: every row), best first:
+ *         idx_out[r, k] = j        d2_out[r, k] = max(0, q_sq[r] + s_j)        q_sq as key_sq, over Q[r]
+ *     and idx = -1, d2 = +inf in the slots past the number of admissible rows.  The product is one ordered fp32 chain over
+ *     k = 0 .. 255 in a fixed permutation that does not depend on j (fira_nn_search's), so identical keys tie exactly.  One pass
+ *     over the store serves a block of up to 64 queries (tiles of 16 rows x the block's queries on the fp32 matrix cores, the
+ *     queries in LDS, a partial top-K per query and workgroup); a second launch merges the partials in the same order.  No
+ *     [R, N] matrix touches memory.  N <= 8 388 608; row offsets are size_t.  exclude (DEVICE [R]) is read when the kernel
+ *     runs.  scratch: fira_knn_search_scratch_bytes(R, N, K) bytes (0 for R = 0 and for arguments fira_knn_search refuses),
+ *     8-byte aligned.  Refused with the reason in fira_last_error() and nothing launched: R < 0, N <= 0, N above the limit, K
+ *     outside 1..16, exclude without owner, a null or misaligned pointer (Q and keys 16-byte aligned), a scratch that is too
+ *     small.  R == 0 is a no-op.  No global atomics, vector stores only, capturable.
+ *
+ *   fira_mix_knn : between fira_decode_step (and fira_decode_hidden + fira_knn_search) and the edit chain.  W = vocab + sou_len +
+ *     sub_len; (lam, inv_T) = coef[0..1], a DEVICE array read when the kernel runs (one captured launch serves every value).
+ *     Over the slots with 0 <= idx[r, k] < N (the others are void):
+ *         w_k = expf(-(d2[r, k] - d2[r, 0]) * inv_T) / (the sum of these over the non-void slots, ascending k)
+ *         dist[r, i] = (1 - lam) * dist[r, i]                                  for every i
+ *         dist[r, values[idx[r, k]]] += lam * w_k                              for k = 0 .. K - 1, in this order
+ *     every multiply and add rounded to fp32 on its own; nothing is renormalised (the weights sum to 1).  lam == 0, and a row
+ *     whose slots are all void: no element of the row is written.  best_id / best_p (both NULL, or both [R]): the arg-max of
+ *     the row AS STORED and its value, in the order of fira_mix_dist.  Geometry limits of fira_merge_dist; any 4-byte alignment
+ *     of dist; R == 0 is a no-op.                                                                                                 */
+size_t fira_knn_search_scratch_bytes(int R, int N, int K);
+int fira_knn_search(void* stream, const float* Q /* [R, 256] */, int R, const float* keys /* [N, 256] */,
+                    const float* key_sq /* [N] */, const int32_t* owner /* [N] or NULL */,
+                    const int32_t* exclude /* device [R] or NULL */, int N, int K, int32_t* idx_out /* [R, K] */,
+                    float* d2_out /* [R, K] */, void* scratch, size_t scratch_bytes);
+int fira_mix_knn(void* stream, const fira_dims* d, int R, const int32_t* idx /* [R, K] */, const float* d2 /* [R, K] */,
+                 const int32_t* values /* [N] */, int N, int K, const float* coef /* device [2]: lam, inv_T */,
+                 float* dist /* [R, vocab + sou_len + sub_len], in place */, int32_t* best_id, float* best_p /* both NULL or both [R] */);
+
 /* On-device sampling of candidate messages (temperature, top-k, top-p).  Workspace: fira_decode_begin_ex /
  * fira_decode_workspace_bytes_ex with n_beam = n_sample (1..8) and the same flags (FIRA_DECODE_KV_BF16 allowed).
  *   fira_decode_step_sample : fira_decode_step_ex for the B * n_sample rows (row r = commit r / n_sample, sample
