@@ -183,6 +183,8 @@ SIGNATURES = {
     "fira_mbr_bleu_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "fira_dev_rouge_l_stats": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "fira_mbr_rouge_l_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "fira_dev_meteor_stats": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "fira_mbr_meteor_stats": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P]),
     "fira_constrain_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P]),
     "fira_merge_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P]),
     "fira_force_dist": (_I, [_P, _DP, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfira_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_bf16.hip", "gemm_wgrad_panel.hip", "gemm_bf16_panel.hip", "gemm_small.hip", "spmm.hip", "spmm_dense.hip", "gcn_fused.hip", "comb_fused.hip", "head_x3.hip", "rowops.hip", "attention.hip", "copyhead.hip", "gradnorm.hip", "beam.hip", "beam_score.hip", "beam_gumbel.hip", "beam_require.hip", "beam_phrase.hip", "contrastive.hip", "sample.hip", "sample_row.hip", "score.hip", "bleu.hip", "rouge.hip", "constrain.hip", "merge.hip", "force.hip", "phrase.hip", "template.hip", "wordset.hip", "penalise.hip", "mix.hip", "retrieve.hip", "knn.hip", "ema.hip", "engine.hip", "layout.cpp", "hostlists.cpp", "lr_schedule.cpp"]
+SOURCES = ["gemm_f32.hip", "gemm_bf16.hip", "gemm_wgrad_panel.hip", "gemm_bf16_panel.hip", "gemm_small.hip", "spmm.hip", "spmm_dense.hip", "gcn_fused.hip", "comb_fused.hip", "head_x3.hip", "rowops.hip", "attention.hip", "copyhead.hip", "gradnorm.hip", "beam.hip", "beam_score.hip", "beam_gumbel.hip", "beam_require.hip", "beam_phrase.hip", "contrastive.hip", "sample.hip", "sample_row.hip", "score.hip", "bleu.hip", "rouge.hip", "meteor.hip", "constrain.hip", "merge.hip", "force.hip", "phrase.hip", "template.hip", "wordset.hip", "penalise.hip", "mix.hip", "retrieve.hip", "knn.hip", "ema.hip", "engine.hip", "layout.cpp", "hostlists.cpp", "lr_schedule.cpp"]
 HEADERS = ["adam_rows.h", "common.h", "decode_row.h", "engine.h", "epilogue.h", "message.h", "mfma_frag.h", "sampler_row.h", "x3.h", os.path.join("..", "..", "include", "fira_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 

@@ -2375,7 +2375,7 @@ class Searcher:
     # ------------------------------------------------------------------ minimum-Bayes-risk pick by expected sentence BLEU
     MBR_MAX_N, MBR_MAX_T = 32, 64
 
-    def mbr(self, tokens, lengths, logp=None, utility="bleu"):
+    def mbr(self, tokens, lengths, logp=None, utility="bleu", classes=None):
         """Minimum-Bayes-risk selection among candidate messages: the candidates of a commit are taken as draws from the model
         and the one with the highest mean sentence BLEU (method 2) against the others wins.  ``tokens`` [B, n, T] vocabulary
         ids and ``lengths`` [B, n] as ``sample`` returns them (or several ``sample`` calls concatenated along n), 1 <= n <= 32,
@@ -2389,10 +2389,31 @@ class Searcher:
 
         ``utility="rouge_l"`` takes sentence-level ROUGE-L (``metrics.rouge_l``: in-order overlap at any distance) in place of
         BLEU: the same messages, the same checks, ``fira_mbr_rouge_l_stats`` as the one launch (4 integers per pair), the
-        utilities ``==`` the mean of ``metrics.rouge_l`` on the words.  Any other ``utility`` is a ValueError."""
+        utilities ``==`` the mean of ``metrics.rouge_l`` on the words.
+
+        ``utility="meteor_exact"`` takes ``metrics.meteor_exact`` -- NLTK's METEOR alignment and score (alpha 0.9, beta 3,
+        gamma 0.5: recall-weighted unigram matches with a fragmentation penalty) WITHOUT its stem and WordNet stages, so not
+        the paper's METEOR and not checked against NLTK -- through ``fira_mbr_meteor_stats`` as the one launch (4 integers per
+        pair).  ``classes`` (this utility only): an integer tensor or sequence of length ``cfg.vocab_size``; ids of equal class
+        match in a second stage after the equal ids (the caller's stems or synonym sets; the project ships none).  A wrong
+        length, a non-integer dtype or ``classes`` with another utility is a ValueError before anything is launched.  Any other
+        ``utility`` is a ValueError."""
         from . import metrics, ops
         if utility not in metrics.MBR_UTILITIES:
             raise ValueError("utility: %r is not one of %s" % (utility, ", ".join(metrics.MBR_UTILITIES)))
+        if classes is not None:
+            if utility != "meteor_exact":
+                raise ValueError("classes: only utility=\"meteor_exact\" takes a class table, not %r" % (utility,))
+            classes = torch.as_tensor(classes)
+            if classes.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+                raise ValueError("classes: expected integers, got %s" % classes.dtype)
+            if tuple(classes.shape) != (self.cfg.vocab_size,):
+                raise ValueError("classes: shape %s, expected (%d,) -- one class per vocabulary id"
+                                 % (tuple(classes.shape), self.cfg.vocab_size))
+            if classes.dtype == torch.int64 and classes.numel():
+                lo, hi = torch.aminmax(classes)
+                if int(lo) < -(1 << 31) or int(hi) >= 1 << 31:
+                    raise ValueError("classes: class outside the int32 range")
         if not (torch.is_tensor(tokens) and torch.is_tensor(lengths)):
             tokens, lengths = torch.as_tensor(tokens), torch.as_tensor(lengths)
         if tokens.dim() != 3:
@@ -2420,8 +2441,11 @@ class Searcher:
             if int(lo) < -(1 << 31) or int(hi) >= 1 << 31:
                 raise ValueError("tokens: id outside the int32 range")
         lengths = lengths.clamp(min=0, max=T)                 # (the message ends at min(length, T) anyway)
-        launch = ops.mbr_bleu_stats if utility == "bleu" else ops.mbr_rouge_l_stats
-        stats = launch(tokens.to(torch.int32).contiguous(), lengths.to(torch.int32).contiguous())
+        tokens, lengths = tokens.to(torch.int32).contiguous(), lengths.to(torch.int32).contiguous()
+        if utility == "meteor_exact":
+            stats = ops.mbr_meteor_stats(tokens, lengths, None if classes is None else classes.to(dev, torch.int32).contiguous())
+        else:
+            stats = (ops.mbr_bleu_stats if utility == "bleu" else ops.mbr_rouge_l_stats)(tokens, lengths)
         util = metrics.mbr_utilities(stats.cpu(), utility)
         pick = metrics.mbr_pick(util, None if logp is None else logp.detach().cpu())
         return pick, torch.tensor(util, dtype=torch.float64).reshape(B, n)

@@ -19,6 +19,7 @@ from .parallel import shard_indices
 
 _STAT_COLS = 12
 _ROUGE_COLS = 4
+_METEOR_COLS = 4
 
 
 def check_vocabulary(r_vocab: Dict[int, str], vocab_size: int) -> None:
@@ -65,11 +66,18 @@ class DevEvaluator:
     on the device ``fira_dev_rouge_l_stats`` on the same ids, 16 more bytes per commit in the pass-wide buffer and the same one
     copy back) and leave the values in ``last_rouge_l``, per commit in shard order.  A second reported figure only: model
     selection, the ``dev_output`` lines and the return values are the BLEU ones either way.
+
+    ``meteor_exact=True``: the same for ``metrics.meteor_exact`` (NLTK's METEOR alignment and score without its stem and WordNet
+    stages -- not the paper's METEOR): ``fira_dev_meteor_stats`` on the device, 16 more bytes per commit behind the ROUGE-L
+    block, the values in ``last_meteor_exact``.  ``meteor_classes`` (needs ``meteor_exact=True``): integers, one per vocabulary
+    id; words of equal class match in a second stage on both passes (the host looks the class of a word up through
+    ``r_vocab``; a hypothesis ``<unkm>`` has none).  A third reported figure only.
     """
 
     def __init__(self, model, store, cfg: FiraConfig, r_vocab: Dict[int, str], var_maps: Sequence[Dict[str, str]],
                  valid_index: Sequence[int], rank: int = 0, world: int = 1,
-                 ids_fn: Optional[Callable] = None, device=None, rouge_l: bool = False):
+                 ids_fn: Optional[Callable] = None, device=None, rouge_l: bool = False, meteor_exact: bool = False,
+                 meteor_classes=None):
         self.model, self.store, self.cfg = model, store, cfg
         self.r_vocab, self.var_maps, self.valid_index = r_vocab, var_maps, valid_index
         self.rank, self.world = rank, world
@@ -84,8 +92,24 @@ class DevEvaluator:
         self.last_scores: List[float] = []       # per-commit scores of the latest pass, in shard order
         self.rouge_l = bool(rouge_l)
         self.last_rouge_l: List[float] = []      # per-commit ROUGE-L of the latest pass (rouge_l=True), in shard order
+        self.meteor_exact = bool(meteor_exact)
+        self.last_meteor_exact: List[float] = []     # per-commit meteor_exact of the latest pass (meteor_exact=True)
+        self.meteor_classes = None               # int32 [vocab_size] on the host, or None
+        if meteor_classes is not None:
+            if not self.meteor_exact:
+                raise ValueError("meteor_classes: needs meteor_exact=True")
+            table = torch.as_tensor(meteor_classes)
+            if table.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+                raise ValueError("meteor_classes: expected integers, got %s" % table.dtype)
+            if tuple(table.shape) != (cfg.vocab_size,):
+                raise ValueError("meteor_classes: shape %s, expected (%d,)" % (tuple(table.shape), cfg.vocab_size))
+            table = table.detach().cpu().long()
+            if table.numel() and (int(table.min()) < -(1 << 31) or int(table.max()) >= 1 << 31):
+                raise ValueError("meteor_classes: class outside the int32 range")
+            self.meteor_classes = table.to(torch.int32)
         self._batches = None                     # resident DeviceBatches (device_pass)
-        self._out = None                         # [n_mine, 12 + T (+ 4)] int32: stats | hyp (| ROUGE-L stats) of one pass
+        self._out = None                         # [n_mine, 12 + T (+ 4) (+ 4)] int32: stats | hyp (| ROUGE-L) (| METEOR) of one pass
+        self._classes_dev = None                 # meteor_classes on the device (device_pass)
 
     def _batch(self, idx):
         from .model import DeviceBatch
@@ -101,7 +125,10 @@ class DevEvaluator:
     @torch.no_grad()
     def host_pass(self):
         cfg, store = self.cfg, self.store
-        lines, total, scores, rouge = [], 0.0, [], []
+        lines, total, scores, rouge, meteor = [], 0.0, [], [], []
+        word_class = None
+        if self.meteor_classes is not None:      # the class of a WORD; the emoji a hypothesis <unkm> is written as has none
+            word_class = {self.r_vocab[i]: c for i, c in enumerate(self.meteor_classes.tolist()) if i in self.r_vocab}
         for lo in range(0, len(self.mine), self.bs):
             idx = self.mine[lo:lo + self.bs]
             ids = self.ids_fn(self._batch(idx)).cpu().tolist()
@@ -116,9 +143,12 @@ class DevEvaluator:
                 scores.append(b)
                 if self.rouge_l:
                     rouge.append(metrics.rouge_l(ref, hyp))
+                if self.meteor_exact:
+                    meteor.append(metrics.meteor_exact(ref, hyp, word_class))
                 lines.append(self._line(i, hyp, b))
         self.last_scores = scores
         self.last_rouge_l = rouge
+        self.last_meteor_exact = meteor
         return total, lambda: lines
 
     # ------------------------------------------------------------------------------ the device pass
@@ -129,8 +159,11 @@ class DevEvaluator:
         if no_eos.size:                          # (the host pass raises ValueError from list.index on such a commit)
             raise ValueError("device dev pass: valid commit %d has no <eos> in its target" % self.mine[int(no_eos[0])])
         self._batches = [self._batch(self.mine[lo:lo + self.bs]) for lo in range(0, len(self.mine), self.bs)]
-        cols = _STAT_COLS + self.cfg.tar_len + (_ROUGE_COLS if self.rouge_l else 0)
+        cols = (_STAT_COLS + self.cfg.tar_len + (_ROUGE_COLS if self.rouge_l else 0)
+                + (_METEOR_COLS if self.meteor_exact else 0))
         self._out = torch.empty((len(self.mine) * cols,), dtype=torch.int32, device=self.device)
+        if self.meteor_classes is not None:
+            self._classes_dev = self.meteor_classes.to(self.device)
 
     @property
     def resident_bytes(self) -> int:
@@ -147,7 +180,9 @@ class DevEvaluator:
             self._build_resident()
         stats = self._out[:n * _STAT_COLS].view(n, _STAT_COLS)
         hyp = self._out[n * _STAT_COLS:n * (_STAT_COLS + T)].view(n, T)
-        rouge = self._out[n * (_STAT_COLS + T):].view(n, _ROUGE_COLS) if self.rouge_l else None
+        r_end = n * (_STAT_COLS + T + (_ROUGE_COLS if self.rouge_l else 0))
+        rouge = self._out[n * (_STAT_COLS + T):r_end].view(n, _ROUGE_COLS) if self.rouge_l else None
+        meteor = self._out[r_end:].view(n, _METEOR_COLS) if self.meteor_exact else None
         off = 0
         for db in self._batches:
             ids = self.ids_fn(db)
@@ -156,6 +191,9 @@ class DevEvaluator:
                                stats=stats[off:off + db.B])
             if self.rouge_l:
                 ops.dev_rouge_l_stats(ids, db.sou, db.sub_token, db.tar, cfg.vocab_size, stats=rouge[off:off + db.B])
+            if self.meteor_exact:
+                ops.dev_meteor_stats(ids, db.sou, db.sub_token, db.tar, cfg.vocab_size, classes=self._classes_dev,
+                                     stats=meteor[off:off + db.B])
             off += db.B
         host = self._out.cpu()                   # the pass's one copy back and its one synchronisation
         st = host[:n * _STAT_COLS].view(n, _STAT_COLS).tolist()
@@ -166,7 +204,9 @@ class DevEvaluator:
             scores.append(b)
         self.last_scores = scores
         self.last_rouge_l = ([metrics.rouge_l_from_stats(r[0], r[1], r[2])
-                              for r in host[n * (_STAT_COLS + T):].view(n, _ROUGE_COLS).tolist()] if self.rouge_l else [])
+                              for r in host[n * (_STAT_COLS + T):r_end].view(n, _ROUGE_COLS).tolist()] if self.rouge_l else [])
+        self.last_meteor_exact = ([metrics.meteor_exact_from_stats(r[0], r[1], r[2], r[3])
+                                   for r in host[r_end:].view(n, _METEOR_COLS).tolist()] if self.meteor_exact else [])
         hyp_host = host[n * _STAT_COLS:n * (_STAT_COLS + T)].view(n, T)
 
         def lines():

@@ -11,6 +11,11 @@
   common subsequence of two word lists.  The reference computes its ROUGE column by calling the ``sumeval`` command-line tool
   (Metrics/Rouge.py); that tool is not available here, so identity with ``sumeval r-nl`` has NOT been checked (its tokenisation
   and stop-word handling may differ) and no claim against the paper's 21.58 is made.
+* ``meteor_exact`` / ``meteor_exact_corpus``: the alignment and the score of NLTK's ``meteor_score`` (alpha = 0.9, beta = 3,
+  gamma = 0.5), which the reference calls (Metrics/Meteor.py), WITHOUT its Porter-stem and WordNet-synonym stages: words match
+  when they are equal, and then, only if the caller supplies ``classes``, when they have the same class.  The project ships no
+  stemmer and no synonym table.  No figure is comparable with the paper's METEOR column, and identity with NLTK has NOT been
+  checked (NLTK is absent).
 """
 from __future__ import annotations
 
@@ -175,7 +180,94 @@ def rouge_l_corpus(references: Iterable[str], predictions: Iterable[str]) -> flo
     return 100.0 * math.fsum(rouge_l(r.split(), p.split()) for r, p in zip(refs, preds)) / len(refs)
 
 
-MBR_UTILITIES = ("bleu", "rouge_l")
+def meteor_exact_from_stats(m: int, chunks: int, hyp_len: int, ref_len: int) -> float:
+    """NLTK's METEOR score (alpha = 0.9, beta = 3, gamma = 0.5) from the four integers of an alignment: ``m`` matched word
+    pairs in ``chunks`` chunks, the two lengths.  ``(1 - pen) * fmean`` with ``P = m / hyp_len``, ``R = m / ref_len``,
+    ``fmean = P * R / (0.9 * P + 0.1 * R)`` and ``pen = 0.5 * (chunks / m) ** 3``, the operations written once and in this
+    order on Python ints and floats; 0.0 when ``m == 0``.  These are the numbers ``fira_dev_meteor_stats`` /
+    ``fira_mbr_meteor_stats`` write, so a value from the device is ``==`` the value from the words."""
+    if m == 0:
+        return 0.0
+    p = m / hyp_len
+    r = m / ref_len
+    fmean = p * r / (0.9 * p + 0.1 * r)
+    pen = 0.5 * (chunks / m) ** 3
+    return (1 - pen) * fmean
+
+
+def _class_of(classes):
+    """word -> class or None (no class) for a mapping, a callable or a table indexed by integer words."""
+    if hasattr(classes, "get"):
+        return classes.get
+    if callable(classes):
+        return classes
+    size = len(classes)
+
+    def lookup(w):
+        if isinstance(w, bool) or not hasattr(w, "__index__"):
+            return None
+        k = w.__index__()
+        return classes[k] if 0 <= k < size else None
+    return lookup
+
+
+def meteor_alignment(reference: Sequence, hypothesis: Sequence, classes=None):
+    """(m, chunks) of NLTK's METEOR alignment (``_match_enums`` and ``_count_chunks``) of two word lists, without NLTK's stem and
+    WordNet stages.  Stage 1 pairs equal words.  Stage 2 runs only with ``classes`` -- a mapping (``.get``), a callable, or a
+    table indexed by integer words -- and pairs the words still free that have the same class; a word whose class is None, that
+    the mapping lacks or that lies outside the table has no class and matches nothing.  A caller with NLTK passes Porter stems
+    or synonym sets through it; the project ships neither.
+
+    Within a stage NLTK walks the hypothesis from its last word to its first and gives each the last free reference word of
+    equal key.  Words of different keys never compete, and for one key that loop pairs the k-th last free occurrence in the
+    hypothesis with the k-th last in the reference: this function pairs by that rank (DESIGN.md 6j-3 has the proof,
+    tests/meteor_ref.py the literal loops).  ``chunks`` is m minus the matches (i, j) for which (i + 1, j + 1) is a match too."""
+    hyp, ref = list(hypothesis), list(reference)
+    partner = {}                                         # hypothesis position -> reference position
+    taken = set()                                        # reference positions
+
+    def stage(key):
+        by_key = {}
+        for j, w in enumerate(ref):
+            if j not in taken:
+                k = key(w)
+                if k is not None:
+                    by_key.setdefault(k, []).append(j)
+        for i in range(len(hyp) - 1, -1, -1):            # the k-th last free hypothesis occurrence pops the k-th last reference one
+            if i not in partner:
+                k = key(hyp[i])
+                js = by_key.get(k) if k is not None else None
+                if js:
+                    partner[i] = js.pop()
+                    taken.add(partner[i])
+
+    stage(lambda w: ("word", w))
+    if classes is not None:
+        stage(_class_of(classes))
+    m = len(partner)
+    return m, m - sum(1 for i, j in partner.items() if partner.get(i + 1) == j + 1)
+
+
+def meteor_exact(reference: Sequence, hypothesis: Sequence, classes=None) -> float:
+    """``meteor_exact_from_stats`` of two word lists: NLTK's alignment and score with exact matches (and the caller's
+    ``classes`` as a second stage), NOT NLTK's ``meteor_score`` with its stemmer and WordNet -- not comparable with the paper's
+    METEOR column, and identity with NLTK has not been checked (NLTK is absent)."""
+    m, chunks = meteor_alignment(reference, hypothesis, classes)
+    return meteor_exact_from_stats(m, chunks, len(hypothesis), len(reference))
+
+
+def meteor_exact_corpus(references: Iterable[str], predictions: Iterable[str], classes=None) -> float:
+    """100 x the mean ``meteor_exact`` of the lines, both sides tokenised by ``str.split()``.  Raises ValueError when the two
+    sides differ in length (or are empty).  Not NLTK's METEOR -- see ``meteor_exact``."""
+    refs, preds = list(references), list(predictions)
+    if len(refs) != len(preds):
+        raise ValueError("meteor_exact_corpus: %d references and %d predictions" % (len(refs), len(preds)))
+    if not refs:
+        raise ValueError("meteor_exact_corpus: no lines")
+    return 100.0 * math.fsum(meteor_exact(r.split(), p.split(), classes) for r, p in zip(refs, preds)) / len(refs)
+
+
+MBR_UTILITIES = ("bleu", "rouge_l", "meteor_exact")
 
 
 def mbr_utilities(stats, utility: str = "bleu") -> List[List[float]]:
@@ -185,15 +277,19 @@ def mbr_utilities(stats, utility: str = "bleu") -> List[List[float]]:
     ``"bleu"``: the twelve integers of ``fira_mbr_bleu_stats``; ``u[b][i]`` is the mean over j != i of
     ``bleu_method2_from_stats`` of pair (i, j) -- Python ints in, ``math.fsum`` for the mean -- so it is ``==`` the same mean of
     ``sentence_bleu_method2`` on the candidates' word lists.  ``"rouge_l"``: the four integers (lcs, hyp_len, ref_len, 0) of
-    ``fira_mbr_rouge_l_stats`` and ``rouge_l_from_stats`` in the same mean, ``==`` that of ``rouge_l``.  0.0 for n == 1."""
+    ``fira_mbr_rouge_l_stats`` and ``rouge_l_from_stats`` in the same mean, ``==`` that of ``rouge_l``.  ``"meteor_exact"``:
+    the four integers (m, chunks, hyp_len, ref_len) of ``fira_mbr_meteor_stats`` and ``meteor_exact_from_stats`` in the same
+    mean, ``==`` that of ``meteor_exact``.  0.0 for n == 1."""
     if utility not in MBR_UTILITIES:
         raise ValueError("mbr_utilities: utility %r is not one of %s" % (utility, ", ".join(MBR_UTILITIES)))
     if hasattr(stats, "tolist"):
         stats = stats.tolist()
     if utility == "bleu":
         score = lambda st: bleu_method2_from_stats(st[0:4], st[4:8], st[8], st[9])
-    else:
+    elif utility == "rouge_l":
         score = lambda st: rouge_l_from_stats(st[0], st[1], st[2])
+    else:
+        score = lambda st: meteor_exact_from_stats(st[0], st[1], st[2], st[3])
     out = []
     for commit in stats:
         n = len(commit)

@@ -896,6 +896,43 @@ def mbr_rouge_l_stats(tokens, length, stats=None):
     return stats
 
 
+def dev_meteor_stats(ids, sou, sub_token, tar, V, classes=None, stats=None):
+    """fira_dev_meteor_stats: per commit the METEOR alignment statistics of the dev pass on token ids; hypothesis and reference
+    are ``dev_bleu_stats``'s.  ids [B,T], sou [B,L], sub_token [B,S], tar [B,T], all int32; ``classes`` int32 [V] or None (exact
+    matches only).  Returns stats [B,4] int32: m (matched pairs), chunks, hyp_len, ref_len -- into ``stats`` when given.
+    ``metrics.meteor_exact_from_stats`` turns a row into the score."""
+    B, T = ids.shape
+    L, S = sou.shape[1], sub_token.shape[1]
+    assert sou.shape[0] == B and sub_token.shape[0] == B and tuple(tar.shape) == (B, T)
+    assert classes is None or tuple(classes.shape) == (int(V),)
+    if stats is None:
+        stats = torch.empty((B, 4), dtype=torch.int32, device=ids.device)
+    assert tuple(stats.shape) == (B, 4)
+    check(_lib.lib().fira_dev_meteor_stats(cur_stream(), B, T, int(V), L, S, ptr(_i32(ids)), ptr(_i32(sou)), ptr(_i32(sub_token)),
+                                           ptr(_i32(tar)), None if classes is None else ptr(_i32(classes)), ptr(_i32(stats))),
+          "fira_dev_meteor_stats")
+    return stats
+
+
+def mbr_meteor_stats(tokens, length, classes=None, stats=None):
+    """fira_mbr_meteor_stats: the METEOR alignment statistics of every ordered pair of a commit's candidate messages (the
+    messages are ``mbr_bleu_stats``'s).  tokens [B,n,T] vocabulary ids, length [B,n], int32 (n <= 32, T <= 64); ``classes``
+    int32 [V] or None (exact matches only).  Returns stats [B,n,n,4] int32 -- row [b,i,j]: m, chunks, hyp_len, ref_len with
+    candidate i as the hypothesis and j as the reference -- into ``stats`` when given.
+    ``metrics.mbr_utilities(stats, "meteor_exact")`` turns it into expected-METEOR utilities."""
+    B, n, T = tokens.shape
+    assert tuple(length.shape) == (B, n)
+    assert classes is None or classes.dim() == 1
+    if stats is None:
+        stats = torch.empty((B, n, n, 4), dtype=torch.int32, device=tokens.device)
+    assert tuple(stats.shape) == (B, n, n, 4)
+    check(_lib.lib().fira_mbr_meteor_stats(cur_stream(), B, n, T, ptr(_i32(tokens)), ptr(_i32(length)),
+                                           0 if classes is None else classes.shape[0],
+                                           None if classes is None else ptr(_i32(classes)), ptr(_i32(stats))),
+          "fira_mbr_meteor_stats")
+    return stats
+
+
 def pool_memory(dims, mem, mem_valid, out=None):
     """fira_pool_memory: the unit vector of every commit -- the mean of its valid encoder-memory rows, L2-normalised.  mem
     [B, sou_len + sub_len, 256] fp32 and mem_valid [B, sou_len + sub_len] int32 (a decode workspace's views).  Returns out

@@ -816,6 +816,27 @@ int fira_dev_rouge_l_stats(void* stream, int B, int T, int V, int L, int S,
                            const int32_t* tar,  /* [B,T] */
                            int32_t* stats);     /* [B,4]: lcs, hyp_len, ref_len, 0 */
 
+/* METEOR alignment statistics on token ids (csrc/meteor.hip; additive, the ABI version is unchanged): m = the matched word
+ * pairs of NLTK's alignment (_match_enums: hypothesis positions from the last to the first, each taking the last free reference
+ * position of equal key), chunks = m minus the matches (i, j) for which (i + 1, j + 1) is a match too (0 when m == 0), and the
+ * two lengths.  Stage 1 matches equal ids.  Stage 2 runs only when classes [V] is given: the words still free whose ids lie in
+ * [0, V) match on equal classes[id]; an id outside [0, V) -- a hypothesis <unkm>, compared as a sentinel -- has no class.  No
+ * stemmer and no synonym table is part of the library: with classes == NULL this is exact matching only, hence "meteor_exact" on
+ * the Python side (metrics.meteor_exact_from_stats: alpha 0.9, beta 3, gamma 0.5); no figure is comparable with NLTK's METEOR
+ * with WordNet.  Messages and limits are the ROUGE-L entries'; with classes, V >= 4 also for the all-pairs entry.  m and chunks
+ * are the same for [b][i][j] and [b][j][i]; on the diagonal (len, len > 0 ? 1 : 0, len, len).  int32 and exact; B == 0 is a
+ * no-op.                                                                                                                       */
+int fira_dev_meteor_stats(void* stream, int B, int T, int V, int L, int S,
+                          const int32_t* ids,  /* [B,T] output indices of fira_forward_dev, in [0, V+L+S) */
+                          const int32_t* sou,  /* [B,L] */  const int32_t* sub_token, /* [B,S] */
+                          const int32_t* tar,  /* [B,T] */
+                          const int32_t* classes, /* [V] or NULL */
+                          int32_t* stats);     /* [B,4]: m, chunks, hyp_len, ref_len */
+int fira_mbr_meteor_stats(void* stream, int B, int n, int T,
+                          const int32_t* tokens, /* [B,n,T] vocabulary ids */  const int32_t* length, /* [B,n] */
+                          int V, const int32_t* classes, /* [V] or NULL (V is then ignored) */
+                          int32_t* stats);       /* [B,n,n,4]: m, chunks, hyp_len, ref_len (candidate i hypothesis, j reference) */
+
 /* Encoder once per batch (run_model.py:202-207) + everything of the decode loop that does not depend
  * on the generated prefix: memory [B,S,256], mem_valid [B,S], cross-attention K/V of all layers,
  * LinearSource(memory).  State lives in the caller's workspace.                                     */
