@@ -19,6 +19,7 @@ import dataclasses
 import functools
 import gc
 import numbers
+import types
 from typing import List, Optional, Tuple
 
 import torch
@@ -1097,15 +1098,6 @@ class _KnnWs:
         self.scratch = torch.empty(need, dtype=torch.uint8, device=dev)
 
 
-def _refuses_knn(search):
-    """``_refuses_phrases`` for ``knn=`` (``Searcher._no_knn``): None and a value with ``lam == 0`` pass; it is not handed on."""
-    @functools.wraps(search)
-    def refusing(self, *args, knn=None, **kwargs):
-        Searcher._no_knn(search.__name__, knn)
-        return search(self, *args, **kwargs)
-    return refusing
-
-
 def rank_values(scores, by: str) -> torch.Tensor:
     """The [B, n] values ``Searcher.rank`` orders candidates by (larger is better)."""
     if by == "mean_logp_word":
@@ -1113,44 +1105,251 @@ def rank_values(scores, by: str) -> torch.Tensor:
     return scores[by]
 
 
-def _refuses_penalties(why: str):
-    """For a search whose published signature stays as it is: ``penalties=`` is taken for one purpose only, to refuse an active
-    value with the reason (``Searcher._no_penalties``) before the search itself is entered; it is not handed on."""
+# ---------------------------------------------------------------------- the options of a search: refusing, checking, resolving
+# The class of every option a search takes by keyword, and what a search that does not take it says (``_refuse``).
+_OPTION = {"constraints": Constraints, "penalties": Penalties, "phrases": Phrases, "template": Template, "wordsets": WordSets,
+           "neighbour": Neighbour, "knn": KnnMT}
+_REFUSAL = {"penalties": "%s does not take penalties (%s); greedy, greedy_many, beam and sample_search do",
+            "phrases": "%s does not take phrases (greedy, greedy_many, beam and sample_search take banned phrases, beam "
+                       "required ones)",
+            "template": "%s does not take a template (greedy, greedy_many, beam and sample_search do)",
+            "wordsets": "%s does not take word sets (greedy, greedy_many, beam and sample_search do)",
+            "neighbour": "%s does not combine with a neighbour (greedy, greedy_many and beam do)",
+            "knn": "%s does not combine with knn= (greedy, greedy_many, beam and sample_search do)"}
+
+
+def _given(option: str, value, check=None, check_first: bool = False):
+    """What every option checker begins with: None for "off" -- no value, or an inactive one: today's launches, buffers and
+    graphs -- else the value, held against ``check`` (the arguments of its ``.check``) when that is given.  A value of another
+    type is a ``ValueError``.  ``check_first``: ``.check`` runs before ``active`` is read (``knn``: a wrong value is refused
+    even where ``lam == 0`` would switch it off)."""
+    if value is None:
+        return None
+    if not isinstance(value, _OPTION[option]):
+        raise ValueError("%s: expected decode.%s or None, got %r" % (option, _OPTION[option].__name__, value))
+    if check_first:
+        value.check(*check)
+    if not getattr(value, "active", True):
+        return None
+    return value if check is None or check_first else value.check(*check)
+
+
+def _refuse(what: str, option: str, value, why: Optional[str] = None):
+    """For the search ``what``, which does not take ``option``: None and an inactive value pass, an active one and a value of
+    the wrong type are refused with the option's text (``why``: the reason it names, for ``penalties``).  A neighbour has no
+    inactive value; ``knn`` names a wrong type as its checker does and is checked before ``active`` is read."""
+    if option == "knn":
+        value = _given(option, value, (), check_first=True)
+    if value is not None and (not isinstance(value, _OPTION[option]) or getattr(value, "active", True)):
+        raise ValueError(_REFUSAL[option] % ((what,) if why is None else (what, why)))
+
+
+def _refuse_each(what: str, why: Optional[str], **values):
+    """``_refuse`` for every ``option=value`` given, in that order; ``why`` is the reason a refusal of ``penalties`` names."""
+    for option, value in values.items():
+        _refuse(what, option, value, why if option == "penalties" else None)
+
+
+def _refuses(*options, why: Optional[str] = None):
+    """For a search whose published signature stays as it is: each keyword named here is taken for one purpose only, to refuse
+    it (``_refuse_each``), in the order given, before the search itself is entered; it is not handed on."""
     def wrap(search):
         @functools.wraps(search)
-        def refusing(self, *args, penalties=None, **kwargs):
-            Searcher._no_penalties(search.__name__, why, penalties)
+        def refusing(self, *args, **kwargs):
+            _refuse_each(search.__name__, why, **{option: kwargs.pop(option, None) for option in options})
             return search(self, *args, **kwargs)
         return refusing
     return wrap
 
 
-def _refuses_phrases(search):
-    """``_refuses_penalties`` for ``phrases=``: taken for one purpose only, to refuse an active value (``Searcher._no_phrases``;
-    None and a value with nothing in it pass, as an inactive ``Penalties`` does); it is not handed on."""
-    @functools.wraps(search)
-    def refusing(self, *args, phrases=None, **kwargs):
-        Searcher._no_phrases(search.__name__, phrases)
-        return search(self, *args, **kwargs)
-    return refusing
+@dataclasses.dataclass(frozen=True)
+class _Part:
+    """One row of ``_PARTS``: what one option of a search adds to its key, its state and its launches.
+
+    ``on``: the resolved value of an ``_Options`` record that turns the part on (None or False: off).  ``key``: value -> the
+    part's components of the state key (default: its name in the table, a marker).  ``flag``: value -> what the state holds
+    under the part's name (None: no such entry, or one of ``entries``).  ``entries``: (name, dtype, shape(q, value)) of every
+    device buffer the part owns in a state, q having ``cfg``, ``B`` and ``R`` -- or value -> such a tuple.  ``arrays``:
+    (options, value, batch) -> the host values of the leading entries, in their order, copied in on every call (one capture
+    serves every value).  ``call``: for a link of the edit chain, its library entry; it gets the stream, the dims, R, the rows
+    per commit, ``gen`` / ``length`` (``rows``), sou, sub, then ``args(st)`` (default: the entries' pointers in their order),
+    the distribution and the best pair."""
+    on: object
+    key: object = None
+    flag: object = None
+    entries: object = ()
+    arrays: object = None
+    call: Optional[str] = None
+    args: object = None
+    rows: bool = True
+
+    def entries_of(self, value):
+        return self.entries(value) if callable(self.entries) else self.entries
 
 
-def _refuses_template(search):
-    """``_refuses_phrases`` for ``template=`` (``Searcher._no_template``); it is not handed on."""
-    @functools.wraps(search)
-    def refusing(self, *args, template=None, **kwargs):
-        Searcher._no_template(search.__name__, template)
-        return search(self, *args, **kwargs)
-    return refusing
+_I32, _F32 = torch.int32, torch.float32
+_PER_COMMIT = lambda q, v: (q.B,)
+_PER_ROW = lambda q, v: (q.R,)
+_MARK = lambda v: True
+_WST = ("allow", "deny", "boost", "ground", "slot_valid", "boost_factor")      # fira_wordset_dist's pointers, in its order
 
 
-def _refuses_wordsets(search):
-    """``_refuses_phrases`` for ``wordsets=`` (``Searcher._no_wordsets``); it is not handed on."""
-    @functools.wraps(search)
-    def refusing(self, *args, wordsets=None, **kwargs):
-        Searcher._no_wordsets(search.__name__, wordsets)
-        return search(self, *args, **kwargs)
-    return refusing
+def _padded(rows, width: int):
+    """(ids [len(rows), width] int32 zero-padded, lengths [len(rows)] int32) of checked id lists, on the host."""
+    host = torch.zeros((len(rows), width), dtype=torch.int32)
+    for b, row in enumerate(rows):
+        host[b, :len(row)] = torch.tensor(row, dtype=torch.int32)
+    return host, torch.tensor([len(row) for row in rows], dtype=torch.int32)
+
+
+def _slot_words(cfg) -> int:
+    return max((cfg.sou_len + cfg.sub_token_len + 31) // 32, 1)
+
+
+def _wordset_entries(wst: WordSets):
+    """One [B, ceil(vocab / 32)] bit set for each set the value gives, the valid slots [B, ceil(slots / 32)] with ``ground`` and
+    the factors [B] with ``boost``."""
+    shape = {"slot_valid": lambda q, v: (q.B, _slot_words(q.cfg)), "boost_factor": _PER_COMMIT}
+    need = wst.given + (("slot_valid",) if "ground" in wst.given else ()) + (("boost_factor",) if "boost" in wst.given else ())
+    return tuple(("wst_" + name, _F32 if name == "boost_factor" else _I32,
+                  shape.get(name, lambda q, v: (q.B, (q.cfg.vocab_size + 31) // 32))) for name in _WST if name in need)
+
+
+def _wordset_arrays(o, wst: WordSets, db: DeviceBatch):
+    """The checked sets, and the valid copy slots of the batch: slot j is valid iff its source id is not <pad> (0) -- the rule
+    by which ``fira_decode_begin`` forms the copy head's mask (mem_valid), so a slot is valid here exactly where the step can
+    give it mass."""
+    a = wst.arrays(db.B, o.cfg.vocab_size)
+    if "ground" in wst.given:
+        ids = torch.cat([db.sou, db.sub_token], 1) if o.cfg.sub_token_len else db.sou
+        n = _slot_words(o.cfg) * 32
+        valid = torch.zeros((db.B, n), dtype=torch.int64, device=ids.device)
+        valid[:, :ids.shape[1]] = ids != PAD
+        words = (valid.view(db.B, n // 32, 32) << torch.arange(32, device=ids.device)).sum(-1)
+        a["slot_valid"] = torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+    return [a[name[len("wst_"):]] for name, _, _ in _wordset_entries(wst)]
+
+
+# Every part of a search that an option switches on.  First the links of the edit chain, IN THE ORDER ``Searcher._edit`` issues
+# them (its docstring says why the order is what it is); then the parts that are no edit: the selections of ``beam`` (required
+# words, required items, a scoring) and the second distribution mixed in by ``Searcher._step`` (a neighbour, knn=).
+_PARTS = {
+    "merge": _Part(lambda o: o.merge, flag=_MARK, call="fira_merge_dist", rows=False),
+    "prefix": _Part(lambda o: o.rows, entries=(("prefix", _I32, lambda q, v: (q.B, q.cfg.tar_len)), ("prefix_len", _I32, _PER_COMMIT)),
+                    arrays=lambda o, rows, db: _padded(rows, o.cfg.tar_len), call="fira_force_dist"),
+    "con": _Part(lambda o: o.con, key=lambda c: (c,), entries=(("banned", _I32, lambda q, c: (max(len(c.banned), 1),)),),
+                 arrays=lambda o, c, db: (torch.tensor(list(c.banned) or [0], dtype=torch.int32),), call="fira_constrain_dist",
+                 args=lambda st: (st["con"].no_repeat_ngram, st["con"].min_length, _lib.ptr(st["banned"]), len(st["con"].banned))),
+    "ban-phrases": _Part(lambda o: o.ban, flag=_MARK, call="fira_ban_phrases_dist",
+                         entries=(("ban_phrase", _I32, lambda q, v: (q.B, Phrases.MAX_BANNED, Phrases.MAX_WORDS)),
+                                  ("ban_phrase_len", _I32, lambda q, v: (q.B, Phrases.MAX_BANNED)), ("n_ban_phrases", _I32, _PER_COMMIT)),
+                         arrays=lambda o, ban, db: ban.banned_arrays(db.B)),
+    "template": _Part(lambda o: o.tpl, flag=_MARK, call="fira_template_dist",
+                      entries=(("tpl_word_class", torch.uint8, lambda q, v: (q.cfg.vocab_size,)),
+                               ("tpl_next", torch.int8, lambda q, v: (Template.MAX_STATES * Template.MAX_CLASSES,)),
+                               ("tpl_need", _I32, lambda q, v: (Template.MAX_STATES,)), ("tpl_start", _I32, _PER_COMMIT)),
+                      arrays=lambda o, tpl, db: tpl.arrays(db.B, o.cfg.vocab_size)),
+    "wordsets": _Part(lambda o: o.wst, key=lambda wst: (("wordsets", tuple(wst.given)),), flag=lambda wst: wst.given,
+                      entries=_wordset_entries, arrays=_wordset_arrays, call="fira_wordset_dist",
+                      args=lambda st: [_lib.ptr(st["wst_" + name]) if "wst_" + name in st else None for name in _WST]),
+    "penalties": _Part(lambda o: o.pen, flag=_MARK, call="fira_penalise_dist",
+                       entries=(("count_factor", _F32, lambda q, v: (q.cfg.tar_len,)),
+                                ("bias_id", _I32, lambda q, v: (q.B, Penalties.MAX_BIASED)),
+                                ("bias_factor", _F32, lambda q, v: (q.B, Penalties.MAX_BIASED)), ("n_bias", _I32, _PER_COMMIT)),
+                       arrays=lambda o, pen, db: (pen.table(o.cfg.tar_len),) + tuple(pen.bias_arrays(db.B))),
+    "require": _Part(lambda o: o.words, entries=(("required", _I32, lambda q, v: (q.B, MAX_REQUIRED)),
+                                                 ("n_required", _I32, _PER_COMMIT), ("met", _I32, _PER_ROW)),
+                     arrays=lambda o, words, db: _padded(words, MAX_REQUIRED)),
+    "require-phrases": _Part(lambda o: o.items, flag=_MARK,
+                             entries=(("item_words", _I32, lambda q, v: (q.B, Phrases.MAX_REQUIRED_WORDS)),
+                                      ("item_len", _I32, lambda q, v: (q.B, Phrases.MAX_ITEMS)), ("n_items", _I32, _PER_COMMIT),
+                                      ("met", _I32, _PER_ROW)),
+                             arrays=lambda o, items, db: items.required_arrays(db.B)),
+    "scoring": _Part(lambda o: o.scoring, key=lambda sc: (sc,), flag=lambda sc: sc,
+                     entries=(("inv_lp", _F32, lambda q, v: (q.cfg.tar_len + 1,)), ("key", _F32, _PER_ROW)),
+                     arrays=lambda o, sc, db: (torch.tensor(sc.inv_lp(o.cfg.tar_len), dtype=torch.float64).to(torch.float32),)),
+    "neighbour": _Part(lambda o: o.nb),
+    "knn": _Part(lambda o: o.kn, key=lambda kn: (("knn", kn.k, id(kn.store)),)),
+}
+_CHAIN = tuple((name, part) for name, part in _PARTS.items() if part.call is not None)
+# The order of the key's components -- the order in which the options came to the searches, which the states in use are keyed
+# by -- and of the fills.
+_KEY_ORDER = ("merge", "prefix", "require", "neighbour", "knn", "penalties", "ban-phrases", "require-phrases", "template",
+              "wordsets", "con", "scoring")
+assert sorted(_KEY_ORDER) == sorted(_PARTS)
+
+
+def _state_key(base, on):
+    """``base`` and, in ``_KEY_ORDER``, the key components of every part that ``on`` (name -> value; None or False: off) has
+    on: see ``Searcher._key``."""
+    return base + tuple(c for name in _KEY_ORDER if on.get(name) is not None and on[name] is not False
+                        for c in ((name,) if _PARTS[name].key is None else _PARTS[name].key(on[name])))
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class _Options:
+    """The resolved options of one search over one batch (``Searcher._options``): the checked values, each None (``merge``:
+    False) where the option is off -- no value, an inactive one, an all-empty prefix.  It launches nothing and allocates
+    nothing until ``state`` / ``fill`` are called; what it answers, it reads from ``_PARTS``."""
+    search: "Searcher"
+    con: Optional[Constraints] = None
+    merge: bool = False
+    rows: Optional[list] = None                  # the checked prefix
+    words: Optional[list] = None                 # the checked required words
+    nb: Optional[Neighbour] = None
+    kn: Optional[KnnMT] = None
+    pen: Optional[Penalties] = None
+    ban: Optional[Phrases] = None                # the Phrases value, where it bans phrases
+    items: Optional[Phrases] = None              # the Phrases value, where it requires items
+    tpl: Optional[Template] = None
+    wst: Optional[WordSets] = None
+    scoring: Optional[BeamScoring] = None
+
+    cfg = property(lambda self: self.search.cfg)
+
+    def on(self, names=_KEY_ORDER):
+        """(name, part, value) of every part that is on, in the order of ``names``."""
+        parts = [(name, _PARTS[name], _PARTS[name].on(self)) for name in names]
+        return [(name, part, value) for name, part, value in parts if value is not None and value is not False]
+
+    @property
+    def mixer(self):
+        """The ``Neighbour``, the ``KnnMT`` or None: what ``Searcher._begin`` / ``_step`` mix a second distribution in from."""
+        return self.nb if self.kn is None else self.kn
+
+    @property
+    def edits(self) -> bool:
+        """Whether any link of the edit chain is on: the state then owns the distribution the chain edits."""
+        return bool(self.on([name for name, _ in _CHAIN]))
+
+    def key(self, base):
+        """The state key of the search (``Searcher._key``)."""
+        return _state_key(base, {name: value for name, _, value in self.on()})
+
+    def state(self, i32, f32, R: int, B: int, dist: bool = False):
+        """What the options own in a state of R rows over B commits: ``con`` always (None: no constraint), the flag and the
+        entries of every part that is on, and the [R, out_len] distribution with any link of the edit chain (``dist=True``: in
+        any case -- the beam family and the samplers, whose selection reads it, and a search that mixes a second one in)."""
+        q = types.SimpleNamespace(cfg=self.cfg, B=B, R=R)
+        st = dict(con=self.con)
+        for name, part, value in self.on():
+            if part.flag is not None:
+                st[name] = part.flag(value)
+            for entry, dtype, shape in part.entries_of(value):
+                if dtype in (_I32, _F32):
+                    st[entry] = (i32 if dtype is _I32 else f32)(*shape(q, value))
+                else:
+                    st[entry] = torch.zeros(shape(q, value), dtype=dtype, device=self.search.model.device_)
+        if dist or self.edits:
+            st["dist"] = f32(R, self.cfg.out_len)
+        return st
+
+    def fill(self, st, db: DeviceBatch):
+        """The checked values into the state's device buffers -- on every call, the way ``Searcher._state`` fills sou / sub."""
+        for _, part, value in self.on():
+            if part.arrays is not None:
+                for (entry, _, _), a in zip(part.entries_of(value), part.arrays(self, value, db)):
+                    st[entry].copy_(a if torch.is_tensor(a) else torch.from_numpy(a.view("int32") if a.dtype == "uint32" else a))
 
 
 class _Loop:
@@ -1168,13 +1367,13 @@ class _Loop:
     the ``chunk`` and the ``bounds`` they were captured with: a graph call with another ``chunk`` is refused, since the captured
     chunks would not match its bounds.  Eager calls take any ``chunk``."""
 
-    def __init__(self, search: "Searcher", db: DeviceBatch, rows: int, key, make, chunk: int, use_graphs: bool, neighbour=None):
+    def __init__(self, search: "Searcher", db: DeviceBatch, rows: int, key, make, chunk: int, use_graphs: bool, mixer=None):
         st = search._ws.get(key)
         if use_graphs and st is not None and st["graphs"] is not None and st["chunk"] != chunk:
             raise ValueError("chunk = %d, but the graphs of %r were captured with chunk = %d (use_graphs=False takes any chunk)"
                              % (chunk, key, st["chunk"]))
         self.T, self.chunk, self.use_graphs = search.cfg.tar_len, chunk, use_graphs
-        self.ws = search._begin(db, rows) if neighbour is None else search._begin(db, rows, neighbour)
+        self.ws = search._begin(db, rows) if mixer is None else search._begin(db, rows, mixer)
         self.st = search._state(key, db, make)
 
     def start(self, steps, reset, stop=None, n_steps: Optional[int] = None):
@@ -1238,10 +1437,12 @@ class _Loop:
 
 
 class Searcher:
-    """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many``, ``beam`` and ``sample_search`` take five options
-    that edit the step's distribution before a word is chosen (``sample_distinct`` takes the first two); ``_edit`` is the one place
-    that issues their kernels, in the order merge, prefix, constraints, banned phrases, template, word sets, penalties.  Each is off by default, and off -- None, False,
-    an inactive value, an all-empty prefix -- means the calls, keys, buffers and graphs of a search without it.
+    """The searches over one model (or an ensemble).  ``greedy`` / ``greedy_many``, ``beam`` and ``sample_search`` take seven options
+    that edit the step's distribution before a word is chosen (``sample_distinct`` takes the first two); ``_options`` resolves
+    them into one ``_Options`` record, ``_PARTS`` says what each adds to the key, the state and the launches, and ``_edit`` issues
+    their kernels, in the order merge, prefix, constraints, banned phrases, template, word sets, penalties.  Each is off by
+    default, and off -- None, False, an inactive value, an all-empty prefix -- means the calls, keys, buffers and graphs of a
+    search without it.
 
     ``constraints``: a ``Constraints`` value.  ``fira_constrain_dist`` zeroes the blocked words' entries of every row between
     the step and the selection; nothing is renormalised (greedy: probability = the product of the UNnormalised entries taken).
@@ -1325,6 +1526,10 @@ class Searcher:
         lane = Searcher(self.model, kv_bf16=bool(self.flags), members=self.members)
         lane.weights = self.weights                           # the very float32 values: normalising twice may move a bit
         return lane
+
+    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None, ban=None, tpl=None, wst=None):
+        """``_Options.state`` for checked values given one by one (the searches hold a record and ask it)."""
+        return _Options(self, con=con, merge=bool(merge), rows=rows, pen=pen, ban=ban, tpl=tpl, wst=wst).state(i32, f32, R, B, dist)
 
     def _no_ensemble(self, what: str):
         if self.members:
@@ -1436,44 +1641,21 @@ class Searcher:
 
     def _active(self, constraints: Optional[Constraints]) -> Optional[Constraints]:
         """None for "no constraint" (None or an inactive value: today's launches, buffers and graphs), else the checked value."""
-        if constraints is None:
-            return None
-        if not isinstance(constraints, Constraints):
-            raise ValueError("constraints: expected decode.Constraints or None, got %r" % (constraints,))
-        return constraints.check(self.cfg) if constraints.active else None
+        return _given("constraints", constraints, (self.cfg,))
 
     def _penalties(self, penalties, B: int) -> Optional[Penalties]:
         """None for "no penalties" (None or an inactive value: today's launches, buffers and graphs), else the value checked
         against the model and the batch; raises before any launch."""
-        if penalties is None:
-            return None
-        if not isinstance(penalties, Penalties):
-            raise ValueError("penalties: expected decode.Penalties or None, got %r" % (penalties,))
-        return penalties.check(self.cfg, B) if penalties.active else None
-
-    @staticmethod
-    def _no_penalties(what: str, why: str, penalties):
-        if penalties is not None and (not isinstance(penalties, Penalties) or penalties.active):
-            raise ValueError("%s does not take penalties (%s); greedy, greedy_many, beam and sample_search do" % (what, why))
-
-    @staticmethod
-    def _no_phrases(what: str, phrases):
-        if phrases is not None and (not isinstance(phrases, Phrases) or phrases.active):
-            raise ValueError("%s does not take phrases (greedy, greedy_many, beam and sample_search take banned phrases, beam "
-                             "required ones)" % what)
+        return _given("penalties", penalties, (self.cfg, B))
 
     def _phrases(self, phrases, B: int, con: Optional[Constraints], what: str, prefix_rows=None, beam: Optional[int] = None,
                  require=None, scoring=None):
         """(ban, req) of a search: each None for "none" (no value, or nothing in it: today's launches, buffers and graphs), else the
         ``Phrases`` value checked against the model, the batch and the search's other options.  ``beam`` None: a search that has
         no banks and refuses required items.  Raises ``ValueError`` naming the reason; nothing is launched before."""
+        phrases = _given("phrases", phrases, (self.cfg, B))
         if phrases is None:
             return None, None
-        if not isinstance(phrases, Phrases):
-            raise ValueError("phrases: expected decode.Phrases or None, got %r" % (phrases,))
-        if not phrases.active:
-            return None, None
-        phrases.check(self.cfg, B)
         cfg = self.cfg
         ban = phrases if phrases.ban_active else None
         req = phrases if phrases.require_active else None
@@ -1516,24 +1698,15 @@ class Searcher:
                         raise ValueError("phrases: commit %d: the required item %r contains the banned phrase %r" % (b, item, ph))
         return ban, req
 
-    @staticmethod
-    def _no_template(what: str, template):
-        if template is not None and (not isinstance(template, Template) or template.active):
-            raise ValueError("%s does not take a template (greedy, greedy_many, beam and sample_search do)" % what)
-
     def _template(self, template, B: int, con: Optional[Constraints], prefix_rows=None, require=None, items=None):
         """None for "no template" (None or the inactive value: today's launches, buffers and graphs), else the ``Template`` value
         checked against the model, the batch and the search's other options: ``prefix_rows`` (the checked prefix), ``con``,
         ``require`` (the checked required words) and ``items`` (a ``Phrases`` value with required items).  Raises ``ValueError``
         naming the reason; nothing is launched before.  What cannot be seen in advance -- a state that admits only words another
         control blocks at that step -- gives the hypothesis probability 0: a zero simply loses."""
+        template = _given("template", template, (self.cfg, B))
         if template is None:
             return None
-        if not isinstance(template, Template):
-            raise ValueError("template: expected decode.Template or None, got %r" % (template,))
-        if not template.active:
-            return None
-        template.check(self.cfg, B)
         T = self.cfg.tar_len
         if require is not None or items is not None:
             raise ValueError("template: does not combine with require= or Phrases(required=) (their <eos> rule and the "
@@ -1553,11 +1726,6 @@ class Searcher:
                                      "tar_len - 1 = %d" % (b, con.min_length, T - 1))
         return template
 
-    @staticmethod
-    def _no_wordsets(what: str, wordsets):
-        if wordsets is not None and (not isinstance(wordsets, WordSets) or wordsets.active):
-            raise ValueError("%s does not take word sets (greedy, greedy_many, beam and sample_search do)" % what)
-
     def _wordsets(self, wordsets, B: int, prefix_rows=None, require=None, items=None):
         """None for "no word sets" (None or an inactive value: today's launches, buffers and graphs), else the ``WordSets`` value
         checked against the model, the batch and the search's other options: no word of ``prefix_rows`` (the checked prefix),
@@ -1565,13 +1733,9 @@ class Searcher:
         ``allow`` or ``deny`` blocks.  Raises ``ValueError`` naming the reason; nothing is launched before.  What the host cannot
         see -- a forced or required word that ``ground`` blocks because the commit does not carry it, a ``Template`` state
         reachable only through blocked words -- leaves the hypothesis probability 0."""
+        wordsets = _given("wordsets", wordsets, (self.cfg, B))
         if wordsets is None:
             return None
-        if not isinstance(wordsets, WordSets):
-            raise ValueError("wordsets: expected decode.WordSets or None, got %r" % (wordsets,))
-        if not wordsets.active:
-            return None
-        wordsets.check(self.cfg, B)
         item_rows = None if items is None else [[w for item in row for w in item] for row in items.required]
         for what, rows in (("prefix", prefix_rows), ("required", require), ("required phrase", item_rows)):
             for b, row in enumerate(rows or ()):
@@ -1580,71 +1744,19 @@ class Searcher:
                         raise ValueError("wordsets: commit %d: the %s word %d is blocked by allow or deny" % (b, what, w))
         return wordsets
 
-    def _fill_wordsets(self, st, wst: WordSets, db: DeviceBatch):
-        """The checked sets into the state's device buffers (every call, like the prefix buffers), and the valid copy slots of
-        the batch: slot j is valid iff its source id is not <pad> (0) -- the rule by which ``fira_decode_begin`` forms the copy
-        head's mask (mem_valid), so a slot is valid here exactly where the step can give it mass."""
-        for name, a in wst.arrays(db.B, self.cfg.vocab_size).items():
-            if a is not None and "wst_" + name in st:
-                st["wst_" + name].copy_(torch.from_numpy(a.view("int32") if a.dtype.kind == "u" else a))
-        if "wst_slot_valid" in st:
-            ids = torch.cat([db.sou, db.sub_token], 1) if self.cfg.sub_token_len else db.sou
-            n = st["wst_slot_valid"].shape[1] * 32
-            valid = torch.zeros((db.B, n), dtype=torch.int64, device=ids.device)
-            valid[:, :ids.shape[1]] = ids != PAD
-            words = (valid.view(db.B, n // 32, 32) << torch.arange(32, device=ids.device)).sum(-1)
-            st["wst_slot_valid"].copy_(torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32))
-
-    def _fill_template(self, st, tpl: Template, B: int):
-        """The checked tables into the state's device buffers (every call, like the prefix buffers)."""
-        for name, a in zip(("tpl_word_class", "tpl_next", "tpl_need", "tpl_start"), tpl.arrays(B, self.cfg.vocab_size)):
-            st[name].copy_(torch.from_numpy(a))
-
-    def _fill_ban_phrases(self, st, ban: Phrases, B: int):
-        """The checked lists into the state's device buffers (every call, like the prefix buffers)."""
-        words, lens, n = ban.banned_arrays(B)
-        st["ban_phrase"].copy_(torch.from_numpy(words))
-        st["ban_phrase_len"].copy_(torch.from_numpy(lens))
-        st["n_ban_phrases"].copy_(torch.from_numpy(n))
-
-    def _fill_required_phrases(self, st, req: Phrases, B: int):
-        words, lens, n = req.required_arrays(B)
-        st["item_words"].copy_(torch.from_numpy(words))
-        st["item_len"].copy_(torch.from_numpy(lens))
-        st["n_items"].copy_(torch.from_numpy(n))
-
-    def _fill_penalties(self, st, pen: Penalties, B: int):
-        """The checked value into the state's device buffers (every call, like the prefix buffers)."""
-        ids, fac, n = pen.bias_arrays(B)
-        st["count_factor"].copy_(torch.from_numpy(pen.table(self.cfg.tar_len)))
-        st["bias_id"].copy_(torch.from_numpy(ids))
-        st["bias_factor"].copy_(torch.from_numpy(fac))
-        st["n_bias"].copy_(torch.from_numpy(n))
-
     def _neighbour(self, neighbour, B: int):
         """None for "no neighbour" (today's launches, buffers and graphs), else the checked value; raises before any launch."""
-        if neighbour is None:
+        if _given("neighbour", neighbour) is None:
             return None
-        if not isinstance(neighbour, Neighbour):
-            raise ValueError("neighbour: expected decode.Neighbour or None, got %r" % (neighbour,))
         if self.members:
             raise ValueError("neighbour: does not combine with an ensemble (members)")
         return neighbour.check(B)
 
-    @staticmethod
-    def _no_neighbour(what: str, neighbour):
-        if neighbour is not None:
-            raise ValueError("%s does not combine with a neighbour (greedy, greedy_many and beam do)" % what)
-
     def _knn(self, knn, B: int, neighbour=None):
         """None for "no retrieval" (None, or ``lam == 0``: today's launches, buffers and graphs), else the checked value; raises
         before any launch."""
+        knn = _given("knn", knn, (B,), check_first=True)
         if knn is None:
-            return None
-        if not isinstance(knn, KnnMT):
-            raise ValueError("knn: expected decode.KnnMT or None, got %r" % (knn,))
-        knn.check(B)
-        if not knn.active:
             return None
         if self.members:
             raise ValueError("knn: does not combine with an ensemble (members)")
@@ -1655,115 +1767,39 @@ class Searcher:
             raise ValueError("knn: the store is on %s, the model on %s" % (knn.store.keys.device, self.model.device_))
         return knn
 
-    @staticmethod
-    def _no_knn(what: str, knn):
-        if knn is not None and not isinstance(knn, KnnMT):
-            raise ValueError("knn: expected decode.KnnMT or None, got %r" % (knn,))
-        if knn is not None and knn.check().active:
-            raise ValueError("%s does not combine with knn= (greedy, greedy_many, beam and sample_search do)" % what)
-
     def _edit(self, st, R, rows_per_commit, gen, length, best):
         """The edit chain: the kernels that edit the step's distribution st["dist"] ([R, out_len], ``rows_per_commit`` rows per
-        commit) between the decoder step and the selection, for whatever the state ``st`` carries, in this order:
+        commit) between the decoder step and the selection, for whatever the state ``st`` carries: the links of ``_PARTS`` that
+        the state has on, in the table's order.  Each link reads its buffers from the state when its kernel runs (``_Part``).
+        Why the order is what it is:
 
-        merge (st["merge"]): ``fira_merge_dist`` folds every copy entry into the generator entry of the word it resolves to
-        (DESIGN.md section 6l).  Words first: a blocked word's mass then sits on its generator entry.
-        force ("prefix" in st): ``fira_force_dist`` leaves the rows still inside their commit's prefix the entries of the prefix
-        word only (section 6q); ``gen`` / ``length`` say where a row is.  The prefix is read from st["prefix"] / st["prefix_len"]
-        when the kernel runs.
-        constrain (st["con"]): ``fira_constrain_dist`` zeroes the blocked words' entries (section 6k); nothing is renormalised.
-        Its scalars are baked into a captured graph.
-        ban phrases ("ban-phrases" in st): ``fira_ban_phrases_dist`` zeroes the entries of the word that would complete a banned
-        phrase (section 6zb).  The lists are read from st["ban_phrase"] / st["ban_phrase_len"] / st["n_ban_phrases"] when the
-        kernel runs.
-        template ("template" in st): ``fira_template_dist`` zeroes the entries of the words the automaton does not admit after
-        the row's hypothesis, and <eos> where it does not accept (section 6zc).  The four tables are read from st["tpl_word_class"]
-        / st["tpl_next"] / st["tpl_need"] / st["tpl_start"] when the kernel runs.
-        word sets ("wordsets" in st): ``fira_wordset_dist`` zeroes the entries of the words the commit's allow / deny / ground sets
-        block and multiplies the entries of its boost set (section 6zd).  After the other hard edits, before the soft one: its one
-        multiplication is the last of its own edits.  The sets st["wst_allow"] / st["wst_deny"] / st["wst_boost"] /
-        st["wst_ground"] (those the state owns; NULL for the rest), st["wst_slot_valid"] and st["wst_boost_factor"] are read when
-        the kernel runs.
-        penalise ("penalties" in st): ``fira_penalise_dist`` multiplies the entries of the words a row already holds, and of the
-        commit's biased words, by their factors (section 6za).  Last: a finite non-negative factor commutes bit for bit with the
-        zeroing links, and after a merge a word's mass sits on its generator entry.  The table and the bias lists are read from
-        st["count_factor"] / st["bias_id"] / st["bias_factor"] / st["n_bias"] when the kernel runs.
+        merge: ``fira_merge_dist`` folds every copy entry into the generator entry of the word it resolves to (DESIGN.md
+        section 6l).  Words first: a blocked word's mass then sits on its generator entry.
+        force: ``fira_force_dist`` leaves the rows still inside their commit's prefix the entries of the prefix word only
+        (section 6q); ``gen`` / ``length`` say where a row is.
+        constrain: ``fira_constrain_dist`` zeroes the blocked words' entries (section 6k); nothing is renormalised.  Its scalars
+        are baked into a captured graph.
+        ban phrases: ``fira_ban_phrases_dist`` zeroes the entries of the word that would complete a banned phrase (section 6zb).
+        template: ``fira_template_dist`` zeroes the entries of the words the automaton does not admit after the row's hypothesis,
+        and <eos> where it does not accept (section 6zc).
+        word sets: ``fira_wordset_dist`` zeroes the entries of the words the commit's allow / deny / ground sets block and
+        multiplies the entries of its boost set (section 6zd).  After the other hard edits, before the soft one: its one
+        multiplication is the last of its own edits.  It gets the sets the state owns and NULL for the rest.
+        penalise: ``fira_penalise_dist`` multiplies the entries of the words a row already holds, and of the commit's biased
+        words, by their factors (section 6za).  Last: a finite non-negative factor commutes bit for bit with the zeroing links,
+        and after a merge a word's mass sits on its generator entry.
 
         ``best``: (best_id, best_p) or None.  The last kernel that edits the distribution takes the arg-max of what is left: a
         pair goes to the last call the chain makes, every other call gets NULL for both (greedy); None: NULL for all (the beam
-        family, whose selection reads the distribution itself).  This is the one place that knows the order and that rule."""
-        lib, s, dims, c = _lib.lib(), _lib.cur_stream(), C.byref(self.model.dims), st["con"]
+        family, whose selection reads the distribution itself).  This is the one place that knows that rule."""
+        lib, s, dims = _lib.lib(), _lib.cur_stream(), C.byref(self.model.dims)
         sou, sub, dist = _lib.ptr(st["sou"]), _lib.ptr(st["sub"]), _lib.ptr(st["dist"])
-        chain = []
-        if st.get("merge", False):
-            chain.append(("fira_merge_dist", lambda *b: lib.fira_merge_dist(s, dims, R, rows_per_commit, sou, sub, dist, *b)))
-        if "prefix" in st:
-            chain.append(("fira_force_dist", lambda *b: lib.fira_force_dist(
-                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["prefix"]),
-                _lib.ptr(st["prefix_len"]), dist, *b)))
-        if c is not None:
-            chain.append(("fira_constrain_dist", lambda *b: lib.fira_constrain_dist(
-                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, c.no_repeat_ngram, c.min_length,
-                _lib.ptr(st["banned"]), len(c.banned), dist, *b)))
-        if "ban-phrases" in st:
-            chain.append(("fira_ban_phrases_dist", lambda *b: lib.fira_ban_phrases_dist(
-                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["ban_phrase"]),
-                _lib.ptr(st["ban_phrase_len"]), _lib.ptr(st["n_ban_phrases"]), dist, *b)))
-        if "template" in st:
-            chain.append(("fira_template_dist", lambda *b: lib.fira_template_dist(
-                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["tpl_word_class"]),
-                _lib.ptr(st["tpl_next"]), _lib.ptr(st["tpl_need"]), _lib.ptr(st["tpl_start"]), dist, *b)))
-        if "wordsets" in st:
-            sets = [_lib.ptr(st[k]) if k in st else None for k in ("wst_allow", "wst_deny", "wst_boost", "wst_ground",
-                                                                    "wst_slot_valid", "wst_boost_factor")]
-            chain.append(("fira_wordset_dist", lambda *b: lib.fira_wordset_dist(
-                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, *sets, dist, *b)))
-        if "penalties" in st:
-            chain.append(("fira_penalise_dist", lambda *b: lib.fira_penalise_dist(
-                s, dims, R, rows_per_commit, _lib.ptr(gen), _lib.ptr(length), sou, sub, _lib.ptr(st["count_factor"]),
-                _lib.ptr(st["bias_id"]), _lib.ptr(st["bias_factor"]), _lib.ptr(st["n_bias"]), dist, *b)))
-        for k, (name, call) in enumerate(chain):
-            last = best is not None and k == len(chain) - 1
-            _lib.check(call(*((_lib.ptr(best[0]), _lib.ptr(best[1])) if last else (None, None))), name)
-
-    def _edit_state(self, i32, f32, R, B, con, merge, rows, dist=False, pen=None, ban=None, tpl=None, wst=None):
-        """What the edit chain (``_edit``) owns in a state of R rows over B commits: ``con`` always (None: no constraint);
-        ``merge`` only when merging; the [R, out_len] distribution when an edit is active (``dist=True``: in any case, for the
-        beam family, whose selection reads it); the banned ids with constraints; the two prefix buffers with a prefix ``rows``;
-        with penalties ``pen`` the "penalties" marker, the count table [tar_len] and the bias lists [B, 16] / [B, 16] / [B]; with
-        banned phrases ``ban`` the "ban-phrases" marker and the lists [B, 8, 4] / [B, 8] / [B]; with a template ``tpl`` the
-        "template" marker and the tables [vocab] uint8 / [32 * 32] int8 / [32] / [B]; with word sets ``wst`` the "wordsets" marker,
-        one [B, ceil(vocab / 32)] bit set for each set the value gives, the valid slots [B, ceil(slots / 32)] with ``ground`` and
-        the factors [B] with ``boost``."""
-        st = dict(con=con)
-        if wst is not None:
-            cfg = self.cfg
-            st.update(wordsets=wst.given, **{"wst_" + name: i32(B, (cfg.vocab_size + 31) // 32) for name in wst.given})
-            if "ground" in wst.given:
-                st["wst_slot_valid"] = i32(B, max((cfg.sou_len + cfg.sub_token_len + 31) // 32, 1))
-            if "boost" in wst.given:
-                st["wst_boost_factor"] = f32(B)
-        if tpl is not None:
-            dev = self.model.device_
-            st.update(template=True, tpl_word_class=torch.zeros(self.cfg.vocab_size, dtype=torch.uint8, device=dev),
-                      tpl_next=torch.zeros(Template.MAX_STATES * Template.MAX_CLASSES, dtype=torch.int8, device=dev),
-                      tpl_need=i32(Template.MAX_STATES), tpl_start=i32(B))
-        if ban is not None:
-            st.update({"ban-phrases": True}, ban_phrase=i32(B, Phrases.MAX_BANNED, Phrases.MAX_WORDS),
-                      ban_phrase_len=i32(B, Phrases.MAX_BANNED), n_ban_phrases=i32(B))
-        if merge:
-            st["merge"] = True
-        if pen is not None:
-            st.update(penalties=True, count_factor=f32(self.cfg.tar_len), bias_id=i32(B, Penalties.MAX_BIASED),
-                      bias_factor=f32(B, Penalties.MAX_BIASED), n_bias=i32(B))
-        if dist or con is not None or merge or rows is not None or pen is not None or ban is not None or tpl is not None \
-                or wst is not None:
-            st["dist"] = f32(R, self.cfg.out_len)
-        if con is not None:
-            st["banned"] = torch.tensor(list(con.banned) or [0], dtype=torch.int32, device=self.model.device_)
-        if rows is not None:
-            st.update(prefix=i32(B, self.cfg.tar_len), prefix_len=i32(B))
-        return st
+        chain = [part for name, part in _CHAIN if st.get(name) is not None]
+        for part in chain:
+            where = (_lib.ptr(gen), _lib.ptr(length)) if part.rows else ()
+            args = [_lib.ptr(st[entry]) for entry, _, _ in part.entries] if part.args is None else part.args(st)
+            last = (_lib.ptr(best[0]), _lib.ptr(best[1])) if best is not None and part is chain[-1] else (None, None)
+            _lib.check(getattr(lib, part.call)(s, dims, R, rows_per_commit, *where, sou, sub, *args, dist, *last), part.call)
 
     def _prefix_rows(self, prefix, B: int, con: Optional[Constraints]):
         """None for "no prefix" (None, or every sequence empty: today's launches, buffers and graphs), else the checked prefix as
@@ -1798,36 +1834,46 @@ class Searcher:
                                      % (b, n, n))
         return rows if any(rows) else None
 
-    def _fill_prefix(self, st, rows):
-        """The checked prefix into the state's device buffers (every call, the way ``_state`` fills sou / sub)."""
-        T = self.cfg.tar_len
-        host = torch.zeros((len(rows), T), dtype=torch.int32)
-        for b, row in enumerate(rows):
-            host[b, :len(row)] = torch.tensor(row, dtype=torch.int32)
-        st["prefix"].copy_(host)
-        st["prefix_len"].copy_(torch.tensor([len(row) for row in rows], dtype=torch.int32))
-
     @staticmethod
     def _key(base, merge: bool, con, scoring=None, forced: bool = False, *, require: bool = False, neighbour: bool = False,
              penalties: bool = False, ban_phrases: bool = False, require_phrases: bool = False, template: bool = False,
              wordsets=(), knn=None):
-        """The state key of a search: today's ``base`` (+ the Constraints value), with "merge" in between for a merged search,
-        so merged and unmerged searches own separate buffers and graphs; "prefix" follows for a prefix-forced search (the
-        marker only: the prefix values live in device buffers), then "require" for a search with required words (a marker
-        too), then "neighbour" for a search with a neighbour (a marker: the batch and the coefficients live in device buffers),
-        then "penalties" for a search with active penalties (a marker: the table and the bias lists live in device buffers),
-        then "ban-phrases" / "require-phrases" for a search with an active ``Phrases`` value (markers: the lists live in device
-        buffers), then "template" for a search with an active ``Template`` (a marker: the tables live in device buffers), then
-        ("wordsets", names) for a search with an active ``WordSets`` (the names of the sets it gives: which pointers a launch
-        gets is baked into a captured graph, the sets themselves live in device buffers); an active BeamScoring value comes
-        last.  ("knn", K, the store) follows "neighbour" for a search with ``knn=`` (K, N and the store's pointers are baked into a
-        captured graph; lam, the temperature and the exclude list live in device buffers)."""
-        return (base + (("merge",) if merge else ()) + (("prefix",) if forced else ()) + (("require",) if require else ())
-                + (("neighbour",) if neighbour else ()) + ((("knn", knn.k, id(knn.store)),) if knn is not None else ())
-                + (("penalties",) if penalties else ())
-                + (("ban-phrases",) if ban_phrases else ()) + (("require-phrases",) if require_phrases else ())
-                + (("template",) if template else ()) + ((("wordsets", tuple(wordsets)),) if wordsets else ())
-                + ((con,) if con is not None else ()) + ((scoring,) if scoring is not None else ()))
+        """The state key of a search, from flags (the searches themselves ask their ``_Options`` record: ``_Options.key``; both
+        read ``_state_key``): ``base``, then the component of every part that is on, in ``_KEY_ORDER`` -- "merge" (merged and
+        unmerged searches own separate buffers and graphs), "prefix", "require", "neighbour", ("knn", K, the store), "penalties",
+        "ban-phrases", "require-phrases", "template", ("wordsets", the names of the sets given), the ``Constraints`` value, the
+        ``BeamScoring`` value.  A marker stands for values that live in device buffers, filled on every call: one capture
+        serves all of them.  What a captured launch bakes in is in the key itself: the scalars of the constraints and of the
+        scoring, K, N and the store's pointers of ``knn=`` (lam, the temperature and the exclude list are device values), and
+        which set pointers a word-set launch gets.  Off -- False, None, () -- adds nothing: today's key."""
+        given = types.SimpleNamespace(given=wordsets) if wordsets else None
+        return _state_key(base, {"merge": merge, "prefix": forced, "require": require, "neighbour": neighbour, "knn": knn,
+                                 "penalties": penalties, "ban-phrases": ban_phrases, "require-phrases": require_phrases,
+                                 "template": template, "wordsets": given, "con": con, "scoring": scoring})
+
+    def _options(self, what: str, db_or_B, *, beam: Optional[int] = None, scoring=None, constraints=None,
+                 merge_copies: bool = False, prefix=None, require=None, neighbour=None, penalties=None, phrases=None,
+                 template=None, wordsets=None, knn=None) -> _Options:
+        """The options of the search ``what`` over a batch (or its size), checked against the model, the batch and one another
+        in the one order every search has had -- constraints, scoring, prefix, required words, neighbour, knn, penalties,
+        phrases, template, word sets -- and resolved into a record.  ``beam``: None for a search without one, which takes
+        neither a scoring nor required words or items.  Raises ``ValueError`` naming the reason; nothing is launched or
+        allocated here."""
+        B = db_or_B if isinstance(db_or_B, int) else db_or_B.B
+        con = self._active(constraints)
+        if scoring is not None:
+            if not isinstance(scoring, BeamScoring):
+                raise ValueError("scoring: expected decode.BeamScoring or None, got %r" % (scoring,))
+            scoring = scoring.check(beam) if scoring.active() or beam < 2 else None
+        rows = self._prefix_rows(prefix, B, con)
+        words = self._required_rows(require, B, beam, con, scoring)
+        nb = self._neighbour(neighbour, B)
+        kn = self._knn(knn, B, nb)
+        pen = self._penalties(penalties, B)
+        ban, items = self._phrases(phrases, B, con, what, rows, beam, words, scoring)
+        tpl = self._template(template, B, con, rows, words, items)
+        wst = self._wordsets(wordsets, B, rows, words, items)
+        return _Options(self, con, bool(merge_copies), rows, words, nb, kn, pen, ban, items, tpl, wst, scoring)
 
     def _required_rows(self, require, B: int, beam: int, con: Optional[Constraints], scoring):
         """None for "no required words" (None, or every sequence empty: today's launches, buffers and graphs), else the checked
@@ -1870,14 +1916,6 @@ class Searcher:
         if scoring is not None:
             raise ValueError("require: required words do not combine with an active scoring (the banks rank by raw probability)")
         return rows
-
-    def _fill_required(self, st, rows):
-        """The checked words into the state's device buffers (every call, like the prefix buffers)."""
-        host = torch.zeros((len(rows), MAX_REQUIRED), dtype=torch.int32)
-        for b, row in enumerate(rows):
-            host[b, :len(row)] = torch.tensor(row, dtype=torch.int32)
-        st["required"].copy_(host)
-        st["n_required"].copy_(torch.tensor([len(row) for row in rows], dtype=torch.int32))
 
     @staticmethod
     def _sbs_key(B: int, n: int, merge: bool, con, temperature: float):
@@ -1957,52 +1995,18 @@ class Searcher:
                                                _lib.ptr(st["alive"]), _lib.ptr(st["tok"]), _lib.ptr(st["n_alive"])),
                        "fira_greedy_advance")
 
-    def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, constraints: Optional[Constraints] = None,
-                     merge_copies: bool = False, prefix=None, neighbour=None, penalties=None, phrases=None, template=None,
-                     wordsets=None, knn=None) -> _Loop:
+    def _greedy_loop(self, db: DeviceBatch, chunk: int, use_graphs: bool, opts: _Options) -> _Loop:
         """Encoder pass + reset of the hypothesis state for one batch on the CURRENT stream; returns the started loop.  The
-        active options join the key (``_key``: ("greedy", B[, "merge"][, "prefix"][, "penalties"][, constraints]), and so own their graphs)
-        and add what ``_edit_state`` lists to the state -- the [B, out_len] distribution with any of them."""
+        options that are on join the key (``_key``, over the base ("greedy", B)), and so own their graphs, and add what
+        ``_Options.state`` lists to the state -- the [B, out_len] distribution with any link of the edit chain, and always with a
+        neighbour or knn=, whose mix takes the arg-max itself ("mix_best") where the chain is empty."""
         B = db.B
-        con = self._active(constraints)                      # raises before anything is launched
-        merge = bool(merge_copies)
-        rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
-        nb = self._neighbour(neighbour, B)                   # likewise
-        kn = self._knn(knn, B, nb)                           # likewise
-        pen = self._penalties(penalties, B)                  # likewise
-        ban, _ = self._phrases(phrases, B, con, "greedy", rows)      # likewise
-        tpl = self._template(template, B, con, rows)         # likewise
-        wst = self._wordsets(wordsets, B, rows)              # likewise
-        marks = {} if tpl is None else {"template": True}    # (off: today's key, argument for argument)
-        if wst is not None:
-            marks["wordsets"] = wst.given
-        if kn is not None:                                   # a second distribution is mixed in, as with a neighbour
-            marks["knn"] = kn
-        if nb is None and kn is None:
-            make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B),
-                                         **self._edit_state(i32, f32, B, B, con, merge, rows, pen=pen, ban=ban, tpl=tpl,
-                                                            **({} if wst is None else {"wst": wst})))
-            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, penalties=pen is not None,
-                                                ban_phrases=ban is not None, **marks), make, chunk, use_graphs)
-        else:                                                # a neighbour or knn=: the state always owns the distribution
-            bare = con is None and not merge and rows is None and pen is None and ban is None and tpl is None and wst is None
-            make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **({"mix_best": True} if bare else {}),
-                                         **self._edit_state(i32, f32, B, B, con, merge, rows, dist=True, pen=pen, ban=ban,
-                                                            tpl=tpl, **({} if wst is None else {"wst": wst})))
-            loop = _Loop(self, db, 1, self._key(("greedy", B), merge, con, forced=rows is not None, neighbour=nb is not None,
-                                                penalties=pen is not None, ban_phrases=ban is not None, **marks), make, chunk,
-                         use_graphs, nb if kn is None else kn)
+        mixed = opts.mixer is not None
+        make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, B), **({"mix_best": True} if mixed and not opts.edits else {}),
+                                     **opts.state(i32, f32, B, B, dist=mixed))
+        loop = _Loop(self, db, 1, opts.key(("greedy", B)), make, chunk, use_graphs, opts.mixer)
         st, ws = loop.st, loop.ws
-        if rows is not None:
-            self._fill_prefix(st, rows)
-        if pen is not None:
-            self._fill_penalties(st, pen, B)
-        if ban is not None:
-            self._fill_ban_phrases(st, ban, B)
-        if tpl is not None:
-            self._fill_template(st, tpl, B)
-        if wst is not None:
-            self._fill_wordsets(st, wst, db)
+        opts.fill(st, db)
         return loop.start(lambda lo, hi: self._greedy_steps(st, ws, B, lo, hi), lambda: self._greedy_reset(st),
                           lambda hi: self._none_alive(st, hi))
 
@@ -2054,8 +2058,24 @@ class Searcher:
         The step loop is launch-bound (~58 small kernels per generated token), so it is captured once per batch size
         into hipGraphs of ``chunk`` steps each and replayed; between chunks one counter is read back to stop as soon
         as every hypothesis has emitted <eos> (run_model.py:276-279)."""
-        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, constraints, merge_copies, prefix, neighbour,
-                                                     penalties, phrases, template, wordsets, knn).run())
+        opts = self._options("greedy", db, constraints=constraints, merge_copies=merge_copies, prefix=prefix,
+                             neighbour=neighbour, penalties=penalties, phrases=phrases, template=template, wordsets=wordsets,
+                             knn=knn)                       # raises before anything is launched
+        return self._greedy_result(self._greedy_loop(db, chunk, use_graphs, opts).run())
+
+    @staticmethod
+    def _per_batch(name: str, value, n: int, expected: str, one=None, unit: str = "values"):
+        """An argument of ``greedy_many`` as a list of one value per batch: None -- or, for an option with a class ``one``, a
+        single value -- stands for every batch; otherwise a sequence as long as the batches."""
+        if value is None or (one is not None and isinstance(value, one)):
+            return [value] * n
+        try:
+            value = list(value)
+        except TypeError:
+            raise ValueError("%s: expected %s, got %r" % (name, expected, value)) from None
+        if len(value) != n:
+            raise ValueError("%s: %d %s for %d batches" % (name, len(value), unit, n))
+        return value
 
     @torch.no_grad()
     def greedy_many(self, dbs, in_flight: int = 4, chunk: int = 5, constraints: Optional[Constraints] = None,
@@ -2086,54 +2106,15 @@ class Searcher:
         ``knn``: one ``KnnMT`` value for every batch (an exclude list then needs batches of one size), or a sequence of one value
         (or None) per batch, as for ``greedy``."""
         dbs = list(dbs)
-        con = self._active(constraints)                      # raises before a lane starts
-        if knn is None or isinstance(knn, KnnMT):
-            knn = [knn] * len(dbs)
-        else:
-            try:
-                knn = list(knn)
-            except TypeError:
-                raise ValueError("knn: expected decode.KnnMT, None or one of them per batch, got %r" % (knn,)) from None
-            if len(knn) != len(dbs):
-                raise ValueError("knn: %d values for %d batches" % (len(knn), len(dbs)))
-        for db, kn in zip(dbs, knn):
-            self._knn(kn, db.B)                              # every batch's, before a lane starts
-        if wordsets is None or isinstance(wordsets, WordSets):
-            wordsets = [wordsets] * len(dbs)
-        else:
-            try:
-                wordsets = list(wordsets)
-            except TypeError:
-                raise ValueError("wordsets: expected decode.WordSets, None or one of them per batch, got %r" % (wordsets,)) from None
-            if len(wordsets) != len(dbs):
-                raise ValueError("wordsets: %d values for %d batches" % (len(wordsets), len(dbs)))
-        for db, w in zip(dbs, wordsets):
-            self._penalties(penalties, db.B)                 # every batch's, before a lane starts
-            if prefix is None:                               # (with prefixes: checked with each batch's, below)
-                self._phrases(phrases, db.B, con, "greedy_many")
-                self._template(template, db.B, con)
-                self._wordsets(w, db.B)
-        if neighbour is not None:
-            try:
-                neighbour = list(neighbour)
-            except TypeError:
-                raise ValueError("neighbour: expected one Neighbour per batch, got %r" % (neighbour,)) from None
-            if len(neighbour) != len(dbs):
-                raise ValueError("neighbour: %d values for %d batches" % (len(neighbour), len(dbs)))
-            for db, nb, kn in zip(dbs, neighbour, knn):
-                self._knn(kn, db.B, self._neighbour(nb, db.B))       # every batch's, before a lane starts
-        if prefix is not None:
-            try:
-                prefix = list(prefix)
-            except TypeError:
-                raise ValueError("prefix: expected one prefix argument per batch, got %r" % (prefix,)) from None
-            if len(prefix) != len(dbs):
-                raise ValueError("prefix: %d prefix arguments for %d batches" % (len(prefix), len(dbs)))
-            for db, p in zip(dbs, prefix):                   # every batch's, before a lane starts
-                self._phrases(phrases, db.B, con, "greedy_many", self._prefix_rows(p, db.B, con))
-                self._template(template, db.B, con, self._prefix_rows(p, db.B, con))
-            for db, p, w in zip(dbs, prefix, wordsets):
-                self._wordsets(w, db.B, self._prefix_rows(p, db.B, con))
+        self._active(constraints)                            # (even for no batch at all)
+        knn = self._per_batch("knn", knn, len(dbs), "decode.KnnMT, None or one of them per batch", KnnMT)
+        wordsets = self._per_batch("wordsets", wordsets, len(dbs), "decode.WordSets, None or one of them per batch", WordSets)
+        neighbour = self._per_batch("neighbour", neighbour, len(dbs), "one Neighbour per batch")
+        prefix = self._per_batch("prefix", prefix, len(dbs), "one prefix argument per batch", unit="prefix arguments")
+        # every batch's options, resolved before a lane starts: every refusal comes before the first device call
+        opts = [self._options("greedy_many", db, constraints=constraints, merge_copies=merge_copies, prefix=p, neighbour=nb,
+                              penalties=penalties, phrases=phrases, template=template, wordsets=w, knn=kn)
+                for db, p, nb, w, kn in zip(dbs, prefix, neighbour, wordsets, knn)]
         n_lane = max(1, min(in_flight, len(dbs)))
         if not hasattr(self, "_lanes") or len(self._lanes) < n_lane:
             streams = concurrent_streams(n_lane, self.model.device_)
@@ -2164,10 +2145,7 @@ class Searcher:
                         else:
                             loop.launch()
                     if active[k] is None and nxt < len(dbs):
-                        loop = lane._greedy_loop(dbs[nxt], chunk, True, constraints, merge_copies,
-                                                 None if prefix is None else prefix[nxt],
-                                                 None if neighbour is None else neighbour[nxt], penalties, phrases,
-                                                 template, wordsets[nxt], knn[nxt])
+                        loop = lane._greedy_loop(dbs[nxt], chunk, True, opts[nxt])
                         loop.launch()
                         active[k] = (nxt, loop)
                         nxt += 1
@@ -2228,8 +2206,7 @@ class Searcher:
                                                _lib.ptr(st["logp"]), _lib.ptr(st["alive"]), _lib.ptr(st["tok"]),
                                                _lib.ptr(st["n_alive"])), "fira_sample_advance")
 
-    @_refuses_knn
-    @_refuses_wordsets
+    @_refuses("knn", "wordsets")
     @torch.no_grad()
     def sample(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                keys=None, chunk: int = 5, use_graphs: bool = True, neighbour=None, min_p: float = 0.0, epsilon: float = 0.0,
@@ -2252,10 +2229,8 @@ class Searcher:
         fixed in the captured launches, so they are part of the state's key; the seed is a device scalar read at run time: one
         capture serves every seed."""
         self._no_ensemble("sample")                           # raises before anything is launched
-        self._no_neighbour("sample", neighbour)
-        self._no_penalties("sample", "its fused step hands no distribution over; sample_search does", penalties)
-        self._no_phrases("sample", phrases)
-        self._no_template("sample", template)
+        _refuse_each("sample", "its fused step hands no distribution over; sample_search does", neighbour=neighbour,
+                     penalties=penalties, phrases=phrases, template=template)
         cuts = self._check_cuts(top_p, min_p, epsilon, eta, typical_p)
         B, T = db.B, self.cfg.tar_len
         R = B * n
@@ -2333,36 +2308,17 @@ class Searcher:
         n, top_k = int(n), int(top_k)
         B, T = db.B, self.cfg.tar_len
         R = B * n
-        con = self._active(constraints)
-        merge = bool(merge_copies)
-        rows = self._prefix_rows(prefix, B, con)
-        nb = self._neighbour(neighbour, B)
-        kn = self._knn(knn, B, nb)
-        pen = self._penalties(penalties, B)
-        ban, _ = self._phrases(phrases, B, con, "sample_search", rows)
-        tpl = self._template(template, B, con, rows)
-        wst = self._wordsets(wordsets, B, rows)
+        opts = self._options("sample_search", db, constraints=constraints, merge_copies=merge_copies, prefix=prefix,
+                             neighbour=neighbour, penalties=penalties, phrases=phrases, template=template, wordsets=wordsets,
+                             knn=knn)
         noise_rows, fill_noise = self._noise(keys, seed, B)
         make = lambda i32, f32: dict(self._hypothesis_rows(i32, f32, R), logp=f32(R), **noise_rows(i32),
-                                     **self._edit_state(i32, f32, R, B, con, merge, rows, dist=True, pen=pen, ban=ban, tpl=tpl,
-                                                        **({} if wst is None else {"wst": wst})))
-        key = self._key(("sample_search", B, n, temperature, top_k, top_p) + cuts, merge, con, forced=rows is not None,
-                        neighbour=nb is not None, penalties=pen is not None, ban_phrases=ban is not None,
-                        **({} if tpl is None else {"template": True}),
-                        **({} if wst is None else {"wordsets": wst.given}), **({} if kn is None else {"knn": kn}))
-        loop = _Loop(self, db, n, key, make, chunk, use_graphs, nb if kn is None else kn)
+                                     **opts.state(i32, f32, R, B, dist=True))
+        loop = _Loop(self, db, n, opts.key(("sample_search", B, n, temperature, top_k, top_p) + cuts), make, chunk, use_graphs,
+                     opts.mixer)
         st, ws = loop.st, loop.ws
         fill_noise(st)
-        if rows is not None:
-            self._fill_prefix(st, rows)
-        if pen is not None:
-            self._fill_penalties(st, pen, B)
-        if ban is not None:
-            self._fill_ban_phrases(st, ban, B)
-        if tpl is not None:
-            self._fill_template(st, tpl, B)
-        if wst is not None:
-            self._fill_wordsets(st, wst, db)
+        opts.fill(st, db)
         loop.start(lambda lo, hi: self._sample_search_steps(st, ws, B, n, lo, hi, temperature, top_k, top_p, cuts),
                    lambda: self._sample_reset(st), lambda hi: self._none_alive(st, hi)).run()
         return (st["out"].view(B, n, T).long(), st["length"].view(B, n).long(), st["prob"].view(B, n).clone(),
@@ -2525,8 +2481,7 @@ class Searcher:
             labels = torch.where(inside & (labels >= 0), labels, torch.full_like(labels, -1)).to(torch.int32)
         return cand.to(torch.int32), length.to(torch.int32), labels
 
-    @_refuses_knn
-    @_refuses_wordsets
+    @_refuses("knn", "wordsets")
     @torch.no_grad()
     def score(self, db: DeviceBatch, cand, lengths=None, labels=None, chunk: int = 5, use_graphs: bool = True, dist=None,
               neighbour=None, penalties=None, phrases=None, template=None):
@@ -2545,10 +2500,8 @@ class Searcher:
         inputs and outputs are plain rows of them.
         ``dist`` (tests): a [tar_len - 1, B * n, out_len] tensor that receives every step's distribution (eager only)."""
         self._no_ensemble("score")                            # raises before anything is launched
-        self._no_neighbour("score", neighbour)
-        self._no_penalties("score", "its fused step hands no distribution over, and it reports the model's probability", penalties)
-        self._no_phrases("score", phrases)
-        self._no_template("score", template)
+        _refuse_each("score", "its fused step hands no distribution over, and it reports the model's probability",
+                     neighbour=neighbour, penalties=penalties, phrases=phrases, template=template)
         cfg = self.cfg
         B, T = db.B, cfg.tar_len
         cand, length, labels = self.check_candidates(cand, lengths, labels, B)        # raises before anything is launched
@@ -2726,66 +2679,21 @@ class Searcher:
         shape, and the ``done`` latch is read back between chunks (run_model.py:276-279)."""
         B, T = db.B, self.cfg.tar_len
         BR = B * beam
-        con = self._active(constraints)                      # raises before anything is launched
-        merge = bool(merge_copies)
-        if scoring is not None:
-            if not isinstance(scoring, BeamScoring):
-                raise ValueError("scoring: expected decode.BeamScoring or None, got %r" % (scoring,))
-            scoring = scoring.check(beam) if scoring.active() or beam < 2 else None
-        rows = self._prefix_rows(prefix, B, con)             # raises before anything is launched
-        words = self._required_rows(require, B, beam, con, scoring)   # likewise
-        nb = self._neighbour(neighbour, B)                   # likewise
-        kn = self._knn(knn, B, nb)                           # likewise
-        pen = self._penalties(penalties, B)                  # likewise
-        ban, items = self._phrases(phrases, B, con, "beam", rows, beam, words, scoring)     # likewise
-        tpl = self._template(template, B, con, rows, words, items)                          # likewise
-        wst = self._wordsets(wordsets, B, rows, words, items)                                # likewise
-
-        def make(i32, f32):
-            st = dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
-                      **self._edit_state(i32, f32, BR, B, con, merge, rows, dist=True, pen=pen, ban=ban, tpl=tpl,
-                                         **({} if wst is None else {"wst": wst})))
-            if items is not None:
-                st.update({"require-phrases": True}, item_words=i32(B, Phrases.MAX_REQUIRED_WORDS),
-                          item_len=i32(B, Phrases.MAX_ITEMS), n_items=i32(B), met=i32(BR))
-            if words is not None:
-                st.update(required=i32(B, MAX_REQUIRED), n_required=i32(B), met=i32(BR))
-            if scoring is not None:
-                st.update(scoring=scoring, key=f32(BR),
-                          inv_lp=torch.tensor(scoring.inv_lp(T), dtype=torch.float64).to(torch.float32).to(self.model.device_))
-            return st
+        opts = self._options("beam", db, beam=beam, scoring=scoring, constraints=constraints, merge_copies=merge_copies,
+                             prefix=prefix, require=require, neighbour=neighbour, penalties=penalties, phrases=phrases,
+                             template=template, wordsets=wordsets, knn=knn)         # raises before anything is launched
+        make = lambda i32, f32: dict(self._beam_rows(i32, f32, BR), prob=[f32(BR), f32(BR)],
+                                     **opts.state(i32, f32, BR, B, dist=True))
         # (a captured graph bakes the constraint scalars, the merge launch and the scoring scalars: they are part of the key)
-        loop = _Loop(self, db, beam, self._key(("beam", B, beam), merge, con, scoring, rows is not None,
-                                               **({} if words is None else {"require": True}),
-                                               **({} if nb is None else {"neighbour": True}),
-                                               **({} if pen is None else {"penalties": True}),
-                                               **({} if ban is None else {"ban_phrases": True}),
-                                               **({} if items is None else {"require_phrases": True}),
-                                               **({} if tpl is None else {"template": True}),
-                                               **({} if wst is None else {"wordsets": wst.given}),
-                                               **({} if kn is None else {"knn": kn})), make, chunk, use_graphs,
-                     *(() if nb is None and kn is None else (nb if kn is None else kn,)))
+        loop = _Loop(self, db, beam, opts.key(("beam", B, beam)), make, chunk, use_graphs, opts.mixer)
         st, ws = loop.st, loop.ws
-        if rows is not None:
-            self._fill_prefix(st, rows)
-        if words is not None:
-            self._fill_required(st, words)
-        if pen is not None:
-            self._fill_penalties(st, pen, B)
-        if ban is not None:
-            self._fill_ban_phrases(st, ban, B)
-        if items is not None:
-            self._fill_required_phrases(st, items, B)
-        if tpl is not None:
-            self._fill_template(st, tpl, B)
-        if wst is not None:
-            self._fill_wordsets(st, wst, db)
+        opts.fill(st, db)
         loop.start(lambda lo, hi: self._beam_steps(st, ws, B, beam, lo, hi), lambda: self._beam_reset(st, B, beam),
                    lambda hi: bool(st["done"].item())).run()
         res = self._family_result(loop, B, beam, ("prob",))
-        if words is not None or items is not None:
+        if opts.words is not None or opts.items is not None:
             return res + (st["met"].view(B, beam).long(),)
-        return res if scoring is None else res + (st["key"].view(B, beam).clone(),)
+        return res if opts.scoring is None else res + (st["key"].view(B, beam).clone(),)
 
     # ------------------------------------------------------------------ stochastic beam search: n samples without replacement
     def _sbs_reset(self, st, B, n):
@@ -2804,8 +2712,7 @@ class Searcher:
                 _lib.ptr(st["G"][nxt]), _lib.ptr(st["logp"][nxt]), _lib.ptr(st["parent"])), "fira_beam_select_gumbel")
         self._family_steps(st, ws, B, n, lo, hi, select)
 
-    @_refuses_knn
-    @_refuses_wordsets
+    @_refuses("knn", "wordsets")
     @torch.no_grad()
     def sample_distinct(self, db: DeviceBatch, n: int, *, temperature: float = 1.0, seed: int = 0, keys=None,
                         merge_copies: bool = True, constraints: Optional[Constraints] = None, chunk: int = 4,
@@ -2830,12 +2737,9 @@ class Searcher:
         hipGraphs of ``chunk`` steps; the state is keyed ("sbs", B, n, merge, constraints, temperature) -- the temperature
         is baked into the captured launches; the seed and the keys are device values: one capture serves them all."""
         B = db.B
-        self._no_neighbour("sample_distinct", neighbour)     # raises before anything is launched
-        self._no_penalties("sample_distinct", "its hypotheses are an exact sample from the model's distribution", penalties)
-        self._no_phrases("sample_distinct", phrases)
-        self._no_template("sample_distinct", template)
-        con = self._active(constraints)                      # raises before anything is launched
-        merge = bool(merge_copies)
+        _refuse_each("sample_distinct", "its hypotheses are an exact sample from the model's distribution",
+                     neighbour=neighbour, penalties=penalties, phrases=phrases, template=template)        # before any launch
+        opts = self._options("sample_distinct", db, constraints=constraints, merge_copies=merge_copies)
         noise_rows, fill_noise = self._noise(keys, seed, B)   # raises before anything is launched
         temperature = float(temperature)
         # the kernel's own limits, before the encoder pass or any other launch
@@ -2846,10 +2750,11 @@ class Searcher:
         BR = B * n
         make = lambda i32, f32: dict(self._beam_rows(i32, f32, BR), phi=[f32(BR), f32(BR)], G=[f32(BR), f32(BR)],
                                      logp=[f32(BR), f32(BR)], **noise_rows(i32),
-                                     **self._edit_state(i32, f32, BR, B, con, merge, None, dist=True))
-        loop = _Loop(self, db, n, self._sbs_key(B, n, merge, con, temperature), make, chunk, use_graphs)
+                                     **opts.state(i32, f32, BR, B, dist=True))
+        loop = _Loop(self, db, n, self._sbs_key(B, n, opts.merge, opts.con, temperature), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
         fill_noise(st)
+        opts.fill(st, db)
         loop.start(lambda lo, hi: self._sbs_steps(st, ws, B, n, lo, hi, temperature), lambda: self._sbs_reset(st, B, n),
                    lambda hi: bool(st["done"].item())).run()
         return self._family_result(loop, B, n, ("logp", "phi", "G"))
@@ -2897,16 +2802,13 @@ class Searcher:
         alpha = self._check_contrastive(self.members, k, alpha)          # raises before anything is launched
         B, T = db.B, self.cfg.tar_len
         BR = B * k
-        con = self._active(constraints)                      # raises before anything is launched
-        rows = self._prefix_rows(prefix, B, con)             # likewise
+        opts = self._options("contrastive", db, constraints=constraints, merge_copies=True, prefix=prefix)      # likewise
         make = lambda i32, f32: dict(self._beam_rows(i32, f32, BR), p=[f32(BR), f32(BR)], prob=[f32(B), f32(B)],
                                      hist=f32(B, T, 256), hidden=f32(BR, 256), ended=i32(B), pick=i32(B), sim=f32(BR),
-                                     score=f32(BR), **self._edit_state(i32, f32, BR, B, con, True, rows, dist=True))
-        loop = _Loop(self, db, k, self._key(("contrastive", B, k, alpha), True, con, None, rows is not None), make, chunk,
-                     use_graphs)
+                                     score=f32(BR), **opts.state(i32, f32, BR, B, dist=True))
+        loop = _Loop(self, db, k, opts.key(("contrastive", B, k, alpha)), make, chunk, use_graphs)
         st, ws = loop.st, loop.ws
-        if rows is not None:
-            self._fill_prefix(st, rows)
+        opts.fill(st, db)
         return loop.start(lambda lo, hi: self._contrastive_steps(st, ws, B, k, lo, hi, alpha),
                           lambda: self._contrastive_reset(st, B, k), lambda hi: bool(st["done"].item()))
 
@@ -2918,11 +2820,7 @@ class Searcher:
         running = (st["ended"] == 0) & (last > 0)
         return gen.long(), length.long(), torch.where(running, st["prob"][cur] * last, st["prob"][cur])
 
-    @_refuses_knn
-    @_refuses_wordsets
-    @_refuses_template
-    @_refuses_phrases
-    @_refuses_penalties("it already penalises degeneration")
+    @_refuses("knn", "wordsets", "template", "phrases", "penalties", why="it already penalises degeneration")
     @torch.no_grad()
     def contrastive(self, db: DeviceBatch, k: int, alpha: float = 0.6, chunk: int = 4, use_graphs: bool = True,
                     constraints: Optional[Constraints] = None, prefix=None):
@@ -2964,3 +2862,10 @@ class Searcher:
             j = min(range(len(p)), key=lambda q: (not p[q] > 0, -m[q], -p[q], q))
             out.append(g[j][:n[j]])
         return out
+
+
+# ``_refuse`` under one name per option, ``Searcher._no_<option>(what[, why], value)``: the stand-in searchers of the tests bind
+# these names when they are imported.
+for _option in _REFUSAL:
+    setattr(Searcher, "_no_" + _option, staticmethod(
+        lambda what, *why_value, _option=_option: _refuse(what, _option, why_value[-1], *why_value[:-1])))

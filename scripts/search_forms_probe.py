@@ -9,8 +9,14 @@ with all three, ``beam`` 4 under a ``BeamScoring`` (alone and with all three), `
 merge_copies and constraints, a two-member ensemble's ``greedy`` and ``beam`` 3 (plain and with all three) -- each with captured
 graphs (twice: capture, then replay) and eager -- then ``sample``, ``score`` and ``greedy_many`` over three batches with two in
 flight.  Two weight sets: the seeded initialisation (mass spread over the entries, so merge and constraints change the messages;
-short messages) and the same with a sharpened generator (every search runs its tar_len - 1 steps).  Only public methods are
-called, so the file runs unchanged against an older tree.  Float tensors are compared through their bits."""
+short messages) and the same with a sharpened generator (every search runs its tar_len - 1 steps).  Then the later controls
+(``control_forms``): ``greedy``, ``beam`` 3 and ``sample_search`` n = 2 with penalties, banned phrases, a template and word sets
+(allow, boost and ground), each alone and all of them with merge, prefix and constraints; ``beam`` 4 with ``require=`` and with
+required items; ``greedy`` and ``beam`` 3 with a ``Neighbour`` and with a ``KnnMT`` over a token store built from the probe's own
+batches, bare and with merge and constraints; ``greedy_many`` with per-batch word sets and prefixes.  The controls' values are
+derived from the plain greedy messages, so that they bite; the output says how many of these forms differ from their plain
+form.  Only public methods are called, so the file runs unchanged against an older tree.  Float tensors are compared through
+their bits."""
 import argparse
 import itertools
 import os
@@ -41,10 +47,44 @@ def forms(search, ens, db, prefix, con, scoring):
     return out
 
 
+def control_forms(decode, search, db, dbs, prefix, con, knn, w, pair):
+    """(name, plain form it is counted against, call) of the forms with the later controls.  ``w``: a word the plain greedy
+    search writes, in no prefix: the hard controls take it away, the soft ones make it unlikely; ``pair``: two words it writes
+    one after the other, the banned phrase."""
+    V = search.cfg.vocab_size
+    taken = {x for row in prefix for x in row}
+    alone = dict(
+        penalties=decode.Penalties(presence=2.0, frequency=0.5, bias={w: -8.0}),
+        phrases=decode.Phrases(banned=[pair, (20, 21)]),
+        template=decode.Template(word_class={w: 1}, next=[[0, -1]], accept=[0]),
+        wordsets=decode.WordSets(allow=[x for x in range(3, V) if x != w], boost=[30, 31, 32], boost_bias=2.0,
+                                 ground=[x for x in range(4, V) if x % 7 == 0 and x not in taken]))
+    every = dict(merge_copies=True, prefix=prefix, constraints=con, **alone)
+    mc = dict(merge_copies=True, constraints=con)
+    nb = decode.Neighbour(dbs[1], [0.9, 0.5, 0.0, 1.0], lam=1.0)
+    searches = (("greedy", "greedy/plain", lambda g, **kw: search.greedy(db, use_graphs=g, **kw)),
+                ("beam3", "beam3/plain", lambda g, **kw: search.beam(db, 3, use_graphs=g, **kw)),
+                ("sample_search2", "sample_search2/plain",
+                 lambda g, **kw: search.sample_search(db, 2, temperature=0.9, top_k=50, seed=11, use_graphs=g, **kw)))
+    out = [("sample_search2/plain", None, lambda g: searches[2][2](g)),
+           ("beam4/plain", None, lambda g: search.beam(db, 4, use_graphs=g))]
+    for tag, plain, call in searches:
+        for name, kw in [(k, {k: v}) for k, v in alone.items()] + [("every", every)]:
+            out.append(("%s/%s" % (tag, name), plain, lambda g, call=call, kw=kw: call(g, **kw)))
+    out.append(("beam4/require", "beam4/plain", lambda g: search.beam(db, 4, use_graphs=g, require=[[20, 21], [], [22], []])))
+    out.append(("beam4/require-phrases", "beam4/plain", lambda g: search.beam(
+        db, 4, use_graphs=g, phrases=decode.Phrases(required=[[(20, 21)], [], [(22,)], []]))))
+    for tag, plain, call in searches[:2]:
+        for name, kw in (("neighbour", dict(neighbour=nb)), ("knn", dict(knn=knn))):
+            out.append(("%s/%s" % (tag, name), plain, lambda g, call=call, kw=kw: call(g, **kw)))
+            out.append(("%s/%s-mc" % (tag, name), plain, lambda g, call=call, kw=kw: call(g, **kw, **mc)))
+    return out, alone["wordsets"]
+
+
 def run(a):
     sys.path.insert(0, os.path.abspath(a.tree))
     import torch
-    from fira_icse_amd import data, decode, synth
+    from fira_icse_amd import data, decode, retrieve, synth
     from fira_icse_amd.config import EOS, START, UNK, FiraConfig
     from fira_icse_amd.decode import BeamScoring, Constraints, Searcher
     from fira_icse_amd.model import DeviceBatch, TransModel
@@ -57,7 +97,7 @@ def run(a):
     prefix = [[5, 6], [], [7], [9, 11, 5]]
     cand = torch.tensor([[[START, 5 + b, 9, 11, EOS, 0], [START, 7, 6 + b, EOS, 0, 0]] for b in range(B)])
     cpu = lambda ts: [t.detach().cpu().clone() for t in ts]
-    res = {}
+    res, differ, counted = {}, [], 0
     for weights in ("init", "sharp"):
         models = []
         for seed in (0, 1):
@@ -81,10 +121,35 @@ def run(a):
             many = search.greedy_many(dbs, in_flight=2, **kw)
             torch.cuda.synchronize()
             res["%s/greedy_many/%s" % (weights, tag)] = cpu(t for r in many for t in r)
-        print("%s: %d forms so far" % (weights, len(res)), flush=True)
+        # the later controls, on values that bite: w is the first word plain greedy writes that no prefix holds
+        taken = {x for row in prefix for x in row}
+        msgs = res["%s/greedy/plain/eager" % weights][0].tolist()
+        w = next((x for row in msgs for x in row[1:] if x > UNK and x not in taken), 12)
+        pair = next(((x, y) for row in msgs for x, y in zip(row[1:], row[2:]) if x > UNK and y > UNK and x not in taken), (w, w))
+        store_ = retrieve.TokenStore.build(Searcher(models[0]), [(list(range(k * B, (k + 1) * B)), d) for k, d in enumerate(dbs)])
+        knn = decode.KnnMT(store_, k=4, lam=0.5, temperature=10.0)
+        more, wst = control_forms(decode, search, db, dbs, prefix, con, knn, w, pair)
+        for name, plain, call in more:
+            for mode, g in (("capture", True), ("replay", True), ("eager", False)):
+                res["%s/%s/%s" % (weights, name, mode)] = cpu(call(g))
+            if plain is not None:
+                counted += 1
+                one, two = res["%s/%s/eager" % (weights, name)], res["%s/%s/eager" % (weights, plain)]
+                if not torch.equal(one[0], two[0]):
+                    differ.append("%s/%s" % (weights, name))
+        many = search.greedy_many(dbs, in_flight=2, wordsets=[wst, None, decode.WordSets(deny=[w])],
+                                  prefix=[prefix, None, prefix])
+        torch.cuda.synchronize()
+        name = "%s/greedy_many/wordsets-prefix" % weights
+        res[name] = cpu(t for r in many for t in r)
+        counted += 1
+        if not all(torch.equal(x, y) for x, y in zip(res[name], res["%s/greedy_many/plain" % weights])):
+            differ.append(name)
+        print("%s: %d forms so far (w = %d, pair = %r)" % (weights, len(res), w, pair), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     torch.save(res, a.out)
     print("wrote %d forms, %d tensors to %s" % (len(res), sum(len(v) for v in res.values()), a.out))
+    print("%d of the %d forms with the later controls differ from their plain form" % (len(differ), counted))
 
 
 def same(x, y):

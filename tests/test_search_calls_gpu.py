@@ -1,7 +1,10 @@
 """The library calls of ONE search step, in order, with which of their pointer arguments are NULL: ``_greedy_steps``, ``_beam_steps``
 and ``_sbs_steps`` at step 1 (so ``parent`` is in play) for every combination of merge_copies / prefix / constraints, a
 ``BeamScoring`` and a two-member ensemble.  The expected sequences are written out below: the edit order is merge, prefix,
-constraints; in greedy exactly the last edit call carries best_id / best_p, in the beam family none does."""
+constraints; in greedy exactly the last edit call carries best_id / best_p, in the beam family none does.  Below them the full
+chain -- merge, prefix, constraints, banned phrases, template, word sets, penalties -- in ``greedy``, ``beam`` and
+``sample_search``, each of the four later links alone, and ``greedy`` with a neighbour and with ``knn=``, whose mix carries the
+pair only where the chain is empty."""
 import pytest
 import torch
 
@@ -9,7 +12,8 @@ import util
 from search_kit import CountingLib, golden_search
 from fira_icse_amd import _lib
 from fira_icse_amd.config import UNK
-from fira_icse_amd.decode import BeamScoring, Constraints, Searcher
+from fira_icse_amd import retrieve
+from fira_icse_amd.decode import BeamScoring, Constraints, KnnMT, Neighbour, Penalties, Phrases, Searcher, Template, WordSets
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +28,14 @@ NULLABLE = {"fira_decode_step_ex": {9: "parent", 10: "dist", 11: "best_id", 12: 
             "fira_mix_dist": {7: "best_id", 8: "best_p"},
             "fira_merge_dist": {7: "best_id", 8: "best_p"},
             "fira_force_dist": {11: "best_id", 12: "best_p"},
-            "fira_constrain_dist": {13: "best_id", 14: "best_p"}}
+            "fira_constrain_dist": {13: "best_id", 14: "best_p"},
+            "fira_ban_phrases_dist": {12: "best_id", 13: "best_p"},
+            "fira_template_dist": {13: "best_id", 14: "best_p"},
+            "fira_wordset_dist": {8: "allow", 9: "deny", 10: "boost", 11: "ground", 12: "slot_valid", 13: "boost_factor",
+                                  15: "best_id", 16: "best_p"},
+            "fira_penalise_dist": {13: "best_id", 14: "best_p"},
+            "fira_mix_neighbour": {7: "best_id", 8: "best_p"},
+            "fira_mix_knn": {10: "best_id", 11: "best_p"}}
 
 
 class RecordingLib(CountingLib):
@@ -64,7 +75,9 @@ def setup():
     second = TransModel(g.cfg, init=False)
     second.load_state_dict(util.perturb_state_dict(reference_init_state_dict(g.cfg), seed=2))
     second.eval()
-    return dict(db=g.db, single=Searcher(g.model), ens=Searcher(g.model, members=(second,)))
+    store = retrieve.TokenStore.build(Searcher(g.model), [(list(g.ids), g.db)])
+    return dict(db=g.db, single=Searcher(g.model), ens=Searcher(g.model, members=(second,)), knn=KnnMT(store, k=4),
+                neighbour=Neighbour(g.db, [0.5, 1.0, 0.25]))
 
 
 def options(flags):
@@ -180,3 +193,114 @@ def test_ensemble_steps(setup, monkeypatch):
         got = beam_step(monkeypatch, ens, db, 3, flags)
         print("beam3", flags or "plain", got)
         assert got == want
+
+
+# ------------------------------------------------------------------------------------------------ the full chain
+BAN = Phrases(banned=[(8, 9)])                        # not in PREFIX
+TEMPLATE = Template(word_class={12: 1}, next=[[0, -1]], accept=[0])       # one state, word 12 never: PREFIX is a path of it
+DENY = WordSets(deny=[13])                            # no word of PREFIX
+ALLOW = WordSets(allow=range(UNK, 200))               # every word of PREFIX
+PENALTIES = Penalties(presence=0.5, frequency=0.25, bias={10: 1.0})
+LINKS = dict(phrases=BAN, template=TEMPLATE, wordsets=DENY, penalties=PENALTIES)
+ALL = dict(merge_copies=True, prefix=PREFIX, constraints=CON, **LINKS)
+# the key components of the options above, as ``_key`` orders them
+ALL_KEY = ("merge", "prefix", "penalties", "ban-phrases", "template", ("wordsets", ("deny",)), CON)
+LINK_KEY = dict(phrases=("ban-phrases",), template=("template",), wordsets=(("wordsets", ("deny",)),), penalties=("penalties",))
+
+ONLY_DENY = ("allow", "boost", "ground", "slot_valid", "boost_factor")
+ONLY_ALLOW = ("deny", "boost", "ground", "slot_valid", "boost_factor")
+BAN_PHRASES, BAN_PHRASES_BEST = ("fira_ban_phrases_dist", NO_BEST), ("fira_ban_phrases_dist", ())
+TEMPLATE_DIST, TEMPLATE_BEST = ("fira_template_dist", NO_BEST), ("fira_template_dist", ())
+WORDSET_DENY, WORDSET_DENY_BEST = ("fira_wordset_dist", ONLY_DENY + NO_BEST), ("fira_wordset_dist", ONLY_DENY)
+WORDSET_ALLOW_BEST = ("fira_wordset_dist", ONLY_ALLOW)
+PENALISE, PENALISE_BEST = ("fira_penalise_dist", NO_BEST), ("fira_penalise_dist", ())
+MIX_NEIGHBOUR, MIX_NEIGHBOUR_BEST = ("fira_mix_neighbour", NO_BEST), ("fira_mix_neighbour", ())
+MIX_KNN, MIX_KNN_BEST = ("fira_mix_knn", NO_BEST), ("fira_mix_knn", ())
+HIDDEN, KNN_SEARCH = ("fira_decode_hidden", ()), ("fira_knn_search", ())
+SAMPLE_DIST, SAMPLE_ADVANCE = ("fira_sample_dist", ()), ("fira_sample_advance", ())
+
+GREEDY_ALL = [G_STEP_DIST, MERGE, FORCE, CONSTRAIN, BAN_PHRASES, TEMPLATE_DIST, WORDSET_DENY, PENALISE_BEST, ADVANCE]
+GREEDY_LINK = {"phrases": [G_STEP_DIST, BAN_PHRASES_BEST, ADVANCE],
+               "template": [G_STEP_DIST, TEMPLATE_BEST, ADVANCE],
+               "wordsets": [G_STEP_DIST, WORDSET_DENY_BEST, ADVANCE],
+               "penalties": [G_STEP_DIST, PENALISE_BEST, ADVANCE]}
+GREEDY_ALLOW = [G_STEP_DIST, WORDSET_ALLOW_BEST, ADVANCE]
+BEAM_ALL = [PREPARE, B_STEP, MERGE, FORCE, CONSTRAIN, BAN_PHRASES, TEMPLATE_DIST, WORDSET_DENY, PENALISE, SELECT]
+SAMPLE_SEARCH_ALL = [G_STEP_DIST, MERGE, FORCE, CONSTRAIN, BAN_PHRASES, TEMPLATE_DIST, WORDSET_DENY, PENALISE, SAMPLE_DIST,
+                     SAMPLE_ADVANCE]
+# a neighbour: the input's step, the neighbour's, the neighbour's row folded into words, the mix; knn=: the step, the hidden rows,
+# the look-up, the mix.  The mix carries the arg-max only where no edit follows.
+NEIGHBOUR_GREEDY = {"": [G_STEP_DIST, G_STEP_DIST, MERGE, MIX_NEIGHBOUR_BEST, ADVANCE],
+                    "c": [G_STEP_DIST, G_STEP_DIST, MERGE, MIX_NEIGHBOUR, CONSTRAIN_BEST, ADVANCE]}
+KNN_GREEDY = {"": [G_STEP_DIST, HIDDEN, KNN_SEARCH, MIX_KNN_BEST, ADVANCE],
+              "c": [G_STEP_DIST, HIDDEN, KNN_SEARCH, MIX_KNN, CONSTRAIN_BEST, ADVANCE]}
+
+
+def greedy_step_of(monkeypatch, search, db, key, ws_key=(B, 1), **kw):
+    """``greedy_step`` for any options: ``key`` is the state's key after ("greedy", B), ``ws_key`` what ``_begin`` returned."""
+    search.greedy(db, use_graphs=False, **kw)
+    st, ws = search._ws[("greedy", B) + key], search._ws[ws_key]
+    search._greedy_reset(st)
+    search._greedy_steps(st, ws, B, 0, 1)
+    return one_step(monkeypatch, lambda: search._greedy_steps(st, ws, B, 1, 2))
+
+
+def test_greedy_full_chain_step(setup, monkeypatch):
+    got = greedy_step_of(monkeypatch, setup["single"], setup["db"], ALL_KEY, **ALL)
+    print(got)
+    assert got == GREEDY_ALL
+
+
+@pytest.mark.parametrize("link", list(GREEDY_LINK))
+def test_greedy_one_link_step(setup, monkeypatch, link):
+    got = greedy_step_of(monkeypatch, setup["single"], setup["db"], LINK_KEY[link], **{link: LINKS[link]})
+    print(link, got)
+    assert got == GREEDY_LINK[link]
+
+
+def test_greedy_allow_alone_gets_null_for_the_other_sets(setup, monkeypatch):
+    got = greedy_step_of(monkeypatch, setup["single"], setup["db"], (("wordsets", ("allow",)),), wordsets=ALLOW)
+    print(got)
+    assert got == GREEDY_ALLOW
+
+
+def test_beam_full_chain_step(setup, monkeypatch):
+    search, db, beam = setup["single"], setup["db"], 3
+    search.beam(db, beam, use_graphs=False, **ALL)
+    st, ws = search._ws[("beam", B, beam) + ALL_KEY], search._ws[(B, beam)]
+    search._beam_reset(st, B, beam)
+    search._beam_steps(st, ws, B, beam, 0, 1)
+    got = one_step(monkeypatch, lambda: search._beam_steps(st, ws, B, beam, 1, 2))
+    print(got)
+    assert got == BEAM_ALL
+
+
+def test_sample_search_full_chain_step(setup, monkeypatch):
+    search, db, n = setup["single"], setup["db"], 2
+    search.sample_search(db, n, seed=3, use_graphs=False, **ALL)
+    st, ws = search._ws[("sample_search", B, n, 1.0, 0, 1.0) + Searcher.CUTS_OFF + ALL_KEY], search._ws[(B, n)]
+    steps = lambda lo, hi: search._sample_search_steps(st, ws, B, n, lo, hi, 1.0, 0, 1.0, Searcher.CUTS_OFF)
+    search._sample_reset(st)
+    steps(0, 1)
+    got = one_step(monkeypatch, lambda: steps(1, 2))
+    print(got)
+    assert got == SAMPLE_SEARCH_ALL
+
+
+@pytest.mark.parametrize("flags", list(NEIGHBOUR_GREEDY), ids=[f or "bare" for f in NEIGHBOUR_GREEDY])
+def test_greedy_neighbour_step(setup, monkeypatch, flags):
+    key = ("neighbour",) + ((CON,) if flags else ())
+    got = greedy_step_of(monkeypatch, setup["single"], setup["db"], key, ("neighbours", B, 1), neighbour=setup["neighbour"],
+                         constraints=CON if flags else None)
+    print(flags or "bare", got)
+    assert got == NEIGHBOUR_GREEDY[flags]
+
+
+@pytest.mark.parametrize("flags", list(KNN_GREEDY), ids=[f or "bare" for f in KNN_GREEDY])
+def test_greedy_knn_step(setup, monkeypatch, flags):
+    kn = setup["knn"]
+    key = (("knn", kn.k, id(kn.store)),) + ((CON,) if flags else ())
+    got = greedy_step_of(monkeypatch, setup["single"], setup["db"], key, ("knn", B, 1, kn.k, id(kn.store)), knn=kn,
+                         constraints=CON if flags else None)
+    print(flags or "bare", got)
+    assert got == KNN_GREEDY[flags]
